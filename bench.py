@@ -21,7 +21,13 @@ Configs 1 and 2 run one raster per rank (weak scaling: tiles / bands are indepen
 `end_to_end`: the same blocks / tiles through RasterFuse.process from page-locked HOST rasters (H2D || kernel || D2H on
 the context's streams) -- the PCIe-inclusive rate, never the headline.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (from the timed launches' own HIP events).
+A plain run only sets up, warms up, times the steps (and writes --dump-outputs); `--full` adds everything else the benchmark
+measures or checks: the parity spot checks against the oracle, the measured copy bandwidth, package power, `cpu_baseline`, the
+NaN / in-painting variants and BASELINE.json's other configs (config 2), the single-GPU projection and `end_to_end` (configs 3 / 4).
+`--dump-outputs DIR` writes a fixed, seeded sample of rows of what the last timed step computed (DIR/corrected.npy, with
+--params also gain / offset / r2; float32, the sampled rows one after another, at most 48 MB in all): with the same arguments
+the inputs are the same from run to run, so two builds can be compared output for output.
 No PyTorch anywhere: the ranks of a launch meet over loopback TCP (homonim_amd/dist.py); RCCL is the library's own communicator.
 """
 import argparse
@@ -80,6 +86,11 @@ def parse_args():
                         'equals the single-rank result iff the totals do (always on for N > 1)')
     p.add_argument('--no-projection', action='store_true',
                    help='configs 3 / 4 at one rank: skip the single-GPU projection (every rank\'s shard of an N = 2 / 4 / 8 launch timed alone)')
+    p.add_argument('--full', action='store_true',
+                   help='also measure and check everything beyond the headline figure (parity spot checks, copy bandwidth, power, CPU '
+                        'baseline, NaN / in-painting variants, other configs, projection, end-to-end); the --no-* options switch parts off')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='after the timed steps write a fixed, seeded sample of rows of the last step\'s outputs as DIR/<name>.npy (float32)')
     args = p.parse_args()
     preset = CONFIGS[args.config]
     for k, v in preset.items():
@@ -91,6 +102,10 @@ def parse_args():
         args.steps = {1: 100, 2: 50, 3: 10, 4: 5}[args.config]
     if args.warmup is None:
         args.warmup = {1: 5, 2: 5, 3: 2, 4: 1}[args.config]
+    if not args.full:   # a plain run: set up, warm up, time the steps, dump, print the line
+        args.no_cpu_baseline = args.no_parity = args.no_end_to_end = args.no_nan_variant = True
+        args.no_other_configs = args.no_power_probe = args.no_projection = True
+    args.copy_probe = args.full
     args.power_probe = not args.no_power_probe and args.config in (1, 2)
     if args.as_rank is not None:
         try:
@@ -299,6 +314,47 @@ def windows_checksum(ctx, windows):
     return total, px
 
 
+DUMP_BYTES = 48 << 20   # --dump-outputs: all sampled rows together
+DUMP_SEED = 20240601
+
+
+def dump_sample_rows(windows, n_arrays, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """ The rows --dump-outputs takes: [(window index, row)] drawn with a fixed seed, so that `n_arrays` arrays of these windows
+    ([(device pointer of the window's first pixel, row stride, height, width)]) fit `budget` bytes together.  Every window gives the
+    same number of rows (all of a window smaller than that); when one row of every window does not fit, a seeded subset of them
+    gives one row each. """
+    rng = np.random.default_rng(seed)
+    per_array = budget // max(1, n_arrays)
+    row_bytes = sum(4 * w for _, _, _, w in windows)
+    chosen = range(len(windows))
+    if row_bytes > per_array:
+        widest = max(4 * w for _, _, _, w in windows)
+        chosen = sorted(rng.choice(len(windows), max(1, per_array // widest), replace=False))
+        row_bytes = sum(4 * windows[i][3] for i in chosen)
+    n = max(1, per_array // max(1, row_bytes))
+    rows = []
+    for i in chosen:
+        h = windows[i][2]
+        rows += [(int(i), int(y)) for y in (range(h) if n >= h else sorted(rng.choice(h, n, replace=False)))]
+    return rows
+
+
+def dump_outputs(ctx, out_dir, arrays, budget=DUMP_BYTES):
+    """ --dump-outputs: `arrays` = {name: windows} (the same window shapes for every name) -> out_dir/<name>.npy, float32: the sampled
+    rows of the windows one after another, downloaded from device memory as the last timed step left it. """
+    os.makedirs(out_dir, exist_ok=True)
+    first = next(iter(arrays.values()))
+    rows = dump_sample_rows(first, len(arrays), budget)
+    for name, windows in arrays.items():
+        out = np.empty(sum(windows[i][3] for i, _ in rows), np.float32)
+        at = 0
+        for i, y in rows:
+            ptr, stride, _, w = windows[i]
+            ctx.d2h(out[at:at + w], ptr + 4 * y * stride)
+            at += w
+        np.save(os.path.join(out_dir, f'{name}.npy'), out)
+
+
 def merge_parity(records):
     """ several spot-check windows -> one record (`passed` = all of them) that keeps the individual windows """
     records = [r for r in records if r is not None]
@@ -489,7 +545,9 @@ def run_resident(args, ctx, dist, rank, world):
         return n_fail
 
     # what this box's HBM gives the same byte mix as a flat stream (before anything is timed; it scribbles on corr)
-    copy_med, copy_best = probe_copy(ctx, bufs['src'], bufs['ref'], bufs['corr'], plane_bytes)
+    copy_med = copy_best = None
+    if args.copy_probe:
+        copy_med, copy_best = probe_copy(ctx, bufs['src'], bufs['ref'], bufs['corr'], plane_bytes)
 
     run(args.warmup)
     ctx.stream_sync(0)
@@ -508,6 +566,10 @@ def run_resident(args, ctx, dist, rank, world):
     n_fail //= max(1, args.steps)
     px_bands = H * W * B
     avg_ms = float(np.mean(launch_ms))
+    if rank == 0 and args.dump_outputs:
+        out_names = (('corrected', 'corr'),) + ((('gain', 'gain'), ('offset', 'offset'), ('r2', 'r2')) if args.params else ())
+        dump_outputs(ctx, args.dump_outputs, {name: [(bufs[buf] + 4 * b * band_stride, stride, H, W) for b in range(B)]
+                                              for name, buf in out_names})
 
     parity = None
     if rank == 0 and not args.no_parity:
@@ -598,7 +660,9 @@ def run_blocks(args, ctx, dist, rank, world):
     bufs['norm'] = ctx.dev_alloc(16 * B * max(1, len(mine)))
     ctx.synth_fill_dev(bufs['src'], bufs['ref'], B, H, W, stride, band_stride, seed=1234, nodata_variant=args.nodata, stream=0)
     ctx.stream_sync(0)
-    copy_med, copy_best = probe_copy(ctx, bufs['src'], bufs['ref'], bufs['corr'], 4 * band_stride * B)
+    copy_med = copy_best = None
+    if args.copy_probe:
+        copy_med, copy_best = probe_copy(ctx, bufs['src'], bufs['ref'], bufs['corr'], 4 * band_stride * B)
     n_streams = ctx.n_streams
 
     bpj = B   # the bands of a block position share a launch (fewer bands per job: no gain, also not for a rank's small shard -- profiles/r06_c3_rank.txt)
@@ -664,6 +728,15 @@ def run_blocks(args, ctx, dist, rank, world):
     elapsed = dist.max_over_ranks(time.perf_counter() - t0)
     my_px = B * sum(bp.src_out_block.height * bp.src_out_block.width for bp in mine)
 
+    def out_windows():   # the out-blocks this rank wrote, every band
+        wins = []
+        for bp in mine:
+            wo = bp.src_out_block
+            wins += [(bufs['corr'] + 4 * (b * band_stride + wo.row_off * stride + wo.col_off), stride, wo.height, wo.width) for b in range(B)]
+        return wins
+    if rank == 0 and args.dump_outputs and mine:
+        dump_outputs(ctx, args.dump_outputs, {'corrected': out_windows()})
+
     parity = None
     if rank == 0 and not args.no_parity and jobs:
         # the LAST block position of the rank (a batched launch that lost its job table would never get there)
@@ -677,12 +750,8 @@ def run_blocks(args, ctx, dist, rank, world):
                             256, 1000, nm[0], 0)
 
     checksum = None
-    if getattr(args, 'checksum', False) or world > 1:   # the out-blocks this rank wrote, every band
-        wins = []
-        for bp in mine:
-            wo = bp.src_out_block
-            wins += [(bufs['corr'] + 4 * (b * band_stride + wo.row_off * stride + wo.col_off), stride, wo.height, wo.width) for b in range(B)]
-        checksum = windows_checksum(ctx, wins)
+    if getattr(args, 'checksum', False) or world > 1:
+        checksum = windows_checksum(ctx, out_windows())
 
     projection = None
     if world == 1 and not args.no_projection and args.as_rank is None:
@@ -803,7 +872,7 @@ def run_tiles(args, ctx, dist, rank, world):
         tiles.append((d, job, ctx.pinned_empty((B,), np.uint64), ctx.event()))
     ctx.stream_sync(0)
     copy_med = copy_best = None
-    if tiles:
+    if tiles and args.copy_probe:
         d0 = tiles[0][0]
         copy_med, copy_best = probe_copy(ctx, d0['src'], d0['ref'], d0['corr'], tile_bytes)
 
@@ -876,6 +945,9 @@ def run_tiles(args, ctx, dist, rank, world):
     ctx.sync()
     dist.barrier()
     elapsed = dist.max_over_ranks(time.perf_counter() - t0)
+    if rank == 0 and args.dump_outputs and tiles:   # this rank's tiles, every band
+        dump_outputs(ctx, args.dump_outputs, {'corrected': [(d['corr'] + 4 * b * band_stride, stride, n, n)
+                                                            for d, job, counts, ev in tiles for b in range(B)]})
 
     parity = None
     if rank == 0 and not args.no_parity and tiles:
@@ -1150,7 +1222,7 @@ def main():
 
         def variant(nd, workload):
             a2 = copy.copy(args)
-            a2.nodata, a2.steps, a2.warmup, a2.power_probe = nd, min(args.steps, 20), 3, False
+            a2.nodata, a2.steps, a2.warmup, a2.power_probe, a2.dump_outputs = nd, min(args.steps, 20), 3, False, None
             r2_ = run_resident(a2, ctx, dist, rank, world)
             rl2 = r2_['roofline']
             return {
@@ -1176,7 +1248,7 @@ def main():
         inpaint_variants = {}
         for nd, steps in ((3, 6), (4, 4)):
             a4 = copy.copy(args)
-            a4.nodata, a4.steps, a4.warmup, a4.power_probe = nd, steps, 2, False
+            a4.nodata, a4.steps, a4.warmup, a4.power_probe, a4.dump_outputs = nd, steps, 2, False, None
             r4 = run_resident(a4, ctx, dist, rank, world)
             inpaint_variants['--nodata %d' % nd] = {
                 'workload': 'the same rasters with a noisy reference: %s of the pixels fail the r2 mask and are in-painted' % ('35 %' if nd == 3 else '94 %'),
@@ -1199,6 +1271,7 @@ def main():
                 setattr(a3, key, CONFIGS[cfg].get(key))
             a3.batches = CONFIGS[cfg].get('batches', 0)
             a3.steps, a3.warmup, a3.no_end_to_end, a3.no_thresh, a3.power_probe, a3.seg_rows = steps, warm, True, False, False, 0
+            a3.dump_outputs = None
             if cfg == 4:   # the pinned-host streaming pipeline (H2D || kernel || D2H through RasterFuse), driver-timed: 8 distinct host tiles
                 a3.no_end_to_end, a3.e2e_distinct = False, 8
             c3 = ctx

@@ -327,6 +327,50 @@ def test_projection_arithmetic_and_the_as_rank_argument(monkeypatch):
     assert bench.SoloDist.max_over_ranks(3.5) == 3.5 and bench.SoloDist.backend() is None
 
 
+def test_bench_plain_and_full_runs_and_the_output_dump(monkeypatch, tmp_path):
+    """ A plain bench.py run does only what its headline needs; `--full` turns every extra measurement and check back on.
+    `--dump-outputs` takes a fixed, seeded sample of rows within its byte budget and writes exactly those rows. """
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(REPO, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    extras = ('no_cpu_baseline', 'no_parity', 'no_end_to_end', 'no_nan_variant', 'no_other_configs', 'no_power_probe', 'no_projection')
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.full, a.copy_probe, a.power_probe, a.dump_outputs) == (7, 2, False, False, False, None)
+    assert all(getattr(a, e) for e in extras)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-cpu-baseline', '--dump-outputs', 'out'])
+    a = bench.parse_args()
+    assert a.full and a.copy_probe and a.power_probe and a.dump_outputs == 'out' and a.no_cpu_baseline
+    assert not any(getattr(a, e) for e in extras if e != 'no_cpu_baseline')
+
+    # the rows: the same on every call, within the budget, every row at most once
+    for wins, n_arrays in (([(0, 16448, 16384, 16384)] * 4, 1), ([(0, 16448, 16384, 16384)] * 4, 4), ([(0, 4096, 4096, 4096)] * 256, 1),
+                           ([(0, 4096, 4096, 4096)] * 5000, 2), ([(0, 64, 10, 64)] * 3, 1)):
+        rows = bench.dump_sample_rows(wins, n_arrays)
+        assert rows == bench.dump_sample_rows(wins, n_arrays) and len(set(rows)) == len(rows)
+        assert 0 < n_arrays * sum(4 * wins[i][3] for i, _ in rows) <= bench.DUMP_BYTES
+        assert all(0 <= y < wins[i][2] for i, y in rows)
+    assert len(bench.dump_sample_rows([(0, 64, 10, 64)] * 3, 1)) == 30   # small windows go whole
+
+    # the file: the sampled rows of device memory one after another (a host array stands in for the device here)
+    mem = np.random.default_rng(5).standard_normal(2 * 300 * 520).astype(np.float32)
+
+    class Ctx:
+        @staticmethod
+        def d2h(arr, ptr):
+            arr[:] = mem[ptr // 4:ptr // 4 + arr.size]
+    wins = {'corrected': [(4 * b * 300 * 520, 520, 300, 500) for b in range(2)],
+            'gain': [(4 * (b * 300 * 520 + 8), 520, 300, 500) for b in range(2)]}
+    bench.dump_outputs(Ctx, str(tmp_path), wins, budget=100 * 4 * 500)
+    rows = bench.dump_sample_rows(wins['corrected'], 2, 100 * 4 * 500)
+    assert len(rows) == 50
+    for name, skip in (('corrected', 0), ('gain', 8)):
+        got = np.load(tmp_path / f'{name}.npy')
+        exp = np.concatenate([mem.reshape(2, 300, 520)[i, y, skip:skip + 500] for i, y in rows])
+        assert got.dtype == np.float32 and np.array_equal(got, exp)
+
+
 _WORKER_NOID = r'''
 import os, sys, time
 sys.path.insert(0, {repo!r})

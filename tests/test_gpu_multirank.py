@@ -81,7 +81,7 @@ def test_bench_joins_an_rccl_group_of_one():
     env.pop('HOMONIM_AMD_DIST_BACKEND', None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(29300 + os.getpid() % 200), os.path.join(REPO, 'bench.py'), '--gpus', '1', '--config', '1',
-           '--steps', '3', '--warmup', '1', '--no-cpu-baseline']
+           '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline']
     run = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
     line = json.loads(run.stdout.strip().splitlines()[-1])
@@ -99,7 +99,7 @@ def test_bench_with_two_ranks(config):
     env = dict(os.environ, HOMONIM_AMD_DIST_BACKEND='host', MASTER_ADDR='127.0.0.1', PYTHONPATH=REPO)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(29700 + (os.getpid() + config) % 200), os.path.join(REPO, 'bench.py'), '--gpus', '2',
-           '--config', str(config), '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-end-to-end']
+           '--config', str(config), '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-end-to-end']
     if config == 3:
         cmd += ['--size', '8192', '--bands', '2']
     run = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -109,6 +109,33 @@ def test_bench_with_two_ranks(config):
     line = json.loads(lines[0])
     assert line['n_gpus'] == 2 and line['value'] > 0 and line['parity_spot_check']['passed']
     assert line['scaling'] == ('weak' if config == 1 else 'strong') and line['dist_backend'] == 'host'
+
+
+def test_bench_plain_run_dumps_the_same_outputs_every_time(tmp_path):
+    """ A plain `bench.py` run times exactly --steps steps and adds nothing after them (no parity check, no other configuration);
+    `--dump-outputs` writes the seeded sample of what the last step computed, and with the same arguments the inputs -- and so the
+    arrays -- are the same from run to run. """
+    import json
+    env = dict(os.environ, PYTHONPATH=REPO)
+    for key in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR'):
+        env.pop(key, None)
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f'run{i}'
+        cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--size', '2048', '--params', '--steps', '3', '--warmup', '1',
+               '--dump-outputs', str(out)]
+        run = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+        assert run.returncode == 0, run.stderr[-3000:]
+        line = json.loads([ln for ln in run.stdout.strip().splitlines() if ln.startswith('{')][-1])
+        assert line['steps'] == 3 and line['warmup'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0
+        assert line['parity_spot_check'] is None and line['cpu_baseline'] is None and 'other_configs' not in line
+        names = sorted(p.name for p in out.iterdir())
+        assert names == ['corrected.npy', 'gain.npy', 'offset.npy', 'r2.npy']
+        arrays = {n: np.load(out / n) for n in names}
+        assert all(a.dtype == np.float32 and a.size == arrays['corrected.npy'].size for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20 and np.isfinite(arrays['corrected.npy']).mean() > 0.99
+        dumps.append(arrays)
+    assert all(_same(dumps[0][n], dumps[1][n]) for n in dumps[0])
 
 
 def test_bench_refuses_a_rank_count_that_disagrees_with_the_launch():
@@ -127,7 +154,7 @@ def test_bench_launches_its_own_ranks():
     for key in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR'):
         env.pop(key, None)
     cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--config', '1', '--steps', '3', '--warmup', '1',
-           '--no-cpu-baseline']
+           '--full', '--no-cpu-baseline']
     run = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.strip().splitlines() if ln.startswith('{')]
@@ -148,8 +175,8 @@ def test_bench_as_rank_and_the_single_gpu_projection(config):
     for key in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR'):
         env.pop(key, None)
     small = ['--size', '8192', '--bands', '2'] if config == 3 else ['--size', '1024', '--tiles', '16']
-    base = [sys.executable, os.path.join(REPO, 'bench.py'), '--config', str(config), '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
-            '--no-end-to-end'] + small
+    base = [sys.executable, os.path.join(REPO, 'bench.py'), '--config', str(config), '--steps', '2', '--warmup', '1', '--full',
+            '--no-cpu-baseline', '--no-end-to-end'] + small
     run = subprocess.run(base, env=env, capture_output=True, text=True, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
     line = json.loads([ln for ln in run.stdout.strip().splitlines() if ln.startswith('{')][-1])
@@ -210,7 +237,7 @@ def _bench(n, launcher, args, extra_env=None, timeout=900):
     env = dict(os.environ, HOMONIM_AMD_DIST_BACKEND='host', PYTHONPATH=REPO, **(extra_env or {}))
     for key in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR', 'LOCAL_WORLD_SIZE', 'GROUP_WORLD_SIZE'):
         env.pop(key, None)
-    common = ['--gpus', str(n), '--no-cpu-baseline', '--no-end-to-end', '--no-nan-variant', '--no-other-configs', '--no-power-probe',
+    common = ['--gpus', str(n), '--full', '--no-cpu-baseline', '--no-end-to-end', '--no-nan-variant', '--no-other-configs', '--no-power-probe',
               '--no-projection', '--checksum'] + args
     if launcher == 'torchrun' and n > 1:   # the driver's launch
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n), '--master-addr', '127.0.0.1',

@@ -1,5 +1,5 @@
 #!/bin/bash
-run() { env $1 python3 bench.py --config 4 --steps 5 --warmup 1 --no-cpu-baseline --no-end-to-end $2 2>/dev/null | tail -1 | python3 -c "
+run() { env $1 python3 bench.py --full --config 4 --steps 5 --warmup 1 --no-cpu-baseline --no-end-to-end $2 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d['roofline']
 print('%-28s %-24s %8.3f ms/step frac %.4f parity=%s' % (sys.argv[1], sys.argv[2], d['ms_per_step'], r['frac'], d['parity_spot_check']['passed']))" "$1" "$2"; }

@@ -1,7 +1,7 @@
 #!/bin/bash
 # ab_env.sh "<bench args>" "ENV1=.. ENV2=.." "ENV=.." ...
 args="$1"; shift
-run() { env $1 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline $args 2>/dev/null | tail -1 | python3 -c "
+run() { env $1 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline $args 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 r = d['roofline']

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of this tree against the round-5 tree (git worktree add _ab/r5 2d25abb; python -m homonim_amd.build there), interleaved, one box
-run() { (cd $1 && python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-nan-variant --no-other-configs --no-power-probe "${@:2}" 2>/dev/null | tail -1) | python3 -c "
+run() { (cd $1 && python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-nan-variant --no-other-configs --no-power-probe "${@:2}" 2>/dev/null | tail -1) | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 r = d['roofline']

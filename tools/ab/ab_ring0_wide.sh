@@ -1,4 +1,4 @@
-run() { python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-nan-variant --no-other-configs --no-power-probe "$@" 2>/dev/null | tail -1 | python3 -c "
+run() { python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-nan-variant --no-other-configs --no-power-probe "$@" 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d['roofline']
 print('%-40s %8.3f ms launch  frac %.4f parity=%s' % (' '.join(sys.argv[1:]), r['avg_launch_ms'], r['frac'], d['parity_spot_check']['passed']))" "$@"; }

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of the wide kernels' horizontal sums: the shipped library (LDS exchange lines) against _ab/lib_nowline.so (tools/mkvariant_full.sh nowline -DHK_WLINE=0: ds_bpermute)
-run() { HOMONIM_AMD_LIB=$1 python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-nan-variant --no-other-configs --no-power-probe "${@:2}" 2>/dev/null | tail -1 | python3 -c "
+run() { HOMONIM_AMD_LIB=$1 python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-nan-variant --no-other-configs --no-power-probe "${@:2}" 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 r = d['roofline']

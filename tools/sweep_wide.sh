@@ -1,6 +1,6 @@
 #!/bin/bash
 # Kernels wider than 15 on the headline workload:  tools/sweep_wide.sh > gpurun_out/sweep_wide.txt
-run() { python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-nan-variant --no-other-configs --no-power-probe "$@" 2>/dev/null | tail -1 | python3 -c "
+run() { python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-nan-variant --no-other-configs --no-power-probe "$@" 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 r = d['roofline']

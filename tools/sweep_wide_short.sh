@@ -1,6 +1,6 @@
 #!/bin/bash
 # A short form of sweep_wide.sh (one box calibration line + the wide kernels the round-6 verdict names):  tools/sweep_wide_short.sh > gpurun_out/x.txt
-run() { python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-nan-variant --no-other-configs --no-power-probe "$@" 2>/dev/null | tail -1 | python3 -c "
+run() { python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-nan-variant --no-other-configs --no-power-probe "$@" 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 r = d['roofline']
