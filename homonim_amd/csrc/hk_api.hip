@@ -2293,7 +2293,7 @@ int hk_block_norm_split_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_j
     na.band_stride = job->band_stride, na.n_bands = job->n_bands;
     na.src_nd_mode = desc->src_nodata_mode, na.ref_nd_mode = desc->ref_nodata_mode;
     na.src_nodata = desc->src_nodata, na.ref_nodata = desc->ref_nodata;
-    HK_HIP(hk::launch_block_norm_split(na, sl.norm_ws, xchg_dev, 1.0 / (double)world_size, phase, norm_dev, sl.stream));
+    HK_HIP(hk::launch_block_norm_split(na, sl.norm_ws, xchg_dev, phase, norm_dev, sl.stream));
     return HK_OK;
 }
 
@@ -2382,7 +2382,7 @@ int hk_block_norm_split_comm_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_
     na.src_nodata = desc->src_nodata, na.ref_nodata = desc->ref_nodata;
     // six phases on the slab, five all-reduces between them, all queued on the job's stream: no host synchronisation
     for (int phase = 0; phase < 6; ++phase) {
-        HK_HIP(hk::launch_block_norm_split(na, sl.norm_ws, sl.comm_xchg, 1.0 / (double)ctx->comm_world, phase, norm_dev, sl.stream));
+        HK_HIP(hk::launch_block_norm_split(na, sl.norm_ws, sl.comm_xchg, phase, norm_dev, sl.stream));
         if (phase < 5)
             HK_RCCL(rccl().AllReduce(sl.comm_xchg, sl.comm_xchg, n, ncclDouble, ncclSum, ctx->comm, sl.stream));
     }

@@ -198,7 +198,7 @@ hipError_t launch_block_norm(const NormArgs& a, void* workspace, double* norm_ou
 // The same statistics for a block whose rows are spread over several ranks: six phases on this rank's slab, the caller
 // all-reduces (SUM) the float64 exchange buffer (norm_split_exchange_doubles() values, device) between them.
 size_t norm_split_exchange_doubles(int n_bands);
-hipError_t launch_block_norm_split(const NormArgs& a, void* workspace, double* xchg, double inv_world, int phase,
+hipError_t launch_block_norm_split(const NormArgs& a, void* workspace, double* xchg, int phase,
                                    double* norm_out, hipStream_t stream);
 
 // Masked comparison sums of homonim/compare.py:243-255 (hk_compare.hip), per band:

@@ -57,6 +57,7 @@ struct NormWS {  // one per band
     // sample stage
     float lo[2], hi[2];  // [src|ref] pivots: values in [lo, hi] are compacted
     double shift[2];
+    unsigned sample_m;   // valid pixels in the sample (a split block's shift averages the ranks that found any)
     // streaming pass
     unsigned long long pn[PASS_WAVES], pbelow[2][PASS_WAVES];
     double p1[2][PASS_WAVES], p2[2][PASS_WAVES];
@@ -270,8 +271,14 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) norm_sample_kernel(const NormA
             for (int i = 0; i < SAMPLE_THREADS / WAVE; ++i) s_all += red[i];
             const double mean = m ? s_all / (double)m : 0.0;
             ws.shift[q] = (mean == mean && fabs(mean) < 1e300) ? mean : 0.0;
-            ws.lo[q] = need[0] ? key2f(spfx[0]) : __int_as_float(0xff800000);
-            ws.hi[q] = need[1] ? key2f(spfx[1]) : __int_as_float(0x7f800000);
+            ws.sample_m = m;
+            // The streaming pass brackets with float compares, the select orders by key: the two agree except that -0.0 == +0.0
+            // as floats.  A low pivot of +0.0 would compact every -0.0 (not below it as a float) with a key below the window's
+            // base, a high pivot of -0.0 every +0.0 with a key above its top: a zero pivot takes the sign that keeps both zeros
+            // inside the window (the same values, compared alike both ways).
+            const float lo = key2f(spfx[0]), hi = key2f(spfx[1]);
+            ws.lo[q] = need[0] ? (lo == 0.0f ? -0.0f : lo) : __int_as_float(0xff800000);
+            ws.hi[q] = need[1] ? (hi == 0.0f ? 0.0f : hi) : __int_as_float(0x7f800000);
         }
         __syncthreads();
     }
@@ -666,7 +673,9 @@ __global__ void __launch_bounds__(NORM_THREADS) norm_select_kernel(NormWS* __res
 // Split blocks: one block's pixels spread over several ranks (each holds some rows), one result.  Every statistic above
 // is a sum over pixels -- the shifted moments and the integer histograms of the radix select -- so the ranks run the same
 // kernels on their slabs and all-reduce (SUM) a small float64 exchange buffer between the phases:
-//   phase 0  sample -> the slab's shift                     | exchange: 2 values per band (the ranks' mean becomes the shift)
+//   phase 0  sample -> the slab's shift                     | exchange: 3 values per band (the mean over the ranks whose sample
+//                                                           |   found valid pixels becomes the shift: a rank without any must not
+//                                                           |   pull it towards 0, the moments about it would cancel)
 //   phase 1  moments of the slab about the common shift     | 5 values per band (n, m1, m2 of src and ref)
 //   phase 2  global n, mean, var, ranks; level-1 histogram  | 4 x 2048 counts per band (exact in float64)
 //   phase 3  level-1 digit; level-2 histogram               | 4 x 2048
@@ -680,14 +689,14 @@ size_t norm_split_exchange_doubles(int n_bands) { return (size_t)n_bands * SPLIT
 __global__ void split_put_shift_kernel(NormWS* __restrict__ ws_all, double* __restrict__ xchg) {
     NormWS& ws = ws_all[blockIdx.x];
     double* x = xchg + (size_t)blockIdx.x * SPLIT_XCHG;
-    for (int i = threadIdx.x; i < SPLIT_XCHG; i += blockDim.x) x[i] = i < 2 ? ws.shift[i] : 0.0;
+    for (int i = threadIdx.x; i < SPLIT_XCHG; i += blockDim.x) x[i] = i < 2 ? ws.shift[i] : (i == 2 && ws.sample_m ? 1.0 : 0.0);
 }
-__global__ void split_get_shift_kernel(NormWS* __restrict__ ws_all, const double* __restrict__ xchg, double scale) {
+__global__ void split_get_shift_kernel(NormWS* __restrict__ ws_all, const double* __restrict__ xchg) {
     if (threadIdx.x != 0) return;
     NormWS& ws = ws_all[blockIdx.x];
     const double* x = xchg + (size_t)blockIdx.x * SPLIT_XCHG;
     for (int q = 0; q < 2; ++q) {
-        ws.shift[q] = x[q] * scale;
+        ws.shift[q] = x[2] > 0.0 ? x[q] / x[2] : 0.0;
         ws.lo[q] = ws.hi[q] = __int_as_float(0xff800000);  // nothing lies between the pivots: the pass takes the moments only
     }
 }
@@ -754,8 +763,7 @@ __global__ void split_hist_kernel(NormWS* __restrict__ ws_all, double* __restric
 }
 
 // One phase of the split-block statistics on this rank's slab (`a`); the caller all-reduces `xchg` between the phases.
-// `inv_world` = 1 / number of ranks (phase 1 turns the sum of the slabs' shifts into their mean).
-hipError_t launch_block_norm_split(const NormArgs& a, void* workspace, double* xchg, double inv_world, int phase,
+hipError_t launch_block_norm_split(const NormArgs& a, void* workspace, double* xchg, int phase,
                                    double* norm_out, hipStream_t stream) {
     NormWS* ws = reinterpret_cast<NormWS*>(workspace);
     const dim3 bands(a.n_bands), block(NORM_THREADS), gfull(FB_BLOCKS, a.n_bands, 2);
@@ -770,7 +778,7 @@ hipError_t launch_block_norm_split(const NormArgs& a, void* workspace, double* x
         break;
     }
     case 1: {
-        HK_LAUNCH(split_get_shift_kernel, bands, dim3(WAVE), 0, stream, ws, xchg, inv_world);
+        HK_LAUNCH(split_get_shift_kernel, bands, dim3(WAVE), 0, stream, ws, xchg);
         if (rows) {
             const dim3 gstream(pass_waves(a.height, a.width), a.n_bands);
             float* mid = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256(sizeof(NormWS) * (size_t)a.n_bands));

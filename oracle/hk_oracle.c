@@ -391,6 +391,8 @@ void hk_oracle_apply(const float* src, const float* params, int H, int W, float*
     for (int64_t i = 0; i < (int64_t)plane; ++i) out[i] = (float)((float)(params[i] * src[i]) + params[plane + i]);
 }
 
+#define ORACLE_SUM_BLOCK 512
+
 /* quickselect with 3-way partitioning: k-th smallest of a[0..n) (a is permuted) */
 static float select_kth(float* a, size_t n, size_t k) {
     size_t lo = 0, hi = n; /* candidates in [lo, hi) */
@@ -445,24 +447,36 @@ int hk_oracle_block_norm(const float* src, int snd_mode, float snd, const float*
         return -1;
     }
     size_t n = 0;
-    double sum_s = 0.0, sum_r = 0.0;
     for (size_t i = 0; i < total; ++i) {
         if (px_valid(src[i], snd_mode, snd) && px_valid(ref[i], rnd_mode, rnd)) {
             s[n] = src[i];
             r[n] = ref[i];
-            sum_s += (double)src[i];
-            sum_r += (double)ref[i];
             ++n;
         }
     }
     norm_out[0] = norm_out[1] = 0.0;
     if (n > 0) {
+        /* every sum runs over blocks of ORACLE_SUM_BLOCK values whose partial sums are then added: the chain of roundings
+           behind a sum is ~block + n / block additions long instead of n (tests/test_exact_stats_cpu.py holds the std
+           ratio to 1e-13 of the exact one) */
+        double sum_s = 0.0, sum_r = 0.0;
+        for (size_t i0 = 0; i0 < n; i0 += ORACLE_SUM_BLOCK) {
+            const size_t i1 = i0 + ORACLE_SUM_BLOCK < n ? i0 + ORACLE_SUM_BLOCK : n;
+            double bs = 0.0, br = 0.0;
+            for (size_t i = i0; i < i1; ++i) bs += (double)s[i], br += (double)r[i];
+            sum_s += bs, sum_r += br;
+        }
         const double mean_s = sum_s / (double)n, mean_r = sum_r / (double)n;
         double vs = 0.0, vr = 0.0;
-        for (size_t i = 0; i < n; ++i) {
-            const double ds = (double)s[i] - mean_s, dr = (double)r[i] - mean_r;
-            vs += ds * ds;
-            vr += dr * dr;
+        for (size_t i0 = 0; i0 < n; i0 += ORACLE_SUM_BLOCK) {
+            const size_t i1 = i0 + ORACLE_SUM_BLOCK < n ? i0 + ORACLE_SUM_BLOCK : n;
+            double bs = 0.0, br = 0.0;
+            for (size_t i = i0; i < i1; ++i) {
+                const double ds = (double)s[i] - mean_s, dr = (double)r[i] - mean_r;
+                bs += ds * ds;
+                br += dr * dr;
+            }
+            vs += bs, vr += br;
         }
         const double n0 = sqrt(vr / (double)n) / sqrt(vs / (double)n);
         const double pr = percentile1(r, n), ps = percentile1(s, n);

@@ -19,8 +19,9 @@ from oracle import oracle_np as onp
 
 def _protocol(vals_per_rank, allreduce):
     """ the six phases with `allreduce` standing for the SUM all-reduce of a numpy array (every rank's copy in, sums out) """
-    world = len(vals_per_rank)
-    shift = allreduce([np.array([v[0].mean() if v[0].size else 0.0, v[1].mean() if v[1].size else 0.0]) for v in vals_per_rank]) / world
+    # the shift: the mean of the slab means over the ranks that have valid values (a rank without any contributes nothing)
+    x = allreduce([np.array([v[0].mean(), v[1].mean(), 1.0]) if v[0].size else np.zeros(3) for v in vals_per_rank])
+    shift = x[:2] / x[2] if x[2] > 0 else np.zeros(2)
     mom = allreduce([onp.split_norm_moments(v, shift) for v in vals_per_rank])
     n = int(mom[0])
     if n == 0:
@@ -81,7 +82,7 @@ def allreduce(parts):           # this rank holds ONE part; the sum comes from t
     dist.all_reduce(t, op=dist.ReduceOp.SUM)
     return t.numpy()
 
-# _protocol divides the shift by len(vals_per_rank): pass a list of the world's length whose own entry is first
+# _protocol takes one entry per rank: pass a list of the world's length whose own entry is first
 norm, prefixes = _protocol([mine] + [mine] * (world - 1), lambda parts: allreduce(parts))
 with open(os.path.join({out!r}, 'rank_%d.json' % rank), 'w') as f:
     json.dump(dict(rank=rank, norm=[float(v) for v in norm], prefixes=[[int(x) for x in row] for row in prefixes]), f)
