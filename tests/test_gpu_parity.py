@@ -19,6 +19,7 @@ import pytest
 from conftest import GOLDEN_CASES, assert_same_f32, case_id
 from homonim_amd import Affine, CRS, KernelModel, Model, RasterArray, RefSpaceModel, SrcSpaceModel, _hk
 from homonim_amd.enums import Resampling
+from oracle import exact_window as ew
 from oracle import oracle_np as onp
 
 pytestmark = pytest.mark.gpu
@@ -279,6 +280,11 @@ def test_randomized_configurations_vs_oracle(ctx, oc, seed, monkeypatch):
         # such windows, profiles/r06b_soak.txt; a handful of pixels may differ, a defect moves thousands)
         n_bad = int(np.count_nonzero(~np.isclose(got_r2[ok], exp_r2[ok], rtol=1e-3, atol=1e-3)))
         assert n_bad <= max(3, int(1e-5 * ok.sum())), f'{what}: R2 of {n_bad} pixels'
+        # ... and every R2 of the kernel lies in its enclosure over all admissible float64 summations (oracle/exact_window.py):
+        # the pixels above are rounding noise of the oracle's order, not licence for the kernel
+        enc = ew.enclose(model, src, nodata['src'], ref, nodata['ref'], kshape, True, None, norm_in)
+        bad = ~enc.params[2].contains(got_r2)
+        assert not bad.any(), f'{what}: R2 outside its enclosure at {np.argwhere(bad)[:3].tolist()}'
         params, exp_params = params[:2], exp_params[:2]
     assert_close_ulp(params, exp_params, 'params: ' + what)
     assert_close_ulp(corr, exp_corr, 'corrected: ' + what)
@@ -593,33 +599,9 @@ def test_certified_r2_test_degenerate_windows(ctx, oc):
 
 
 def _adversarial_pair(kind, shape, seed):
-    """ Rasters whose windows sit where the r2-mask certificate is tight: tiny variance on a large mean (flat DN
-    imagery), R2 spread around the threshold, integer data, and magnitudes outside the certificate's windows. """
-    rng = np.random.default_rng(seed)
-    h, w = shape
-    yy, xx = np.mgrid[0:h, 0:w]
-    if kind == 'flat-dn':
-        sd = 10 ** (-2 + 3.5 * xx / w)                               # std 0.01 .. 30 on a mean of 5000
-        src = 5000 + sd * rng.normal(size=shape)
-        ref = 0.8 * src + 300 + sd * 10 ** (-1.5 + 2 * yy / h) * rng.normal(size=shape)
-    elif kind == 'marginal':
-        src = rng.normal(100, 10, shape)
-        ref = src + (3 + 40 * xx / w) * rng.normal(size=shape)       # R2 from ~0.9 down to ~0.05 across the columns
-    elif kind == 'integer':
-        src = rng.integers(0, 255, shape).astype(float)
-        ref = np.round(src * (0.5 + yy / h)) + rng.integers(0, 6, shape)
-    elif kind == 'tiny':
-        src = 1e-17 * rng.uniform(0.05, 1, shape)
-        ref = 1.2 * src + 1e-18 + 1e-19 * rng.normal(size=shape)
-    elif kind == 'huge':
-        src = 1e14 * rng.uniform(0.05, 1, shape)
-        ref = 1.2 * src + 1e13 + 1e12 * rng.normal(size=shape)
-    elif kind == 'small-gain':
-        src = 1e4 * rng.uniform(0.05, 1, shape)
-        ref = 10 ** (-8 + 7 * xx / w) * src + 1e-3 * rng.normal(size=shape)   # gains 1e-8 .. 0.1 (window edge 2^-20)
-    else:
-        raise ValueError(kind)
-    return src.astype(np.float32), ref.astype(np.float32)
+    """ Rasters whose windows sit where the r2-mask certificate is tight (oracle/exact_window.py raster_pair) """
+    assert kind in ew.ADVERSARIAL_KINDS
+    return ew.raster_pair(kind, shape, seed)
 
 
 @pytest.mark.oracle
@@ -633,6 +615,7 @@ def test_r2_certificate_on_adversarial_rasters(ctx, oc, kind, kernel_shape, noda
         src[60:64, 100:130] = np.nan
         ref[10, ::37] = np.nan
     n_valid = int((~np.isnan(src) & ~np.isnan(ref)).sum())
+    enc = ew.enclose('gain-offset', src, nodata, ref, nodata, kernel_shape, True)
     for thresh in (0.25, 0.0, 0.9):
         # (1) the certificate against the kernel's own exact evaluation (parameter output switches the certificate
         #     off): identical counts and corrected values, bit for bit
@@ -650,6 +633,16 @@ def test_r2_certificate_on_adversarial_rasters(ctx, oc, kind, kernel_shape, noda
         else:
             assert n_fail == exp_fail, (kind, thresh)
             assert_close_ulp(corr, exp_corr, 'corrected', max_frac=1e-3)
+        # (3) against the enclosures of every admissible float64 summation (oracle/exact_window.py): the count lies between the
+        #     certain and the possible failures, every pixel that certainly passes is corrected inside its enclosure (bit for bit
+        #     where that is one value), and where no decision is open the count is the oracle's
+        d = ew.decide(enc, thresh)
+        n_cf, n_und = int(d.certain_fail.sum()), int(d.undecided.sum())
+        assert n_cf <= n_fail <= n_cf + n_und and n_cf <= exp_fail <= n_cf + n_und, (kind, thresh, n_fail, exp_fail, n_cf, n_und)
+        if n_und == 0:
+            assert n_fail == exp_fail, (kind, thresh)
+        bad = ~enc.corr.contains(corr) & d.certain_pass
+        assert not bad.any(), f'{kind} {thresh}: corrected outside its enclosure at {np.argwhere(bad)[:3].tolist()}'
 
 
 @pytest.mark.oracle
