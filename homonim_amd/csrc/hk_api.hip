@@ -19,6 +19,7 @@
 #include <map>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <vector>
 
 #include "../../include/homonim_hk.h"
@@ -257,7 +258,7 @@ struct Slot {
     // exchange buffer of hk_block_norm_split_comm_dev on THIS stream: sequences queued on different streams run concurrently on
     // the device (comm_mu only orders their queuing), so they must not share one
     double* comm_xchg = nullptr;
-    size_t comm_xchg_doubles = 0;
+    size_t comm_xchg_bytes = 0;
     // Pinned words of the slot (PIN_BYTES of hipHostMalloc'd memory): small results and arguments travel through them,
     // never through the caller's pageable memory.  fail_host = the first word (the r2-mask failure counter).
     unsigned long long* fail_host = nullptr;
@@ -288,7 +289,7 @@ struct Slot {
     int tbl_next = 0;
     // gain-offset with the r2 mask: the wave-rows the certificate build leaves to the list launch (FitArgs::open_rows), one bit each
     unsigned* open_rows = nullptr;
-    size_t open_rows_words = 0;
+    size_t open_rows_bytes = 0;
     bool direct_pending = false;  // copies queued straight from / to page-locked CALLER arrays since the last stream synchronisation
     bool busy = false;         // leased by a host-pointer call (SlotLease)
     int dev_inflight = 0;      // device-job entry points currently queuing on this stream (DevEnter): a lease waits for them
@@ -297,6 +298,17 @@ struct Slot {
 
 constexpr int64_t ROW_ALIGN = 64;  // device rows padded to 64 elements (256 B)
 
+// The launch switches of the environment (README "Environment switches"), read once per context by hk_ctx_create.
+struct LaunchPolicy {
+    // runs of this many consecutive units (neighbouring strips) per XCD, 0 = plain round-robin (hk_fit_kernel.h); 16 measured
+    // best across models on MI355X (gain 5x5: -12 %, gain-offset without the r2 mask: -4 %, VALU-bound variants: -1 %)
+    int xcd_remap = 16;
+    int force_general = 0;              // HK_FORCE_GENERAL: never take the dense specialisation (testing)
+    std::optional<int> use_ring;        // HK_USE_RING: a ring mode forced where the shape has a build of it (testing)
+    int wave_slots = 256 * 12;          // HK_WAVE_SLOTS: resident waves of the device (3 per SIMD), seg_policy()
+    std::optional<int> seg_big, seg_tail;  // HK_SEG_BIG / HK_SEG_TAIL: the two segment heights of seg_policy()
+};
+
 }  // namespace
 
 struct hk_ctx {
@@ -304,13 +316,10 @@ struct hk_ctx {
     std::vector<Slot> slots;
     std::mutex mu;
     std::condition_variable cv;
-    int xcd_remap = 0;
+    LaunchPolicy launch;
     // the last HOST-POINTER gain-offset call with a threshold found pixels failing the r2 mask: real imagery usually does, block
     // after block, so the next call lets its first pass leave what the in-painting reads (offsets + source flags, 5 bytes per
     // pixel of stores) instead of running it again when the count comes back non-zero.  Either choice gives the same results.
-    // (Rounds 3-5 also chose the kernel BUILD by it -- certificate-only or complete -- with a back-off and, on the device-job
-    // path, an expiry count; since round 6 the certificate build always runs first and hands the wave-rows it cannot settle to
-    // a list launch, and a device-resident job says by carrying `scratch` that it wants the in-painting's inputs left there.)
     std::atomic<int> expect_r2_failures{0};
     // RCCL communicator of the one data-path collective (hk_comm_init; the split-block statistics)
     ncclComm_t comm = nullptr;
@@ -430,19 +439,36 @@ RcclApi& rccl() {
             return fail(HK_ERR_HIP, "%s failed: %s (%s:%d)", #expr, rccl().GetErrorString(_r), __FILE__, __LINE__); \
     } while (0)
 
-int ensure_dev(Slot& s, size_t bytes) {
-    if (fits(s.dev_bytes, bytes)) return HK_OK;
-    if (s.dev) {
+// A grow-only device buffer of a slot (`buf`, `have` bytes): a request that fits() it keeps it; a larger one drains the slot's
+// stream (work queued there may still read the buffer), frees it and allocates `need` bytes, plus `slack` unless guarded (the
+// buffer then ends where its last user's does).  The caller holds whatever lock guards the slot's scratch.
+template <class T>
+int grow_slot_buf(Slot& s, T*& buf, size_t& have, size_t need, size_t slack = 0) {
+    if (fits(have, need)) return HK_OK;
+    if (buf) {
         HK_HIP(hipStreamSynchronize(s.stream));
-        HK_HIP(dev_free(s.dev));
-        s.dev = nullptr;
-        s.dev_bytes = 0;
+        HK_HIP(dev_free(buf));
+        buf = nullptr, have = 0;
     }
-    const size_t want = guard_mode() ? bytes : bytes + bytes / 8;  // (guarded: the buffer ends where its last user's does)
-    if (dev_malloc(&s.dev, want) != hipSuccess) return fail(HK_ERR_NOMEM, "hipMalloc(%zu) failed", want);
-    s.dev_bytes = want;
+    const size_t want = guard_mode() ? need : need + slack;
+    void* p = nullptr;
+    if (dev_malloc(&p, want) != hipSuccess) return fail(HK_ERR_NOMEM, "hipMalloc(%zu) failed", want);
+    buf = static_cast<T*>(p), have = want;
     return HK_OK;
 }
+
+// the staging slab of the host-pointer calls (an eighth to spare)
+int ensure_dev(Slot& s, size_t bytes) { return grow_slot_buf(s, s.dev, s.dev_bytes, bytes, bytes / 8); }
+
+// Bump allocation inside the staging slab: every buffer at a 256-byte aligned offset, in the order it is taken.
+struct SlabLayout {
+    size_t total = 0;
+    size_t take(size_t bytes) {
+        const size_t off = total;
+        total += (bytes + 255) / 256 * 256;
+        return off;
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Host staging.  BASELINE.json north_star: "blocks stream ... into pinned host buffers and hipMemcpyAsync to HBM".  The HIP
@@ -703,6 +729,17 @@ int stage_finish(Slot& s) {
     return HK_OK;
 }
 
+// A host raster into the float32 device plane `dplane` (row stride `dstride` elements): float32 directly, other dtypes through
+// the raw plane `raw` (the same stride, in elements of the dtype) and the on-device conversion
+int stage_in(Slot& s, const void* host, int64_t hstride, int dt, float* dplane, void* raw, int64_t dstride, int h, int w) {
+    const size_t es = hk::dtype_size(dt);
+    void* dst = dt ? raw : static_cast<void*>(dplane);
+    const int rc = stage_h2d(s, dst, dstride * es, host, hstride * es, (size_t)w * es, h);
+    if (rc) return rc;
+    if (dt) HK_HIP(hk::launch_cast_in(dt, dst, dstride, dplane, dstride, h, w, s.stream));
+    return HK_OK;
+}
+
 void slot_release(Slot& s) {
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.dev) (void)dev_free(s.dev);
@@ -801,7 +838,19 @@ float r2_failcert_scale(float thresh) {
     return kf;
 }
 
-void fill_args(hk::FitArgs& a, const hk_fit_desc* d, int xcd_remap) {
+// Fewer resident waves for the dense `gain` kernel on large rasters: at 8 KB of LDS per wave 20 waves per CU stream their rows
+// at once and the HBM answers with ~5.0 TB/s; 4 KB of unused LDS per wave leave 12 (three lock-step workgroups per CU) and it
+// answers with 5.4: gain 5x5 at 16384^2 x 4 2.58 -> 2.37 ms, configs[1] 0.631 -> 0.605 ms, 3x3 -2.5 % (profiles/r03_lds_pad.txt).
+// Not for the general (nodata) build -- its registers keep it at that occupancy already --, not for 7x7 (12 KB ring), not for
+// launches of less than ~128 M pixels (a 4-band 4096^2 tile: +3 %); the VALU-bound builds want every wave (headline +8 % at 16
+// -> 14 waves).  lds_pad_by_size: the build takes the pad by the launch's size, lds_pad_of: the pad for that many pixels.
+bool lds_pad_by_size(const hk_fit_desc* d, const LaunchPolicy& lp) {
+    return d->model == HK_MODEL_GAIN && !needs_r2(d) && d->kh <= 5 && d->kw <= 7 && d->src_nodata_mode == HK_NODATA_NONE &&
+           d->ref_nodata_mode == HK_NODATA_NONE && !lp.force_general;
+}
+int lds_pad_of(long long pixels) { return pixels >= (128ll << 20) ? 4096 : 0; }
+
+void fill_args(hk::FitArgs& a, const hk_fit_desc* d, const LaunchPolicy& lp) {
     a.rh = d->kh / 2;
     a.rw = d->kw / 2;
     a.overlap_lanes = hk::overlap_lanes_for(a.rw);
@@ -818,7 +867,7 @@ void fill_args(hk::FitArgs& a, const hk_fit_desc* d, int xcd_remap) {
     a.n_full = (float)(d->kh * d->kw);
     a.nd_full = (double)(d->kh * d->kw);
     a.inv_n_full = 1.0 / (double)(d->kh * d->kw);
-    a.force_general = getenv("HK_FORCE_GENERAL") ? atoi(getenv("HK_FORCE_GENERAL")) : 0;
+    a.force_general = lp.force_general;
     // ring mode (hk_fit_kernel.h): full LDS ring while it leaves room for >= 11 waves per CU (kh <= 5), centre-only ring up
     // to kh = 39 (1 KB per wave and row of the half-height; 33 - 39 rows: 3 - 13 % faster than re-loading, from 41 rows
     // slower -- headline workload, round 5), everything re-loaded beyond -- that path exists
@@ -849,54 +898,53 @@ void fill_args(hk::FitArgs& a, const hk_fit_desc* d, int xcd_remap) {
     if (!needs_r2(d) && a.use_ring == 1 && d->model != HK_MODEL_GAIN_OFFSET &&
         (d->kh <= 5 || (d->model == HK_MODEL_GAIN && d->kh <= 7)))
         a.seg_rows_pref = 32;
-    if (const char* e = getenv("HK_USE_RING")) {  // testing hook
-        const int m = atoi(e);
+    if (lp.use_ring) {
+        const int m = *lp.use_ring;
         const bool mem_bound = d->model != HK_MODEL_GAIN_OFFSET && !needs_r2(d);
         if (m == 1 && d->kh <= 63 && (d->kw <= 7 || (mem_bound && d->kw <= 15))) a.use_ring = 1;
         if (m == 2 && d->kh <= 127) a.use_ring = 2;
         if (m == 3 && mem_bound && d->kh >= 7 && d->kh / 2 <= hk::split_ring_rows(d->model) && d->kw >= 5 && d->kw <= 15) a.use_ring = 3;
         if (m == 0 && d->kw >= 9) a.use_ring = 0;
     }
-    a.xcd_remap = xcd_remap;
-    // Fewer resident waves for the dense `gain` kernel on large rasters: at 8 KB of LDS per wave 20 waves per CU stream their rows
-    // at once and the HBM answers with ~5.0 TB/s; 4 KB of unused LDS per wave leave 12 (three lock-step workgroups per CU) and it
-    // answers with 5.4: gain 5x5 at 16384^2 x 4 2.58 -> 2.37 ms, configs[1] 0.631 -> 0.605 ms, 3x3 -2.5 % (profiles/r03_lds_pad.txt).
-    // Not for the general (nodata) build -- its registers keep it at that occupancy already --, not for 7x7 (12 KB ring), not for
-    // launches of less than ~128 M pixels (a 4-band 4096^2 tile: +3 %); the VALU-bound builds want every wave (headline +8 % at 16
-    // -> 14 waves).  -1 = decided by fill_grid() from the job's size.
-    a.lds_pad = 0;
-    if (d->model == HK_MODEL_GAIN && !needs_r2(d) && d->kh <= 5 && d->kw <= 7 && d->src_nodata_mode == HK_NODATA_NONE &&
-        d->ref_nodata_mode == HK_NODATA_NONE && !a.force_general)
-        a.lds_pad = -1;
+    a.xcd_remap = lp.xcd_remap;
+    a.lds_pad = lds_pad_by_size(d, lp) ? -1 : 0;  // -1 = decided by fill_grid() from the job's size
     a.out_y0 = 0, a.out_y1 = a.height, a.out_x0 = 0, a.out_x1 = a.width;  // store window: the whole job (callers narrow it)
 }
 
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
+// Row segments of the units (segment, band, strip), one wave each.  A wave re-reads 2*rh priming rows, so long segments waste
+// less; but a launch ends when its last wave does, so its final segments are short.  A launch of at least `two_size_from`
+// units therefore gets `big` rows per segment for most of its units and `tail` rows for those of its last `tail_waves` waves
+// (dispatched last); smaller launches and an explicit height use `uniform` rows throughout.  fill_grid applies this over the
+// rows of one job, hk_fit_apply_batch_dev over the jobs of a batched launch.
+struct SegPolicy {
+    int uniform;
+    int big, tail;
+    long long two_size_from;  // 6 generations of resident waves
+    double tail_waves;        // the last 1.25 generations
+};
+SegPolicy seg_policy(int kh, const LaunchPolicy& lp) {
+    const int uniform = kh <= 5 ? 64 : (kh <= 9 ? 128 : 256);
+    const long long slots = lp.wave_slots;
+    return {uniform, lp.seg_big.value_or(2 * uniform), lp.seg_tail.value_or(uniform / 2), 6 * slots, 1.25 * (double)slots};
 }
 
-// Units of one launch: (segment, band, strip), one wave each.  A wave re-reads 2*rh priming rows, so long segments waste
-// less; but the launch ends when its last wave does, so the final segments are short.  Large rasters therefore get
-// `big` rows per segment for most of the height and `tail` rows for the last ~1.25 "generations" of resident waves
-// (dispatched last, segment-major order); small rasters and an explicit `seg_rows` use one size.
-void fill_grid(hk::FitArgs& a, int seg_rows) {
+// The units of one launch (fill_args done).  `seg_rows` > 0: segments of that height; otherwise the build's own preference
+// (fill_args) or seg_policy().
+void fill_grid(hk::FitArgs& a, int seg_rows, const LaunchPolicy& lp) {
     const int out_w = (hk::WAVE - 2 * a.overlap_lanes) * hk::PX;
-    const int kh = 2 * a.rh + 1;
+    const SegPolicy seg = seg_policy(2 * a.rh + 1, lp);
     a.n_strips = (a.width + out_w - 1) / out_w;
-    if (seg_rows <= 0 && a.seg_rows_pref > 0) seg_rows = a.seg_rows_pref;  // the build's own preference (fill_args)
-    const int uniform = seg_rows > 0 ? seg_rows : (kh <= 5 ? 64 : (kh <= 9 ? 128 : 256));
+    if (seg_rows <= 0 && a.seg_rows_pref > 0) seg_rows = a.seg_rows_pref;
+    const int uniform = seg_rows > 0 ? seg_rows : seg.uniform;
     a.seg_rows = uniform < a.height ? uniform : a.height;
     a.seg_rows_tail = a.seg_rows;
     a.n_segs = (a.height + a.seg_rows - 1) / a.seg_rows;
     a.n_segs_big = a.n_segs;
-    const long long slots = (long long)env_int("HK_WAVE_SLOTS", 256 * 12);  // resident waves of the device (3 per SIMD)
-    const long long per_row_band = (long long)a.n_strips * a.n_bands;        // units per segment row
-    if (seg_rows <= 0 && per_row_band * a.n_segs >= 6 * slots) {
-        const int big = env_int("HK_SEG_BIG", 2 * uniform), tail = env_int("HK_SEG_TAIL", uniform / 2);
-        const double gens = 1.25;
-        // image rows whose big-segment units make up `gens` generations of resident waves
-        long long tail_rows = (long long)(gens * (double)slots / (double)per_row_band * big);
+    const long long per_row_band = (long long)a.n_strips * a.n_bands;  // units per segment row
+    if (seg_rows <= 0 && per_row_band * a.n_segs >= seg.two_size_from) {
+        const int big = seg.big, tail = seg.tail;
+        // image rows whose big-segment units make up the tail's waves
+        long long tail_rows = (long long)(seg.tail_waves / (double)per_row_band * big);
         tail_rows = (tail_rows + tail - 1) / tail * tail;
         if (big > 0 && tail > 0 && tail_rows < a.height - big) {
             const int n_big = (int)((a.height - tail_rows) / big);
@@ -908,26 +956,12 @@ void fill_grid(hk::FitArgs& a, int seg_rows) {
         }
     }
     a.total_units = a.n_strips * a.n_segs * a.n_bands;
-    if (a.lds_pad < 0) a.lds_pad = ((long long)a.height * a.width * a.n_bands >= (128ll << 20)) ? 4096 : 0;
+    if (a.lds_pad < 0) a.lds_pad = lds_pad_of((long long)a.height * a.width * a.n_bands);
 }
 
-// kernel_model.py:364-371 for ONE band whose first pass counted failing pixels: in-paint the offsets of the failing
-// pixels from the passing ones (restated GDALFillNodata) and run the fit again with `offset_in`, which recomputes their
-// gains and re-applies.  `a` is the first pass's argument block (n_bands == 1).
-// scratch of the in-painting branch: [offset | column tables] (rounds 1-4 kept a `filled` plane and room for gain / r2 in front: the
-// targets are filled in place since round 5)
+// scratch of the in-painting branch: [offset | column tables]
 static int ensure_inpaint_scratch(Slot& sl, size_t plane, int height, long long stride) {
-    const size_t need = plane + hk::inpaint_workspace_bytes(height, stride);
-    if (!fits(sl.aux_bytes, need)) {
-        if (sl.aux) {
-            HK_HIP(hipStreamSynchronize(sl.stream));
-            HK_HIP(dev_free(sl.aux));
-        }
-        sl.aux = nullptr, sl.aux_bytes = 0;
-        if (dev_malloc(&sl.aux, need) != hipSuccess) return fail(HK_ERR_NOMEM, "hipMalloc(%zu) failed", need);
-        sl.aux_bytes = need;
-    }
-    return HK_OK;
+    return grow_slot_buf(sl, sl.aux, sl.aux_bytes, plane + hk::inpaint_workspace_bytes(height, stride));
 }
 
 // gain-offset with the r2 mask when nothing but the corrected block (and, from scratch, the offsets) is asked for and the failures
@@ -935,29 +969,13 @@ static int ensure_inpaint_scratch(Slot& sl, size_t plane, int height, long long 
 // PROOFS.md appendix A settles a wave-row whose every valid pixel certainly passes) and marks the wave-rows it cannot settle in
 // a bit plane; the LIST launch -- the complete build on a persistent grid, one run of marked rows per wave at a time -- follows on
 // the same stream and does those rows with the reference's own R2 expression.  Together they write every row once and count every
-// failing pixel once; an empty bit plane (clean rasters) costs the list launch a few microseconds.  Rounds 3 - 5 instead voided the
-// whole band on the first open wave-row (HK_COUNT_RETRY in its counter), ran it again with the complete build and remembered, with
-// a back-off and an expiry count, which build to start the next launches with.  (The certificate has builds for the full and the
-// centre ring, its constants assume window counts below 2^16, and the in-painting's source flags do not fit its registers: other
-// shapes, R2 / gain output and launches that leave the in-painting's inputs run the complete build over the whole grid.)
-static_assert(HK_COUNT_RETRY == hk::FIT_RETRY_BIT, "public and kernel-side re-run bits differ");
+// failing pixel once; an empty bit plane (clean rasters) costs the list launch a few microseconds.  (The certificate has builds for
+// the full and the centre ring, its constants assume window counts below 2^16, and the in-painting's source flags do not fit its
+// registers: other shapes, R2 / gain output and launches that leave the in-painting's inputs run the complete build over the
+// whole grid.)
 static bool cert_list_eligible(const hk::FitArgs& a, const hk_fit_desc* desc) {
     return desc->model == HK_MODEL_GAIN_OFFSET && a.has_thresh && a.fail_count && !a.r2 && !a.gain && !a.flag && !a.offset_in &&
            !a.jobs && (a.use_ring == 1 || a.use_ring == 2) && (long long)desc->kh * desc->kw <= 65535;
-}
-
-static int ensure_open_rows(hk_ctx* ctx, Slot& sl, size_t words) {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (sl.open_rows && sl.open_rows_words >= words) return HK_OK;
-    if (sl.open_rows) {
-        HK_HIP(hipStreamSynchronize(sl.stream));
-        HK_HIP(dev_free(sl.open_rows));
-        sl.open_rows = nullptr, sl.open_rows_words = 0;
-    }
-    void* p = nullptr;
-    if (dev_malloc(&p, words * sizeof(unsigned)) != hipSuccess) return fail(HK_ERR_NOMEM, "hipMalloc(%zu) failed", words * sizeof(unsigned));
-    sl.open_rows = static_cast<unsigned*>(p), sl.open_rows_words = words;
-    return HK_OK;
 }
 
 // the fused launch of one job (fill_args + fill_grid done): certificate build + list launch where they apply, the one build otherwise
@@ -967,12 +985,15 @@ static int launch_fit(hk_ctx* ctx, Slot& sl, hk::FitArgs& a, const hk_fit_desc* 
         HK_HIP(hk::launch_fit_apply(a, desc->model, r2, sl.stream));
         return HK_OK;
     }
-    const size_t words = (size_t)a.n_bands * (size_t)a.n_strips * (size_t)((a.height + 31) / 32);
-    const int rc = ensure_open_rows(ctx, sl, words);
-    if (rc) return rc;
+    const size_t bytes = (size_t)a.n_bands * (size_t)a.n_strips * (size_t)((a.height + 31) / 32) * sizeof(unsigned);
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        const int rc = grow_slot_buf(sl, sl.open_rows, sl.open_rows_bytes, bytes);
+        if (rc) return rc;
+    }
     hk::FitArgs c = a;
     c.open_rows = sl.open_rows;
-    HK_HIP(hipMemsetAsync(c.open_rows, 0, words * sizeof(unsigned), sl.stream));
+    HK_HIP(hipMemsetAsync(c.open_rows, 0, bytes, sl.stream));
     c.cert_only = 1;
     HK_HIP(hk::launch_fit_apply(c, desc->model, r2, sl.stream));
     c.cert_only = 0, c.list_mode = 1;
@@ -980,6 +1001,9 @@ static int launch_fit(hk_ctx* ctx, Slot& sl, hk::FitArgs& a, const hk_fit_desc* 
     return HK_OK;
 }
 
+// kernel_model.py:364-371 for ONE band whose first pass counted failing pixels: in-paint the offsets of the failing
+// pixels from the passing ones (restated GDALFillNodata) and run the fit again with `offset_in`, which recomputes their
+// gains and re-applies.  `a` is the first pass's argument block (n_bands == 1).
 // `n_fail`: the band's r2-mask failure count.  `pre_offset` / `pre_flag` (both or neither): offsets and source flags (r2 > thresh) & (gain > 0) & valid left by the pass
 // that counted the failures (FitArgs::flag) -- the in-painting then starts right away.  `drop_params`: the parameter
 // planes in `a` are scratch, the closing pass need not write them.
@@ -1027,9 +1051,43 @@ static int inpaint_band(Slot& sl, const hk::FitArgs& a, const hk_fit_desc* desc,
     return HK_OK;
 }
 
-// Device-side KernelModel.fit (+ apply when d_corr) of one float32 block already in HBM: block statistics for
-// gain-blk-offset (or the caller's norm), the fused kernel, and the in-painting branch of gain-offset
-// (kernel_model.py:361-371) when valid pixels fail the r2 mask.  d_gain / d_off / d_r2 / d_corr are nullable planes.
+// The fused kernel's argument block for a device-resident job, or for band `band` of it alone: its planes, shape and store
+// window, the build's launch policy (fill_args) and its units (fill_grid with the job's seg_rows).
+int job_fit_args(hk::FitArgs& a, const hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_job& job, int band = -1) {
+    const int b = band < 0 ? 0 : band;
+    const long long off = (long long)b * job.band_stride;
+    auto plane = [off](float* p) { return p ? p + off : nullptr; };
+    memset(&a, 0, sizeof(a));
+    a.src = job.src + off, a.ref = job.ref + off;
+    a.gain = plane(job.gain), a.offset = plane(job.offset), a.r2 = plane(job.r2), a.corr = plane(job.corr);
+    a.norm = job.norm ? job.norm + 2 * b : nullptr;
+    a.fail_count = job.fail_count ? reinterpret_cast<unsigned long long*>(job.fail_count) + b : nullptr;
+    a.height = job.height, a.width = job.width, a.stride = job.stride;
+    a.band_stride = band < 0 ? job.band_stride : 0;
+    a.n_bands = band < 0 ? job.n_bands : 1;
+    fill_args(a, desc, ctx->launch);
+    fill_grid(a, job.seg_rows, ctx->launch);
+    if (job.out_rows || job.out_cols) {  // the halo crop of a block processed in place inside a larger raster
+        if (a.has_thresh)
+            return fail(HK_ERR_UNSUPPORTED, "a store window is not supported together with r2_inpaint_thresh (the in-painting "
+                                            "needs the parameters of the whole block)");
+        a.out_y0 = job.out_row0, a.out_y1 = job.out_row0 + job.out_rows;
+        a.out_x0 = job.out_col0, a.out_x1 = job.out_col0 + job.out_cols;
+    }
+    return HK_OK;
+}
+
+// The block statistics' argument block (gain-blk-offset) for n_bands planes src / ref + band * band_stride
+hk::NormArgs norm_args(const hk_fit_desc* desc, const float* src, const float* ref, int height, int width, long long stride,
+                       long long band_stride = 0, int n_bands = 1) {
+    hk::NormArgs na;
+    na.src = src, na.ref = ref, na.height = height, na.width = width, na.stride = stride;
+    na.band_stride = band_stride, na.n_bands = n_bands;
+    na.src_nd_mode = desc->src_nodata_mode, na.ref_nd_mode = desc->ref_nodata_mode;
+    na.src_nodata = desc->src_nodata, na.ref_nodata = desc->ref_nodata;
+    return na;
+}
+
 // A fit whose r2-mask outcome has not been looked at yet (run_host reads the counter together with the outputs: one
 // stream synchronisation per block when no pixel fails, which is the usual case on well-conditioned imagery)
 struct FitPending {
@@ -1072,31 +1130,27 @@ int fit_on_device(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, const double* 
             memcpy(sl.pin<double>(Slot::PIN_NORM_IN), norm_in, 2 * sizeof(double));  // (caller memory -> pinned words)
             HK_HIP(hipMemcpyAsync(d_norm, sl.pin<double>(Slot::PIN_NORM_IN), 2 * sizeof(double), hipMemcpyHostToDevice, sl.stream));
         } else {
-            hk::NormArgs na;
-            na.src = d_src, na.ref = d_ref, na.height = height, na.width = width, na.stride = stride;
-            na.band_stride = 0, na.n_bands = 1;
-            na.src_nd_mode = desc->src_nodata_mode, na.ref_nd_mode = desc->ref_nodata_mode;
-            na.src_nodata = desc->src_nodata, na.ref_nodata = desc->ref_nodata;
-            HK_HIP(hk::launch_block_norm(na, d_norm_ws, d_norm, sl.stream));
+            HK_HIP(hk::launch_block_norm(norm_args(desc, d_src, d_ref, height, width, stride), d_norm_ws, d_norm, sl.stream));
         }
     }
+    hk_dev_job job = {};
+    job.src = d_src, job.ref = d_ref, job.gain = d_gain, job.offset = d_off, job.r2 = d_r2, job.corr = d_corr;
+    job.norm = blk ? d_norm : nullptr;
+    job.fail_count = reinterpret_cast<uint64_t*>(d_fail);
+    job.n_bands = 1, job.height = height, job.width = width, job.stride = stride;
+    // the in-painting branch needs the parameters of the whole block: the store window only narrows the other models
+    if (win && !(desc->model == HK_MODEL_GAIN_OFFSET && desc->has_r2_thresh))
+        job.out_row0 = win[0], job.out_rows = win[1] - win[0], job.out_col0 = win[2], job.out_cols = win[3] - win[2];
     FitPending local;
     FitPending& p = defer ? *defer : local;
     hk::FitArgs& a = p.a;
-    memset(&a, 0, sizeof(a));
-    a.src = d_src, a.ref = d_ref, a.gain = d_gain, a.offset = d_off, a.r2 = d_r2, a.corr = d_corr;
-    a.norm = blk ? d_norm : nullptr;
-    a.fail_count = d_fail;
-    a.height = height, a.width = width, a.stride = stride, a.band_stride = 0, a.n_bands = 1;
-    fill_args(a, desc, ctx->xcd_remap);
-    fill_grid(a, 0);
-    // the in-painting branch needs the parameters of the whole block: the store window only narrows the other models
-    if (win && !a.has_thresh) a.out_y0 = win[0], a.out_y1 = win[1], a.out_x0 = win[2], a.out_x1 = win[3];
+    int rc = job_fit_args(a, ctx, desc, job);
+    if (rc) return rc;
     p.scratch_params = false;
     if (a.has_thresh && desc->model == HK_MODEL_GAIN_OFFSET && ctx->expect_r2_failures.load()) {
         // what the in-painting reads -- offsets and source flags -- into the slot's scratch right away (layout of
         // inpaint_band): no second "first pass".  With the caller's own offset plane only the flags are scratch.
-        int rc = ensure_inpaint_scratch(sl, plane, height, stride);
+        rc = ensure_inpaint_scratch(sl, plane, height, stride);
         if (rc) return rc;
         char* aux = static_cast<char*>(sl.aux);
         a.flag = hk::inpaint_flag_plane(aux + plane, height, stride);
@@ -1105,10 +1159,8 @@ int fit_on_device(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, const double* 
             p.scratch_params = !d_gain && !d_r2;
         }
     }
-    {
-        const int lrc = launch_fit(ctx, sl, a, desc, r2);
-        if (lrc) return lrc;
-    }
+    rc = launch_fit(ctx, sl, a, desc, r2);
+    if (rc) return rc;
     p.active = a.has_thresh != 0;
     if (defer || !p.active) return HK_OK;
 
@@ -1163,27 +1215,25 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
     const bool want_norm = blk || norm_only;
 
-    // bump allocation inside the stream's device slab (everything 256-byte aligned)
-    size_t total = 0;
-    auto take = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
-    const size_t o_src = take(plane), o_ref = take(plane);
+    SlabLayout L;
+    const size_t o_src = L.take(plane), o_ref = L.take(plane);
     size_t o_gain = 0, o_off = 0, o_r2 = 0, o_corr = 0, o_raw_s = 0, o_raw_r = 0, o_raw_o = 0;
     if (!norm_only) {
         if (params_out) {
-            o_gain = take(plane), o_off = take(plane);
-            if (n_param_bands == 3) o_r2 = take(plane);
+            o_gain = L.take(plane), o_off = L.take(plane);
+            if (n_param_bands == 3) o_r2 = L.take(plane);
         }
-        if (corr_out) o_corr = take(plane);
-        if (corr_out && out_cast) o_raw_o = take((size_t)stride * height * hk::dtype_size(odt));
+        if (corr_out) o_corr = L.take(plane);
+        if (corr_out && out_cast) o_raw_o = L.take((size_t)stride * height * hk::dtype_size(odt));
     }
-    if (sdt) o_raw_s = take((size_t)stride * height * hk::dtype_size(sdt));
-    if (rdt) o_raw_r = take((size_t)stride * height * hk::dtype_size(rdt));
-    const size_t o_aux = take(256);
-    const size_t o_ws = want_norm ? take(hk::norm_workspace_bytes(1, height, width)) : 0;
+    if (sdt) o_raw_s = L.take((size_t)stride * height * hk::dtype_size(sdt));
+    if (rdt) o_raw_r = L.take((size_t)stride * height * hk::dtype_size(rdt));
+    const size_t o_aux = L.take(256);
+    const size_t o_ws = want_norm ? L.take(hk::norm_workspace_bytes(1, height, width)) : 0;
 
     SlotLease lease(ctx);
     Slot& sl = lease.slot();
-    rc = ensure_dev(sl, total);
+    rc = ensure_dev(sl, L.total);
     if (rc) return rc;
     char* base = static_cast<char*>(sl.dev);
     float* d_src = reinterpret_cast<float*>(base + o_src);
@@ -1196,26 +1246,12 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
     unsigned long long* d_fail = reinterpret_cast<unsigned long long*>(base + o_aux + 64);
     void* d_ws = base + o_ws;
 
-    // stage in: float32 planes directly, other dtypes through a raw plane + on-device conversion
-    auto stage_in = [&](const void* host, int64_t hstride, int dt, float* dplane, size_t o_raw) -> int {
-        const size_t es = hk::dtype_size(dt);
-        void* dst = dt ? static_cast<void*>(base + o_raw) : static_cast<void*>(dplane);
-        const int src_rc = stage_h2d(sl, dst, stride * es, host, hstride * es, (size_t)width * es, height);
-        if (src_rc) return src_rc;
-        if (dt) HK_HIP(hk::launch_cast_in(dt, dst, stride, dplane, stride, height, width, sl.stream));
-        return HK_OK;
-    };
-    rc = stage_in(src, src_stride, sdt, d_src, o_raw_s);
+    rc = stage_in(sl, src, src_stride, sdt, d_src, base + o_raw_s, stride, height, width);
     if (rc) return rc;
-    rc = stage_in(ref, ref_stride, rdt, d_ref, o_raw_r);
+    rc = stage_in(sl, ref, ref_stride, rdt, d_ref, base + o_raw_r, stride, height, width);
     if (rc) return rc;
     if (norm_only) {
-        hk::NormArgs na;
-        na.src = d_src, na.ref = d_ref, na.height = height, na.width = width, na.stride = stride;
-        na.band_stride = 0, na.n_bands = 1;
-        na.src_nd_mode = desc->src_nodata_mode, na.ref_nd_mode = desc->ref_nodata_mode;
-        na.src_nodata = desc->src_nodata, na.ref_nodata = desc->ref_nodata;
-        HK_HIP(hk::launch_block_norm(na, d_ws, d_norm, sl.stream));
+        HK_HIP(hk::launch_block_norm(norm_args(desc, d_src, d_ref, height, width, stride), d_ws, d_norm, sl.stream));
         HK_HIP(hipMemcpyAsync(sl.pin<double>(Slot::PIN_NORM), d_norm, 2 * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
         if ((rc = stage_finish(sl))) return rc;
         if (norm_out) memcpy(norm_out, sl.pin<double>(Slot::PIN_NORM), 2 * sizeof(double));
@@ -1247,8 +1283,7 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
     };
 
     // The fit, its outputs and its r2-mask counter are queued back to back and the stream is synchronised ONCE; only
-    // when pixels failed the mask (or the certificate-only build asks for its re-run) do the in-painting passes follow,
-    // and the outputs are copied again behind them.
+    // when pixels failed the mask do the in-painting passes follow, and the outputs are copied again behind them.
     FitPending pending;
     const int kwin[4] = {wr0, wr0 + wrows, wc0 / hk::PX * hk::PX, width};  // rows exactly, columns from the window's first quad
     rc = fit_on_device(ctx, sl, desc, norm_in, d_src, d_ref, height, width, stride, d_gain, d_off, d_r2, d_corr, d_norm,
@@ -1274,7 +1309,7 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
             if ((rc = stage_out())) return rc;
             HK_HIP(hipMemcpyAsync(sl.fail_host, d_fail, sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
             if ((rc = stage_finish(sl))) return rc;
-            n_fail = *sl.fail_host;  // (the in-painting passes do not count; a re-run of the complete build does)
+            n_fail = *sl.fail_host;  // (the in-painting passes do not count)
         }
     }
     if (r2_fail_count) *r2_fail_count = n_fail;
@@ -1328,10 +1363,16 @@ int hk_ctx_create(int device_id, int n_streams, hk_ctx** out) {
     if (!ctx) return fail(HK_ERR_NOMEM, "out of host memory");
     ctx->device = device_id;
     ctx->slots.resize(n_streams);
-    const char* remap = getenv("HK_XCD_REMAP");
-    // runs of this many consecutive units (neighbouring strips) per XCD, 0 = plain round-robin (hk_fit_kernel.h); 16 measured
-    // best across models on MI355X (gain 5x5: -12 %, gain-offset without the r2 mask: -4 %, VALU-bound variants: -1 %)
-    ctx->xcd_remap = remap ? std::min(std::max(atoi(remap), 0), 256) : 16;
+    {
+        auto env = [](const char* name) { const char* e = getenv(name); return e ? std::optional<int>(atoi(e)) : std::nullopt; };
+        LaunchPolicy& lp = ctx->launch;
+        if (const auto remap = env("HK_XCD_REMAP")) lp.xcd_remap = std::min(std::max(*remap, 0), 256);
+        lp.force_general = env("HK_FORCE_GENERAL").value_or(0);
+        lp.use_ring = env("HK_USE_RING");
+        lp.wave_slots = env("HK_WAVE_SLOTS").value_or(lp.wave_slots);
+        lp.seg_big = env("HK_SEG_BIG");
+        lp.seg_tail = env("HK_SEG_TAIL");
+    }
     for (auto& s : ctx->slots) {
         hipError_t e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
         if (e != hipSuccess) {
@@ -1419,15 +1460,17 @@ int hk_apply(hk_ctx* ctx, const float* src, int64_t src_stride, const float* par
     HK_ENTER(ctx);
     const int64_t stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
     const size_t plane = (size_t)stride * height * sizeof(float);
+    SlabLayout L;
+    const size_t o_src = L.take(plane), o_gain = L.take(plane), o_off = L.take(plane), o_out = L.take(plane);
     SlotLease lease(ctx);
     Slot& sl = lease.slot();
-    int rc = ensure_dev(sl, 4 * plane);
+    int rc = ensure_dev(sl, L.total);
     if (rc) return rc;
     char* base = static_cast<char*>(sl.dev);
-    float* d_src = reinterpret_cast<float*>(base);
-    float* d_gain = reinterpret_cast<float*>(base + plane);
-    float* d_off = reinterpret_cast<float*>(base + 2 * plane);
-    float* d_out = reinterpret_cast<float*>(base + 3 * plane);
+    float* d_src = reinterpret_cast<float*>(base + o_src);
+    float* d_gain = reinterpret_cast<float*>(base + o_gain);
+    float* d_off = reinterpret_cast<float*>(base + o_off);
+    float* d_out = reinterpret_cast<float*>(base + o_out);
     const size_t wbytes = (size_t)width * sizeof(float);
     if ((rc = stage_h2d(sl, d_src, stride * 4, src, src_stride * 4, wbytes, height))) return rc;
     if ((rc = stage_h2d(sl, d_gain, stride * 4, params, wbytes, wbytes, height))) return rc;
@@ -1463,30 +1506,29 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     const int64_t ss = (src_width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;  // source-grid row stride
     const int64_t rs = (ref_width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;  // reference-grid row stride
     const size_t splane = (size_t)ss * src_height * 4, rplane = (size_t)rs * ref_height * 4;
-    size_t total = 0;
-    auto take = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
-    const size_t o_src = take(splane), o_ref = take(rplane), o_ds = take(rplane);
-    const size_t o_gain = take(rplane), o_off = take(rplane), o_r2 = r2 ? take(rplane) : 0;
+    SlabLayout L;
+    const size_t o_src = L.take(splane), o_ref = L.take(rplane), o_ds = L.take(rplane);
+    const size_t o_gain = L.take(rplane), o_off = L.take(rplane), o_r2 = r2 ? L.take(rplane) : 0;
     // bilinear / cubic_spline parameters are up-sampled inside the apply kernel (no full-resolution parameter planes)
     const bool fused_up = (space->up_resampling == 1 || space->up_resampling == 3) && ref_width >= 4 &&
                           space->up[0] <= 1.0 + 1e-9 && space->up[2] <= 1.0 + 1e-9 &&
                           (long long)ref_height * rs < 0x7fffffffLL;
-    const size_t o_gus = fused_up ? 0 : take(splane), o_ous = fused_up ? 0 : take(splane), o_corr = take(splane);
-    const size_t o_rowtab = fused_up ? take(hk::upsample_apply_workspace_bytes(src_height)) : 0;
-    const size_t o_vs = space->mask_partial ? take(splane) : 0, o_cov = space->mask_partial ? take(rplane) : 0;
-    const size_t o_mk = space->mask_partial ? take((size_t)rs * ref_height) : 0;
-    const size_t o_mkf = space->mask_partial ? take(rplane) : 0, o_keep = space->mask_partial ? take(splane) : 0;
-    const size_t o_cnt = space->mask_partial ? take((size_t)rs * ref_height * 2) : 0;
-    const size_t o_raw_s = sdt ? take((size_t)ss * src_height * hk::dtype_size(sdt)) : 0;
-    const size_t o_raw_r = rdt ? take((size_t)rs * ref_height * hk::dtype_size(rdt)) : 0;
-    const size_t o_raw_o = out_cast ? take((size_t)ss * src_height * hk::dtype_size(odt)) : 0;
-    const size_t o_aux = take(256);
+    const size_t o_gus = fused_up ? 0 : L.take(splane), o_ous = fused_up ? 0 : L.take(splane), o_corr = L.take(splane);
+    const size_t o_rowtab = fused_up ? L.take(hk::upsample_apply_workspace_bytes(src_height)) : 0;
+    const size_t o_vs = space->mask_partial ? L.take(splane) : 0, o_cov = space->mask_partial ? L.take(rplane) : 0;
+    const size_t o_mk = space->mask_partial ? L.take((size_t)rs * ref_height) : 0;
+    const size_t o_mkf = space->mask_partial ? L.take(rplane) : 0, o_keep = space->mask_partial ? L.take(splane) : 0;
+    const size_t o_cnt = space->mask_partial ? L.take((size_t)rs * ref_height * 2) : 0;
+    const size_t o_raw_s = sdt ? L.take((size_t)ss * src_height * hk::dtype_size(sdt)) : 0;
+    const size_t o_raw_r = rdt ? L.take((size_t)rs * ref_height * hk::dtype_size(rdt)) : 0;
+    const size_t o_raw_o = out_cast ? L.take((size_t)ss * src_height * hk::dtype_size(odt)) : 0;
+    const size_t o_aux = L.take(256);
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
-    const size_t o_ws = blk ? take(hk::norm_workspace_bytes(1, ref_height, ref_width)) : 0;
+    const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, ref_height, ref_width)) : 0;
 
     SlotLease lease(ctx);
     Slot& sl = lease.slot();
-    rc = ensure_dev(sl, total);
+    rc = ensure_dev(sl, L.total);
     if (rc) return rc;
     char* base = static_cast<char*>(sl.dev);
     auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
@@ -1496,17 +1538,8 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     unsigned long long* d_fail = reinterpret_cast<unsigned long long*>(base + o_aux + 64);
     const float nan = std::nanf("");
 
-    auto stage_in = [&](const void* host, int64_t hstride, int dt, float* dplane, size_t o_raw, int64_t dstride, int h,
-                        int w) -> int {
-        const size_t es = hk::dtype_size(dt);
-        void* dst = dt ? static_cast<void*>(base + o_raw) : static_cast<void*>(dplane);
-        const int src_rc = stage_h2d(sl, dst, dstride * es, host, hstride * es, (size_t)w * es, h);
-        if (src_rc) return src_rc;
-        if (dt) HK_HIP(hk::launch_cast_in(dt, dst, dstride, dplane, dstride, h, w, sl.stream));
-        return HK_OK;
-    };
-    if ((rc = stage_in(src, src_stride, sdt, d_src, o_raw_s, ss, src_height, src_width))) return rc;
-    if ((rc = stage_in(ref, ref_stride, rdt, d_ref, o_raw_r, rs, ref_height, ref_width))) return rc;
+    if ((rc = stage_in(sl, src, src_stride, sdt, d_src, base + o_raw_s, ss, src_height, src_width))) return rc;
+    if ((rc = stage_in(sl, ref, ref_stride, rdt, d_ref, base + o_raw_r, rs, ref_height, ref_width))) return rc;
 
     // RefSpaceModel.fit (:476-482): source -> reference grid (nodata nan), then the base-class fit there
     HK_HIP(hk::launch_resample(space->down_resampling, d_src, ss, 0, src_height, src_width, 1, desc->src_nodata_mode,
@@ -1533,10 +1566,9 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
         HK_HIP(hk::launch_resample(5, F(o_vs), ss, 0, src_height, src_width, 1, HK_NODATA_NONE, 0.f, space->down[0],
                                    space->down[1], space->down[2], space->down[3], F(o_cov), rs, 0, ref_height, ref_width,
                                    0.f, sl.stream));
-        // parameters sit in consecutive planes only by construction of the bump allocator above (gain, offset)
-        if (o_off != o_gain + ((rplane + 255) / 256 * 256)) return fail(HK_ERR_HIP, "internal: parameter planes not adjacent");
         unsigned char* d_mk = reinterpret_cast<unsigned char*>(base + o_mk);
-        HK_HIP(hk::launch_partial_mask(F(o_cov), 3, 0.f, d_gain, 2, (long long)((rplane + 255) / 256 * 256 / 4), nullptr,
+        // the parameters as two bands: gain, and offset one band stride further on
+        HK_HIP(hk::launch_partial_mask(F(o_cov), 3, 0.f, d_gain, 2, (long long)(o_off - o_gain) / 4, nullptr,
                                        ref_height, ref_width, rs, desc->kh, desc->kw,
                                        reinterpret_cast<unsigned short*>(base + o_cnt), nullptr, nullptr, d_mk, sl.stream));
         HK_HIP(hk::launch_cast_in(1, d_mk, rs, F(o_mkf), rs, ref_height, ref_width, sl.stream));
@@ -1618,14 +1650,13 @@ int hk_partial_mask(hk_ctx* ctx, const float* in, int64_t in_stride, int32_t in_
     HK_ENTER(ctx);
     const int64_t stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
     const size_t plane = (size_t)stride * height * sizeof(float);
-    size_t total = 0;
-    auto take = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
-    const size_t o_in = take(plane), o_par = take(plane * n_param_bands), o_src = src ? take(plane) : 0;
-    const size_t o_pout = params_out ? take(plane * n_param_bands) : 0, o_corr = corr_out ? take(plane) : 0;
-    const size_t o_mask = mask_out ? take((size_t)stride * height) : 0, o_cnt = take((size_t)stride * height * 2);
+    SlabLayout L;
+    const size_t o_in = L.take(plane), o_par = L.take(plane * n_param_bands), o_src = src ? L.take(plane) : 0;
+    const size_t o_pout = params_out ? L.take(plane * n_param_bands) : 0, o_corr = corr_out ? L.take(plane) : 0;
+    const size_t o_mask = mask_out ? L.take((size_t)stride * height) : 0, o_cnt = L.take((size_t)stride * height * 2);
     SlotLease lease(ctx);
     Slot& sl = lease.slot();
-    int rc = ensure_dev(sl, total);
+    int rc = ensure_dev(sl, L.total);
     if (rc) return rc;
     char* base = static_cast<char*>(sl.dev);
     float* d_in = reinterpret_cast<float*>(base + o_in);
@@ -1796,14 +1827,6 @@ static int check_job(hk_ctx* ctx, const hk_dev_job* job, bool allow_no_rows = fa
     return HK_OK;
 }
 
-// narrow the kernel's store window to the job's (the halo crop of a block processed in place inside a larger raster)
-static void apply_job_window(hk::FitArgs& a, const hk_dev_job* job) {
-    if (job->out_rows || job->out_cols) {
-        a.out_y0 = job->out_row0, a.out_y1 = job->out_row0 + job->out_rows;
-        a.out_x0 = job->out_col0, a.out_x1 = job->out_col0 + job->out_cols;
-    }
-}
-
 int hk_fit_apply_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_job* job) {
     int rc = validate_desc(desc);
     if (rc) return rc;
@@ -1813,18 +1836,7 @@ int hk_fit_apply_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_job* job
     if (desc->model == HK_MODEL_GAIN_BLK_OFFSET && !job->norm) return fail(HK_ERR_ARG, "gain-blk-offset needs job->norm");
     HK_ENTER(ctx);
     hk::FitArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = job->src, a.ref = job->ref, a.gain = job->gain, a.offset = job->offset, a.r2 = job->r2, a.corr = job->corr;
-    a.norm = job->norm;
-    a.fail_count = reinterpret_cast<unsigned long long*>(job->fail_count);
-    a.height = job->height, a.width = job->width, a.stride = job->stride, a.band_stride = job->band_stride;
-    a.n_bands = job->n_bands;
-    fill_args(a, desc, ctx->xcd_remap);
-    fill_grid(a, job->seg_rows);
-    apply_job_window(a, job);
-    if ((job->out_rows || job->out_cols) && a.has_thresh)
-        return fail(HK_ERR_UNSUPPORTED, "a store window is not supported together with r2_inpaint_thresh (the in-painting "
-                                        "needs the parameters of the whole block)");
+    if ((rc = job_fit_args(a, ctx, desc, *job))) return rc;
     if (desc->model == HK_MODEL_GAIN_OFFSET && a.has_thresh && job->scratch) {
         // a job that carries scratch gets the in-painting's inputs -- offsets + source flags, 5 bytes per pixel -- left there by
         // this pass (hk_inpaint_dev_counts starts from them): a caller that expects pixels to fail the r2 mask provides it
@@ -1902,13 +1914,7 @@ int hk_inpaint_dev_counts(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_job
         if (n_fail == 0) continue;
         const long long off = (long long)b * job->band_stride;
         hk::FitArgs a;
-        memset(&a, 0, sizeof(a));
-        a.src = job->src + off, a.ref = job->ref + off;
-        a.gain = job->gain ? job->gain + off : nullptr, a.offset = job->offset ? job->offset + off : nullptr;
-        a.r2 = job->r2 ? job->r2 + off : nullptr, a.corr = job->corr ? job->corr + off : nullptr;
-        a.height = job->height, a.width = job->width, a.stride = job->stride, a.band_stride = 0, a.n_bands = 1;
-        fill_args(a, desc, ctx->xcd_remap);
-        fill_grid(a, job->seg_rows);
+        if ((rc = job_fit_args(a, ctx, desc, *job, b))) return rc;
         std::unique_lock<std::mutex> lk(ctx->mu);  // the slot's scratch may be (re)allocated
         // offsets + source flags left by the pass that counted, which writes them whenever the job carries scratch (hk_fit_apply_dev)
         float* pre_off = nullptr;
@@ -1918,7 +1924,6 @@ int hk_inpaint_dev_counts(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_job
             pre_off = a.offset ? a.offset : job_scratch_offset(job) + off;
         }
         total += n_fail;
-        if (n_fail == 0) continue;
         rc = inpaint_band(sl, a, desc, r2, plane, n_fail, false, pre_off, pre_flag);
         if (rc) return rc;
     }
@@ -1953,16 +1958,7 @@ static int ensure_stream_ws(hk_ctx* ctx, Slot& sl, size_t need) {
     // device-resident jobs on one stream are issued by one caller at a time (stream order); the lock only protects
     // the (re)allocation against other streams' callers touching the context
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (!fits(sl.norm_ws_bytes, need)) {
-        if (sl.norm_ws) {
-            HK_HIP(hipStreamSynchronize(sl.stream));
-            HK_HIP(dev_free(sl.norm_ws));
-            sl.norm_ws = nullptr, sl.norm_ws_bytes = 0;
-        }
-        if (dev_malloc(&sl.norm_ws, need) != hipSuccess) return fail(HK_ERR_NOMEM, "hipMalloc(%zu) failed", need);
-        sl.norm_ws_bytes = need;
-    }
-    return HK_OK;
+    return grow_slot_buf(sl, sl.norm_ws, sl.norm_ws_bytes, need);
 }
 
 static int check_nodata_mode(int32_t mode) {
@@ -2004,16 +2000,17 @@ int hk_compare_sums(hk_ctx* ctx, const float* src, int64_t src_stride, int32_t s
     HK_ENTER(ctx);
     const int64_t stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
     const size_t plane = (size_t)stride * height * sizeof(float);
-    const size_t ws_bytes = hk::compare_workspace_bytes(1);
+    SlabLayout L;
+    const size_t o_src = L.take(plane), o_ref = L.take(plane), o_ws = L.take(hk::compare_workspace_bytes(1)), o_sums = L.take(256);
     SlotLease lease(ctx);
     Slot& sl = lease.slot();
-    rc = ensure_dev(sl, 2 * plane + ws_bytes + 256);
+    rc = ensure_dev(sl, L.total);
     if (rc) return rc;
     char* base = static_cast<char*>(sl.dev);
-    float* d_src = reinterpret_cast<float*>(base);
-    float* d_ref = reinterpret_cast<float*>(base + plane);
-    void* d_ws = base + 2 * plane;
-    double* d_sums = reinterpret_cast<double*>(base + 2 * plane + ws_bytes);
+    float* d_src = reinterpret_cast<float*>(base + o_src);
+    float* d_ref = reinterpret_cast<float*>(base + o_ref);
+    void* d_ws = base + o_ws;
+    double* d_sums = reinterpret_cast<double*>(base + o_sums);
     const size_t wbytes = (size_t)width * sizeof(float);
     if ((rc = stage_h2d(sl, d_src, stride * 4, src, src_stride * 4, wbytes, height))) return rc;
     if ((rc = stage_h2d(sl, d_ref, stride * 4, ref, ref_stride * 4, wbytes, height))) return rc;
@@ -2040,11 +2037,7 @@ int hk_block_norm_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_job* jo
     Slot& sl = ctx->slots[job->stream];
     rc = ensure_stream_ws(ctx, sl, hk::norm_workspace_bytes(job->n_bands, job->height, job->width));
     if (rc) return rc;
-    hk::NormArgs na;
-    na.src = job->src, na.ref = job->ref, na.height = job->height, na.width = job->width, na.stride = job->stride;
-    na.band_stride = job->band_stride, na.n_bands = job->n_bands;
-    na.src_nd_mode = desc->src_nodata_mode, na.ref_nd_mode = desc->ref_nodata_mode;
-    na.src_nodata = desc->src_nodata, na.ref_nodata = desc->ref_nodata;
+    const hk::NormArgs na = norm_args(desc, job->src, job->ref, job->height, job->width, job->stride, job->band_stride, job->n_bands);
     HK_HIP(hk::launch_block_norm(na, sl.norm_ws, norm_dev, sl.stream));
     return HK_OK;
 }
@@ -2126,13 +2119,9 @@ int hk_block_norm_batch_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_j
     void* tbl = nullptr;
     rc = upload_table(ctx, sl, planes.data(), planes.size() * sizeof(hk::NormPlane), &tbl);
     if (rc) return rc;
-    hk::NormArgs na;
+    hk::NormArgs na = norm_args(desc, nullptr, nullptr, max_h, max_w, 0, 0, (int)planes.size());
     na.planes = static_cast<const hk::NormPlane*>(tbl);
-    na.src = na.ref = nullptr, na.height = max_h, na.width = max_w, na.stride = 0, na.band_stride = 0;
-    na.n_bands = (int)planes.size();
     na.grid_waves = max_waves;
-    na.src_nd_mode = desc->src_nodata_mode, na.ref_nd_mode = desc->ref_nodata_mode;
-    na.src_nodata = desc->src_nodata, na.ref_nodata = desc->ref_nodata;
     HK_HIP(hk::launch_block_norm(na, sl.norm_ws, norm_dev, sl.stream));
     return HK_OK;
 }
@@ -2160,76 +2149,47 @@ int hk_fit_apply_batch_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_jo
     }
     HK_ENTER(ctx);
     Slot& sl = ctx->slots[jobs[0].stream];
-    const int wpb = hk::fit_lockstep_waves();
-    std::vector<hk::FitJob> table((size_t)n_jobs);
-    hk::FitArgs a0;  // the launch's argument block: everything the jobs share, and job 0's own fields (which the table overrides)
-    memset(&a0, 0, sizeof(a0));
-    long long groups[2] = {0, 0}, total_px = 0;
-    bool pad_by_size = false;
-    // fill_grid()'s two segment heights, applied to the LAUNCH: the jobs run in order, so the jobs whose units make up the last
-    // ~1.25 generations of resident waves get short segments (they level the end of the launch) and all earlier ones long
-    // segments (half the priming rows).  Results do not depend on the segment height (exact running sums).
-    std::vector<int> seg_of((size_t)n_jobs, 0);
-    {
-        long long units = 0;
-        std::vector<long long> first((size_t)n_jobs + 1, 0);
-        int uniform = 0;
-        bool any_explicit = false;
+    std::vector<hk::FitArgs> args((size_t)n_jobs);
+    std::vector<long long> first((size_t)n_jobs + 1, 0);  // first unit of each job in the launch
+    bool any_explicit = false;
+    for (int32_t j = 0; j < n_jobs; ++j) {
+        if (desc->model == HK_MODEL_GAIN_BLK_OFFSET && !jobs[j].norm) return fail(HK_ERR_ARG, "gain-blk-offset needs job->norm (job %d)", j);
+        hk::FitArgs& a = args[(size_t)j];
+        if ((rc = job_fit_args(a, ctx, desc, jobs[j]))) return rc;
+        any_explicit |= jobs[j].seg_rows > 0 || a.seg_rows_pref > 0;
+        first[(size_t)j + 1] = first[(size_t)j] + (long long)a.n_strips * a.n_segs * a.n_bands;
+    }
+    // seg_policy() applied to the LAUNCH: the jobs run in order, so the jobs whose units make up its tail get short segments
+    // (they level the end of the launch) and all earlier ones long segments.  Results do not depend on the segment height
+    // (exact running sums).
+    const SegPolicy seg = seg_policy(desc->kh, ctx->launch);
+    const long long units = first[(size_t)n_jobs];
+    if (!any_explicit && units >= seg.two_size_from) {
+        const long long tail_from = units - (long long)seg.tail_waves;
         for (int32_t j = 0; j < n_jobs; ++j) {
-            hk::FitArgs a;
-            memset(&a, 0, sizeof(a));
-            a.height = jobs[j].height, a.width = jobs[j].width, a.n_bands = jobs[j].n_bands;
-            fill_args(a, desc, ctx->xcd_remap);
-            fill_grid(a, jobs[j].seg_rows);
-            any_explicit |= jobs[j].seg_rows > 0 || a.seg_rows_pref > 0;
-            if (j == 0) uniform = 2 * a.rh + 1 <= 5 ? 64 : (2 * a.rh + 1 <= 9 ? 128 : 256);
-            first[(size_t)j] = units;
-            units += (long long)a.n_strips * a.n_segs * a.n_bands;
-        }
-        first[(size_t)n_jobs] = units;
-        const long long slots = (long long)env_int("HK_WAVE_SLOTS", 256 * 12);
-        if (!any_explicit && units >= 6 * slots) {
-            const long long tail_from = units - (long long)(1.25 * (double)slots);
-            for (int32_t j = 0; j < n_jobs; ++j) seg_of[(size_t)j] = first[(size_t)j + 1] <= tail_from ? 2 * uniform : uniform / 2;
+            const int rows = first[(size_t)j + 1] <= tail_from ? seg.big : seg.tail;
+            if (rows > 0) fill_grid(args[(size_t)j], rows, ctx->launch);
         }
     }
+    // (only models without the r2 mask have builds with the job-table look-up: no certificate, no in-painting inputs here)
+    const int wpb = hk::fit_lockstep_waves();
+    std::vector<hk::FitJob> table((size_t)n_jobs);
+    long long groups[2] = {0, 0}, total_px = 0;
     for (int32_t j = 0; j < n_jobs; ++j) {
-        const hk_dev_job* job = &jobs[j];
-        if (desc->model == HK_MODEL_GAIN_BLK_OFFSET && !job->norm) return fail(HK_ERR_ARG, "gain-blk-offset needs job->norm (job %d)", j);
-        hk::FitArgs a;
-        memset(&a, 0, sizeof(a));
-        a.src = job->src, a.ref = job->ref, a.gain = job->gain, a.offset = job->offset, a.r2 = job->r2, a.corr = job->corr;
-        a.norm = job->norm;
-        a.fail_count = reinterpret_cast<unsigned long long*>(job->fail_count);
-        a.height = job->height, a.width = job->width, a.stride = job->stride, a.band_stride = job->band_stride;
-        a.n_bands = job->n_bands;
-        fill_args(a, desc, ctx->xcd_remap);
-        if (j == 0) pad_by_size = a.lds_pad < 0;  // fill_grid() would decide by the job's size: the launch's counts (below)
-        fill_grid(a, seg_of[(size_t)j] > 0 ? seg_of[(size_t)j] : job->seg_rows);
-        apply_job_window(a, job);
-        if ((job->out_rows || job->out_cols) && a.has_thresh)
-            return fail(HK_ERR_UNSUPPORTED, "a store window is not supported together with r2_inpaint_thresh (the in-painting "
-                                            "needs the parameters of the whole block)");
-        // (only models without the r2 mask have builds with the job-table look-up: no certificate, no in-painting inputs here)
+        const hk::FitArgs& a = args[(size_t)j];
         hk::FitJob& e = table[(size_t)j];
-        memset(&e, 0, sizeof(e));
-        e.src = a.src, e.ref = a.ref, e.gain = a.gain, e.offset = a.offset, e.r2 = a.r2, e.corr = a.corr, e.norm = a.norm;
-        e.fail_count = a.fail_count, e.flag = a.flag;
-        e.stride = a.stride, e.band_stride = a.band_stride, e.height = a.height, e.width = a.width, e.n_bands = a.n_bands;
-        e.seg_rows = a.seg_rows, e.n_strips = a.n_strips, e.n_segs = a.n_segs, e.seg_rows_tail = a.seg_rows_tail;
-        e.n_segs_big = a.n_segs_big;
-        e.out_y0 = a.out_y0, e.out_y1 = a.out_y1, e.out_x0 = a.out_x0, e.out_x1 = a.out_x1;
+        hk::fit_job_of(e, a);
         e.first_group[0] = (int)groups[0], e.first_group[1] = (int)groups[1];
         groups[0] += (long long)a.n_strips * a.n_segs * a.n_bands;
         groups[1] += (long long)((a.n_strips + wpb - 1) / wpb) * a.n_segs * a.n_bands;
         total_px += (long long)a.height * a.width * a.n_bands;
         if (groups[0] > 0x7fffff00ll) return fail(HK_ERR_ARG, "the batch has too many wave units for one launch");
-        if (j == 0) a0 = a;
     }
+    hk::FitArgs a0 = args[0];  // the launch's argument block: everything the jobs share, and job 0's own fields (which the table overrides)
     a0.cert_only = 0;
     a0.n_jobs = n_jobs;
     a0.batch_groups[0] = (int)groups[0], a0.batch_groups[1] = (int)groups[1];
-    if (pad_by_size) a0.lds_pad = total_px >= (128ll << 20) ? 4096 : 0;  // fill_grid()'s occupancy policy, for the whole launch
+    if (lds_pad_by_size(desc, ctx->launch)) a0.lds_pad = lds_pad_of(total_px);  // by the size of the whole launch
     void* tbl = nullptr;
     rc = upload_table(ctx, sl, table.data(), table.size() * sizeof(hk::FitJob), &tbl);
     if (rc) return rc;
@@ -2288,11 +2248,7 @@ int hk_block_norm_split_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_j
     // the phases of one block share the stream's workspace: phase 0 sizes it, the others find it as it was left
     rc = ensure_stream_ws(ctx, sl, hk::norm_workspace_bytes(job->n_bands, job->height > 0 ? job->height : 1, job->width));
     if (rc) return rc;
-    hk::NormArgs na;
-    na.src = job->src, na.ref = job->ref, na.height = job->height, na.width = job->width, na.stride = job->stride;
-    na.band_stride = job->band_stride, na.n_bands = job->n_bands;
-    na.src_nd_mode = desc->src_nodata_mode, na.ref_nd_mode = desc->ref_nodata_mode;
-    na.src_nodata = desc->src_nodata, na.ref_nodata = desc->ref_nodata;
+    const hk::NormArgs na = norm_args(desc, job->src, job->ref, job->height, job->width, job->stride, job->band_stride, job->n_bands);
     HK_HIP(hk::launch_block_norm_split(na, sl.norm_ws, xchg_dev, phase, norm_dev, sl.stream));
     return HK_OK;
 }
@@ -2365,21 +2321,9 @@ int hk_block_norm_split_comm_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_
     rc = ensure_stream_ws(ctx, sl, hk::norm_workspace_bytes(job->n_bands, job->height > 0 ? job->height : 1, job->width));
     if (rc) return rc;
     const size_t n = hk::norm_split_exchange_doubles(job->n_bands);
-    if (sl.comm_xchg_doubles < n) {
-        if (sl.comm_xchg) {
-            HK_HIP(hipStreamSynchronize(sl.stream));  // an earlier sequence on this stream may still use it
-            HK_HIP(dev_free(sl.comm_xchg));
-            sl.comm_xchg = nullptr, sl.comm_xchg_doubles = 0;
-        }
-        if (dev_malloc(reinterpret_cast<void**>(&sl.comm_xchg), n * sizeof(double)) != hipSuccess)
-            return fail(HK_ERR_NOMEM, "hipMalloc(%zu) failed", n * sizeof(double));
-        sl.comm_xchg_doubles = n;
-    }
-    hk::NormArgs na;
-    na.src = job->src, na.ref = job->ref, na.height = job->height, na.width = job->width, na.stride = job->stride;
-    na.band_stride = job->band_stride, na.n_bands = job->n_bands;
-    na.src_nd_mode = desc->src_nodata_mode, na.ref_nd_mode = desc->ref_nodata_mode;
-    na.src_nodata = desc->src_nodata, na.ref_nodata = desc->ref_nodata;
+    rc = grow_slot_buf(sl, sl.comm_xchg, sl.comm_xchg_bytes, n * sizeof(double));
+    if (rc) return rc;
+    const hk::NormArgs na = norm_args(desc, job->src, job->ref, job->height, job->width, job->stride, job->band_stride, job->n_bands);
     // six phases on the slab, five all-reduces between them, all queued on the job's stream: no host synchronisation
     for (int phase = 0; phase < 6; ++phase) {
         HK_HIP(hk::launch_block_norm_split(na, sl.norm_ws, sl.comm_xchg, phase, norm_dev, sl.stream));

@@ -1923,9 +1923,10 @@ static hipError_t launch_build(const FitArgs& a, hipStream_t stream) {
 
 // gain-offset with the r2 mask exists in two builds.  The FULL one carries the reference's R2 expression inline for the
 // wave-rows the float32 certificate cannot settle (and for R2 output): 154 VGPRs, 3 waves per SIMD.  The CERTIFICATE-ONLY
-// one (a.cert_only, chosen by the host when no R2 plane is written and the previous launch had no failures) has nothing
-// but the certificate: 128 VGPRs and no LDS table = 4 waves per SIMD (-5 % on clean rasters); a wave-row it cannot settle
-// sets FIT_RETRY_BIT in the band's fail counter and the host re-runs the band with the full build.
+// one (a.cert_only, chosen by the host when the failures are counted and neither R2, gain nor the in-painting's flags are
+// written) has nothing but the certificate: 128 VGPRs and no LDS table = 4 waves per SIMD (-5 % on clean rasters); a
+// wave-row it cannot settle is marked in a.open_rows, and the host's LIST launch of the full build (a.list_mode) follows
+// on the same stream and does those rows (hk_api.hip launch_fit).
 template <int MODEL, bool R2, int RW, bool DENSE, int RING>
 static hipError_t launch_one(const FitArgs& a, hipStream_t stream) {
     if constexpr (MODEL == 2 && R2 && (RING == 1 || RING == 2)) {

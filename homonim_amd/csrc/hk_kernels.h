@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 namespace hk {
 
@@ -43,11 +44,6 @@ BuildRecord SiteRecord<Tag>::rec{Tag::name()};
 // "name\tlaunches\n" per record, '\0'-terminated; returns the bytes needed (incl. the terminator) whatever `len` is
 size_t ledger_text(char* buf, size_t len, bool reset);
 
-// Device-side argument block of the fused fit(+apply) kernel.  One wave = one (band, row-segment, column-strip) unit.
-// Set in a band's r2-failure counter by the certificate-only build: the count is void, run the band again with
-// cert_only = 0.  (Counts themselves are < 2^63.)
-constexpr unsigned long long FIT_RETRY_BIT = 1ull << 63;
-
 // One job of a BATCHED launch (FitArgs::jobs, device memory): many device-resident jobs -- the block positions of a mosaic, the
 // tiles of a tile list -- run as ONE kernel launch instead of one launch (and one launch tail) each.  A workgroup finds its job
 // by a binary search over `first_group` and takes the job's planes, shape and unit grid from here instead of from FitArgs.
@@ -70,6 +66,7 @@ struct FitJob {
 };
 static_assert(sizeof(FitJob) % 8 == 0, "FitJob entries are read with scalar loads");
 
+// Device-side argument block of the fused fit(+apply) kernel.  One wave = one (band, row-segment, column-strip) unit.
 struct FitArgs {
     const FitJob* jobs;     // batched launch: n_jobs entries (device), else NULL -- the fields below then describe the one job
     int n_jobs;
@@ -104,7 +101,7 @@ struct FitArgs {
     float r2_thresh;
     int cert_only;          // gain-offset + r2 mask, no R2 plane, fail_count and open_rows set: run the CERTIFICATE build (launch_one),
                             // which settles a wave-row by the two-sided float32 certificate or marks it in `open_rows`
-    // Round 6: the wave-rows the certificate build cannot settle: one bit per (band, strip, row), 32 rows per word, word index
+    // The wave-rows the certificate build cannot settle: one bit per (band, strip, row), 32 rows per word, word index
     // (band * n_strips + strip) * ceil(height / 32) + row / 32 (zeroed before the certificate launch).
     // list_mode != 0: THIS launch is the list launch -- the complete build on a persistent grid over the runs of marked rows.
     unsigned* open_rows;
@@ -126,6 +123,18 @@ struct FitArgs {
     // out_x0 and out_x1 are multiples of PX (or out_x1 == width): whole quads are stored.
     int out_y0, out_y1, out_x0, out_x1;
 };
+
+// The batched launch's table entry of one job from the job's own argument block (fill_args + fill_grid done); first_group
+// is left to the caller
+inline void fit_job_of(FitJob& e, const FitArgs& a) {
+    memset(&e, 0, sizeof(e));
+    e.src = a.src, e.ref = a.ref, e.gain = a.gain, e.offset = a.offset, e.r2 = a.r2, e.corr = a.corr, e.norm = a.norm;
+    e.fail_count = a.fail_count, e.flag = a.flag;
+    e.stride = a.stride, e.band_stride = a.band_stride, e.height = a.height, e.width = a.width, e.n_bands = a.n_bands;
+    e.seg_rows = a.seg_rows, e.n_strips = a.n_strips, e.n_segs = a.n_segs, e.seg_rows_tail = a.seg_rows_tail;
+    e.n_segs_big = a.n_segs_big;
+    e.out_y0 = a.out_y0, e.out_y1 = a.out_y1, e.out_x0 = a.out_x0, e.out_x1 = a.out_x1;
+}
 
 // model: 0 gain, 1 gain-blk-offset, 2 gain-offset.  with_r2: compute the R2 quantity set.
 hipError_t launch_fit_apply(const FitArgs& a, int model, bool with_r2, hipStream_t stream);

@@ -18,6 +18,13 @@
  *                       hk_host_alloc / hk_host_register holds all of it; with this switch the library also asks the HIP runtime
  *                       about every page of every row of such an array before the copy is queued and fails the call
  *                       (HK_ERR_ARG) if one is not page-locked host memory.  The test-suite runs with it.
+ *
+ * Launch switches (environment, read by hk_ctx_create for that context; a context created before a change does not see it):
+ *   HK_XCD_REMAP=G      runs of G consecutive units per XCD (default 16, clamped to 0..256; 0 = plain round-robin).
+ *   HK_USE_RING=M       force ring mode M (0 / 1 / 2 / 3) of the fused kernel where the shape has a build of it (tests).
+ *   HK_FORCE_GENERAL=1  never take the dense (nodata None) builds (tests).
+ *   HK_WAVE_SLOTS, HK_SEG_BIG, HK_SEG_TAIL   resident waves of the device and the long / short row-segment heights of the
+ *                       two-size segment policy, of single jobs and batched launches: forced onto small rasters (tests).
  */
 #ifndef HOMONIM_HK_DEVTOOLS_H
 #define HOMONIM_HK_DEVTOOLS_H

@@ -18,6 +18,7 @@ import warnings
 import numpy as np
 import pytest
 
+from _launch_env import launch_context
 from homonim_amd import _hk
 from oracle import oracle_np as onp
 
@@ -161,7 +162,7 @@ def test_paired_builds_of_the_wide_kernels_vs_oracle(ctx, oc, model, find_r2, th
 @pytest.mark.oracle
 @pytest.mark.parametrize('ring', ['0', '1', '2', '3'])
 @pytest.mark.parametrize('model, find_r2, thresh, nodata', CONFIGS)
-def test_forced_ring_modes_of_every_width_vs_oracle(ctx, oc, model, find_r2, thresh, nodata, ring, monkeypatch):
+def test_forced_ring_modes_of_every_width_vs_oracle(ctx, oc, model, find_r2, thresh, nodata, ring):
     """ The ring modes a shape does not get by default (HK_USE_RING; the library ignores the switch where the mode has no build):
     full ring on tall kernels (one wave per workgroup: its LDS no longer fits four), centre ring on short ones, everything
     re-loaded from 9 wide, split ring from 7 rows -- every width, numeric nodata on the general builds. """
@@ -169,28 +170,26 @@ def test_forced_ring_modes_of_every_width_vs_oracle(ctx, oc, model, find_r2, thr
     src, ref = _pair(11, nodata, numeric)
     nd = nodata if numeric is None else numeric
     heights = {'0': (5, 17), '1': (3, 11, 17), '2': (1, 5, 65), '3': (7, 11, 15)}[ring]
-    monkeypatch.setenv('HK_USE_RING', ring)
-    with warnings.catch_warnings():
+    with warnings.catch_warnings(), launch_context(ctx, {'HK_USE_RING': ring}) as c:
         warnings.simplefilter('ignore')
         for kh in heights:
             for kw in WIDTHS:
                 if model == 'gain-offset' and kh * kw < 2:
                     continue
-                _check_shape(ctx, oc, model, find_r2, thresh, nd, (kh, kw), src, ref, f'ring {ring}: {model} r2={find_r2} thresh={thresh} nodata={nd} {kh}x{kw}')
+                _check_shape(c, oc, model, find_r2, thresh, nd, (kh, kw), src, ref, f'ring {ring}: {model} r2={find_r2} thresh={thresh} nodata={nd} {kh}x{kw}')
 
 
 @pytest.mark.oracle
 @pytest.mark.parametrize('model, find_r2, thresh', [('gain', False, None), ('gain', True, None), ('gain-offset', False, None),
                                                     ('gain-offset', True, None), ('gain-offset', False, 0.25), ('gain-offset', True, 0.25)])
-def test_general_builds_on_rasters_without_nodata_vs_oracle(ctx, oc, model, find_r2, thresh, monkeypatch):
+def test_general_builds_on_rasters_without_nodata_vs_oracle(ctx, oc, model, find_r2, thresh):
     """ HK_FORCE_GENERAL: the NaN-aware builds on rasters whose nodata is None (every row `clean`: their dense short cut all the way). """
     src, ref = _pair(13, None)
-    monkeypatch.setenv('HK_FORCE_GENERAL', '1')
-    with warnings.catch_warnings():
+    with warnings.catch_warnings(), launch_context(ctx, {'HK_FORCE_GENERAL': '1'}) as c:
         warnings.simplefilter('ignore')
         for kh in (3, 5, 9, 17):
             for kw in WIDTHS:
-                _check_shape(ctx, oc, model, find_r2, thresh, None, (kh, kw), src, ref, f'general: {model} r2={find_r2} thresh={thresh} {kh}x{kw}')
+                _check_shape(c, oc, model, find_r2, thresh, None, (kh, kw), src, ref, f'general: {model} r2={find_r2} thresh={thresh} {kh}x{kw}')
 
 
 @pytest.mark.oracle

@@ -12,6 +12,7 @@ from oracle import exact_window as ew
 
 pytestmark = pytest.mark.gpu
 
+from _launch_env import launch_context  # noqa: E402
 from homonim_amd import _hk  # noqa: E402
 
 H, W = 160, 600
@@ -143,13 +144,12 @@ VARIANTS = [('ring0', {'HK_USE_RING': '0'}), ('ring1', {'HK_USE_RING': '1'}), ('
 @pytest.mark.oracle
 @pytest.mark.parametrize('kind, kshape', [('bright-65535', (5, 5)), ('bright-1e4', (15, 15)), ('dn-saturated', (9, 11))])
 @pytest.mark.parametrize('variant', [v[0] for v in VARIANTS])
-def test_launch_variants_lie_in_the_enclosure(ctx, oc, kind, kshape, variant, monkeypatch):
+def test_launch_variants_lie_in_the_enclosure(ctx, oc, kind, kshape, variant):
     """ Ring modes, the NaN-aware builds on dense rasters and two segment policies on rasters tall enough for several row
     segments: the running sums restart elsewhere, the enclosure holds all the same. """
-    for k, v in dict(VARIANTS)[variant].items():
-        monkeypatch.setenv(k, v)
     src, ref = _pair(kind, (420, 300), None, seed=5)
-    _run_all_models(ctx, oc, f'{kind}/{variant}', kshape, None, src, ref, thresholds=(0.25,))
+    with launch_context(ctx, dict(VARIANTS)[variant]) as c:
+        _run_all_models(c, oc, f'{kind}/{variant}', kshape, None, src, ref, thresholds=(0.25,))
 
 
 def _dev_plane(c, arr, stride, d, name):

@@ -16,6 +16,7 @@ import warnings
 import numpy as np
 import pytest
 
+from _launch_env import launch_context
 from conftest import GOLDEN_CASES, assert_same_f32, case_id
 from homonim_amd import Affine, CRS, KernelModel, Model, RasterArray, RefSpaceModel, SrcSpaceModel, _hk
 from homonim_amd.enums import Resampling
@@ -216,7 +217,7 @@ def test_tall_kernels_vs_oracle(ctx, oc, model, find_r2, thresh, kernel_shape):
 
 @pytest.mark.oracle
 @pytest.mark.parametrize('seed', range(240))
-def test_randomized_configurations_vs_oracle(ctx, oc, seed, monkeypatch):
+def test_randomized_configurations_vs_oracle(ctx, oc, seed):
     """ A seeded sweep over the configuration space (model, odd kernel shape up to 17 x 15 -- seeds from 120: 17 to 63 rows by 17 to
     55 columns, the builds of kernels wider than 15 --, R2 output, threshold, the three nodata kinds on either raster, raster shape
     from one pixel to a few strips / segments, fused vs parameter output): every draw must reproduce the C oracle (= the reference's
@@ -237,11 +238,11 @@ def test_randomized_configurations_vs_oracle(ctx, oc, seed, monkeypatch):
     find_r2 = bool(rng.integers(2))
     thresh = [None, 0.25, 0.6][rng.integers(3)] if model == 'gain-offset' else None
     h, w = int(rng.integers(1, 420)), int(rng.integers(1, 700))
+    env = {}
     if seed >= 180:
         h, w = int(rng.integers(400, 1500)), int(rng.integers(200, 900))
-        monkeypatch.setenv('HK_WAVE_SLOTS', '4')
-        monkeypatch.setenv('HK_SEG_BIG', str(int(rng.choice([96, 160, 200, 300]))))
-        monkeypatch.setenv('HK_SEG_TAIL', str(int(rng.choice([8, 16, 40]))))
+        env = {'HK_WAVE_SLOTS': '4', 'HK_SEG_BIG': str(int(rng.choice([96, 160, 200, 300]))),
+               'HK_SEG_TAIL': str(int(rng.choice([8, 16, 40])))}
     src = rng.uniform(0.05, 1, (h, w)).astype(np.float32)
     ref = ((0.6 + rng.random()) * src + 0.1 * rng.random() + rng.normal(0, 0.02 + 0.2 * rng.random(), (h, w))).astype(np.float32)
     nodata = {}
@@ -261,12 +262,12 @@ def test_randomized_configurations_vs_oracle(ctx, oc, seed, monkeypatch):
                                                   norm_in)
     cfg = dict(model=model, kernel_shape=kshape, find_r2=find_r2, r2_inpaint_thresh=thresh, src_nodata=nodata['src'],
                ref_nodata=nodata['ref'])
-    with warnings.catch_warnings():
+    with warnings.catch_warnings(), launch_context(ctx, env) as c:
         warnings.simplefilter('ignore')
-        params, corr, _, n_fail = _fit_via_abi(ctx, cfg, src, ref, norm_in=norm_in)
+        params, corr, _, n_fail = _fit_via_abi(c, cfg, src, ref, norm_in=norm_in)
         desc = _hk.make_desc(model, kshape, find_r2, thresh, nodata['src'], nodata['ref'])
-        _, corr_fused, _, n_fail_fused = ctx.fit_apply(desc, src, ref, exp_params.shape[0], want_params=False, want_corr=True,
-                                                       norm_in=norm_in)
+        _, corr_fused, _, n_fail_fused = c.fit_apply(desc, src, ref, exp_params.shape[0], want_params=False, want_corr=True,
+                                                     norm_in=norm_in)
     what = f'{model} {kshape} r2={find_r2} thresh={thresh} {h}x{w} nodata={nodata}'
     if exp_params.shape[0] == 3 and kshape[0] * kshape[1] < 9:
         # R2 of a window of < 9 pixels is rounding noise wherever sstot = N*sum(r^2) - sum(r)^2 cancels (values like -1.8
@@ -535,17 +536,17 @@ def test_raster_fuse_uint8_output(ctx):
 ])
 @pytest.mark.oracle
 @pytest.mark.parametrize('shape', [(260, 1003), (131, 250), (64, 1024)])
-def test_dense_path_equals_general_path(ctx, model, kernel_shape, find_r2, thresh, shape, monkeypatch):
+def test_dense_path_equals_general_path(ctx, model, kernel_shape, find_r2, thresh, shape):
     """ nodata None on both rasters selects the DENSE kernels (geometric window count, no mask ring); results must be
     bit-identical to the general kernels and to the oracle -- ragged widths included. """
     import warnings
     src, ref = onp.synth_pair(*shape, seed=shape[1], nodata_variant='none')
     cfg = dict(model=model, kernel_shape=kernel_shape, find_r2=find_r2, r2_inpaint_thresh=thresh, src_nodata=None,
                ref_nodata=None)
-    monkeypatch.setenv('HK_FORCE_GENERAL', '1')
-    p_gen, c_gen, _, f_gen = _fit_via_abi(ctx, cfg, src, ref)
-    monkeypatch.setenv('HK_FORCE_GENERAL', '0')
-    p_den, c_den, _, f_den = _fit_via_abi(ctx, cfg, src, ref)
+    with launch_context(ctx, {'HK_FORCE_GENERAL': '1'}) as c:
+        p_gen, c_gen, _, f_gen = _fit_via_abi(c, cfg, src, ref)
+    with launch_context(ctx, {'HK_FORCE_GENERAL': '0'}) as c:
+        p_den, c_den, _, f_den = _fit_via_abi(c, cfg, src, ref)
     assert_same_f32(p_den, p_gen, 'params dense vs general')
     assert_same_f32(c_den, c_gen, 'corrected dense vs general')
     assert f_den == f_gen
@@ -735,7 +736,7 @@ def test_pinned_arrays_and_caller_outputs(ctx):
     ('gain', (1, 5), True, None, np.nan), ('gain-offset', (31, 31), False, None, np.nan),
 ])
 @pytest.mark.oracle
-def test_lds_ring_and_reload_modes_agree(ctx, model, kernel_shape, find_r2, thresh, nodata, monkeypatch):
+def test_lds_ring_and_reload_modes_agree(ctx, model, kernel_shape, find_r2, thresh, nodata):
     """ The leaving / centre rows come from a full LDS ring (mode 1, short kernels), from a centre-only LDS ring plus a
     re-loaded leaving row (mode 2, tall kernels) or are both re-loaded (mode 0); every mode must give the same bytes,
     whichever the default for the shape is. """
@@ -746,9 +747,8 @@ def test_lds_ring_and_reload_modes_agree(ctx, model, kernel_shape, find_r2, thre
     norm_in = onp.fit_block_norm(src, nodata, ref, nodata) if model == 'gain-blk-offset' else None
     out = {}
     for mode in ('1', '2', '0'):
-        monkeypatch.setenv('HK_USE_RING', mode)
-        out[mode] = _fit_via_abi(ctx, cfg, src, ref, norm_in=norm_in)
-    monkeypatch.delenv('HK_USE_RING')
+        with launch_context(ctx, {'HK_USE_RING': mode}) as c:
+            out[mode] = _fit_via_abi(c, cfg, src, ref, norm_in=norm_in)
     for mode in ('2', '0'):
         assert_same_f32(out['1'][0], out[mode][0], f'params ring mode 1 vs {mode}')
         assert_same_f32(out['1'][1], out[mode][1], f'corrected ring mode 1 vs {mode}')
@@ -764,7 +764,7 @@ def test_lds_ring_and_reload_modes_agree(ctx, model, kernel_shape, find_r2, thre
     ('gain', (3, 3), None, np.nan), ('gain-blk-offset', (5, 7), None, np.nan),
 ])
 @pytest.mark.oracle
-def test_two_segment_sizes_equal_one_size(ctx, model, kernel_shape, thresh, nodata, monkeypatch):
+def test_two_segment_sizes_equal_one_size(ctx, model, kernel_shape, thresh, nodata):
     """ Large rasters are cut into long row segments followed by short ones (hk_api.hip fill_grid).  Forcing that
     policy onto a small raster (HK_WAVE_SLOTS: pretend the device holds few waves) must give the bytes of the one-size
     partition wherever the float64 window sums are exact, and the oracle's values. """
@@ -777,12 +777,8 @@ def test_two_segment_sizes_equal_one_size(ctx, model, kernel_shape, thresh, noda
     norm_in = onp.fit_block_norm(src, nodata, ref, nodata) if model == 'gain-blk-offset' else None
     one = _fit_via_abi(ctx, cfg, src, ref, norm_in=norm_in)
     for big, tail in (('96', '16'), ('200', '8')):
-        monkeypatch.setenv('HK_WAVE_SLOTS', '4')
-        monkeypatch.setenv('HK_SEG_BIG', big)
-        monkeypatch.setenv('HK_SEG_TAIL', tail)
-        two = _fit_via_abi(ctx, cfg, src, ref, norm_in=norm_in)
-        for k in ('HK_WAVE_SLOTS', 'HK_SEG_BIG', 'HK_SEG_TAIL'):
-            monkeypatch.delenv(k)
+        with launch_context(ctx, {'HK_WAVE_SLOTS': '4', 'HK_SEG_BIG': big, 'HK_SEG_TAIL': tail}) as c:
+            two = _fit_via_abi(c, cfg, src, ref, norm_in=norm_in)
         assert_same_f32(one[0], two[0], f'params, segments {big}/{tail}')
         assert_same_f32(one[1], two[1], f'corrected, segments {big}/{tail}')
         assert one[3] == two[3]
@@ -1745,7 +1741,7 @@ def test_south_up_and_mirrored_grids(ctx):
     ('gain-blk-offset', (9, 9), np.nan), ('gain-blk-offset', (11, 5), np.nan), ('gain-blk-offset', (15, 15), 0.0),
 ])
 @pytest.mark.oracle
-def test_split_ring_agrees_with_the_other_ring_modes(ctx, model, kernel_shape, nodata, monkeypatch):
+def test_split_ring_agrees_with_the_other_ring_modes(ctx, model, kernel_shape, nodata):
     """ Ring mode 3 (round 3): the rh newest rows of a tall kernel's window stay in registers, the rh + 1 older ones in an LDS
     ring -- no re-load of the leaving row.  Same bytes as the centre-ring / re-load modes, on rasters with a NaN frame and
     holes, numeric nodata and none, taller than one wave segment; and equal to the oracle. """
@@ -1758,9 +1754,8 @@ def test_split_ring_agrees_with_the_other_ring_modes(ctx, model, kernel_shape, n
     norm_in = onp.fit_block_norm(src, nodata, ref, nodata) if model == 'gain-blk-offset' else None
     out = {}
     for mode in ('3', '2', '0'):
-        monkeypatch.setenv('HK_USE_RING', mode)
-        out[mode] = _fit_via_abi(ctx, cfg, src, ref, norm_in=norm_in)
-    monkeypatch.delenv('HK_USE_RING')
+        with launch_context(ctx, {'HK_USE_RING': mode}) as c:
+            out[mode] = _fit_via_abi(c, cfg, src, ref, norm_in=norm_in)
     out['default'] = _fit_via_abi(ctx, cfg, src, ref, norm_in=norm_in)
     for mode in ('2', '0', 'default'):
         assert_same_f32(out['3'][0], out[mode][0], f'params ring mode 3 vs {mode}')

@@ -8,6 +8,4 @@ cfgs=${@:-3 4}
 for rep in 1 2; do
 for c in $cfgs; do
 for b in 0 1 2 4; do run "--config $c --steps 8 --warmup 2 --batches $b" "A=1"; done
-run "--config $c --steps 8 --warmup 2 --batches 1" "HK_BATCH_SEGS=0"
-run "--config $c --steps 8 --warmup 2 --batches 2" "HK_BATCH_SEGS=0"
 done; done
