@@ -12,8 +12,18 @@ from homonim_amd.raster_array import RasterArray
 from homonim_amd.fuse import RasterFuse
 from homonim_amd.compare import RasterCompare
 
+
+
+def __getattr__(name):
+    # ParamStats is imported on first use, so that `python -m homonim_amd.stats` runs the module once
+    if name == 'ParamStats':
+        from homonim_amd.stats import ParamStats
+        return ParamStats
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
+
+
 __version__ = '0.1.0'
 __all__ = [
     'Model', 'ProcCrs', 'Resampling', 'ConfigWarning', 'DeviceError', 'HomonimError', 'Affine', 'CRS', 'Window',
-    'KernelModel', 'RefSpaceModel', 'SrcSpaceModel', 'RasterArray', 'RasterFuse', 'RasterCompare',
+    'KernelModel', 'RefSpaceModel', 'SrcSpaceModel', 'RasterArray', 'RasterFuse', 'RasterCompare', 'ParamStats',
 ]

@@ -69,7 +69,7 @@ _P = C.POINTER
 _f32p, _f64p, _u64p = _P(C.c_float), _P(C.c_double), _P(C.c_uint64)
 
 # name -> (restype, argtypes); kept in one table so tests can check every symbol of the header is exported
-ABI_VERSION = 6   # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
+ABI_VERSION = 7   # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
 # entry points declared in include/homonim_hk_devtools.h (measurement / test aids), the rest in include/homonim_hk.h
 DEVTOOLS = ('hk_synth_fill_dev', 'hk_stream_probe_dev', 'hk_debug_stage_stamps', 'hk_r2_certificate_constants', 'hk_debug_staging_counters',
             'hk_debug_build_ledger', 'hk_debug_checksum_dev', 'hk_debug_fail_after_d2h')
@@ -96,6 +96,9 @@ SIGNATURES = {
     'hk_block_norm': (C.c_int, [C.c_void_p, _P(FitDesc), _f32p, C.c_int64, _f32p, C.c_int64, C.c_int32, C.c_int32, _f64p]),
     'hk_compare_sums': (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int32, C.c_float, _f32p, C.c_int64, C.c_int32, C.c_float,
                                   C.c_int32, C.c_int32, _f64p]),
+    'hk_param_stats': (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_int32, C.c_int32, _f64p]),
+    'hk_param_stats_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                     C.c_int32, C.c_float, C.c_double, C.c_void_p]),
     'hk_fit': (C.c_int, [C.c_void_p, _P(FitDesc), _f32p, C.c_int64, _f32p, C.c_int64, C.c_int32, C.c_int32, _f64p,
                          _f32p, C.c_int32, _f64p, _u64p]),
     'hk_apply': (C.c_int, [C.c_void_p, _f32p, C.c_int64, _f32p, C.c_int32, C.c_int32, _f32p]),
@@ -149,6 +152,7 @@ SIGNATURES = {
     'hk_debug_checksum_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint64)]),
 }  # yapf: disable
 
+PARAM_STATS_N = 10    # values per band of hk_param_stats / hk_param_stats_dev
 COMM_ID_BYTES = 128   # HK_COMM_ID_BYTES = sizeof(ncclUniqueId)
 
 
@@ -333,6 +337,18 @@ class Context:
         _check(self._lib.hk_compare_sums(self._h, _ptr(src), src.strides[0] // 4, sm, sv, _ptr(ref), ref.strides[0] // 4,
                                          rm, rv, src.shape[0], src.shape[1], _ptr(sums, _f64p)))
         return sums
+
+    def param_stats(self, plane: np.ndarray, nodata=float('nan'), thresh: Optional[float] = None) -> np.ndarray:
+        """ float64[10] = [min, max, sum x, sum x^2, N, N(x < thresh), col_min, row_min, col_max, row_max] over the valid
+        pixels of one 2-D float32 raster in host memory (homonim/stats.py:217-229, :135-173; hk_param_stats).  ``thresh``
+        None counts nothing. """
+        plane = _as_f32_2d(plane, 'plane')
+        stats = np.zeros(PARAM_STATS_N, np.float64)
+        mode, value = nodata_code(nodata)
+        _check(self._lib.hk_param_stats(self._h, _ptr(plane), plane.strides[0] // 4, mode, value,
+                                        float('nan') if thresh is None else float(thresh), plane.shape[0], plane.shape[1],
+                                        _ptr(stats, _f64p)))
+        return stats
 
     def fit_apply(self, desc: FitDesc, src: np.ndarray, ref: np.ndarray, n_param_bands: int, want_params: bool,
                   want_corr: bool, norm_in: Optional[np.ndarray] = None, out_params: Optional[np.ndarray] = None,
@@ -706,6 +722,15 @@ class Context:
     def compare_sums_dev(self, job: DevJob, src_nodata, ref_nodata, sums_dptr: int):
         (sm, sv), (rm, rv) = nodata_code(src_nodata), nodata_code(ref_nodata)
         _check(self._lib.hk_compare_sums_dev(self._h, C.byref(job), sm, sv, rm, rv, C.c_void_p(sums_dptr)))
+
+    def param_stats_dev(self, planes_dptr: int, n_bands: int, height: int, width: int, stride: int, band_stride: int,
+                        stats_dptr: int, nodata=float('nan'), thresh: Optional[float] = None, stream: int = 0):
+        """ Queue the statistics of ``n_bands`` device-resident float32 planes in one launch: ``n_bands`` x 10 float64 into
+        ``stats_dptr`` (hk_param_stats_dev; asynchronous). """
+        mode, value = nodata_code(nodata)
+        _check(self._lib.hk_param_stats_dev(self._h, C.c_void_p(planes_dptr), n_bands, height, width, stride, band_stride,
+                                            stream, mode, value, float('nan') if thresh is None else float(thresh),
+                                            C.c_void_p(stats_dptr)))
 
     def synth_fill_dev(self, src_dptr, ref_dptr, n_bands, height, width, stride, band_stride, seed=0, nodata_variant=0,
                        stream=0):

@@ -262,7 +262,7 @@ struct Slot {
     // Pinned words of the slot (PIN_BYTES of hipHostMalloc'd memory): small results and arguments travel through them,
     // never through the caller's pageable memory.  fail_host = the first word (the r2-mask failure counter).
     unsigned long long* fail_host = nullptr;
-    static constexpr size_t PIN_NORM = 64, PIN_SUMS = 128, PIN_NORM_IN = 192, PIN_WORD = 256, PIN_COUNTS = 1024, PIN_BYTES = 16384;
+    static constexpr size_t PIN_NORM = 64, PIN_SUMS = 128, PIN_NORM_IN = 192, PIN_WORD = 256, PIN_STATS = 512, PIN_COUNTS = 1024, PIN_BYTES = 16384;
     template <class T> T* pin(size_t off) const { return reinterpret_cast<T*>(reinterpret_cast<char*>(fail_host) + off); }
     // Pinned staging ring of the host-pointer calls (stage_h2d / stage_d2h below): STAGE_N chunks of stage_chunk bytes.
     // A chunk is re-used once the copy that last used it has completed (stage_ev); a device-to-host chunk additionally
@@ -2023,6 +2023,66 @@ int hk_compare_sums(hk_ctx* ctx, const float* src, int64_t src_stride, int32_t s
     HK_HIP(hipMemcpyAsync(sl.pin<double>(Slot::PIN_SUMS), d_sums, 7 * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
     if ((rc = stage_finish(sl))) return rc;
     memcpy(sums_out, sl.pin<double>(Slot::PIN_SUMS), 7 * sizeof(double));
+    return HK_OK;
+}
+
+// ParamStats.stats / get_block_sums (homonim/stats.py:217-229): see include/homonim_hk.h
+static int check_param_stats(hk_ctx* ctx, const void* planes, const void* out, int32_t n_bands, int32_t height, int32_t width,
+                             int64_t stride, int32_t nodata_mode) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    if (!planes || !out) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (n_bands < 1 || height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d x %d", n_bands, height, width);
+    if (n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", n_bands);
+    if (stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
+    return check_nodata_mode(nodata_mode);
+}
+
+int hk_param_stats_dev(hk_ctx* ctx, const float* planes_dev, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                       int64_t band_stride, int32_t stream, int32_t nodata_mode, float nodata, double thresh, double* stats_dev) {
+    int rc = check_param_stats(ctx, planes_dev, stats_dev, n_bands, height, width, stride, nodata_mode);
+    if (rc) return rc;
+    if (band_stride < 0) return fail(HK_ERR_ARG, "band_stride is negative");
+    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    DevEnter entered(ctx, stream);
+    HK_ENTER(ctx);
+    Slot& sl = ctx->slots[stream];
+    rc = ensure_stream_ws(ctx, sl, hk::param_stats_workspace_bytes(n_bands));
+    if (rc) return rc;
+    hk::ParamStatsArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.planes = planes_dev, pa.height = height, pa.width = width, pa.stride = stride, pa.band_stride = band_stride;
+    pa.n_bands = n_bands, pa.nd_mode = nodata_mode, pa.nodata = nodata, pa.thresh = thresh;
+    HK_HIP(hk::launch_param_stats(pa, sl.norm_ws, stats_dev, sl.stream));
+    return HK_OK;
+}
+
+int hk_param_stats(hk_ctx* ctx, const float* plane, int64_t stride, int32_t nodata_mode, float nodata, double thresh,
+                   int32_t height, int32_t width, double stats_out[10]) {
+    static_assert(hk::PARAM_STATS_N == 10, "stats_out[10] of include/homonim_hk.h");
+    int rc = check_param_stats(ctx, plane, stats_out, 1, height, width, stride, nodata_mode);
+    if (rc) return rc;
+    HK_ENTER(ctx);
+    const int64_t d_stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    SlabLayout L;
+    const size_t o_plane = L.take((size_t)d_stride * height * sizeof(float)), o_ws = L.take(hk::param_stats_workspace_bytes(1)),
+                 o_stats = L.take(256);
+    SlotLease lease(ctx);
+    Slot& sl = lease.slot();
+    rc = ensure_dev(sl, L.total);
+    if (rc) return rc;
+    char* base = static_cast<char*>(sl.dev);
+    float* d_plane = reinterpret_cast<float*>(base + o_plane);
+    double* d_stats = reinterpret_cast<double*>(base + o_stats);
+    if ((rc = stage_h2d(sl, d_plane, d_stride * 4, plane, stride * 4, (size_t)width * sizeof(float), height))) return rc;
+    hk::ParamStatsArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.planes = d_plane, pa.height = height, pa.width = width, pa.stride = d_stride, pa.band_stride = 0, pa.n_bands = 1;
+    pa.nd_mode = nodata_mode, pa.nodata = nodata, pa.thresh = thresh;
+    HK_HIP(hk::launch_param_stats(pa, base + o_ws, d_stats, sl.stream));
+    const size_t bytes = hk::PARAM_STATS_N * sizeof(double);
+    HK_HIP(hipMemcpyAsync(sl.pin<double>(Slot::PIN_STATS), d_stats, bytes, hipMemcpyDeviceToHost, sl.stream));
+    if ((rc = stage_finish(sl))) return rc;
+    memcpy(stats_out, sl.pin<double>(Slot::PIN_STATS), bytes);
     return HK_OK;
 }
 

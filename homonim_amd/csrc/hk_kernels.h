@@ -226,6 +226,26 @@ struct CompareArgs {
 size_t compare_workspace_bytes(int n_bands);
 hipError_t launch_compare_sums(const CompareArgs& a, void* workspace, double* sums_out, hipStream_t stream);
 
+// Masked per-band statistics of a parameter image, homonim/stats.py:217-229 (hk_param_stats.hip), over the pixels valid under
+// (nd_mode, nodata): stats_out[band * PARAM_STATS_N + k] =
+//     [min, max, sum x, sum x^2, N, N(x < thresh), col_min, row_min, col_max, row_max]
+// with x as float64; the last four are the bounding box of the valid pixels.  A band without a valid pixel gives
+// [+inf, -inf, 0, 0, 0, 0, width, height, -1, -1].
+constexpr int PARAM_STATS_N = 10;
+struct ParamStatsArgs {
+    const float* planes;
+    int height, width;
+    long long stride;       // elements between rows
+    long long band_stride;  // elements between planes
+    int n_bands;
+    int nd_mode;
+    float nodata;
+    double thresh;
+    int vec_ok;             // set by the launcher: 16-byte row loads are legal
+};
+size_t param_stats_workspace_bytes(int n_bands);
+hipError_t launch_param_stats(const ParamStatsArgs& a, void* workspace, double* stats_out, hipStream_t stream);
+
 hipError_t launch_synth_fill(float* src, float* ref, int n_bands, int height, int width, long long stride,
                              long long band_stride, unsigned long long seed, int nodata_variant, hipStream_t stream);
 

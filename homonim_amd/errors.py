@@ -28,11 +28,12 @@ class ImageProfileError(HomonimError):
 
 
 class ImageFormatError(HomonimError):
-    """ Kept for API compatibility (band / format validation lives with GDAL in the reference). """
+    """ utils.validate_param_image / ParamStats: the file is not a parameter image (band count, FUSE_* tags or band
+    descriptions). """
 
 
 class IoError(HomonimError):
-    """ A closed RasterFuse / RasterCompare was used, or homonim_amd/tiff.py met a file outside its TIFF subset. """
+    """ A closed RasterFuse / RasterCompare / ParamStats was used, or homonim_amd/tiff.py met a file outside its TIFF subset. """
 
 
 class HomonimWarning(RuntimeWarning):

@@ -271,6 +271,7 @@ class RasterFuse:
         reference does through GDAL (RefSpaceModel / SrcSpaceModel); the reference must cover the source.
         """
         self._src_filename = self._ref_filename = None
+        self._ref_descriptions = ()   # band descriptions of a reference opened from a file (name the parameter bands)
         if isinstance(src, (str, os.PathLike)):  # a GeoTIFF, as homonim.RasterFuse(src_filename, ref_filename, ...)
             from homonim_amd.tiff import read_tiff
             self._src_filename = os.fspath(src)
@@ -283,6 +284,7 @@ class RasterFuse:
             if crs is not None and tif.crs != crs:
                 raise NotImplementedError('source and reference CRSs differ: re-projection between CRSs is not built (GDAL warp)')
             ref, ref_nodata, ref_transform = tif.array, tif.nodata, tif.transform
+            self._ref_descriptions = tif.descriptions
         if isinstance(src, RasterArray):
             src, src_nodata, crs, transform = src.array, src.nodata, src.crs, src.transform
         if isinstance(ref, RasterArray):
@@ -561,7 +563,7 @@ class RasterFuse:
                 self._save(corr_filename, corr, self._transform, nodata, meta)
             if want_params and isinstance(param_filename, (str, os.PathLike)):
                 param_tf = self._ref_transform if (self._proc_crs == ProcCrs.ref and not self._same_grid) else self._transform
-                self._save(param_filename, params, param_tf, float('nan'), meta)
+                self._save(param_filename, params, param_tf, float('nan'), meta, self._param_descriptions(n_param))
         return corr, params
 
     @staticmethod
@@ -600,12 +602,21 @@ class RasterFuse:
                 for f in as_completed(futures):
                     f.result()  # re-raise worker exceptions (fuse.py:404-408)
 
-    def _save(self, filename, array: np.ndarray, transform: Affine, nodata, metadata: Dict):
+    def _param_descriptions(self, n_param: int) -> List[str]:
+        """ Band descriptions of the parameter file (homonim/fuse.py:241-248): ``<ref band>_GAIN``, ``_OFFSET``, ``_R2`` in the
+        file's band order, ``<ref band>`` being the reference band's own description or ``B<n>``. """
+        n_src = self._src.shape[0]
+        names = [(self._ref_descriptions[bi] if bi < len(self._ref_descriptions) else None) or f'B{bi + 1}' for bi in range(n_src)]
+        return [f'{name}_{param}' for param in ('GAIN', 'OFFSET', 'R2')[:n_param] for name in names]
+
+    def _save(self, filename, array: np.ndarray, transform: Affine, nodata, metadata: Dict,
+              descriptions: Optional[List[str]] = None):
         """ ``.tif`` / ``.tiff``: tiled DEFLATE GeoTIFF like the reference's default output profile (no overviews);
         anything else: ``numpy.save``. """
         if os.fspath(filename).lower().endswith(('.tif', '.tiff')):
             from homonim_amd.tiff import write_tiff
-            write_tiff(filename, array, transform, self._crs, nodata, {k: str(v) for k, v in metadata.items()})
+            write_tiff(filename, array, transform, self._crs, nodata, {k: str(v) for k, v in metadata.items()},
+                       descriptions=descriptions)
         else:
             np.save(filename, array)
 

@@ -6,13 +6,15 @@ profile, homonim/fuse.py:124-149): classic or BigTIFF, little / big endian, stri
 ``contig``, uncompressed or DEFLATE (zlib) with predictor none / horizontal differencing, 8 / 16 / 32 / 64-bit integer
 and IEEE float samples; north-up geo-referencing from ModelPixelScale + ModelTiepoint or ModelTransformation; nodata
 from GDAL_NODATA; EPSG code / citation from the GeoKey directory; the ``<GDALMetadata>`` items (where the reference keeps
-its FUSE_* provenance, fuse.py:193-207).  The writer produces tiled, DEFLATE, band-separate files like the reference's
+its FUSE_* provenance, fuse.py:193-207) and the per-band ``DESCRIPTION`` items among them (the band names of a parameter
+file, fuse.py:241-248).  The writer produces tiled, DEFLATE, band-separate files like the reference's
 default output profile.  Everything else (other compressions, rotated grids, overviews, palettes) raises.
 """
+import mmap
 import re
 import struct
 import zlib
-from typing import Dict, NamedTuple, Optional
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 from xml.sax.saxutils import escape, unescape
 
 import numpy as np
@@ -36,6 +38,20 @@ class TiffRaster(NamedTuple):
     crs: CRS
     nodata: Optional[float]
     metadata: Dict[str, str]     # dataset-level <GDALMetadata> items
+    descriptions: Tuple[Optional[str], ...] = ()   # per band: GDAL's band description, None where the file has none
+
+
+class TiffHeader(NamedTuple):
+    """ What ``read_tiff_header`` finds without decoding a pixel. """
+    count: int
+    height: int
+    width: int
+    dtype: str                   # numpy name of the sample type, or '' outside the reader's subset
+    transform: Affine
+    crs: CRS
+    nodata: Optional[float]
+    metadata: Dict[str, str]
+    descriptions: Tuple[Optional[str], ...]
 
 
 def _read_ifd(buf: bytes):
@@ -131,6 +147,45 @@ def _metadata(tags) -> Dict[str, str]:
     return out
 
 
+def _descriptions(tags, count: int) -> Tuple[Optional[str], ...]:
+    """ GDAL's band descriptions: ``<Item name="DESCRIPTION" sample="N" role="description">`` with N counted from 0 """
+    out = [None] * count
+    for m in re.finditer(r'<Item name="DESCRIPTION"([^>]*)>(.*?)</Item>', tags.get(T_GDAL_METADATA) or '', flags=re.S):
+        sample = re.search(r'sample="(\d+)"', m.group(1))
+        if sample and 'role="description"' in m.group(1) and int(sample.group(1)) < count:
+            out[int(sample.group(1))] = unescape(m.group(2), {'&quot;': '"'})
+    return tuple(out)
+
+
+def _nodata_tag(t) -> Optional[float]:
+    try:
+        return float(t[T_GDAL_NODATA].strip()) if T_GDAL_NODATA in t else None
+    except ValueError:
+        return None
+
+
+def read_tiff_header(path) -> TiffHeader:
+    """ Shape, geo-referencing, nodata, ``<GDALMetadata>`` items and band descriptions of the first image of a GeoTIFF.  Only
+    the directory and the values it points to are read (the file is mapped, not loaded): validating a parameter file does not
+    cost its pixels. """
+    with open(path, 'rb') as f:
+        try:
+            buf = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+        except ValueError:   # an empty file cannot be mapped
+            raise IoError('not a TIFF file')
+        with buf:
+            bo, t = _read_ifd(buf)
+    if T_WIDTH not in t or T_HEIGHT not in t:
+        raise IoError('not a TIFF file')
+    w, h = t[T_WIDTH][0], t[T_HEIGHT][0]
+    spp = t.get(T_SPP, (1,))[0]
+    bits, fmt = t.get(T_BITS, (1,)), t.get(T_FORMAT, (1,) * spp)
+    uniform = len(set(bits)) == 1 and len(set(fmt)) == 1 and (fmt[0], bits[0]) in _SAMPLE_DTYPES
+    dtype = np.dtype(_SAMPLE_DTYPES[(fmt[0], bits[0])]).name if uniform else ''
+    tf, crs = _geo(t, h)
+    return TiffHeader(spp, h, w, dtype, tf, crs, _nodata_tag(t), _metadata(t), _descriptions(t, spp))
+
+
 def read_tiff(path) -> TiffRaster:
     """ Read the first image of a GeoTIFF into a (bands, height, width) array. """
     with open(path, 'rb') as f:
@@ -175,21 +230,17 @@ def read_tiff(path) -> TiffRaster:
             out[plane, y0:y0 + hh, x0:x0 + ww] = block[:hh, :ww, 0]
         else:
             out[:, y0:y0 + hh, x0:x0 + ww] = np.moveaxis(block[:hh, :ww, :], 2, 0)
-    nodata = None
-    if T_GDAL_NODATA in t:
-        try:
-            nodata = float(t[T_GDAL_NODATA].strip())
-        except ValueError:
-            nodata = None
     tf, crs = _geo(t, h)
-    return TiffRaster(out, tf, crs, nodata, _metadata(t))
+    return TiffRaster(out, tf, crs, _nodata_tag(t), _metadata(t), _descriptions(t, spp))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = None, nodata: Optional[float] = None,
-               metadata: Optional[Dict[str, str]] = None, tile: int = 512, compress: bool = True):
+               metadata: Optional[Dict[str, str]] = None, tile: int = 512, compress: bool = True,
+               descriptions: Optional[Sequence[Optional[str]]] = None):
     """ Write (bands, height, width) as a classic little-endian GeoTIFF: tiled, DEFLATE, band-separate -- the reference's
-    default output profile (homonim/fuse.py:124-149: tiled 512 x 512, compress=deflate, interleave=band). """
+    default output profile (homonim/fuse.py:124-149: tiled 512 x 512, compress=deflate, interleave=band).  ``descriptions``:
+    one band description per band (None: none for that band), written as GDAL writes them. """
     a = np.asarray(array)
     if a.ndim == 2:
         a = a[None]
@@ -245,8 +296,12 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
     elif name:
         add(T_GEOKEYS, 3, [1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 1026, T_GEOASCII, len(name) + 1, 0])
         add(T_GEOASCII, 2, name + '|')
-    if metadata:
-        items = ''.join(f'  <Item name="{escape(str(k), {chr(34): "&quot;"})}">{escape(str(v))}</Item>\n' for k, v in metadata.items())
+    if descriptions is not None and len(descriptions) != nb:
+        raise ValueError(f'{len(descriptions)} band descriptions for {nb} bands')
+    if metadata or (descriptions and any(d is not None for d in descriptions)):
+        items = ''.join(f'  <Item name="{escape(str(k), {chr(34): "&quot;"})}">{escape(str(v))}</Item>\n' for k, v in (metadata or {}).items())
+        items += ''.join(f'  <Item name="DESCRIPTION" sample="{i}" role="description">{escape(str(d))}</Item>\n'
+                         for i, d in enumerate(descriptions or ()) if d is not None)
         add(T_GDAL_METADATA, 2, f'<GDALMetadata>\n{items}</GDALMetadata>\n')
     if nodata is not None:
         add(T_GDAL_NODATA, 2, 'nan' if (isinstance(nodata, float) and np.isnan(nodata)) else repr(float(nodata)) if a.dtype.kind == 'f' else str(int(nodata)))

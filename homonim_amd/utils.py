@@ -1,8 +1,10 @@
 """
-The four pure helpers of homonim/utils.py the hot path touches, restated (same names, arguments and errors):
+The pure helpers of homonim/utils.py this package touches, restated (same names, arguments and errors):
 ``nan_equals`` (:54-56), ``validate_kernel_shape`` (:104-133), ``overlap_for_kernel`` (:136-153),
-``validate_threads`` (:156-164).
+``validate_threads`` (:156-164), ``validate_param_image`` (:313-330).
 """
+import os
+import pathlib
 import warnings
 from multiprocessing import cpu_count
 from typing import Tuple, Union
@@ -10,7 +12,7 @@ from typing import Tuple, Union
 import numpy as np
 
 from homonim_amd.enums import Model
-from homonim_amd.errors import ConfigWarning
+from homonim_amd.errors import ConfigWarning, ImageFormatError, IoError
 
 
 def nan_equals(a: Union[np.ndarray, float], b: Union[np.ndarray, float]) -> np.ndarray:
@@ -49,3 +51,28 @@ def validate_threads(threads: int) -> int:
     if threads > _cpu_count:
         raise ValueError(f"'threads' is limited to the number of processors ({_cpu_count})")
     return threads
+
+
+PARAM_TAGS = ('FUSE_MODEL', 'FUSE_KERNEL_SHAPE', 'FUSE_PROC_CRS', 'FUSE_REF_FILE')
+
+
+def validate_param_image(param_filename: Union[str, os.PathLike]):
+    """ Check the file is a valid parameter image (utils.py:313-330): a band count that is a multiple of 3, the FUSE_* tags of
+    ``PARAM_TAGS``, and band descriptions ending in gain / offset / r2 (case-insensitive), a third of the bands each.  Only
+    the file's header is read; the header is returned. """
+    from homonim_amd.tiff import read_tiff_header
+    param_filename = pathlib.Path(param_filename)
+    if not param_filename.exists():
+        raise FileNotFoundError(f'{param_filename} does not exist')
+    invalid = ImageFormatError(f'{param_filename.name} is not a valid parameter image.')
+    try:
+        header = read_tiff_header(param_filename)
+    except IoError as ex:
+        raise invalid from ex
+    if header.count == 0 or header.count % 3 != 0 or not set(PARAM_TAGS) <= set(header.metadata):
+        raise invalid
+    n_refl_bands = header.count // 3
+    suffixes = ['gain'] * n_refl_bands + ['offset'] * n_refl_bands + ['r2'] * n_refl_bands
+    if not all((desc or '').lower().endswith(suffix) for suffix, desc in zip(suffixes, header.descriptions)):
+        raise invalid
+    return header

@@ -70,8 +70,9 @@ typedef struct {
  * another must not call further: structs grow at their end between versions (hk_out_window: 32 -> 40 bytes in version 3) and
  * carry no size field; version 5 added entry points (hk_device_pci_bus_id; hk_debug_staging_counters in the devtools header); version 6: a raw
  * r2-mask failure counter is always a count (HK_COUNT_RETRY is never set any more), and a device-resident job that carries `scratch`
- * always gets the in-painting's inputs left there.  hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
-#define HK_ABI_VERSION 6
+ * always gets the in-painting's inputs left there; version 7 added entry points (hk_param_stats, hk_param_stats_dev).
+ * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
+#define HK_ABI_VERSION 7
 int hk_abi_version(void);
 const char* hk_backend_name(void);            /* "hip-gfx950" */
 const char* hk_last_error(void);              /* thread-local text of the last failure */
@@ -106,6 +107,14 @@ int hk_block_norm(hk_ctx* ctx, const hk_fit_desc* desc, const float* src, int64_
 int hk_compare_sums(hk_ctx* ctx, const float* src, int64_t src_stride, int32_t src_nodata_mode, float src_nodata,
                     const float* ref, int64_t ref_stride, int32_t ref_nodata_mode, float ref_nodata, int32_t height,
                     int32_t width, double sums_out[7]);
+
+/* ParamStats.stats / get_block_sums (homonim/stats.py:217-229) and the data window of stats.py:135-173 for one band (or one
+ * strip of rows of a band) of a parameter image in host memory:
+ * stats_out = [ min, max, sum x, sum x^2, N, N(x < thresh), col_min, row_min, col_max, row_max ] over the valid pixels
+ * (see hk_param_stats_dev for the arithmetic and the empty band).  Strips combine exactly: min of mins, max of maxes, sums of
+ * sums and counts, union of boxes (row indices are relative to the strip). */
+int hk_param_stats(hk_ctx* ctx, const float* plane, int64_t stride, int32_t nodata_mode, float nodata, double thresh,
+                   int32_t height, int32_t width, double stats_out[10]);
 
 /* KernelModel.fit (homonim/kernel_model.py:411-440 -> _fit_gain :231-274, _fit_gain_blk_offset :276-303,
  * _fit_gain_offset :305-373, _r2_array :142-214).
@@ -364,6 +373,21 @@ int hk_block_norm_split_comm_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_
  * r2 / RMSE / rRMSE follow from them as in compare.py:142-160. */
 int hk_compare_sums_dev(hk_ctx* ctx, const hk_dev_job* job, int32_t src_nodata_mode, float src_nodata,
                         int32_t ref_nodata_mode, float ref_nodata, double* sums_dev);
+/* The masked statistics of ParamStats.stats / get_block_sums (homonim/stats.py:217-229) of `n_bands` device-resident float32
+ * planes (plane b at planes_dev + b * band_stride, `stride` elements between rows; any parameter raster will do, not only a
+ * job's) in ONE launch on pooled stream `stream`, per band into stats_dev (device, n_bands x 10 float64; asynchronous, no host
+ * synchronisation):
+ *   [ min, max, sum x, sum x^2, N, N(x < thresh), col_min, row_min, col_max, row_max ]
+ * over the pixels valid under (nodata_mode, nodata) with utils.nan_equals semantics; the last four are the bounding box of the
+ * valid pixels (stats.py:135-173).  Every pixel term is (double)x resp. (double)x * (double)x (exact), accumulated in float64
+ * in a fixed order: bit-identical run to run and to hk_param_stats on the same plane.  min / max are the float32 values, the
+ * counts are exact (64-bit, returned as doubles), x < thresh is decided in float64 (a NaN thresh counts nothing); +-inf
+ * pixels are data.  Under HK_NODATA_NONE / HK_NODATA_VALUE a NaN pixel is valid and makes min, max and both sums NaN, as in
+ * numpy.  A band without a valid pixel gives [ +inf, -inf, 0, 0, 0, 0, width, height, -1, -1 ].  16-byte loads are used when
+ * planes_dev is 16-byte aligned and stride and band_stride are multiples of 4; any other layout is accepted and gives the same
+ * bits.  mean / std / Inpaint (%) follow as in stats.py:175-192. */
+int hk_param_stats_dev(hk_ctx* ctx, const float* planes_dev, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                       int64_t band_stride, int32_t stream, int32_t nodata_mode, float nodata, double thresh, double* stats_dev);
 
 
 /* HIP events on the pooled streams, so callers time exactly the stream the kernels run on. */
