@@ -9,7 +9,8 @@ from homonim_amd.errors import ConfigWarning, DeviceError, HomonimError
 from homonim_amd.geo import Affine, CRS, Window
 from homonim_amd.kernel_model import KernelModel, RefSpaceModel, SrcSpaceModel
 from homonim_amd.raster_array import RasterArray
-from homonim_amd.fuse import RasterFuse
+from homonim_amd.fuse import RasterFuse, overview_factors
+from homonim_amd.tiff import read_tiff_overviews
 from homonim_amd.compare import RasterCompare
 
 
@@ -26,4 +27,5 @@ __version__ = '0.1.0'
 __all__ = [
     'Model', 'ProcCrs', 'Resampling', 'ConfigWarning', 'DeviceError', 'HomonimError', 'Affine', 'CRS', 'Window',
     'KernelModel', 'RefSpaceModel', 'SrcSpaceModel', 'RasterArray', 'RasterFuse', 'RasterCompare', 'ParamStats',
+    'overview_factors', 'read_tiff_overviews',
 ]

@@ -12,7 +12,7 @@ import weakref
 import math
 import os
 import threading
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -69,7 +69,7 @@ _P = C.POINTER
 _f32p, _f64p, _u64p = _P(C.c_float), _P(C.c_double), _P(C.c_uint64)
 
 # name -> (restype, argtypes); kept in one table so tests can check every symbol of the header is exported
-ABI_VERSION = 7   # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
+ABI_VERSION = 8   # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
 # entry points declared in include/homonim_hk_devtools.h (measurement / test aids), the rest in include/homonim_hk.h
 DEVTOOLS = ('hk_synth_fill_dev', 'hk_stream_probe_dev', 'hk_debug_stage_stamps', 'hk_r2_certificate_constants', 'hk_debug_staging_counters',
             'hk_debug_build_ledger', 'hk_debug_checksum_dev', 'hk_debug_fail_after_d2h')
@@ -99,6 +99,11 @@ SIGNATURES = {
     'hk_param_stats': (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_int32, C.c_int32, _f64p]),
     'hk_param_stats_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
                                      C.c_int32, C.c_float, C.c_double, C.c_void_p]),
+    'hk_overview_count': (C.c_int, [C.c_int32, C.c_int32, _P(C.c_int32)]),
+    'hk_overviews': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                               C.c_double, C.c_int32, _P(C.c_void_p), _P(C.c_int64), _P(C.c_int64)]),
+    'hk_overviews_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                   C.c_int32, C.c_double, C.c_int32, _P(C.c_void_p), _P(C.c_int64), _P(C.c_int64), C.c_int32]),
     'hk_fit': (C.c_int, [C.c_void_p, _P(FitDesc), _f32p, C.c_int64, _f32p, C.c_int64, C.c_int32, C.c_int32, _f64p,
                          _f32p, C.c_int32, _f64p, _u64p]),
     'hk_apply': (C.c_int, [C.c_void_p, _f32p, C.c_int64, _f32p, C.c_int32, C.c_int32, _f32p]),
@@ -161,6 +166,18 @@ def r2_certificate_constants(thresh: float):
     pb, fa, k, kf = C.c_double(), C.c_double(), C.c_float(), C.c_float()
     _check(load_library().hk_r2_certificate_constants(C.c_float(thresh), C.byref(pb), C.byref(fa), C.byref(k), C.byref(kf)))
     return pb.value, fa.value, k.value, kf.value
+
+
+def overview_count(height: int, width: int) -> int:
+    """ Number of internal overviews of a raster of this shape (hk_overview_count; host-only). """
+    n = C.c_int32(0)
+    _check(load_library().hk_overview_count(int(height), int(width), C.byref(n)))
+    return int(n.value)
+
+
+def overview_shapes(height: int, width: int, n_levels: int):
+    """ [(ceil(height / 2^m), ceil(width / 2^m)) for m = 1..n_levels] """
+    return [(-(-int(height) // (1 << m)), -(-int(width) // (1 << m))) for m in range(1, int(n_levels) + 1)]
 
 
 def comm_unique_id() -> bytes:
@@ -349,6 +366,37 @@ class Context:
                                         float('nan') if thresh is None else float(thresh), plane.shape[0], plane.shape[1],
                                         _ptr(stats, _f64p)))
         return stats
+
+    def overviews(self, array: np.ndarray, nodata, n_levels: int) -> list:
+        """ Average overviews of a (bands, h, w) or (h, w) raster of any DTYPE_CODES dtype in host memory: ``n_levels`` arrays
+        of the same rank and dtype, level m of shape (ceil(h / 2^m), ceil(w / 2^m)), each the clipped 2 x 2 mean of the
+        valid pixels of the level before it (hk_overviews; all levels from one pass over the raster on the device).  Rows and
+        bands may be strided (unit column stride); anything else is copied first. """
+        arr = np.asarray(array)
+        squeeze = arr.ndim == 2
+        if squeeze:
+            arr = arr[None]
+        if arr.ndim != 3 or arr.size == 0:
+            raise ValueError('`array` must be a non-empty 2-D or 3-D raster')
+        if arr.dtype.name not in DTYPE_CODES:
+            raise ValueError(f"unsupported dtype '{arr.dtype}'")
+        it = arr.dtype.itemsize
+        if (arr.strides[2] != it or arr.strides[1] % it or arr.strides[1] < arr.shape[2] * it or arr.strides[0] % it
+                or arr.strides[0] < 0):
+            arr = np.ascontiguousarray(arr)
+        nb, h, w = arr.shape
+        n_levels = int(n_levels)
+        if n_levels < 1:
+            return []
+        outs = [np.empty((nb, lh, lw), arr.dtype) for lh, lw in overview_shapes(h, w, n_levels)]
+        ptrs = (C.c_void_p * n_levels)(*[o.ctypes.data for o in outs])
+        strides = (C.c_int64 * n_levels)(*[o.shape[2] for o in outs])
+        bstrides = (C.c_int64 * n_levels)(*[o.shape[1] * o.shape[2] for o in outs])
+        mode, value = nodata_code(nodata)
+        _check(self._lib.hk_overviews(self._h, arr.ctypes.data_as(C.c_void_p), DTYPE_CODES[arr.dtype.name], nb, h, w,
+                                      arr.strides[1] // it, arr.strides[0] // it if nb > 1 else 0, mode, value, n_levels, ptrs,
+                                      strides, bstrides))
+        return [o[0] for o in outs] if squeeze else outs
 
     def fit_apply(self, desc: FitDesc, src: np.ndarray, ref: np.ndarray, n_param_bands: int, want_params: bool,
                   want_corr: bool, norm_in: Optional[np.ndarray] = None, out_params: Optional[np.ndarray] = None,
@@ -731,6 +779,17 @@ class Context:
         _check(self._lib.hk_param_stats_dev(self._h, C.c_void_p(planes_dptr), n_bands, height, width, stride, band_stride,
                                             stream, mode, value, float('nan') if thresh is None else float(thresh),
                                             C.c_void_p(stats_dptr)))
+
+    def overviews_dev(self, planes_dptr: int, dtype: str, n_bands: int, height: int, width: int, stride: int, band_stride: int,
+                      nodata, out_dptrs: Sequence[int], out_strides: Sequence[int], out_band_strides: Sequence[int],
+                      stream: int = 0):
+        """ Queue the average overviews of ``n_bands`` device-resident planes of dtype ``dtype``: level m = 1..len(out_dptrs)
+        into ``out_dptrs[m - 1]`` (strides in elements; hk_overviews_dev; asynchronous). """
+        n = len(out_dptrs)
+        mode, value = nodata_code(nodata)
+        _check(self._lib.hk_overviews_dev(self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height,
+                                          width, stride, band_stride, mode, value, n, (C.c_void_p * n)(*out_dptrs),
+                                          (C.c_int64 * n)(*out_strides), (C.c_int64 * n)(*out_band_strides), stream))
 
     def synth_fill_dev(self, src_dptr, ref_dptr, n_bands, height, width, stride, band_stride, seed=0, nodata_variant=0,
                        stream=0):

@@ -2086,6 +2086,125 @@ int hk_param_stats(hk_ctx* ctx, const float* plane, int64_t stride, int32_t noda
     return HK_OK;
 }
 
+// Internal overviews (homonim/fuse.py:152-165): see include/homonim_hk.h
+int hk_overview_count(int32_t height, int32_t width, int32_t* n) {
+    if (!n) return fail(HK_ERR_ARG, "n is NULL");
+    if (height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d", height, width);
+    int lg = 0;  // int(min(log2(height), log2(width)))
+    for (int32_t m = height < width ? height : width; m > 1; m >>= 1) ++lg;
+    *n = lg - 8 < 0 ? 0 : (lg - 8 > 8 ? 8 : lg - 8);
+    return HK_OK;
+}
+
+constexpr int OVERVIEW_MAX_LEVELS = 31;
+
+static int check_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                           int64_t stride, int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels,
+                           void* const out[], const int64_t out_stride[], const int64_t out_band_stride[]) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    if (!planes || !out || !out_stride || !out_band_stride) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!hk::dtype_size(dtype)) return fail(HK_ERR_ARG, "bad dtype %d", dtype);
+    if (n_bands < 1 || height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d x %d", n_bands, height, width);
+    if (n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", n_bands);
+    if (stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
+    if (band_stride < 0) return fail(HK_ERR_ARG, "band_stride is negative");
+    if (n_levels < 1 || n_levels > OVERVIEW_MAX_LEVELS) return fail(HK_ERR_ARG, "n_levels %d outside 1..%d", n_levels, OVERVIEW_MAX_LEVELS);
+    for (int m = 1; m <= n_levels; ++m) {
+        const int64_t wm = ((int64_t)width + (1ll << m) - 1) >> m;
+        if (!out[m - 1]) return fail(HK_ERR_ARG, "level %d: NULL plane", m);
+        if (out_stride[m - 1] < wm) return fail(HK_ERR_ARG, "level %d: row stride smaller than its width %lld", m, (long long)wm);
+        if (out_band_stride[m - 1] < 0) return fail(HK_ERR_ARG, "level %d: band_stride is negative", m);
+    }
+    int rc = check_nodata_mode(nodata_mode);
+    if (rc) return rc;
+    if (nodata_mode == HK_NODATA_VALUE && dtype != HK_DTYPE_F32 && dtype != HK_DTYPE_F64) {
+        const double lo[7] = {0, 0, 0, -32768.0, 0, -2147483648.0, 0}, hi[7] = {0, 255.0, 65535.0, 32767.0, 4294967295.0, 2147483647.0, 0};
+        if (!(nodata >= lo[dtype] && nodata <= hi[dtype]) || nodata != floor(nodata))
+            return fail(HK_ERR_ARG, "nodata %g is not a value of the integer sample type", nodata);
+    }
+    return HK_OK;
+}
+
+int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                     int64_t stride, int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels,
+                     void* const out_dev[], const int64_t out_stride[], const int64_t out_band_stride[], int32_t stream) {
+    int rc = check_overviews(ctx, planes_dev, dtype, n_bands, height, width, stride, band_stride, nodata_mode, nodata, n_levels,
+                             out_dev, out_stride, out_band_stride);
+    if (rc) return rc;
+    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    DevEnter entered(ctx, stream);
+    HK_ENTER(ctx);
+    static_assert(sizeof(long long) == sizeof(int64_t), "strides are handed on as they are");
+    HK_HIP(hk::launch_overviews(dtype, planes_dev, height, width, stride, band_stride, n_bands, nodata_mode, nodata, n_levels,
+                                out_dev, reinterpret_cast<const long long*>(out_stride),
+                                reinterpret_cast<const long long*>(out_band_stride), ctx->slots[stream].stream));
+    return HK_OK;
+}
+
+// rows of source per strip of the host path: a multiple of 2^n_levels (cells of no level straddle two strips, so the strips are
+// independent and their size cannot change a bit), all bands of at most OVERVIEW_STRIP_BYTES; HK_OVERVIEW_STRIP_KB (read at every
+// call) lowers the bound for tests of the strip path
+constexpr size_t OVERVIEW_STRIP_BYTES = 64u << 20;
+static int64_t overview_strip_rows(int32_t n_bands, int32_t height, int32_t width, int esize, int32_t n_levels) {
+    if (n_levels >= 31 || ((int64_t)1 << n_levels) >= height) return height;
+    const char* e = getenv("HK_OVERVIEW_STRIP_KB");
+    const size_t cap = (e && atol(e) > 0) ? (size_t)atol(e) << 10 : OVERVIEW_STRIP_BYTES;
+    const int64_t unit = (int64_t)1 << n_levels;
+    const int64_t rows = (int64_t)(cap / ((size_t)n_bands * width * esize)) / unit * unit;
+    return rows < unit ? unit : rows;
+}
+
+int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                 int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels, void* const out[],
+                 const int64_t out_stride[], const int64_t out_band_stride[]) {
+    int rc = check_overviews(ctx, planes, dtype, n_bands, height, width, stride, band_stride, nodata_mode, nodata, n_levels, out,
+                             out_stride, out_band_stride);
+    if (rc) return rc;
+    HK_ENTER(ctx);
+    const size_t es = hk::dtype_size(dtype);
+    const int64_t strip = overview_strip_rows(n_bands, height, width, (int)es, n_levels);
+    const int64_t rows_max = strip < height ? strip : height;
+    auto ceil_shift = [](int64_t v, int m) { return (v + ((int64_t)1 << m) - 1) >> m; };
+    auto row_align = [](int64_t w) { return (w + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN; };
+    // device slab of one strip: the source planes, then every level's planes, rows padded to ROW_ALIGN elements
+    SlabLayout L;
+    const int64_t d_stride = row_align(width);
+    const size_t o_src = L.take((size_t)n_bands * rows_max * d_stride * es);
+    size_t o_lev[OVERVIEW_MAX_LEVELS];
+    long long l_stride[OVERVIEW_MAX_LEVELS], l_band[OVERVIEW_MAX_LEVELS];
+    for (int m = 1; m <= n_levels; ++m) {
+        l_stride[m - 1] = row_align(ceil_shift(width, m));
+        l_band[m - 1] = l_stride[m - 1] * ceil_shift(rows_max, m);
+        o_lev[m - 1] = L.take((size_t)n_bands * l_band[m - 1] * es);
+    }
+    SlotLease lease(ctx);
+    Slot& sl = lease.slot();
+    rc = ensure_dev(sl, L.total);
+    if (rc) return rc;
+    char* base = static_cast<char*>(sl.dev);
+    void* d_out[OVERVIEW_MAX_LEVELS];
+    for (int m = 1; m <= n_levels; ++m) d_out[m - 1] = base + o_lev[m - 1];
+    const char* h_src = static_cast<const char*>(planes);
+    for (int64_t r0 = 0; r0 < height; r0 += strip) {
+        const int64_t rows = std::min<int64_t>(strip, height - r0);
+        for (int b = 0; b < n_bands; ++b)
+            if ((rc = stage_h2d(sl, base + o_src + (size_t)b * rows_max * d_stride * es, d_stride * es,
+                                h_src + ((size_t)b * band_stride + (size_t)r0 * stride) * es, stride * es, (size_t)width * es, rows)))
+                return rc;
+        HK_HIP(hk::launch_overviews(dtype, base + o_src, (int)rows, width, d_stride, rows_max * d_stride, n_bands, nodata_mode,
+                                    nodata, n_levels, d_out, l_stride, l_band, sl.stream));
+        for (int m = 1; m <= n_levels; ++m) {
+            char* h_out = static_cast<char*>(out[m - 1]);
+            for (int b = 0; b < n_bands; ++b)
+                if ((rc = stage_d2h(sl, h_out + ((size_t)b * out_band_stride[m - 1] + (size_t)(r0 >> m) * out_stride[m - 1]) * es,
+                                    out_stride[m - 1] * es, base + o_lev[m - 1] + (size_t)b * l_band[m - 1] * es,
+                                    l_stride[m - 1] * es, (size_t)ceil_shift(width, m) * es, ceil_shift(rows, m))))
+                    return rc;
+        }
+    }
+    return stage_finish(sl);
+}
+
 int hk_block_norm_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_job* job, double* norm_dev) {
     int rc = validate_desc(desc);
     if (rc) return rc;

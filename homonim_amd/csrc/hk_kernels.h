@@ -246,6 +246,25 @@ struct ParamStatsArgs {
 size_t param_stats_workspace_bytes(int n_bands);
 hipError_t launch_param_stats(const ParamStatsArgs& a, void* workspace, double* stats_out, hipStream_t stream);
 
+// Average overviews (hk_overview.hip; homonim/fuse.py:152-165): level m = 1..n_levels of shape (ceil(height / 2^m),
+// ceil(width / 2^m)), each the clipped 2 x 2 mean of the valid pixels of the level before it, all bands, OVERVIEW_PASS_LEVELS
+// levels per launch.  dtype = hk_dtype; strides in elements; out[m - 1] / out_stride / out_band_stride describe level m.
+constexpr int OVERVIEW_PASS_LEVELS = 6;
+struct OverviewArgs {
+    const void* src;
+    int height, width;
+    long long stride, band_stride;
+    int nd_mode;
+    int n_levels;  // of this launch: 1..OVERVIEW_PASS_LEVELS
+    double nodata;
+    void* out[OVERVIEW_PASS_LEVELS];
+    long long out_stride[OVERVIEW_PASS_LEVELS], out_band_stride[OVERVIEW_PASS_LEVELS];
+    int vec_ok, out_vec_ok;  // set by the launcher: 16-byte row loads / 8-byte level-1 stores are legal
+};
+hipError_t launch_overviews(int dtype, const void* src, int height, int width, long long stride, long long band_stride,
+                            int n_bands, int nd_mode, double nodata, int n_levels, void* const* out, const long long* out_stride,
+                            const long long* out_band_stride, hipStream_t stream);
+
 hipError_t launch_synth_fill(float* src, float* ref, int n_bands, int height, int width, long long stride,
                              long long band_stride, unsigned long long seed, int nodata_variant, hipStream_t stream);
 

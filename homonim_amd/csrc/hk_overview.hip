@@ -1,0 +1,253 @@
+// hk_overview.hip -- the internal overviews of homonim/fuse.py:152-165 (RasterFuse.build_overviews: factors 2, 4, ... with
+// Resampling.average): every level of the pyramid from ONE pass over the source.
+//
+// Semantics.  Level m has shape (ceil(H / 2^m), ceil(W / 2^m)) and is computed from level m - 1 AS STORED: its
+// pixel (i, j) takes the pixels (2i..2i+1, 2j..2j+1) of level m - 1 that lie inside that level and are valid under
+// (nodata_mode, nodata) -- NONE: all (a NaN is data and propagates), NAN: not NaN, VALUE: not equal to the value.  A cell without
+// a valid pixel gives nodata.  float32: the valid values summed as float64 in row-major order, divided by their count in float64,
+// rounded once (bit-identical to resample_kernel<5> of hk_resample.hip for the mapping (2, 0, 2, 0)); float64: the same without
+// the rounding; integers: floor((2 S + n) / (2 n)) of the exact 64-bit sum S -- round half up.  (2 S + n < 2^36 is exact as a
+// double, and a quotient that is not an integer is at least 1 / 8 away from one, so floor of the float64 division is exact.)
+//
+// One workgroup owns a source tile of 64 rows x TW columns (TW = 64 pixels of 4 or 8 bytes, 128 of 2, 256 of 1: at least 256
+// bytes per row), reads it with one 16-byte load per lane and row, forms level 1 in registers -- a lane that holds the same
+// 16 bytes of two adjacent rows owns 8 bytes of complete cells -- and hands levels 2..6 down through LDS (two buffers, one
+// barrier per level), storing every level as it goes: 6 levels per launch, which is all six of a 16384^2 raster.
+// WHY THE CASCADE INSIDE A TILE IS THE GLOBAL CASCADE: tile origins are multiples of 64 = 2^6 in both directions, so on level
+// m - 1 (m <= 6) a tile starts at an even index, and the 2 x 2 cell of any level-m pixel never straddles two tiles; a cell is
+// clipped against the GLOBAL shape of level m - 1 (ceil(H / 2^(m-1)), ...), which is what an odd edge means.  Deeper levels (at
+// most 2 of the 8 the rule allows, 4^-6 of the data) come from a second launch of the same kernel over level 6.
+// The arithmetic of a cell does not depend on how its pixels were loaded: where 16-byte loads are not legal (base or strides
+// not 16-byte aligned, the raster's last columns) a scalar path reads the same elements, so the bits do not depend on alignment.
+//
+// HBM-bound: one read of the source + 1/3 of it written, no atomics.  The sample type is a template argument; the nodata mode is
+// a RUN-TIME value: validity is two compares combined with the (wave-uniform) mode without a branch -- the disassembly of the
+// pixel path holds v_cmp / s_and only, no s_cbranch on the mode -- and a third of the builds the launch ledger has to see checked.
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "hk_kernels.h"
+
+namespace hk {
+
+namespace {
+
+constexpr int OVW_THREADS = 256;
+constexpr int OVW_ROWS = 1 << OVERVIEW_PASS_LEVELS;  // tile rows
+
+template <class T>
+__device__ __forceinline__ bool ovalid(T v, int mode, double nodata) {
+    if constexpr (std::is_floating_point<T>::value)
+        return !(((mode == 1) & (v != v)) | ((mode == 2) & ((double)v == nodata)));
+    else
+        return !((mode == 2) & ((double)v == nodata));
+}
+
+// one output pixel from the (up to) four pixels of its cell in row-major order; p*: the pixel lies inside the source level
+template <class T>
+__device__ __forceinline__ T cell(T a, T b, T c, T d, bool pa, bool pb, bool pc, bool pd, int mode, double nodata, T fill) {
+    const bool ma = pa & ovalid(a, mode, nodata), mb = pb & ovalid(b, mode, nodata), mc = pc & ovalid(c, mode, nodata),
+               md = pd & ovalid(d, mode, nodata);
+    const int n = (int)ma + (int)mb + (int)mc + (int)md;
+    if constexpr (std::is_floating_point<T>::value) {
+        double s = 0.0;  // masked pixels add zeros (the sum starts at +0 and never is -0: adding +0 changes nothing)
+        s += ma ? (double)a : 0.0;
+        s += mb ? (double)b : 0.0;
+        s += mc ? (double)c : 0.0;
+        s += md ? (double)d : 0.0;
+        return n ? (T)(s / (double)n) : fill;
+    } else {
+        long long s = 0;
+        s += ma ? (long long)a : 0;
+        s += mb ? (long long)b : 0;
+        s += mc ? (long long)c : 0;
+        s += md ? (long long)d : 0;
+        return n ? (T)(long long)floor((double)(2 * s + n) / (double)(2 * n)) : fill;
+    }
+}
+
+template <class T>
+struct Tile {
+    static constexpr int VEC = 16 / (int)sizeof(T);                              // pixels per 16-byte load
+    static constexpr int TW = sizeof(T) >= 4 ? 64 : 256 / (int)sizeof(T);        // tile columns
+    static constexpr int QPR = TW / VEC;                                         // lanes per tile row
+};
+
+// VEC pixels of one row from column gx on (`rem` = width - gx of them exist, none when !row_ok); absent ones read as 0
+template <class T>
+__device__ __forceinline__ void load_row(const T* __restrict__ p, int rem, bool row_ok, bool vec_ok, T (&r)[Tile<T>::VEC]) {
+    constexpr int VEC = Tile<T>::VEC;
+    if (row_ok && vec_ok && rem >= VEC) {
+        const uint4 t = *reinterpret_cast<const uint4*>(p);
+        __builtin_memcpy(r, &t, 16);
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) r[i] = (row_ok && i < rem) ? p[i] : T(0);
+    }
+}
+
+// level M (2..6) of the tile from level M - 1 in LDS; stores it to LDS and to the level's plane
+template <int M, class T>
+__device__ __forceinline__ void level_step(const OverviewArgs& a, const T* __restrict__ lsrc, T* __restrict__ ldst, int band,
+                                           T fill) {
+    constexpr int TW = Tile<T>::TW;
+    constexpr int hm = OVW_ROWS >> M, wm = TW >> M, ws = TW >> (M - 1);
+    const int sh = (a.height + (1 << (M - 1)) - 1) >> (M - 1), sw = (a.width + (1 << (M - 1)) - 1) >> (M - 1);  // level M - 1
+    const int sy0 = blockIdx.y * (OVW_ROWS >> (M - 1)), sx0 = blockIdx.x * ws;
+    T* __restrict__ out = static_cast<T*>(a.out[M - 1]) + (long long)band * a.out_band_stride[M - 1];
+    for (int c = threadIdx.x; c < hm * wm; c += OVW_THREADS) {
+        const int i = c / wm, j = c % wm;
+        const bool y0 = sy0 + 2 * i < sh, y1 = sy0 + 2 * i + 1 < sh, x0 = sx0 + 2 * j < sw, x1 = sx0 + 2 * j + 1 < sw;
+        const T* __restrict__ q = lsrc + 2 * i * ws + 2 * j;
+        const T v = cell<T>(q[0], q[1], q[ws], q[ws + 1], y0 & x0, y0 & x1, y1 & x0, y1 & x1, a.nd_mode, a.nodata, fill);
+        ldst[i * wm + j] = v;
+        if (y0 & x0) out[(long long)(blockIdx.y * hm + i) * a.out_stride[M - 1] + blockIdx.x * wm + j] = v;
+    }
+}
+
+// level 1 of the tile in registers: lane `item` holds VEC pixels of rows 2 rp and 2 rp + 1 and owns the VEC / 2 cells under them.
+// INTERIOR (the whole tile lies inside the raster and 16-byte loads are legal; wave-uniform): no bounds, and the loads of all of
+// the lane's items (2, or 4 of float64) are issued before the first cell is formed.
+template <bool INTERIOR, class T>
+__device__ __forceinline__ void level_one(const OverviewArgs& a, const T* __restrict__ plane, T* __restrict__ out1,
+                                          T* __restrict__ lds_a, T fill) {
+    constexpr int VEC = Tile<T>::VEC, TW = Tile<T>::TW, QPR = Tile<T>::QPR, HALF = VEC / 2;
+    constexpr int ITEMS = QPR * (OVW_ROWS / 2), NIT = ITEMS / OVW_THREADS;
+    static_assert(ITEMS % OVW_THREADS == 0, "every lane owns the same number of items");
+    const int w1 = (a.width + 1) >> 1;
+    const int y0 = blockIdx.y * OVW_ROWS, x0 = blockIdx.x * TW;
+    // the cells under one item's two rows: to LDS and to the level-1 plane
+    auto finish = [&](int q, int rp, const T(&r0)[VEC], const T(&r1)[VEC], bool r0ok, bool r1ok, int rem) {
+        const int gy = y0 + 2 * rp, gx = x0 + q * VEC;
+        T res[HALF];
+#pragma unroll
+        for (int c = 0; c < HALF; ++c) {
+            const bool c0 = 2 * c < rem, c1 = 2 * c + 1 < rem;
+            res[c] = cell<T>(r0[2 * c], r0[2 * c + 1], r1[2 * c], r1[2 * c + 1], r0ok & c0, r0ok & c1, r1ok & c0, r1ok & c1,
+                             a.nd_mode, a.nodata, fill);
+        }
+        uint2 packed;
+        __builtin_memcpy(&packed, res, 8);
+        *reinterpret_cast<uint2*>(&lds_a[rp * (TW / 2) + q * HALF]) = packed;
+        const int ox = gx >> 1;
+        T* __restrict__ o = out1 + (long long)(gy >> 1) * a.out_stride[0] + ox;
+        if (r0ok && a.out_vec_ok && ox + HALF <= w1) {
+            *reinterpret_cast<uint2*>(o) = packed;
+        } else if (r0ok) {
+#pragma unroll
+            for (int c = 0; c < HALF; ++c)
+                if (ox + c < w1) o[c] = res[c];
+        }
+    };
+    if constexpr (INTERIOR) {
+        T r0[NIT][VEC], r1[NIT][VEC];
+#pragma unroll
+        for (int k = 0; k < NIT; ++k) {
+            const int item = threadIdx.x + k * OVW_THREADS;
+            const T* __restrict__ p = plane + (long long)(y0 + 2 * (item / QPR)) * a.stride + x0 + (item % QPR) * VEC;
+            load_row<T>(p, VEC, true, true, r0[k]);
+            load_row<T>(p + a.stride, VEC, true, true, r1[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < NIT; ++k) {
+            const int item = threadIdx.x + k * OVW_THREADS;
+            finish(item % QPR, item / QPR, r0[k], r1[k], true, true, VEC);
+        }
+    } else {
+        for (int item = threadIdx.x; item < ITEMS; item += OVW_THREADS) {
+            const int q = item % QPR, rp = item / QPR;
+            const int gy = y0 + 2 * rp, gx = x0 + q * VEC;
+            const bool r0ok = gy < a.height, r1ok = gy + 1 < a.height;
+            const T* __restrict__ p = plane + (long long)gy * a.stride + gx;
+            T r0[VEC], r1[VEC];
+            load_row<T>(p, a.width - gx, r0ok, a.vec_ok, r0);
+            load_row<T>(p + a.stride, a.width - gx, r1ok, a.vec_ok, r1);
+            finish(q, rp, r0, r1, r0ok, r1ok, a.width - gx);
+        }
+    }
+}
+
+}  // namespace
+
+template <class T>
+__global__ void __launch_bounds__(OVW_THREADS) overview_kernel(const OverviewArgs a) {
+    constexpr int TW = Tile<T>::TW;
+    static_assert(Tile<T>::VEC / 2 * sizeof(T) == 8, "a lane's level-1 pixels are one 8-byte store");
+    __shared__ __attribute__((aligned(16))) T lds_a[(OVW_ROWS / 2) * (TW / 2)];
+    __shared__ __attribute__((aligned(16))) T lds_b[(OVW_ROWS / 4) * (TW / 4)];
+    const int band = blockIdx.z;
+    const T* __restrict__ plane = static_cast<const T*>(a.src) + (long long)band * a.band_stride;
+    T* __restrict__ out1 = static_cast<T*>(a.out[0]) + (long long)band * a.out_band_stride[0];
+    const T fill = (a.nd_mode == 0) ? T(0) : (T)a.nodata;
+    const int y0 = blockIdx.y * OVW_ROWS, x0 = blockIdx.x * TW;
+    if (a.vec_ok && y0 + OVW_ROWS <= a.height && x0 + TW <= a.width)
+        level_one<true, T>(a, plane, out1, lds_a, fill);
+    else
+        level_one<false, T>(a, plane, out1, lds_a, fill);
+    if (a.n_levels < 2) return;
+    __syncthreads();
+    level_step<2, T>(a, lds_a, lds_b, band, fill);
+    if (a.n_levels < 3) return;
+    __syncthreads();
+    level_step<3, T>(a, lds_b, lds_a, band, fill);
+    if (a.n_levels < 4) return;
+    __syncthreads();
+    level_step<4, T>(a, lds_a, lds_b, band, fill);
+    if (a.n_levels < 5) return;
+    __syncthreads();
+    level_step<5, T>(a, lds_b, lds_a, band, fill);
+    if (a.n_levels < 6) return;
+    __syncthreads();
+    level_step<6, T>(a, lds_a, lds_b, band, fill);
+}
+
+namespace {
+
+template <class T>
+int tile_width() { return Tile<T>::TW; }
+
+bool aligned_to(const void* p, long long stride, long long band_stride, int esize, int bytes) {
+    return ((uintptr_t)p % bytes == 0) && ((stride * esize) % bytes == 0) && ((band_stride * esize) % bytes == 0);
+}
+
+}  // namespace
+
+hipError_t launch_overviews(int dtype, const void* src, int height, int width, long long stride, long long band_stride,
+                            int n_bands, int nd_mode, double nodata, int n_levels, void* const* out, const long long* out_stride,
+                            const long long* out_band_stride, hipStream_t stream) {
+    const int esize = dtype_size(dtype);
+    if (!esize) return hipErrorInvalidValue;
+    const bool is_float = dtype == 0 || dtype == 6;
+    for (int l0 = 0; l0 < n_levels; l0 += OVERVIEW_PASS_LEVELS) {
+        OverviewArgs a;
+        memset(&a, 0, sizeof(a));
+        a.src = src, a.height = height, a.width = width, a.stride = stride, a.band_stride = band_stride;
+        a.nd_mode = (!is_float && nd_mode == 1) ? 0 : nd_mode;  // an integer never is NaN
+        a.nodata = dtype == 0 ? (double)(float)nodata : nodata;
+        a.n_levels = n_levels - l0 < OVERVIEW_PASS_LEVELS ? n_levels - l0 : OVERVIEW_PASS_LEVELS;
+        for (int k = 0; k < a.n_levels; ++k)
+            a.out[k] = out[l0 + k], a.out_stride[k] = out_stride[l0 + k], a.out_band_stride[k] = out_band_stride[l0 + k];
+        a.vec_ok = aligned_to(src, stride, band_stride, esize, 16);
+        a.out_vec_ok = aligned_to(a.out[0], a.out_stride[0], a.out_band_stride[0], esize, 8);
+        const int tw = esize >= 4 ? tile_width<float>() : (esize == 2 ? tile_width<short>() : tile_width<unsigned char>());
+        const dim3 grid((width + tw - 1) / tw, (height + OVW_ROWS - 1) / OVW_ROWS, n_bands), block(OVW_THREADS);
+        switch (dtype) {
+            case 0: HK_LAUNCH(overview_kernel<float>, grid, block, 0, stream, a); break;
+            case 1: HK_LAUNCH(overview_kernel<unsigned char>, grid, block, 0, stream, a); break;
+            case 2: HK_LAUNCH(overview_kernel<unsigned short>, grid, block, 0, stream, a); break;
+            case 3: HK_LAUNCH(overview_kernel<short>, grid, block, 0, stream, a); break;
+            case 4: HK_LAUNCH(overview_kernel<unsigned int>, grid, block, 0, stream, a); break;
+            case 5: HK_LAUNCH(overview_kernel<int>, grid, block, 0, stream, a); break;
+            default: HK_LAUNCH(overview_kernel<double>, grid, block, 0, stream, a); break;
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        const int k = a.n_levels;  // the next pass reads the coarsest level of this one
+        src = a.out[k - 1], stride = a.out_stride[k - 1], band_stride = a.out_band_stride[k - 1];
+        height = (int)(((long long)height + (1 << k) - 1) >> k), width = (int)(((long long)width + (1 << k) - 1) >> k);
+    }
+    return hipSuccess;
+}
+
+}  // namespace hk

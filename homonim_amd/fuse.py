@@ -487,7 +487,12 @@ class RasterFuse:
         ``(corrected, params)``: float32 arrays (bands, H, W) and (n_param_bands * bands, H, W) or None.  When
         ``corr_filename`` / ``param_filename`` are paths the arrays are also written there: ``.tif`` as a tiled DEFLATE
         GeoTIFF with the reference's FUSE_* provenance tags (homonim_amd/tiff.py), anything else with ``numpy.save``
-        (``build_ovw`` and ``out_profile['driver'|'creation_options']`` are accepted and ignored).  With ``world_size > 1`` only this rank's blocks are filled in (others stay nodata).
+        (``out_profile['driver'|'creation_options']`` are accepted and ignored).  ``build_ovw`` (default, as in the reference:
+        fuse.py:152-165): a ``.tif`` gets internal overviews -- ``overview_factors(shape)``: factors 2, 4, ... while the shorter
+        side keeps 256 pixels, ``Resampling.average`` cascaded level to level, built on the GPU (``Context.overviews``) from the
+        finished rasters under their own dtype and nodata; a raster too small for a level, ``build_ovw=False`` and ``.npy``
+        outputs give the file without them.  The returned arrays are the same either way.
+        With ``world_size > 1`` only this rank's blocks are filled in (others stay nodata).
         ``corr_out``: a caller-owned corrected raster (bands, H, W) of the output dtype to fill instead of a new one, e.g.
         page-locked memory of a pipeline that processes many rasters (it is NOT pre-filled with nodata).
         """
@@ -542,8 +547,14 @@ class RasterFuse:
         # on request: page-lock the rasters in place for the duration of the block loop (direct copies); by default pageable
         # rasters go through the context's pinned staging ring (hk_api.hip stage_h2d / stage_d2h) block by block
         pinned = self._pin(models[0].context, [self._src, self._ref, corr, params]) if device_config['pin'] else []
+        corr_ovw = param_ovw = None
         try:
             self._run_blocks(blocks, models, process_block, corr, params, nodata, block_config)
+            # internal overviews of the files to be written, while the rasters are still page-locked (direct copies)
+            if build_ovw and self._is_tiff(corr_filename):
+                corr_ovw = self._overviews(models[0].context, corr, nodata)
+            if build_ovw and want_params and self._is_tiff(param_filename):
+                param_ovw = self._overviews(models[0].context, params, float('nan'))
         finally:
             for arr in pinned:
                 try:
@@ -560,10 +571,11 @@ class RasterFuse:
                         FUSE_MODEL=model_type.name, FUSE_KERNEL_SHAPE=tuple(kernel_shape),
                         **{f'FUSE_{k.upper()}': getattr(v, 'name', v) for k, v in model_config.items()})
             if isinstance(corr_filename, (str, os.PathLike)):
-                self._save(corr_filename, corr, self._transform, nodata, meta)
+                self._save(corr_filename, corr, self._transform, nodata, meta, overviews=corr_ovw)
             if want_params and isinstance(param_filename, (str, os.PathLike)):
                 param_tf = self._ref_transform if (self._proc_crs == ProcCrs.ref and not self._same_grid) else self._transform
-                self._save(param_filename, params, param_tf, float('nan'), meta, self._param_descriptions(n_param))
+                self._save(param_filename, params, param_tf, float('nan'), meta, self._param_descriptions(n_param),
+                           overviews=param_ovw)
         return corr, params
 
     @staticmethod
@@ -609,16 +621,39 @@ class RasterFuse:
         names = [(self._ref_descriptions[bi] if bi < len(self._ref_descriptions) else None) or f'B{bi + 1}' for bi in range(n_src)]
         return [f'{name}_{param}' for param in ('GAIN', 'OFFSET', 'R2')[:n_param] for name in names]
 
+    @staticmethod
+    def _is_tiff(filename) -> bool:
+        return isinstance(filename, (str, os.PathLike)) and os.fspath(filename).lower().endswith(('.tif', '.tiff'))
+
+    @staticmethod
+    def _overviews(ctx, array: np.ndarray, nodata) -> Optional[List[np.ndarray]]:
+        """ The internal overviews of a finished (bands, H, W) raster (homonim/fuse.py:152-165), finest first; None when the
+        raster is too small for one. """
+        n_levels = len(overview_factors(array.shape[-2:]))
+        return ctx.overviews(array, nodata, n_levels) if n_levels else None
+
     def _save(self, filename, array: np.ndarray, transform: Affine, nodata, metadata: Dict,
-              descriptions: Optional[List[str]] = None):
-        """ ``.tif`` / ``.tiff``: tiled DEFLATE GeoTIFF like the reference's default output profile (no overviews);
-        anything else: ``numpy.save``. """
-        if os.fspath(filename).lower().endswith(('.tif', '.tiff')):
+              descriptions: Optional[List[str]] = None, overviews: Optional[List[np.ndarray]] = None):
+        """ ``.tif`` / ``.tiff``: tiled DEFLATE GeoTIFF like the reference's default output profile, with ``overviews`` as its
+        internal overviews when given; anything else: ``numpy.save``. """
+        if self._is_tiff(filename):
             from homonim_amd.tiff import write_tiff
             write_tiff(filename, array, transform, self._crs, nodata, {k: str(v) for k, v in metadata.items()},
-                       descriptions=descriptions)
+                       descriptions=descriptions, overviews=overviews)
         else:
             np.save(filename, array)
+
+
+def overview_factors(shape: Sequence[int], max_num_levels: int = 8, min_level_pixels: int = 256) -> List[int]:
+    """ The decimation factors of the internal overviews of a raster of ``shape`` (rows, columns), as
+    ``RasterFuse._build_overviews`` picks them (homonim/fuse.py:152-165): successive powers of 2 such that the coarsest level
+    keeps at least ``min_level_pixels`` along the shorter dimension, ``max_num_levels`` at most; ``[]`` for a small raster. """
+    height, width = int(shape[-2]), int(shape[-1])
+    if height < 1 or width < 1:
+        return []
+    max_ovw_levels = min(height, width).bit_length() - 1   # int(min(log2(shape))), exactly
+    n = min(int(max_num_levels), max_ovw_levels - int(math.log2(min_level_pixels)))
+    return [2 ** m for m in range(1, n + 1)]
 
 
 def convert_dtype(array: np.ndarray, dtype: str, nodata: Optional[float]) -> np.ndarray:

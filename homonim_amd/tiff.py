@@ -8,13 +8,14 @@ and IEEE float samples; north-up geo-referencing from ModelPixelScale + ModelTie
 from GDAL_NODATA; EPSG code / citation from the GeoKey directory; the ``<GDALMetadata>`` items (where the reference keeps
 its FUSE_* provenance, fuse.py:193-207) and the per-band ``DESCRIPTION`` items among them (the band names of a parameter
 file, fuse.py:241-248).  The writer produces tiled, DEFLATE, band-separate files like the reference's
-default output profile.  Everything else (other compressions, rotated grids, overviews, palettes) raises.
+default output profile, with internal overviews (reduced-resolution images chained behind the first) on request;
+``read_tiff_overviews`` reads those back.  Everything else (other compressions, rotated grids, palettes) raises.
 """
 import mmap
 import re
 import struct
 import zlib
-from typing import Dict, NamedTuple, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 from xml.sax.saxutils import escape, unescape
 
 import numpy as np
@@ -27,6 +28,7 @@ _TYPES = {1: 'B', 2: 'c', 3: 'H', 4: 'I', 5: 'II', 6: 'b', 7: 'B', 8: 'h', 9: 'i
 _SAMPLE_DTYPES = {(1, 8): 'u1', (1, 16): 'u2', (1, 32): 'u4', (1, 64): 'u8', (2, 8): 'i1', (2, 16): 'i2', (2, 32): 'i4',
                   (2, 64): 'i8', (3, 32): 'f4', (3, 64): 'f8'}
 
+T_SUBFILE = 254   # NewSubfileType: bit 0 = reduced-resolution version of another image of the file
 T_WIDTH, T_HEIGHT, T_BITS, T_COMPRESSION, T_PHOTOMETRIC, T_STRIP_OFFSETS, T_SPP, T_ROWS_PER_STRIP = 256, 257, 258, 259, 262, 273, 277, 278
 T_STRIP_COUNTS, T_PLANAR, T_PREDICTOR, T_TILE_W, T_TILE_H, T_TILE_OFFSETS, T_TILE_COUNTS, T_EXTRA, T_FORMAT = 279, 284, 317, 322, 323, 324, 325, 338, 339
 T_PIXEL_SCALE, T_TIEPOINT, T_TRANSFORMATION, T_GEOKEYS, T_GEODOUBLES, T_GEOASCII, T_GDAL_METADATA, T_GDAL_NODATA = 33550, 33922, 34264, 34735, 34736, 34737, 42112, 42113
@@ -54,7 +56,8 @@ class TiffHeader(NamedTuple):
     descriptions: Tuple[Optional[str], ...]
 
 
-def _read_ifd(buf: bytes):
+def _read_ifd(buf: bytes, offset: Optional[int] = None):
+    """ -> (byte order, tags, offset of the next directory or 0) of the directory at ``offset`` (None: the file's first) """
     if buf[:2] == b'II':
         bo = '<'
     elif buf[:2] == b'MM':
@@ -64,9 +67,11 @@ def _read_ifd(buf: bytes):
     magic = struct.unpack(bo + 'H', buf[2:4])[0]
     if magic == 42:
         big, (off,) = False, struct.unpack(bo + 'I', buf[4:8])
+        off = off if offset is None else offset
         n, pos, esz, cfmt, vsz = struct.unpack(bo + 'H', buf[off:off + 2])[0], off + 2, 12, 'I', 4
     elif magic == 43:
         big, (off,) = True, struct.unpack(bo + 'Q', buf[8:16])
+        off = off if offset is None else offset
         n, pos, esz, cfmt, vsz = struct.unpack(bo + 'Q', buf[off:off + 8])[0], off + 8, 20, 'Q', 8
     else:
         raise IoError('not a TIFF file')
@@ -91,7 +96,8 @@ def _read_ifd(buf: bytes):
             tags[code] = tuple(v[2 * k] / v[2 * k + 1] if v[2 * k + 1] else 0. for k in range(count))
         else:
             tags[code] = struct.unpack(bo + item * count, raw)
-    return bo, tags
+    (next_off,) = struct.unpack(bo + cfmt, buf[pos + n * esz: pos + n * esz + vsz])
+    return bo, tags, next_off
 
 
 def _geo(tags, height):
@@ -174,7 +180,7 @@ def read_tiff_header(path) -> TiffHeader:
         except ValueError:   # an empty file cannot be mapped
             raise IoError('not a TIFF file')
         with buf:
-            bo, t = _read_ifd(buf)
+            bo, t, _ = _read_ifd(buf)
     if T_WIDTH not in t or T_HEIGHT not in t:
         raise IoError('not a TIFF file')
     w, h = t[T_WIDTH][0], t[T_HEIGHT][0]
@@ -190,7 +196,30 @@ def read_tiff(path) -> TiffRaster:
     """ Read the first image of a GeoTIFF into a (bands, height, width) array. """
     with open(path, 'rb') as f:
         buf = f.read()
-    bo, t = _read_ifd(buf)
+    bo, t, _ = _read_ifd(buf)
+    out = _decode_image(buf, bo, t)
+    tf, crs = _geo(t, out.shape[1])
+    return TiffRaster(out, tf, crs, _nodata_tag(t), _metadata(t), _descriptions(t, out.shape[0]))
+
+
+def read_tiff_overviews(path) -> List[np.ndarray]:
+    """ The internal overviews of a GeoTIFF: the reduced-resolution images (NewSubfileType bit 0) chained behind the first, in
+    file order, each as a (bands, height, width) array.  ``[]`` for a file without any. """
+    with open(path, 'rb') as f:
+        buf = f.read()
+    bo, t, nxt = _read_ifd(buf)
+    out, seen = [], set()
+    while nxt and nxt not in seen:
+        seen.add(nxt)
+        bo, t, following = _read_ifd(buf, nxt)
+        if t.get(T_SUBFILE, (0,))[0] & 1:
+            out.append(_decode_image(buf, bo, t))
+        nxt = following
+    return out
+
+
+def _decode_image(buf, bo, t) -> np.ndarray:
+    """ The pixels of the image a directory describes, (bands, height, width) in native byte order """
     w, h = t[T_WIDTH][0], t[T_HEIGHT][0]
     spp = t.get(T_SPP, (1,))[0]
     bits = t.get(T_BITS, (1,))
@@ -230,17 +259,69 @@ def read_tiff(path) -> TiffRaster:
             out[plane, y0:y0 + hh, x0:x0 + ww] = block[:hh, :ww, 0]
         else:
             out[:, y0:y0 + hh, x0:x0 + ww] = np.moveaxis(block[:hh, :ww, :], 2, 0)
-    tf, crs = _geo(t, h)
-    return TiffRaster(out, tf, crs, _nodata_tag(t), _metadata(t), _descriptions(t, spp))
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+OVERVIEW_TILE = 128   # GDAL's default block size of overviews (GDAL_TIFF_OVR_BLOCKSIZE)
+
+
+def _tile_chunks(a: np.ndarray, tile: int, compress: bool) -> List[bytes]:
+    nb, h, w = a.shape
+    across, down = -(-w // tile), -(-h // tile)
+    chunks = []
+    for b in range(nb):
+        for by in range(down):
+            for bx in range(across):
+                blk = np.zeros((tile, tile), a.dtype)
+                part = a[b, by * tile:(by + 1) * tile, bx * tile:(bx + 1) * tile]
+                blk[:part.shape[0], :part.shape[1]] = part
+                raw = blk.tobytes()
+                chunks.append(zlib.compress(raw, 6) if compress else raw)
+    return chunks
+
+
+def _directory(entries, chunks, ifd_off: int, has_next: bool) -> Tuple[bytes, int]:
+    """ One image of a classic TIFF placed at ``ifd_off``: directory, the values that do not fit an entry, tile data.
+    -> (bytes, offset just behind them: where the next directory goes) """
+    entries = sorted(entries, key=lambda e: e[0])
+    ifd_size = 2 + 12 * len(entries) + 4
+    extra_off = ifd_off + ifd_size
+    placed = {}
+    for code, typ, count, payload in entries:
+        if len(payload) > 4:
+            placed[code] = extra_off
+            extra_off += len(payload) + len(payload) % 2
+    offsets, pos = [], extra_off
+    for c in chunks:
+        offsets.append(pos)
+        pos += len(c) + (len(c) % 2)
+    if pos >= 2 ** 32:
+        raise IoError('raster too large for a classic TIFF (BigTIFF writing is not built)')
+    off_payload = struct.pack('<' + 'I' * len(offsets), *offsets)
+    entries = [(code, typ, count, off_payload if code == T_TILE_OFFSETS else payload) for code, typ, count, payload in entries]
+    parts = [struct.pack('<H', len(entries))]
+    for code, typ, count, payload in entries:
+        parts.append(struct.pack('<HHI', code, typ, count))
+        parts.append(payload.ljust(4, b'\0') if len(payload) <= 4 else struct.pack('<I', placed[code]))
+    parts.append(struct.pack('<I', pos if has_next else 0))
+    for code, typ, count, payload in entries:
+        if len(payload) > 4:
+            parts.append(payload + b'\0' * (len(payload) % 2))
+    for c in chunks:
+        parts.append(c + b'\0' * (len(c) % 2))
+    return b''.join(parts), pos
+
+
 def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = None, nodata: Optional[float] = None,
                metadata: Optional[Dict[str, str]] = None, tile: int = 512, compress: bool = True,
-               descriptions: Optional[Sequence[Optional[str]]] = None):
+               descriptions: Optional[Sequence[Optional[str]]] = None, overviews: Optional[Sequence[np.ndarray]] = None):
     """ Write (bands, height, width) as a classic little-endian GeoTIFF: tiled, DEFLATE, band-separate -- the reference's
     default output profile (homonim/fuse.py:124-149: tiled 512 x 512, compress=deflate, interleave=band).  ``descriptions``:
-    one band description per band (None: none for that band), written as GDAL writes them. """
+    one band description per band (None: none for that band), written as GDAL writes them.  ``overviews``: the internal
+    overviews (homonim/fuse.py:152-165), finest first, each (bands, h_m, w_m) of the raster's dtype: one directory per level
+    chained behind the main image's, NewSubfileType = 1, 128-pixel tiles, the main image's sample format, planar
+    configuration and compression, GDAL_NODATA and no geo tags.  The main image is written the same with and without them. """
     a = np.asarray(array)
     if a.ndim == 2:
         a = a[None]
@@ -252,39 +333,45 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
         raise IoError('rotated / sheared grids are not supported')
     fmt, bits = key
     nb, h, w = a.shape
+    levels = []
+    for lv in (overviews or ()):
+        lv = np.asarray(lv)
+        lv = lv[None] if lv.ndim == 2 else lv
+        if lv.ndim != 3 or lv.shape[0] != nb or lv.dtype != a.dtype or lv.size == 0:
+            raise ValueError(f'an overview of shape {lv.shape}, dtype {lv.dtype} for a raster of {nb} band(s), dtype {a.dtype}')
+        levels.append(lv.astype(lv.dtype.newbyteorder('<'), copy=False))
     a = a.astype(a.dtype.newbyteorder('<'), copy=False)
     tile = max(16, (int(tile) + 15) // 16 * 16)
-    across, down = -(-w // tile), -(-h // tile)
-    chunks = []
-    for b in range(nb):
-        for by in range(down):
-            for bx in range(across):
-                blk = np.zeros((tile, tile), a.dtype)
-                part = a[b, by * tile:(by + 1) * tile, bx * tile:(bx + 1) * tile]
-                blk[:part.shape[0], :part.shape[1]] = part
-                raw = blk.tobytes()
-                chunks.append(zlib.compress(raw, 6) if compress else raw)
 
     def ascii_(s):
         return s.encode('latin-1', 'replace') + b'\0'
 
-    entries = []  # (code, type, count, payload bytes)
+    def image_entries(img, img_tile, chunks, reduced):
+        entries = []  # (code, type, count, payload bytes)
 
-    def add(code, typ, values):
-        if typ == 2:
-            payload = ascii_(values)
-            entries.append((code, 2, len(payload), payload))
-        else:
-            payload = struct.pack('<' + _TYPES[typ] * len(values), *values)
-            entries.append((code, typ, len(values), payload))
+        def add(code, typ, values):
+            if typ == 2:
+                payload = ascii_(values)
+                entries.append((code, 2, len(payload), payload))
+            else:
+                payload = struct.pack('<' + _TYPES[typ] * len(values), *values)
+                entries.append((code, typ, len(values), payload))
 
-    add(T_WIDTH, 4, [w]), add(T_HEIGHT, 4, [h]), add(T_BITS, 3, [bits] * nb)
-    add(T_COMPRESSION, 3, [8 if compress else 1]), add(T_PHOTOMETRIC, 3, [1]), add(T_SPP, 3, [nb]), add(T_PLANAR, 3, [2])
-    add(T_TILE_W, 4, [tile]), add(T_TILE_H, 4, [tile])
-    add(T_TILE_OFFSETS, 4, [0] * len(chunks)), add(T_TILE_COUNTS, 4, [len(c) for c in chunks])
-    if nb > 1:
-        add(T_EXTRA, 3, [0] * (nb - 1))
-    add(T_FORMAT, 3, [fmt] * nb)
+        if reduced:
+            add(T_SUBFILE, 4, [1])
+        add(T_WIDTH, 4, [img.shape[2]]), add(T_HEIGHT, 4, [img.shape[1]]), add(T_BITS, 3, [bits] * nb)
+        add(T_COMPRESSION, 3, [8 if compress else 1]), add(T_PHOTOMETRIC, 3, [1]), add(T_SPP, 3, [nb]), add(T_PLANAR, 3, [2])
+        add(T_TILE_W, 4, [img_tile]), add(T_TILE_H, 4, [img_tile])
+        add(T_TILE_OFFSETS, 4, [0] * len(chunks)), add(T_TILE_COUNTS, 4, [len(c) for c in chunks])
+        if nb > 1:
+            add(T_EXTRA, 3, [0] * (nb - 1))
+        add(T_FORMAT, 3, [fmt] * nb)
+        if nodata is not None:
+            add(T_GDAL_NODATA, 2, 'nan' if (isinstance(nodata, float) and np.isnan(nodata)) else repr(float(nodata)) if a.dtype.kind == 'f' else str(int(nodata)))
+        return entries, add
+
+    chunks = _tile_chunks(a, tile, compress)
+    entries, add = image_entries(a, tile, chunks, False)
     add(T_PIXEL_SCALE, 12, [float(transform.a), float(-transform.e), 0.])
     add(T_TIEPOINT, 12, [0., 0., 0., float(transform.c), float(transform.f), 0.])
     name = crs.to_string() if crs is not None else ''
@@ -303,40 +390,18 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
         items += ''.join(f'  <Item name="DESCRIPTION" sample="{i}" role="description">{escape(str(d))}</Item>\n'
                          for i, d in enumerate(descriptions or ()) if d is not None)
         add(T_GDAL_METADATA, 2, f'<GDALMetadata>\n{items}</GDALMetadata>\n')
-    if nodata is not None:
-        add(T_GDAL_NODATA, 2, 'nan' if (isinstance(nodata, float) and np.isnan(nodata)) else repr(float(nodata)) if a.dtype.kind == 'f' else str(int(nodata)))
-    entries.sort(key=lambda e: e[0])
 
-    ifd_off = 8
-    ifd_size = 2 + 12 * len(entries) + 4
-    extra_off = ifd_off + ifd_size
-    extras, placed = [], {}
-    for code, typ, count, payload in entries:
-        if len(payload) > 4:
-            placed[code] = extra_off
-            pad = payload + b'\0' * (len(payload) % 2)
-            extras.append(pad)
-            extra_off += len(pad)
-    data_off = extra_off
-    offsets, pos = [], data_off
-    for c in chunks:
-        offsets.append(pos)
-        pos += len(c) + (len(c) % 2)
-    if pos >= 2 ** 32:
-        raise IoError('raster too large for a classic TIFF (BigTIFF writing is not built)')
-    off_payload = struct.pack('<' + 'I' * len(offsets), *offsets)
+    # the images one behind the other, each directory in front of its own data: the main image lies where it does without
+    # overviews, and the 4 GiB bound of a classic TIFF is checked on every offset up to the file's end
+    blobs = []
+    blob, pos = _directory(entries, chunks, 8, bool(levels))
+    blobs.append(blob)
+    for k, lv in enumerate(levels):
+        lv_chunks = _tile_chunks(lv, OVERVIEW_TILE, compress)
+        lv_entries, _ = image_entries(lv, OVERVIEW_TILE, lv_chunks, True)
+        blob, pos = _directory(lv_entries, lv_chunks, pos, k + 1 < len(levels))
+        blobs.append(blob)
     with open(path, 'wb') as f:
-        f.write(b'II' + struct.pack('<HI', 42, ifd_off))
-        f.write(struct.pack('<H', len(entries)))
-        for code, typ, count, payload in entries:
-            if code == T_TILE_OFFSETS:
-                payload = off_payload
-            f.write(struct.pack('<HHI', code, typ, count))
-            f.write(payload.ljust(4, b'\0') if len(payload) <= 4 else struct.pack('<I', placed[code]))
-        f.write(struct.pack('<I', 0))
-        for (code, typ, count, payload), _ in zip([e for e in entries if len(e[3]) > 4], extras):
-            if code == T_TILE_OFFSETS:
-                payload = off_payload
-            f.write(payload + b'\0' * (len(payload) % 2))
-        for c in chunks:
-            f.write(c + b'\0' * (len(c) % 2))
+        f.write(b'II' + struct.pack('<HI', 42, 8))
+        for blob in blobs:
+            f.write(blob)

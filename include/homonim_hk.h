@@ -70,9 +70,10 @@ typedef struct {
  * another must not call further: structs grow at their end between versions (hk_out_window: 32 -> 40 bytes in version 3) and
  * carry no size field; version 5 added entry points (hk_device_pci_bus_id; hk_debug_staging_counters in the devtools header); version 6: a raw
  * r2-mask failure counter is always a count (HK_COUNT_RETRY is never set any more), and a device-resident job that carries `scratch`
- * always gets the in-painting's inputs left there; version 7 added entry points (hk_param_stats, hk_param_stats_dev).
+ * always gets the in-painting's inputs left there; version 7 added entry points (hk_param_stats, hk_param_stats_dev); version 8
+ * added entry points (hk_overview_count, hk_overviews, hk_overviews_dev).
  * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
-#define HK_ABI_VERSION 7
+#define HK_ABI_VERSION 8
 int hk_abi_version(void);
 const char* hk_backend_name(void);            /* "hip-gfx950" */
 const char* hk_last_error(void);              /* thread-local text of the last failure */
@@ -115,6 +116,21 @@ int hk_compare_sums(hk_ctx* ctx, const float* src, int64_t src_stride, int32_t s
  * sums and counts, union of boxes (row indices are relative to the strip). */
 int hk_param_stats(hk_ctx* ctx, const float* plane, int64_t stride, int32_t nodata_mode, float nodata, double thresh,
                    int32_t height, int32_t width, double stats_out[10]);
+
+/* The number of internal overviews RasterFuse.build_overviews gives a raster of this shape (homonim/fuse.py:152-165):
+ * n = min(8, int(min(log2(height), log2(width))) - 8), never below 0; the factors are 2^1 .. 2^n, so that the coarsest level
+ * keeps at least 256 pixels on the shorter side.  Plain host arithmetic (no device needed). */
+int hk_overview_count(int32_t height, int32_t width, int32_t* n);
+
+/* Average overviews of an n_bands x height x width raster of sample type `dtype` (hk_dtype, below) in host memory (plane b at
+ * planes + b * band_stride, `stride` elements between rows): level m = 1..n_levels, of shape (ceil(height / 2^m),
+ * ceil(width / 2^m)), into out[m - 1] (host; out_stride[m - 1] elements between rows, out_band_stride[m - 1] between planes).
+ * See hk_overviews_dev for the arithmetic.  The raster travels in strips of whole rows, each a multiple of 2^n_levels rows and at
+ * most 64 MiB over all bands (HK_OVERVIEW_STRIP_KB lowers the bound, for tests): no cell of any level straddles two strips, so
+ * neither the strip size nor the layout of the arrays changes a bit of the result. */
+int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                 int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels, void* const out[],
+                 const int64_t out_stride[], const int64_t out_band_stride[]);
 
 /* KernelModel.fit (homonim/kernel_model.py:411-440 -> _fit_gain :231-274, _fit_gain_blk_offset :276-303,
  * _fit_gain_offset :305-373, _r2_array :142-214).
@@ -389,6 +405,22 @@ int hk_compare_sums_dev(hk_ctx* ctx, const hk_dev_job* job, int32_t src_nodata_m
 int hk_param_stats_dev(hk_ctx* ctx, const float* planes_dev, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
                        int64_t band_stride, int32_t stream, int32_t nodata_mode, float nodata, double thresh, double* stats_dev);
 
+/* Average overviews (the internal overviews of homonim/fuse.py:152-165: factors 2, 4, ... with Resampling.average) of `n_bands`
+ * device-resident planes of sample type `dtype` (hk_dtype), all levels from one pass over the source, on pooled stream `stream`
+ * (asynchronous).  Level m = 1..n_levels has shape (ceil(height / 2^m), ceil(width / 2^m)) and is written to out_dev[m - 1]
+ * (device; strides in elements).  It is computed from level m - 1 as stored (level 0 = the raster), as GDAL cascades `average`:
+ * pixel (i, j) takes the pixels (2i..2i+1, 2j..2j+1) of level m - 1 that lie inside it and are valid under (nodata_mode, nodata)
+ * -- HK_NODATA_NONE: all, a NaN is data and propagates; HK_NODATA_NAN: not NaN (every pixel of an integer type); HK_NODATA_VALUE:
+ * not equal to `nodata` (an integer type: a value of the type; float32: compared after rounding it to float32).  A cell without
+ * a valid pixel gives nodata.  float32: the valid values are summed as float64 in row-major order, divided by their count in
+ * float64 and rounded once to float32 -- bit-identical to hk_reproject with Resampling.average on the mapping (2, 0, 2, 0);
+ * float64: the same without the rounding; integer types: floor((2 S + n) / (2 n)) of the exact sum S of the n valid values
+ * (round half up, GDAL's + 0.5).  GDAL >= 3.3 weights fractional source pixels where a dimension is odd; whole cells clipped at
+ * the edge are used here (the two agree for even sizes).  16-byte loads are used where the planes allow it; any other layout
+ * gives the same bits.  n_levels <= 31; a level past 1 x 1 repeats it. */
+int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                     int64_t stride, int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels,
+                     void* const out_dev[], const int64_t out_stride[], const int64_t out_band_stride[], int32_t stream);
 
 /* HIP events on the pooled streams, so callers time exactly the stream the kernels run on. */
 int hk_event_create(hk_ctx* ctx, hk_event** ev);
