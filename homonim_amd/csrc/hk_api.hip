@@ -1636,6 +1636,151 @@ int hk_reproject(hk_ctx* ctx, const float* src, int32_t n_bands, int32_t src_hei
     return stage_finish(sl);
 }
 
+static int check_nodata_mode(int32_t mode);
+
+int hk_reproject_dev(hk_ctx* ctx, const float* src_dev, int32_t n_bands, int32_t src_height, int32_t src_width,
+                     int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode, float src_nodata, double kx, double ox,
+                     double ky, double oy, int32_t resampling, float* dst_dev, int32_t dst_height, int32_t dst_width,
+                     int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    if (!src_dev || !dst_dev) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (n_bands < 1 || src_height < 1 || src_width < 1 || dst_height < 1 || dst_width < 1)
+        return fail(HK_ERR_ARG, "empty raster");
+    if (n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", n_bands);
+    if (src_stride < src_width || dst_stride < dst_width) return fail(HK_ERR_ARG, "row stride smaller than width");
+    if (src_band_stride < 0 || dst_band_stride < 0) return fail(HK_ERR_ARG, "band_stride is negative");
+    if (!(kx > 0.0) || !(ky > 0.0)) return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
+    if (!resampling_built(resampling)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not a warp method", resampling);
+    if (dst_height > 65535) return fail(HK_ERR_UNSUPPORTED, "destination taller than 65535 rows");
+    int rc = check_nodata_mode(src_nodata_mode);
+    if (rc) return rc;
+    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    DevEnter entered(ctx, stream);
+    HK_ENTER(ctx);
+    HK_HIP(hk::launch_resample(resampling, src_dev, src_stride, src_band_stride, src_height, src_width, n_bands, src_nodata_mode,
+                               src_nodata, kx, ox, ky, oy, dst_dev, dst_stride, dst_band_stride, dst_height, dst_width, dst_fill,
+                               ctx->slots[stream].stream));
+    return HK_OK;
+}
+
+// Re-sampling between grids of two CRSs (hk_warp.hip): see include/homonim_hk.h
+static int check_warp_lattice(hk_ctx* ctx, const hk_warp_desc* warp, int32_t height, int32_t width, const void* x, const void* y,
+                              int64_t stride) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    if (!warp || !x || !y) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (height < 1 || width < 1) return fail(HK_ERR_ARG, "empty lattice %d x %d", height, width);
+    if (height > 65535) return fail(HK_ERR_UNSUPPORTED, "lattice taller than 65535 rows");
+    if (stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
+    return HK_OK;
+}
+
+// hipErrorInvalidValue of the warp launchers carries a reason: an unusable descriptor (HK_ERR_ARG), or CRSs the warp is not
+// built for (different ellipsoids: HK_ERR_UNSUPPORTED)
+static int warp_launch_status(hipError_t e, const char* why) {
+    if (e == hipSuccess) return HK_OK;
+    (void)hipGetLastError();
+    if (e == hipErrorInvalidValue && why)
+        return fail(strstr(why, "ellipsoids") ? HK_ERR_UNSUPPORTED : HK_ERR_ARG, "warp: %s", why);
+    return fail(HK_ERR_HIP, "warp launch failed: %s", hipGetErrorString(e));
+}
+
+int hk_warp_coords_dev(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double off_col, int32_t height, int32_t width,
+                       double* x_dev, double* y_dev, int64_t stride, int32_t stream) {
+    int rc = check_warp_lattice(ctx, warp, height, width, x_dev, y_dev, stride);
+    if (rc) return rc;
+    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    DevEnter entered(ctx, stream);
+    HK_ENTER(ctx);
+    const char* why = nullptr;
+    return warp_launch_status(hk::launch_warp_coords(warp, off_row, off_col, x_dev, y_dev, stride, height, width,
+                                                     ctx->slots[stream].stream, &why), why);
+}
+
+int hk_warp_coords(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double off_col, int32_t height, int32_t width,
+                   double* x_out, double* y_out, int64_t stride) {
+    int rc = check_warp_lattice(ctx, warp, height, width, x_out, y_out, stride);
+    if (rc) return rc;
+    HK_ENTER(ctx);
+    const int64_t d_stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    SlabLayout L;
+    const size_t plane = (size_t)d_stride * height * sizeof(double);
+    const size_t o_x = L.take(plane), o_y = L.take(plane);
+    SlotLease lease(ctx);
+    Slot& sl = lease.slot();
+    if ((rc = ensure_dev(sl, L.total))) return rc;
+    char* base = static_cast<char*>(sl.dev);
+    const char* why = nullptr;
+    if ((rc = warp_launch_status(hk::launch_warp_coords(warp, off_row, off_col, reinterpret_cast<double*>(base + o_x),
+                                                        reinterpret_cast<double*>(base + o_y), d_stride, height, width, sl.stream,
+                                                        &why), why)))
+        return rc;
+    if ((rc = stage_d2h(sl, x_out, (size_t)stride * 8, base + o_x, (size_t)d_stride * 8, (size_t)width * 8, height))) return rc;
+    if ((rc = stage_d2h(sl, y_out, (size_t)stride * 8, base + o_y, (size_t)d_stride * 8, (size_t)width * 8, height))) return rc;
+    return stage_finish(sl);
+}
+
+static int check_reproject_crs(hk_ctx* ctx, const hk_warp_desc* warp, const float* src, int32_t n_bands, int32_t src_height,
+                               int32_t src_width, int32_t src_nodata_mode, double kx, double ky, int32_t resampling,
+                               const float* dst, int32_t dst_height, int32_t dst_width) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    if (!warp || !src || !dst) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (n_bands < 1 || src_height < 1 || src_width < 1 || dst_height < 1 || dst_width < 1)
+        return fail(HK_ERR_ARG, "empty raster");
+    if (!(kx > 0.0) || !(ky > 0.0) || !std::isfinite(kx) || !std::isfinite(ky))
+        return fail(HK_ERR_ARG, "kx, ky must be positive and finite");
+    if (!resampling_built(resampling))
+        return fail(HK_ERR_UNSUPPORTED, "resampling %d is not a warp method", resampling);
+    if (resampling > 4)
+        return fail(HK_ERR_UNSUPPORTED, "resampling %d works on a destination pixel's footprint, which is not built across CRSs "
+                                        "(nearest, bilinear, cubic, cubic_spline and lanczos are)", resampling);
+    if (dst_height > 65535) return fail(HK_ERR_UNSUPPORTED, "destination taller than 65535 rows");
+    return check_nodata_mode(src_nodata_mode);
+}
+
+int hk_reproject_crs_dev(hk_ctx* ctx, const hk_warp_desc* warp, const float* src_dev, int32_t n_bands, int32_t src_height,
+                         int32_t src_width, int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode,
+                         float src_nodata, double kx, double ky, int32_t resampling, float* dst_dev, int32_t dst_height,
+                         int32_t dst_width, int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream) {
+    int rc = check_reproject_crs(ctx, warp, src_dev, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst_dev,
+                                 dst_height, dst_width);
+    if (rc) return rc;
+    if (src_stride < src_width || dst_stride < dst_width) return fail(HK_ERR_ARG, "row stride smaller than width");
+    if (src_band_stride < 0 || dst_band_stride < 0) return fail(HK_ERR_ARG, "band_stride is negative");
+    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    DevEnter entered(ctx, stream);
+    HK_ENTER(ctx);
+    const char* why = nullptr;
+    return warp_launch_status(hk::launch_warp_resample(resampling, warp, src_dev, src_stride, src_band_stride, src_height,
+                                                       src_width, n_bands, src_nodata_mode, src_nodata, kx, ky, dst_dev,
+                                                       dst_stride, dst_band_stride, dst_height, dst_width, dst_fill,
+                                                       ctx->slots[stream].stream, &why), why);
+}
+
+int hk_reproject_crs(hk_ctx* ctx, const hk_warp_desc* warp, const float* src, int32_t n_bands, int32_t src_height,
+                     int32_t src_width, int32_t src_nodata_mode, float src_nodata, double kx, double ky, int32_t resampling,
+                     float* dst, int32_t dst_height, int32_t dst_width, float dst_fill) {
+    int rc = check_reproject_crs(ctx, warp, src, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst,
+                                 dst_height, dst_width);
+    if (rc) return rc;
+    HK_ENTER(ctx);
+    const size_t sbytes = (size_t)n_bands * src_height * src_width * 4, dbytes = (size_t)n_bands * dst_height * dst_width * 4;
+    const size_t o_dst = (sbytes + 255) / 256 * 256;
+    SlotLease lease(ctx);
+    Slot& sl = lease.slot();
+    if ((rc = ensure_dev(sl, o_dst + dbytes))) return rc;
+    float* d_src = static_cast<float*>(sl.dev);
+    float* d_dst = reinterpret_cast<float*>(static_cast<char*>(sl.dev) + o_dst);
+    if ((rc = stage_h2d(sl, d_src, sbytes, src, sbytes, sbytes, 1))) return rc;
+    const char* why = nullptr;
+    if ((rc = warp_launch_status(hk::launch_warp_resample(resampling, warp, d_src, src_width, (long long)src_height * src_width,
+                                                          src_height, src_width, n_bands, src_nodata_mode, src_nodata, kx, ky,
+                                                          d_dst, dst_width, (long long)dst_height * dst_width, dst_height,
+                                                          dst_width, dst_fill, sl.stream, &why), why)))
+        return rc;
+    if ((rc = stage_d2h(sl, dst, dbytes, d_dst, dbytes, dbytes, 1))) return rc;
+    return stage_finish(sl);
+}
+
 int hk_partial_mask(hk_ctx* ctx, const float* in, int64_t in_stride, int32_t in_nodata_mode, float in_nodata,
                     const float* params, int32_t n_param_bands, const float* src, int64_t src_stride, int32_t height,
                     int32_t width, int32_t kh, int32_t kw, float* params_out, float* corr_out, uint8_t* mask_out) {

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <string.h>
 
+struct hk_warp_desc;  // include/homonim_hk.h
+
 namespace hk {
 
 constexpr int PX = 4;      // pixels per lane per row (one 16-byte load)
@@ -299,6 +301,15 @@ hipError_t launch_resample(int mode, const float* src, long long src_stride, lon
                            int n_bands, int nd_mode, float nodata, double kx, double ox, double ky, double oy, float* dst,
                            long long dst_stride, long long dst_band_stride, int dh, int dw, float dst_fill,
                            hipStream_t stream);
+
+// Re-sampling between grids of two CRSs (hk_warp.hip): the continuous source pixel coordinates of destination positions, and
+// launch_resample's modes 0..4 on them.  `why` receives the reason when hipErrorInvalidValue is returned.
+hipError_t launch_warp_coords(const hk_warp_desc* desc, double off_row, double off_col, double* x, double* y, long long stride,
+                              int h, int w, hipStream_t stream, const char** why);
+hipError_t launch_warp_resample(int mode, const hk_warp_desc* desc, const float* src, long long src_stride,
+                                long long src_band_stride, int sh, int sw, int n_bands, int nd_mode, float nodata, double kx,
+                                double ky, float* dst, long long dst_stride, long long dst_band_stride, int dh, int dw,
+                                float dst_fill, hipStream_t stream, const char** why);
 
 size_t upsample_apply_workspace_bytes(int height);
 hipError_t launch_upsample_apply(int mode, const float* src, long long src_stride, int nd_mode, float nodata,

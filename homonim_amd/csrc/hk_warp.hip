@@ -1,0 +1,374 @@
+// hk_warp.hip -- re-sampling between grids of DIFFERENT coordinate reference systems: what the reference gets from GDAL when
+// utils.same_orientation_crs (homonim/utils.py:190-209) wraps the processing-grid image in a WarpedVRT, and RasterArray.reproject
+// (homonim/raster_array.py:526-578) with another `crs`.
+//
+// Per destination pixel: destination geo-transform -> destination CRS inverse -> (lon, lat) -> source CRS forward -> inverse
+// source geo-transform = continuous source pixel coordinates (integers = pixel edges), all in float64.  What is then done with
+// the coordinate is the per-tap arithmetic of hk_resample.hip, operation for operation (hk_resample_taps.h and the kernel bodies
+// below): only `sx, sy` come from warp_coord() instead of `k * (j + 0.5) + o`.  Every pixel is transformed exactly -- GDAL's
+// default warp interpolates the transformation linearly within 0.125 pixel.
+//
+// CRSs: geographic (degrees) and Transverse Mercator on one ellipsoid (no datum shifts).  Transverse Mercator is the Krueger
+// series in the third flattening n to n^6 (Karney 2011, "Transverse Mercator with an accuracy of a few nanometers", eqs. 35 / 36
+// for the alpha / beta coefficients): truncation < 1e-12 m on the WGS84 ellipsoid, far below float64 rounding of a 1e7 m
+// coordinate.  The six-term series are summed by one complex Clenshaw recurrence from a single sincos(2 xi) and exp(2 eta); the
+// inverse takes the conformal latitude to the geodetic one by Newton on tau = tan(phi) (Karney eqs. 7-9, 19-21), three steps from
+// tau' / (1 - e^2): the error squares per step from ~e^2, i.e. it is below 1e-20 after the third.
+//
+// The coordinate kernel (hk_warp_coords*) and the re-samplers call the same warp_coord() with the same arguments under
+// -ffp-contract=off: the coordinates a re-sampler uses are, bit for bit, the ones the coordinate kernel returns.
+#include "../../include/homonim_hk.h"
+#include "hk_kernels.h"
+#include "hk_resample_taps.h"
+
+#include <math.h>
+
+namespace hk {
+
+// One CRS, ready for the device.  Passed by value inside the kernel argument struct; alp / bet are indexed by unrolled constants only.
+struct CrsParams {
+    int kind;        // hk_crs_kind
+    double e, e2m;   // first eccentricity, 1 - e^2
+    double ka;       // k0 * A: scale factor x rectifying radius
+    double xi0;      // xi of the latitude of origin (northing origin on the conformal sphere)
+    double lon0;     // central meridian, degrees
+    double fe, fn;
+    double alp[6], bet[6];
+};
+
+struct WarpMap {
+    CrsParams src, dst;
+    double dx0, ddx, dy0, ddy;  // destination geo-transform: X = dx0 + col * ddx, Y = dy0 + row * ddy
+    double sx0, sdx, sy0, sdy;  // source geo-transform, inverted per pixel: col = (X - sx0) / sdx
+};
+
+constexpr double WARP_DEG = 57.295779513082320877;   // degrees per radian
+constexpr double WARP_COORD_MAX = 1e15;              // a source coordinate at or beyond this (or NaN) is "no data"
+
+// sum_j c[j] sin(2 (j + 1) (xi + i eta)), real and imaginary part (Clenshaw on the complex argument)
+__device__ __forceinline__ void tm_series(const double (&c)[6], double xi, double eta, double& re, double& im) {
+    double s0, c0;
+    sincos(2.0 * xi, &s0, &c0);
+    const double ex = exp(2.0 * eta), exi = 1.0 / ex;
+    const double ch0 = 0.5 * (ex + exi), sh0 = 0.5 * (ex - exi);
+    const double ar = 2.0 * (c0 * ch0), ai = -2.0 * (s0 * sh0);  // 2 cos(2 zeta)
+    double y0r = 0.0, y0i = 0.0, y1r = 0.0, y1i = 0.0;
+#pragma unroll
+    for (int j = 5; j >= 0; --j) {
+        const double tr = ar * y0r - ai * y0i - y1r + c[j];
+        const double ti = ar * y0i + ai * y0r - y1i;
+        y1r = y0r, y1i = y0i, y0r = tr, y0i = ti;
+    }
+    const double zr = s0 * ch0, zi = c0 * sh0;  // sin(2 zeta)
+    re = zr * y0r - zi * y0i;
+    im = zr * y0i + zi * y0r;
+}
+
+// tan of the conformal latitude from tan of the geodetic latitude
+__device__ __forceinline__ double tm_taup(double tau, double t1 /* sqrt(1 + tau^2) */, double e) {
+    const double sig = sinh(e * atanh(e * tau / t1));
+    return tau * sqrt(1.0 + sig * sig) - sig * t1;
+}
+
+// (lat, lon - lon0) in radians -> (easting, northing); false beyond 90 degrees from the central meridian
+__device__ __forceinline__ bool tm_forward(const CrsParams& c, double phi, double dlam, double& x, double& y) {
+    const double tau = tan(phi);
+    const double tp = tm_taup(tau, sqrt(1.0 + tau * tau), c.e);
+    double sl, cl;
+    sincos(dlam, &sl, &cl);
+    const double xip = atan2(tp, cl), etap = asinh(sl / hypot(tp, cl));
+    double zr, zi;
+    tm_series(c.alp, xip, etap, zr, zi);
+    x = c.fe + c.ka * (etap + zi);
+    y = c.fn + c.ka * ((xip + zr) - c.xi0);
+    return cl > 0.0;
+}
+
+// (easting, northing) -> (lat, lon - lon0) in radians
+__device__ __forceinline__ void tm_inverse(const CrsParams& c, double x, double y, double& phi, double& dlam) {
+    const double xi = (y - c.fn) / c.ka + c.xi0, eta = (x - c.fe) / c.ka;
+    double zr, zi;
+    tm_series(c.bet, xi, eta, zr, zi);
+    const double xip = xi - zr, etap = eta - zi;
+    double s, cx;
+    sincos(xip, &s, &cx);
+    const double sh = sinh(etap);
+    const double tp = s / hypot(sh, cx);
+    dlam = atan2(sh, cx);
+    double tau = tp / c.e2m;
+#pragma unroll
+    for (int it = 0; it < 3; ++it) {
+        const double t1 = sqrt(1.0 + tau * tau);
+        const double tpi = tm_taup(tau, t1, c.e);
+        tau += (tp - tpi) / sqrt(1.0 + tpi * tpi) * (1.0 + c.e2m * (tau * tau)) / (c.e2m * t1);
+    }
+    phi = atan(tau);
+}
+
+// a longitude (difference) in degrees brought to (-180, 180]
+__device__ __forceinline__ double wrap180(double d) {
+    d = remainder(d, 360.0);
+    return d <= -180.0 ? d + 360.0 : d;
+}
+
+// THE coordinate function: destination pixel position (row, col; continuous, integers = pixel edges) -> continuous source pixel
+// coordinates; NaN where the position has no image in the source CRS.
+__device__ __forceinline__ void warp_coord(const WarpMap& m, double row, double col, double& sx, double& sy) {
+    const double X = m.dx0 + col * m.ddx, Y = m.dy0 + row * m.ddy;
+    double lon, lat;  // degrees
+    bool ok = true;
+    if (m.dst.kind == HK_CRS_GEOGRAPHIC) {
+        lon = X, lat = Y;
+        ok = fabs(Y) <= 90.0;
+    } else {
+        double phi, dlam;
+        tm_inverse(m.dst, X, Y, phi, dlam);
+        lon = m.dst.lon0 + dlam * WARP_DEG, lat = phi * WARP_DEG;
+    }
+    double x, y;
+    if (m.src.kind == HK_CRS_GEOGRAPHIC) {
+        x = wrap180(lon), y = lat;
+    } else {
+        ok = tm_forward(m.src, lat / WARP_DEG, wrap180(lon - m.src.lon0) / WARP_DEG, x, y) && ok;
+    }
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    sx = ok ? (x - m.sx0) / m.sdx : nan;
+    sy = ok ? (y - m.sy0) / m.sdy : nan;
+}
+
+__device__ __forceinline__ bool warp_coord_usable(double sx, double sy) {
+    return fabs(sx) < WARP_COORD_MAX && fabs(sy) < WARP_COORD_MAX;  // false for NaN
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+struct WarpCoordArgs {
+    double* x;
+    double* y;
+    long long stride;
+    int h, w;
+    double off_row, off_col;
+    WarpMap map;
+};
+
+__global__ void __launch_bounds__(256) warp_coords_kernel(const WarpCoordArgs a) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= a.w) return;
+    double sx, sy;
+    warp_coord(a.map, (double)i + a.off_row, (double)j + a.off_col, sx, sy);
+    a.x[(long long)i * a.stride + j] = sx;
+    a.y[(long long)i * a.stride + j] = sy;
+}
+
+struct WarpArgs {
+    const float* src;
+    float* dst;
+    long long src_stride, src_band_stride, dst_stride, dst_band_stride;
+    int sh, sw, dh, dw, n_bands;
+    int nd_mode;
+    float nodata;
+    float dst_fill;
+    double kx, ky;  // source pixels per destination pixel (mean step): pick and scale the stretched kernels
+    WarpMap map;
+};
+
+// resample_kernel<0 / 1 / 3> of hk_resample.hip with warped coordinates; one thread per destination pixel, all bands
+template <int MODE>
+__global__ void __launch_bounds__(256) warp_kernel(const WarpArgs a) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= a.dw) return;
+    double sx, sy;
+    warp_coord(a.map, (double)i + 0.5, (double)j + 0.5, sx, sy);
+    const bool usable = warp_coord_usable(sx, sy);
+    const long long cy = usable ? (long long)floor(sy + 1e-10) : -1, cx = usable ? (long long)floor(sx + 1e-10) : -1;
+    const bool inside = cx >= 0 && cx < a.sw && cy >= 0 && cy < a.sh;
+    constexpr int NT = MODE == 1 ? 2 : 4, T0 = MODE == 1 ? 0 : -1;
+    int iy = 0, ix = 0;
+    double wys[4] = {0.0, 0.0, 0.0, 0.0}, wxs[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (MODE != 0) {
+        if (inside) {
+            iy = (int)floor(sy - 0.5), ix = (int)floor(sx - 0.5);
+            const double dy = sy - 0.5 - (double)iy, dx = sx - 0.5 - (double)ix;
+            if constexpr (MODE == 1) {
+                wys[0] = 1.0 - dy, wys[1] = dy, wxs[0] = 1.0 - dx, wxs[1] = dx;
+            } else {
+                bspline4(dy, wys);
+                bspline4(dx, wxs);
+            }
+        }
+    }
+    for (int b = 0; b < a.n_bands; ++b) {
+        const float* __restrict__ sp = a.src + (long long)b * a.src_band_stride;
+        double result = 0.0;
+        bool got = false;
+        if (inside) {
+            const float vc = sp[cy * a.src_stride + cx];
+            if (rs_valid(vc, a.nd_mode, a.nodata)) {
+                if constexpr (MODE == 0) {
+                    result = (double)vc, got = true;
+                } else {
+                    double acc = 0.0, wacc = 0.0;
+#pragma unroll
+                    for (int tj = 0; tj < NT; ++tj) {
+                        const int yy = iy + T0 + tj;
+                        if (yy < 0 || yy >= a.sh) continue;
+#pragma unroll
+                        for (int ti = 0; ti < NT; ++ti) {
+                            const int xx = ix + T0 + ti;
+                            if (xx < 0 || xx >= a.sw) continue;
+                            const float v = sp[(long long)yy * a.src_stride + xx];
+                            if (!rs_valid(v, a.nd_mode, a.nodata)) continue;
+                            const double wgt = wxs[ti] * wys[tj];
+                            acc += (double)v * wgt;
+                            wacc += wgt;
+                        }
+                    }
+                    if (!(wacc < 1e-6)) {
+                        result = (wacc < 0.99999 || wacc > 1.00001) ? acc / wacc : acc;
+                        got = true;
+                    }
+                }
+            }
+        }
+        a.dst[(long long)b * a.dst_band_stride + (long long)i * a.dst_stride + j] = got ? (float)result : a.dst_fill;
+    }
+}
+
+// resample_conv_kernel<1..4> of hk_resample.hip (GWKResample for any scale) with warped coordinates
+template <int KIND>
+__global__ void __launch_bounds__(256) warp_conv_kernel(const WarpArgs a) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= a.dw) return;
+    constexpr int R = KIND == 1 ? 1 : (KIND == 4 ? 3 : 2);
+    const double xs = a.kx > 1.0 ? 1.0 / a.kx : 1.0, ys = a.ky > 1.0 ? 1.0 / a.ky : 1.0;
+    const int rx = xs < 1.0 ? (int)ceil((double)R / xs) : R, ry = ys < 1.0 ? (int)ceil((double)R / ys) : R;
+    double sx, sy;
+    warp_coord(a.map, (double)i + 0.5, (double)j + 0.5, sx, sy);
+    const bool usable = warp_coord_usable(sx, sy);
+    const long long cy = usable ? (long long)floor(sy + 1e-10) : -1, cx = usable ? (long long)floor(sx + 1e-10) : -1;
+    const bool inside = cx >= 0 && cx < a.sw && cy >= 0 && cy < a.sh;
+    int iy = 0, ix = 0;
+    double dy = 0.0, dx = 0.0;
+    if (inside) {
+        iy = (int)floor(sy - 0.5), ix = (int)floor(sx - 0.5);
+        dy = sy - 0.5 - (double)iy, dx = sx - 0.5 - (double)ix;
+    }
+    for (int b = 0; b < a.n_bands; ++b) {
+        const float* __restrict__ sp = a.src + (long long)b * a.src_band_stride;
+        double result = 0.0;
+        bool got = false;
+        if (inside && rs_valid(sp[cy * a.src_stride + cx], a.nd_mode, a.nodata)) {
+            double acc = 0.0, wacc = 0.0;
+            for (int tj = 1 - ry; tj <= ry; ++tj) {
+                const int yy = iy + tj;
+                if (yy < 0 || yy >= a.sh) continue;
+                const double wy = conv_weight<KIND>(((double)tj - dy) * ys);
+                if (wy == 0.0) continue;
+                for (int ti = 1 - rx; ti <= rx; ++ti) {
+                    const int xx = ix + ti;
+                    if (xx < 0 || xx >= a.sw) continue;
+                    const float v = sp[(long long)yy * a.src_stride + xx];
+                    if (!rs_valid(v, a.nd_mode, a.nodata)) continue;
+                    const double wgt = conv_weight<KIND>(((double)ti - dx) * xs) * wy;
+                    acc += (double)v * wgt;
+                    wacc += wgt;
+                }
+            }
+            if (!(fabs(wacc) < 1e-6)) result = acc / wacc, got = true;
+        }
+        a.dst[(long long)b * a.dst_band_stride + (long long)i * a.dst_stride + j] = got ? (float)result : a.dst_fill;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host: descriptor -> device parameters
+
+static bool crs_params(const hk_crs_desc& d, CrsParams& p, const char** why) {
+    memset(&p, 0, sizeof(p));
+    p.kind = d.kind;
+    if (d.kind != HK_CRS_GEOGRAPHIC && d.kind != HK_CRS_TMERC) return *why = "unknown CRS kind", false;
+    if (!(d.a > 0.0) || !(d.inv_f == 0.0 || d.inv_f > 1.0) || !isfinite(d.a) || !isfinite(d.inv_f)) return *why = "bad ellipsoid", false;
+    p.lon0 = d.lon0, p.fe = d.fe, p.fn = d.fn;
+    if (d.kind == HK_CRS_GEOGRAPHIC) return true;
+    if (!(d.k0 > 0.0) || !isfinite(d.k0) || !(fabs(d.lat0) <= 90.0) || !isfinite(d.lon0) || !isfinite(d.fe) || !isfinite(d.fn))
+        return *why = "bad Transverse Mercator parameters", false;
+    const double f = d.inv_f == 0.0 ? 0.0 : 1.0 / d.inv_f, n = f / (2.0 - f);
+    const double n2 = n * n, n3 = n2 * n, n4 = n2 * n2, n5 = n4 * n, n6 = n3 * n3;
+    p.e = sqrt(f * (2.0 - f)), p.e2m = (1.0 - f) * (1.0 - f);
+    p.ka = d.k0 * (d.a / (1.0 + n) * (1.0 + n2 / 4.0 + n4 / 64.0 + n6 / 256.0));
+    p.alp[0] = n / 2.0 - 2.0 * n2 / 3.0 + 5.0 * n3 / 16.0 + 41.0 * n4 / 180.0 - 127.0 * n5 / 288.0 + 7891.0 * n6 / 37800.0;
+    p.alp[1] = 13.0 * n2 / 48.0 - 3.0 * n3 / 5.0 + 557.0 * n4 / 1440.0 + 281.0 * n5 / 630.0 - 1983433.0 * n6 / 1935360.0;
+    p.alp[2] = 61.0 * n3 / 240.0 - 103.0 * n4 / 140.0 + 15061.0 * n5 / 26880.0 + 167603.0 * n6 / 181440.0;
+    p.alp[3] = 49561.0 * n4 / 161280.0 - 179.0 * n5 / 168.0 + 6601661.0 * n6 / 7257600.0;
+    p.alp[4] = 34729.0 * n5 / 80640.0 - 3418889.0 * n6 / 1995840.0;
+    p.alp[5] = 212378941.0 * n6 / 319334400.0;
+    p.bet[0] = n / 2.0 - 2.0 * n2 / 3.0 + 37.0 * n3 / 96.0 - n4 / 360.0 - 81.0 * n5 / 512.0 + 96199.0 * n6 / 604800.0;
+    p.bet[1] = n2 / 48.0 + n3 / 15.0 - 437.0 * n4 / 1440.0 + 46.0 * n5 / 105.0 - 1118711.0 * n6 / 3870720.0;
+    p.bet[2] = 17.0 * n3 / 480.0 - 37.0 * n4 / 840.0 - 209.0 * n5 / 4480.0 + 5569.0 * n6 / 90720.0;
+    p.bet[3] = 4397.0 * n4 / 161280.0 - 11.0 * n5 / 504.0 - 830251.0 * n6 / 7257600.0;
+    p.bet[4] = 4583.0 * n5 / 161280.0 - 108847.0 * n6 / 3991680.0;
+    p.bet[5] = 20648693.0 * n6 / 638668800.0;
+    // xi of the latitude of origin: the series on the central meridian (eta = 0)
+    const double tau = tan(d.lat0 / WARP_DEG), t1 = sqrt(1.0 + tau * tau);
+    const double sig = sinh(p.e * atanh(p.e * tau / t1));
+    const double xip = atan(tau * sqrt(1.0 + sig * sig) - sig * t1);
+    double xi0 = xip;
+    for (int j = 0; j < 6; ++j) xi0 += p.alp[j] * sin(2.0 * (j + 1) * xip);
+    p.xi0 = fabs(d.lat0) == 90.0 ? copysign(1.5707963267948966, d.lat0) : xi0;
+    return true;
+}
+
+static bool warp_map(const hk_warp_desc& d, WarpMap& m, const char** why) {
+    if (!crs_params(d.src_crs, m.src, why) || !crs_params(d.dst_crs, m.dst, why)) return false;
+    if (d.src_crs.a != d.dst_crs.a || d.src_crs.inv_f != d.dst_crs.inv_f)
+        return *why = "the two CRSs are on different ellipsoids (no datum shifts)", false;
+    for (int k = 0; k < 4; ++k)
+        if (!isfinite(d.src_gt[k]) || !isfinite(d.dst_gt[k])) return *why = "geo-transform is not finite", false;
+    if (d.src_gt[1] == 0.0 || d.src_gt[3] == 0.0 || d.dst_gt[1] == 0.0 || d.dst_gt[3] == 0.0)
+        return *why = "degenerate geo-transform", false;
+    m.dx0 = d.dst_gt[0], m.ddx = d.dst_gt[1], m.dy0 = d.dst_gt[2], m.ddy = d.dst_gt[3];
+    m.sx0 = d.src_gt[0], m.sdx = d.src_gt[1], m.sy0 = d.src_gt[2], m.sdy = d.src_gt[3];
+    return true;
+}
+
+hipError_t launch_warp_coords(const hk_warp_desc* desc, double off_row, double off_col, double* x, double* y, long long stride,
+                              int h, int w, hipStream_t stream, const char** why) {
+    WarpCoordArgs a;
+    if (!warp_map(*desc, a.map, why)) return hipErrorInvalidValue;
+    a.x = x, a.y = y, a.stride = stride, a.h = h, a.w = w, a.off_row = off_row, a.off_col = off_col;
+    HK_LAUNCH(warp_coords_kernel, dim3((w + 255) / 256, h), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+// mode = rasterio.enums.Resampling value 0..4
+hipError_t launch_warp_resample(int mode, const hk_warp_desc* desc, const float* src, long long src_stride,
+                                long long src_band_stride, int sh, int sw, int n_bands, int nd_mode, float nodata, double kx,
+                                double ky, float* dst, long long dst_stride, long long dst_band_stride, int dh, int dw,
+                                float dst_fill, hipStream_t stream, const char** why) {
+    WarpArgs a;
+    if (!warp_map(*desc, a.map, why)) return hipErrorInvalidValue;
+    a.src = src, a.dst = dst, a.src_stride = src_stride, a.src_band_stride = src_band_stride, a.dst_stride = dst_stride;
+    a.dst_band_stride = dst_band_stride, a.sh = sh, a.sw = sw, a.dh = dh, a.dw = dw, a.n_bands = n_bands, a.nd_mode = nd_mode;
+    a.nodata = nodata, a.dst_fill = dst_fill, a.kx = kx, a.ky = ky;
+    const dim3 grid((dw + 255) / 256, dh), block(256);
+    const bool stretched = kx > 1.0 + 1e-9 || ky > 1.0 + 1e-9;  // as launch_resample picks the kernels
+    switch (mode) {
+        case 0: HK_LAUNCH(warp_kernel<0>, grid, block, 0, stream, a); break;
+        case 1:
+            if (stretched) HK_LAUNCH(warp_conv_kernel<1>, grid, block, 0, stream, a);
+            else HK_LAUNCH(warp_kernel<1>, grid, block, 0, stream, a);
+            break;
+        case 2: HK_LAUNCH(warp_conv_kernel<2>, grid, block, 0, stream, a); break;
+        case 3:
+            if (stretched) HK_LAUNCH(warp_conv_kernel<3>, grid, block, 0, stream, a);
+            else HK_LAUNCH(warp_kernel<3>, grid, block, 0, stream, a);
+            break;
+        case 4: HK_LAUNCH(warp_conv_kernel<4>, grid, block, 0, stream, a); break;
+        default: *why = "resampling is not one of nearest / bilinear / cubic / cubic_spline / lanczos"; return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace hk

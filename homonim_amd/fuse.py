@@ -15,7 +15,10 @@ model.apply -> write`` on a thread pool (fuse.py:295-319,396-408).  This module 
   and/or over ranks (one process per GPU), with no data-path collective.
 
 Rasters may also be given / written as GeoTIFF paths (homonim_amd/tiff.py: the classic-TIFF subset the reference's
-rasters use); band matching by wavelength and re-projection BETWEEN CRSs stay outside (GDAL).
+rasters use).  A source and a reference in different CRSs are brought together as the reference's
+``utils.same_orientation_crs`` does (homonim/utils.py:190-209): the processing-grid image is warped, bilinear, into the other's
+CRS on the device (hk_warp.hip; the CRSs homonim_amd/crs.py knows), everything after that runs on one CRS.  Band matching by
+wavelength stays outside (GDAL).
 """
 import math
 import os
@@ -26,8 +29,9 @@ from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequenc
 import numpy as np
 
 from homonim_amd import _hk, utils
-from homonim_amd.enums import Model, ProcCrs
-from homonim_amd.errors import BlockSizeError, ConfigWarning, DeviceError, IoError
+from homonim_amd import crs as crs_defs
+from homonim_amd.enums import Model, ProcCrs, Resampling
+from homonim_amd.errors import BlockSizeError, ConfigWarning, DeviceError, ImageFormatWarning, IoError
 from homonim_amd.geo import Affine, CRS, Window
 from homonim_amd.kernel_model import KernelModel, RefSpaceModel, SrcSpaceModel
 from homonim_amd.raster_array import RasterArray
@@ -252,7 +256,7 @@ def shard(items: Sequence, index: int, count: int, contiguous: bool = False) -> 
 
 class RasterFuse:
     """
-    Correct a source raster to surface reflectance by fusion with a reference raster of the same CRS.
+    Correct a source raster to surface reflectance by fusion with a reference raster.
 
     src, ref : float32 arrays (bands, height, width) or (height, width), ``RasterArray`` instances, or GeoTIFF paths
     (nodata, CRS and geo-transform then come from the files; bands are paired in file order).
@@ -264,11 +268,14 @@ class RasterFuse:
     def __init__(self, src: Union[np.ndarray, RasterArray], ref: Union[np.ndarray, RasterArray],
                  src_nodata: Optional[float] = float('nan'), ref_nodata: Optional[float] = float('nan'),
                  proc_crs: ProcCrs = ProcCrs.auto, crs: Optional[CRS] = None, transform: Optional[Affine] = None,
-                 ref_transform: Optional[Affine] = None):
+                 ref_transform: Optional[Affine] = None, ref_crs: Optional[CRS] = None):
         """
-        ``transform`` / ``ref_transform``: geo-transforms of the source / reference rasters (same CRS, north-up).  When
-        they (or the shapes) differ, blocks are cut on the processing grid and re-sampled on the device as the
-        reference does through GDAL (RefSpaceModel / SrcSpaceModel); the reference must cover the source.
+        ``transform`` / ``ref_transform``: geo-transforms of the source / reference rasters (north-up).  When they (or the
+        shapes) differ, blocks are cut on the processing grid and re-sampled on the device as the reference does through
+        GDAL (RefSpaceModel / SrcSpaceModel); the reference must cover the source.  ``crs`` / ``ref_crs``: their CRSs (taken
+        from files and ``RasterArray`` instances); ``ref_crs`` defaults to ``crs``.  When the two differ the processing-grid
+        image -- ``proc_crs=src``: the source, otherwise the reference -- is first warped into the other's CRS
+        (``_to_one_crs``), with the reference's warning.
         """
         self._src_filename = self._ref_filename = None
         self._ref_descriptions = ()   # band descriptions of a reference opened from a file (name the parameter bands)
@@ -281,14 +288,12 @@ class RasterFuse:
             from homonim_amd.tiff import read_tiff
             self._ref_filename = os.fspath(ref)
             tif = read_tiff(ref)
-            if crs is not None and tif.crs != crs:
-                raise NotImplementedError('source and reference CRSs differ: re-projection between CRSs is not built (GDAL warp)')
-            ref, ref_nodata, ref_transform = tif.array, tif.nodata, tif.transform
+            ref, ref_nodata, ref_transform, ref_crs = tif.array, tif.nodata, tif.transform, tif.crs
             self._ref_descriptions = tif.descriptions
         if isinstance(src, RasterArray):
             src, src_nodata, crs, transform = src.array, src.nodata, src.crs, src.transform
         if isinstance(ref, RasterArray):
-            ref, ref_nodata, ref_transform = ref.array, ref.nodata, ref.transform
+            ref, ref_nodata, ref_transform, ref_crs = ref.array, ref.nodata, ref.transform, ref.crs
         src = np.asarray(src)
         ref = np.asarray(ref)
         if src.ndim == 2:
@@ -306,6 +311,9 @@ class RasterFuse:
         ref, ref_transform = north_up(ref, ref_transform)
         if ref.shape[0] < src.shape[0]:
             raise ValueError('`ref` has fewer bands than `src`')
+        if crs is not None and ref_crs is not None and not crs_defs.same_crs(crs, ref_crs):
+            src, src_nodata, crs, transform, ref, ref_nodata, ref_transform, proc_crs = self._to_one_crs(
+                src, src_nodata, crs, transform, ref, ref_nodata, ref_crs, ref_transform, ProcCrs(proc_crs))
         self._src, self._ref = src, ref
         self._src_nodata, self._ref_nodata = src_nodata, ref_nodata
         self._crs = crs or CRS()
@@ -324,6 +332,44 @@ class RasterFuse:
         self._proc_crs = resolve_proc_crs(self._src_grid, self._ref_grid, proc_crs)
         self._closed = False
         self._write_lock = threading.Lock()
+
+    def _to_one_crs(self, src, src_nodata, crs, transform, ref, ref_nodata, ref_crs, ref_transform, proc_crs: ProcCrs):
+        """ Source and reference in different CRSs: what ``RasterPairReader`` does with such a pair (homonim/raster_pair.py:160-166,
+        homonim/utils.py:190-209).  Warn; resolve ``proc_crs=auto`` from the pixel areas, the reference's pixel brought into the
+        source's CRS at the source's centre; warp the processing-grid image -- ``proc_crs=src``: the source, otherwise the reference
+        -- into the other's CRS on ``geo.suggested_warp_grid``, bilinear, all bands in one device call.  Returns the pair on one
+        CRS and the resolved ``proc_crs``; an image without nodata gets NaN for what the warp leaves empty. """
+        import warnings
+        names = [os.path.basename(fn) if fn else 'memory' for fn in (self._src_filename, self._ref_filename)]
+        warnings.warn(f'Source and reference image will be re-projected to the same CRS: {names[0]} and {names[1]}',
+                      category=ImageFormatWarning)
+        crs_defs.definitions(crs, ref_crs)   # NotImplementedError naming an unknown CRS / two ellipsoids
+        if transform is None or ref_transform is None:
+            raise ValueError('source and reference in different CRSs need their geo-transforms (`transform`, `ref_transform`)')
+        # the reference's pixel at the source's centre, in source CRS units
+        h, w = src.shape[-2:]
+        xc, yc = transform.c + transform.a * w / 2, transform.f + transform.e * h / 2
+        xr, yr = crs_defs.transform_coords(crs, ref_crs, xc, yc)
+        px, py = crs_defs.transform_coords(ref_crs, crs, xr + np.array([0., ref_transform.a, 0.]),
+                                           yr + np.array([0., 0., ref_transform.e]))
+        ref_res = (float(np.hypot(px[1] - px[0], py[1] - py[0])), float(np.hypot(px[2] - px[0], py[2] - py[0])))
+        if not all(math.isfinite(v) and v > 0 for v in ref_res):
+            from homonim_amd.errors import ImageContentError
+            raise ImageContentError('Reference extent does not cover source image')
+        proc_crs = resolve_proc_crs(Grid(transform, h, w), Grid(Affine(ref_res[0], 0., 0., 0., -ref_res[1], 0.), 1, 1), proc_crs)
+        dev = int(os.environ.get('HOMONIM_AMD_DEVICE', os.environ.get('LOCAL_RANK', '0')))
+        ctx = _hk.get_context(dev)
+        if proc_crs == ProcCrs.src:
+            nodata = float('nan') if src_nodata is None else src_nodata
+            ra = RasterArray(src, crs, transform, nodata=src_nodata).reproject(crs=ref_crs, nodata=nodata,
+                                                                              resampling=Resampling.bilinear, context=ctx)
+            src, src_nodata, crs, transform = ra.array, nodata, ref_crs, ra.transform
+        else:
+            nodata = float('nan') if ref_nodata is None else ref_nodata
+            ra = RasterArray(ref, ref_crs, ref_transform, nodata=ref_nodata).reproject(crs=crs, nodata=nodata,
+                                                                                      resampling=Resampling.bilinear, context=ctx)
+            ref, ref_nodata, ref_transform = ra.array, nodata, ra.transform
+        return src, src_nodata, crs, transform, ref, ref_nodata, ref_transform, proc_crs
 
     # -- context manager parity with the reference (files there, nothing to open here) --------------------------------
     def __enter__(self):

@@ -105,3 +105,30 @@ def grid_mapping(src_transform, dst_transform) -> Tuple[float, float, float, flo
         raise NotImplementedError('degenerate geo-transform')
     kx, ky = d.a / s.a, d.e / s.e
     return kx, (d.c - s.c) / s.a, ky, (d.f - s.f) / s.e
+
+
+def suggested_warp_grid(crs, transform, shape: Tuple[int, int], dst_crs) -> Tuple[Affine, Tuple[int, int]]:
+    """
+    (transform, (height, width)) of the grid a raster (``crs``, axis-aligned ``transform``, ``shape`` = (height, width)) gets
+    in ``dst_crs`` when nothing else is asked for -- GDAL's suggested warp output restated: the extent is the bounding box of the
+    raster's outline transformed with 21 points per edge; the pixel is square, its size the transformed corner-to-corner
+    diagonal divided by the diagonal in pixels; the size is ``int(extent / res + 0.5)``; the grid is north-up.
+    """
+    import numpy as np
+
+    from homonim_amd import crs as _crs
+    if transform.b or transform.d:
+        raise NotImplementedError('re-projection between rotated / sheared grids is not built')
+    height, width = int(shape[0]), int(shape[1])
+    t = np.linspace(0., 1., 21)
+    cols = np.concatenate([t * width, np.full(21, float(width)), t[::-1] * width, np.zeros(21)])
+    rows = np.concatenate([np.zeros(21), t * height, np.full(21, float(height)), t[::-1] * height])
+    xs, ys = _crs.transform_coords(crs, dst_crs, transform.c + cols * transform.a, transform.f + rows * transform.e)
+    if not (np.isfinite(xs).all() and np.isfinite(ys).all()):
+        raise ValueError(f'the raster outline has no image in {dst_crs!r}')
+    left, right, bottom, top = float(xs.min()), float(xs.max()), float(ys.min()), float(ys.max())
+    # corners of the outline: points 0 (upper left) and 42 (lower right)
+    diag = float(np.hypot(xs[42] - xs[0], ys[42] - ys[0]))
+    res = diag / float(np.hypot(width, height))
+    out_w, out_h = max(int((right - left) / res + 0.5), 1), max(int((top - bottom) / res + 0.5), 1)
+    return Affine(res, 0., left, 0., -res, top), (out_h, out_w)

@@ -17,8 +17,9 @@ Differences a caller can observe (all documented in DESIGN.md):
   GDAL itself unpinned, hk_inpaint.hip) and the gains of the failing pixels are recomputed as in :370-371.
 * ``RefSpaceModel`` / ``SrcSpaceModel`` re-sample between same-CRS, axis-aligned grids on the device (every
   ``rasterio.enums.Resampling`` warp method: a restatement of GDAL's warp kernels, pinned against the real stack's
-  published accuracy table for average / cubic_spline, otherwise unpinned); other CRSs and rotations raise
-  ``NotImplementedError``, ``gauss`` is rejected as in rasterio.
+  published accuracy table for average / cubic_spline, otherwise unpinned); rasters of two CRSs (bring one to the other's
+  with ``RasterArray.reproject(crs=...)``, as ``RasterFuse`` does) and rotations raise ``NotImplementedError``, ``gauss`` is
+  rejected as in rasterio.
 """
 from typing import Dict, Optional, Tuple
 
@@ -186,6 +187,14 @@ def _same_grid(a: RasterArray, b: RasterArray) -> bool:
     return a.transform == b.transform and a.shape == b.shape and a.crs == b.crs
 
 
+def _require_one_crs(a: RasterArray, b: RasterArray):
+    """ The models work on one CRS (the reference's RasterPairReader hands them blocks it has brought to one, homonim/utils.py:190-209). """
+    from homonim_amd.crs import same_crs
+    if not same_crs(a.crs, b.crs):
+        raise NotImplementedError(f'the kernel models take rasters of one CRS, got {a.crs!r} and {b.crs!r}: bring one to the '
+                                  'other\'s with RasterArray.reproject(crs=...) first (RasterFuse does)')
+
+
 def _full_coverage_mask(model: KernelModel, in_mask_ra: RasterArray, param_ra: RasterArray) -> np.ndarray:
     """
     kernel_model.py:375-409: the mask of parameter-grid pixels fully covered by the input mask (re-projected with
@@ -207,12 +216,14 @@ class RefSpaceModel(KernelModel):
     """
 
     def fit(self, src_ra: RasterArray, ref_ra: RasterArray) -> RasterArray:
+        _require_one_crs(src_ra, ref_ra)
         if not _same_grid(src_ra, ref_ra):  # identical grids: the reference's `average` re-sampling is the identity
             resampling = self._get_resampling(src_ra.res, ref_ra.res)
             src_ra = src_ra.reproject(**ref_ra.proj_profile, resampling=resampling, context=self.context)  # :480
         return KernelModel.fit(self, src_ra, ref_ra)
 
     def apply(self, src_ra: RasterArray, param_ra: RasterArray) -> RasterArray:
+        _require_one_crs(src_ra, param_ra)
         if _same_grid(src_ra, param_ra):
             if self._mask_partial:
                 # full-coverage mask of the source mask & parameters, eroded by (kh+2) x (kw+2), then apply (:493-503)
@@ -250,8 +261,7 @@ class RefSpaceModel(KernelModel):
         if _same_grid(src_ra, ref_ra) and not self._mask_partial:
             return KernelModel.fit_apply(self, src_ra, ref_ra, want_params, out_dtype, out_nodata)
         from homonim_amd.geo import grid_mapping
-        if src_ra.crs != ref_ra.crs:
-            raise NotImplementedError('re-projection between different CRSs is not built (GDAL warp)')
+        _require_one_crs(src_ra, ref_ra)
         down = self._get_resampling(src_ra.res, ref_ra.res)
         up = self._get_resampling(ref_ra.res, src_ra.res)
         count = 3 if self._emit_r2 else 2
@@ -270,6 +280,7 @@ class SrcSpaceModel(KernelModel):
     """ Parameters estimated on the source grid (kernel_model.py:506-535): the reference block is re-sampled to it. """
 
     def fit(self, src_ra: RasterArray, ref_ra: RasterArray) -> RasterArray:
+        _require_one_crs(src_ra, ref_ra)
         ref_us_ra = ref_ra
         if not _same_grid(src_ra, ref_ra):
             resampling = self._get_resampling(ref_ra.res, src_ra.res)

@@ -10,10 +10,11 @@ properties :223-351, ``profile``/``proj_profile`` :281-296, ``copy`` :389-391):
 * ``nodata = None`` means "every pixel valid"; changing a numeric/NaN nodata re-labels the currently masked pixels;
 * multi-band arrays are band-major and a pixel is valid if it is valid in ANY band.
 
-``reproject`` (raster_array.py:526-578) runs on the GPU for same-CRS, north-up, axis-aligned grids with the nearest /
-bilinear / cubic_spline / average kernels -- a restatement of GDAL's warp kernels, see hk_resample.hip.  Dataset IO
-stays outside this package (GDAL).
+``reproject`` (raster_array.py:526-578) runs on the GPU for north-up, axis-aligned grids: within one CRS with every warp
+method -- a restatement of GDAL's warp kernels, see hk_resample.hip -- and between the CRSs homonim_amd/crs.py knows with
+nearest / bilinear / cubic / cubic_spline / lanczos (hk_warp.hip).  Dataset IO stays outside this package (GDAL).
 """
+import math
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -166,17 +167,20 @@ class RasterArray:
                   nodata: Optional[float] = default_nodata, dtype: str = default_dtype,
                   resampling: Resampling = Resampling.lanczos, context=None) -> 'RasterArray':
         """
-        Re-sample onto another grid of the same CRS (raster_array.py:526-578).  ``transform`` needs ``shape``; the default
-        is this array's own grid.  Returns a float32 RasterArray with ``nodata`` where nothing valid contributes
-        (0 when ``nodata`` is None, as GDAL leaves the zero-initialised destination).
+        Re-sample onto another grid (raster_array.py:526-578).  ``transform`` needs ``shape``; the default is this array's own
+        grid, or -- with another ``crs`` -- ``geo.suggested_warp_grid``.  Across CRSs (homonim_amd/crs.py lists the known ones)
+        nearest, bilinear, cubic, cubic_spline and lanczos are built (hk_warp.hip).  Returns a float32 RasterArray with
+        ``nodata`` where nothing valid contributes (0 when ``nodata`` is None, as GDAL leaves the zero-initialised
+        destination).
         """
         if transform is not None and shape is None:
             raise ValueError('If `transform` is specified, `shape` is required')
         if isinstance(resampling, str):
             resampling = Resampling[resampling]
         crs = crs or self._crs
-        if crs != self._crs:
-            raise NotImplementedError('re-projection between different CRSs is not built (GDAL warp)')
+        from homonim_amd import crs as crs_defs  # (deferred like _hk below)
+        if not crs_defs.same_crs(crs, self._crs):
+            return self._reproject_crs(crs, transform, shape, nodata, dtype, resampling, context)
         transform = transform or self._transform
         shape = tuple(shape or self.shape)
         if np.dtype(dtype or self.dtype) != np.float32:
@@ -195,3 +199,38 @@ class RasterArray:
             src, kx, ox = src[..., ::-1], -kx, src.shape[-1] - ox
         out = ctx.reproject(src, self._nodata, (kx, ox, ky, oy), shape, int(resampling), fill)
         return RasterArray(out, crs, transform, nodata=nodata)
+
+    def _reproject_crs(self, crs, transform, shape, nodata, dtype, resampling: Resampling, context) -> 'RasterArray':
+        """ ``reproject`` onto a grid of another CRS: every destination pixel is transformed on the device (hk_warp.hip). """
+        from homonim_amd import _hk, crs as crs_defs
+        from homonim_amd.geo import suggested_warp_grid
+        if int(resampling) > int(Resampling.lanczos):
+            raise NotImplementedError(f"'{Resampling(resampling).name}' re-sampling between different CRSs is not built: it works on "
+                                      'a destination pixel\'s footprint (nearest, bilinear, cubic, cubic_spline and lanczos are)')
+        dst_def, src_def = crs_defs.definitions(crs, self._crs)   # NotImplementedError: unknown CRS, two ellipsoids
+        if transform is None:
+            transform, shape = suggested_warp_grid(self._crs, self._transform, self.shape, crs)
+        shape = tuple(shape)
+        if np.dtype(dtype or self.dtype) != np.float32:
+            raise NotImplementedError('re-projection yields float32 only')
+        warp = _hk.make_warp_desc(src_def, self._transform, dst_def, transform)
+        scale = warp_scale(crs, transform, shape, self._crs, self._transform)
+        ctx = context or _hk.default_context()
+        fill = 0.0 if nodata is None else float(nodata)
+        out = ctx.reproject_crs(self._array, self._nodata, warp, scale, shape, int(resampling), fill)
+        return RasterArray(out, crs, transform, nodata=nodata)
+
+
+def warp_scale(dst_crs, dst_transform, dst_shape, src_crs, src_transform) -> Tuple[float, float]:
+    """ (kx, ky): source pixels per destination pixel of a warp, the mean step along the destination's central row and column
+    (``crs.transform_coords`` of the two ends of each); they pick the stretched re-sampling kernels and scale their support. """
+    from homonim_amd import crs as crs_defs
+    h, w = float(dst_shape[0]), float(dst_shape[1])
+    cols, rows = np.array([0., w, w / 2, w / 2]), np.array([h / 2, h / 2, 0., h])
+    xs, ys = crs_defs.transform_coords(dst_crs, src_crs, dst_transform.c + cols * dst_transform.a,
+                                       dst_transform.f + rows * dst_transform.e)
+    px, py = (xs - src_transform.c) / src_transform.a, (ys - src_transform.f) / src_transform.e
+    kx, ky = float(np.hypot(px[1] - px[0], py[1] - py[0])) / w, float(np.hypot(px[3] - px[2], py[3] - py[2])) / h
+    if not (math.isfinite(kx) and math.isfinite(ky) and kx > 0 and ky > 0):
+        raise ValueError('the destination grid has no image in the source CRS')
+    return kx, ky

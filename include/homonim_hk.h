@@ -71,9 +71,10 @@ typedef struct {
  * carry no size field; version 5 added entry points (hk_device_pci_bus_id; hk_debug_staging_counters in the devtools header); version 6: a raw
  * r2-mask failure counter is always a count (HK_COUNT_RETRY is never set any more), and a device-resident job that carries `scratch`
  * always gets the in-painting's inputs left there; version 7 added entry points (hk_param_stats, hk_param_stats_dev); version 8
- * added entry points (hk_overview_count, hk_overviews, hk_overviews_dev).
+ * added entry points (hk_overview_count, hk_overviews, hk_overviews_dev); version 9 added hk_crs_desc / hk_warp_desc and entry
+ * points (hk_warp_coords, hk_warp_coords_dev, hk_reproject_crs, hk_reproject_crs_dev, hk_reproject_dev).
  * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
-#define HK_ABI_VERSION 8
+#define HK_ABI_VERSION 9
 int hk_abi_version(void);
 const char* hk_backend_name(void);            /* "hip-gfx950" */
 const char* hk_last_error(void);              /* thread-local text of the last failure */
@@ -170,6 +171,59 @@ int hk_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const float* src, int64_t
 int hk_reproject(hk_ctx* ctx, const float* src, int32_t n_bands, int32_t src_height, int32_t src_width,
                  int32_t src_nodata_mode, float src_nodata, double kx, double ox, double ky, double oy, int32_t resampling,
                  float* dst, int32_t dst_height, int32_t dst_width, float dst_fill);
+
+/* RasterArray.reproject (homonim/raster_array.py:526-578) between grids of DIFFERENT coordinate reference systems, and the
+ * up-front warp of utils.same_orientation_crs (homonim/utils.py:190-209), which brings the processing-grid image of a
+ * RasterPairReader into the other image's CRS (homonim/raster_pair.py:160-166).
+ * A CRS is geographic (coordinates in degrees, longitude first) or Transverse Mercator on an ellipsoid (a, 1 / f; inv_f = 0: a
+ * sphere); there are no datum shifts: the two CRSs of a warp share their ellipsoid (HK_ERR_UNSUPPORTED otherwise).  Transverse
+ * Mercator is the Krueger series in n to n^6 (Karney 2011), float64 throughout: every destination pixel is transformed exactly
+ * (GDAL's default warp interpolates the transformation within 0.125 pixel).  Geo-transforms are axis-aligned:
+ * x = gt[0] + col * gt[1], y = gt[2] + row * gt[3] on continuous pixel coordinates whose integers are pixel edges. */
+typedef enum { HK_CRS_GEOGRAPHIC = 0, HK_CRS_TMERC = 1 } hk_crs_kind;
+typedef struct hk_crs_desc {
+    int32_t kind;      /* hk_crs_kind */
+    int32_t reserved;  /* 0 */
+    double a, inv_f;   /* ellipsoid: semi-major axis (metres), inverse flattening */
+    double lat0, lon0; /* Transverse Mercator: latitude of origin, central meridian (degrees); geographic: 0 */
+    double k0;         /* scale factor on the central meridian */
+    double fe, fn;     /* false easting / northing (metres) */
+} hk_crs_desc;
+typedef struct hk_warp_desc {
+    hk_crs_desc src_crs, dst_crs;
+    double src_gt[4], dst_gt[4];
+} hk_warp_desc;
+/* The continuous SOURCE pixel coordinates (column into x_out, row into y_out; float64, `stride` elements between rows) of the
+ * destination positions (row + off_row, col + off_col), row < height, col < width: offsets 0.5 give the pixel centres, offsets 0
+ * on a (dst_height + 1) x (dst_width + 1) lattice the pixel corners.  NaN where a position has no image in the source CRS
+ * (|latitude| > 90 degrees, 90 degrees or more from a Transverse Mercator's central meridian).  These are, bit for bit, the
+ * coordinates hk_reproject_crs* uses for the same descriptor at offsets 0.5.  Elements between a row's end and `stride` are not
+ * written.  hk_warp_coords: host planes; hk_warp_coords_dev: device planes, asynchronous on pooled stream `stream`. */
+int hk_warp_coords(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double off_col, int32_t height, int32_t width,
+                   double* x_out, double* y_out, int64_t stride);
+int hk_warp_coords_dev(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double off_col, int32_t height, int32_t width,
+                       double* x_dev, double* y_dev, int64_t stride, int32_t stream);
+/* hk_reproject across CRSs: per destination pixel the source coordinate comes from `warp` instead of an affine mapping, the
+ * re-sampling arithmetic is hk_reproject's own.  resampling: 0 nearest, 1 bilinear, 2 cubic, 3 cubic_spline, 4 lanczos (the
+ * footprint methods -- average, mode, max, min, med, q1, q3, sum, rms -- are HK_ERR_UNSUPPORTED across CRSs: the reference's
+ * up-front warp is bilinear).  kx, ky (> 0): source pixels per destination pixel, the mean step along the destination's central
+ * row / column; they pick the stretched (down-sampling) kernels and scale their support as hk_reproject's kx, ky do.  A pixel
+ * whose coordinate is NaN or lies outside the source gets dst_fill.  All bands are re-sampled in one launch; a thread computes
+ * its pixel's coordinate once.  hk_reproject_crs: host rasters, contiguous like hk_reproject's; hk_reproject_crs_dev: device
+ * rasters (strides in elements), asynchronous on pooled stream `stream`. */
+int hk_reproject_crs(hk_ctx* ctx, const hk_warp_desc* warp, const float* src, int32_t n_bands, int32_t src_height,
+                     int32_t src_width, int32_t src_nodata_mode, float src_nodata, double kx, double ky, int32_t resampling,
+                     float* dst, int32_t dst_height, int32_t dst_width, float dst_fill);
+int hk_reproject_crs_dev(hk_ctx* ctx, const hk_warp_desc* warp, const float* src_dev, int32_t n_bands, int32_t src_height,
+                         int32_t src_width, int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode,
+                         float src_nodata, double kx, double ky, int32_t resampling, float* dst_dev, int32_t dst_height,
+                         int32_t dst_width, int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream);
+/* hk_reproject on device-resident rasters (strides in elements), asynchronous on pooled stream `stream`: the same kernels, the
+ * same bits. */
+int hk_reproject_dev(hk_ctx* ctx, const float* src_dev, int32_t n_bands, int32_t src_height, int32_t src_width,
+                     int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode, float src_nodata, double kx, double ox,
+                     double ky, double oy, int32_t resampling, float* dst_dev, int32_t dst_height, int32_t dst_width,
+                     int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream);
 
 /* `mask_partial` on a shared grid: KernelModel._full_coverage_mask (homonim/kernel_model.py:375-409) -- the mask of
  * pixels that are valid in `in` (nodata as given) and have parameters, eroded by a (kh+2) x (kw+2) rectangle with a
