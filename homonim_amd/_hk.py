@@ -58,6 +58,11 @@ class WarpDesc(C.Structure):
     _fields_ = [('src_crs', CrsDesc), ('dst_crs', CrsDesc), ('src_gt', C.c_double * 4), ('dst_gt', C.c_double * 4)]
 
 
+class AffineWarpDesc(C.Structure):
+    _fields_ = [('src_crs', CrsDesc), ('dst_crs', CrsDesc), ('same_crs', C.c_int32), ('reserved', C.c_int32),
+                ('src_gt', C.c_double * 6), ('dst_gt', C.c_double * 6)]
+
+
 class OutWindow(C.Structure):
     _fields_ = [('stride', C.c_int64), ('band_stride', C.c_int64), ('row0', C.c_int32), ('col0', C.c_int32),
                 ('rows', C.c_int32), ('cols', C.c_int32), ('param_stride', C.c_int64)]
@@ -78,7 +83,7 @@ _P = C.POINTER
 _f32p, _f64p, _u64p = _P(C.c_float), _P(C.c_double), _P(C.c_uint64)
 
 # name -> (restype, argtypes); kept in one table so tests can check every symbol of the header is exported
-ABI_VERSION = 9   # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
+ABI_VERSION = 10  # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
 # entry points declared in include/homonim_hk_devtools.h (measurement / test aids), the rest in include/homonim_hk.h
 DEVTOOLS = ('hk_synth_fill_dev', 'hk_stream_probe_dev', 'hk_debug_stage_stamps', 'hk_r2_certificate_constants', 'hk_debug_staging_counters',
             'hk_debug_build_ledger', 'hk_debug_checksum_dev', 'hk_debug_fail_after_d2h')
@@ -134,6 +139,15 @@ SIGNATURES = {
     'hk_reproject_crs_dev': (C.c_int, [C.c_void_p, _P(WarpDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                        C.c_int32, C.c_float, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_int64, C.c_int64, C.c_float, C.c_int32]),
+    'hk_warp_coords_affine': (C.c_int, [C.c_void_p, _P(AffineWarpDesc), C.c_double, C.c_double, C.c_int32, C.c_int32, _f64p, _f64p,
+                                        C.c_int64]),
+    'hk_warp_coords_affine_dev': (C.c_int, [C.c_void_p, _P(AffineWarpDesc), C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_int64, C.c_int32]),
+    'hk_reproject_affine': (C.c_int, [C.c_void_p, _P(AffineWarpDesc), _f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                      C.c_double, C.c_double, C.c_int32, _f32p, C.c_int32, C.c_int32, C.c_float]),
+    'hk_reproject_affine_dev': (C.c_int, [C.c_void_p, _P(AffineWarpDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                          C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_int32, C.c_int64, C.c_int64, C.c_float, C.c_int32]),
     'hk_partial_mask': (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int32, C.c_float, _f32p, C.c_int32, _f32p, C.c_int64,
                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _f32p, _P(C.c_uint8)]),
     'hk_fit_apply_io': (C.c_int, [C.c_void_p, _P(FitDesc), _P(IoDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -286,6 +300,22 @@ def make_warp_desc(src_def, src_transform, dst_def, dst_transform) -> WarpDesc:
         if t.b or t.d:
             raise NotImplementedError('re-projection between rotated / sheared grids is not built')
         gt[0], gt[1], gt[2], gt[3] = float(t.c), float(t.a), float(t.f), float(t.e)
+    return w
+
+
+def make_affine_warp_desc(src_def, src_transform, dst_def, dst_transform) -> AffineWarpDesc:
+    """ hk_affine_warp_desc from the geo-transforms of two grids, rotated and sheared ones included, and their CRS definitions
+    (homonim_amd.crs.CrsDef).  Both definitions None: the grids share one CRS, whatever it is (``same_crs``). """
+    if (src_def is None) != (dst_def is None):
+        raise ValueError('give both CRS definitions, or neither for two grids of one CRS')
+    w = AffineWarpDesc()
+    w.same_crs, w.reserved = int(src_def is None), 0
+    if src_def is not None:
+        for desc, d in ((w.src_crs, src_def), (w.dst_crs, dst_def)):
+            desc.kind, desc.reserved = int(d.kind), 0
+            desc.a, desc.inv_f, desc.lat0, desc.lon0, desc.k0, desc.fe, desc.fn = (float(v) for v in d[1:])
+    for gt, t in ((w.src_gt, src_transform), (w.dst_gt, dst_transform)):
+        gt[0], gt[1], gt[2], gt[3], gt[4], gt[5] = float(t.a), float(t.b), float(t.c), float(t.d), float(t.e), float(t.f)
     return w
 
 
@@ -583,6 +613,9 @@ class Context:
         """ hk_warp_coords: the continuous source pixel coordinates ``(x, y)`` (float64 planes of ``shape``) of the destination
         positions (row + offset[0], col + offset[1]) -- offset 0.5: pixel centres; offset 0 on a (h + 1, w + 1) lattice: corners.
         These are the coordinates ``reproject_crs`` uses.  ``out``: an (x, y) pair of float64 planes to fill, rows may be padded. """
+        return self._warp_coords(self._lib.hk_warp_coords, warp, shape, offset, out)
+
+    def _warp_coords(self, entry, warp, shape, offset, out):
         h, w = int(shape[0]), int(shape[1])
         x, y = out if out is not None else (np.empty((h, w), np.float64), np.empty((h, w), np.float64))
         for a in (x, y):
@@ -590,9 +623,19 @@ class Context:
                 raise ValueError('coordinate planes must be float64 arrays of `shape` with contiguous rows')
         if x.strides[0] != y.strides[0]:
             raise ValueError('the two coordinate planes must share their row stride')
-        _check(self._lib.hk_warp_coords(self._h, C.byref(warp), float(offset[0]), float(offset[1]), h, w, _ptr(x, _f64p),
-                                        _ptr(y, _f64p), x.strides[0] // 8))
+        _check(entry(self._h, C.byref(warp), float(offset[0]), float(offset[1]), h, w, _ptr(x, _f64p), _ptr(y, _f64p),
+                     x.strides[0] // 8))
         return x, y
+
+    def warp_coords_affine(self, warp: AffineWarpDesc, shape, offset=(0.5, 0.5), out=None):
+        """ hk_warp_coords_affine: ``warp_coords`` between rotated / sheared grids; the coordinates ``reproject_affine`` uses. """
+        return self._warp_coords(self._lib.hk_warp_coords_affine, warp, shape, offset, out)
+
+    def warp_coords_affine_dev(self, warp: AffineWarpDesc, shape, x_dptr: int, y_dptr: int, stride: int, offset=(0.5, 0.5),
+                               stream: int = 0):
+        """ hk_warp_coords_affine_dev: the same into device planes (asynchronous). """
+        _check(self._lib.hk_warp_coords_affine_dev(self._h, C.byref(warp), float(offset[0]), float(offset[1]), int(shape[0]),
+                                                   int(shape[1]), C.c_void_p(x_dptr), C.c_void_p(y_dptr), int(stride), int(stream)))
 
     def warp_coords_dev(self, warp: WarpDesc, shape, x_dptr: int, y_dptr: int, stride: int, offset=(0.5, 0.5), stream: int = 0):
         """ hk_warp_coords_dev: the same into device planes (asynchronous). """
@@ -603,6 +646,9 @@ class Context:
                       dst_fill: float) -> np.ndarray:
         """ hk_reproject_crs: (bands, h, w) or (h, w) float32 -> same rank on a destination grid of another CRS; ``scale`` =
         (kx, ky), source pixels per destination pixel; all bands in one device call. """
+        return self._reproject_warp(self._lib.hk_reproject_crs, src, src_nodata, warp, scale, dst_shape, resampling, dst_fill)
+
+    def _reproject_warp(self, entry, src, src_nodata, warp, scale, dst_shape, resampling, dst_fill):
         arr = np.ascontiguousarray(src, dtype=np.float32)
         squeeze = arr.ndim == 2
         if squeeze:
@@ -611,9 +657,24 @@ class Context:
         dh, dw = int(dst_shape[0]), int(dst_shape[1])
         out = np.empty((nb, dh, dw), np.float32)
         mode, val = nodata_code(src_nodata)
-        _check(self._lib.hk_reproject_crs(self._h, C.byref(warp), _ptr(arr), nb, sh, sw, mode, val, float(scale[0]), float(scale[1]),
-                                          int(resampling), _ptr(out), dh, dw, float(dst_fill)))
+        _check(entry(self._h, C.byref(warp), _ptr(arr), nb, sh, sw, mode, val, float(scale[0]), float(scale[1]), int(resampling),
+                     _ptr(out), dh, dw, float(dst_fill)))
         return out[0] if squeeze else out
+
+    def reproject_affine(self, src: np.ndarray, src_nodata, warp: AffineWarpDesc, scale, dst_shape, resampling: int,
+                         dst_fill: float) -> np.ndarray:
+        """ hk_reproject_affine: ``reproject_crs`` between rotated / sheared grids, in one CRS or across two. """
+        return self._reproject_warp(self._lib.hk_reproject_affine, src, src_nodata, warp, scale, dst_shape, resampling, dst_fill)
+
+    def reproject_affine_dev(self, warp: AffineWarpDesc, src_dptr: int, n_bands: int, src_shape, src_stride: int,
+                             src_band_stride: int, src_nodata, scale, resampling: int, dst_dptr: int, dst_shape, dst_stride: int,
+                             dst_band_stride: int, dst_fill: float, stream: int = 0):
+        """ hk_reproject_affine_dev: device rasters, strides in elements (asynchronous). """
+        mode, val = nodata_code(src_nodata)
+        _check(self._lib.hk_reproject_affine_dev(
+            self._h, C.byref(warp), C.c_void_p(src_dptr), int(n_bands), int(src_shape[0]), int(src_shape[1]), int(src_stride),
+            int(src_band_stride), mode, val, float(scale[0]), float(scale[1]), int(resampling), C.c_void_p(dst_dptr),
+            int(dst_shape[0]), int(dst_shape[1]), int(dst_stride), int(dst_band_stride), float(dst_fill), int(stream)))
 
     def reproject_crs_dev(self, warp: WarpDesc, src_dptr: int, n_bands: int, src_shape, src_stride: int, src_band_stride: int,
                           src_nodata, scale, resampling: int, dst_dptr: int, dst_shape, dst_stride: int, dst_band_stride: int,

@@ -20,6 +20,7 @@
 #include <mutex>
 #include <new>
 #include <optional>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/homonim_hk.h"
@@ -1663,8 +1664,9 @@ int hk_reproject_dev(hk_ctx* ctx, const float* src_dev, int32_t n_bands, int32_t
     return HK_OK;
 }
 
-// Re-sampling between grids of two CRSs (hk_warp.hip): see include/homonim_hk.h
-static int check_warp_lattice(hk_ctx* ctx, const hk_warp_desc* warp, int32_t height, int32_t width, const void* x, const void* y,
+// Re-sampling between grids of two CRSs and between rotated / sheared grids (hk_warp.hip): see include/homonim_hk.h.  The entry
+// points of hk_warp_desc and of hk_affine_warp_desc share their bodies; hk::launch_warp_* is overloaded on the descriptor.
+static int check_warp_lattice(hk_ctx* ctx, const void* warp, int32_t height, int32_t width, const void* x, const void* y,
                               int64_t stride) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
     if (!warp || !x || !y) return fail(HK_ERR_ARG, "NULL pointer argument");
@@ -1684,8 +1686,9 @@ static int warp_launch_status(hipError_t e, const char* why) {
     return fail(HK_ERR_HIP, "warp launch failed: %s", hipGetErrorString(e));
 }
 
-int hk_warp_coords_dev(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double off_col, int32_t height, int32_t width,
-                       double* x_dev, double* y_dev, int64_t stride, int32_t stream) {
+extern "C++" template <typename Desc>
+static int warp_coords_dev(hk_ctx* ctx, const Desc* warp, double off_row, double off_col, int32_t height, int32_t width,
+                           double* x_dev, double* y_dev, int64_t stride, int32_t stream) {
     int rc = check_warp_lattice(ctx, warp, height, width, x_dev, y_dev, stride);
     if (rc) return rc;
     if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
@@ -1696,8 +1699,9 @@ int hk_warp_coords_dev(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, do
                                                      ctx->slots[stream].stream, &why), why);
 }
 
-int hk_warp_coords(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double off_col, int32_t height, int32_t width,
-                   double* x_out, double* y_out, int64_t stride) {
+extern "C++" template <typename Desc>
+static int warp_coords_host(hk_ctx* ctx, const Desc* warp, double off_row, double off_col, int32_t height, int32_t width,
+                            double* x_out, double* y_out, int64_t stride) {
     int rc = check_warp_lattice(ctx, warp, height, width, x_out, y_out, stride);
     if (rc) return rc;
     HK_ENTER(ctx);
@@ -1719,7 +1723,27 @@ int hk_warp_coords(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double
     return stage_finish(sl);
 }
 
-static int check_reproject_crs(hk_ctx* ctx, const hk_warp_desc* warp, const float* src, int32_t n_bands, int32_t src_height,
+int hk_warp_coords_dev(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double off_col, int32_t height, int32_t width,
+                       double* x_dev, double* y_dev, int64_t stride, int32_t stream) {
+    return warp_coords_dev(ctx, warp, off_row, off_col, height, width, x_dev, y_dev, stride, stream);
+}
+
+int hk_warp_coords(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double off_col, int32_t height, int32_t width,
+                   double* x_out, double* y_out, int64_t stride) {
+    return warp_coords_host(ctx, warp, off_row, off_col, height, width, x_out, y_out, stride);
+}
+
+int hk_warp_coords_affine_dev(hk_ctx* ctx, const hk_affine_warp_desc* warp, double off_row, double off_col, int32_t height,
+                              int32_t width, double* x_dev, double* y_dev, int64_t stride, int32_t stream) {
+    return warp_coords_dev(ctx, warp, off_row, off_col, height, width, x_dev, y_dev, stride, stream);
+}
+
+int hk_warp_coords_affine(hk_ctx* ctx, const hk_affine_warp_desc* warp, double off_row, double off_col, int32_t height,
+                          int32_t width, double* x_out, double* y_out, int64_t stride) {
+    return warp_coords_host(ctx, warp, off_row, off_col, height, width, x_out, y_out, stride);
+}
+
+static int check_reproject_crs(hk_ctx* ctx, const void* warp, bool affine, const float* src, int32_t n_bands, int32_t src_height,
                                int32_t src_width, int32_t src_nodata_mode, double kx, double ky, int32_t resampling,
                                const float* dst, int32_t dst_height, int32_t dst_width) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
@@ -1731,17 +1755,20 @@ static int check_reproject_crs(hk_ctx* ctx, const hk_warp_desc* warp, const floa
     if (!resampling_built(resampling))
         return fail(HK_ERR_UNSUPPORTED, "resampling %d is not a warp method", resampling);
     if (resampling > 4)
-        return fail(HK_ERR_UNSUPPORTED, "resampling %d works on a destination pixel's footprint, which is not built across CRSs "
-                                        "(nearest, bilinear, cubic, cubic_spline and lanczos are)", resampling);
+        return fail(HK_ERR_UNSUPPORTED, affine ? "resampling %d works on a destination pixel's footprint, which is not built between "
+                                                 "rotated / sheared grids (nearest, bilinear, cubic, cubic_spline and lanczos are)"
+                                               : "resampling %d works on a destination pixel's footprint, which is not built across CRSs "
+                                                 "(nearest, bilinear, cubic, cubic_spline and lanczos are)", resampling);
     if (dst_height > 65535) return fail(HK_ERR_UNSUPPORTED, "destination taller than 65535 rows");
     return check_nodata_mode(src_nodata_mode);
 }
 
-int hk_reproject_crs_dev(hk_ctx* ctx, const hk_warp_desc* warp, const float* src_dev, int32_t n_bands, int32_t src_height,
-                         int32_t src_width, int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode,
-                         float src_nodata, double kx, double ky, int32_t resampling, float* dst_dev, int32_t dst_height,
-                         int32_t dst_width, int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream) {
-    int rc = check_reproject_crs(ctx, warp, src_dev, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst_dev,
+extern "C++" template <typename Desc>
+static int reproject_warp_dev(hk_ctx* ctx, const Desc* warp, const float* src_dev, int32_t n_bands, int32_t src_height,
+                              int32_t src_width, int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode,
+                              float src_nodata, double kx, double ky, int32_t resampling, float* dst_dev, int32_t dst_height,
+                              int32_t dst_width, int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream) {
+    int rc = check_reproject_crs(ctx, warp, std::is_same<Desc, hk_affine_warp_desc>::value, src_dev, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst_dev,
                                  dst_height, dst_width);
     if (rc) return rc;
     if (src_stride < src_width || dst_stride < dst_width) return fail(HK_ERR_ARG, "row stride smaller than width");
@@ -1756,10 +1783,11 @@ int hk_reproject_crs_dev(hk_ctx* ctx, const hk_warp_desc* warp, const float* src
                                                        ctx->slots[stream].stream, &why), why);
 }
 
-int hk_reproject_crs(hk_ctx* ctx, const hk_warp_desc* warp, const float* src, int32_t n_bands, int32_t src_height,
-                     int32_t src_width, int32_t src_nodata_mode, float src_nodata, double kx, double ky, int32_t resampling,
-                     float* dst, int32_t dst_height, int32_t dst_width, float dst_fill) {
-    int rc = check_reproject_crs(ctx, warp, src, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst,
+extern "C++" template <typename Desc>
+static int reproject_warp_host(hk_ctx* ctx, const Desc* warp, const float* src, int32_t n_bands, int32_t src_height,
+                               int32_t src_width, int32_t src_nodata_mode, float src_nodata, double kx, double ky,
+                               int32_t resampling, float* dst, int32_t dst_height, int32_t dst_width, float dst_fill) {
+    int rc = check_reproject_crs(ctx, warp, std::is_same<Desc, hk_affine_warp_desc>::value, src, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst,
                                  dst_height, dst_width);
     if (rc) return rc;
     HK_ENTER(ctx);
@@ -1779,6 +1807,39 @@ int hk_reproject_crs(hk_ctx* ctx, const hk_warp_desc* warp, const float* src, in
         return rc;
     if ((rc = stage_d2h(sl, dst, dbytes, d_dst, dbytes, dbytes, 1))) return rc;
     return stage_finish(sl);
+}
+
+int hk_reproject_crs_dev(hk_ctx* ctx, const hk_warp_desc* warp, const float* src_dev, int32_t n_bands, int32_t src_height,
+                         int32_t src_width, int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode,
+                         float src_nodata, double kx, double ky, int32_t resampling, float* dst_dev, int32_t dst_height,
+                         int32_t dst_width, int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream) {
+    return reproject_warp_dev(ctx, warp, src_dev, n_bands, src_height, src_width, src_stride, src_band_stride, src_nodata_mode,
+                              src_nodata, kx, ky, resampling, dst_dev, dst_height, dst_width, dst_stride, dst_band_stride, dst_fill,
+                              stream);
+}
+
+int hk_reproject_crs(hk_ctx* ctx, const hk_warp_desc* warp, const float* src, int32_t n_bands, int32_t src_height,
+                     int32_t src_width, int32_t src_nodata_mode, float src_nodata, double kx, double ky, int32_t resampling,
+                     float* dst, int32_t dst_height, int32_t dst_width, float dst_fill) {
+    return reproject_warp_host(ctx, warp, src, n_bands, src_height, src_width, src_nodata_mode, src_nodata, kx, ky, resampling, dst,
+                               dst_height, dst_width, dst_fill);
+}
+
+int hk_reproject_affine_dev(hk_ctx* ctx, const hk_affine_warp_desc* warp, const float* src_dev, int32_t n_bands,
+                            int32_t src_height, int32_t src_width, int64_t src_stride, int64_t src_band_stride,
+                            int32_t src_nodata_mode, float src_nodata, double kx, double ky, int32_t resampling, float* dst_dev,
+                            int32_t dst_height, int32_t dst_width, int64_t dst_stride, int64_t dst_band_stride, float dst_fill,
+                            int32_t stream) {
+    return reproject_warp_dev(ctx, warp, src_dev, n_bands, src_height, src_width, src_stride, src_band_stride, src_nodata_mode,
+                              src_nodata, kx, ky, resampling, dst_dev, dst_height, dst_width, dst_stride, dst_band_stride, dst_fill,
+                              stream);
+}
+
+int hk_reproject_affine(hk_ctx* ctx, const hk_affine_warp_desc* warp, const float* src, int32_t n_bands, int32_t src_height,
+                        int32_t src_width, int32_t src_nodata_mode, float src_nodata, double kx, double ky, int32_t resampling,
+                        float* dst, int32_t dst_height, int32_t dst_width, float dst_fill) {
+    return reproject_warp_host(ctx, warp, src, n_bands, src_height, src_width, src_nodata_mode, src_nodata, kx, ky, resampling, dst,
+                               dst_height, dst_width, dst_fill);
 }
 
 int hk_partial_mask(hk_ctx* ctx, const float* in, int64_t in_stride, int32_t in_nodata_mode, float in_nodata,

@@ -4,7 +4,8 @@
 #include <stdint.h>
 #include <string.h>
 
-struct hk_warp_desc;  // include/homonim_hk.h
+struct hk_warp_desc;         // include/homonim_hk.h
+struct hk_affine_warp_desc;  // include/homonim_hk.h
 
 namespace hk {
 
@@ -307,6 +308,13 @@ hipError_t launch_resample(int mode, const float* src, long long src_stride, lon
 hipError_t launch_warp_coords(const hk_warp_desc* desc, double off_row, double off_col, double* x, double* y, long long stride,
                               int h, int w, hipStream_t stream, const char** why);
 hipError_t launch_warp_resample(int mode, const hk_warp_desc* desc, const float* src, long long src_stride,
+                                long long src_band_stride, int sh, int sw, int n_bands, int nd_mode, float nodata, double kx,
+                                double ky, float* dst, long long dst_stride, long long dst_band_stride, int dh, int dw,
+                                float dst_fill, hipStream_t stream, const char** why);
+// The same for rotated / sheared grids, in one CRS or across two (hk_affine_warp_desc): full affines at both ends.
+hipError_t launch_warp_coords(const hk_affine_warp_desc* desc, double off_row, double off_col, double* x, double* y,
+                              long long stride, int h, int w, hipStream_t stream, const char** why);
+hipError_t launch_warp_resample(int mode, const hk_affine_warp_desc* desc, const float* src, long long src_stride,
                                 long long src_band_stride, int sh, int sw, int n_bands, int nd_mode, float nodata, double kx,
                                 double ky, float* dst, long long dst_stride, long long dst_band_stride, int dh, int dw,
                                 float dst_fill, hipStream_t stream, const char** why);

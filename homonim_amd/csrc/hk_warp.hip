@@ -22,6 +22,8 @@
 #include "hk_resample_taps.h"
 
 #include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
 
 namespace hk {
 
@@ -36,11 +38,37 @@ struct CrsParams {
     double alp[6], bet[6];
 };
 
-struct WarpMap {
+// How a destination pixel position becomes a source pixel coordinate: the template parameter of warp_coord() and of everything
+// that carries a map.  WARP_AXIS: two CRSs, axis-aligned geo-transforms (hk_warp_desc).  WARP_AFFINE: two CRSs, full six-coefficient
+// affines at both ends (rotated / sheared grids).  WARP_AFFINE_SAME: full affines within ONE CRS -- no CRS mathematics at all, so
+// it serves CRSs this library cannot define.
+enum { WARP_AXIS = 0, WARP_AFFINE = 1, WARP_AFFINE_SAME = 2 };
+
+// geo-transform in Affine order: x = a * col + b * row + c, y = d * col + e * row + f
+struct AffineGt {
+    double a, b, c, d, e, f;
+};
+
+template <int PATH>
+struct WarpMapT;
+template <>
+struct WarpMapT<WARP_AXIS> {
     CrsParams src, dst;
     double dx0, ddx, dy0, ddy;  // destination geo-transform: X = dx0 + col * ddx, Y = dy0 + row * ddy
     double sx0, sdx, sy0, sdy;  // source geo-transform, inverted per pixel: col = (X - sx0) / sdx
 };
+template <>
+struct WarpMapT<WARP_AFFINE> {
+    CrsParams src, dst;
+    AffineGt d, s;  // destination and source geo-transforms
+    double det;     // s.a * s.e - s.b * s.d, formed once on the host
+};
+template <>
+struct WarpMapT<WARP_AFFINE_SAME> {
+    AffineGt d, s;
+    double det;
+};
+using WarpMap = WarpMapT<WARP_AXIS>;
 
 constexpr double WARP_DEG = 57.295779513082320877;   // degrees per radian
 constexpr double WARP_COORD_MAX = 1e15;              // a source coordinate at or beyond this (or NaN) is "no data"
@@ -112,28 +140,47 @@ __device__ __forceinline__ double wrap180(double d) {
 }
 
 // THE coordinate function: destination pixel position (row, col; continuous, integers = pixel edges) -> continuous source pixel
-// coordinates; NaN where the position has no image in the source CRS.
-__device__ __forceinline__ void warp_coord(const WarpMap& m, double row, double col, double& sx, double& sy) {
-    const double X = m.dx0 + col * m.ddx, Y = m.dy0 + row * m.ddy;
+// coordinates; NaN where the position has no image in the source CRS.  The association of every expression is part of the
+// contract (the tests restate it): axis-aligned X = dx0 + col * ddx and (x - sx0) / sdx; affine X = (c + col * a) + row * b,
+// Y = (f + col * d) + row * e, u = x - s.c, v = y - s.f, column (u * s.e - v * s.b) / det, row (v * s.a - u * s.d) / det.
+// The order of the declarations below is the one the axis-aligned builds were first compiled from: with it they compile to the
+// same instructions as before the affine paths existed (the compiler's schedule follows the order of the locals).
+template <int PATH>
+__device__ __forceinline__ void warp_coord(const WarpMapT<PATH>& m, double row, double col, double& sx, double& sy) {
+    double X, Y;
+    if constexpr (PATH == WARP_AXIS) X = m.dx0 + col * m.ddx, Y = m.dy0 + row * m.ddy;
+    else X = (m.d.c + col * m.d.a) + row * m.d.b, Y = (m.d.f + col * m.d.d) + row * m.d.e;
     double lon, lat;  // degrees
     bool ok = true;
-    if (m.dst.kind == HK_CRS_GEOGRAPHIC) {
-        lon = X, lat = Y;
-        ok = fabs(Y) <= 90.0;
-    } else {
-        double phi, dlam;
-        tm_inverse(m.dst, X, Y, phi, dlam);
-        lon = m.dst.lon0 + dlam * WARP_DEG, lat = phi * WARP_DEG;
+    if constexpr (PATH != WARP_AFFINE_SAME) {
+        if (m.dst.kind == HK_CRS_GEOGRAPHIC) {
+            lon = X, lat = Y;
+            ok = fabs(Y) <= 90.0;
+        } else {
+            double phi, dlam;
+            tm_inverse(m.dst, X, Y, phi, dlam);
+            lon = m.dst.lon0 + dlam * WARP_DEG, lat = phi * WARP_DEG;
+        }
     }
     double x, y;
-    if (m.src.kind == HK_CRS_GEOGRAPHIC) {
-        x = wrap180(lon), y = lat;
+    if constexpr (PATH == WARP_AFFINE_SAME) {
+        x = X, y = Y;  // one CRS: no CRS mathematics
     } else {
-        ok = tm_forward(m.src, lat / WARP_DEG, wrap180(lon - m.src.lon0) / WARP_DEG, x, y) && ok;
+        if (m.src.kind == HK_CRS_GEOGRAPHIC) {
+            x = wrap180(lon), y = lat;
+        } else {
+            ok = tm_forward(m.src, lat / WARP_DEG, wrap180(lon - m.src.lon0) / WARP_DEG, x, y) && ok;
+        }
     }
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    sx = ok ? (x - m.sx0) / m.sdx : nan;
-    sy = ok ? (y - m.sy0) / m.sdy : nan;
+    if constexpr (PATH == WARP_AXIS) {
+        sx = ok ? (x - m.sx0) / m.sdx : nan;
+        sy = ok ? (y - m.sy0) / m.sdy : nan;
+    } else {
+        const double u = x - m.s.c, v = y - m.s.f;
+        sx = ok ? (u * m.s.e - v * m.s.b) / m.det : nan;
+        sy = ok ? (v * m.s.a - u * m.s.d) / m.det : nan;
+    }
 }
 
 __device__ __forceinline__ bool warp_coord_usable(double sx, double sy) {
@@ -141,26 +188,54 @@ __device__ __forceinline__ bool warp_coord_usable(double sx, double sy) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-struct WarpCoordArgs {
+// Thread mapping.  The axis-aligned builds keep one workgroup = 256 consecutive pixels of one destination row: their source
+// footprint is a row segment, whatever the CRSs.  Between rotated grids a destination row crosses source rows -- at 90 degrees the
+// 64 lanes of a wave would read 64 source rows, one cache line each -- so the affine builds run on a two-dimensional thread tile
+// (blockDim.x x blockDim.y = 256, chosen by warp_tile()): a workgroup's source footprint stays compact at any angle.
+
+// a thread's destination row: the launch's row of workgroups (axis-aligned builds), or its place in the tile
+template <int PATH>
+__device__ __forceinline__ int warp_row() {
+    if constexpr (PATH == WARP_AXIS) return blockIdx.y;
+    else return blockIdx.y * blockDim.y + threadIdx.y;
+}
+
+template <int PATH>
+struct WarpCoordArgsT {
     double* x;
     double* y;
     long long stride;
     int h, w;
     double off_row, off_col;
-    WarpMap map;
+    WarpMapT<PATH> map;
 };
+using WarpCoordArgs = WarpCoordArgsT<WARP_AXIS>;
 
-__global__ void __launch_bounds__(256) warp_coords_kernel(const WarpCoordArgs a) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    if (j >= a.w) return;
+template <int PATH>
+__device__ __forceinline__ void warp_coords_pixel(const WarpCoordArgsT<PATH>& a, int i, int j) {
     double sx, sy;
     warp_coord(a.map, (double)i + a.off_row, (double)j + a.off_col, sx, sy);
     a.x[(long long)i * a.stride + j] = sx;
     a.y[(long long)i * a.stride + j] = sy;
 }
 
-struct WarpArgs {
+__global__ void __launch_bounds__(256) warp_coords_kernel(const WarpCoordArgs a) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= a.w) return;
+    warp_coords_pixel(a, i, j);
+}
+
+template <int PATH>
+__global__ void __launch_bounds__(256) warp_coords_tile_kernel(const WarpCoordArgsT<PATH> a) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y * blockDim.y + threadIdx.y;
+    if (j >= a.w || i >= a.h) return;
+    warp_coords_pixel(a, i, j);
+}
+
+template <int PATH>
+struct WarpArgsT {
     const float* src;
     float* dst;
     long long src_stride, src_band_stride, dst_stride, dst_band_stride;
@@ -169,15 +244,16 @@ struct WarpArgs {
     float nodata;
     float dst_fill;
     double kx, ky;  // source pixels per destination pixel (mean step): pick and scale the stretched kernels
-    WarpMap map;
+    WarpMapT<PATH> map;
 };
+using WarpArgs = WarpArgsT<WARP_AXIS>;
 
 // resample_kernel<0 / 1 / 3> of hk_resample.hip with warped coordinates; one thread per destination pixel, all bands
-template <int MODE>
-__global__ void __launch_bounds__(256) warp_kernel(const WarpArgs a) {
+template <int MODE, int PATH = WARP_AXIS>
+__global__ void __launch_bounds__(256) warp_kernel(const WarpArgsT<PATH> a) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    if (j >= a.dw) return;
+    const int i = warp_row<PATH>();
+    if (j >= a.dw || (PATH != WARP_AXIS && i >= a.dh)) return;
     double sx, sy;
     warp_coord(a.map, (double)i + 0.5, (double)j + 0.5, sx, sy);
     const bool usable = warp_coord_usable(sx, sy);
@@ -236,11 +312,11 @@ __global__ void __launch_bounds__(256) warp_kernel(const WarpArgs a) {
 }
 
 // resample_conv_kernel<1..4> of hk_resample.hip (GWKResample for any scale) with warped coordinates
-template <int KIND>
-__global__ void __launch_bounds__(256) warp_conv_kernel(const WarpArgs a) {
+template <int KIND, int PATH = WARP_AXIS>
+__global__ void __launch_bounds__(256) warp_conv_kernel(const WarpArgsT<PATH> a) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    if (j >= a.dw) return;
+    const int i = warp_row<PATH>();
+    if (j >= a.dw || (PATH != WARP_AXIS && i >= a.dh)) return;
     constexpr int R = KIND == 1 ? 1 : (KIND == 4 ? 3 : 2);
     const double xs = a.kx > 1.0 ? 1.0 / a.kx : 1.0, ys = a.ky > 1.0 ? 1.0 / a.ky : 1.0;
     const int rx = xs < 1.0 ? (int)ceil((double)R / xs) : R, ry = ys < 1.0 ? (int)ceil((double)R / ys) : R;
@@ -281,6 +357,17 @@ __global__ void __launch_bounds__(256) warp_conv_kernel(const WarpArgs a) {
         a.dst[(long long)b * a.dst_band_stride + (long long)i * a.dst_stride + j] = got ? (float)result : a.dst_fill;
     }
 }
+
+// the affine builds by names of one template argument, which is what HK_LAUNCH can spell
+template <int MODE>
+constexpr auto warp_affine_kernel = warp_kernel<MODE, WARP_AFFINE>;
+template <int MODE>
+constexpr auto warp_same_kernel = warp_kernel<MODE, WARP_AFFINE_SAME>;
+template <int KIND>
+constexpr auto warp_conv_affine_kernel = warp_conv_kernel<KIND, WARP_AFFINE>;
+template <int KIND>
+constexpr auto warp_conv_same_kernel = warp_conv_kernel<KIND, WARP_AFFINE_SAME>;
+
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host: descriptor -> device parameters
@@ -333,6 +420,23 @@ static bool warp_map(const hk_warp_desc& d, WarpMap& m, const char** why) {
     return true;
 }
 
+// one launch of the build that `mode` (rasterio.enums.Resampling value 0..4) and `stretched` pick, among the builds of one path
+#define HK_WARP_LAUNCH_MODES(plain, conv)                                                                                        \
+    switch (mode) {                                                                                                              \
+        case 0: HK_LAUNCH(plain<0>, grid, block, 0, stream, a); break;                                                           \
+        case 1:                                                                                                                  \
+            if (stretched) HK_LAUNCH(conv<1>, grid, block, 0, stream, a);                                                        \
+            else HK_LAUNCH(plain<1>, grid, block, 0, stream, a);                                                                 \
+            break;                                                                                                               \
+        case 2: HK_LAUNCH(conv<2>, grid, block, 0, stream, a); break;                                                            \
+        case 3:                                                                                                                  \
+            if (stretched) HK_LAUNCH(conv<3>, grid, block, 0, stream, a);                                                        \
+            else HK_LAUNCH(plain<3>, grid, block, 0, stream, a);                                                                 \
+            break;                                                                                                               \
+        case 4: HK_LAUNCH(conv<4>, grid, block, 0, stream, a); break;                                                            \
+        default: *why = "resampling is not one of nearest / bilinear / cubic / cubic_spline / lanczos"; return hipErrorInvalidValue; \
+    }
+
 hipError_t launch_warp_coords(const hk_warp_desc* desc, double off_row, double off_col, double* x, double* y, long long stride,
                               int h, int w, hipStream_t stream, const char** why) {
     WarpCoordArgs a;
@@ -354,21 +458,98 @@ hipError_t launch_warp_resample(int mode, const hk_warp_desc* desc, const float*
     a.nodata = nodata, a.dst_fill = dst_fill, a.kx = kx, a.ky = ky;
     const dim3 grid((dw + 255) / 256, dh), block(256);
     const bool stretched = kx > 1.0 + 1e-9 || ky > 1.0 + 1e-9;  // as launch_resample picks the kernels
-    switch (mode) {
-        case 0: HK_LAUNCH(warp_kernel<0>, grid, block, 0, stream, a); break;
-        case 1:
-            if (stretched) HK_LAUNCH(warp_conv_kernel<1>, grid, block, 0, stream, a);
-            else HK_LAUNCH(warp_kernel<1>, grid, block, 0, stream, a);
-            break;
-        case 2: HK_LAUNCH(warp_conv_kernel<2>, grid, block, 0, stream, a); break;
-        case 3:
-            if (stretched) HK_LAUNCH(warp_conv_kernel<3>, grid, block, 0, stream, a);
-            else HK_LAUNCH(warp_kernel<3>, grid, block, 0, stream, a);
-            break;
-        case 4: HK_LAUNCH(warp_conv_kernel<4>, grid, block, 0, stream, a); break;
-        default: *why = "resampling is not one of nearest / bilinear / cubic / cubic_spline / lanczos"; return hipErrorInvalidValue;
+    HK_WARP_LAUNCH_MODES(warp_kernel, warp_conv_kernel);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// full affines (hk_affine_warp_desc)
+
+static bool affine_gt(const double (&src)[6], const double (&dst)[6], AffineGt& s, AffineGt& d, double& det, const char** why) {
+    for (int k = 0; k < 6; ++k)
+        if (!isfinite(src[k]) || !isfinite(dst[k])) return *why = "geo-transform is not finite", false;
+    s = {src[0], src[1], src[2], src[3], src[4], src[5]};
+    d = {dst[0], dst[1], dst[2], dst[3], dst[4], dst[5]};
+    det = s.a * s.e - s.b * s.d;
+    const double ddet = d.a * d.e - d.b * d.d;
+    if (det == 0.0 || ddet == 0.0 || !isfinite(det) || !isfinite(ddet)) return *why = "degenerate geo-transform", false;
+    return true;
+}
+
+static bool warp_map(const hk_affine_warp_desc& d, WarpMapT<WARP_AFFINE>& m, const char** why) {
+    if (!crs_params(d.src_crs, m.src, why) || !crs_params(d.dst_crs, m.dst, why)) return false;
+    if (d.src_crs.a != d.dst_crs.a || d.src_crs.inv_f != d.dst_crs.inv_f)
+        return *why = "the two CRSs are on different ellipsoids (no datum shifts)", false;
+    return affine_gt(d.src_gt, d.dst_gt, m.s, m.d, m.det, why);
+}
+
+static bool warp_map(const hk_affine_warp_desc& d, WarpMapT<WARP_AFFINE_SAME>& m, const char** why) {
+    return affine_gt(d.src_gt, d.dst_gt, m.s, m.d, m.det, why);
+}
+
+// The thread tile of the affine builds, width x height = 256.  32 x 8 is provisional: profiles/warp.txt holds no measurement
+// yet.  HK_WARP_TILE=WxH, read once, overrides it for that measurement (tools/warp_timing.py).  Any tile gives the same bits: a
+// thread's pixel is all it sees.
+static dim3 warp_tile() {
+    static const dim3 tile = [] {
+        int w = 32, h = 8, ew = 0, eh = 0;
+        const char* e = getenv("HK_WARP_TILE");
+        if (e && sscanf(e, "%dx%d", &ew, &eh) == 2 && ew >= 1 && eh >= 1 && ew * eh == 256) w = ew, h = eh;
+        return dim3(w, h);
+    }();
+    return tile;
+}
+
+static dim3 warp_tile_grid(dim3 tile, int h, int w) { return dim3((w + tile.x - 1) / tile.x, (h + tile.y - 1) / tile.y); }
+
+template <int PATH>
+static hipError_t launch_coords_tiled(const hk_affine_warp_desc* desc, double off_row, double off_col, double* x, double* y,
+                                      long long stride, int h, int w, hipStream_t stream, const char** why) {
+    WarpCoordArgsT<PATH> a;
+    if (!warp_map(*desc, a.map, why)) return hipErrorInvalidValue;
+    a.x = x, a.y = y, a.stride = stride, a.h = h, a.w = w, a.off_row = off_row, a.off_col = off_col;
+    const dim3 block = warp_tile(), grid = warp_tile_grid(block, h, w);
+    if constexpr (PATH == WARP_AFFINE) HK_LAUNCH(warp_coords_tile_kernel<WARP_AFFINE>, grid, block, 0, stream, a);
+    else HK_LAUNCH(warp_coords_tile_kernel<WARP_AFFINE_SAME>, grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_warp_coords(const hk_affine_warp_desc* desc, double off_row, double off_col, double* x, double* y,
+                              long long stride, int h, int w, hipStream_t stream, const char** why) {
+    return desc->same_crs ? launch_coords_tiled<WARP_AFFINE_SAME>(desc, off_row, off_col, x, y, stride, h, w, stream, why)
+                          : launch_coords_tiled<WARP_AFFINE>(desc, off_row, off_col, x, y, stride, h, w, stream, why);
+}
+
+template <int PATH>
+static hipError_t launch_resample_tiled(int mode, const hk_affine_warp_desc* desc, const float* src, long long src_stride,
+                                        long long src_band_stride, int sh, int sw, int n_bands, int nd_mode, float nodata,
+                                        double kx, double ky, float* dst, long long dst_stride, long long dst_band_stride, int dh,
+                                        int dw, float dst_fill, hipStream_t stream, const char** why) {
+    WarpArgsT<PATH> a;
+    if (!warp_map(*desc, a.map, why)) return hipErrorInvalidValue;
+    a.src = src, a.dst = dst, a.src_stride = src_stride, a.src_band_stride = src_band_stride, a.dst_stride = dst_stride;
+    a.dst_band_stride = dst_band_stride, a.sh = sh, a.sw = sw, a.dh = dh, a.dw = dw, a.n_bands = n_bands, a.nd_mode = nd_mode;
+    a.nodata = nodata, a.dst_fill = dst_fill, a.kx = kx, a.ky = ky;
+    const dim3 block = warp_tile(), grid = warp_tile_grid(block, dh, dw);
+    const bool stretched = kx > 1.0 + 1e-9 || ky > 1.0 + 1e-9;
+    if constexpr (PATH == WARP_AFFINE) {
+        HK_WARP_LAUNCH_MODES(warp_affine_kernel, warp_conv_affine_kernel);
+    } else {
+        HK_WARP_LAUNCH_MODES(warp_same_kernel, warp_conv_same_kernel);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_warp_resample(int mode, const hk_affine_warp_desc* desc, const float* src, long long src_stride,
+                                long long src_band_stride, int sh, int sw, int n_bands, int nd_mode, float nodata, double kx,
+                                double ky, float* dst, long long dst_stride, long long dst_band_stride, int dh, int dw,
+                                float dst_fill, hipStream_t stream, const char** why) {
+    return desc->same_crs ? launch_resample_tiled<WARP_AFFINE_SAME>(mode, desc, src, src_stride, src_band_stride, sh, sw, n_bands,
+                                                                    nd_mode, nodata, kx, ky, dst, dst_stride, dst_band_stride, dh,
+                                                                    dw, dst_fill, stream, why)
+                          : launch_resample_tiled<WARP_AFFINE>(mode, desc, src, src_stride, src_band_stride, sh, sw, n_bands,
+                                                               nd_mode, nodata, kx, ky, dst, dst_stride, dst_band_stride, dh, dw,
+                                                               dst_fill, stream, why);
 }
 
 }  // namespace hk

@@ -32,7 +32,7 @@ from homonim_amd import _hk, utils
 from homonim_amd import crs as crs_defs
 from homonim_amd.enums import Model, ProcCrs, Resampling
 from homonim_amd.errors import BlockSizeError, ConfigWarning, DeviceError, ImageFormatWarning, IoError
-from homonim_amd.geo import Affine, CRS, Window
+from homonim_amd.geo import Affine, CRS, Window, is_rotated, pixel_size, suggested_warp_grid
 from homonim_amd.kernel_model import KernelModel, RefSpaceModel, SrcSpaceModel
 from homonim_amd.raster_array import RasterArray
 
@@ -227,7 +227,8 @@ def _as_affine(transform, name: str) -> Optional[Affine]:
 def north_up(array: np.ndarray, transform: Optional[Affine]):
     """ (array, transform) with rows running north to south and columns west to east: a raster whose geo-transform has a
     positive row step (south-up) or a negative column step is flipped along that axis -- what the reference's
-    ``utils.same_orientation_crs`` obtains by re-projecting it through a WarpedVRT.  Rotated grids are not handled. """
+    ``utils.same_orientation_crs`` obtains by re-projecting it through a WarpedVRT.  A flip cannot bring a rotated or sheared
+    grid north-up: ``RasterFuse`` warps those on the device (``_north_up_warp``), this function refuses them. """
     if transform is None:
         return array, transform
     if transform.b or transform.d:
@@ -306,14 +307,24 @@ class RasterFuse:
         transform = _as_affine(transform, 'transform')
         ref_transform = _as_affine(ref_transform, 'ref_transform')
         # south-up (or column-mirrored) rasters are brought to north-up first, as the reference does through a WarpedVRT
-        # (homonim/utils.py:190-209; for an axis-aligned raster that re-projection is the flip); outputs are north-up
-        src, transform = north_up(src, transform)
-        ref, ref_transform = north_up(ref, ref_transform)
+        # (homonim/utils.py:190-209; for an axis-aligned raster that re-projection is the flip); outputs are north-up.  Rotated and
+        # sheared rasters are left for the warps below: the same WarpedVRT, bilinear
+        src_rotated = transform is not None and is_rotated(transform)
+        ref_rotated = ref_transform is not None and is_rotated(ref_transform)
+        if not src_rotated:
+            src, transform = north_up(src, transform)
+        if not ref_rotated:
+            ref, ref_transform = north_up(ref, ref_transform)
         if ref.shape[0] < src.shape[0]:
             raise ValueError('`ref` has fewer bands than `src`')
         if crs is not None and ref_crs is not None and not crs_defs.same_crs(crs, ref_crs):
             src, src_nodata, crs, transform, ref, ref_nodata, ref_transform, proc_crs = self._to_one_crs(
                 src, src_nodata, crs, transform, ref, ref_nodata, ref_crs, ref_transform, ProcCrs(proc_crs))
+        else:
+            if src_rotated:
+                src, src_nodata, transform = self._north_up_warp(src, src_nodata, crs or ref_crs, transform)
+            if ref_rotated:
+                ref, ref_nodata, ref_transform = self._north_up_warp(ref, ref_nodata, ref_crs or crs, ref_transform)
         self._src, self._ref = src, ref
         self._src_nodata, self._ref_nodata = src_nodata, ref_nodata
         self._crs = crs or CRS()
@@ -333,12 +344,31 @@ class RasterFuse:
         self._closed = False
         self._write_lock = threading.Lock()
 
+    @staticmethod
+    def _device_context():
+        return _hk.get_context(int(os.environ.get('HOMONIM_AMD_DEVICE', os.environ.get('LOCAL_RANK', '0'))))
+
+    @classmethod
+    def _north_up_warp(cls, array, nodata, crs, transform):
+        """ A rotated / sheared raster brought north-up in its own CRS, whatever its label: warped bilinearly onto
+        ``geo.suggested_warp_grid`` of that CRS, all bands in one device call (homonim/utils.py:190-209).  Returns (array, nodata,
+        transform); an image without nodata gets NaN for what the warp leaves empty. """
+        crs = crs or CRS()
+        out_nodata = float('nan') if nodata is None else nodata
+        grid, shape = suggested_warp_grid(crs, transform, array.shape[-2:], crs)
+        ra = RasterArray(array, crs, transform, nodata=nodata).reproject(
+            transform=grid, shape=shape, nodata=out_nodata, resampling=Resampling.bilinear, context=cls._device_context())
+        return ra.array, out_nodata, ra.transform
+
     def _to_one_crs(self, src, src_nodata, crs, transform, ref, ref_nodata, ref_crs, ref_transform, proc_crs: ProcCrs):
         """ Source and reference in different CRSs: what ``RasterPairReader`` does with such a pair (homonim/raster_pair.py:160-166,
         homonim/utils.py:190-209).  Warn; resolve ``proc_crs=auto`` from the pixel areas, the reference's pixel brought into the
         source's CRS at the source's centre; warp the processing-grid image -- ``proc_crs=src``: the source, otherwise the reference
         -- into the other's CRS on ``geo.suggested_warp_grid``, bilinear, all bands in one device call.  Returns the pair on one
-        CRS and the resolved ``proc_crs``; an image without nodata gets NaN for what the warp leaves empty. """
+        CRS and the resolved ``proc_crs``; an image without nodata gets NaN for what the warp leaves empty.
+        Rotated / sheared grids: pixel sizes are the lengths of the column and row step vectors, the source's centre goes through
+        the full affine; the processing-grid image goes from its rotated grid into the other CRS in that single warp, the other
+        image, if rotated, is brought north-up in its own CRS (``_north_up_warp``). """
         import warnings
         names = [os.path.basename(fn) if fn else 'memory' for fn in (self._src_filename, self._ref_filename)]
         warnings.warn(f'Source and reference image will be re-projected to the same CRS: {names[0]} and {names[1]}',
@@ -348,17 +378,23 @@ class RasterFuse:
             raise ValueError('source and reference in different CRSs need their geo-transforms (`transform`, `ref_transform`)')
         # the reference's pixel at the source's centre, in source CRS units
         h, w = src.shape[-2:]
-        xc, yc = transform.c + transform.a * w / 2, transform.f + transform.e * h / 2
+        xc, yc = transform * (w / 2, h / 2)   # (the axis-aligned c + a * w / 2, f + e * h / 2 to the bit: b = d = 0)
         xr, yr = crs_defs.transform_coords(crs, ref_crs, xc, yc)
-        px, py = crs_defs.transform_coords(ref_crs, crs, xr + np.array([0., ref_transform.a, 0.]),
-                                           yr + np.array([0., 0., ref_transform.e]))
+        px, py = crs_defs.transform_coords(ref_crs, crs, xr + np.array([0., ref_transform.a, ref_transform.b]),
+                                           yr + np.array([0., ref_transform.d, ref_transform.e]))
         ref_res = (float(np.hypot(px[1] - px[0], py[1] - py[0])), float(np.hypot(px[2] - px[0], py[2] - py[0])))
         if not all(math.isfinite(v) and v > 0 for v in ref_res):
             from homonim_amd.errors import ImageContentError
             raise ImageContentError('Reference extent does not cover source image')
-        proc_crs = resolve_proc_crs(Grid(transform, h, w), Grid(Affine(ref_res[0], 0., 0., 0., -ref_res[1], 0.), 1, 1), proc_crs)
-        dev = int(os.environ.get('HOMONIM_AMD_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-        ctx = _hk.get_context(dev)
+        src_res = pixel_size(transform)   # (abs(a), abs(e)) exactly for an axis-aligned grid
+        proc_crs = resolve_proc_crs(Grid(Affine(src_res[0], 0., 0., 0., -src_res[1], 0.), h, w),
+                                    Grid(Affine(ref_res[0], 0., 0., 0., -ref_res[1], 0.), 1, 1), proc_crs)
+        ctx = self._device_context()
+        # the image that stays in its CRS, if rotated, goes north-up there
+        if proc_crs == ProcCrs.src and is_rotated(ref_transform):
+            ref, ref_nodata, ref_transform = self._north_up_warp(ref, ref_nodata, ref_crs, ref_transform)
+        elif proc_crs != ProcCrs.src and is_rotated(transform):
+            src, src_nodata, transform = self._north_up_warp(src, src_nodata, crs, transform)
         if proc_crs == ProcCrs.src:
             nodata = float('nan') if src_nodata is None else src_nodata
             ra = RasterArray(src, crs, transform, nodata=src_nodata).reproject(crs=ref_crs, nodata=nodata,

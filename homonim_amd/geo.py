@@ -24,6 +24,18 @@ class Affine(namedtuple('Affine', 'a b c d e f')):
     def scale(cls, sx: float, sy: float = None) -> 'Affine':
         return cls(sx, 0., 0., 0., sx if sy is None else sy, 0.)
 
+    @classmethod
+    def rotation(cls, angle: float) -> 'Affine':
+        """ Counter-clockwise rotation by ``angle`` degrees about the origin; the entries are exactly 0 / +-1 at multiples of
+        90 degrees, as in the ``affine`` package. """
+        import math
+        quarter = angle % 360.
+        if quarter in (0., 90., 180., 270.):
+            ca, sa = {0.: (1., 0.), 90.: (0., 1.), 180.: (-1., 0.), 270.: (0., -1.)}[quarter]
+        else:
+            ca, sa = math.cos(math.radians(angle)), math.sin(math.radians(angle))
+        return cls(ca, -sa, 0., sa, ca, 0.)
+
     def __mul__(self, other):
         if isinstance(other, Affine) or (hasattr(other, 'a') and hasattr(other, 'f')):
             a, b, c, d, e, f = self
@@ -91,6 +103,17 @@ def _is_affine(obj) -> bool:
     return type(obj).__name__ == 'Affine' and all(hasattr(obj, k) for k in 'abcdef')
 
 
+def is_rotated(transform) -> bool:
+    """ True for a geo-transform with a rotation or shear term (``b`` or ``d`` not zero). """
+    return bool(transform.b or transform.d)
+
+
+def pixel_size(transform) -> Tuple[float, float]:
+    """ The lengths of a geo-transform's column and row step vectors, ``hypot(a, d)`` and ``hypot(b, e)``. """
+    import math
+    return math.hypot(transform.a, transform.d), math.hypot(transform.b, transform.e)
+
+
 def grid_mapping(src_transform, dst_transform) -> Tuple[float, float, float, float]:
     """
     (kx, ox, ky, oy) with ``src_col = kx * dst_col + ox`` and ``src_row = ky * dst_row + oy`` on continuous pixel
@@ -109,21 +132,23 @@ def grid_mapping(src_transform, dst_transform) -> Tuple[float, float, float, flo
 
 def suggested_warp_grid(crs, transform, shape: Tuple[int, int], dst_crs) -> Tuple[Affine, Tuple[int, int]]:
     """
-    (transform, (height, width)) of the grid a raster (``crs``, axis-aligned ``transform``, ``shape`` = (height, width)) gets
-    in ``dst_crs`` when nothing else is asked for -- GDAL's suggested warp output restated: the extent is the bounding box of the
-    raster's outline transformed with 21 points per edge; the pixel is square, its size the transformed corner-to-corner
-    diagonal divided by the diagonal in pixels; the size is ``int(extent / res + 0.5)``; the grid is north-up.
+    (transform, (height, width)) of the grid a raster (``crs``, ``transform`` -- rotated and sheared ones included --, ``shape`` =
+    (height, width)) gets in ``dst_crs`` when nothing else is asked for -- GDAL's suggested warp output restated: the extent is the
+    bounding box of the raster's outline transformed with 21 points per edge; the pixel is square, its size the transformed
+    corner-to-corner diagonal divided by the diagonal in pixels; the size is ``int(extent / res + 0.5)``; the grid is north-up.
+    ``dst_crs`` equal to ``crs`` -- whatever its label, known to homonim_amd/crs.py or not -- is the identity transformation: the
+    north-up grid of a rotated raster in its own CRS.
     """
     import numpy as np
 
     from homonim_amd import crs as _crs
-    if transform.b or transform.d:
-        raise NotImplementedError('re-projection between rotated / sheared grids is not built')
     height, width = int(shape[0]), int(shape[1])
     t = np.linspace(0., 1., 21)
     cols = np.concatenate([t * width, np.full(21, float(width)), t[::-1] * width, np.zeros(21)])
     rows = np.concatenate([np.zeros(21), t * height, np.full(21, float(height)), t[::-1] * height])
-    xs, ys = _crs.transform_coords(crs, dst_crs, transform.c + cols * transform.a, transform.f + rows * transform.e)
+    xs, ys = (transform.c + cols * transform.a) + rows * transform.b, (transform.f + cols * transform.d) + rows * transform.e
+    if not _crs.same_crs(crs, dst_crs):
+        xs, ys = _crs.transform_coords(crs, dst_crs, xs, ys)
     if not (np.isfinite(xs).all() and np.isfinite(ys).all()):
         raise ValueError(f'the raster outline has no image in {dst_crs!r}')
     left, right, bottom, top = float(xs.min()), float(xs.max()), float(ys.min()), float(ys.max())

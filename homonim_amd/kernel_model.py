@@ -193,6 +193,12 @@ def _require_one_crs(a: RasterArray, b: RasterArray):
     if not same_crs(a.crs, b.crs):
         raise NotImplementedError(f'the kernel models take rasters of one CRS, got {a.crs!r} and {b.crs!r}: bring one to the '
                                   'other\'s with RasterArray.reproject(crs=...) first (RasterFuse does)')
+    # ... and on axis-aligned grids: between two different grids the models re-sample with the footprint methods, which are not
+    # built for rotated / sheared ones (RasterFuse brings such rasters north-up before it cuts blocks)
+    from homonim_amd.geo import is_rotated
+    if (is_rotated(a.transform) or is_rotated(b.transform)) and not _same_grid(a, b):
+        raise NotImplementedError('re-projection between rotated / sheared grids is not built for the kernel models: bring the '
+                                  'raster north-up with RasterArray.reproject first (RasterFuse does)')
 
 
 def _full_coverage_mask(model: KernelModel, in_mask_ra: RasterArray, param_ra: RasterArray) -> np.ndarray:

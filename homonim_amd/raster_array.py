@@ -10,9 +10,10 @@ properties :223-351, ``profile``/``proj_profile`` :281-296, ``copy`` :389-391):
 * ``nodata = None`` means "every pixel valid"; changing a numeric/NaN nodata re-labels the currently masked pixels;
 * multi-band arrays are band-major and a pixel is valid if it is valid in ANY band.
 
-``reproject`` (raster_array.py:526-578) runs on the GPU for north-up, axis-aligned grids: within one CRS with every warp
-method -- a restatement of GDAL's warp kernels, see hk_resample.hip -- and between the CRSs homonim_amd/crs.py knows with
-nearest / bilinear / cubic / cubic_spline / lanczos (hk_warp.hip).  Dataset IO stays outside this package (GDAL).
+``reproject`` (raster_array.py:526-578) runs on the GPU: between axis-aligned grids of one CRS with every warp method -- a
+restatement of GDAL's warp kernels, see hk_resample.hip --; between the CRSs homonim_amd/crs.py knows, and to or from rotated
+and sheared grids (in one CRS of any label, or across two known ones), with nearest / bilinear / cubic / cubic_spline / lanczos
+(hk_warp.hip).  Dataset IO stays outside this package (GDAL).
 """
 import math
 from typing import Dict, Optional, Tuple
@@ -21,7 +22,7 @@ import numpy as np
 
 from homonim_amd.enums import Resampling
 from homonim_amd.errors import ImageProfileError
-from homonim_amd.geo import Window, _is_affine, _is_crs, grid_mapping, window_transform
+from homonim_amd.geo import Window, _is_affine, _is_crs, grid_mapping, is_rotated, window_transform
 from homonim_amd.utils import nan_equals
 
 _PROFILE_GEO_KEYS = ('crs', 'transform', 'nodata')
@@ -168,8 +169,9 @@ class RasterArray:
                   resampling: Resampling = Resampling.lanczos, context=None) -> 'RasterArray':
         """
         Re-sample onto another grid (raster_array.py:526-578).  ``transform`` needs ``shape``; the default is this array's own
-        grid, or -- with another ``crs`` -- ``geo.suggested_warp_grid``.  Across CRSs (homonim_amd/crs.py lists the known ones)
-        nearest, bilinear, cubic, cubic_spline and lanczos are built (hk_warp.hip).  Returns a float32 RasterArray with
+        grid, or -- with another ``crs`` -- ``geo.suggested_warp_grid``.  Across CRSs (homonim_amd/crs.py lists the known ones), and
+        whenever this array's or the target's geo-transform is rotated or sheared, nearest, bilinear, cubic, cubic_spline and
+        lanczos are built (hk_warp.hip).  Returns a float32 RasterArray with
         ``nodata`` where nothing valid contributes (0 when ``nodata`` is None, as GDAL leaves the zero-initialised
         destination).
         """
@@ -179,7 +181,10 @@ class RasterArray:
             resampling = Resampling[resampling]
         crs = crs or self._crs
         from homonim_amd import crs as crs_defs  # (deferred like _hk below)
-        if not crs_defs.same_crs(crs, self._crs):
+        same_crs = crs_defs.same_crs(crs, self._crs)
+        if is_rotated(self._transform) or (transform is not None and is_rotated(transform)):
+            return self._reproject_affine(crs, same_crs, transform, shape, nodata, dtype, resampling, context)
+        if not same_crs:
             return self._reproject_crs(crs, transform, shape, nodata, dtype, resampling, context)
         transform = transform or self._transform
         shape = tuple(shape or self.shape)
@@ -221,15 +226,50 @@ class RasterArray:
         return RasterArray(out, crs, transform, nodata=nodata)
 
 
+    def _reproject_affine(self, crs, same_crs: bool, transform, shape, nodata, dtype, resampling: Resampling,
+                          context) -> 'RasterArray':
+        """ ``reproject`` from or onto a rotated / sheared grid, in one CRS -- of any label -- or across two known ones: full
+        affines at both ends of the device's coordinate function (hk_warp.hip). """
+        from homonim_amd import _hk, crs as crs_defs
+        from homonim_amd.geo import suggested_warp_grid
+        if int(resampling) > int(Resampling.lanczos):
+            raise NotImplementedError(f"'{Resampling(resampling).name}' re-sampling between rotated / sheared grids is not built: it "
+                                      'works on a destination pixel\'s footprint (nearest, bilinear, cubic, cubic_spline and lanczos '
+                                      'are)')
+        if np.dtype(dtype or self.dtype) != np.float32:
+            raise NotImplementedError('re-projection yields float32 only')
+        dst_def, src_def = (None, None) if same_crs else crs_defs.definitions(crs, self._crs)
+        if transform is None:   # (`reproject` has refused a transform without a shape)
+            transform, shape = (self._transform, shape or self.shape) if same_crs else suggested_warp_grid(
+                self._crs, self._transform, self.shape, crs)
+        shape = tuple(shape)
+        warp = _hk.make_affine_warp_desc(src_def, self._transform, dst_def, transform)
+        scale = warp_scale(crs, transform, shape, self._crs, self._transform)
+        ctx = context or _hk.default_context()
+        fill = 0.0 if nodata is None else float(nodata)
+        out = ctx.reproject_affine(self._array, self._nodata, warp, scale, shape, int(resampling), fill)
+        return RasterArray(out, crs, transform, nodata=nodata)
+
+
 def warp_scale(dst_crs, dst_transform, dst_shape, src_crs, src_transform) -> Tuple[float, float]:
     """ (kx, ky): source pixels per destination pixel of a warp, the mean step along the destination's central row and column
-    (``crs.transform_coords`` of the two ends of each); they pick the stretched re-sampling kernels and scale their support. """
+    (``crs.transform_coords`` of the two ends of each; the identity within one CRS, whatever its label), through the full affines
+    of the two grids; they pick the stretched re-sampling kernels and scale their support. """
     from homonim_amd import crs as crs_defs
     h, w = float(dst_shape[0]), float(dst_shape[1])
     cols, rows = np.array([0., w, w / 2, w / 2]), np.array([h / 2, h / 2, 0., h])
-    xs, ys = crs_defs.transform_coords(dst_crs, src_crs, dst_transform.c + cols * dst_transform.a,
-                                       dst_transform.f + rows * dst_transform.e)
-    px, py = (xs - src_transform.c) / src_transform.a, (ys - src_transform.f) / src_transform.e
+    d, s = dst_transform, src_transform
+    if is_rotated(d):
+        xs, ys = (d.c + cols * d.a) + rows * d.b, (d.f + cols * d.d) + rows * d.e
+    else:
+        xs, ys = d.c + cols * d.a, d.f + rows * d.e
+    if not crs_defs.same_crs(dst_crs, src_crs):
+        xs, ys = crs_defs.transform_coords(dst_crs, src_crs, xs, ys)
+    if is_rotated(s):
+        u, v, det = xs - s.c, ys - s.f, s.a * s.e - s.b * s.d
+        px, py = (u * s.e - v * s.b) / det, (v * s.a - u * s.d) / det
+    else:
+        px, py = (xs - s.c) / s.a, (ys - s.f) / s.e
     kx, ky = float(np.hypot(px[1] - px[0], py[1] - py[0])) / w, float(np.hypot(px[3] - px[2], py[3] - py[2])) / h
     if not (math.isfinite(kx) and math.isfinite(ky) and kx > 0 and ky > 0):
         raise ValueError('the destination grid has no image in the source CRS')

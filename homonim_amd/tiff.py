@@ -4,12 +4,13 @@ Minimal GeoTIFF reader / writer for the rasters either side of the hot path (no 
 Covers what the reference reads and writes (all of homonim's test rasters and its own output
 profile, homonim/fuse.py:124-149): classic or BigTIFF, little / big endian, strips or tiles, planar ``separate`` or
 ``contig``, uncompressed or DEFLATE (zlib) with predictor none / horizontal differencing, 8 / 16 / 32 / 64-bit integer
-and IEEE float samples; north-up geo-referencing from ModelPixelScale + ModelTiepoint or ModelTransformation; nodata
+and IEEE float samples; geo-referencing from ModelPixelScale + ModelTiepoint or ModelTransformation; nodata
 from GDAL_NODATA; EPSG code / citation from the GeoKey directory; the ``<GDALMetadata>`` items (where the reference keeps
 its FUSE_* provenance, fuse.py:193-207) and the per-band ``DESCRIPTION`` items among them (the band names of a parameter
 file, fuse.py:241-248).  The writer produces tiled, DEFLATE, band-separate files like the reference's
 default output profile, with internal overviews (reduced-resolution images chained behind the first) on request;
-``read_tiff_overviews`` reads those back.  Everything else (other compressions, rotated grids, palettes) raises.
+``read_tiff_overviews`` reads those back.  A rotated or sheared grid is read from, and on request written as, a
+ModelTransformation matrix.  Everything else (other compressions, palettes) raises.
 """
 import mmap
 import re
@@ -102,10 +103,8 @@ def _read_ifd(buf: bytes, offset: Optional[int] = None):
 
 def _geo(tags, height):
     if T_TRANSFORMATION in tags:
-        m = tags[T_TRANSFORMATION]
-        if m[1] != 0 or m[4] != 0:
-            raise IoError('rotated / sheared GeoTIFFs are not supported')
-        tf = Affine(m[0], 0., m[3], 0., m[5], m[7])
+        m = tags[T_TRANSFORMATION]   # the 4 x 4 matrix, row-major: rotation and shear terms included
+        tf = Affine(m[0], m[1], m[3], m[4], m[5], m[7])
     elif T_PIXEL_SCALE in tags and T_TIEPOINT in tags:
         sx, sy = tags[T_PIXEL_SCALE][:2]
         i, j, _, x, y, _ = tags[T_TIEPOINT][:6]
@@ -315,13 +314,17 @@ def _directory(entries, chunks, ifd_off: int, has_next: bool) -> Tuple[bytes, in
 
 def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = None, nodata: Optional[float] = None,
                metadata: Optional[Dict[str, str]] = None, tile: int = 512, compress: bool = True,
-               descriptions: Optional[Sequence[Optional[str]]] = None, overviews: Optional[Sequence[np.ndarray]] = None):
+               descriptions: Optional[Sequence[Optional[str]]] = None, overviews: Optional[Sequence[np.ndarray]] = None,
+               rotated: bool = False):
     """ Write (bands, height, width) as a classic little-endian GeoTIFF: tiled, DEFLATE, band-separate -- the reference's
     default output profile (homonim/fuse.py:124-149: tiled 512 x 512, compress=deflate, interleave=band).  ``descriptions``:
     one band description per band (None: none for that band), written as GDAL writes them.  ``overviews``: the internal
     overviews (homonim/fuse.py:152-165), finest first, each (bands, h_m, w_m) of the raster's dtype: one directory per level
     chained behind the main image's, NewSubfileType = 1, 128-pixel tiles, the main image's sample format, planar
-    configuration and compression, GDAL_NODATA and no geo tags.  The main image is written the same with and without them. """
+    configuration and compression, GDAL_NODATA and no geo tags.  The main image is written the same with and without them.
+    ``rotated``: accept a rotated / sheared ``transform`` and write it as a ModelTransformation matrix instead of pixel scale +
+    tie point; without it such a transform is refused -- everything this package produces is north-up, so a rotated grid on
+    the way out is a mistake unless it is asked for. """
     a = np.asarray(array)
     if a.ndim == 2:
         a = a[None]
@@ -329,8 +332,8 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
            ('f', 4): (3, 32), ('f', 8): (3, 64)}.get((a.dtype.kind, a.dtype.itemsize))
     if key is None:
         raise IoError(f"unsupported dtype '{a.dtype}'")
-    if transform.b != 0 or transform.d != 0:
-        raise IoError('rotated / sheared grids are not supported')
+    if (transform.b != 0 or transform.d != 0) and not rotated:
+        raise IoError('rotated / sheared grids are not written unless asked for (rotated=True)')
     fmt, bits = key
     nb, h, w = a.shape
     levels = []
@@ -372,8 +375,13 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
 
     chunks = _tile_chunks(a, tile, compress)
     entries, add = image_entries(a, tile, chunks, False)
-    add(T_PIXEL_SCALE, 12, [float(transform.a), float(-transform.e), 0.])
-    add(T_TIEPOINT, 12, [0., 0., 0., float(transform.c), float(transform.f), 0.])
+    if transform.b != 0 or transform.d != 0:   # a rotated / sheared grid: the full matrix instead of pixel scale + tie point
+        add(T_TRANSFORMATION, 12, [float(transform.a), float(transform.b), 0., float(transform.c),
+                                   float(transform.d), float(transform.e), 0., float(transform.f),
+                                   0., 0., 0., 0., 0., 0., 0., 1.])
+    else:
+        add(T_PIXEL_SCALE, 12, [float(transform.a), float(-transform.e), 0.])
+        add(T_TIEPOINT, 12, [0., 0., 0., float(transform.c), float(transform.f), 0.])
     name = crs.to_string() if crs is not None else ''
     m = re.fullmatch(r'EPSG:(\d+)', name or '')
     if m:

@@ -72,9 +72,11 @@ typedef struct {
  * r2-mask failure counter is always a count (HK_COUNT_RETRY is never set any more), and a device-resident job that carries `scratch`
  * always gets the in-painting's inputs left there; version 7 added entry points (hk_param_stats, hk_param_stats_dev); version 8
  * added entry points (hk_overview_count, hk_overviews, hk_overviews_dev); version 9 added hk_crs_desc / hk_warp_desc and entry
- * points (hk_warp_coords, hk_warp_coords_dev, hk_reproject_crs, hk_reproject_crs_dev, hk_reproject_dev).
+ * points (hk_warp_coords, hk_warp_coords_dev, hk_reproject_crs, hk_reproject_crs_dev, hk_reproject_dev); version 10 added
+ * hk_affine_warp_desc and entry points (hk_warp_coords_affine, hk_warp_coords_affine_dev, hk_reproject_affine,
+ * hk_reproject_affine_dev).
  * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
-#define HK_ABI_VERSION 9
+#define HK_ABI_VERSION 10
 int hk_abi_version(void);
 const char* hk_backend_name(void);            /* "hip-gfx950" */
 const char* hk_last_error(void);              /* thread-local text of the last failure */
@@ -218,6 +220,41 @@ int hk_reproject_crs_dev(hk_ctx* ctx, const hk_warp_desc* warp, const float* src
                          int32_t src_width, int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode,
                          float src_nodata, double kx, double ky, int32_t resampling, float* dst_dev, int32_t dst_height,
                          int32_t dst_width, int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream);
+/* Rotated and sheared grids: what utils.same_orientation_crs (homonim/utils.py:182-209) obtains from a bilinear WarpedVRT for
+ * every image that is not north-up, and RasterArray.reproject between such grids.  The geo-transforms are full affines in Affine
+ * order (a, b, c, d, e, f): x = a * col + b * row + c, y = d * col + e * row + f on continuous pixel coordinates whose integers
+ * are pixel edges.  Per destination position, float64, in exactly this association:
+ *   X = (c + col * a) + row * b, Y = (f + col * d) + row * e                      (destination geo-transform)
+ *   (x, y) = (X, Y) when same_crs != 0; otherwise destination CRS -> (lon, lat) -> source CRS as for hk_warp_desc
+ *   u = x - sc, v = y - sf, col_s = (u * se - v * sb) / det, row_s = (v * sa - u * sd) / det   (source geo-transform)
+ * with det = sa * se - sb * sd formed once on the host.  same_crs != 0: the two grids share their CRS, whatever it is; src_crs
+ * and dst_crs are ignored, so CRSs this library cannot define are served too.  Every pixel is transformed exactly (GDAL's
+ * default warp interpolates the transformation within 0.125 pixel).  A non-finite coefficient or a zero determinant of either
+ * geo-transform is HK_ERR_ARG.  These builds run on a two-dimensional thread tile: 32 x 8 destination pixels, a provisional
+ * choice until tools/warp_timing.py has been run (HK_WARP_TILE=WxH with W * H = 256, read once, overrides it -- a measurement
+ * aid, the results do not depend on it). */
+typedef struct hk_affine_warp_desc {
+    hk_crs_desc src_crs, dst_crs;
+    int32_t same_crs;  /* non-zero: one CRS, src_crs / dst_crs are ignored */
+    int32_t reserved;  /* 0 */
+    double src_gt[6], dst_gt[6];
+} hk_affine_warp_desc;
+/* hk_warp_coords / hk_warp_coords_dev / hk_reproject_crs / hk_reproject_crs_dev for an hk_affine_warp_desc: the same arguments, the
+ * same staging and the same errors (the footprint methods are HK_ERR_UNSUPPORTED here as well).  The coordinates are, bit for
+ * bit, the ones the re-samplers use.  kx, ky: source pixels per destination pixel, the lengths of the destination's column and
+ * row steps in source pixels. */
+int hk_warp_coords_affine(hk_ctx* ctx, const hk_affine_warp_desc* warp, double off_row, double off_col, int32_t height,
+                          int32_t width, double* x_out, double* y_out, int64_t stride);
+int hk_warp_coords_affine_dev(hk_ctx* ctx, const hk_affine_warp_desc* warp, double off_row, double off_col, int32_t height,
+                              int32_t width, double* x_dev, double* y_dev, int64_t stride, int32_t stream);
+int hk_reproject_affine(hk_ctx* ctx, const hk_affine_warp_desc* warp, const float* src, int32_t n_bands, int32_t src_height,
+                        int32_t src_width, int32_t src_nodata_mode, float src_nodata, double kx, double ky, int32_t resampling,
+                        float* dst, int32_t dst_height, int32_t dst_width, float dst_fill);
+int hk_reproject_affine_dev(hk_ctx* ctx, const hk_affine_warp_desc* warp, const float* src_dev, int32_t n_bands,
+                            int32_t src_height, int32_t src_width, int64_t src_stride, int64_t src_band_stride,
+                            int32_t src_nodata_mode, float src_nodata, double kx, double ky, int32_t resampling, float* dst_dev,
+                            int32_t dst_height, int32_t dst_width, int64_t dst_stride, int64_t dst_band_stride, float dst_fill,
+                            int32_t stream);
 /* hk_reproject on device-resident rasters (strides in elements), asynchronous on pooled stream `stream`: the same kernels, the
  * same bits. */
 int hk_reproject_dev(hk_ctx* ctx, const float* src_dev, int32_t n_bands, int32_t src_height, int32_t src_width,
