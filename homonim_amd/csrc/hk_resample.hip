@@ -7,7 +7,8 @@
 // oracle/oracle_np.py::reproject, which the tests hold it to bit for bit.
 //   mapping : src_col = kx * dst_col + ox, src_row = ky * dst_row + oy on continuous coordinates (integers = pixel edges)
 //   0 nearest      : source pixel containing the destination centre (floor(x + 1e-10))
-//   5 average      : weighted mean of the valid source pixels under the destination pixel's footprint
+//   5 average      : weighted mean of the valid source pixels under the destination pixel's footprint clipped to the
+//                    plane; a footprint wholly outside the plane, however close, holds no pixel
 //   1 bilinear / 3 cubic_spline : centre pixel must be valid; separable 2 / 4-tap (cubic B-spline) kernel, invalid or
 //                    outside taps skipped, renormalised by the accumulated weight (up-sampling: the fast path below)
 //   1 bilinear / 2 cubic / 3 cubic_spline / 4 lanczos, any scale (resample_conv_kernel): GDAL's GWKResample -- taps
@@ -55,7 +56,7 @@ __global__ void __launch_bounds__(256) resample_kernel(const ResampleArgs a) {
         int ix0 = (int)floor(x0 + 1e-10), ix1 = (int)ceil(x1 - 1e-10);
         if (iy0 == iy1 && iy1 < a.sh) ++iy1;
         if (ix0 == ix1 && ix1 < a.sw) ++ix1;
-        if (iy1 > iy0 && iy0 >= 0 && ix1 > ix0 && ix0 >= 0) {
+        if (iy1 > iy0 && iy0 >= 0 && ix1 > ix0 && ix0 >= 0 && y1 > y0 && x1 > x0) {  // shares area with the plane
             double tot = 0.0, wsum = 0.0;
             for (int yy = iy0; yy < iy1; ++yy) {
                 double wy = 1.0;
@@ -94,7 +95,7 @@ __global__ void __launch_bounds__(256) resample_kernel(const ResampleArgs a) {
         int ix0 = (int)floor(x0 + 1e-10), ix1 = (int)ceil(x1 - 1e-10);
         if (iy0 == iy1 && iy1 < a.sh) ++iy1;
         if (ix0 == ix1 && ix1 < a.sw) ++ix1;
-        if (iy1 > iy0 && iy0 >= 0 && ix1 > ix0 && ix0 >= 0) {
+        if (iy1 > iy0 && iy0 >= 0 && ix1 > ix0 && ix0 >= 0 && y1 > y0 && x1 > x0) {  // shares area with the plane
             int n = 0;
             for (int yy = iy0; yy < iy1; ++yy)
                 for (int xx = ix0; xx < ix1; ++xx) n += rs_valid(sp[(long long)yy * a.src_stride + xx], a.nd_mode, a.nodata) ? 1 : 0;

@@ -457,7 +457,8 @@ def fit(model: str, src, src_nodata, ref, ref_nodata, kernel_shape=(5, 5), find_
 #              coordinates whose integers are pixel EDGES (pixel i covers [i, i+1)).
 #   nearest  : GWKNearest -- the source pixel containing the destination pixel centre (floor(x + 1e-10)).
 #   average  : GWKAverageOrMode -- weighted mean of the valid source pixels overlapping the destination pixel's footprint,
-#              weight = fractional overlap per axis; nodata when no valid pixel.
+#              weight = fractional overlap per axis; nodata when no valid pixel, or when the footprint clipped to the
+#              raster is empty (a destination pixel wholly outside the source, however close to it).
 #   mode / med / q1 / q3 : the same function's rank-order branches over the same footprint, unweighted (see the code).
 #   bilinear / cubic_spline : GWKResample -- the source pixel under the destination centre must be valid; separable
 #              2 / 4-tap kernel (cubic B-spline) around it, taps outside the raster or invalid are skipped and the sum is
@@ -636,7 +637,7 @@ def reproject(src: np.ndarray, src_nodata, mapping, dst_shape, dst_nodata=np.nan
             iy0, iy1 = int(np.floor(y0 + 1e-10)), int(np.ceil(y1 - 1e-10))
             if iy0 == iy1 and iy1 < sh:
                 iy1 += 1
-            if iy1 <= iy0 or iy0 < 0:
+            if iy1 <= iy0 or iy0 < 0 or not y1 > y0:   # a footprint that shares no area with the raster holds no pixel
                 continue
             wy = np.ones(iy1 - iy0)
             if iy0 + 1 != iy1:
@@ -647,7 +648,7 @@ def reproject(src: np.ndarray, src_nodata, mapping, dst_shape, dst_nodata=np.nan
                 ix0, ix1 = int(np.floor(x0 + 1e-10)), int(np.ceil(x1 - 1e-10))
                 if ix0 == ix1 and ix1 < sw:
                     ix1 += 1
-                if ix1 <= ix0 or ix0 < 0:
+                if ix1 <= ix0 or ix0 < 0 or not x1 > x0:
                     continue
                 wx = np.ones(ix1 - ix0)
                 if ix0 + 1 != ix1:

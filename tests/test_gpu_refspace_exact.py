@@ -1,0 +1,320 @@
+""" hk_refspace_fit_apply's last stage in isolation: the fused up-sample + apply (upsample_apply_kernel<1|3>, hk_resample.hip) and
+the unfused branches the host falls back to (resample_kernel x 2 + apply_space_kernel), on synthetic pairs.
+
+A case starts from the parameters the call itself returns on the reference grid, so no difference of the fit can blur it: every
+corrected pixel must equal, bit for bit, ``f32(f32(p_us[0] * src) + p_us[1])`` with ``p_us`` the ORACLE's up-sampling of those
+parameters (oracle_np.reproject, itself held to the exact statement of tests/_resample_exact.py), masked with the source mask or
+with mask_partial's full-coverage mask.  No pixel is exempt and there is no allowance.  The returned parameters in turn must equal the
+device's own fit of the device's own down-sampled source.
+
+The kernel has a straight-line path (a whole wave's taps inside the plane and free of NaN: unaligned float2 / float4 loads from a
+clamped base) and a general per-tap path; the choice is restated on the host from the returned parameters, and the three large
+geometries must send at least a tenth of their valued pixels down each.  The cases walk what the kernel's geometry depends on:
+non-integer, anisotropic and offset ratios, a source that outgrows the parameter plane and one that is outgrown by it, clustered NaN in
+the parameters, heights around its 16-row blocks, widths around its 64-lane waves and 256-column blocks, parameter planes 5, 4 (the
+clamped load base) and 3 (host fallback) columns wide, numeric and absent nodata, typed input and output. """
+import functools
+import math
+
+import numpy as np
+import pytest
+
+from conftest import assert_same_f32
+from homonim_amd import _hk
+from homonim_amd.fuse import convert_dtype
+from oracle import oracle_np as onp
+
+pytestmark = pytest.mark.gpu
+
+NAN = float('nan')
+CODES = onp.RESAMPLING_CODES
+AVERAGE = CODES['average']
+FUSED = ('bilinear', 'cubic_spline')
+WAVE, BLOCK_COLS = 64, 256   # lanes of a wave, columns of a block of upsample_apply_kernel
+
+# (source shape, down mapping reference -> source pixels, reference shape)
+G_25 = ((70, 300), (2.5, 1.25, 2.5, -.5), (27, 119))      # the source outgrows the plane on three sides
+G_3 = ((37, 261), (3., 0., 3., 0.), (12, 87))             # aligned 3:1, the last source row and column beyond the plane's centres
+G_2 = ((70, 300), (2., 0., 2., 0.), (35, 150))            # aligned 2:1
+G_ANISO = ((70, 300), (2., 0., 4., 0.), (18, 150))
+G_PAST = ((70, 300), (2.5, -3.75, 2.5, -5.), (30, 122))   # the reference outgrows the source at the top and on the left
+LARGE = (G_25, G_3, G_2)
+
+
+@pytest.fixture(scope='module')
+def ctx():
+    return _hk.default_context()
+
+
+def _up(down):
+    kx, ox, ky, oy = down
+    return (1. / kx, -ox / kx, 1. / ky, -oy / ky)
+
+
+def _covering(shape, down):
+    """ the smallest reference shape whose footprint covers a source of `shape` """
+    kx, ox, ky, oy = down
+    return (max(int(math.ceil((shape[0] - oy) / ky)), 1), max(int(math.ceil((shape[1] - ox) / kx)), 1))
+
+
+@functools.lru_cache(maxsize=None)
+def _pair(src_shape, down, ref_shape, holes='base', noise_patch=False):
+    """ The base input: a source with nodata rows, columns, a block and scattered pixels; the reference = 1.3 x the down-sampled
+    source + 0.1 + noise, with a hole of its own.  NaN marks nodata; read-only, shared between the cases. """
+    h, w = src_shape
+    src, _ = onp.synth_pair(h, w, 5, 'none')
+    rng = np.random.default_rng(1234)
+    if holes == 'base':
+        src[:2] = np.nan
+        src[:, -3:] = np.nan
+        src[30:41, 100:131] = np.nan
+    elif holes == 'small':     # shapes down to one row or a dozen columns: a block and a run that leave most of them standing
+        src[h // 3:h // 3 + 3, w // 3:w // 3 + max(w // 6, 1)] = np.nan
+        src[-1, -2:] = np.nan
+    if holes != 'none':
+        src[rng.random((h, w)) < 0.002] = np.nan
+    ds = onp.reproject(src, np.nan, down, ref_shape, dst_nodata=np.nan, resampling='average' if max(down[0], down[2]) >= 1 else 'cubic_spline')
+    ref = (1.3 * ds + 0.1 + rng.normal(0., .01, ref_shape)).astype(np.float32)
+    if holes in ('base', 'none'):
+        ref[5:9, 60:70] = np.nan
+    elif holes == 'small':
+        ref[ref_shape[0] // 2, 3 * ref_shape[1] // 4:] = np.nan
+    if noise_patch:
+        ref[12:18, 20:40] = rng.normal(.5, .3, (6, 20)).astype(np.float32)
+    src.setflags(write=False)
+    ref.setflags(write=False)
+    return src, ref
+
+
+def _with_nodata(src, nodata):
+    """ the NaN-marked source with `nodata` (a number that no pixel holds) in place of NaN """
+    if nodata is None or np.isnan(nodata):
+        return src
+    assert not (src == np.float32(nodata)).any()
+    return np.where(np.isnan(src), np.float32(nodata), src)
+
+
+def _n_bands(model, thresh):
+    return 3 if (model == 'gain-offset' and thresh is not None) else 2
+
+
+def _expected(src_f32, nodata, params, down, up, method, mask_partial, kernel_shape):
+    p_us = [onp.reproject(params[b], np.nan, up, src_f32.shape, dst_nodata=np.nan, resampling=method) for b in range(2)]
+    valid = onp.mask_of(src_f32, nodata)
+    if mask_partial:
+        cover = onp.reproject(valid.astype(np.float32), None, down, params.shape[1:], dst_nodata=None, resampling='average')
+        keep = onp.full_coverage_mask(cover >= 1, params[:2], kernel_shape)
+        valid = onp.reproject(keep.astype(np.float32), None, up, src_f32.shape, dst_nodata=0, resampling='nearest').astype(bool)
+    with np.errstate(invalid='ignore'):
+        exp = np.where(valid, (p_us[0] * src_f32).astype(np.float32) + p_us[1], np.float32(np.nan)).astype(np.float32)
+    return exp, valid
+
+
+def _run(ctx, src, ref, down, method, *, up=None, model='gain-offset', kernel_shape=(5, 5), nodata=NAN, mask_partial=False,
+         thresh=None, down_method='average', out_dtype='float32', out_nodata=None, what=''):
+    """ one call of hk_refspace_fit_apply held to the expected composition; -> (params, corrected, source mask used, r2 failures) """
+    up = _up(down) if up is None else up
+    n = _n_bands(model, thresh)
+    desc = _hk.make_desc(model, kernel_shape, False, thresh, nodata, NAN)
+    params, corr, n_fail = ctx.refspace_fit_apply(desc, src, ref, down, up, CODES[down_method], CODES[method], mask_partial, n, True,
+                                                  out_dtype=out_dtype, out_nodata=out_nodata)
+    src_f32 = np.asarray(src, dtype=np.float32)
+    # the parameters: the device's fit of the device's down-sampled source (the block statistics from the same pair)
+    ds = ctx.reproject(src_f32, nodata, down, ref.shape, CODES[down_method], NAN)
+    fit_desc = _hk.make_desc(model, kernel_shape, False, thresh, NAN, NAN)
+    norm = ctx.block_norm(fit_desc, ds, ref) if model == 'gain-blk-offset' else None
+    fit_params = ctx.fit_apply(fit_desc, ds, np.asarray(ref, dtype=np.float32), n, want_params=True, want_corr=False, norm_in=norm)[0]
+    assert_same_f32(params, fit_params, f'{what}: returned parameters vs fit of the re-sampled source')
+    assert np.isfinite(params[:2]).mean() > 0.3, f'{what}: too few parameters to test anything'
+    exp, valid = _expected(src_f32, nodata, params, down, up, method, mask_partial, kernel_shape)
+    if out_dtype != 'float32' or out_nodata is not None:
+        exp_typed = convert_dtype(exp, out_dtype, out_nodata)
+        assert corr.dtype == exp_typed.dtype
+        np.testing.assert_array_equal(corr, exp_typed, err_msg=what)
+    else:
+        assert_same_f32(corr, exp, f'{what}: corrected block vs the oracle composition')
+    print(f'{what}: {int(np.isfinite(exp).sum())} of {exp.size} pixels corrected')
+    assert np.isfinite(exp).sum() > (0.05 if mask_partial else 0.3) * exp.size, f'{what}: too few corrected pixels to test anything'
+    return params, corr, valid, n_fail
+
+
+def _path_counts(params, on, up, method):
+    """ The path choice of upsample_apply_kernel restated on the host: a lane NEEDS a value when its pixel is kept and the
+    destination centre falls inside the plane; it is straight when all its taps are inside the plane and no tap of either plane is NaN
+    (or when it needs nothing); a wave -- 64 consecutive columns of a 256-column block, one destination row -- takes the straight-line
+    path when all its lanes are straight.  -> (needed pixels served by the straight-line path, by the general path, the plane of needed pixels) """
+    kx, ox, ky, oy = up
+    ph, pw = params.shape[1:]
+    h, w = on.shape
+    nt, t0 = (2, 0) if method == 'bilinear' else (4, -1)
+    bad = np.isnan(params[0]) | np.isnan(params[1])
+
+    def axis(k, o, n_dst, n_src):
+        s = k * (np.arange(n_dst) + 0.5) + o
+        c = np.floor(s + 1e-10).astype(np.int64)
+        first = np.floor(s - 0.5).astype(np.int64) + t0
+        return (c >= 0) & (c < n_src), first, (first >= 0) & (first + nt <= n_src)
+
+    cy_ok, y0, y_in = axis(ky, oy, h, ph)
+    cx_ok, x0, x_in = axis(kx, ox, w, pw)
+    need = on & cy_ok[:, None] & cx_ok[None, :]
+    # any NaN among the nt x nt taps, where they are all inside (integral image of the NaN flags)
+    integ = np.zeros((ph + 1, pw + 1), np.int64)
+    integ[1:, 1:] = bad.cumsum(0).cumsum(1)
+    ya, xa = np.clip(y0, 0, max(ph - nt, 0)), np.clip(x0, 0, max(pw - nt, 0))
+    yb, xb = np.minimum(ya + nt, ph), np.minimum(xa + nt, pw)
+    n_bad = (integ[yb[:, None], xb[None, :]] - integ[ya[:, None], xb[None, :]] - integ[yb[:, None], xa[None, :]]
+             + integ[ya[:, None], xa[None, :]])
+    lane_straight = ~need | (y_in[:, None] & x_in[None, :] & (n_bad == 0))
+    straight = general = 0
+    for c0 in range(0, w, WAVE):       # 256 is a multiple of 64: waves never straddle a block
+        wave = lane_straight[:, c0:c0 + WAVE].all(axis=1)
+        n_need = need[:, c0:c0 + WAVE].sum(axis=1)
+        straight += int(n_need[wave].sum())
+        general += int(n_need[~wave].sum())
+    assert straight + general == int(need.sum())
+    return straight, general, need
+
+
+# -- the fused kernel ------------------------------------------------------------------------------------------------
+@pytest.mark.oracle
+@pytest.mark.parametrize('method', FUSED)
+@pytest.mark.parametrize('geometry', [G_25, G_3, G_2, G_ANISO, G_PAST], ids=['2.5to1', '3to1', '2to1', '2x4', 'ref-past-src'])
+def test_fused_upsample_apply_geometries_and_both_paths(ctx, geometry, method):
+    src_shape, down, ref_shape = geometry
+    src, ref = _pair(src_shape, down, ref_shape)
+    params, corr, valid, _ = _run(ctx, src, ref, down, method, what=f'{geometry} {method}')
+    straight, general, need = _path_counts(params, valid, _up(down), method)
+    print(f'{geometry} {method}: {straight} pixels through the straight-line path, {general} through the general path')
+    if geometry is G_25:   # the source extends past the plane: three rows and a column of valid pixels have no centre in it
+        assert int((valid & ~need).sum()) > 900 and np.isnan(corr[valid & ~need]).all()
+    if geometry in LARGE:
+        assert straight >= 0.1 * (straight + general) and general >= 0.1 * (straight + general), (straight, general)
+
+
+@pytest.mark.oracle
+@pytest.mark.parametrize('method', FUSED)
+@pytest.mark.parametrize('shape', [(1, 130), (15, 130), (16, 130), (17, 130), (33, 130), (20, 63), (20, 64), (20, 65), (20, 255),
+                                   (20, 256), (20, 257)], ids=lambda s: f'{s[0]}x{s[1]}')
+def test_fused_upsample_apply_around_the_row_blocks_and_the_waves(ctx, shape, method):
+    """ heights around the 16 destination rows a block walks; widths around a wave and a block """
+    down = (2.5, 1.25, 2.5, -.5) if shape[1] == 130 else (2., -.5, 3., 0.)
+    ref_shape = _covering(shape, down)
+    src, ref = _pair(shape, down, ref_shape, 'small')
+    _run(ctx, src, ref, down, method, kernel_shape=(3, 3), what=f'{shape} {method}')
+
+
+@pytest.mark.oracle
+@pytest.mark.parametrize('method', FUSED)
+@pytest.mark.parametrize('src_width, ref_width', [(12, 5), (10, 4), (7, 3)])
+def test_narrow_parameter_planes(ctx, src_width, ref_width, method):
+    """ 5 and 4 columns: every load base of cubic_spline is clamped (4: all of them to column 0); 3 columns: the host takes the unfused
+    branch, which must give the same composition """
+    down = (2.5, 0., 2.5, 0.)
+    shape = (40, src_width)
+    ref_shape = _covering(shape, down)
+    assert ref_shape[1] == ref_width
+    src, ref = _pair(shape, down, ref_shape, 'small')
+    _run(ctx, src, ref, down, method, model='gain', kernel_shape=(3, 3), what=f'ref width {ref_width} {method}')
+
+
+@pytest.mark.oracle
+@pytest.mark.parametrize('method', FUSED)
+@pytest.mark.parametrize('nodata', [0., -9999., None], ids=['0', '-9999', 'none'])
+def test_fused_upsample_apply_numeric_and_absent_nodata(ctx, nodata, method):
+    """ (NaN nodata is every other case.)  Without a nodata value the source is free of NaN and every pixel is kept; the parameters
+    still carry the NaN of the reference's hole. """
+    src_shape, down, ref_shape = G_25
+    src, ref = _pair(src_shape, down, ref_shape, 'none' if nodata is None else 'base')
+    params, _, _, _ = _run(ctx, _with_nodata(src, nodata), ref, down, method, nodata=nodata, what=f'nodata {nodata} {method}')
+    assert np.isnan(params[0]).any()
+
+
+@pytest.mark.oracle
+@pytest.mark.parametrize('method', FUSED)
+@pytest.mark.parametrize('geometry, kernel_shape', [(G_25, (3, 3)), (G_25, (5, 5)), (G_3, (3, 3)), (G_3, (5, 5))],
+                         ids=['2.5to1-k3', '2.5to1-k5', '3to1-k3', '3to1-k5'])
+def test_fused_upsample_apply_mask_partial(ctx, geometry, kernel_shape, method):
+    src_shape, down, ref_shape = geometry
+    src, ref = _pair(src_shape, down, ref_shape)
+    _, corr, keep, _ = _run(ctx, src, ref, down, method, kernel_shape=kernel_shape, mask_partial=True,
+                            what=f'mask_partial {geometry} {kernel_shape} {method}')
+    assert 0 < keep.sum() < (~np.isnan(src)).sum()
+
+
+@pytest.mark.oracle
+@pytest.mark.parametrize('method', FUSED)
+@pytest.mark.parametrize('model, thresh', [('gain', None), ('gain-offset', None), ('gain-blk-offset', None), ('gain-offset', 0.25)],
+                         ids=['gain', 'gain-offset', 'gain-blk-offset', 'gain-offset-inpaint'])
+def test_fused_upsample_apply_models(ctx, model, thresh, method):
+    src_shape, down, ref_shape = G_2
+    src, ref = _pair(src_shape, down, ref_shape, noise_patch=thresh is not None)
+    _, _, _, n_fail = _run(ctx, src, ref, down, method, model=model, thresh=thresh, what=f'{model} {thresh} {method}')
+    if thresh is not None:
+        assert n_fail > 0, 'the noise patch of the reference must send some parameters through in-painting'
+
+
+# -- the unfused branches ----------------------------------------------------------------------------------------------
+@pytest.mark.oracle
+@pytest.mark.parametrize('method, mask_partial', [('nearest', False), ('nearest', True), ('cubic', False), ('average', False),
+                                                  ('average', True)])
+def test_unfused_upsampling_methods(ctx, method, mask_partial):
+    """ every up-sampling method but bilinear and cubic_spline: resample_kernel / resample_conv_kernel x 2 + apply_space_kernel """
+    src_shape, down, ref_shape = G_25
+    src, ref = _pair(src_shape, down, ref_shape)
+    _run(ctx, src, ref, down, method, mask_partial=mask_partial, what=f'unfused {method} mask_partial={mask_partial}')
+
+
+@pytest.mark.oracle
+@pytest.mark.parametrize('method, mask_partial', [('average', False), ('bilinear', False), ('bilinear', True)])
+def test_reference_finer_than_the_source_takes_the_unfused_branch(ctx, method, mask_partial):
+    """ up-ratio 2: the parameters are DOWN-sampled to the source grid, which the fused kernel does not do whatever the method """
+    src_shape, down, ref_shape = (35, 150), (.5, 0., .5, 0.), (70, 300)
+    src, ref = _pair(src_shape, down, ref_shape, 'small')
+    _run(ctx, src, ref, down, method, down_method='cubic_spline', mask_partial=mask_partial, kernel_shape=(3, 3),
+         what=f'finer reference {method} mask_partial={mask_partial}')
+
+
+# -- typed input and output ----------------------------------------------------------------------------------------------
+@pytest.mark.oracle
+@pytest.mark.parametrize('method', FUSED)
+@pytest.mark.parametrize('src_dtype, nodata, out_dtype', [('uint8', 0, 'uint8'), ('int16', -9999, 'uint16'), ('uint8', 255, 'float32')])
+def test_fused_upsample_apply_typed_io(ctx, src_dtype, nodata, out_dtype, method):
+    src_shape, down, ref_shape = G_25
+    src, ref = _pair(src_shape, down, ref_shape)
+    dn = np.where(np.isnan(src), nodata, np.round(src * 200.)).astype(src_dtype)    # 10 .. 200: no pixel holds a nodata value
+    dn_ref = np.where(np.isnan(ref), np.float32(np.nan), ref * np.float32(200.)).astype(np.float32)
+    _run(ctx, dn, dn_ref, down, method, nodata=float(nodata), out_dtype=out_dtype, out_nodata=None if out_dtype == 'float32' else 0,
+         what=f'{src_dtype} -> {out_dtype} {method}')
+
+
+# -- fused against unfused, many alignments --------------------------------------------------------------------------------
+def test_fused_equals_unfused_over_random_geometries(ctx):
+    """ Device against device (hk_reproject is pinned to the oracle and to the exact statement elsewhere), so it is cheap: 30 random
+    non-dyadic, anisotropic ratios in [1.2, 6] with sub-pixel offsets, shapes up to 200 x 700, NaN blocks in source and reference.
+    The wave-uniform decisions of the fused kernel fall differently in each. """
+    for seed in range(30):
+        rng = np.random.default_rng(1000 + seed)
+        h, w = int(rng.integers(8, 201)), int(rng.integers(24, 701))
+        kx, ky = rng.uniform(1.2, 6., 2)
+        down = (float(kx), float(rng.uniform(-kx, kx)), float(ky), float(rng.uniform(-ky, ky)))
+        ref_shape = _covering((h, w), down)
+        ref_shape = (max(ref_shape[0] - int(rng.integers(0, 2)), 1), max(ref_shape[1] - int(rng.integers(0, 2)), 1))
+        method = FUSED[seed % 2]
+        src = rng.uniform(.05, 1., (h, w)).astype(np.float32)
+        for _ in range(3):
+            y, x = int(rng.integers(0, h)), int(rng.integers(0, w))
+            src[y:y + int(rng.integers(1, 12)), x:x + int(rng.integers(1, 40))] = np.nan
+        ref = rng.uniform(.05, 1.3, ref_shape).astype(np.float32)
+        for _ in range(2):
+            y, x = int(rng.integers(0, ref_shape[0])), int(rng.integers(0, ref_shape[1]))
+            ref[y:y + int(rng.integers(1, 4)), x:x + int(rng.integers(1, 9))] = np.nan
+        up = _up(down)
+        desc = _hk.make_desc('gain-offset', (3, 3), False, None, NAN, NAN)
+        params, corr, _ = ctx.refspace_fit_apply(desc, src, ref, down, up, AVERAGE, CODES[method], False, 2, True)
+        p_us = ctx.reproject(params, NAN, up, src.shape, CODES[method], NAN)
+        with np.errstate(invalid='ignore'):
+            exp = np.where(np.isnan(src), np.float32(np.nan), (p_us[0] * src).astype(np.float32) + p_us[1]).astype(np.float32)
+        what = f'seed {seed}: {h} x {w}, down {down}, reference {ref_shape}, {method}'
+        assert_same_f32(corr, exp, what)
+        assert np.isfinite(exp).sum() > 0.2 * exp.size, what
