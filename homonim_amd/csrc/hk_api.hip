@@ -1542,10 +1542,16 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     if ((rc = stage_in(sl, src, src_stride, sdt, d_src, base + o_raw_s, ss, src_height, src_width))) return rc;
     if ((rc = stage_in(sl, ref, ref_stride, rdt, d_ref, base + o_raw_r, rs, ref_height, ref_width))) return rc;
 
+    // one plane from the source grid down to the reference grid, or from there up to the source grid
+    auto resample = [&](int mode, bool down, const float* from, int nd_mode, float nodata, float* to, float fill) {
+        hk::ResamplePlanes p = {from, to, ss, 0, rs, 0, src_height, src_width, ref_height, ref_width, 1, nd_mode, nodata, fill};
+        if (!down) std::swap(p.src_stride, p.dst_stride), std::swap(p.sh, p.dh), std::swap(p.sw, p.dw);
+        const double* m = down ? space->down : space->up;
+        return hk::launch_resample(mode, p, m[0], m[1], m[2], m[3], sl.stream);
+    };
+
     // RefSpaceModel.fit (:476-482): source -> reference grid (nodata nan), then the base-class fit there
-    HK_HIP(hk::launch_resample(space->down_resampling, d_src, ss, 0, src_height, src_width, 1, desc->src_nodata_mode,
-                               desc->src_nodata, space->down[0], space->down[1], space->down[2], space->down[3], d_ds, rs, 0,
-                               ref_height, ref_width, nan, sl.stream));
+    HK_HIP(resample(space->down_resampling, true, d_src, desc->src_nodata_mode, desc->src_nodata, d_ds, nan));
     hk_fit_desc fd = *desc;
     fd.src_nodata_mode = HK_NODATA_NAN, fd.src_nodata = nan;
     rc = fit_on_device(ctx, sl, &fd, nullptr, d_ds, d_ref, ref_height, ref_width, rs, d_gain, d_off, d_r2, nullptr, d_norm,
@@ -1555,27 +1561,21 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     // RefSpaceModel.apply (:484-503): gain / offset -> source grid, re-mask, apply
     if (!fused_up)
         for (int b = 0; b < 2; ++b)
-            HK_HIP(hk::launch_resample(space->up_resampling, b ? d_off : d_gain, rs, 0, ref_height, ref_width, 1,
-                                       HK_NODATA_NAN, nan, space->up[0], space->up[1], space->up[2], space->up[3],
-                                       b ? d_ous : d_gus, ss, 0, src_height, src_width, nan, sl.stream));
+            HK_HIP(resample(space->up_resampling, false, b ? d_off : d_gain, HK_NODATA_NAN, nan, b ? d_ous : d_gus, nan));
     const float* d_keep = nullptr;
     if (space->mask_partial) {
         // _full_coverage_mask (:375-409): source mask --average--> reference grid (>= 1) & parameter mask, eroded by
         // (kh+2) x (kw+2); back to the source grid with `nearest` (nodata 0)
         HK_HIP(hk::launch_valid_plane(d_src, ss, desc->src_nodata_mode, desc->src_nodata, F(o_vs), ss, src_height,
                                       src_width, sl.stream));
-        HK_HIP(hk::launch_resample(5, F(o_vs), ss, 0, src_height, src_width, 1, HK_NODATA_NONE, 0.f, space->down[0],
-                                   space->down[1], space->down[2], space->down[3], F(o_cov), rs, 0, ref_height, ref_width,
-                                   0.f, sl.stream));
+        HK_HIP(resample(5, true, F(o_vs), HK_NODATA_NONE, 0.f, F(o_cov), 0.f));
         unsigned char* d_mk = reinterpret_cast<unsigned char*>(base + o_mk);
         // the parameters as two bands: gain, and offset one band stride further on
         HK_HIP(hk::launch_partial_mask(F(o_cov), 3, 0.f, d_gain, 2, (long long)(o_off - o_gain) / 4, nullptr,
                                        ref_height, ref_width, rs, desc->kh, desc->kw,
                                        reinterpret_cast<unsigned short*>(base + o_cnt), nullptr, nullptr, d_mk, sl.stream));
         HK_HIP(hk::launch_cast_in(1, d_mk, rs, F(o_mkf), rs, ref_height, ref_width, sl.stream));
-        HK_HIP(hk::launch_resample(0, F(o_mkf), rs, 0, ref_height, ref_width, 1, HK_NODATA_NONE, 0.f, space->up[0],
-                                   space->up[1], space->up[2], space->up[3], F(o_keep), ss, 0, src_height, src_width, 0.f,
-                                   sl.stream));
+        HK_HIP(resample(0, false, F(o_mkf), HK_NODATA_NONE, 0.f, F(o_keep), 0.f));
         d_keep = F(o_keep);
     }
     if (fused_up) {
@@ -1630,9 +1630,9 @@ int hk_reproject(hk_ctx* ctx, const float* src, int32_t n_bands, int32_t src_hei
     float* d_src = static_cast<float*>(sl.dev);
     float* d_dst = reinterpret_cast<float*>(static_cast<char*>(sl.dev) + o_dst);
     if ((rc = stage_h2d(sl, d_src, sbytes, src, sbytes, sbytes, 1))) return rc;
-    HK_HIP(hk::launch_resample(resampling, d_src, src_width, (long long)src_height * src_width, src_height, src_width,
-                               n_bands, src_nodata_mode, src_nodata, kx, ox, ky, oy, d_dst, dst_width,
-                               (long long)dst_height * dst_width, dst_height, dst_width, dst_fill, sl.stream));
+    const hk::ResamplePlanes p = {d_src, d_dst, src_width, (long long)src_height * src_width, dst_width, (long long)dst_height * dst_width,
+                                  src_height, src_width, dst_height, dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill};
+    HK_HIP(hk::launch_resample(resampling, p, kx, ox, ky, oy, sl.stream));
     if ((rc = stage_d2h(sl, dst, dbytes, d_dst, dbytes, dbytes, 1))) return rc;
     return stage_finish(sl);
 }
@@ -1658,9 +1658,9 @@ int hk_reproject_dev(hk_ctx* ctx, const float* src_dev, int32_t n_bands, int32_t
     if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
-    HK_HIP(hk::launch_resample(resampling, src_dev, src_stride, src_band_stride, src_height, src_width, n_bands, src_nodata_mode,
-                               src_nodata, kx, ox, ky, oy, dst_dev, dst_stride, dst_band_stride, dst_height, dst_width, dst_fill,
-                               ctx->slots[stream].stream));
+    const hk::ResamplePlanes p = {src_dev, dst_dev, src_stride, src_band_stride, dst_stride, dst_band_stride,
+                                  src_height, src_width, dst_height, dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill};
+    HK_HIP(hk::launch_resample(resampling, p, kx, ox, ky, oy, ctx->slots[stream].stream));
     return HK_OK;
 }
 
@@ -1695,8 +1695,8 @@ static int warp_coords_dev(hk_ctx* ctx, const Desc* warp, double off_row, double
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
     const char* why = nullptr;
-    return warp_launch_status(hk::launch_warp_coords(warp, off_row, off_col, x_dev, y_dev, stride, height, width,
-                                                     ctx->slots[stream].stream, &why), why);
+    const hk::WarpLattice l = {x_dev, y_dev, stride, height, width, off_row, off_col};
+    return warp_launch_status(hk::launch_warp_coords(warp, l, ctx->slots[stream].stream, &why), why);
 }
 
 extern "C++" template <typename Desc>
@@ -1714,10 +1714,9 @@ static int warp_coords_host(hk_ctx* ctx, const Desc* warp, double off_row, doubl
     if ((rc = ensure_dev(sl, L.total))) return rc;
     char* base = static_cast<char*>(sl.dev);
     const char* why = nullptr;
-    if ((rc = warp_launch_status(hk::launch_warp_coords(warp, off_row, off_col, reinterpret_cast<double*>(base + o_x),
-                                                        reinterpret_cast<double*>(base + o_y), d_stride, height, width, sl.stream,
-                                                        &why), why)))
-        return rc;
+    const hk::WarpLattice l = {reinterpret_cast<double*>(base + o_x), reinterpret_cast<double*>(base + o_y), d_stride, height, width,
+                               off_row, off_col};
+    if ((rc = warp_launch_status(hk::launch_warp_coords(warp, l, sl.stream, &why), why))) return rc;
     if ((rc = stage_d2h(sl, x_out, (size_t)stride * 8, base + o_x, (size_t)d_stride * 8, (size_t)width * 8, height))) return rc;
     if ((rc = stage_d2h(sl, y_out, (size_t)stride * 8, base + o_y, (size_t)d_stride * 8, (size_t)width * 8, height))) return rc;
     return stage_finish(sl);
@@ -1777,10 +1776,9 @@ static int reproject_warp_dev(hk_ctx* ctx, const Desc* warp, const float* src_de
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
     const char* why = nullptr;
-    return warp_launch_status(hk::launch_warp_resample(resampling, warp, src_dev, src_stride, src_band_stride, src_height,
-                                                       src_width, n_bands, src_nodata_mode, src_nodata, kx, ky, dst_dev,
-                                                       dst_stride, dst_band_stride, dst_height, dst_width, dst_fill,
-                                                       ctx->slots[stream].stream, &why), why);
+    const hk::ResamplePlanes p = {src_dev, dst_dev, src_stride, src_band_stride, dst_stride, dst_band_stride,
+                                  src_height, src_width, dst_height, dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill};
+    return warp_launch_status(hk::launch_warp_resample(resampling, warp, p, kx, ky, ctx->slots[stream].stream, &why), why);
 }
 
 extern "C++" template <typename Desc>
@@ -1800,11 +1798,9 @@ static int reproject_warp_host(hk_ctx* ctx, const Desc* warp, const float* src, 
     float* d_dst = reinterpret_cast<float*>(static_cast<char*>(sl.dev) + o_dst);
     if ((rc = stage_h2d(sl, d_src, sbytes, src, sbytes, sbytes, 1))) return rc;
     const char* why = nullptr;
-    if ((rc = warp_launch_status(hk::launch_warp_resample(resampling, warp, d_src, src_width, (long long)src_height * src_width,
-                                                          src_height, src_width, n_bands, src_nodata_mode, src_nodata, kx, ky,
-                                                          d_dst, dst_width, (long long)dst_height * dst_width, dst_height,
-                                                          dst_width, dst_fill, sl.stream, &why), why)))
-        return rc;
+    const hk::ResamplePlanes p = {d_src, d_dst, src_width, (long long)src_height * src_width, dst_width, (long long)dst_height * dst_width,
+                                  src_height, src_width, dst_height, dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill};
+    if ((rc = warp_launch_status(hk::launch_warp_resample(resampling, warp, p, kx, ky, sl.stream, &why), why))) return rc;
     if ((rc = stage_d2h(sl, dst, dbytes, d_dst, dbytes, dbytes, 1))) return rc;
     return stage_finish(sl);
 }

@@ -297,27 +297,42 @@ hipError_t launch_inpaint_offsets(float* offset, const float* gain, const float*
                                   int height, int width, void* workspace, hipStream_t stream,
                                   const unsigned char* flag_ready = nullptr, unsigned long long n_targets = 0);
 
-// Re-sampling between axis-aligned grids (hk_resample.hip).  mode = rasterio.enums.Resampling value (0, 1, 3, 5).
-hipError_t launch_resample(int mode, const float* src, long long src_stride, long long src_band_stride, int sh, int sw,
-                           int n_bands, int nd_mode, float nodata, double kx, double ox, double ky, double oy, float* dst,
-                           long long dst_stride, long long dst_band_stride, int dh, int dw, float dst_fill,
-                           hipStream_t stream);
+// What every re-sampling launch carries, whatever maps a destination pixel to the source (hk_resample.hip, hk_warp.hip): hk_api.hip
+// fills one per entry point, the kernels' argument structs embed it.  Strides in elements.
+struct ResamplePlanes {
+    const float* src;
+    float* dst;
+    long long src_stride, src_band_stride, dst_stride, dst_band_stride;
+    int sh, sw, dh, dw, n_bands;
+    int nd_mode;
+    float nodata;
+    float dst_fill;  // value of destination pixels that receive nothing
+};
+// kx, ky = source pixels per destination pixel.  An axis is down-sampled: bilinear / cubic_spline leave their 2 / 4-tap kernels for
+// GWKResample, whose support scales with the step (cubic and lanczos always run it)
+inline bool resample_stretched(double kx, double ky) { return kx > 1.0 + 1e-9 || ky > 1.0 + 1e-9; }
 
-// Re-sampling between grids of two CRSs (hk_warp.hip): the continuous source pixel coordinates of destination positions, and
-// launch_resample's modes 0..4 on them.  `why` receives the reason when hipErrorInvalidValue is returned.
-hipError_t launch_warp_coords(const hk_warp_desc* desc, double off_row, double off_col, double* x, double* y, long long stride,
-                              int h, int w, hipStream_t stream, const char** why);
-hipError_t launch_warp_resample(int mode, const hk_warp_desc* desc, const float* src, long long src_stride,
-                                long long src_band_stride, int sh, int sw, int n_bands, int nd_mode, float nodata, double kx,
-                                double ky, float* dst, long long dst_stride, long long dst_band_stride, int dh, int dw,
-                                float dst_fill, hipStream_t stream, const char** why);
+// Re-sampling between same-CRS axis-aligned grids (hk_resample.hip): src_col = kx * dst_col + ox, src_row = ky * dst_row + oy.
+// mode = rasterio.enums.Resampling value (0..6, 8..14).
+hipError_t launch_resample(int mode, const ResamplePlanes& p, double kx, double ox, double ky, double oy, hipStream_t stream);
+
+// Re-sampling between grids of two CRSs (hk_warp.hip): the continuous source pixel coordinates of the destination positions
+// (row + off_row, col + off_col) of an h x w lattice, and launch_resample's modes 0..4 on them (kx, ky: the mean step, which picks
+// and scales the stretched kernels).  `why` receives the reason when hipErrorInvalidValue is returned.
+struct WarpLattice {
+    double* x;
+    double* y;
+    long long stride;
+    int h, w;
+    double off_row, off_col;
+};
+hipError_t launch_warp_coords(const hk_warp_desc* desc, const WarpLattice& l, hipStream_t stream, const char** why);
+hipError_t launch_warp_resample(int mode, const hk_warp_desc* desc, const ResamplePlanes& p, double kx, double ky,
+                                hipStream_t stream, const char** why);
 // The same for rotated / sheared grids, in one CRS or across two (hk_affine_warp_desc): full affines at both ends.
-hipError_t launch_warp_coords(const hk_affine_warp_desc* desc, double off_row, double off_col, double* x, double* y,
-                              long long stride, int h, int w, hipStream_t stream, const char** why);
-hipError_t launch_warp_resample(int mode, const hk_affine_warp_desc* desc, const float* src, long long src_stride,
-                                long long src_band_stride, int sh, int sw, int n_bands, int nd_mode, float nodata, double kx,
-                                double ky, float* dst, long long dst_stride, long long dst_band_stride, int dh, int dw,
-                                float dst_fill, hipStream_t stream, const char** why);
+hipError_t launch_warp_coords(const hk_affine_warp_desc* desc, const WarpLattice& l, hipStream_t stream, const char** why);
+hipError_t launch_warp_resample(int mode, const hk_affine_warp_desc* desc, const ResamplePlanes& p, double kx, double ky,
+                                hipStream_t stream, const char** why);
 
 size_t upsample_apply_workspace_bytes(int height);
 hipError_t launch_upsample_apply(int mode, const float* src, long long src_stride, int nd_mode, float nodata,

@@ -1,207 +1,147 @@
 // hk_resample.hip -- re-sampling between same-CRS, north-up, axis-aligned grids: RasterArray.reproject
 // (homonim/raster_array.py:526-578 -> rasterio.warp.reproject -> GDAL warp) as RefSpaceModel / SrcSpaceModel use it
-// (homonim/kernel_model.py:397,480,491,497,520).
+// (homonim/kernel_model.py:397,480,491,497,520), and RefSpaceModel.apply fused with its up-sampling.
 //
-// GDAL is not part of /root/reference and not installed here: its published warp kernels (gdal/alg/gdalwarpkernel.cpp)
-// are RESTATED, parity with GDAL itself unpinned; the arithmetic below is, operation for operation, the one of
-// oracle/oracle_np.py::reproject, which the tests hold it to bit for bit.
+// GDAL is not part of the reference project and not installed here: its published warp kernels are RESTATED, parity with GDAL
+// itself unpinned.  What is done with a source coordinate is stated once, in hk_resample_taps.h; this file supplies the coordinate
 //   mapping : src_col = kx * dst_col + ox, src_row = ky * dst_row + oy on continuous coordinates (integers = pixel edges)
-//   0 nearest      : source pixel containing the destination centre (floor(x + 1e-10))
-//   5 average      : weighted mean of the valid source pixels under the destination pixel's footprint clipped to the
-//                    plane; a footprint wholly outside the plane, however close, holds no pixel
-//   1 bilinear / 3 cubic_spline : centre pixel must be valid; separable 2 / 4-tap (cubic B-spline) kernel, invalid or
-//                    outside taps skipped, renormalised by the accumulated weight (up-sampling: the fast path below)
-//   1 bilinear / 2 cubic / 3 cubic_spline / 4 lanczos, any scale (resample_conv_kernel): GDAL's GWKResample -- taps
-//                    i in [1 - R', R'] per axis with R' = ceil(R / scale) when the axis is down-sampled (scale =
-//                    min(1, 1 / k) < 1), else R (1, 2, 2, 3); weight f((i - delta) * scale); always renormalised
-//   8 max / 9 min / 13 sum / 14 rms : over the source pixels of the destination pixel's footprint (the window of
-//                    `average`); sum and rms weight the edge pixels by their overlap like average
-// One thread per destination pixel (gather); float64 accumulation, float32 result.
+// and the methods that need a scaled mapping's rectangular footprint (the destination pixel's edges mapped and clipped to the plane):
+//   5 average      : weighted mean of the valid source pixels under the footprint, edge pixels by their overlap
+//   8 max / 9 min / 13 sum / 14 rms : over the same pixels; sum and rms weight the edge pixels like average
+//   6 mode / 10 med / 11 q1 / 12 q3 : rank order of the same pixels, no weights
+// One thread per destination pixel (gather), one row per workgroup, one band per blockIdx.z; float64 accumulation, float32 result.
 #include "hk_kernels.h"
 #include "hk_resample_taps.h"
 
 namespace hk {
 
 struct ResampleArgs {
-    const float* src;
-    float* dst;
-    long long src_stride, src_band_stride, dst_stride, dst_band_stride;
-    int sh, sw, dh, dw;
-    int nd_mode;
-    float nodata;
-    float dst_fill;  // value of destination pixels that receive nothing
+    ResamplePlanes p;
     double kx, ox, ky, oy;
 };
 
+// the mapping on one axis: destination position (pixel index = its leading edge, + 0.5 = its centre) -> source coordinate
+__device__ __forceinline__ double scaled_coord(double k, double o, double pos) { return k * pos + o; }
+
+// 0 nearest, 1 bilinear / 3 cubic_spline when no axis is down-sampled, and the footprint methods
 template <int MODE>
 __global__ void __launch_bounds__(256) resample_kernel(const ResampleArgs a) {
+    const ResamplePlanes& p = a.p;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = blockIdx.y;
-    if (j >= a.dw) return;
-    const float* __restrict__ sp = a.src + (long long)blockIdx.z * a.src_band_stride;
-    float* __restrict__ dp = a.dst + (long long)blockIdx.z * a.dst_band_stride;
+    if (j >= p.dw) return;
+    const float* __restrict__ sp = p.src + (long long)blockIdx.z * p.src_band_stride;
+    float* __restrict__ dp = p.dst + (long long)blockIdx.z * p.dst_band_stride;
     double result = 0.0;
     bool got = false;
-    if constexpr (MODE == 0) {
-        const long long cx = (long long)floor(a.kx * ((double)j + 0.5) + a.ox + 1e-10);
-        const long long cy = (long long)floor(a.ky * ((double)i + 0.5) + a.oy + 1e-10);
-        if (cx >= 0 && cx < a.sw && cy >= 0 && cy < a.sh) {
-            const float v = sp[cy * a.src_stride + cx];
-            if (rs_valid(v, a.nd_mode, a.nodata)) result = (double)v, got = true;
-        }
-    } else if constexpr (MODE == 5 || MODE == 8 || MODE == 9 || MODE == 13 || MODE == 14) {
-        const double y0 = fmax(a.ky * (double)i + a.oy, 0.0), y1 = fmin(a.ky * (double)(i + 1) + a.oy, (double)a.sh);
-        const double x0 = fmax(a.kx * (double)j + a.ox, 0.0), x1 = fmin(a.kx * (double)(j + 1) + a.ox, (double)a.sw);
-        int iy0 = (int)floor(y0 + 1e-10), iy1 = (int)ceil(y1 - 1e-10);
-        int ix0 = (int)floor(x0 + 1e-10), ix1 = (int)ceil(x1 - 1e-10);
-        if (iy0 == iy1 && iy1 < a.sh) ++iy1;
-        if (ix0 == ix1 && ix1 < a.sw) ++ix1;
-        if (iy1 > iy0 && iy0 >= 0 && ix1 > ix0 && ix0 >= 0 && y1 > y0 && x1 > x0) {  // shares area with the plane
-            double tot = 0.0, wsum = 0.0;
-            for (int yy = iy0; yy < iy1; ++yy) {
-                double wy = 1.0;
-                if (iy0 + 1 != iy1) wy = yy == iy0 ? 1.0 - (y0 - (double)iy0) : (yy == iy1 - 1 ? 1.0 - ((double)iy1 - y1) : 1.0);
-                for (int xx = ix0; xx < ix1; ++xx) {
-                    const float v = sp[(long long)yy * a.src_stride + xx];
-                    if (!rs_valid(v, a.nd_mode, a.nodata)) continue;
-                    double wx = 1.0;
-                    if (ix0 + 1 != ix1) wx = xx == ix0 ? 1.0 - (x0 - (double)ix0) : (xx == ix1 - 1 ? 1.0 - ((double)ix1 - x1) : 1.0);
-                    const double wgt = wx * wy;
-                    if constexpr (MODE == 8) {
-                        tot = wsum > 0.0 ? fmax(tot, (double)v) : (double)v;
-                    } else if constexpr (MODE == 9) {
-                        tot = wsum > 0.0 ? fmin(tot, (double)v) : (double)v;
-                    } else if constexpr (MODE == 14) {
-                        tot += (double)v * (double)v * wgt;
-                    } else {
-                        tot += (double)v * wgt;
+    if constexpr (MODE >= 5) {
+        FootAxis fy, fx;
+        // the destination pixel's leading and trailing edges on each axis
+        const bool rows = rs_footprint_axis(scaled_coord(a.ky, a.oy, (double)i), scaled_coord(a.ky, a.oy, (double)(i + 1)), p.sh, fy);
+        const bool cols = rs_footprint_axis(scaled_coord(a.kx, a.ox, (double)j), scaled_coord(a.kx, a.ox, (double)(j + 1)), p.sw, fx);
+        if (rows && cols) {  // shares area with the plane
+            if constexpr (MODE == 5 || MODE == 8 || MODE == 9 || MODE == 13 || MODE == 14) {
+                double tot = 0.0, wsum = 0.0;
+                for (int yy = fy.i0; yy < fy.i1; ++yy) {
+                    const double wy = rs_edge_weight(fy, yy);
+                    for (int xx = fx.i0; xx < fx.i1; ++xx) {
+                        const float v = sp[(long long)yy * p.src_stride + xx];
+                        if (!rs_valid(v, p.nd_mode, p.nodata)) continue;
+                        const double wgt = rs_edge_weight(fx, xx) * wy;
+                        if constexpr (MODE == 8) {
+                            tot = wsum > 0.0 ? fmax(tot, (double)v) : (double)v;
+                        } else if constexpr (MODE == 9) {
+                            tot = wsum > 0.0 ? fmin(tot, (double)v) : (double)v;
+                        } else if constexpr (MODE == 14) {
+                            tot += (double)v * (double)v * wgt;
+                        } else {
+                            tot += (double)v * wgt;
+                        }
+                        wsum += wgt;
                     }
-                    wsum += wgt;
                 }
-            }
-            if (wsum > 0.0) {
-                result = (MODE == 5) ? tot / wsum : ((MODE == 14) ? sqrt(tot / wsum) : tot);
-                got = true;
-            }
-        }
-    } else if constexpr (MODE == 6 || MODE == 10 || MODE == 11 || MODE == 12) {
-        // GWKAverageOrMode's rank-order branches over the same footprint as `average` (no weights): med / q1 / q3 = element
-        // ceil(q * n - 1) of the sorted valid values; mode = the value whose running count first reaches the highest
-        // count, in row-major scan order.  No per-thread storage: the footprint (a few dozen pixels, cache-resident) is
-        // scanned once per candidate.
-        const double y0 = fmax(a.ky * (double)i + a.oy, 0.0), y1 = fmin(a.ky * (double)(i + 1) + a.oy, (double)a.sh);
-        const double x0 = fmax(a.kx * (double)j + a.ox, 0.0), x1 = fmin(a.kx * (double)(j + 1) + a.ox, (double)a.sw);
-        int iy0 = (int)floor(y0 + 1e-10), iy1 = (int)ceil(y1 - 1e-10);
-        int ix0 = (int)floor(x0 + 1e-10), ix1 = (int)ceil(x1 - 1e-10);
-        if (iy0 == iy1 && iy1 < a.sh) ++iy1;
-        if (ix0 == ix1 && ix1 < a.sw) ++ix1;
-        if (iy1 > iy0 && iy0 >= 0 && ix1 > ix0 && ix0 >= 0 && y1 > y0 && x1 > x0) {  // shares area with the plane
-            int n = 0;
-            for (int yy = iy0; yy < iy1; ++yy)
-                for (int xx = ix0; xx < ix1; ++xx) n += rs_valid(sp[(long long)yy * a.src_stride + xx], a.nd_mode, a.nodata) ? 1 : 0;
-            if (n > 0) {
-                constexpr double q = MODE == 10 ? 0.5 : (MODE == 11 ? 0.25 : 0.75);
-                int want = (int)ceil(q * (double)n - 1.0);
-                want = want < 0 ? 0 : want;
-                int best_cnt = 0, best_last = 0;
-                for (int yc = iy0; yc < iy1 && !(MODE != 6 && got); ++yc) {
-                    for (int xc = ix0; xc < ix1; ++xc) {
-                        const float c = sp[(long long)yc * a.src_stride + xc];
-                        if (!rs_valid(c, a.nd_mode, a.nodata)) continue;
-                        int less = 0, equal = 0, last = 0, pos = 0;
-                        for (int yy = iy0; yy < iy1; ++yy)
-                            for (int xx = ix0; xx < ix1; ++xx, ++pos) {
-                                const float v = sp[(long long)yy * a.src_stride + xx];
-                                if (!rs_valid(v, a.nd_mode, a.nodata)) continue;
-                                less += v < c ? 1 : 0;
-                                if (v == c) ++equal, last = pos;
+                if (wsum > 0.0) {
+                    result = (MODE == 5) ? tot / wsum : ((MODE == 14) ? sqrt(tot / wsum) : tot);
+                    got = true;
+                }
+            } else {
+                // GWKAverageOrMode's rank-order branches (no weights): med / q1 / q3 = element ceil(q * n - 1) of the sorted valid
+                // values; mode = the value whose running count first reaches the highest count, in row-major scan order.  No
+                // per-thread storage: the footprint (a few dozen pixels, cache-resident) is scanned once per candidate.
+                static_assert(MODE == 6 || MODE == 10 || MODE == 11 || MODE == 12, "not a resampling method of this kernel");
+                int n = 0;
+                for (int yy = fy.i0; yy < fy.i1; ++yy)
+                    for (int xx = fx.i0; xx < fx.i1; ++xx)
+                        n += rs_valid(sp[(long long)yy * p.src_stride + xx], p.nd_mode, p.nodata) ? 1 : 0;
+                if (n > 0) {
+                    constexpr double q = MODE == 10 ? 0.5 : (MODE == 11 ? 0.25 : 0.75);
+                    int want = (int)ceil(q * (double)n - 1.0);
+                    want = want < 0 ? 0 : want;
+                    int best_cnt = 0, best_last = 0;
+                    for (int yc = fy.i0; yc < fy.i1 && !(MODE != 6 && got); ++yc) {
+                        for (int xc = fx.i0; xc < fx.i1; ++xc) {
+                            const float c = sp[(long long)yc * p.src_stride + xc];
+                            if (!rs_valid(c, p.nd_mode, p.nodata)) continue;
+                            int less = 0, equal = 0, last = 0, pos = 0;
+                            for (int yy = fy.i0; yy < fy.i1; ++yy)
+                                for (int xx = fx.i0; xx < fx.i1; ++xx, ++pos) {
+                                    const float v = sp[(long long)yy * p.src_stride + xx];
+                                    if (!rs_valid(v, p.nd_mode, p.nodata)) continue;
+                                    less += v < c ? 1 : 0;
+                                    if (v == c) ++equal, last = pos;
+                                }
+                            if constexpr (MODE == 6) {
+                                // the value that reaches the highest count first = most occurrences, then earliest last occurrence
+                                if (equal > best_cnt || (equal == best_cnt && last < best_last))
+                                    best_cnt = equal, best_last = last, result = (double)c, got = true;
+                            } else if (less <= want && want < less + equal) {
+                                result = (double)c, got = true;
+                                break;
                             }
-                        if constexpr (MODE == 6) {
-                            // the value that reaches the highest count first = most occurrences, then earliest last occurrence
-                            if (equal > best_cnt || (equal == best_cnt && last < best_last))
-                                best_cnt = equal, best_last = last, result = (double)c, got = true;
-                        } else if (less <= want && want < less + equal) {
-                            result = (double)c, got = true;
-                            break;
                         }
                     }
                 }
             }
         }
     } else {
-        constexpr int NT = MODE == 1 ? 2 : 4, T0 = MODE == 1 ? 0 : -1;
-        const double sy = a.ky * ((double)i + 0.5) + a.oy, sx = a.kx * ((double)j + 0.5) + a.ox;
-        const long long cy = (long long)floor(sy + 1e-10), cx = (long long)floor(sx + 1e-10);
-        if (cx >= 0 && cx < a.sw && cy >= 0 && cy < a.sh && rs_valid(sp[cy * a.src_stride + cx], a.nd_mode, a.nodata)) {
-            const int iy = (int)floor(sy - 0.5), ix = (int)floor(sx - 0.5);
-            const double dy = sy - 0.5 - (double)iy, dx = sx - 0.5 - (double)ix;
-            double wys[4], wxs[4];
-            if constexpr (MODE == 1) {
-                wys[0] = 1.0 - dy, wys[1] = dy, wxs[0] = 1.0 - dx, wxs[1] = dx;
+        static_assert(MODE == 0 || MODE == 1 || MODE == 3, "not a resampling method of this kernel");
+        const double sy = scaled_coord(a.ky, a.oy, (double)i + 0.5), sx = scaled_coord(a.kx, a.ox, (double)j + 0.5);
+        long long cx, cy;
+        float vc;
+        if (rs_centre(sx, sy, p.sh, p.sw, cx, cy) && rs_centre_value(sp, p.src_stride, cx, cy, p.nd_mode, p.nodata, vc)) {
+            if constexpr (MODE == 0) {
+                result = (double)vc, got = true;
             } else {
-                bspline4(dy, wys);
-                bspline4(dx, wxs);
-            }
-            double acc = 0.0, wacc = 0.0;
-            for (int tj = 0; tj < NT; ++tj) {
-                const int yy = iy + T0 + tj;
-                if (yy < 0 || yy >= a.sh) continue;
-                for (int ti = 0; ti < NT; ++ti) {
-                    const int xx = ix + T0 + ti;
-                    if (xx < 0 || xx >= a.sw) continue;
-                    const float v = sp[(long long)yy * a.src_stride + xx];
-                    if (!rs_valid(v, a.nd_mode, a.nodata)) continue;
-                    const double wgt = wxs[ti] * wys[tj];
-                    acc += (double)v * wgt;
-                    wacc += wgt;
-                }
-            }
-            if (!(wacc < 1e-6)) {
-                result = (wacc < 0.99999 || wacc > 1.00001) ? acc / wacc : acc;
-                got = true;
+                Taps2 t;
+                rs_taps2<MODE>(sx, sy, t);
+                got = rs_tap_sum<MODE>(sp, p.src_stride, p.sh, p.sw, p.nd_mode, p.nodata, t, result);
             }
         }
     }
-    dp[(long long)i * a.dst_stride + j] = got ? (float)result : a.dst_fill;
+    dp[(long long)i * p.dst_stride + j] = got ? (float)result : p.dst_fill;
 }
 
 // GWKResample for any scale: bilinear (1) / cubic (2) / cubic_spline (3) / lanczos (4)
 template <int KIND>
 __global__ void __launch_bounds__(256) resample_conv_kernel(const ResampleArgs a) {
+    const ResamplePlanes& p = a.p;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = blockIdx.y;
-    if (j >= a.dw) return;
-    const float* __restrict__ sp = a.src + (long long)blockIdx.z * a.src_band_stride;
-    float* __restrict__ dp = a.dst + (long long)blockIdx.z * a.dst_band_stride;
-    constexpr int R = KIND == 1 ? 1 : (KIND == 4 ? 3 : 2);
-    const double xs = a.kx > 1.0 ? 1.0 / a.kx : 1.0, ys = a.ky > 1.0 ? 1.0 / a.ky : 1.0;
-    const int rx = xs < 1.0 ? (int)ceil((double)R / xs) : R, ry = ys < 1.0 ? (int)ceil((double)R / ys) : R;
-    const double sy = a.ky * ((double)i + 0.5) + a.oy, sx = a.kx * ((double)j + 0.5) + a.ox;
-    const long long cy = (long long)floor(sy + 1e-10), cx = (long long)floor(sx + 1e-10);
+    if (j >= p.dw) return;
+    const float* __restrict__ sp = p.src + (long long)blockIdx.z * p.src_band_stride;
+    float* __restrict__ dp = p.dst + (long long)blockIdx.z * p.dst_band_stride;
+    const double sy = scaled_coord(a.ky, a.oy, (double)i + 0.5), sx = scaled_coord(a.kx, a.ox, (double)j + 0.5);
+    long long cx, cy;
+    float vc;
     double result = 0.0;
     bool got = false;
-    if (cx >= 0 && cx < a.sw && cy >= 0 && cy < a.sh && rs_valid(sp[cy * a.src_stride + cx], a.nd_mode, a.nodata)) {
-        const int iy = (int)floor(sy - 0.5), ix = (int)floor(sx - 0.5);
-        const double dy = sy - 0.5 - (double)iy, dx = sx - 0.5 - (double)ix;
-        double acc = 0.0, wacc = 0.0;
-        for (int tj = 1 - ry; tj <= ry; ++tj) {
-            const int yy = iy + tj;
-            if (yy < 0 || yy >= a.sh) continue;
-            const double wy = conv_weight<KIND>(((double)tj - dy) * ys);
-            if (wy == 0.0) continue;
-            for (int ti = 1 - rx; ti <= rx; ++ti) {
-                const int xx = ix + ti;
-                if (xx < 0 || xx >= a.sw) continue;
-                const float v = sp[(long long)yy * a.src_stride + xx];
-                if (!rs_valid(v, a.nd_mode, a.nodata)) continue;
-                const double wgt = conv_weight<KIND>(((double)ti - dx) * xs) * wy;
-                acc += (double)v * wgt;
-                wacc += wgt;
-            }
-        }
-        if (!(fabs(wacc) < 1e-6)) result = acc / wacc, got = true;
+    if (rs_centre(sx, sy, p.sh, p.sw, cx, cy) && rs_centre_value(sp, p.src_stride, cx, cy, p.nd_mode, p.nodata, vc)) {
+        double dy, dx;
+        const int iy = rs_axis_origin(sy, dy), ix = rs_axis_origin(sx, dx);
+        got = rs_conv_sum<KIND>(sp, p.src_stride, p.sh, p.sw, p.nd_mode, p.nodata, rs_conv_axis<KIND>(a.ky), rs_conv_axis<KIND>(a.kx),
+                                iy, ix, dy, dx, result);
     }
-    dp[(long long)i * a.dst_stride + j] = got ? (float)result : a.dst_fill;
+    dp[(long long)i * p.dst_stride + j] = got ? (float)result : p.dst_fill;
 }
 
 // valid(src) as a float32 0/1 plane: RasterArray.mask_ra (raster_array.py:320-327) before it is re-projected
@@ -237,10 +177,13 @@ __global__ void __launch_bounds__(256) apply_space_kernel(const float* __restric
 // ---------------------------------------------------------------------------------------------------------------------
 // RefSpaceModel.apply fused (kernel_model.py:484-503): the up-sampled gain / offset never exist as full-resolution
 // planes.  Per destination pixel the bilinear / cubic-spline values of BOTH parameter planes are formed exactly as
-// resample_kernel<MODE> does (same weights, same tap order, same renormalisation rule), masked like apply_space_kernel and
+// resample_kernel<MODE> forms them (same weights, same tap order, same renormalisation rule), masked like apply_space_kernel and
 // applied.  The work that does not depend on the pixel is hoisted: the row geometry and weights come from a table made
-// by row_table_kernel (one entry per destination row), the column geometry and weights are computed once per thread,
-// which then walks down its column.
+// by row_table_kernel (one entry per destination row, from rs_axis_taps), the column geometry and weights are computed once per
+// thread, which then walks down its column.
+// upsample_apply_kernel does NOT call hk_resample_taps.h: it is the one re-sampler on a measured hot path, and sharing rs_tap_sum
+// with its general path cost it a wave per SIMD (cubic_spline 82 -> 118 VGPRs, bilinear 46 -> 58) for no change in results.  Its
+// column set-up mirrors rs_centre and rs_axis_taps, its two tap sums mirror rs_tap_sum: a change of the rule there is made here too.
 constexpr int UP_ROWS = 16;  // destination rows per thread of upsample_apply_kernel (amortises the column weights)
 struct RowTab {
     double w[4];
@@ -254,21 +197,14 @@ template <int MODE>
 __global__ void __launch_bounds__(256) row_table_kernel(RowTab* __restrict__ tab, int dh, int sh, double ky, double oy) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= dh) return;
-    const double sy = ky * ((double)i + 0.5) + oy;
-    const long long cy = (long long)floor(sy + 1e-10);
+    const double sy = scaled_coord(ky, oy, (double)i + 0.5);
+    long long cy;
     RowTab t;
-    t.iy = (int)floor(sy - 0.5);
-    t.centre = (cy >= 0 && cy < sh) ? (int)cy : -1;
-    const double dy = sy - 0.5 - (double)t.iy;
-    if constexpr (MODE == 1) {
-        t.w[0] = 1.0 - dy, t.w[1] = dy, t.w[2] = t.w[3] = 0.0;
-    } else {
-        bspline4(dy, t.w);
-    }
-    constexpr int NT = MODE == 1 ? 2 : 4, T0 = MODE == 1 ? 0 : -1;
+    t.centre = rs_centre_axis(sy, sh, cy) ? (int)cy : -1;
+    t.iy = rs_axis_taps<MODE>(sy, t.w);
     t.all_in = 1;
     for (int tj = 0; tj < 4; ++tj) {
-        const int yy = t.iy + T0 + (tj < NT ? tj : NT - 1);
+        const int yy = t.iy + RS_T0<MODE> + (tj < RS_NT<MODE> ? tj : RS_NT<MODE> - 1);
         if (yy < 0 || yy >= sh) t.all_in = 0;
         t.yy[tj] = min(max(yy, 0), sh - 1);
     }
@@ -433,16 +369,10 @@ hipError_t launch_apply_space(const float* src, long long src_stride, int nd_mod
     return hipGetLastError();
 }
 
-hipError_t launch_resample(int mode, const float* src, long long src_stride, long long src_band_stride, int sh, int sw,
-                           int n_bands, int nd_mode, float nodata, double kx, double ox, double ky, double oy, float* dst,
-                           long long dst_stride, long long dst_band_stride, int dh, int dw, float dst_fill,
-                           hipStream_t stream) {
-    ResampleArgs a;
-    a.src = src, a.dst = dst, a.src_stride = src_stride, a.src_band_stride = src_band_stride, a.dst_stride = dst_stride;
-    a.dst_band_stride = dst_band_stride, a.sh = sh, a.sw = sw, a.dh = dh, a.dw = dw, a.nd_mode = nd_mode, a.nodata = nodata;
-    a.dst_fill = dst_fill, a.kx = kx, a.ox = ox, a.ky = ky, a.oy = oy;
-    const dim3 grid((dw + 255) / 256, dh, n_bands), block(256);
-    const bool stretched = kx > 1.0 + 1e-9 || ky > 1.0 + 1e-9;  // an axis is down-sampled: the kernel support scales with it
+hipError_t launch_resample(int mode, const ResamplePlanes& p, double kx, double ox, double ky, double oy, hipStream_t stream) {
+    const ResampleArgs a = {p, kx, ox, ky, oy};
+    const dim3 grid((p.dw + 255) / 256, p.dh, p.n_bands), block(256);
+    const bool stretched = resample_stretched(kx, ky);
     switch (mode) {
         case 0: HK_LAUNCH(resample_kernel<0>, grid, block, 0, stream, a); break;
         case 1:
@@ -457,11 +387,11 @@ hipError_t launch_resample(int mode, const float* src, long long src_stride, lon
         case 4: HK_LAUNCH(resample_conv_kernel<4>, grid, block, 0, stream, a); break;
         case 5: HK_LAUNCH(resample_kernel<5>, grid, block, 0, stream, a); break;
         case 6: HK_LAUNCH(resample_kernel<6>, grid, block, 0, stream, a); break;
+        case 8: HK_LAUNCH(resample_kernel<8>, grid, block, 0, stream, a); break;
+        case 9: HK_LAUNCH(resample_kernel<9>, grid, block, 0, stream, a); break;
         case 10: HK_LAUNCH(resample_kernel<10>, grid, block, 0, stream, a); break;
         case 11: HK_LAUNCH(resample_kernel<11>, grid, block, 0, stream, a); break;
         case 12: HK_LAUNCH(resample_kernel<12>, grid, block, 0, stream, a); break;
-        case 8: HK_LAUNCH(resample_kernel<8>, grid, block, 0, stream, a); break;
-        case 9: HK_LAUNCH(resample_kernel<9>, grid, block, 0, stream, a); break;
         case 13: HK_LAUNCH(resample_kernel<13>, grid, block, 0, stream, a); break;
         case 14: HK_LAUNCH(resample_kernel<14>, grid, block, 0, stream, a); break;
         default: return hipErrorInvalidValue;

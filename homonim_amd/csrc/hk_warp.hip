@@ -4,9 +4,9 @@
 //
 // Per destination pixel: destination geo-transform -> destination CRS inverse -> (lon, lat) -> source CRS forward -> inverse
 // source geo-transform = continuous source pixel coordinates (integers = pixel edges), all in float64.  What is then done with
-// the coordinate is the per-tap arithmetic of hk_resample.hip, operation for operation (hk_resample_taps.h and the kernel bodies
-// below): only `sx, sy` come from warp_coord() instead of `k * (j + 0.5) + o`.  Every pixel is transformed exactly -- GDAL's
-// default warp interpolates the transformation linearly within 0.125 pixel.
+// the coordinate is stated in hk_resample_taps.h, the same functions hk_resample.hip calls: the kernels below get `sx, sy` from
+// warp_coord() instead of `k * (j + 0.5) + o`, call them and store.  Every pixel is transformed exactly -- GDAL's default warp
+// interpolates the transformation linearly within 0.125 pixel.
 //
 // CRSs: geographic (degrees) and Transverse Mercator on one ellipsoid (no datum shifts).  Transverse Mercator is the Krueger
 // series in the third flattening n to n^6 (Karney 2011, "Transverse Mercator with an accuracy of a few nanometers", eqs. 35 / 36
@@ -68,7 +68,6 @@ struct WarpMapT<WARP_AFFINE_SAME> {
     AffineGt d, s;
     double det;
 };
-using WarpMap = WarpMapT<WARP_AXIS>;
 
 constexpr double WARP_DEG = 57.295779513082320877;   // degrees per radian
 constexpr double WARP_COORD_MAX = 1e15;              // a source coordinate at or beyond this (or NaN) is "no data"
@@ -202,172 +201,88 @@ __device__ __forceinline__ int warp_row() {
 
 template <int PATH>
 struct WarpCoordArgsT {
-    double* x;
-    double* y;
-    long long stride;
-    int h, w;
-    double off_row, off_col;
+    WarpLattice l;
     WarpMapT<PATH> map;
 };
-using WarpCoordArgs = WarpCoordArgsT<WARP_AXIS>;
 
 template <int PATH>
-__device__ __forceinline__ void warp_coords_pixel(const WarpCoordArgsT<PATH>& a, int i, int j) {
+__global__ void __launch_bounds__(256) warp_coords_kernel(const WarpCoordArgsT<PATH> a) {
+    const WarpLattice& l = a.l;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = warp_row<PATH>();
+    if (j >= l.w || (PATH != WARP_AXIS && i >= l.h)) return;
     double sx, sy;
-    warp_coord(a.map, (double)i + a.off_row, (double)j + a.off_col, sx, sy);
-    a.x[(long long)i * a.stride + j] = sx;
-    a.y[(long long)i * a.stride + j] = sy;
-}
-
-__global__ void __launch_bounds__(256) warp_coords_kernel(const WarpCoordArgs a) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    if (j >= a.w) return;
-    warp_coords_pixel(a, i, j);
-}
-
-template <int PATH>
-__global__ void __launch_bounds__(256) warp_coords_tile_kernel(const WarpCoordArgsT<PATH> a) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y * blockDim.y + threadIdx.y;
-    if (j >= a.w || i >= a.h) return;
-    warp_coords_pixel(a, i, j);
+    warp_coord(a.map, (double)i + l.off_row, (double)j + l.off_col, sx, sy);
+    l.x[(long long)i * l.stride + j] = sx;
+    l.y[(long long)i * l.stride + j] = sy;
 }
 
 template <int PATH>
 struct WarpArgsT {
-    const float* src;
-    float* dst;
-    long long src_stride, src_band_stride, dst_stride, dst_band_stride;
-    int sh, sw, dh, dw, n_bands;
-    int nd_mode;
-    float nodata;
-    float dst_fill;
+    ResamplePlanes p;
     double kx, ky;  // source pixels per destination pixel (mean step): pick and scale the stretched kernels
     WarpMapT<PATH> map;
 };
-using WarpArgs = WarpArgsT<WARP_AXIS>;
 
-// resample_kernel<0 / 1 / 3> of hk_resample.hip with warped coordinates; one thread per destination pixel, all bands
-template <int MODE, int PATH = WARP_AXIS>
+// a thread's destination pixel -> its source coordinate and centre pixel; false when the pixel has no image inside the plane
+template <int PATH>
+__device__ __forceinline__ bool warp_centre(const WarpArgsT<PATH>& a, int i, int j, double& sx, double& sy, long long& cx,
+                                            long long& cy) {
+    warp_coord(a.map, (double)i + 0.5, (double)j + 0.5, sx, sy);
+    return warp_coord_usable(sx, sy) && rs_centre(sx, sy, a.p.sh, a.p.sw, cx, cy);
+}
+
+// 0 nearest, 1 bilinear / 3 cubic_spline when no axis is down-sampled; one thread per destination pixel, all bands: what depends
+// on the coordinate alone (centre pixel, taps and weights) is formed once, outside the band loop
+template <int MODE, int PATH>
 __global__ void __launch_bounds__(256) warp_kernel(const WarpArgsT<PATH> a) {
+    const ResamplePlanes& p = a.p;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = warp_row<PATH>();
-    if (j >= a.dw || (PATH != WARP_AXIS && i >= a.dh)) return;
+    if (j >= p.dw || (PATH != WARP_AXIS && i >= p.dh)) return;
     double sx, sy;
-    warp_coord(a.map, (double)i + 0.5, (double)j + 0.5, sx, sy);
-    const bool usable = warp_coord_usable(sx, sy);
-    const long long cy = usable ? (long long)floor(sy + 1e-10) : -1, cx = usable ? (long long)floor(sx + 1e-10) : -1;
-    const bool inside = cx >= 0 && cx < a.sw && cy >= 0 && cy < a.sh;
-    constexpr int NT = MODE == 1 ? 2 : 4, T0 = MODE == 1 ? 0 : -1;
-    int iy = 0, ix = 0;
-    double wys[4] = {0.0, 0.0, 0.0, 0.0}, wxs[4] = {0.0, 0.0, 0.0, 0.0};
+    long long cx = -1, cy = -1;
+    const bool inside = warp_centre(a, i, j, sx, sy, cx, cy);
+    Taps2 t = {};
     if constexpr (MODE != 0) {
-        if (inside) {
-            iy = (int)floor(sy - 0.5), ix = (int)floor(sx - 0.5);
-            const double dy = sy - 0.5 - (double)iy, dx = sx - 0.5 - (double)ix;
-            if constexpr (MODE == 1) {
-                wys[0] = 1.0 - dy, wys[1] = dy, wxs[0] = 1.0 - dx, wxs[1] = dx;
-            } else {
-                bspline4(dy, wys);
-                bspline4(dx, wxs);
-            }
-        }
+        if (inside) rs_taps2<MODE>(sx, sy, t);
     }
-    for (int b = 0; b < a.n_bands; ++b) {
-        const float* __restrict__ sp = a.src + (long long)b * a.src_band_stride;
+    for (int b = 0; b < p.n_bands; ++b) {
+        const float* __restrict__ sp = p.src + (long long)b * p.src_band_stride;
         double result = 0.0;
         bool got = false;
-        if (inside) {
-            const float vc = sp[cy * a.src_stride + cx];
-            if (rs_valid(vc, a.nd_mode, a.nodata)) {
-                if constexpr (MODE == 0) {
-                    result = (double)vc, got = true;
-                } else {
-                    double acc = 0.0, wacc = 0.0;
-#pragma unroll
-                    for (int tj = 0; tj < NT; ++tj) {
-                        const int yy = iy + T0 + tj;
-                        if (yy < 0 || yy >= a.sh) continue;
-#pragma unroll
-                        for (int ti = 0; ti < NT; ++ti) {
-                            const int xx = ix + T0 + ti;
-                            if (xx < 0 || xx >= a.sw) continue;
-                            const float v = sp[(long long)yy * a.src_stride + xx];
-                            if (!rs_valid(v, a.nd_mode, a.nodata)) continue;
-                            const double wgt = wxs[ti] * wys[tj];
-                            acc += (double)v * wgt;
-                            wacc += wgt;
-                        }
-                    }
-                    if (!(wacc < 1e-6)) {
-                        result = (wacc < 0.99999 || wacc > 1.00001) ? acc / wacc : acc;
-                        got = true;
-                    }
-                }
-            }
+        float vc;
+        if (inside && rs_centre_value(sp, p.src_stride, cx, cy, p.nd_mode, p.nodata, vc)) {
+            if constexpr (MODE == 0) result = (double)vc, got = true;
+            else got = rs_tap_sum<MODE>(sp, p.src_stride, p.sh, p.sw, p.nd_mode, p.nodata, t, result);
         }
-        a.dst[(long long)b * a.dst_band_stride + (long long)i * a.dst_stride + j] = got ? (float)result : a.dst_fill;
+        p.dst[(long long)b * p.dst_band_stride + (long long)i * p.dst_stride + j] = got ? (float)result : p.dst_fill;
     }
 }
 
-// resample_conv_kernel<1..4> of hk_resample.hip (GWKResample for any scale) with warped coordinates
-template <int KIND, int PATH = WARP_AXIS>
+// GWKResample for any scale: bilinear (1) / cubic (2) / cubic_spline (3) / lanczos (4); threads and bands as in warp_kernel
+template <int KIND, int PATH>
 __global__ void __launch_bounds__(256) warp_conv_kernel(const WarpArgsT<PATH> a) {
+    const ResamplePlanes& p = a.p;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = warp_row<PATH>();
-    if (j >= a.dw || (PATH != WARP_AXIS && i >= a.dh)) return;
-    constexpr int R = KIND == 1 ? 1 : (KIND == 4 ? 3 : 2);
-    const double xs = a.kx > 1.0 ? 1.0 / a.kx : 1.0, ys = a.ky > 1.0 ? 1.0 / a.ky : 1.0;
-    const int rx = xs < 1.0 ? (int)ceil((double)R / xs) : R, ry = ys < 1.0 ? (int)ceil((double)R / ys) : R;
+    if (j >= p.dw || (PATH != WARP_AXIS && i >= p.dh)) return;
+    const ConvAxis ay = rs_conv_axis<KIND>(a.ky), ax = rs_conv_axis<KIND>(a.kx);
     double sx, sy;
-    warp_coord(a.map, (double)i + 0.5, (double)j + 0.5, sx, sy);
-    const bool usable = warp_coord_usable(sx, sy);
-    const long long cy = usable ? (long long)floor(sy + 1e-10) : -1, cx = usable ? (long long)floor(sx + 1e-10) : -1;
-    const bool inside = cx >= 0 && cx < a.sw && cy >= 0 && cy < a.sh;
+    long long cx = -1, cy = -1;
+    const bool inside = warp_centre(a, i, j, sx, sy, cx, cy);
     int iy = 0, ix = 0;
     double dy = 0.0, dx = 0.0;
-    if (inside) {
-        iy = (int)floor(sy - 0.5), ix = (int)floor(sx - 0.5);
-        dy = sy - 0.5 - (double)iy, dx = sx - 0.5 - (double)ix;
-    }
-    for (int b = 0; b < a.n_bands; ++b) {
-        const float* __restrict__ sp = a.src + (long long)b * a.src_band_stride;
+    if (inside) iy = rs_axis_origin(sy, dy), ix = rs_axis_origin(sx, dx);
+    for (int b = 0; b < p.n_bands; ++b) {
+        const float* __restrict__ sp = p.src + (long long)b * p.src_band_stride;
         double result = 0.0;
-        bool got = false;
-        if (inside && rs_valid(sp[cy * a.src_stride + cx], a.nd_mode, a.nodata)) {
-            double acc = 0.0, wacc = 0.0;
-            for (int tj = 1 - ry; tj <= ry; ++tj) {
-                const int yy = iy + tj;
-                if (yy < 0 || yy >= a.sh) continue;
-                const double wy = conv_weight<KIND>(((double)tj - dy) * ys);
-                if (wy == 0.0) continue;
-                for (int ti = 1 - rx; ti <= rx; ++ti) {
-                    const int xx = ix + ti;
-                    if (xx < 0 || xx >= a.sw) continue;
-                    const float v = sp[(long long)yy * a.src_stride + xx];
-                    if (!rs_valid(v, a.nd_mode, a.nodata)) continue;
-                    const double wgt = conv_weight<KIND>(((double)ti - dx) * xs) * wy;
-                    acc += (double)v * wgt;
-                    wacc += wgt;
-                }
-            }
-            if (!(fabs(wacc) < 1e-6)) result = acc / wacc, got = true;
-        }
-        a.dst[(long long)b * a.dst_band_stride + (long long)i * a.dst_stride + j] = got ? (float)result : a.dst_fill;
+        float vc;
+        const bool got = inside && rs_centre_value(sp, p.src_stride, cx, cy, p.nd_mode, p.nodata, vc) &&
+                         rs_conv_sum<KIND>(sp, p.src_stride, p.sh, p.sw, p.nd_mode, p.nodata, ay, ax, iy, ix, dy, dx, result);
+        p.dst[(long long)b * p.dst_band_stride + (long long)i * p.dst_stride + j] = got ? (float)result : p.dst_fill;
     }
 }
-
-// the affine builds by names of one template argument, which is what HK_LAUNCH can spell
-template <int MODE>
-constexpr auto warp_affine_kernel = warp_kernel<MODE, WARP_AFFINE>;
-template <int MODE>
-constexpr auto warp_same_kernel = warp_kernel<MODE, WARP_AFFINE_SAME>;
-template <int KIND>
-constexpr auto warp_conv_affine_kernel = warp_conv_kernel<KIND, WARP_AFFINE>;
-template <int KIND>
-constexpr auto warp_conv_same_kernel = warp_conv_kernel<KIND, WARP_AFFINE_SAME>;
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host: descriptor -> device parameters
@@ -407,7 +322,7 @@ static bool crs_params(const hk_crs_desc& d, CrsParams& p, const char** why) {
     return true;
 }
 
-static bool warp_map(const hk_warp_desc& d, WarpMap& m, const char** why) {
+static bool warp_map(const hk_warp_desc& d, WarpMapT<WARP_AXIS>& m, const char** why) {
     if (!crs_params(d.src_crs, m.src, why) || !crs_params(d.dst_crs, m.dst, why)) return false;
     if (d.src_crs.a != d.dst_crs.a || d.src_crs.inv_f != d.dst_crs.inv_f)
         return *why = "the two CRSs are on different ellipsoids (no datum shifts)", false;
@@ -418,48 +333,6 @@ static bool warp_map(const hk_warp_desc& d, WarpMap& m, const char** why) {
     m.dx0 = d.dst_gt[0], m.ddx = d.dst_gt[1], m.dy0 = d.dst_gt[2], m.ddy = d.dst_gt[3];
     m.sx0 = d.src_gt[0], m.sdx = d.src_gt[1], m.sy0 = d.src_gt[2], m.sdy = d.src_gt[3];
     return true;
-}
-
-// one launch of the build that `mode` (rasterio.enums.Resampling value 0..4) and `stretched` pick, among the builds of one path
-#define HK_WARP_LAUNCH_MODES(plain, conv)                                                                                        \
-    switch (mode) {                                                                                                              \
-        case 0: HK_LAUNCH(plain<0>, grid, block, 0, stream, a); break;                                                           \
-        case 1:                                                                                                                  \
-            if (stretched) HK_LAUNCH(conv<1>, grid, block, 0, stream, a);                                                        \
-            else HK_LAUNCH(plain<1>, grid, block, 0, stream, a);                                                                 \
-            break;                                                                                                               \
-        case 2: HK_LAUNCH(conv<2>, grid, block, 0, stream, a); break;                                                            \
-        case 3:                                                                                                                  \
-            if (stretched) HK_LAUNCH(conv<3>, grid, block, 0, stream, a);                                                        \
-            else HK_LAUNCH(plain<3>, grid, block, 0, stream, a);                                                                 \
-            break;                                                                                                               \
-        case 4: HK_LAUNCH(conv<4>, grid, block, 0, stream, a); break;                                                            \
-        default: *why = "resampling is not one of nearest / bilinear / cubic / cubic_spline / lanczos"; return hipErrorInvalidValue; \
-    }
-
-hipError_t launch_warp_coords(const hk_warp_desc* desc, double off_row, double off_col, double* x, double* y, long long stride,
-                              int h, int w, hipStream_t stream, const char** why) {
-    WarpCoordArgs a;
-    if (!warp_map(*desc, a.map, why)) return hipErrorInvalidValue;
-    a.x = x, a.y = y, a.stride = stride, a.h = h, a.w = w, a.off_row = off_row, a.off_col = off_col;
-    HK_LAUNCH(warp_coords_kernel, dim3((w + 255) / 256, h), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-// mode = rasterio.enums.Resampling value 0..4
-hipError_t launch_warp_resample(int mode, const hk_warp_desc* desc, const float* src, long long src_stride,
-                                long long src_band_stride, int sh, int sw, int n_bands, int nd_mode, float nodata, double kx,
-                                double ky, float* dst, long long dst_stride, long long dst_band_stride, int dh, int dw,
-                                float dst_fill, hipStream_t stream, const char** why) {
-    WarpArgs a;
-    if (!warp_map(*desc, a.map, why)) return hipErrorInvalidValue;
-    a.src = src, a.dst = dst, a.src_stride = src_stride, a.src_band_stride = src_band_stride, a.dst_stride = dst_stride;
-    a.dst_band_stride = dst_band_stride, a.sh = sh, a.sw = sw, a.dh = dh, a.dw = dw, a.n_bands = n_bands, a.nd_mode = nd_mode;
-    a.nodata = nodata, a.dst_fill = dst_fill, a.kx = kx, a.ky = ky;
-    const dim3 grid((dw + 255) / 256, dh), block(256);
-    const bool stretched = kx > 1.0 + 1e-9 || ky > 1.0 + 1e-9;  // as launch_resample picks the kernels
-    HK_WARP_LAUNCH_MODES(warp_kernel, warp_conv_kernel);
-    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -487,9 +360,9 @@ static bool warp_map(const hk_affine_warp_desc& d, WarpMapT<WARP_AFFINE_SAME>& m
     return affine_gt(d.src_gt, d.dst_gt, m.s, m.d, m.det, why);
 }
 
-// The thread tile of the affine builds, width x height = 256.  32 x 8 is provisional: profiles/warp.txt holds no measurement
-// yet.  HK_WARP_TILE=WxH, read once, overrides it for that measurement (tools/warp_timing.py).  Any tile gives the same bits: a
-// thread's pixel is all it sees.
+// The thread tile of the affine builds, width x height = 256.  32 x 8 is provisional: no measurement has chosen it yet
+// (profiles/warp.txt).  HK_WARP_TILE=WxH, read once, overrides it for that measurement (tools/warp_timing.py).  Any tile gives
+// the same bits: a thread's pixel is all it sees.
 static dim3 warp_tile() {
     static const dim3 tile = [] {
         int w = 32, h = 8, ew = 0, eh = 0;
@@ -500,56 +373,81 @@ static dim3 warp_tile() {
     return tile;
 }
 
-static dim3 warp_tile_grid(dim3 tile, int h, int w) { return dim3((w + tile.x - 1) / tile.x, (h + tile.y - 1) / tile.y); }
-
+// ---------------------------------------------------------------------------------------------------------------------
+// The launch path: descriptor -> map, then the build of PATH that the arguments pick, on PATH's thread mapping (above).  Each
+// build is launched under its own spelling, which is its name in the launch ledger (HK_LAUNCH).
 template <int PATH>
-static hipError_t launch_coords_tiled(const hk_affine_warp_desc* desc, double off_row, double off_col, double* x, double* y,
-                                      long long stride, int h, int w, hipStream_t stream, const char** why) {
+static dim3 warp_block() {
+    return PATH == WARP_AXIS ? dim3(256, 1) : warp_tile();
+}
+static dim3 warp_grid(dim3 block, int h, int w) { return dim3((w + block.x - 1) / block.x, (h + block.y - 1) / block.y); }
+
+template <int PATH, typename Desc>
+static hipError_t launch_coords_path(const Desc* desc, const WarpLattice& l, hipStream_t stream, const char** why) {
     WarpCoordArgsT<PATH> a;
     if (!warp_map(*desc, a.map, why)) return hipErrorInvalidValue;
-    a.x = x, a.y = y, a.stride = stride, a.h = h, a.w = w, a.off_row = off_row, a.off_col = off_col;
-    const dim3 block = warp_tile(), grid = warp_tile_grid(block, h, w);
-    if constexpr (PATH == WARP_AFFINE) HK_LAUNCH(warp_coords_tile_kernel<WARP_AFFINE>, grid, block, 0, stream, a);
-    else HK_LAUNCH(warp_coords_tile_kernel<WARP_AFFINE_SAME>, grid, block, 0, stream, a);
+    a.l = l;
+    const dim3 block = warp_block<PATH>(), grid = warp_grid(block, l.h, l.w);
+    if constexpr (PATH == WARP_AXIS) HK_LAUNCH(warp_coords_kernel<WARP_AXIS>, grid, block, 0, stream, a);
+    else if constexpr (PATH == WARP_AFFINE) HK_LAUNCH(warp_coords_kernel<WARP_AFFINE>, grid, block, 0, stream, a);
+    else HK_LAUNCH(warp_coords_kernel<WARP_AFFINE_SAME>, grid, block, 0, stream, a);
     return hipGetLastError();
 }
 
-hipError_t launch_warp_coords(const hk_affine_warp_desc* desc, double off_row, double off_col, double* x, double* y,
-                              long long stride, int h, int w, hipStream_t stream, const char** why) {
-    return desc->same_crs ? launch_coords_tiled<WARP_AFFINE_SAME>(desc, off_row, off_col, x, y, stride, h, w, stream, why)
-                          : launch_coords_tiled<WARP_AFFINE>(desc, off_row, off_col, x, y, stride, h, w, stream, why);
-}
+// the build of one path that `mode` (rasterio.enums.Resampling value 0..4) and `stretched` pick.  `path` must be spelled, not a
+// template parameter: the parenthesised kernel is the ledger's name of the build, and two builds under one name would hide one.
+#define HK_WARP_LAUNCH_MODES(path)                                                                                               \
+    switch (mode) {                                                                                                              \
+        case 0: HK_LAUNCH((warp_kernel<0, path>), grid, block, 0, stream, a); break;                                             \
+        case 1:                                                                                                                  \
+            if (stretched) HK_LAUNCH((warp_conv_kernel<1, path>), grid, block, 0, stream, a);                                    \
+            else HK_LAUNCH((warp_kernel<1, path>), grid, block, 0, stream, a);                                                   \
+            break;                                                                                                               \
+        case 2: HK_LAUNCH((warp_conv_kernel<2, path>), grid, block, 0, stream, a); break;                                        \
+        case 3:                                                                                                                  \
+            if (stretched) HK_LAUNCH((warp_conv_kernel<3, path>), grid, block, 0, stream, a);                                    \
+            else HK_LAUNCH((warp_kernel<3, path>), grid, block, 0, stream, a);                                                   \
+            break;                                                                                                               \
+        case 4: HK_LAUNCH((warp_conv_kernel<4, path>), grid, block, 0, stream, a); break;                                        \
+        default: *why = "resampling is not one of nearest / bilinear / cubic / cubic_spline / lanczos"; return hipErrorInvalidValue; \
+    }
 
-template <int PATH>
-static hipError_t launch_resample_tiled(int mode, const hk_affine_warp_desc* desc, const float* src, long long src_stride,
-                                        long long src_band_stride, int sh, int sw, int n_bands, int nd_mode, float nodata,
-                                        double kx, double ky, float* dst, long long dst_stride, long long dst_band_stride, int dh,
-                                        int dw, float dst_fill, hipStream_t stream, const char** why) {
+template <int PATH, typename Desc>
+static hipError_t launch_resample_path(int mode, const Desc* desc, const ResamplePlanes& p, double kx, double ky, hipStream_t stream,
+                                       const char** why) {
     WarpArgsT<PATH> a;
     if (!warp_map(*desc, a.map, why)) return hipErrorInvalidValue;
-    a.src = src, a.dst = dst, a.src_stride = src_stride, a.src_band_stride = src_band_stride, a.dst_stride = dst_stride;
-    a.dst_band_stride = dst_band_stride, a.sh = sh, a.sw = sw, a.dh = dh, a.dw = dw, a.n_bands = n_bands, a.nd_mode = nd_mode;
-    a.nodata = nodata, a.dst_fill = dst_fill, a.kx = kx, a.ky = ky;
-    const dim3 block = warp_tile(), grid = warp_tile_grid(block, dh, dw);
-    const bool stretched = kx > 1.0 + 1e-9 || ky > 1.0 + 1e-9;
-    if constexpr (PATH == WARP_AFFINE) {
-        HK_WARP_LAUNCH_MODES(warp_affine_kernel, warp_conv_affine_kernel);
+    a.p = p, a.kx = kx, a.ky = ky;
+    const dim3 block = warp_block<PATH>(), grid = warp_grid(block, p.dh, p.dw);
+    const bool stretched = resample_stretched(kx, ky);
+    if constexpr (PATH == WARP_AXIS) {
+        HK_WARP_LAUNCH_MODES(WARP_AXIS)
+    } else if constexpr (PATH == WARP_AFFINE) {
+        HK_WARP_LAUNCH_MODES(WARP_AFFINE)
     } else {
-        HK_WARP_LAUNCH_MODES(warp_same_kernel, warp_conv_same_kernel);
+        HK_WARP_LAUNCH_MODES(WARP_AFFINE_SAME)
     }
     return hipGetLastError();
 }
 
-hipError_t launch_warp_resample(int mode, const hk_affine_warp_desc* desc, const float* src, long long src_stride,
-                                long long src_band_stride, int sh, int sw, int n_bands, int nd_mode, float nodata, double kx,
-                                double ky, float* dst, long long dst_stride, long long dst_band_stride, int dh, int dw,
-                                float dst_fill, hipStream_t stream, const char** why) {
-    return desc->same_crs ? launch_resample_tiled<WARP_AFFINE_SAME>(mode, desc, src, src_stride, src_band_stride, sh, sw, n_bands,
-                                                                    nd_mode, nodata, kx, ky, dst, dst_stride, dst_band_stride, dh,
-                                                                    dw, dst_fill, stream, why)
-                          : launch_resample_tiled<WARP_AFFINE>(mode, desc, src, src_stride, src_band_stride, sh, sw, n_bands,
-                                                               nd_mode, nodata, kx, ky, dst, dst_stride, dst_band_stride, dh, dw,
-                                                               dst_fill, stream, why);
+hipError_t launch_warp_coords(const hk_warp_desc* desc, const WarpLattice& l, hipStream_t stream, const char** why) {
+    return launch_coords_path<WARP_AXIS>(desc, l, stream, why);
+}
+
+hipError_t launch_warp_coords(const hk_affine_warp_desc* desc, const WarpLattice& l, hipStream_t stream, const char** why) {
+    return desc->same_crs ? launch_coords_path<WARP_AFFINE_SAME>(desc, l, stream, why)
+                          : launch_coords_path<WARP_AFFINE>(desc, l, stream, why);
+}
+
+hipError_t launch_warp_resample(int mode, const hk_warp_desc* desc, const ResamplePlanes& p, double kx, double ky, hipStream_t stream,
+                                const char** why) {
+    return launch_resample_path<WARP_AXIS>(mode, desc, p, kx, ky, stream, why);
+}
+
+hipError_t launch_warp_resample(int mode, const hk_affine_warp_desc* desc, const ResamplePlanes& p, double kx, double ky,
+                                hipStream_t stream, const char** why) {
+    return desc->same_crs ? launch_resample_path<WARP_AFFINE_SAME>(mode, desc, p, kx, ky, stream, why)
+                          : launch_resample_path<WARP_AFFINE>(mode, desc, p, kx, ky, stream, why);
 }
 
 }  // namespace hk
