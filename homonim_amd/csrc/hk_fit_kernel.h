@@ -24,6 +24,14 @@
 
 namespace hk {
 
+// The only compile-time switches left are INSTRUMENTS; an experiment that was decided is recorded in profiles/ (FLOOR.md, the root
+// HISTORY.md), not kept behind a macro:
+//   HK_STAMPS                        in-kernel stage stamps (below; tools/stage_stamps.py)
+//   HK_ABLATE=bits                   timing builds with one ingredient taken out (below; FLOOR.md section 3)
+//   HK_DEV_SUBSET, HK_DEV_SUBSET15   development builds that instantiate a few kernels only (launch_rw)
+//   HK_FIT_ONE_TU                    every instantiation in the translation unit of hk_kernels.hip (the A/B tooling under tools/)
+//   HK_TU_MODEL, HK_TU_R2            the MODEL x R2 that one translation unit of hk_fit_tu.hip instantiates (homonim_amd/build.py)
+
 // In-kernel stage stamps (build with -DHK_STAMPS; tools/stage_stamps.py): every wave accumulates the shader-clock cycles it spends
 // between the marked points of a row iteration (s_memtime; waits for memory land in the stage that needs the data) and adds them
 // to hk_stamps[] when it ends; [15] counts iterations, [14] waves.  Costs ~10 % of the kernel's time; never in the shipped build.
@@ -59,9 +67,6 @@ static inline hipError_t read_stamps_tu(unsigned long long* acc16, bool reset) {
 // 2: gain-blk-offset without its float64 quotient, 4: no horizontal sums, 8: no corrected-plane stores.
 #ifndef HK_ABLATE
 #define HK_ABLATE 0
-#endif
-#ifndef HK_PACKED_NSUM
-#define HK_PACKED_NSUM 1  // window counts of the narrow kernels summed as packed bytes (fit_apply_kernel)
 #endif
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -170,38 +175,32 @@ __host__ __device__ constexpr bool specific_before(int rw, int i, int j, bool ri
 //     crossbar, one instruction per dword whatever the distance);
 //   * lanes that lie wholly inside all four windows are summed once into a common term.
 // RW = 2: 4 shifted values (8 DPP moves) + 9 adds per 4 pixels; RW = 7: 2 DPP-shifted + 6 permuted values + 13 adds.
-// XCH (float64 quantities of the kernels whose strips overlap by one lane): the distance-1 neighbours' partial sums travel
-// through a wave-private LDS exchange line instead of DPP moves -- the kernel is bound by VALU issue (a 64-bit value costs two
-// 4-cycle v_mov_b32_dpp), while the LDS pipe has room: per quantity and direction one ds_write_b128 + one ds_read_b128 of the
-// neighbour's slot.  `xch` = this lane's 16-byte slot; slots -1 and 64 exist (never written: lanes 0 and 63 are overlap lanes
-// whose sums are discarded).  LDS operations of one wave execute in order, so the line is re-used without waiting.
-__device__ __forceinline__ void xch_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-typedef double hk_d2 __attribute__((ext_vector_type(2)));
+// (LDS exchange for the distance-1 neighbours was tried and lost: root HISTORY.md, "LDS exchange instead of DPP".)
 // DPP2: the neighbours at distance 2 through two chained wave shifts (four v_mov_b32_dpp per float64 value) instead of the LDS
 // crossbar (two ds_bpermute_b32).  One ds_bpermute costs the CU 2.6 ns whichever SIMD issued it, a DPP move 0.6 ns of one SIMD's
 // issue (profiles/r05_ubench_xlane.txt): the builds whose five float64 quantities make them crossbar-bound gain, the VALU-bound ones lose.
-#ifndef HK_DPP2
-#define HK_DPP2 1
-#endif
-template <int RW, typename T, bool XCH = false, bool DPP2 = false>
-__device__ __forceinline__ void hsum(const T (&V)[PX], T (&H)[PX], int lane, [[maybe_unused]] char* xch = nullptr) {
+
+// the lane's own partial sums (5 adds): pre[k] = V[0..k-1], suf[k] = V[4-k..3], k = 1..4
+template <typename T>
+__device__ __forceinline__ void own_partials(const T (&V)[PX], T (&pre)[PX + 1], T (&suf)[PX + 1]) {
+    pre[1] = V[0];
+    pre[2] = V[0] + V[1];
+    pre[3] = pre[2] + V[2];
+    suf[1] = V[3];
+    suf[2] = V[2] + V[3];
+    suf[3] = V[1] + suf[2];
+    pre[4] = suf[4] = pre[2] + suf[2];
+}
+
+template <int RW, typename T, bool DPP2 = false>
+__device__ __forceinline__ void hsum(const T (&V)[PX], T (&H)[PX], int lane) {
     if constexpr (RW == 0) {
 #pragma unroll
         for (int i = 0; i < PX; ++i) H[i] = V[i];
     } else {
         constexpr int OL = (RW + PX - 1) / PX;
-        T pre[PX + 1], suf[PX + 1];  // pre[k] = V[0..k-1], suf[k] = V[4-k..3]
-        pre[1] = V[0];
-        pre[2] = V[0] + V[1];
-        pre[3] = pre[2] + V[2];
-        suf[1] = V[3];
-        suf[2] = V[2] + V[3];
-        suf[3] = V[1] + suf[2];
-        pre[4] = suf[4] = pre[2] + suf[2];
+        T pre[PX + 1], suf[PX + 1];
+        own_partials(V, pre, suf);
         constexpr bool OWN_FULL = RW >= PX - 1;  // every output's window holds the lane's own four columns
         T common = pre[PX];
         static_for<0, PX>([&](auto I) {
@@ -218,26 +217,6 @@ __device__ __forceinline__ void hsum(const T (&V)[PX], T (&H)[PX], int lane, [[m
         static_for<1, OL + 1>([&](auto J) {
             constexpr int j = decltype(J)::value;
             T ls[PX + 1], rp[PX + 1];
-            if constexpr (XCH && j == 1 && std::is_same<T, double>::value && (RW == 1 || RW == 2)) {
-                // needed from the left: suf[1..RW], from the right: pre[1..RW]
-                if constexpr (RW == 2) {
-                    *reinterpret_cast<hk_d2*>(xch) = hk_d2{(double)suf[1], (double)suf[2]};
-                    xch_order();
-                    const hk_d2 l = *reinterpret_cast<const hk_d2*>(xch - 16);
-                    xch_order();
-                    *reinterpret_cast<hk_d2*>(xch) = hk_d2{(double)pre[1], (double)pre[2]};
-                    xch_order();
-                    const hk_d2 r = *reinterpret_cast<const hk_d2*>(xch + 16);
-                    xch_order();
-                    ls[1] = (T)l.x, ls[2] = (T)l.y, rp[1] = (T)r.x, rp[2] = (T)r.y;
-                } else {
-                    *reinterpret_cast<hk_d2*>(xch) = hk_d2{(double)suf[1], (double)pre[1]};
-                    xch_order();
-                    ls[1] = (T)*reinterpret_cast<const double*>(xch - 16);
-                    rp[1] = (T)*reinterpret_cast<const double*>(xch + 16 + 8);
-                    xch_order();
-                }
-            } else
             static_for<1, PX + 1>([&](auto K) {
                 constexpr int k = decltype(K)::value;
                 if constexpr (need_left_at(RW, j, k)) {
@@ -319,77 +298,37 @@ __host__ __device__ constexpr int wide_e(int rw_code) { return rw_code >= -PX ? 
 __host__ __device__ constexpr bool wide_paired(int rw_code) { return rw_code < -PX; }
 __host__ __device__ constexpr int wide_whole_lanes(int e, int f) { return lane_full_for_all(2 * PX + e, 2) ? f : f - 1; }
 __host__ __device__ constexpr bool wide_pairs(int e, int f) { return wide_whole_lanes(e, f) >= 3 && (wide_whole_lanes(e, f) & 1); }
-template <int E, typename T, bool PAIR = false>
-__device__ __forceinline__ void hsum_wide(const T (&V)[PX], T (&H)[PX], const WideLanes& wl, int lane) {
-    constexpr int RV = 2 * PX + E;  // the virtual half-width whose lanes 2 and 3 stand for the lanes F and F + 1
-    T pre[PX + 1], suf[PX + 1];     // pre[k] = V[0..k-1], suf[k] = V[4-k..3]
-    pre[1] = V[0];
-    pre[2] = V[0] + V[1];
-    pre[3] = pre[2] + V[2];
-    suf[1] = V[3];
-    suf[2] = V[2] + V[3];
-    suf[3] = V[1] + suf[2];
-    pre[4] = suf[4] = pre[2] + suf[2];
-    // the lane's own four columns and the whole lanes (PAIR: see above; the launch made sure that W is odd and >= 3)
-    constexpr bool FULL2 = lane_full_for_all(RV, 2);
-    T common = pre[PX];
-    if constexpr (PAIR) {
-        const int W = FULL2 ? wl.f : wl.f - 1;  // wave-uniform
-        // pairs (o, o + 1) for o = -W, ..., -3, [-1], [1], 3, ..., W - 2 (in brackets: a DPP move away from A)
-        const T A = pre[PX] + dpp_from_right(pre[PX]);
-        common = bperm_from<T>(pre[PX], lane + W);
-        common = common + dpp_from_left(A);
-        common = common + dpp_from_right(A);
-        for (int o = 3; o <= W - 2; o += 2) common = common + bperm_from<T>(A, lane + o);  // (wave-uniform trip counts)
-        for (int o = 3; o <= W; o += 2) common = common + bperm_from<T>(A, lane - o);
-    } else {
-        if (wl.f >= 2) {  // wave-uniform (F = 1: a tall kernel 9 - 15 wide on the everything-re-loaded path)
-            common = common + dpp_from_left(pre[PX]);
-            common = common + dpp_from_right(pre[PX]);
-        }
-        for (int j = 2; j < wl.f; ++j) {  // wave-uniform
-            common = common + bperm_from<T>(pre[PX], lane - j);
-            common = common + bperm_from<T>(pre[PX], lane + j);
-        }
+
+// Where the wide sum (hsum_wide below) takes the partial sums of another lane from.  A source answers, for T = a lane's four
+// columns and o = a lane distance (o > 0: to the right):
+//   publish(pre, suf)              the lane's own partial sums are ready (they outlive the source)
+//   whole(o)                       T(o)
+//   pair_left1(), pair_right1()    T(-1) + T(0) and T(1) + T(2): the pairs next to the lane
+//   pair(o)                        T(o) + T(o + 1)
+//   left<J, K>(), right<J, K>()    suf[K] of the lane F + J - 2 to the left, pre[K] of the lane F + J - 2 to the right (J = 2, 3)
+//   done()                         the sum has taken all it needs
+// First source: the LDS crossbar.  Paired form: A = T + T(right neighbour) is formed BEFORE the first fetch.
+template <typename T, bool PAIR>
+struct WideCrossbar {
+    const WideLanes& wl;
+    const int lane;
+    const T *pre, *suf;
+    T A;  // paired form: T + T(right neighbour)
+    __device__ __forceinline__ WideCrossbar(const WideLanes& wl_, int lane_) : wl(wl_), lane(lane_) {}
+    __device__ __forceinline__ void publish(const T (&pre_)[PX + 1], const T (&suf_)[PX + 1]) {
+        pre = pre_, suf = suf_;
+        if constexpr (PAIR) A = pre[PX] + dpp_from_right(pre[PX]);
     }
-    static_for<2, 4>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        T ls[PX + 1], rp[PX + 1];
-        static_for<1, PX + 1>([&](auto K) {
-            constexpr int k = decltype(K)::value;
-            if constexpr (PAIR && j == 2 && k == PX && FULL2) {
-                // (the lanes F as a whole: part of the pairs above)
-            } else {
-                if constexpr (need_left_at(RV, j, k)) ls[k] = bperm_at(suf[k], j == 2 ? wl.lf1 + 4 : wl.lf1);
-                if constexpr (need_right_at(RV, j, k)) rp[k] = bperm_at(pre[k], j == 2 ? wl.rf : wl.rf + 4);
-            }
-        });
-        if constexpr (lane_full_for_all(RV, j)) {
-            if constexpr (!PAIR) {
-                common = common + ls[PX];
-                common = common + rp[PX];
-            }
-        } else {
-            static_for<0, PX>([&](auto I) {
-                constexpr int i = decltype(I)::value;
-                constexpr int ll = left_len(RV, i, j), rl = right_len(RV, i, j);
-                if constexpr (ll > 0) {
-                    if constexpr (specific_before(RV, i, j, false, true)) H[i] = H[i] + ls[ll];
-                    else H[i] = ls[ll];
-                }
-                if constexpr (rl > 0) {
-                    if constexpr (specific_before(RV, i, j, true, true)) H[i] = H[i] + rp[rl];
-                    else H[i] = rp[rl];
-                }
-            });
-        }
-    });
-    static_for<0, PX>([&](auto I) {
-        constexpr int i = decltype(I)::value;
-        if constexpr (specific_before(RV, i, 4, false, true)) H[i] = common + H[i];
-        else H[i] = common;
-    });
-}
+    __device__ __forceinline__ T whole(int o) const { return bperm_from<T>(pre[PX], lane + o); }
+    __device__ __forceinline__ T pair_left1() const { return dpp_from_left(A); }
+    __device__ __forceinline__ T pair_right1() const { return dpp_from_right(A); }
+    __device__ __forceinline__ T pair(int o) const { return bperm_from<T>(A, lane + o); }
+    template <int J, int K>
+    __device__ __forceinline__ T left() const { return bperm_at(suf[K], J == 2 ? wl.lf1 + 4 : wl.lf1); }
+    template <int J, int K>
+    __device__ __forceinline__ T right() const { return bperm_at(pre[K], J == 2 ? wl.rf : wl.rf + 4); }
+    __device__ __forceinline__ void done() const {}
+};
 
 // The float64 quantities of the kernels wider than 15 exchange their partial sums through wave-private LDS LINES instead of
 // ds_bpermute (round 6).  A ds_bpermute_b32 moves 4 bytes per lane in 4 LDS-array cycles (2.6 ns of the CU's crossbar in
@@ -401,68 +340,89 @@ __device__ __forceinline__ void hsum_wide(const T (&V)[PX], T (&H)[PX], const Wi
 // 21 / 31 wide 5.27 / 5.54 / 6.66 -> 5.88 / 6.03 / 7.43: there the wave also holds a centre ring of kh / 2 + 1 rows in LDS, the
 // lines' 6.3 KB cost it three of ten resident waves per CU, and at three whole neighbour lanes 17 LDS operations replace 20.  So
 // the lines serve the builds that re-load both rows (RING 0: kernels taller than 39 rows, no LDS ring), ds_bpermute the others.
-// Same terms, same order of additions as hsum_wide: bit-identical results.  `line` = this lane's entry of line 0; every
-// line has WLINE_G guard entries either side that are never written: their readers are overlap lanes whose sums are discarded.
+// The lines are the second source of the one wide sum (hsum_wide): the same terms in the same order of additions as through the
+// crossbar BY CONSTRUCTION, hence bit-identical results.  `line` = this lane's entry of line 0; every line has WLINE_G guard
+// entries either side that are never written: their readers are overlap lanes whose sums are discarded.
 constexpr int WLINE_G = 26;                                 // >= F + 1 for every admitted width (overlap lanes <= 24: F <= 24)
 constexpr int WLINE_STRIDE = (WAVE + 2 * WLINE_G) * 8;      // bytes per line
 constexpr size_t WLINE_BYTES = 7 * (size_t)WLINE_STRIDE;    // 6.3 KB per wave
-#ifndef HK_WLINE
-#define HK_WLINE 1
-#endif
 template <int RW, int RING>
-constexpr bool use_wline() { return HK_WLINE && RW < 0 && RING == 0; }
-template <int E, bool PAIR = false>
-__device__ __forceinline__ void hsum_wide_line(const double (&V)[PX], double (&H)[PX], const WideLanes& wl, int lane, char* line) {
-    constexpr int RV = 2 * PX + E;
-    double pre[PX + 1], suf[PX + 1];
-    pre[1] = V[0];
-    pre[2] = V[0] + V[1];
-    pre[3] = pre[2] + V[2];
-    suf[1] = V[3];
-    suf[2] = V[2] + V[3];
-    suf[3] = V[1] + suf[2];
-    pre[4] = suf[4] = pre[2] + suf[2];
-    auto at = [&](const char* p, int array) -> double { return *reinterpret_cast<const double*>(p + array * WLINE_STRIDE); };
-    *reinterpret_cast<double*>(line) = pre[4];
+constexpr bool use_wline() { return RW < 0 && RING == 0; }
+// LDS operations of one wave execute in order: this keeps the compiler from moving a read of the lines across a write of them
+__device__ __forceinline__ void xch_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <bool PAIR>
+struct WideLines {
+    const WideLanes& wl;
+    char* const line;
+    const double *pre, *suf;
+    double tl, tr;  // paired form: T of the lanes next door (DPP)
+    __device__ __forceinline__ WideLines(const WideLanes& wl_, char* line_) : wl(wl_), line(line_) {}
+    static __device__ __forceinline__ double at(const char* p, int array) { return *reinterpret_cast<const double*>(p + array * WLINE_STRIDE); }
+    __device__ __forceinline__ void publish(const double (&pre_)[PX + 1], const double (&suf_)[PX + 1]) {
+        pre = pre_, suf = suf_;
+        *reinterpret_cast<double*>(line) = pre[4];
 #pragma unroll
-    for (int k = 1; k <= 3; ++k) {
-        *reinterpret_cast<double*>(line + k * WLINE_STRIDE) = suf[k];
-        *reinterpret_cast<double*>(line + (3 + k) * WLINE_STRIDE) = pre[k];
+        for (int k = 1; k <= 3; ++k) {
+            *reinterpret_cast<double*>(line + k * WLINE_STRIDE) = suf[k];
+            *reinterpret_cast<double*>(line + (3 + k) * WLINE_STRIDE) = pre[k];
+        }
+        xch_order();
+        if constexpr (PAIR) tl = dpp_from_left(pre[PX]), tr = dpp_from_right(pre[PX]);
     }
-    xch_order();
-    // the whole lanes: the same terms in the same order as hsum_wide (PAIR: pairs of neighbouring lanes, see there)
+    __device__ __forceinline__ double whole(int o) const { return at(line + o * 8, 0); }
+    __device__ __forceinline__ double pair_left1() const { return tl + pre[PX]; }
+    __device__ __forceinline__ double pair_right1() const { return tr + at(line + 2 * 8, 0); }
+    __device__ __forceinline__ double pair(int o) const { return at(line + o * 8, 0) + at(line + (o + 1) * 8, 0); }
+    template <int J, int K>
+    __device__ __forceinline__ double left() const { return at(line - (wl.f + J - 2) * 8, K == PX ? 0 : K); }
+    template <int J, int K>
+    __device__ __forceinline__ double right() const { return at(line + (wl.f + J - 2) * 8, K == PX ? 0 : 3 + K); }
+    // the next quantity rewrites the lines: every read has been issued (LDS operations of a wave run in order)
+    __device__ __forceinline__ void done() const { xch_order(); }
+};
+
+// The wide sum: the terms and the order of their additions, stated once for both sources.
+template <int E, bool PAIR, typename T, typename SRC>
+__device__ __forceinline__ void hsum_wide(const T (&V)[PX], T (&H)[PX], const WideLanes& wl, SRC src) {
+    constexpr int RV = 2 * PX + E;  // the virtual half-width whose lanes 2 and 3 stand for the lanes F and F + 1
+    T pre[PX + 1], suf[PX + 1];
+    own_partials(V, pre, suf);
+    src.publish(pre, suf);
+    // the lane's own four columns and the whole lanes (PAIR: see WideCrossbar; the launch made sure that W is odd and >= 3)
     constexpr bool FULL2 = lane_full_for_all(RV, 2);
-    double common = pre[PX];
+    T common = pre[PX];
     if constexpr (PAIR) {
         const int W = FULL2 ? wl.f : wl.f - 1;  // wave-uniform
-        const double tl = dpp_from_left(pre[PX]), tr = dpp_from_right(pre[PX]);
-        common = at(line + W * 8, 0);
-        common = common + (tl + pre[PX]);               // the pairs (-1, 0) and (1, 2)
-        common = common + (tr + at(line + 2 * 8, 0));
-        for (int o = 3; o <= W - 2; o += 2) common = common + (at(line + o * 8, 0) + at(line + (o + 1) * 8, 0));
-        for (int o = 3; o <= W; o += 2) common = common + (at(line - o * 8, 0) + at(line - (o - 1) * 8, 0));
+        // the single lane W, then the pairs (o, o + 1) for o = [-1], [1], 3, ..., W - 2, -3, ..., -W (in brackets: a DPP move away)
+        common = src.whole(W);
+        common = common + src.pair_left1();
+        common = common + src.pair_right1();
+        for (int o = 3; o <= W - 2; o += 2) common = common + src.pair(o);  // (wave-uniform trip counts)
+        for (int o = 3; o <= W; o += 2) common = common + src.pair(-o);
     } else {
-        if (wl.f >= 2) {  // wave-uniform
+        if (wl.f >= 2) {  // wave-uniform (F = 1: a tall kernel 9 - 15 wide on the everything-re-loaded path)
             common = common + dpp_from_left(pre[PX]);
             common = common + dpp_from_right(pre[PX]);
         }
         for (int j = 2; j < wl.f; ++j) {  // wave-uniform: the whole lanes beyond the DPP neighbours
-            common = common + at(line - j * 8, 0);
-            common = common + at(line + j * 8, 0);
+            common = common + src.whole(-j);
+            common = common + src.whole(j);
         }
     }
-    static_for<2, 4>([&](auto J) {
+    static_for<2, 4>([&](auto J) {  // the lanes F (j == 2) and F + 1 (j == 3) to the left / right
         constexpr int j = decltype(J)::value;
-        // the lanes F (j == 2) and F + 1 (j == 3) to the left / right
-        const char* const lb = line - (wl.f + j - 2) * 8;
-        const char* const rb = line + (wl.f + j - 2) * 8;
-        double ls[PX + 1], rp[PX + 1];
+        T ls[PX + 1], rp[PX + 1];
         static_for<1, PX + 1>([&](auto K) {
             constexpr int k = decltype(K)::value;
             if constexpr (PAIR && j == 2 && k == PX && FULL2) {
+                // (the lanes F as a whole: part of the pairs above)
             } else {
-                if constexpr (need_left_at(RV, j, k)) ls[k] = at(lb, k == PX ? 0 : k);
-                if constexpr (need_right_at(RV, j, k)) rp[k] = at(rb, k == PX ? 0 : 3 + k);
+                if constexpr (need_left_at(RV, j, k)) ls[k] = src.template left<j, k>();
+                if constexpr (need_right_at(RV, j, k)) rp[k] = src.template right<j, k>();
             }
         });
         if constexpr (lane_full_for_all(RV, j)) {
@@ -490,22 +450,22 @@ __device__ __forceinline__ void hsum_wide_line(const double (&V)[PX], double (&H
         if constexpr (specific_before(RV, i, 4, false, true)) H[i] = common + H[i];
         else H[i] = common;
     });
-    xch_order();  // the next quantity rewrites the lines: every read above has been issued (LDS operations of a wave run in order)
+    src.done();
 }
 
 // RW >= 0: compile-time half-width; RW = -1 - E: wide kernel with rw mod 4 == E (hsum_wide), RW = -5 - E: its paired form.  DPP2: see hsum.
-// `xch`: the lane's slot of the LDS exchange line (XCH builds of hsum; the float64 sums of the wide kernels: hsum_wide_line)
-template <int RW, typename T, bool XCH = false, bool DPP2 = false, bool WLINE = false>
-__device__ __forceinline__ void hsum_any(const T (&V)[PX], T (&H)[PX], const WideLanes& wl, int lane, char* xch = nullptr) {
+// WLINE, `line`: the float64 sums of the wide kernels through the LDS exchange lines (WideLines); the lane's entry of line 0
+template <int RW, typename T, bool DPP2 = false, bool WLINE = false>
+__device__ __forceinline__ void hsum_any(const T (&V)[PX], T (&H)[PX], const WideLanes& wl, int lane, char* line = nullptr) {
     if constexpr ((HK_ABLATE & 4) != 0) {
 #pragma unroll
         for (int i = 0; i < PX; ++i) H[i] = V[i];
     } else if constexpr (RW >= 0)
-        hsum<RW, T, XCH, DPP2>(V, H, lane, xch);
-    else if constexpr (WLINE && std::is_same<T, double>::value) {
-        hsum_wide_line<wide_e(RW), wide_paired(RW)>(V, H, wl, lane, xch);
-    } else
-        hsum_wide<wide_e(RW), T, wide_paired(RW)>(V, H, wl, lane);
+        hsum<RW, T, DPP2>(V, H, lane);
+    else if constexpr (WLINE && std::is_same<T, double>::value)
+        hsum_wide<wide_e(RW), wide_paired(RW)>(V, H, wl, WideLines<wide_paired(RW)>(wl, line));
+    else
+        hsum_wide<wide_e(RW), wide_paired(RW)>(V, H, wl, WideCrossbar<T, wide_paired(RW)>(wl, lane));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -544,13 +504,11 @@ __device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elemen
 //     q  = n * y1                  <= 2^-44 + 2^-52 relative = 513 float64 ulps of q at most
 // RN64(n / d) lies within 514 ulps of q, so both round to the same float32 unless one of its rounding boundaries (the
 // midpoints of neighbouring float32 values: low 29 mantissa bits == 0x10000000) lies within 514 ulps of q.  quot_guard()
-// maps q to a word that is < 2 * HK_DIV_GUARD + 1 exactly when q is that close (probability 2^-18 per pixel); such a
+// maps q to a word that is < 2 * DIV_GUARD + 1 exactly when q is that close (probability 2^-18 per pixel); such a
 // pixel pair -- and one with a quotient outside the float32 normal range (every infinite / NaN / zero-denominator case;
 // an exactly zero quotient is exempt, it is exact) -- is divided again the IEEE way, so results are identical by
 // construction.
-#ifndef HK_DIV_GUARD
-#define HK_DIV_GUARD 1024u
-#endif
+constexpr unsigned DIV_GUARD = 1024u;
 __device__ __forceinline__ double fast_quot(double n, double d) {
     double y = __builtin_amdgcn_rcp(d);
     const double e = __fma_rn(-d, y, 1.0);
@@ -558,7 +516,7 @@ __device__ __forceinline__ double fast_quot(double n, double d) {
     return __dmul_rn(n, y);
 }
 __device__ __forceinline__ unsigned quot_guard(double q) {
-    return ((unsigned)__double2loint(q) & 0x1fffffffu) - (0x10000000u - HK_DIV_GUARD);
+    return ((unsigned)__double2loint(q) & 0x1fffffffu) - (0x10000000u - DIV_GUARD);
 }
 // biased float64 exponent of q relative to that of 2^-126: <= 0x0fd00000 exactly for |q| in [2^-126, 2^128), and 0 for a
 // zero / float64-denormal q (num == 0 or an underflowing quotient: the IEEE quotient rounds to the same signed float32 zero)
@@ -639,9 +597,7 @@ constexpr unsigned RING_SENTINEL = 0x7fc0deadu;
 // Tall kernels re-load the leaving row from global memory (ring modes 2 / 0): that is the row's LAST use, so the re-load is
 // non-temporal -- it no longer displaces the rows still waiting for theirs (gain-blk-offset 15x15 x 8 bands at 16384^2:
 // 11.09 -> 10.37 ms; gain-offset 15x15 -0.6 %).  Entering rows stay cached: the neighbouring strips and the re-load need them.
-#ifndef HK_NT_LEAVE
-#define HK_NT_LEAVE true
-#endif
+constexpr bool NT_LEAVE = true;  // load_row<NT>: the re-load of a leaving row
 template <bool NT = false, bool SB = false>
 __device__ __forceinline__ RowRaw load_row(const float* __restrict__ sp, const float* __restrict__ rp, long long stride,
                                            int row, int height, unsigned xq) {
@@ -813,15 +769,9 @@ struct ColSums {
 // ---------------------------------------------------------------------------------------------------------------------
 // The fused kernel.  MODEL: 0 gain, 1 gain-blk-offset, 2 gain-offset.  R2: compute the R2 quantity set.
 // RW: compile-time kernel half-width, or -1 - E for the kernels wider than 15 whose half-width is 4 F + E (F run-time, hsum_wide).  DENSE: both inputs have nodata None.
-#ifndef HK_CERT_SKIP
-#define HK_CERT_SKIP 3  // rows for which the r2-mask certificate is not attempted after it failed (measured)
-#endif
-#ifndef HK_FIT_MIN_WAVES_WIDE
-#define HK_FIT_MIN_WAVES_WIDE 2  // the general gain-offset + R2 kernels of width >= 9 spill at 3 waves per SIMD
-#endif
-#ifndef HK_FIT_MIN_WAVES
-#define HK_FIT_MIN_WAVES 3  // waves per SIMD the register allocator must leave room for (tuned on MI355X)
-#endif
+constexpr int CERT_SKIP = 3;           // rows for which the r2-mask certificate is not attempted after it failed (measured)
+constexpr int FIT_MIN_WAVES_WIDE = 2;  // the general gain-offset + R2 kernels of width >= 9 spill at 3 waves per SIMD
+constexpr int FIT_MIN_WAVES = 3;       // waves per SIMD the register allocator must leave room for (tuned on MI355X)
 // RING: where the leaving row (t - kh) and the window's centre row (t - rh) come from:
 //   1  both from a wave-private LDS ring of kh processed rows (short kernels, kh <= 5);
 //   2  centre row from an LDS ring of rh + 1 rows holding only `s` + mask (20 B per lane-row), leaving row re-loaded from
@@ -833,50 +783,22 @@ struct ColSums {
 //      row (mode 2 moves 20 instead of 12 bytes per pixel through the fabric at 15x15) with 16 KB instead of 30 KB of LDS per
 //      wave.  The row that leaves the registers IS the window's centre row, so the centre needs no LDS read either.
 // WPB = waves per workgroup.  The memory-bound builds with a full LDS ring (gain, gain-blk-offset without R2, short kernels)
-// put HK_WPB_MEM ADJACENT STRIPS of one segment into a workgroup and keep them in lock-step with a barrier per row: the
+// put WPB_MEM ADJACENT STRIPS of one segment into a workgroup and keep them in lock-step with a barrier per row: the
 // workgroup then reads and writes 4 KB of every row together instead of 1 KB per wave at unrelated times, which the HBM
 // pays back -- strip-march pattern without arithmetic 4 720 -> 4 910 GB/s (tools/ubench_strips.hip); gain 5x5 at 16384^2
 // 2.70 -> 2.55 ms, gain-blk-offset 5x5 4.57 -> 4.34 ms (8 waves: 2.51 / 4.38; configs[1]'s smaller raster prefers 4).
 // Not for the VALU-bound gain-offset builds with the R2 work (their waves would only wait for each other: 0 to +2 %) and not for the tall
 // kernels that re-load their leaving rows (15x15: +14 %, the re-loads of a whole workgroup then collide).
-#ifndef HK_WPB_MEM
-#define HK_WPB_MEM 4
-#endif
-// Which float64 horizontal sums exchange their partial sums through LDS (hsum's XCH) instead of DPP: bit 0 S, 1 R, 2 P,
-// 3 S2, 4 R2.  One 16-byte slot per lane + one at each end = XCH_BYTES per wave behind the row rings.
-#ifndef HK_XCH
-#define HK_XCH 0
-#endif
-// (HK_SRING_MAX / HK_SRING_MAX_BLK, hk_kernels.h: register rows of the split ring -- 7 = kernels up to 15 rows tall; the
+constexpr int WPB_MEM = 4;
+// (SPLIT_RING_ROWS / SPLIT_RING_ROWS_BLK, hk_kernels.h: register rows of the split ring -- 7 = kernels up to 15 rows tall; the
 // gain-blk-offset builds use the mode up to 11 rows only (hk_api.hip fill_args) and hold 5: 16 VGPRs less, no spill)
-#ifndef HK_CERT_R2_F32
-#define HK_CERT_R2_F32 1
-#endif
-constexpr size_t XCH_BYTES = (WAVE + 2) * 16;
-template <int MODEL, int RW, int RING, int WPB>
-constexpr int xch_mask() {
-    return (MODEL == 2 && (RW == 1 || RW == 2) && RING == 1 && WPB == 1) ? HK_XCH : 0;
-}
 
 // Waves per SIMD the register allocator has to leave room for.  Four for the certificate-only build of the narrow kernels (128
 // VGPRs), three (168 VGPRs) by default -- and two (256 VGPRs) for the builds that do not fit into 168 without spilling to
-// scratch memory (HK_NOSPILL; tools/kernel_regs.py --spills lists none with it): the wide NaN-aware builds with the R2 work
+// scratch memory (tools/kernel_regs.py --spills lists none): the wide NaN-aware builds with the R2 work
 // and the NaN-aware split-ring builds of `gain` -- measured equal or 10-15 % FASTER at two waves, profiles/r04_nospill.txt.  Where
 // two waves were slower the registers were found elsewhere: gain-blk-offset's split ring holds 5 instead of 7 rows (it serves
 // kernels up to 11 rows), the certificate-only builds of the kernels wider than 15 give up their leaving row in flight (PF_OLD).
-#ifndef HK_NOSPILL
-#define HK_NOSPILL 1
-#endif
-#ifndef HK_CERT_WIDE_3WAVES
-#define HK_CERT_WIDE_3WAVES 1
-#endif
-// rows in flight of the kernels wider than 15: HK_PF_WIDE entering, HK_PO_WIDE leaving (see fit_unit; 1 / 1 measured best)
-#ifndef HK_PF_WIDE
-#define HK_PF_WIDE 1
-#endif
-#ifndef HK_PO_WIDE
-#define HK_PO_WIDE 1
-#endif
 template <int MODEL, bool R2, int RW, bool DENSE, int RING, bool CERT_ONLY>
 constexpr int fit_min_waves() {
     if (CERT_ONLY && RW >= 0 && RW <= 3) return 4;
@@ -884,23 +806,24 @@ constexpr int fit_min_waves() {
     // equal.  Beyond 15 wide with kw / 2 mod 4 = 1 .. 3 they were two registers short -- a loop-invariant 64-bit vector address pair
     // per plane -- and take their row addresses as opaque scalars since round 6 (row_address, fit_scalar_bases): 19 / 21 / 23 wide
     // on NaN-nodata rasters 6.45 -> 5.78 ms, 31 wide 7.1 -> 6.9, profiles/r06b_ab_scalar_base.txt)
-    if (MODEL == 2 && R2 && !DENSE && (RW < 0 || RW >= 4) && !(CERT_ONLY && HK_CERT_WIDE_3WAVES && RW < 0)) return HK_FIT_MIN_WAVES_WIDE;
-    if (HK_NOSPILL) {
-        // (round 6: with the LDS exchange lines the compiler issues a quantity's neighbour reads together -- 8 to 25 registers more
-        // at the peak -- in the builds that use them: kernels taller than 39 rows)
-        if (use_wline<RW, RING>() && MODEL == 2) return 2;
-        if (RW < 0 && (HK_PF_WIDE > 1 || HK_PO_WIDE > 1)) return 2;  // (rows in flight instead of a third wave: see fit_unit)
-        if (RW < 0 && R2 && !CERT_ONLY) return 2;                          // wider than 15 with the R2 work (10 - 28 spilled registers at three)
-        if (MODEL == 2 && R2 && !DENSE && RW == 3) return 2;               // gain-offset + R2, 7 wide, NaN-aware
-        if (MODEL != 2 && R2 && !DENSE && RW >= 4 && RING == 2) return 2;  // gain / gain-blk-offset + R2, 9-15 wide, NaN-aware
-        // gain, NaN-aware split ring: 15 wide stays at two waves (175 registers); 11 / 13 wide take their row addresses as opaque
-        // scalars (fit_scalar_bases) and fit three: 3.33 -> 3.05 / 3.52 -> 3.40 ms on NaN-nodata rasters -- at 15 rows the ring's
-        // 16 KB allow ten waves per CU whatever the registers say and the tighter allocation ran 2 % slower
-        // (profiles/r06b_scalar_base.txt)
-        if (RING == 3 && !DENSE && MODEL == 0 && RW == 7) return 2;
-    }
-    return HK_FIT_MIN_WAVES;
+    if (MODEL == 2 && R2 && !DENSE && (RW < 0 || RW >= 4) && !(CERT_ONLY && RW < 0)) return FIT_MIN_WAVES_WIDE;
+    // (round 6: with the LDS exchange lines the compiler issues a quantity's neighbour reads together -- 8 to 25 registers more
+    // at the peak -- in the builds that use them: kernels taller than 39 rows)
+    if (use_wline<RW, RING>() && MODEL == 2) return 2;
+    if (RW < 0 && R2 && !CERT_ONLY) return 2;                          // wider than 15 with the R2 work (10 - 28 spilled registers at three)
+    if (MODEL == 2 && R2 && !DENSE && RW == 3) return 2;               // gain-offset + R2, 7 wide, NaN-aware
+    if (MODEL != 2 && R2 && !DENSE && RW >= 4 && RING == 2) return 2;  // gain / gain-blk-offset + R2, 9-15 wide, NaN-aware
+    // gain, NaN-aware split ring: 15 wide stays at two waves (175 registers); 11 / 13 wide take their row addresses as opaque
+    // scalars (fit_scalar_bases) and fit three: 3.33 -> 3.05 / 3.52 -> 3.40 ms on NaN-nodata rasters -- at 15 rows the ring's
+    // 16 KB allow ten waves per CU whatever the registers say and the tighter allocation ran 2 % slower
+    // (profiles/r06b_scalar_base.txt)
+    if (RING == 3 && !DENSE && MODEL == 0 && RW == 7) return 2;
+    return FIT_MIN_WAVES;
 }
+
+// rows in flight of the light `gain` kernel (fit_unit): 4 and 6 rows measured the same (2.91-2.97 ms): the wait is on the LDS ring,
+// not on HBM latency
+constexpr int PF_GAIN = 2;
 
 // One unit of the fused kernel: the strip `strip` of band `band`, output rows [y0, y1) (priming rows included, the wave marches
 // from y0 - rh).  LIST: the unit is a run of a list launch -- rows that are not marked in FitArgs::open_rows are neither stored
@@ -944,21 +867,16 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
     // One row in flight: the next row's load is issued as soon as the current one has been consumed, so it lands in the
     // same registers (no queue rotation).  A two-row queue was measured equal or slower (8 more VGPRs + 8 moves per row).
     // The light `gain` kernel without R2 is HBM-bound (VALU 37 % busy, ~3 waves per SIMD because of the LDS ring): it keeps
-    // HK_PF_GAIN rows in flight in a small register queue (moves are free there).
-#ifndef HK_PF_GAIN
-#define HK_PF_GAIN 2  // 4 and 6 rows measured the same (2.91-2.97 ms): the wait is on the LDS ring, not on HBM latency
-#endif
-#ifndef HK_PF_BLKA
-#define HK_PF_BLKA 1  // gain-blk-offset: 2 / 3 / 4 rows in flight measured the same at 15x15 (profiles/r03_blk15_ablation.txt)
-#endif
+    // PF_GAIN rows in flight in a small register queue (moves are free there).  gain-blk-offset keeps one: 2 / 3 / 4 rows in
+    // flight measured the same at 15x15 (profiles/r03_blk15_ablation.txt).
     // Kernels wider than 15 (round 6, profiles/r06_pmcl_k31.txt): at 31 x 31 a wave spends 37 % of its life in s_waitcnt and 19 % in
     // issue stalls with the VALU 22 % and the LDS array 45 % busy, and 82 % of its L2 requests go on to the fabric.  More rows in
-    // flight per wave (register queues of HK_PF_WIDE entering / HK_PO_WIDE leaving rows, two waves per SIMD for the registers) do
+    // flight per wave (register queues of entering and of leaving rows, two waves per SIMD for the registers) do
     // NOT buy that time back: 2 / 2, 3 / 3, 4 / 4 and 3 / 1 rows all measured 5 - 15 % slower than one row each at three waves
     // (profiles/r06_ab_prefetch.txt) -- the third wave covers more latency than the queues.  What did pay: the certificate builds of
     // these widths now fetch their leaving row one iteration ahead like the others (it fits since the build lost its gain / R2
     // stores): 17 / 21 / 31 wide 5.27 / 5.54 / 6.66 -> 4.94 / 5.23 / 6.22 ms.
-    constexpr int PFD = (MODEL == 0 && !R2) ? HK_PF_GAIN : ((MODEL == 1 && !R2) ? HK_PF_BLKA : (RW < 0 ? HK_PF_WIDE : 1));
+    constexpr int PFD = (MODEL == 0 && !R2) ? PF_GAIN : 1;  // entering rows in flight
     RowRaw q0 = load_row<false, SB>(sp, rp, a.stride, t_first, H, xq);
     [[maybe_unused]] RowRaw qq[PFD > 1 ? PFD - 1 : 1];
     if constexpr (PFD > 1) {
@@ -1004,16 +922,15 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
     // RING 1: [slot][s|r][lane]; RING 2: [slot][lane] (s only); one ring per wave of the workgroup
     float4* ring_v = lds4 + (size_t)wave_in_wg * (size_t)(ring_rows * (ring2p ? 2 : 1) * WAVE);
     // slots start as rows that were never added: zero contribution, no valid pixel
-    constexpr int XCH = xch_mask<MODEL, RW, RING, WPB>();
     // The 15-wide builds of `gain` and gain-offset fetch their distance-2 neighbours through two chained DPP shifts instead of
     // ds_bpermute (hsum DPP2): 15 x 15 gain-offset + r2 mask 4.51 -> 4.44 ms dense, 4.96 -> 4.61 on NaN-nodata rasters, 5.91 -> 5.51
     // with scattered holes, `gain` 3.08 -> 2.99; 9 - 13 wide equal or 2 % slower, gain-blk-offset (VALU-bound) 1 % slower: not those
     // (profiles/r05_ab_dpp2_15wide.txt).  Kernels wider than 15 gain nothing from the same exchange (profiles/r05_ab_dpp_chain_wide.txt:
     // at 31 wide the launch moves 2.16 x its algorithmic bytes through the HBM -- the re-loaded leaving rows -- and is bound there).
-    constexpr bool DPPX = HK_DPP2 && RW == 7 && MODEL != 1;
-    // (kernels wider than 15: the lane's entry of the wave's first exchange line, hsum_wide_line; one wave per workgroup there)
-    [[maybe_unused]] char* const xch = reinterpret_cast<char*>(lds4 + (size_t)WPB * (size_t)(ring_rows * (ring2p ? 2 : 1) * WAVE)) +
-                                       (RW < 0 ? (size_t)(lane + WLINE_G) * 8 : (size_t)wave_in_wg * XCH_BYTES + 16 + (size_t)lane * 16);
+    constexpr bool DPPX = RW == 7 && MODEL != 1;
+    // (kernels wider than 15: the lane's entry of the wave's first exchange line, WideLines; one wave per workgroup there)
+    [[maybe_unused]] char* const wline = reinterpret_cast<char*>(lds4 + (size_t)WPB * (size_t)(ring_rows * (ring2p ? 2 : 1) * WAVE)) +
+                                         (size_t)(lane + WLINE_G) * 8;
     const float ring_init = DENSE ? 0.f : __uint_as_float(RING_SENTINEL);
     {
         // four registers the compiler must treat as unrelated: one ds_write_b128 per slot and plane (the vectorised form of this
@@ -1081,11 +998,8 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
     const double* __restrict__ inv_lut = HK_INV_N.v;
     // General gain-offset builds of the narrow kernels: window counts <= 63 are looked up in a LANE-resident copy of the table
     // (lane n holds RN64(1/n); two ds_bpermute per pixel) instead of a global-memory gather whose latency sits in every
-    // wave-row that has a hole in reach (HK_LANE_LUT, profiles/r03_lane_lut.txt).
-#ifndef HK_LANE_LUT
-#define HK_LANE_LUT 1
-#endif
-    constexpr bool LANE_LUT = HK_LANE_LUT && GO && !DENSE && RW >= 0 && RW <= 3;
+    // wave-row that has a hole in reach (profiles/r03_lane_lut.txt).
+    constexpr bool LANE_LUT = GO && !DENSE && RW >= 0 && RW <= 3;
     [[maybe_unused]] const bool lane_lut = LANE_LUT && lut_ok && kh * (2 * rw + 1) <= WAVE - 1;  // wave-uniform
     [[maybe_unused]] double lut_lane = 0.0;
     if constexpr (LANE_LUT) lut_lane = inv_lut[lane];
@@ -1127,17 +1041,9 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
     // gain-offset kernels, which would spill)
     // (the builds of the kernels wider than 15 with the R2 work run at two waves per SIMD -- fit_min_waves -- and have the registers)
     // ... and so do, since round 6, their certificate builds at three waves)
-    constexpr bool PF_OLD = !ring && !sring && (DENSE || MODEL != 2 || (RW < 0 && R2)) && !(RW < 0 && CERT_ONLY && HK_PO_WIDE < 1);
-    constexpr int POD = PF_OLD ? (RW < 0 ? (HK_PO_WIDE > 1 ? HK_PO_WIDE : 1) : 1) : 0;  // leaving rows in flight
+    constexpr bool PF_OLD = !ring && !sring && (DENSE || MODEL != 2 || (RW < 0 && R2));
     [[maybe_unused]] RowRaw qo_next;
-    [[maybe_unused]] RowRaw qoq[POD > 1 ? POD - 1 : 1];
-    if constexpr (PF_OLD) {
-        qo_next = load_row<HK_NT_LEAVE, SB>(sp, rp, a.stride, t_first - kh, H, xq);
-        if constexpr (POD > 1) {
-#pragma unroll
-            for (int d = 1; d < POD; ++d) qoq[d - 1] = load_row<HK_NT_LEAVE, SB>(sp, rp, a.stride, t_first - kh + d, H, xq);
-        }
-    }
+    if constexpr (PF_OLD) qo_next = load_row<NT_LEAVE, SB>(sp, rp, a.stride, t_first - kh, H, xq);
     // RING 1: the first leaving row is the zero row the ring was initialised with
     [[maybe_unused]] RowZ zold_next;
 #pragma unroll
@@ -1170,16 +1076,9 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
         if constexpr (PF_OLD) {
             // the leaving row is fetched one iteration ahead (it comes from L2 / the Infinity Cache): qo_next holds row t_old
             qo = qo_next;
-            if constexpr (POD > 1) {
-                qo_next = qoq[0];
-#pragma unroll
-                for (int d = 1; d < POD - 1; ++d) qoq[d - 1] = qoq[d];
-                qoq[POD - 2] = load_row<HK_NT_LEAVE, SB>(sp, rp, a.stride, t_old + POD, H, xq);
-            } else {
-                qo_next = load_row<HK_NT_LEAVE, SB>(sp, rp, a.stride, (HK_ABLATE & 1) ? t + 1 : t_old + 1, H, xq);
-            }
+            qo_next = load_row<NT_LEAVE, SB>(sp, rp, a.stride, (HK_ABLATE & 1) ? t + 1 : t_old + 1, H, xq);
         } else if constexpr (!ring && !sring) {
-            qo = load_row<HK_NT_LEAVE, SB>(sp, rp, a.stride, t_old, H, xq);
+            qo = load_row<NT_LEAVE, SB>(sp, rp, a.stride, t_old, H, xq);
         }
         if constexpr (RING == 0) qc = load_row<false, SB>(sp, rp, a.stride, y_c, H, xq);
 
@@ -1294,13 +1193,13 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
             // one of those float64 quadruples is live beside S2 / R2 (12-16 VGPRs less at the pressure peak)
             double HS[PX], HR[PX];
             [[maybe_unused]] float Sf0[PX], Rf0[PX], Pf0[PX];
-            hsum_any<RW, double, (XCH & 1) != 0, DPPX, use_wline<RW, RING>()>(cs.S, HS, wl, lane, xch);
+            hsum_any<RW, double, DPPX, use_wline<RW, RING>()>(cs.S, HS, wl, lane, wline);
             if constexpr (GO) {
 #pragma unroll
                 for (int i = 0; i < PX; ++i) Sf0[i] = (float)HS[i];
                 __builtin_amdgcn_sched_barrier(0);
             }
-            hsum_any<RW, double, (XCH & 2) != 0, DPPX, use_wline<RW, RING>()>(cs.R, HR, wl, lane, xch);
+            hsum_any<RW, double, DPPX, use_wline<RW, RING>()>(cs.R, HR, wl, lane, wline);
             if constexpr (GO) {
 #pragma unroll
                 for (int i = 0; i < PX; ++i) Rf0[i] = (float)HR[i];
@@ -1308,29 +1207,25 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
             }
             double HP[PX], HS2[PX], HR2[PX];
             float Nf[PX];
-            if constexpr (CS::NEED_P) hsum_any<RW, double, (XCH & 4) != 0, DPPX, use_wline<RW, RING>()>(cs.P, HP, wl, lane, xch);
+            if constexpr (CS::NEED_P) hsum_any<RW, double, DPPX, use_wline<RW, RING>()>(cs.P, HP, wl, lane, wline);
             if constexpr (GO) {
 #pragma unroll
                 for (int i = 0; i < PX; ++i) Pf0[i] = (float)HP[i];
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (CS::NEED_S2) hsum_any<RW, double, (XCH & 8) != 0, DPPX, use_wline<RW, RING>()>(cs.S2, HS2, wl, lane, xch);
+            if constexpr (CS::NEED_S2) hsum_any<RW, double, DPPX, use_wline<RW, RING>()>(cs.S2, HS2, wl, lane, wline);
             // Certificate-only build: the window sum of ref^2 feeds nothing but the float32 r2-mask certificate, so its
             // horizontal stage runs in float32 on the rounded column sums (non-negative terms: <= 5 roundings, relative
             // error <= 4.03 * 2^-24 instead of 2^-24 -- DESIGN.md appendix A budgets it): four converts + nine float32 adds,
             // the neighbours' values as DPP operands, instead of nine float64 adds + eight DPP moves + four converts
             [[maybe_unused]] float HR2f[PX];
-            if constexpr (CS::NEED_R2S && CERT_ONLY && HK_CERT_R2_F32) {
+            if constexpr (CS::NEED_R2S && CERT_ONLY) {
                 float V2[PX];
 #pragma unroll
                 for (int i = 0; i < PX; ++i) V2[i] = (float)cs.R2s[i];
-                hsum_any<RW, float, false, DPPX>(V2, HR2f, wl, lane);
+                hsum_any<RW, float, DPPX>(V2, HR2f, wl, lane);
             } else if constexpr (CS::NEED_R2S) {
-                hsum_any<RW, double, (XCH & 16) != 0, DPPX, use_wline<RW, RING>()>(cs.R2s, HR2, wl, lane, xch);
-                if constexpr (CERT_ONLY) {
-#pragma unroll
-                    for (int i = 0; i < PX; ++i) HR2f[i] = (float)HR2[i];
-                }
+                hsum_any<RW, double, DPPX, use_wline<RW, RING>()>(cs.R2s, HR2, wl, lane, wline);
             }
             if constexpr (USE_N) {
                 if constexpr (DENSE) {
@@ -1346,7 +1241,7 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
                         for (int i = 0; i < PX; ++i) Nf[i] = a.n_full;
                     } else {
                         bool packed = false;
-                        if constexpr (HK_PACKED_NSUM && RW >= 1 && RW <= 3) {
+                        if constexpr (RW >= 1 && RW <= 3) {
                             if (kh * (2 * rw + 1) <= 255) {  // wave-uniform: every window count fits a byte
                                 // the four column counts travel and add as the bytes of one word: the 2 * RW + 1 shifted views
                                 // of the 12 columns (left lane | own | right lane) are v_alignbyte_b32 of neighbouring words,
@@ -1366,7 +1261,7 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
                             const int VN[PX] = {(int)(cs.N & 0xffu), (int)((cs.N >> 8) & 0xffu), (int)((cs.N >> 16) & 0xffu),
                                                 (int)(cs.N >> 24)};
                             int HN[PX];
-                            hsum_any<RW, int, false, DPPX>(VN, HN, wl, lane);
+                            hsum_any<RW, int, DPPX>(VN, HN, wl, lane);
 #pragma unroll
                             for (int i = 0; i < PX; ++i) Nf[i] = (float)HN[i];
                         }
@@ -1422,7 +1317,7 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
                             // operands are still in registers.  The certificate build leaves the range test to its certificate,
                             // which passes gains inside (2^-20, 2^20) only and has no other consumer of the rest (their rows are
                             // marked for the list launch).
-                            bool again = min(quot_guard(qx), quot_guard(qy)) < 2u * HK_DIV_GUARD + 1u;
+                            bool again = min(quot_guard(qx), quot_guard(qy)) < 2u * DIV_GUARD + 1u;
                             if constexpr (!CERT_ONLY) again |= max(quot_range(qx), quot_range(qy)) > 0x0fd00000u;
                             if (again) {
                                 g2.x = (float)__ddiv_rn((double)num2.x, denx);
@@ -1518,7 +1413,7 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
                             ssum = __dadd_rn(__dmul_rn(n0, HS[i]), UN ? n1_n_full : __dmul_rn(n1, (double)Nf[i]));
                         const double q = (HK_ABLATE & 2) ? __dadd_rn((double)Rf[i], ssum) : fast_quot((double)Rf[i], ssum);
                         gp[i] = (float)q;
-                        if ((quot_guard(q) < 2u * HK_DIV_GUARD + 1u) | (quot_range(q) > 0x0fd00000u))
+                        if ((quot_guard(q) < 2u * DIV_GUARD + 1u) | (quot_range(q) > 0x0fd00000u))
                             gp[i] = (float)__ddiv_rn((double)Rf[i], ssum);
                         o[i] = (float)__dmul_rn((double)gp[i], n1);
                         g[i] = (float)__dmul_rn((double)gp[i], n0);
@@ -1541,7 +1436,7 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
                         if constexpr (GO) {
                             if (try_cert) {
                                 exact = __any(uncertain & out_lane);
-                                if (!CERT_ONLY && exact) cert_skip = HK_CERT_SKIP;  // failing regions are coherent: skip the certificate for a few rows
+                                if (!CERT_ONLY && exact) cert_skip = CERT_SKIP;  // failing regions are coherent: skip the certificate for a few rows
                                 if (!exact) {  // every valid pixel of the wave-row is certified: the failing ones are known
                                     passed &= ~cert_failed;
                                     if (out_lane) nfail += (unsigned)__popc(cert_failed & 0x01010101u);
@@ -1913,12 +1808,11 @@ template <int MODEL, bool R2, int RW, bool DENSE, int RING, bool CERT_ONLY>
 static hipError_t launch_build(const FitArgs& a, hipStream_t stream) {
     const size_t lds = fit_lds_bytes_of(2 * a.rh + 1, RING, RING == 1 && MODEL != 2 && !R2);
     // every build without the R2 work (gain-offset without a threshold gains 3 % as well: 2.77 -> 2.68 ms)
-    constexpr bool LOCKSTEP = !R2 && RING == 1 && HK_WPB_MEM > 1;
+    constexpr bool LOCKSTEP = !R2 && RING == 1 && WPB_MEM > 1;
     if constexpr (LOCKSTEP) {
-        if (lds * HK_WPB_MEM <= 64 * 1024) return launch_wpb<MODEL, R2, RW, DENSE, RING, CERT_ONLY, HK_WPB_MEM>(a, lds, stream);
+        if (lds * WPB_MEM <= 64 * 1024) return launch_wpb<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB_MEM>(a, lds, stream);
     }
-    if constexpr (RW < 0) return launch_wpb<MODEL, R2, RW, DENSE, RING, CERT_ONLY, 1>(a, lds + (use_wline<RW, RING>() ? WLINE_BYTES : 0), stream);
-    return launch_wpb<MODEL, R2, RW, DENSE, RING, CERT_ONLY, 1>(a, lds + (xch_mask<MODEL, RW, RING, 1>() ? XCH_BYTES : 0), stream);
+    return launch_wpb<MODEL, R2, RW, DENSE, RING, CERT_ONLY, 1>(a, lds + (use_wline<RW, RING>() ? WLINE_BYTES : 0), stream);
 }
 
 // gain-offset with the r2 mask exists in two builds.  The FULL one carries the reference's R2 expression inline for the

@@ -64,7 +64,7 @@ struct FitJob {
     int height, width, n_bands;
     int seg_rows, n_strips, n_segs, seg_rows_tail, n_segs_big;
     int out_y0, out_y1, out_x0, out_x1;
-    int first_group[2];  // first workgroup of the job in the launch: [0] one strip per workgroup, [1] HK_WPB_MEM strips (lock-step builds)
+    int first_group[2];  // first workgroup of the job in the launch: [0] one strip per workgroup, [1] WPB_MEM strips (lock-step builds)
     int pad_;
 };
 static_assert(sizeof(FitJob) % 8 == 0, "FitJob entries are read with scalar loads");
@@ -73,7 +73,7 @@ static_assert(sizeof(FitJob) % 8 == 0, "FitJob entries are read with scalar load
 struct FitArgs {
     const FitJob* jobs;     // batched launch: n_jobs entries (device), else NULL -- the fields below then describe the one job
     int n_jobs;
-    int batch_groups[2];    // batched launch: workgroups of all jobs, [0] one strip per workgroup, [1] HK_WPB_MEM strips
+    int batch_groups[2];    // batched launch: workgroups of all jobs, [0] one strip per workgroup, [1] WPB_MEM strips
     const float* src;
     const float* ref;
     float* gain;
@@ -161,7 +161,7 @@ constexpr bool fit_batch_build(int model, bool with_r2) { return model == 1 && !
 bool fit_batch_supported(int model, bool with_r2);
 // stage stamps of a -DHK_STAMPS build of the fused kernel (all zero otherwise): 16 counters, optionally cleared after reading
 hipError_t read_stamps(unsigned long long* out16, bool reset);
-// strips per workgroup of the lock-step builds (HK_WPB_MEM): FitJob::first_group[1] / FitArgs::batch_groups[1] count those
+// strips per workgroup of the lock-step builds (WPB_MEM): FitJob::first_group[1] / FitArgs::batch_groups[1] count those
 int fit_lockstep_waves();
 // LDS bytes one wave needs (its row ring; hk_fit_kernel.h)
 size_t fit_lds_bytes(int kh, int ring_mode, bool ahead);
@@ -180,13 +180,8 @@ struct NormPlane {
     int height, width;
 };
 // Register rows of the split ring (ring mode 3 of the fused kernel) a build holds = the largest kernel half-height it serves.
-#ifndef HK_SRING_MAX
-#define HK_SRING_MAX 7
-#endif
-#ifndef HK_SRING_MAX_BLK
-#define HK_SRING_MAX_BLK 5
-#endif
-__host__ __device__ constexpr int split_ring_rows(int model) { return model == 1 ? HK_SRING_MAX_BLK : HK_SRING_MAX; }
+constexpr int SPLIT_RING_ROWS = 7, SPLIT_RING_ROWS_BLK = 5;  // (_BLK: the gain-blk-offset builds)
+__host__ __device__ constexpr int split_ring_rows(int model) { return model == 1 ? SPLIT_RING_ROWS_BLK : SPLIT_RING_ROWS; }
 
 struct NormArgs {
     const NormPlane* planes = nullptr;  // batched launch: n_bands entries (device), else NULL -- the planes are then src/ref + band * band_stride

@@ -91,7 +91,7 @@ hipError_t launch_fit_apply(const FitArgs& a, int model, bool with_r2, hipStream
     return hipErrorInvalidValue;
 }
 
-int fit_lockstep_waves() { return HK_WPB_MEM; }
+int fit_lockstep_waves() { return WPB_MEM; }
 bool fit_batch_supported(int model, bool with_r2) { return fit_batch_build(model, with_r2); }
 size_t fit_lds_bytes(int kh, int ring_mode, bool ahead) { return fit_lds_bytes_of(kh, ring_mode, ahead); }
 
@@ -305,8 +305,8 @@ __device__ int hsum_wide_check(int lane) {
         if (wide_pairs(E, f)) {   // (both forms where the width allows the paired one: the same sums)
             double Hp[PX];
             int Hpi[PX];
-            hsum_wide<E, double, true>(V, Hp, wl, lane);
-            hsum_wide<E, int, true>(Vi, Hpi, wl, lane);
+            hsum_wide<E, true>(V, Hp, wl, WideCrossbar<double, true>(wl, lane));
+            hsum_wide<E, true>(Vi, Hpi, wl, WideCrossbar<int, true>(wl, lane));
             if (lane >= ol && lane < WAVE - ol)
                 for (int i = 0; i < PX; ++i) {
                     int ei = 0;
@@ -315,8 +315,8 @@ __device__ int hsum_wide_check(int lane) {
                     if (Hpi[i] != ei || Hp[i] != ed) bad = 1;
                 }
         }
-        hsum_wide<E, double>(V, Hd, wl, lane);
-        hsum_wide<E, int>(Vi, Hi, wl, lane);
+        hsum_wide<E, false>(V, Hd, wl, WideCrossbar<double, false>(wl, lane));
+        hsum_wide<E, false>(Vi, Hi, wl, WideCrossbar<int, false>(wl, lane));
         if (lane >= ol && lane < WAVE - ol) {
             for (int i = 0; i < PX; ++i) {
                 int ei = 0;
@@ -349,7 +349,7 @@ __global__ void selftest_kernel(int* result) {
 #pragma unroll
         for (int i = 0; i < PX; ++i) V[i] = (double)((lane * PX + i) * 3 + 1) + 0.5;
         hsum<7, double>(V, Hd, lane);
-        hsum<7, double, false, true>(V, Hc, lane);
+        hsum<7, double, true>(V, Hc, lane);
         if (lane >= 2 && lane < WAVE - 2)
             for (int i = 0; i < PX; ++i)
                 if (Hd[i] != Hc[i]) code |= 64;
@@ -369,7 +369,7 @@ __global__ void selftest_kernel(int* result) {
             // and the guarded quotient against the IEEE one
             const double n = (double)(float)((double)(it + 1) * 0.37 - 90.0);
             const double q = fast_quot(n, d);
-            const bool again = (quot_guard(q) < 2u * HK_DIV_GUARD + 1u) | (quot_range(q) > 0x0fd00000u);
+            const bool again = (quot_guard(q) < 2u * DIV_GUARD + 1u) | (quot_range(q) > 0x0fd00000u);
             if (!again && (float)q != (float)__ddiv_rn(n, d)) code |= 1024;
         }
     }
