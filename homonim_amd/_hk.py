@@ -45,6 +45,10 @@ class SpaceDesc(C.Structure):
                 ('up_resampling', C.c_int32), ('mask_partial', C.c_int32)]
 
 
+class SrcSpaceDesc(C.Structure):
+    _fields_ = [('map', C.c_double * 4), ('resampling', C.c_int32), ('mask_partial', C.c_int32)]
+
+
 # numpy dtype name -> hk_dtype
 DTYPE_CODES = {'float32': 0, 'uint8': 1, 'uint16': 2, 'int16': 3, 'uint32': 4, 'int32': 5, 'float64': 6}
 
@@ -83,7 +87,7 @@ _P = C.POINTER
 _f32p, _f64p, _u64p = _P(C.c_float), _P(C.c_double), _P(C.c_uint64)
 
 # name -> (restype, argtypes); kept in one table so tests can check every symbol of the header is exported
-ABI_VERSION = 10  # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
+ABI_VERSION = 11  # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
 # entry points declared in include/homonim_hk_devtools.h (measurement / test aids), the rest in include/homonim_hk.h
 DEVTOOLS = ('hk_synth_fill_dev', 'hk_stream_probe_dev', 'hk_debug_stage_stamps', 'hk_r2_certificate_constants', 'hk_debug_staging_counters',
             'hk_debug_build_ledger', 'hk_debug_checksum_dev', 'hk_debug_fail_after_d2h')
@@ -124,6 +128,9 @@ SIGNATURES = {
     'hk_fit_apply': (C.c_int, [C.c_void_p, _P(FitDesc), _f32p, C.c_int64, _f32p, C.c_int64, C.c_int32, C.c_int32,
                                _f64p, _f32p, C.c_int32, _f32p, _f64p, _u64p]),
     'hk_refspace_fit_apply': (C.c_int, [C.c_void_p, _P(FitDesc), _P(IoDesc), _P(SpaceDesc), C.c_void_p, C.c_int64, C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _f32p, C.c_int32,
+                                        C.c_void_p, _u64p]),
+    'hk_srcspace_fit_apply': (C.c_int, [C.c_void_p, _P(FitDesc), _P(IoDesc), _P(SrcSpaceDesc), C.c_void_p, C.c_int64, C.c_int32,
                                         C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _f32p, C.c_int32,
                                         C.c_void_p, _u64p]),
     'hk_reproject': (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_double, C.c_double,
@@ -589,6 +596,35 @@ class Context:
         fail = C.c_uint64(0)
         vp = C.c_void_p
         _check(self._lib.hk_refspace_fit_apply(
+            self._h, C.byref(desc), C.byref(io), C.byref(sp), src.ctypes.data_as(vp), src.strides[0] // src.dtype.itemsize,
+            src.shape[0], src.shape[1], ref.ctypes.data_as(vp), ref.strides[0] // ref.dtype.itemsize, ref.shape[0],
+            ref.shape[1], _ptr(params) if want_params else None, n_param_bands, corr.ctypes.data_as(vp), C.byref(fail)))
+        return params, corr, int(fail.value)
+
+    def srcspace_fit_apply(self, desc: FitDesc, src: np.ndarray, ref: np.ndarray, mapping, resampling: int, mask_partial: bool,
+                           n_param_bands: int, want_params: bool, out_dtype: str = 'float32',
+                           out_nodata: Optional[float] = None, out_corr: Optional[np.ndarray] = None):
+        """ hk_srcspace_fit_apply: SrcSpaceModel.fit + KernelModel.apply of one block pair on different grids, all on the device.
+        ``mapping``: reference <- source grid as ``reproject`` takes it, both factors positive.  ``src`` / ``ref`` may be float32 or
+        any dtype of DTYPE_CODES.  -> (params on the source grid | None, corrected on the source grid, r2_fail_count) """
+        src, ref = _as_2d_native(src, 'src'), _as_2d_native(ref, 'ref')
+        out_dtype = np.dtype(out_dtype)
+        if out_dtype.name not in DTYPE_CODES:
+            raise ValueError(f'unsupported output dtype {out_dtype}')
+        keep_nan = out_nodata is None or (isinstance(out_nodata, float) and math.isnan(out_nodata))
+        io = IoDesc(DTYPE_CODES[src.dtype.name], DTYPE_CODES[ref.dtype.name], DTYPE_CODES[out_dtype.name],
+                    0 if (keep_nan and out_dtype.kind == 'f') or out_nodata is None else 1,
+                    0.0 if out_nodata is None or keep_nan else float(out_nodata))
+        sp = SrcSpaceDesc()
+        for i in range(4):
+            sp.map[i] = float(mapping[i])
+        sp.resampling, sp.mask_partial = int(resampling), int(bool(mask_partial))
+        params = np.empty((n_param_bands, *src.shape), np.float32) if want_params else None
+        corr = out_corr if out_corr is not None else np.empty(src.shape, out_dtype)
+        assert corr.shape == src.shape and corr.dtype == out_dtype and corr.flags['C_CONTIGUOUS']
+        fail = C.c_uint64(0)
+        vp = C.c_void_p
+        _check(self._lib.hk_srcspace_fit_apply(
             self._h, C.byref(desc), C.byref(io), C.byref(sp), src.ctypes.data_as(vp), src.strides[0] // src.dtype.itemsize,
             src.shape[0], src.shape[1], ref.ctypes.data_as(vp), ref.strides[0] // ref.dtype.itemsize, ref.shape[0],
             ref.shape[1], _ptr(params) if want_params else None, n_param_bands, corr.ctypes.data_as(vp), C.byref(fail)))

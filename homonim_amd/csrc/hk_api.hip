@@ -1608,6 +1608,128 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     return HK_OK;
 }
 
+int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_srcspace_desc* space,
+                          const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
+                          int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
+                          int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    int rc = validate_desc(desc);
+    if (rc) return rc;
+    if (!space || !src || !ref || !corr_out) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (src_height < 1 || src_width < 1 || ref_height < 1 || ref_width < 1) return fail(HK_ERR_ARG, "empty raster");
+    if (src_stride < src_width || ref_stride < ref_width) return fail(HK_ERR_ARG, "row stride smaller than width");
+    if (!resampling_built(space->resampling)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not built", space->resampling);
+    if (!(space->map[0] > 0 && space->map[2] > 0)) return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
+    if (src_height > 65535 || ref_height > 65535) return fail(HK_ERR_UNSUPPORTED, "block taller than 65535 rows");
+    const int sdt = io ? io->src_dtype : 0, rdt = io ? io->ref_dtype : 0, odt = io ? io->out_dtype : 0;
+    if (!hk::dtype_size(sdt) || !hk::dtype_size(rdt) || !hk::dtype_size(odt)) return fail(HK_ERR_ARG, "unknown dtype");
+    const bool out_cast = io && (odt != 0 || io->out_has_nodata);
+    const bool r2 = needs_r2(desc);
+    if (params_out && n_param_bands != (r2 ? 3 : 2))
+        return fail(HK_ERR_ARG, "n_param_bands must be %d for this model configuration", r2 ? 3 : 2);
+    const bool partial = space->mask_partial != 0;
+    if (partial && (desc->kh + 2) * (desc->kw + 2) > 65535) return fail(HK_ERR_UNSUPPORTED, "kernel too large for mask_partial");
+    HK_ENTER(ctx);
+
+    const int64_t ss = (src_width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;  // source-grid row stride
+    const int64_t rs = (ref_width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;  // reference-grid row stride
+    const size_t splane = (size_t)ss * src_height * 4, rplane = (size_t)rs * ref_height * 4;
+    const int n_par = r2 ? 3 : 2;
+    // `average` reads the reference as it was uploaded (footprint_typed_kernel): no float32 copy, no valid plane
+    const bool typed_foot = space->resampling == 5;
+    SlabLayout L;
+    const size_t o_src = L.take(splane), o_rus = L.take(splane);
+    const size_t o_par = L.take(splane);  // gain, offset, (r2): planes of one size, one band stride apart
+    for (int b = 1; b < n_par; ++b) L.take(splane);
+    const size_t o_corr = L.take(splane);
+    const size_t o_cov = partial ? L.take(splane) : 0, o_cnt = partial ? L.take((size_t)ss * src_height * 2) : 0;
+    const size_t o_mpar = (partial && params_out) ? L.take(splane) : 0;  // the masked parameters
+    if (partial && params_out)
+        for (int b = 1; b < n_par; ++b) L.take(splane);
+    const size_t o_ref = (!typed_foot || !rdt) ? L.take(rplane) : 0, o_vr = (partial && !typed_foot) ? L.take(rplane) : 0;
+    const size_t o_raw_s = sdt ? L.take((size_t)ss * src_height * hk::dtype_size(sdt)) : 0;
+    const size_t o_raw_r = rdt ? L.take((size_t)rs * ref_height * hk::dtype_size(rdt)) : 0;
+    const size_t o_raw_o = out_cast ? L.take((size_t)ss * src_height * hk::dtype_size(odt)) : 0;
+    const size_t o_aux = L.take(256);
+    const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
+    const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, src_height, src_width)) : 0;
+
+    SlotLease lease(ctx);
+    Slot& sl = lease.slot();
+    rc = ensure_dev(sl, L.total);
+    if (rc) return rc;
+    char* base = static_cast<char*>(sl.dev);
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+    const long long pbs = (long long)((splane + 255) / 256 * 256 / 4);  // band stride of the parameter planes, elements
+    float *d_src = F(o_src), *d_rus = F(o_rus), *d_gain = F(o_par), *d_off = d_gain + pbs, *d_r2 = r2 ? d_gain + 2 * pbs : nullptr;
+    float* d_corr = F(o_corr);
+    double* d_norm = reinterpret_cast<double*>(base + o_aux);
+    unsigned long long* d_fail = reinterpret_cast<unsigned long long*>(base + o_aux + 64);
+    const float nan = std::nanf("");
+    const double* m = space->map;
+
+    if ((rc = stage_in(sl, src, src_stride, sdt, d_src, base + o_raw_s, ss, src_height, src_width))) return rc;
+
+    // SrcSpaceModel.fit (:520): reference -> source grid (nodata nan), and for mask_partial the coverage of its valid mask
+    // (_full_coverage_mask, :375-399: mask_ra re-projected with `average`, no nodata)
+    if (typed_foot) {
+        const size_t es = hk::dtype_size(rdt);
+        void* d_raw = rdt ? static_cast<void*>(base + o_raw_r) : static_cast<void*>(base + o_ref);
+        if ((rc = stage_h2d(sl, d_raw, rs * es, ref, ref_stride * es, (size_t)ref_width * es, ref_height))) return rc;
+        HK_HIP(hk::launch_footprint_typed(rdt, d_raw, rs, ref_height, ref_width, desc->ref_nodata_mode, desc->ref_nodata, d_rus,
+                                          partial ? F(o_cov) : nullptr, ss, src_height, src_width, nan, m[0], m[1], m[2], m[3],
+                                          sl.stream));
+    } else {
+        float* d_ref = F(o_ref);
+        if ((rc = stage_in(sl, ref, ref_stride, rdt, d_ref, base + o_raw_r, rs, ref_height, ref_width))) return rc;
+        hk::ResamplePlanes p = {d_ref, d_rus, rs, 0, ss, 0, ref_height, ref_width, src_height, src_width, 1,
+                                desc->ref_nodata_mode, desc->ref_nodata, nan};
+        HK_HIP(hk::launch_resample(space->resampling, p, m[0], m[1], m[2], m[3], sl.stream));
+        if (partial) {
+            HK_HIP(hk::launch_valid_plane(d_ref, rs, desc->ref_nodata_mode, desc->ref_nodata, F(o_vr), rs, ref_height, ref_width,
+                                          sl.stream));
+            p.src = F(o_vr), p.dst = F(o_cov), p.nd_mode = HK_NODATA_NONE, p.nodata = 0.f, p.dst_fill = 0.f;
+            HK_HIP(hk::launch_resample(5, p, m[0], m[1], m[2], m[3], sl.stream));
+        }
+    }
+
+    // KernelModel.fit on the source grid; without mask_partial the fused kernel applies as well: the parameters are nodata
+    // wherever the source is, so that masking them with the source mask (:533) changes nothing
+    hk_fit_desc fd = *desc;
+    fd.ref_nodata_mode = HK_NODATA_NAN, fd.ref_nodata = nan;
+    rc = fit_on_device(ctx, sl, &fd, nullptr, d_src, d_rus, src_height, src_width, ss, d_gain, d_off, d_r2,
+                       partial ? nullptr : d_corr, d_norm, d_fail, base + o_ws);
+    if (rc) return rc;
+
+    float* d_pout = d_gain;
+    if (partial) {
+        // :526-531: coverage >= 1 & "has gain or offset", eroded by (kh+2) x (kw+2), on ALL parameter bands; then KernelModel.apply
+        d_pout = params_out ? F(o_mpar) : nullptr;
+        HK_HIP(hk::launch_partial_mask(F(o_cov), 3, 0.f, d_gain, n_par, pbs, d_src, src_height, src_width, ss, desc->kh, desc->kw,
+                                       reinterpret_cast<unsigned short*>(base + o_cnt), d_pout, d_corr, nullptr, sl.stream));
+    }
+
+    if (params_out) {
+        const size_t wb = (size_t)src_width * 4;
+        for (int b = 0; b < n_param_bands; ++b)
+            if ((rc = stage_d2h(sl, params_out + (size_t)b * src_height * src_width, wb, d_pout + (size_t)b * pbs, ss * 4, wb, src_height)))
+                return rc;
+    }
+    if (out_cast) {
+        const size_t es = hk::dtype_size(odt);
+        void* d_raw = base + o_raw_o;
+        HK_HIP(hk::launch_cast_out(odt, d_corr, ss, d_raw, ss, src_height, src_width, io->out_has_nodata, io->out_nodata,
+                                   sl.stream));
+        if ((rc = stage_d2h(sl, corr_out, (size_t)src_width * es, d_raw, ss * es, (size_t)src_width * es, src_height))) return rc;
+    } else {
+        if ((rc = stage_d2h(sl, corr_out, (size_t)src_width * 4, d_corr, ss * 4, (size_t)src_width * 4, src_height))) return rc;
+    }
+    HK_HIP(hipMemcpyAsync(sl.fail_host, d_fail, sizeof(uint64_t), hipMemcpyDeviceToHost, sl.stream));
+    if ((rc = stage_finish(sl))) return rc;
+    if (r2_fail_count) *r2_fail_count = *sl.fail_host;
+    return HK_OK;
+}
+
 int hk_reproject(hk_ctx* ctx, const float* src, int32_t n_bands, int32_t src_height, int32_t src_width,
                  int32_t src_nodata_mode, float src_nodata, double kx, double ox, double ky, double oy, int32_t resampling,
                  float* dst, int32_t dst_height, int32_t dst_width, float dst_fill) {

@@ -310,6 +310,13 @@ inline bool resample_stretched(double kx, double ky) { return kx > 1.0 + 1e-9 ||
 // Re-sampling between same-CRS axis-aligned grids (hk_resample.hip): src_col = kx * dst_col + ox, src_row = ky * dst_row + oy.
 // mode = rasterio.enums.Resampling value (0..6, 8..14).
 hipError_t launch_resample(int mode, const ResamplePlanes& p, double kx, double ox, double ky, double oy, hipStream_t stream);
+// `average` (mode 5) of ONE plane of sample type `dtype` (hk_dtype) read as it was uploaded: bit for bit launch_cast_in followed by
+// launch_resample(5, ...) into `value` (pixels that receive nothing: `fill`) and, when `coverage` is not NULL, launch_valid_plane
+// followed by launch_resample(5, ...) without nodata and fill 0 into it -- the typed pixels are read once.  Both destination planes
+// have row stride dst_stride.
+hipError_t launch_footprint_typed(int dtype, const void* src, long long src_stride, int sh, int sw, int nd_mode, float nodata,
+                                  float* value, float* coverage, long long dst_stride, int dh, int dw, float fill, double kx,
+                                  double ox, double ky, double oy, hipStream_t stream);
 
 // Re-sampling between grids of two CRSs (hk_warp.hip): the continuous source pixel coordinates of the destination positions
 // (row + off_row, col + off_col) of an h x w lattice, and launch_resample's modes 0..4 on them (kx, ky: the mean step, which picks

@@ -10,6 +10,8 @@
 //   8 max / 9 min / 13 sum / 14 rms : over the same pixels; sum and rms weight the edge pixels like average
 //   6 mode / 10 med / 11 q1 / 12 q3 : rank order of the same pixels, no weights
 // One thread per destination pixel (gather), one row per workgroup, one band per blockIdx.z; float64 accumulation, float32 result.
+// footprint_typed_kernel<T> is `average` on a plane of any sample type as it was uploaded, with the coverage fraction of its valid
+// mask from the same loop (hk_srcspace_fit_apply: the reference block of SrcSpaceModel.fit is read once).
 #include "hk_kernels.h"
 #include "hk_resample_taps.h"
 
@@ -142,6 +144,60 @@ __global__ void __launch_bounds__(256) resample_conv_kernel(const ResampleArgs a
                                 iy, ix, dy, dx, result);
     }
     dp[(long long)i * p.dst_stride + j] = got ? (float)result : p.dst_fill;
+}
+
+// `average` of a plane of sample type T as it was uploaded, and the coverage fraction of its valid mask, from ONE pass over the
+// typed pixels under the footprint (SrcSpaceModel.fit across grids, kernel_model.py:520 and :375-409: the reference block is the
+// big input there).  The value is resample_kernel<5> on the plane cast_in_kernel<T> would have written: the same (float) conversion,
+// in registers, the same loop and accumulation order.  The coverage is resample_kernel<5> without nodata on the plane
+// valid_plane_kernel would have written from that: sum of w * [valid] over sum of w, over ALL pixels of the clipped footprint.
+// One loop serves both: an invalid pixel adds w * 0.0 = +0.0 there, which changes no bit of a sum of non-negative terms, and a
+// valid one adds w * 1.0 = w, so the numerator is `wsum`, the weight sum of the value, bit for bit; only the denominator `wall`
+// is new.  A footprint that shares no area with the plane gets `fill` and coverage 0.
+template <typename T>
+struct FootTypedArgs {
+    const T* src;
+    long long src_stride;
+    int sh, sw;
+    int nd_mode;
+    float nodata;
+    float* value;
+    float* coverage;  // nullable
+    long long dst_stride;
+    int dh, dw;
+    float fill;
+    double kx, ox, ky, oy;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256) footprint_typed_kernel(const FootTypedArgs<T> a) {
+    typedef __attribute__((address_space(1))) const T gT;
+    typedef __attribute__((address_space(1))) float gfloat;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= a.dw) return;
+    gT* const sp = (gT*)a.src;
+    double tot = 0.0, wsum = 0.0, wall = 0.0;
+    FootAxis fy, fx;
+    const bool rows = rs_footprint_axis(scaled_coord(a.ky, a.oy, (double)i), scaled_coord(a.ky, a.oy, (double)(i + 1)), a.sh, fy);
+    const bool cols = rs_footprint_axis(scaled_coord(a.kx, a.ox, (double)j), scaled_coord(a.kx, a.ox, (double)(j + 1)), a.sw, fx);
+    if (rows && cols) {
+        for (int yy = fy.i0; yy < fy.i1; ++yy) {
+            const double wy = rs_edge_weight(fy, yy);
+            gT* const row = sp + (long long)yy * a.src_stride;
+            for (int xx = fx.i0; xx < fx.i1; ++xx) {
+                const float v = (float)row[xx];
+                const double wgt = rs_edge_weight(fx, xx) * wy;
+                wall += wgt;
+                if (!rs_valid(v, a.nd_mode, a.nodata)) continue;
+                tot += (double)v * wgt;
+                wsum += wgt;
+            }
+        }
+    }
+    const long long o = (long long)i * a.dst_stride + j;
+    ((gfloat*)a.value)[o] = wsum > 0.0 ? (float)(tot / wsum) : a.fill;
+    if (a.coverage) ((gfloat*)a.coverage)[o] = wall > 0.0 ? (float)(wsum / wall) : 0.f;
 }
 
 // valid(src) as a float32 0/1 plane: RasterArray.mask_ra (raster_array.py:320-327) before it is re-projected
@@ -396,6 +452,34 @@ hipError_t launch_resample(int mode, const ResamplePlanes& p, double kx, double 
         case 14: HK_LAUNCH(resample_kernel<14>, grid, block, 0, stream, a); break;
         default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+template <typename T>
+static FootTypedArgs<T> foot_typed_args(const void* src, long long src_stride, int sh, int sw, int nd_mode, float nodata, float* value,
+                                        float* coverage, long long dst_stride, int dh, int dw, float fill, double kx, double ox,
+                                        double ky, double oy) {
+    return {static_cast<const T*>(src), src_stride, sh, sw, nd_mode, nodata, value, coverage, dst_stride, dh, dw, fill, kx, ox, ky, oy};
+}
+
+hipError_t launch_footprint_typed(int dtype, const void* src, long long src_stride, int sh, int sw, int nd_mode, float nodata,
+                                  float* value, float* coverage, long long dst_stride, int dh, int dw, float fill, double kx,
+                                  double ox, double ky, double oy, hipStream_t stream) {
+    const dim3 grid((dw + 255) / 256, dh), block(256);
+#define HK_FOOT_TYPED(T)                                                                                                          \
+    HK_LAUNCH(footprint_typed_kernel<T>, grid, block, 0, stream,                                                                  \
+              foot_typed_args<T>(src, src_stride, sh, sw, nd_mode, nodata, value, coverage, dst_stride, dh, dw, fill, kx, ox, ky, oy))
+    switch (dtype) {
+        case 0: HK_FOOT_TYPED(float); break;
+        case 1: HK_FOOT_TYPED(unsigned char); break;
+        case 2: HK_FOOT_TYPED(unsigned short); break;
+        case 3: HK_FOOT_TYPED(short); break;
+        case 4: HK_FOOT_TYPED(unsigned int); break;
+        case 5: HK_FOOT_TYPED(int); break;
+        case 6: HK_FOOT_TYPED(double); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef HK_FOOT_TYPED
     return hipGetLastError();
 }
 

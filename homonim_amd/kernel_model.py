@@ -11,6 +11,8 @@ Differences a caller can observe (all documented in DESIGN.md):
 * ``fit`` does NOT zero-fill / normalise the caller's ``src_ra`` / ``ref_ra`` in place (the reference does,
   kernel_model.py:246-247,292-295,320-321; its own wrappers always pass temporaries or copies).
 * ``fit_apply`` is an extra, fused entry point for ``RasterFuse._process_block``'s fit->apply pair (fuse.py:305-307).
+  ``RefSpaceModel`` / ``SrcSpaceModel`` have it across grids as well: one call per block pair, typed blocks in, everything
+  between them on the device (hk_refspace_fit_apply, hk_srcspace_fit_apply).
 * gain-offset with ``r2_inpaint_thresh`` set: the kernel evaluates the r2 mask (kernel_model.py:363); when no valid
   pixel fails it the reference's GDAL ``fillnodata`` branch is the identity and results are identical; when some
   fail, the offsets are in-painted on the device by a restatement of GDAL's published fill algorithm (parity with
@@ -311,11 +313,33 @@ class SrcSpaceModel(KernelModel):
     def fit_apply(self, src_ra: RasterArray, ref_ra: RasterArray, want_params: bool = False,
                   out_dtype: str = RasterArray.default_dtype,
                   out_nodata: Optional[float] = RasterArray.default_nodata) -> Tuple[RasterArray, Optional[RasterArray]]:
-        """ One fused pass on a shared grid; with ``mask_partial`` (or across grids) the reference's own sequence
-        ``apply(src_ra, fit(src_ra, ref_ra))`` -- SrcSpaceModel.fit masks the parameters with the eroded full-coverage
-        mask (kernel_model.py:526-531), which the fused kernel does not know about. """
+        """ One fused pass on a shared grid.  Across grids everything between the two blocks stays in HBM as well
+        (hk_srcspace_fit_apply): one upload of source + reference in their own dtypes, one download of the corrected block; with
+        `average` the reference block -- the finer, larger one -- is read once, by the kernel that forms the averaged value and
+        the coverage fraction of ``mask_partial`` together.  ``mask_partial`` on a shared grid keeps the reference's own sequence
+        ``apply(src_ra, fit(src_ra, ref_ra))`` -- SrcSpaceModel.fit masks the parameters with the eroded full-coverage mask
+        (kernel_model.py:526-531), which the fused kernel does not know about. """
         if self.fuses_into(src_ra, ref_ra):
             return KernelModel.fit_apply(self, src_ra, ref_ra, want_params, out_dtype, out_nodata)
+        _require_one_crs(src_ra, ref_ra)
+        if not _same_grid(src_ra, ref_ra):
+            from homonim_amd.geo import grid_mapping
+            kx, ox, ky, oy = grid_mapping(ref_ra.transform, src_ra.transform)
+            ref = self._band(ref_ra, 'ref_ra')
+            # grids of opposite orientation along an axis: flip the reference along it, as RasterArray.reproject does
+            if ky < 0:
+                ref, ky, oy = ref[::-1, :], -ky, ref.shape[0] - oy
+            if kx < 0:
+                ref, kx, ox = ref[:, ::-1], -kx, ref.shape[1] - ox
+            count = 3 if self._emit_r2 else 2
+            params, corr, _ = self.context.srcspace_fit_apply(
+                self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), ref, (kx, ox, ky, oy),
+                int(self._get_resampling(ref_ra.res, src_ra.res)), self._mask_partial, count, want_params, out_dtype=out_dtype,
+                out_nodata=out_nodata
+            )
+            profile = self._param_profile(src_ra, count)
+            corr_ra = RasterArray.from_profile(corr, dict(profile, count=1, nodata=out_nodata, dtype=str(np.dtype(out_dtype))))
+            return corr_ra, (RasterArray.from_profile(params, profile) if want_params else None)
         param_ra = self.fit(src_ra.copy(), ref_ra)
         corr_ra = self.apply(src_ra, param_ra)
         if np.dtype(out_dtype) != np.float32 or not (out_nodata is None or (isinstance(out_nodata, float) and np.isnan(out_nodata))):

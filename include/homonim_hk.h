@@ -74,9 +74,9 @@ typedef struct {
  * added entry points (hk_overview_count, hk_overviews, hk_overviews_dev); version 9 added hk_crs_desc / hk_warp_desc and entry
  * points (hk_warp_coords, hk_warp_coords_dev, hk_reproject_crs, hk_reproject_crs_dev, hk_reproject_dev); version 10 added
  * hk_affine_warp_desc and entry points (hk_warp_coords_affine, hk_warp_coords_affine_dev, hk_reproject_affine,
- * hk_reproject_affine_dev).
+ * hk_reproject_affine_dev); version 11 added hk_srcspace_desc and the entry point hk_srcspace_fit_apply.
  * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
-#define HK_ABI_VERSION 10
+#define HK_ABI_VERSION 11
 int hk_abi_version(void);
 const char* hk_backend_name(void);            /* "hip-gfx950" */
 const char* hk_last_error(void);              /* thread-local text of the last failure */
@@ -332,6 +332,27 @@ typedef struct {
     int32_t mask_partial;
 } hk_space_desc;
 int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_space_desc* space,
+                          const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
+                          int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
+                          int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count);
+
+/* SrcSpaceModel.fit + KernelModel.apply (homonim/kernel_model.py:506-535, :442-463) of one block pair on DIFFERENT grids of one
+ * CRS, entirely on the device -- source and reference blocks in, corrected block (source grid) out:
+ *   reference --resampling--> source grid (destination nodata NaN); KernelModel.fit there (incl. block statistics / in-painting);
+ *   all parameter bands masked with the source mask, or (mask_partial) with the full-coverage mask of kernel_model.py:375-409:
+ *   the reference's valid mask averaged onto the source grid (>= 1) & "has gain or offset", eroded by (kh+2) x (kw+2) (:526-531);
+ *   KernelModel.apply; conversion to the output dtype.
+ * map = mapping reference <- source grid (ref_col = map[0] * src_col + map[1], ref_row = map[2] * src_row + map[3]) as hk_reproject
+ * defines it.  With `average` the typed reference pixels are read once, by a kernel that forms the averaged value and the
+ * coverage fraction together; every other method goes through a float32 copy of the block and hk_reproject's kernels.  The results
+ * are bit for bit those of hk_reproject, hk_fit, hk_partial_mask and hk_apply called one after the other.  params_out (nullable):
+ * n_param_bands planes on the SOURCE grid.  io (nullable) types src / ref / corr_out as in hk_fit_apply_io. */
+typedef struct {
+    double map[4];
+    int32_t resampling;    /* rasterio.enums.Resampling value, KernelModel._get_resampling(ref.res, src.res) */
+    int32_t mask_partial;
+} hk_srcspace_desc;
+int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_srcspace_desc* space,
                           const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
                           int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
                           int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count);
