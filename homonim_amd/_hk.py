@@ -90,7 +90,7 @@ _f32p, _f64p, _u64p = _P(C.c_float), _P(C.c_double), _P(C.c_uint64)
 ABI_VERSION = 11  # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
 # entry points declared in include/homonim_hk_devtools.h (measurement / test aids), the rest in include/homonim_hk.h
 DEVTOOLS = ('hk_synth_fill_dev', 'hk_stream_probe_dev', 'hk_debug_stage_stamps', 'hk_r2_certificate_constants', 'hk_debug_staging_counters',
-            'hk_debug_build_ledger', 'hk_debug_checksum_dev', 'hk_debug_fail_after_d2h')
+            'hk_debug_build_ledger', 'hk_debug_checksum_dev', 'hk_debug_fail_after_d2h', 'hk_debug_inpaint_plane_dev')
 
 SIGNATURES = {
     'hk_abi_version': (C.c_int, []),
@@ -196,6 +196,8 @@ SIGNATURES = {
     'hk_debug_build_ledger': (C.c_int, [C.c_char_p, C.c_size_t, _P(C.c_size_t), C.c_int32]),
     'hk_debug_fail_after_d2h': (C.c_int, [C.c_int32]),
     'hk_debug_checksum_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint64)]),
+    'hk_debug_inpaint_plane_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
+                                             C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
 }  # yapf: disable
 
 PARAM_STATS_N = 10    # values per band of hk_param_stats / hk_param_stats_dev
@@ -823,6 +825,61 @@ class Context:
         out = C.c_uint64(0)
         _check(self._lib.hk_debug_checksum_dev(self._h, C.c_void_p(plane_dptr), stride, height, width, stream, C.byref(out)))
         return int(out.value)
+
+    def inpaint_plane_dev(self, plane_dptr: int, flags_dptr: Optional[int], gain_dptr: Optional[int], r2_dptr: Optional[int],
+                          thresh: float, height: int, width: int, stride: int, mode: int = 0, stream: int = 0):
+        """ The in-painting step alone on device-resident planes (hk_debug_inpaint_plane_dev; synchronises the stream). """
+        vp = lambda p: C.c_void_p(p) if p else None   # noqa: E731
+        _check(self._lib.hk_debug_inpaint_plane_dev(self._h, vp(plane_dptr), vp(flags_dptr), vp(gain_dptr), vp(r2_dptr),
+                                                    float(thresh), int(height), int(width), int(stride), int(mode), int(stream)))
+
+    def inpaint_plane(self, plane: np.ndarray, flags: Optional[np.ndarray] = None, gain: Optional[np.ndarray] = None,
+                      r2: Optional[np.ndarray] = None, thresh: Optional[float] = None, mode: int = 0,
+                      stride: Optional[int] = None, pad_value: Optional[float] = None, pad_flag: Optional[int] = None) -> np.ndarray:
+        """ Test aid: in-paint the targets of a 2-D float32 ``plane`` from its sources, the in-painting step of the gain-offset
+        model on its own.  The mask is ``flags`` (uint8: 1 source, 0 target, 2 neither) or ``gain`` / ``r2`` / ``thresh``
+        (source = (r2 > thresh) & (gain > 0)).  ``mode``: see hk_debug_inpaint_plane_dev.  ``stride`` (elements, default: the
+        width rounded up to 4) is the row pitch of every plane on the device; the padding holds ``pad_value`` (planes) and
+        ``pad_flag`` (flags), zero by default.  -> the filled height x width plane. """
+        if flags is not None and (gain is not None or r2 is not None or thresh is not None):
+            raise ValueError('give either `flags` or `gain` / `r2` / `thresh`')
+        if flags is None and (gain is None or r2 is None or thresh is None):
+            raise ValueError('without `flags`, all of `gain`, `r2` and `thresh` are needed')
+        plane = np.ascontiguousarray(plane, np.float32)
+        if plane.ndim != 2 or plane.size == 0:
+            raise ValueError('`plane` must be a non-empty 2-D raster')
+        h, w = plane.shape
+        stride = (w + 3) // 4 * 4 if stride is None else int(stride)
+        if stride < w:
+            raise ValueError(f'stride {stride} is less than the width {w}')
+
+        def padded(a, dtype, name, pad):
+            a = np.asarray(a)
+            if a.shape != (h, w):
+                raise ValueError(f'`{name}` must have the shape of `plane`')
+            out = np.full((h, stride), 0 if pad is None else pad, dtype)
+            out[:, :w] = a
+            return out
+
+        if flags is not None:
+            hosts = [padded(plane, np.float32, 'plane', pad_value), padded(flags, np.uint8, 'flags', pad_flag), None, None]
+        else:
+            hosts = [padded(plane, np.float32, 'plane', pad_value), None, padded(gain, np.float32, 'gain', pad_value),
+                     padded(r2, np.float32, 'r2', pad_value)]
+        dptrs = [None] * 4
+        try:
+            for i, a in enumerate(hosts):
+                if a is not None:
+                    dptrs[i] = self.dev_alloc(a.nbytes)
+                    self.h2d(dptrs[i], a)
+            self.inpaint_plane_dev(dptrs[0], dptrs[1], dptrs[2], dptrs[3], 0.0 if flags is not None else thresh, h, w, stride, mode)
+            out = np.empty((h, stride), np.float32)
+            self.d2h(out, dptrs[0])
+        finally:
+            for p in dptrs:
+                if p:
+                    self.dev_free(p)
+        return np.ascontiguousarray(out[:, :w])
 
     # -- device-resident helpers (bench / streaming) ------------------------------------------------------------------
     def dev_alloc(self, nbytes: int) -> int:

@@ -2878,6 +2878,61 @@ int hk_debug_checksum_dev(hk_ctx* ctx, const float* plane, int64_t stride, int32
     return HK_OK;
 }
 
+int hk_debug_inpaint_plane_dev(hk_ctx* ctx, float* plane_dev, const uint8_t* flags_dev, const float* gain_dev, const float* r2_dev,
+                               float thresh, int32_t height, int32_t width, int64_t stride, int32_t mode, int32_t stream) {
+    if (!ctx || !plane_dev) return fail(HK_ERR_ARG, "NULL argument");
+    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (mode < 0 || mode > 3) return fail(HK_ERR_ARG, "mode %d: 0 (the library's choice), 1 / 2 (packed search by rows / columns), 3 (general search only)", mode);
+    // the bit planes' launches take one grid row per 64 raster rows
+    if (height < 1 || width < 1 || height > 65535 * 64) return fail(HK_ERR_ARG, "bad shape %d x %d", height, width);
+    // rows are read as 4-byte flag groups, stored as 8-byte table pairs and staged as 16-byte table quads
+    if (stride < width || stride % 4 != 0) return fail(HK_ERR_ARG, "stride %lld: at least the width (%d) and a multiple of 4", (long long)stride, width);
+    // (launch_inpaint_offsets leaves the packed search out at such a stride: modes 1 and 2 would not run what they name)
+    if ((mode == 1 || mode == 2) && stride >= (1ll << 23))
+        return fail(HK_ERR_ARG, "mode %d: the packed search takes strides below 2^23 only (stride %lld)", mode, (long long)stride);
+    if (flags_dev ? (gain_dev || r2_dev) : (!gain_dev || !r2_dev))
+        return fail(HK_ERR_ARG, "give either flags_dev or both of gain_dev and r2_dev");
+    auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+    if (misaligned(plane_dev) || misaligned(flags_dev) || misaligned(gain_dev) || misaligned(r2_dev))
+        return fail(HK_ERR_ARG, "device planes must be 4-byte aligned (the flag plane too: it is read four columns at a time)");
+    HK_ENTER(ctx);
+    DevEnter entered(ctx, stream);
+    Slot& sl = ctx->slots[stream];
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);  // the slot's scratch may be (re)allocated
+        const int rc = ensure_inpaint_scratch(sl, 0, height, stride);
+        if (rc) return rc;
+    }
+    unsigned long long n_targets = 0;  // mode 1: unknown -> row order
+    if (mode == 2) n_targets = (unsigned long long)height * (unsigned long long)width;  // every pixel failing -> column order
+    if (mode == 0) {  // as inpaint_band is told by the pass that counted: the number of pixels that are not sources
+        const size_t n = (size_t)height * (size_t)stride;
+        std::vector<uint8_t> hf;
+        std::vector<float> hg, hr;
+        try {
+            hf.resize(flags_dev ? n : 0), hg.resize(flags_dev ? 0 : n), hr.resize(flags_dev ? 0 : n);
+        } catch (...) {
+            return fail(HK_ERR_NOMEM, "out of host memory (counting the targets of %d x %lld pixels)", height, (long long)stride);
+        }
+        HK_HIP(hipStreamSynchronize(sl.stream));
+        if (flags_dev) {
+            HK_HIP(hipMemcpy(hf.data(), flags_dev, n, hipMemcpyDeviceToHost));
+        } else {
+            HK_HIP(hipMemcpy(hg.data(), gain_dev, n * sizeof(float), hipMemcpyDeviceToHost));
+            HK_HIP(hipMemcpy(hr.data(), r2_dev, n * sizeof(float), hipMemcpyDeviceToHost));
+        }
+        for (int y = 0; y < height; ++y)
+            for (int x = 0; x < width; ++x) {
+                const size_t i = (size_t)y * (size_t)stride + x;
+                n_targets += flags_dev ? hf[i] == 0 : !((hr[i] > thresh) && (hg[i] > 0.f));
+            }
+    }
+    HK_HIP(hk::launch_inpaint_offsets(plane_dev, gain_dev, r2_dev, thresh, stride, height, width, sl.aux, sl.stream, flags_dev,
+                                      n_targets, mode != 3));
+    HK_HIP(hipStreamSynchronize(sl.stream));
+    return HK_OK;
+}
+
 int hk_event_create(hk_ctx* ctx, hk_event** ev) {
     if (!ctx || !ev) return fail(HK_ERR_ARG, "NULL argument");
     HK_ENTER(ctx);

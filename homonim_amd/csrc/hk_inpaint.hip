@@ -645,7 +645,7 @@ unsigned char* inpaint_flag_plane(void* workspace, int height, long long stride)
 
 hipError_t launch_inpaint_offsets(float* offset, const float* gain, const float* r2, float thresh, long long stride,
                                   int height, int width, void* workspace, hipStream_t stream,
-                                  const unsigned char* flag_ready, unsigned long long n_targets) {
+                                  const unsigned char* flag_ready, unsigned long long n_targets, bool packed_search) {
     const size_t plane = (size_t)height * stride;
     unsigned* tb = static_cast<unsigned*>(workspace);  // (down^2 << 16) | up^2 row distances, 4 bytes per pixel
     unsigned char* ws_flag = inpaint_flag_plane(workspace, height, stride);
@@ -673,7 +673,8 @@ hipError_t launch_inpaint_offsets(float* offset, const float* gain, const float*
     // column by column where more than 60 % of the pixels fail, row by row otherwise (HISTORY.md 53).
     const bool by_column = (double)n_targets > 0.6 * (double)height * (double)width;
     // the packed search addresses the plane through 32-bit offsets from its tile and 24-bit multiplies by the row stride
-    const bool fast = stride < (1ll << 23);
+    // (`packed_search` false: a test asks for the general search of every target, hk_debug_inpaint_plane_dev)
+    const bool fast = packed_search && stride < (1ll << 23);
     if (fast) {
         const int n_tiles8 = (height + 7) / 8, wgs_y = (n_tiles8 + 3) / 4;  // a workgroup takes four tiles (it copies the finish tables into LDS once)
         const dim3 gf((width + 255) / 256, wgs_y < 65535 ? wgs_y : 65535);

@@ -287,10 +287,12 @@ size_t inpaint_workspace_bytes(int height, long long stride);
 // `flag_ready` (nullable): source flags already written by the fit kernel (FitArgs::flag; 1 byte per pixel, row stride
 // `stride`) -- gain / r2 are then not read.  inpaint_flag_plane(): the workspace's own flag plane, for a fit to write into.
 // `n_targets`: the number of failing pixels if the caller knows it (0 = unknown): picks the order in which a tile's targets are searched.
+// `packed_search` false (test aid only): the packed search is left out and the general one takes every target.
 unsigned char* inpaint_flag_plane(void* workspace, int height, long long stride);
 hipError_t launch_inpaint_offsets(float* offset, const float* gain, const float* r2, float thresh, long long stride,
                                   int height, int width, void* workspace, hipStream_t stream,
-                                  const unsigned char* flag_ready = nullptr, unsigned long long n_targets = 0);
+                                  const unsigned char* flag_ready = nullptr, unsigned long long n_targets = 0,
+                                  bool packed_search = true);
 
 // What every re-sampling launch carries, whatever maps a destination pixel to the source (hk_resample.hip, hk_warp.hip): hk_api.hip
 // fills one per entry point, the kernels' argument structs embed it.  Strides in elements.

@@ -84,6 +84,22 @@ int hk_debug_fail_after_d2h(int32_t on);
  * comparing with the oracle ever launched. */
 int hk_debug_build_ledger(char* buf, size_t len, size_t* needed, int32_t reset);
 
+/* Test aid: the in-painting step alone (hk_inpaint.hip; kernel_model.py:366) on a source mask of the caller's choosing, where
+ * hk_fit_apply* only ever hands it the mask its own fit produced.  `plane_dev`: height x stride float32, device-resident; its
+ * targets are filled in place, everything else stays as it is.  The mask comes EITHER from `flags_dev` -- one byte per pixel at
+ * the same stride: 1 = source, 0 = target, anything else = neither (what the fit kernel writes; gain_dev and r2_dev NULL) -- OR
+ * from `gain_dev` / `r2_dev` (same stride) and `thresh`: source = (r2 > thresh) & (gain > 0), target otherwise (flags_dev NULL).
+ * `mode` 0: what a fit would get -- the library counts the targets and picks the order of the packed search by their share;
+ * 1 / 2: packed search with a tile's targets in row / column order; 3: no packed search, the general search takes every
+ * target.  All four give the same plane.  Runs on pooled stream `stream` with that stream's in-painting scratch and
+ * synchronises it before returning.  HK_ERR_ARG, before anything is launched, for what the kernels do not take: a shape
+ * below 1 x 1, stride < width or not a multiple of 4, a plane that is not 4-byte aligned (the flag plane included), both or
+ * neither of the two mask inputs, mode 1 or 2 with a stride of 2^23 or more (the packed search does not take those; modes 0 and
+ * 3 run the general search alone there).  HK_ERR_NOMEM when mode 0 cannot hold the mask on the host to count it. */
+int hk_debug_inpaint_plane_dev(hk_ctx* ctx, float* plane_dev, const uint8_t* flags_dev, const float* gain_dev,
+                               const float* r2_dev, float thresh, int32_t height, int32_t width, int64_t stride,
+                               int32_t mode, int32_t stream);
+
 #ifdef __cplusplus
 }
 #endif
