@@ -87,7 +87,8 @@ _P = C.POINTER
 _f32p, _f64p, _u64p = _P(C.c_float), _P(C.c_double), _P(C.c_uint64)
 
 # name -> (restype, argtypes); kept in one table so tests can check every symbol of the header is exported
-ABI_VERSION = 11  # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
+DEFLATE_CHUNK = 16384  # HK_DEFLATE_CHUNK: raw bytes per DEFLATE block of Context.deflate_tiles
+ABI_VERSION = 12  # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
 # entry points declared in include/homonim_hk_devtools.h (measurement / test aids), the rest in include/homonim_hk.h
 DEVTOOLS = ('hk_synth_fill_dev', 'hk_stream_probe_dev', 'hk_debug_stage_stamps', 'hk_r2_certificate_constants', 'hk_debug_staging_counters',
             'hk_debug_build_ledger', 'hk_debug_checksum_dev', 'hk_debug_fail_after_d2h', 'hk_debug_inpaint_plane_dev')
@@ -122,6 +123,11 @@ SIGNATURES = {
                                C.c_double, C.c_int32, _P(C.c_void_p), _P(C.c_int64), _P(C.c_int64)]),
     'hk_overviews_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                    C.c_int32, C.c_double, C.c_int32, _P(C.c_void_p), _P(C.c_int64), _P(C.c_int64), C.c_int32]),
+    'hk_deflate_bound': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int64), _P(C.c_int64)]),
+    'hk_deflate_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                   C.c_void_p, C.c_int64, _P(C.c_int64), _P(C.c_int64)]),
+    'hk_deflate_tiles_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                       C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]),
     'hk_fit': (C.c_int, [C.c_void_p, _P(FitDesc), _f32p, C.c_int64, _f32p, C.c_int64, C.c_int32, C.c_int32, _f64p,
                          _f32p, C.c_int32, _f64p, _u64p]),
     'hk_apply': (C.c_int, [C.c_void_p, _f32p, C.c_int64, _f32p, C.c_int32, C.c_int32, _f32p]),
@@ -221,6 +227,15 @@ def overview_count(height: int, width: int) -> int:
 def overview_shapes(height: int, width: int, n_levels: int):
     """ [(ceil(height / 2^m), ceil(width / 2^m)) for m = 1..n_levels] """
     return [(-(-int(height) // (1 << m)), -(-int(width) // (1 << m))) for m in range(1, int(n_levels) + 1)]
+
+
+def deflate_bound(dtype, n_bands: int, height: int, width: int, tile: int):
+    """ -> (number of tiles, bytes that always hold their zlib streams) of ``Context.deflate_tiles`` (hk_deflate_bound; no device
+    needed): per tile 2 + sum over its chunks of (chunk + 5) + 6, rounded up to even. """
+    n_tiles, cap = C.c_int64(), C.c_int64()
+    _check(load_library().hk_deflate_bound(DTYPE_CODES[np.dtype(dtype).name], n_bands, height, width, int(tile), C.byref(n_tiles),
+                                           C.byref(cap)))
+    return n_tiles.value, cap.value
 
 
 def comm_unique_id() -> bytes:
@@ -469,6 +484,44 @@ class Context:
                                       arr.strides[1] // it, arr.strides[0] // it if nb > 1 else 0, mode, value, n_levels, ptrs,
                                       strides, bstrides))
         return [o[0] for o in outs] if squeeze else outs
+
+    def deflate_tiles_packed(self, array: np.ndarray, tile: int):
+        """ ``deflate_tiles`` as the library returns it: (uint8 array of the streams, int64 offsets [n_tiles + 1], int64 sizes
+        [n_tiles]) -- tile t's stream is ``out[offsets[t]:offsets[t] + sizes[t]]``; offsets are even and ``offsets[-1]`` is the
+        number of bytes used. """
+        arr = np.asarray(array)
+        if arr.ndim == 2:
+            arr = arr[None]
+        if arr.ndim != 3 or arr.size == 0:
+            raise ValueError('`array` must be a non-empty 2-D or 3-D raster')
+        if arr.dtype.name == 'int8':   # (the bytes are what is compressed: the signedness of a sample does not enter)
+            arr = arr.view(np.uint8)
+        if arr.dtype.name not in DTYPE_CODES:
+            raise ValueError(f"unsupported dtype '{arr.dtype}'")
+        if arr.dtype.byteorder == '>':
+            arr = arr.astype(arr.dtype.newbyteorder('<'))
+        it = arr.dtype.itemsize
+        if (arr.strides[2] != it or arr.strides[1] % it or arr.strides[1] < arr.shape[2] * it or arr.strides[0] % it
+                or arr.strides[0] < 0):
+            arr = np.ascontiguousarray(arr)
+        nb, h, w = arr.shape
+        code, tile = DTYPE_CODES[arr.dtype.name], int(tile)
+        n_tiles, cap = C.c_int64(), C.c_int64()
+        _check(self._lib.hk_deflate_bound(code, nb, h, w, tile, C.byref(n_tiles), C.byref(cap)))
+        out = np.empty(cap.value, np.uint8)
+        offsets, sizes = np.empty(n_tiles.value + 1, np.int64), np.empty(n_tiles.value, np.int64)
+        _check(self._lib.hk_deflate_tiles(self._h, arr.ctypes.data_as(C.c_void_p), code, nb, h, w, arr.strides[1] // it,
+                                          arr.strides[0] // it if nb > 1 else 0, tile, out.ctypes.data_as(C.c_void_p), cap.value,
+                                          offsets.ctypes.data_as(_P(C.c_int64)), sizes.ctypes.data_as(_P(C.c_int64))))
+        return out, offsets, sizes
+
+    def deflate_tiles(self, array: np.ndarray, tile: int) -> list:
+        """ One zlib stream per ``tile`` x ``tile`` tile of a (bands, h, w) or (h, w) raster in host memory, made on the device
+        (hk_deflate_tiles; the stream format: include/homonim_hk.h): ``bytes`` objects in the order band, tile row, tile column,
+        edge tiles zero-padded, samples little-endian -- what ``tiff.write_tiff`` takes as ``compressor``.  Any dtype
+        ``write_tiff`` accepts; rows and bands may be strided (unit column stride), anything else is copied first. """
+        out, offsets, sizes = self.deflate_tiles_packed(array, tile)
+        return [out[o:o + n].tobytes() for o, n in zip(offsets[:-1].tolist(), sizes.tolist())]
 
     def fit_apply(self, desc: FitDesc, src: np.ndarray, ref: np.ndarray, n_param_bands: int, want_params: bool,
                   want_corr: bool, norm_in: Optional[np.ndarray] = None, out_params: Optional[np.ndarray] = None,
@@ -1034,6 +1087,15 @@ class Context:
         _check(self._lib.hk_overviews_dev(self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height,
                                           width, stride, band_stride, mode, value, n, (C.c_void_p * n)(*out_dptrs),
                                           (C.c_int64 * n)(*out_strides), (C.c_int64 * n)(*out_band_strides), stream))
+
+    def deflate_tiles_dev(self, planes_dptr: int, dtype: str, n_bands: int, height: int, width: int, stride: int, band_stride: int,
+                          tile: int, out_dptr: int, out_capacity: int, offsets_dptr: int, sizes_dptr: int, stream: int = 0):
+        """ Queue the zlib streams of the tiles of ``n_bands`` device-resident planes of dtype ``dtype`` (strides in elements):
+        the streams into ``out_dptr`` (``deflate_bound`` bytes), ``n_tiles + 1`` int64 offsets into ``offsets_dptr``, ``n_tiles``
+        int64 sizes into ``sizes_dptr`` (hk_deflate_tiles_dev; asynchronous). """
+        _check(self._lib.hk_deflate_tiles_dev(self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height,
+                                              width, stride, band_stride, tile, C.c_void_p(out_dptr), out_capacity,
+                                              C.c_void_p(offsets_dptr), C.c_void_p(sizes_dptr), stream))
 
     def synth_fill_dev(self, src_dptr, ref_dptr, n_bands, height, width, stride, band_stride, seed=0, nodata_variant=0,
                        stream=0):

@@ -2529,6 +2529,123 @@ int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands
     return stage_finish(sl);
 }
 
+// DEFLATE streams of a raster's tiles (hk_deflate.hip): see include/homonim_hk.h
+static int deflate_shape(int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int32_t tile, int64_t* n_tiles, int64_t* bytes,
+                         int64_t* n_chunks) {
+    const int es = hk::dtype_size(dtype);
+    if (!es) return fail(HK_ERR_ARG, "bad dtype %d", dtype);
+    if (n_bands < 1 || height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d x %d", n_bands, height, width);
+    if (tile < 16 || tile > 512 || tile % 16) return fail(HK_ERR_ARG, "tile %d is not a multiple of 16 in 16..512", tile);
+    const int64_t across = ((int64_t)width + tile - 1) / tile, down = ((int64_t)height + tile - 1) / tile;
+    const int64_t raw = (int64_t)tile * tile * es, cpt = (raw + HK_DEFLATE_CHUNK - 1) / HK_DEFLATE_CHUNK;
+    const int64_t per_tile = 2 + raw + 5 * cpt + 6;   // header, every chunk stored, final block and Adler-32
+    *n_tiles = (int64_t)n_bands * across * down;
+    *bytes = *n_tiles * (per_tile + (per_tile & 1));
+    if (n_chunks) *n_chunks = *n_tiles * cpt;
+    return HK_OK;
+}
+
+int hk_deflate_bound(int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int32_t tile, int64_t* n_tiles, int64_t* bytes) {
+    if (!n_tiles || !bytes) return fail(HK_ERR_ARG, "NULL pointer argument");
+    return deflate_shape(dtype, n_bands, height, width, tile, n_tiles, bytes, nullptr);
+}
+
+static int check_deflate(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                         int64_t stride, int64_t band_stride, int32_t tile, const void* out, int64_t out_capacity,
+                         const int64_t* tile_offsets, const int64_t* tile_sizes, int64_t* n_tiles, int64_t* n_chunks) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    if (!planes || !out || !tile_offsets || !tile_sizes) return fail(HK_ERR_ARG, "NULL pointer argument");
+    int64_t bytes = 0;
+    const int rc = deflate_shape(dtype, n_bands, height, width, tile, n_tiles, &bytes, n_chunks);
+    if (rc) return rc;
+    if (stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
+    if (band_stride < 0) return fail(HK_ERR_ARG, "band_stride is negative");
+    if (out_capacity < bytes) return fail(HK_ERR_ARG, "out_capacity %lld is below hk_deflate_bound's %lld", (long long)out_capacity, (long long)bytes);
+    return HK_OK;
+}
+
+int hk_deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                         int64_t stride, int64_t band_stride, int32_t tile, void* out_dev, int64_t out_capacity,
+                         int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream) {
+    int64_t n_tiles = 0, n_chunks = 0;
+    int rc = check_deflate(ctx, planes_dev, dtype, n_bands, height, width, stride, band_stride, tile, out_dev, out_capacity,
+                           tile_offsets_dev, tile_sizes_dev, &n_tiles, &n_chunks);
+    if (rc) return rc;
+    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (n_chunks > 0x7FFFFFFFll) return fail(HK_ERR_ARG, "%lld chunks are more than one launch takes", (long long)n_chunks);
+    DevEnter entered(ctx, stream);
+    HK_ENTER(ctx);
+    Slot& sl = ctx->slots[stream];
+    rc = ensure_stream_ws(ctx, sl, hk::deflate_workspace_bytes(n_chunks));
+    if (rc) return rc;
+    static_assert(sizeof(long long) == sizeof(int64_t), "offsets are handed on as they are");
+    HK_HIP(hk::launch_deflate_tiles(planes_dev, hk::dtype_size(dtype), n_bands, height, width, stride, band_stride, tile, sl.norm_ws,
+                                    static_cast<unsigned char*>(out_dev), reinterpret_cast<long long*>(tile_offsets_dev),
+                                    reinterpret_cast<long long*>(tile_sizes_dev), sl.stream));
+    return HK_OK;
+}
+
+// tile rows per group of the host path: whole tile rows of ONE band of at most DEFLATE_GROUP_BYTES raw bytes (at least one tile
+// row); HK_DEFLATE_GROUP_KB (read at every call) lowers the bound for tests of the group path.  Tiles are independent, so the
+// grouping cannot change a byte.
+constexpr size_t DEFLATE_GROUP_BYTES = 64u << 20;
+
+int hk_deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                     int64_t band_stride, int32_t tile, void* out, int64_t out_capacity, int64_t* tile_offsets, int64_t* tile_sizes) {
+    int64_t n_tiles = 0, n_chunks = 0;
+    int rc = check_deflate(ctx, planes, dtype, n_bands, height, width, stride, band_stride, tile, out, out_capacity, tile_offsets,
+                           tile_sizes, &n_tiles, &n_chunks);
+    if (rc) return rc;
+    HK_ENTER(ctx);
+    const size_t es = hk::dtype_size(dtype);
+    const int64_t across = ((int64_t)width + tile - 1) / tile, down = ((int64_t)height + tile - 1) / tile;
+    const char* e = getenv("HK_DEFLATE_GROUP_KB");
+    const size_t cap = (e && atol(e) > 0) ? (size_t)atol(e) << 10 : DEFLATE_GROUP_BYTES;
+    const int64_t row_raw = across * tile * tile * (int64_t)es;   // raw bytes of one tile row
+    const int64_t g_down = std::max<int64_t>(1, std::min<int64_t>(down, (int64_t)(cap / (size_t)row_raw)));
+    int64_t g_tiles = 0, g_bytes = 0, g_chunks = 0;
+    if ((rc = deflate_shape(dtype, 1, (int32_t)std::min<int64_t>(g_down * tile, height), width, tile, &g_tiles, &g_bytes, &g_chunks))) return rc;
+    // device slab of one group: its rows (padded to ROW_ALIGN elements: 16-byte loads are legal), the chunk slots, the streams,
+    // offsets and sizes
+    SlabLayout L;
+    const int64_t d_stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    const int64_t g_rows = std::min<int64_t>(g_down * tile, height);
+    const size_t o_src = L.take((size_t)g_rows * d_stride * es);
+    const size_t o_work = L.take(hk::deflate_workspace_bytes(g_chunks));
+    const size_t o_out = L.take((size_t)g_bytes);
+    const size_t o_off = L.take((size_t)(g_tiles + 1) * sizeof(int64_t));
+    const size_t o_siz = L.take((size_t)g_tiles * sizeof(int64_t));
+    SlotLease lease(ctx);
+    Slot& sl = lease.slot();
+    if ((rc = ensure_dev(sl, L.total))) return rc;
+    char* base = static_cast<char*>(sl.dev);
+    const char* h_src = static_cast<const char*>(planes);
+    char* h_out = static_cast<char*>(out);
+    int64_t used = 0, t0 = 0;
+    for (int b = 0; b < n_bands; ++b)
+        for (int64_t ty = 0; ty < down; ty += g_down) {
+            const int64_t r0 = ty * tile, rows = std::min<int64_t>(g_down * tile, height - r0);
+            const int64_t nt = across * ((rows + tile - 1) / tile);
+            if ((rc = stage_h2d(sl, base + o_src, d_stride * es, h_src + ((size_t)b * band_stride + (size_t)r0 * stride) * es,
+                                stride * es, (size_t)width * es, rows)))
+                return rc;
+            HK_HIP(hk::launch_deflate_tiles(base + o_src, (int)es, 1, (int)rows, width, d_stride, 0, tile, base + o_work,
+                                            reinterpret_cast<unsigned char*>(base + o_out), reinterpret_cast<long long*>(base + o_off),
+                                            reinterpret_cast<long long*>(base + o_siz), sl.stream));
+            // the offsets first (they say how many bytes there are), then only the compressed bytes
+            if ((rc = stage_d2h(sl, tile_offsets + t0, 0, base + o_off, 0, (size_t)(nt + 1) * sizeof(int64_t), 1))) return rc;
+            if ((rc = stage_d2h(sl, tile_sizes + t0, 0, base + o_siz, 0, (size_t)nt * sizeof(int64_t), 1))) return rc;
+            if ((rc = stage_finish(sl))) return rc;
+            const int64_t got = tile_offsets[t0 + nt];
+            if (got < 0 || got > out_capacity - used) return fail(HK_ERR_HIP, "deflate: a group reports %lld bytes, %lld are left", (long long)got, (long long)(out_capacity - used));
+            if ((rc = stage_d2h(sl, h_out + used, 0, base + o_out, 0, (size_t)got, 1))) return rc;
+            if ((rc = stage_finish(sl))) return rc;
+            for (int64_t k = 0; k <= nt; ++k) tile_offsets[t0 + k] += used;
+            used += got, t0 += nt;
+        }
+    return HK_OK;
+}
+
 int hk_block_norm_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_job* job, double* norm_dev) {
     int rc = validate_desc(desc);
     if (rc) return rc;

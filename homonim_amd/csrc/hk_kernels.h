@@ -263,6 +263,26 @@ hipError_t launch_overviews(int dtype, const void* src, int height, int width, l
                             int n_bands, int nd_mode, double nodata, int n_levels, void* const* out, const long long* out_stride,
                             const long long* out_band_stride, hipStream_t stream);
 
+// DEFLATE streams of the tiles of a tiled GeoTIFF (hk_deflate.hip, which states the stream format): the raster's tiles of
+// `tile` x `tile` samples of `esize` bytes, edge tiles zero-padded, in the order band, tile row, tile column; one zlib stream per
+// tile into `out` at tile_offsets[t] (even), tile_sizes[t] bytes long; tile_offsets[n_tiles] = the bytes used.  Strides in
+// elements.  `work`: deflate_workspace_bytes(number of chunks) of device memory; everything is queued on `stream`.
+struct DeflateArgs {
+    const void* src;
+    int es, height, width;
+    long long stride, band_stride;
+    int tile, across, down;   // tile size in samples, tiles per tile row, tile rows per band
+    int tile_bytes, cpt;      // raw bytes and chunks per tile
+    int vec_ok;               // set by the launcher: 16-byte row loads are legal
+    unsigned char* slots;     // one slot per chunk
+    unsigned* sizes;          // bytes of every chunk's block(s)
+    unsigned* adler;          // per chunk: (sum of bytes mod 65521) | (weighted sum mod 65521) << 16
+};
+size_t deflate_workspace_bytes(long long n_chunks);
+hipError_t launch_deflate_tiles(const void* src, int esize, int n_bands, int height, int width, long long stride,
+                                long long band_stride, int tile, void* work, unsigned char* out, long long* tile_offsets,
+                                long long* tile_sizes, hipStream_t stream);
+
 hipError_t launch_synth_fill(float* src, float* ref, int n_bands, int height, int width, long long stride,
                              long long band_stride, unsigned long long seed, int nodata_variant, hipStream_t stream);
 

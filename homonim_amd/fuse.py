@@ -444,7 +444,7 @@ class RasterFuse:
     @staticmethod
     def create_device_config(devices: Optional[Sequence[int]] = None, streams: int = 4, rank: int = 0,
                              world_size: int = 1, contiguous: bool = False, pin: bool = True,
-                             separate_contexts: bool = False) -> Dict:
+                             separate_contexts: bool = False, deflate: str = 'host') -> Dict:
         """ (this package only) GPUs of this process, streams per GPU, this process's shard of the block list
         (round-robin, or ``contiguous`` runs), whether every entry of ``devices`` gets a context of its own even when a
         device is listed twice, and ``pin``: True (default) -- the rasters are registered in place for the duration of the
@@ -453,10 +453,14 @@ class RasterFuse:
         array the library did not page-lock itself travel through the library's own page-locked staging ring, so the runtime
         is never handed pageable memory either way (the registered path ran clean as the first process of five fresh
         leases, profiles/r04_abort_followup.txt); False -- everything through the staging ring: the GPU never touches
-        caller-allocated pages. """
+        caller-allocated pages.  ``deflate``: who compresses the tiles of the GeoTIFFs ``process`` writes: 'host' (default) --
+        zlib level 6 on the writing thread, byte for byte as before; 'device' -- ``Context.deflate_tiles``: the same pixels, tags
+        and overviews in files a few percent larger, written without the minutes of host zlib. """
+        if deflate not in ('host', 'device'):
+            raise ValueError(f"`deflate` must be 'host' or 'device', not {deflate!r}")
         return dict(devices=None if devices is None else list(devices), streams=int(streams), rank=int(rank),
                     world_size=int(world_size), contiguous=bool(contiguous), pin=bool(pin),
-                    separate_contexts=bool(separate_contexts))
+                    separate_contexts=bool(separate_contexts), deflate=deflate)
 
     def block_pairs(self, overlap: Tuple[int, int] = (0, 0), max_block_mem: float = math.inf) -> Iterable[BlockPair]:
         if self._same_grid:
@@ -638,17 +642,18 @@ class RasterFuse:
                 c.close()
 
         if isinstance(corr_filename, (str, os.PathLike)) or (want_params and isinstance(param_filename, (str, os.PathLike))):
+            compressor = models[0].context.deflate_tiles if device_config['deflate'] == 'device' else None
             # provenance tags of homonim/fuse.py:193-207
             meta = dict(FUSE_SRC_FILE=os.path.basename(self._src_filename or 'memory'),
                         FUSE_REF_FILE=os.path.basename(self._ref_filename or 'memory'), FUSE_PROC_CRS=self._proc_crs.name,
                         FUSE_MODEL=model_type.name, FUSE_KERNEL_SHAPE=tuple(kernel_shape),
                         **{f'FUSE_{k.upper()}': getattr(v, 'name', v) for k, v in model_config.items()})
             if isinstance(corr_filename, (str, os.PathLike)):
-                self._save(corr_filename, corr, self._transform, nodata, meta, overviews=corr_ovw)
+                self._save(corr_filename, corr, self._transform, nodata, meta, overviews=corr_ovw, compressor=compressor)
             if want_params and isinstance(param_filename, (str, os.PathLike)):
                 param_tf = self._ref_transform if (self._proc_crs == ProcCrs.ref and not self._same_grid) else self._transform
                 self._save(param_filename, params, param_tf, float('nan'), meta, self._param_descriptions(n_param),
-                           overviews=param_ovw)
+                           overviews=param_ovw, compressor=compressor)
         return corr, params
 
     @staticmethod
@@ -706,13 +711,14 @@ class RasterFuse:
         return ctx.overviews(array, nodata, n_levels) if n_levels else None
 
     def _save(self, filename, array: np.ndarray, transform: Affine, nodata, metadata: Dict,
-              descriptions: Optional[List[str]] = None, overviews: Optional[List[np.ndarray]] = None):
+              descriptions: Optional[List[str]] = None, overviews: Optional[List[np.ndarray]] = None, compressor=None):
         """ ``.tif`` / ``.tiff``: tiled DEFLATE GeoTIFF like the reference's default output profile, with ``overviews`` as its
-        internal overviews when given; anything else: ``numpy.save``. """
+        internal overviews when given, its tiles compressed by ``compressor`` (``tiff.write_tiff``; None: host zlib); anything
+        else: ``numpy.save``. """
         if self._is_tiff(filename):
             from homonim_amd.tiff import write_tiff
             write_tiff(filename, array, transform, self._crs, nodata, {k: str(v) for k, v in metadata.items()},
-                       descriptions=descriptions, overviews=overviews)
+                       descriptions=descriptions, overviews=overviews, compressor=compressor)
         else:
             np.save(filename, array)
 

@@ -315,7 +315,7 @@ def _directory(entries, chunks, ifd_off: int, has_next: bool) -> Tuple[bytes, in
 def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = None, nodata: Optional[float] = None,
                metadata: Optional[Dict[str, str]] = None, tile: int = 512, compress: bool = True,
                descriptions: Optional[Sequence[Optional[str]]] = None, overviews: Optional[Sequence[np.ndarray]] = None,
-               rotated: bool = False):
+               rotated: bool = False, compressor=None):
     """ Write (bands, height, width) as a classic little-endian GeoTIFF: tiled, DEFLATE, band-separate -- the reference's
     default output profile (homonim/fuse.py:124-149: tiled 512 x 512, compress=deflate, interleave=band).  ``descriptions``:
     one band description per band (None: none for that band), written as GDAL writes them.  ``overviews``: the internal
@@ -324,7 +324,13 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
     configuration and compression, GDAL_NODATA and no geo tags.  The main image is written the same with and without them.
     ``rotated``: accept a rotated / sheared ``transform`` and write it as a ModelTransformation matrix instead of pixel scale +
     tie point; without it such a transform is refused -- everything this package produces is north-up, so a rotated grid on
-    the way out is a mistake unless it is asked for. """
+    the way out is a mistake unless it is asked for.  ``compressor``: a callable ``(array3d, tile) -> list of bytes`` that returns
+    one zlib stream per tile of a (bands, h, w) array in this writer's tile order -- band, tile row, tile column; a tile is
+    ``tile`` rows of ``tile`` little-endian samples, edge tiles zero-padded -- used for the main image (at ``tile``) and for every
+    overview level (at 128) in place of ``zlib.compress`` (e.g. ``Context.deflate_tiles``: this module itself imports no GPU
+    code).  None: zlib level 6 on this thread, the same bytes as ever. """
+    if compressor is not None and not compress:
+        raise ValueError('a compressor was given for an uncompressed file (compress=False)')
     a = np.asarray(array)
     if a.ndim == 2:
         a = a[None]
@@ -373,7 +379,16 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
             add(T_GDAL_NODATA, 2, 'nan' if (isinstance(nodata, float) and np.isnan(nodata)) else repr(float(nodata)) if a.dtype.kind == 'f' else str(int(nodata)))
         return entries, add
 
-    chunks = _tile_chunks(a, tile, compress)
+    def tile_streams(img, img_tile):
+        if compressor is None:
+            return _tile_chunks(img, img_tile, compress)
+        streams = [bytes(c) for c in compressor(img, img_tile)]
+        expected = img.shape[0] * (-(-img.shape[1] // img_tile)) * (-(-img.shape[2] // img_tile))
+        if len(streams) != expected:
+            raise ValueError(f'the compressor returned {len(streams)} streams for {expected} tiles')
+        return streams
+
+    chunks = tile_streams(a, tile)
     entries, add = image_entries(a, tile, chunks, False)
     if transform.b != 0 or transform.d != 0:   # a rotated / sheared grid: the full matrix instead of pixel scale + tie point
         add(T_TRANSFORMATION, 12, [float(transform.a), float(transform.b), 0., float(transform.c),
@@ -405,7 +420,7 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
     blob, pos = _directory(entries, chunks, 8, bool(levels))
     blobs.append(blob)
     for k, lv in enumerate(levels):
-        lv_chunks = _tile_chunks(lv, OVERVIEW_TILE, compress)
+        lv_chunks = tile_streams(lv, OVERVIEW_TILE)
         lv_entries, _ = image_entries(lv, OVERVIEW_TILE, lv_chunks, True)
         blob, pos = _directory(lv_entries, lv_chunks, pos, k + 1 < len(levels))
         blobs.append(blob)

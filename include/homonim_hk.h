@@ -74,9 +74,10 @@ typedef struct {
  * added entry points (hk_overview_count, hk_overviews, hk_overviews_dev); version 9 added hk_crs_desc / hk_warp_desc and entry
  * points (hk_warp_coords, hk_warp_coords_dev, hk_reproject_crs, hk_reproject_crs_dev, hk_reproject_dev); version 10 added
  * hk_affine_warp_desc and entry points (hk_warp_coords_affine, hk_warp_coords_affine_dev, hk_reproject_affine,
- * hk_reproject_affine_dev); version 11 added hk_srcspace_desc and the entry point hk_srcspace_fit_apply.
+ * hk_reproject_affine_dev); version 11 added hk_srcspace_desc and the entry point hk_srcspace_fit_apply; version 12 added entry
+ * points (hk_deflate_bound, hk_deflate_tiles, hk_deflate_tiles_dev).
  * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
-#define HK_ABI_VERSION 11
+#define HK_ABI_VERSION 12
 int hk_abi_version(void);
 const char* hk_backend_name(void);            /* "hip-gfx950" */
 const char* hk_last_error(void);              /* thread-local text of the last failure */
@@ -134,6 +135,26 @@ int hk_overview_count(int32_t height, int32_t width, int32_t* n);
 int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
                  int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels, void* const out[],
                  const int64_t out_stride[], const int64_t out_band_stride[]);
+
+/* DEFLATE on the device: one zlib stream per tile of a tiled, band-separate GeoTIFF (homonim/fuse.py:124-149: tiled, compress =
+ * deflate, interleave = band), in place of zlib.compress on a host thread.  A tile is `tile` x `tile` samples (`tile` a multiple of
+ * 16 in 16..512), little-endian, edge tiles zero-padded; tiles are ordered band, tile row, tile column.  Every stream is: 78 9C; per
+ * HK_DEFLATE_CHUNK raw bytes either one dynamic-Huffman block followed by an empty stored block, or one stored block (whenever the
+ * former would not be smaller); a final empty fixed block (03 00); the Adler-32.  Matches are runs at two distances only, the sample
+ * size and the tile's row length; the bytes are a function of the input alone.  Any inflater reads the streams; they are a few
+ * percent larger than zlib level 6. */
+#define HK_DEFLATE_CHUNK 16384
+/* n_tiles = n_bands x ceil(height / tile) x ceil(width / tile); bytes = the capacity that always suffices: per tile
+ * 2 + sum over its chunks (chunk + 5) + 6, rounded up to even.  Plain host arithmetic (no device needed). */
+int hk_deflate_bound(int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int32_t tile, int64_t* n_tiles, int64_t* bytes);
+/* The streams of a raster in host memory (plane b at planes + b * band_stride, `stride` elements between rows) into `out` (host,
+ * out_capacity >= hk_deflate_bound's bytes): tile t's stream is the tile_sizes[t] bytes at out + tile_offsets[t]; offsets are even
+ * (an odd stream is followed by one zero byte, as a TIFF writer pads it) and increasing, tile_offsets[n_tiles] = the bytes used.
+ * The raster travels through the pinned staging ring in groups of whole tile rows of one band, at most 64 MiB of raw bytes each
+ * (HK_DEFLATE_GROUP_KB lowers the bound, for tests), and only compressed bytes come back. */
+int hk_deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                     int64_t band_stride, int32_t tile, void* out, int64_t out_capacity, int64_t* tile_offsets /* n_tiles + 1 */,
+                     int64_t* tile_sizes /* n_tiles */);
 
 /* KernelModel.fit (homonim/kernel_model.py:411-440 -> _fit_gain :231-274, _fit_gain_blk_offset :276-303,
  * _fit_gain_offset :305-373, _r2_array :142-214).
@@ -533,6 +554,13 @@ int hk_param_stats_dev(hk_ctx* ctx, const float* planes_dev, int32_t n_bands, in
 int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
                      int64_t stride, int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels,
                      void* const out_dev[], const int64_t out_stride[], const int64_t out_band_stride[], int32_t stream);
+
+/* hk_deflate_tiles for device-resident planes: streams, offsets and sizes stay on the device (out_dev of out_capacity >=
+ * hk_deflate_bound's bytes; tile_offsets_dev: n_tiles + 1, tile_sizes_dev: n_tiles int64).  Queued on pooled stream `stream`;
+ * asynchronous.  The whole raster is one launch: at most 2^31 - 1 chunks. */
+int hk_deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                         int64_t stride, int64_t band_stride, int32_t tile, void* out_dev, int64_t out_capacity,
+                         int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream);
 
 /* HIP events on the pooled streams, so callers time exactly the stream the kernels run on. */
 int hk_event_create(hk_ctx* ctx, hk_event** ev);
