@@ -91,7 +91,8 @@ DEFLATE_CHUNK = 16384  # HK_DEFLATE_CHUNK: raw bytes per DEFLATE block of Contex
 ABI_VERSION = 12  # HK_ABI_VERSION of the include/homonim_hk.h these mirrors were written against
 # entry points declared in include/homonim_hk_devtools.h (measurement / test aids), the rest in include/homonim_hk.h
 DEVTOOLS = ('hk_synth_fill_dev', 'hk_stream_probe_dev', 'hk_debug_stage_stamps', 'hk_r2_certificate_constants', 'hk_debug_staging_counters',
-            'hk_debug_build_ledger', 'hk_debug_checksum_dev', 'hk_debug_fail_after_d2h', 'hk_debug_inpaint_plane_dev')
+            'hk_debug_build_ledger', 'hk_debug_checksum_dev', 'hk_debug_fail_after_d2h', 'hk_debug_inpaint_plane_dev',
+            'hk_debug_cast_plane_dev')
 
 SIGNATURES = {
     'hk_abi_version': (C.c_int, []),
@@ -204,6 +205,8 @@ SIGNATURES = {
     'hk_debug_checksum_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint64)]),
     'hk_debug_inpaint_plane_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
                                              C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    'hk_debug_cast_plane_dev': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_double, C.c_int32]),
 }  # yapf: disable
 
 PARAM_STATS_N = 10    # values per band of hk_param_stats / hk_param_stats_dev
@@ -300,6 +303,32 @@ def nodata_code(nodata):
     if math.isnan(nodata):
         return NODATA_NAN, float('nan')
     return NODATA_VALUE, nodata
+
+
+def out_nodata_code(out_dtype, out_nodata):
+    """ Output nodata -> (out_has_nodata, out_nodata) of hk_io_desc.  None, and NaN for a float dtype: masked pixels keep NaN;
+    NaN for an integer dtype: 0.  Any other value must survive the cast to ``out_dtype`` as RasterArray._convert_array_dtype
+    demands (homonim/raster_array.py:357-358): an integer of the type's range for an integer type, no overflow for float32;
+    the library refuses the same with HK_ERR_ARG (hk_api.hip validate_out_nodata). """
+    out_dtype = np.dtype(out_dtype)
+    if out_nodata is None:
+        return 0, 0.0
+    value = float(out_nodata)
+    if math.isnan(value):
+        return (0, 0.0) if out_dtype.kind == 'f' else (1, 0.0)
+    if out_dtype.kind == 'f':
+        ok = math.isinf(value) or out_dtype.itemsize == 8 or abs(value) < float.fromhex('0x1.ffffffp127')
+    else:
+        info = np.iinfo(out_dtype)
+        ok = math.isfinite(value) and value == math.floor(value) and info.min <= value <= info.max
+    if not ok:
+        raise ValueError(f"'nodata' value: {out_nodata} cannot be safely cast to '{out_dtype.name}'")
+    return 1, value
+
+
+def _io_desc(src: np.ndarray, ref: np.ndarray, out_dtype: np.dtype, out_nodata) -> IoDesc:
+    return IoDesc(DTYPE_CODES[src.dtype.name], DTYPE_CODES[ref.dtype.name], DTYPE_CODES[out_dtype.name],
+                  *out_nodata_code(out_dtype, out_nodata))
 
 
 def make_desc(model: str, kernel_shape, find_r2: bool, r2_inpaint_thresh: Optional[float], src_nodata, ref_nodata):
@@ -541,7 +570,6 @@ class Context:
         out_dtype = np.dtype(out_dtype)
         if out_dtype.name not in DTYPE_CODES:
             raise ValueError(f'unsupported output dtype {out_dtype}')
-        keep_nan = out_nodata is None or (isinstance(out_nodata, float) and math.isnan(out_nodata))
         params = corr = None
         if want_params:
             params = out_params if out_params is not None else np.empty((n_param_bands, h, w), np.float32)
@@ -554,9 +582,7 @@ class Context:
         nin = None
         if norm_in is not None:
             nin = np.ascontiguousarray(norm_in, dtype=np.float64)
-        io = IoDesc(DTYPE_CODES[src.dtype.name], DTYPE_CODES[ref.dtype.name], DTYPE_CODES[out_dtype.name],
-                    0 if (keep_nan and out_dtype.kind == 'f') or out_nodata is None else 1,
-                    0.0 if out_nodata is None or keep_nan else float(out_nodata))
+        io = _io_desc(src, ref, out_dtype, out_nodata)
         vp = C.c_void_p
         _check(self._lib.hk_fit_apply_io(
             self._h, C.byref(desc), C.byref(io), src.ctypes.data_as(vp), src.strides[0] // src.dtype.itemsize,
@@ -603,10 +629,7 @@ class Context:
                 stride = pstride
         if out_dtype.name not in DTYPE_CODES:
             raise ValueError(f'unsupported output dtype {out_dtype}')
-        keep_nan = out_nodata is None or (isinstance(out_nodata, float) and math.isnan(out_nodata))
-        io = IoDesc(DTYPE_CODES[src.dtype.name], DTYPE_CODES[ref.dtype.name], DTYPE_CODES[out_dtype.name],
-                    0 if (keep_nan and out_dtype.kind == 'f') or out_nodata is None else 1,
-                    0.0 if out_nodata is None or keep_nan else float(out_nodata))
+        io = _io_desc(src, ref, out_dtype, out_nodata)
         win = OutWindow(stride, band_stride, row0, col0, rows, cols, pstride)
         norm = np.zeros(2, np.float64)
         fail = C.c_uint64(0)
@@ -637,10 +660,7 @@ class Context:
         -> (params on the reference grid | None, corrected on the source grid, r2_fail_count) """
         src, ref = _as_2d_native(src, 'src'), _as_2d_native(ref, 'ref')
         out_dtype = np.dtype(out_dtype)
-        keep_nan = out_nodata is None or (isinstance(out_nodata, float) and math.isnan(out_nodata))
-        io = IoDesc(DTYPE_CODES[src.dtype.name], DTYPE_CODES[ref.dtype.name], DTYPE_CODES[out_dtype.name],
-                    0 if (keep_nan and out_dtype.kind == 'f') or out_nodata is None else 1,
-                    0.0 if out_nodata is None or keep_nan else float(out_nodata))
+        io = _io_desc(src, ref, out_dtype, out_nodata)
         sp = SpaceDesc()
         for i in range(4):
             sp.down[i], sp.up[i] = float(down[i]), float(up[i])
@@ -666,10 +686,7 @@ class Context:
         out_dtype = np.dtype(out_dtype)
         if out_dtype.name not in DTYPE_CODES:
             raise ValueError(f'unsupported output dtype {out_dtype}')
-        keep_nan = out_nodata is None or (isinstance(out_nodata, float) and math.isnan(out_nodata))
-        io = IoDesc(DTYPE_CODES[src.dtype.name], DTYPE_CODES[ref.dtype.name], DTYPE_CODES[out_dtype.name],
-                    0 if (keep_nan and out_dtype.kind == 'f') or out_nodata is None else 1,
-                    0.0 if out_nodata is None or keep_nan else float(out_nodata))
+        io = _io_desc(src, ref, out_dtype, out_nodata)
         sp = SrcSpaceDesc()
         for i in range(4):
             sp.map[i] = float(mapping[i])
@@ -933,6 +950,64 @@ class Context:
                 if p:
                     self.dev_free(p)
         return np.ascontiguousarray(out[:, :w])
+
+    def cast_plane_dev(self, to_typed: bool, dtype, src_dptr: int, src_stride: int, dst_dptr: int, dst_stride: int, height: int,
+                       width: int, has_nodata: bool = False, nodata: float = 0.0, stream: int = 0):
+        """ One dtype conversion of hk_convert.hip alone on device-resident planes (hk_debug_cast_plane_dev; synchronises the
+        stream).  ``dtype``: a name of DTYPE_CODES or an hk_dtype code. """
+        code = dtype if isinstance(dtype, int) else DTYPE_CODES[np.dtype(dtype).name]
+        vp = lambda p: C.c_void_p(p) if p else None   # noqa: E731
+        _check(self._lib.hk_debug_cast_plane_dev(self._h, int(bool(to_typed)), code, vp(src_dptr), int(src_stride), vp(dst_dptr),
+                                                 int(dst_stride), int(height), int(width), int(bool(has_nodata)), float(nodata),
+                                                 int(stream)))
+
+    def _cast_plane(self, to_typed, array, dst_dtype, dtype, has_nodata, nodata, stride, dst_stride, sentinel, full):
+        if array.ndim != 2 or array.size == 0:
+            raise ValueError('`array` must be a non-empty 2-D raster')
+        h, w = array.shape
+        stride = (w + 3) // 4 * 4 if stride is None else int(stride)
+        dst_stride = stride if dst_stride is None else int(dst_stride)
+        if stride < w or dst_stride < w:
+            raise ValueError(f'stride {min(stride, dst_stride)} is less than the width {w}')
+        src = np.zeros((h, stride), array.dtype)   # the padding of the source rows is zero
+        src[:, :w] = array
+        out = np.empty((h, dst_stride), dst_dtype)
+        out.view(np.uint8)[...] = sentinel
+        dptrs = [None, None]
+        try:
+            dptrs[0], dptrs[1] = self.dev_alloc(src.nbytes), self.dev_alloc(out.nbytes)
+            self.h2d(dptrs[0], src)
+            self.h2d(dptrs[1], out)
+            self.cast_plane_dev(to_typed, dtype, dptrs[0], stride, dptrs[1], dst_stride, h, w, has_nodata, nodata)
+            self.d2h(out, dptrs[1])
+        finally:
+            for p in dptrs:
+                if p:
+                    self.dev_free(p)
+        return out if full else np.ascontiguousarray(out[:, :w])
+
+    def cast_in_plane(self, array: np.ndarray, stride: Optional[int] = None, dst_stride: Optional[int] = None, sentinel: int = 0xA5,
+                      full: bool = False) -> np.ndarray:
+        """ Test aid: a 2-D raster of an integer type of DTYPE_CODES or of float64 converted to float32 by the device's input
+        conversion alone (cast_in_kernel: what RasterArray.from_rio_dataset's read with out_dtype float32 gives).  ``stride`` /
+        ``dst_stride`` (elements; default: the width rounded up to 4, and ``stride``) are the row pitches of the source and
+        the destination plane on the device; the source's padding holds zero, every byte of the destination holds ``sentinel``
+        before the call.  -> the height x width result, or with ``full`` the whole height x dst_stride plane. """
+        array = np.asarray(array)
+        if array.dtype.name not in DTYPE_CODES or array.dtype == np.float32:
+            raise ValueError(f"no input conversion from dtype '{array.dtype}'")
+        return self._cast_plane(False, array, np.float32, array.dtype, False, 0.0, stride, dst_stride, sentinel, full)
+
+    def cast_out_plane(self, array_f32: np.ndarray, dtype, nodata, stride: Optional[int] = None, dst_stride: Optional[int] = None,
+                       sentinel: int = 0xA5, full: bool = False) -> np.ndarray:
+        """ Test aid: a 2-D float32 raster converted to ``dtype`` by the device's output conversion alone (cast_out_kernel:
+        RasterArray._convert_array_dtype -- round half to even, clip, NaN -> ``nodata``); ``nodata`` as ``fit_apply`` takes
+        ``out_nodata``.  Strides, padding, ``sentinel`` and ``full`` as for ``cast_in_plane``. """
+        dtype = np.dtype(dtype)
+        if dtype.name not in DTYPE_CODES:
+            raise ValueError(f'unsupported output dtype {dtype}')
+        has, value = out_nodata_code(dtype, nodata)
+        return self._cast_plane(True, np.asarray(array_f32, np.float32), dtype, dtype, has, value, stride, dst_stride, sentinel, full)
 
     # -- device-resident helpers (bench / streaming) ------------------------------------------------------------------
     def dev_alloc(self, nbytes: int) -> int:

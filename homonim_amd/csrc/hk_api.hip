@@ -783,6 +783,23 @@ int validate_desc(const hk_fit_desc* d) {
     return HK_OK;
 }
 
+// RasterArray._convert_array_dtype refuses an output nodata that does not survive the cast to the output dtype
+// (raster_array.py:357-358, rasterio.dtypes.can_cast_dtype); cast_out_kernel converts it with `(T)nodata`, which is undefined for
+// a value the type cannot hold.  Integer types: an integer of the type's range (NaN and +-inf are none); float32: anything that
+// does not overflow it (can_cast_dtype compares floats with np.allclose); float64: anything.  `dtype` is a valid hk_dtype.
+int validate_out_nodata(int dtype, int has_nodata, double nodata) {
+    if (!has_nodata || dtype == HK_DTYPE_F64) return HK_OK;
+    static const char* const names[7] = {"float32", "uint8", "uint16", "int16", "uint32", "int32", "float64"};
+    static const double lo[7] = {0, 0, 0, -32768.0, 0, -2147483648.0, 0}, hi[7] = {0, 255.0, 65535.0, 32767.0, 4294967295.0, 2147483647.0, 0};
+    bool ok;
+    if (dtype == HK_DTYPE_F32)
+        ok = !std::isfinite(nodata) || std::fabs(nodata) < 0x1.ffffffp127;  // below the midpoint of FLT_MAX and 2^128
+    else
+        ok = std::isfinite(nodata) && nodata >= lo[dtype] && nodata <= hi[dtype] && nodata == std::floor(nodata);
+    if (!ok) return fail(HK_ERR_ARG, "'nodata' value: %.17g cannot be safely cast to '%s'", nodata, names[dtype]);
+    return HK_OK;
+}
+
 // The reference decides `(1 - f32(f64(ssres / sstot))) > thresh` (kernel_model.py:212-213,363).  Returns a float64 factor
 // c such that, for sstot > 0, `ssres < c * sstot` PROVES that decision true: c sits 2^-40 (relative) below the
 // float32 rounding boundary of the largest quotient that still passes, which swallows the 2^-53 errors of the float64
@@ -1188,6 +1205,7 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
     if (src_stride < width || ref_stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
     const int sdt = io ? io->src_dtype : 0, rdt = io ? io->ref_dtype : 0, odt = io ? io->out_dtype : 0;
     if (!hk::dtype_size(sdt) || !hk::dtype_size(rdt) || !hk::dtype_size(odt)) return fail(HK_ERR_ARG, "unknown dtype");
+    if (io && (rc = validate_out_nodata(odt, io->out_has_nodata, io->out_nodata))) return rc;
     const bool out_cast = io && (odt != 0 || io->out_has_nodata);
     const bool r2 = needs_r2(desc);
     if (!norm_only) {
@@ -1498,6 +1516,7 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     if (src_height > 65535 || ref_height > 65535) return fail(HK_ERR_UNSUPPORTED, "block taller than 65535 rows");
     const int sdt = io ? io->src_dtype : 0, rdt = io ? io->ref_dtype : 0, odt = io ? io->out_dtype : 0;
     if (!hk::dtype_size(sdt) || !hk::dtype_size(rdt) || !hk::dtype_size(odt)) return fail(HK_ERR_ARG, "unknown dtype");
+    if (io && (rc = validate_out_nodata(odt, io->out_has_nodata, io->out_nodata))) return rc;
     const bool out_cast = io && (odt != 0 || io->out_has_nodata);
     const bool r2 = needs_r2(desc);
     if (params_out && n_param_bands != (r2 ? 3 : 2))
@@ -1623,6 +1642,7 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     if (src_height > 65535 || ref_height > 65535) return fail(HK_ERR_UNSUPPORTED, "block taller than 65535 rows");
     const int sdt = io ? io->src_dtype : 0, rdt = io ? io->ref_dtype : 0, odt = io ? io->out_dtype : 0;
     if (!hk::dtype_size(sdt) || !hk::dtype_size(rdt) || !hk::dtype_size(odt)) return fail(HK_ERR_ARG, "unknown dtype");
+    if (io && (rc = validate_out_nodata(odt, io->out_has_nodata, io->out_nodata))) return rc;
     const bool out_cast = io && (odt != 0 || io->out_has_nodata);
     const bool r2 = needs_r2(desc);
     if (params_out && n_param_bands != (r2 ? 3 : 2))
@@ -3046,6 +3066,37 @@ int hk_debug_inpaint_plane_dev(hk_ctx* ctx, float* plane_dev, const uint8_t* fla
     }
     HK_HIP(hk::launch_inpaint_offsets(plane_dev, gain_dev, r2_dev, thresh, stride, height, width, sl.aux, sl.stream, flags_dev,
                                       n_targets, mode != 3));
+    HK_HIP(hipStreamSynchronize(sl.stream));
+    return HK_OK;
+}
+
+int hk_debug_cast_plane_dev(hk_ctx* ctx, int32_t to_typed, int32_t dtype, const void* src_dev, int64_t src_stride, void* dst_dev,
+                            int64_t dst_stride, int32_t height, int32_t width, int32_t has_nodata, double nodata, int32_t stream) {
+    if (!ctx || !src_dev || !dst_dev) return fail(HK_ERR_ARG, "NULL argument");
+    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (to_typed != 0 && to_typed != 1) return fail(HK_ERR_ARG, "to_typed %d: 0 (cast_in) or 1 (cast_out)", to_typed);
+    const size_t es = hk::dtype_size(dtype);
+    if (!es) return fail(HK_ERR_ARG, "unknown dtype %d", dtype);
+    if (!to_typed && dtype == HK_DTYPE_F32) return fail(HK_ERR_ARG, "float32 has no input conversion");
+    if (height < 1 || width < 1) return fail(HK_ERR_ARG, "bad shape %d x %d", height, width);
+    // a lane takes four columns at once: the float32 side as one 16-byte access, the typed side sample by sample
+    for (const int64_t s : {src_stride, dst_stride})
+        if (s < width || s % 4 != 0) return fail(HK_ERR_ARG, "stride %lld: at least the width (%d) and a multiple of 4", (long long)s, width);
+    const void *f32_plane = to_typed ? src_dev : dst_dev, *typed_plane = to_typed ? static_cast<const void*>(dst_dev) : src_dev;
+    if ((reinterpret_cast<uintptr_t>(f32_plane) & 15u) != 0 || reinterpret_cast<uintptr_t>(typed_plane) % es != 0)
+        return fail(HK_ERR_ARG, "the float32 plane must be 16-byte aligned, the typed plane aligned to its sample size");
+    if (to_typed) {
+        const int rc = validate_out_nodata(dtype, has_nodata, nodata);
+        if (rc) return rc;
+    }
+    HK_ENTER(ctx);
+    DevEnter entered(ctx, stream);
+    Slot& sl = ctx->slots[stream];
+    if (to_typed)
+        HK_HIP(hk::launch_cast_out(dtype, static_cast<const float*>(src_dev), src_stride, dst_dev, dst_stride, height, width, has_nodata,
+                                   nodata, sl.stream));
+    else
+        HK_HIP(hk::launch_cast_in(dtype, src_dev, src_stride, static_cast<float*>(dst_dev), dst_stride, height, width, sl.stream));
     HK_HIP(hipStreamSynchronize(sl.stream));
     return HK_OK;
 }

@@ -586,6 +586,12 @@ class RasterFuse:
             if isinstance(fn, (str, os.PathLike)) and os.path.exists(fn) and not overwrite:
                 raise FileExistsError(f"Corrected / parameter file exists and won't be overwritten: {fn}")
 
+        nodata = out_profile['nodata']
+        out_dtype = np.dtype(out_profile['dtype'])
+        if out_dtype.name not in _hk.DTYPE_CODES:
+            raise ValueError(f"unsupported output dtype '{out_profile['dtype']}'")
+        _hk.out_nodata_code(out_dtype, nodata)  # a nodata the dtype cannot hold is refused (homonim/raster_array.py:357-358)
+
         model_cls = SrcSpaceModel if self._proc_crs == ProcCrs.src else RefSpaceModel
         devices = device_config['devices']
         if devices is None:
@@ -602,10 +608,6 @@ class RasterFuse:
             models.append(m)
 
         n_src = self._src.shape[0]
-        nodata = out_profile['nodata']
-        out_dtype = np.dtype(out_profile['dtype'])
-        if out_dtype.name not in _hk.DTYPE_CODES:
-            raise ValueError(f"unsupported output dtype '{out_profile['dtype']}'")
         fill = (np.nan if out_dtype.kind == 'f' else 0) if nodata is None else nodata
         if corr_out is not None:
             if corr_out.shape != (n_src, *self.shape) or corr_out.dtype != out_dtype or not corr_out.flags['C_CONTIGUOUS']:
@@ -741,6 +743,7 @@ def convert_dtype(array: np.ndarray, dtype: str, nodata: Optional[float]) -> np.
     clip for integer types, NaN (the internal nodata) -> ``nodata``.  ``RasterFuse.process`` does this conversion on the
     device (hk_convert.hip); this helper documents the semantics and serves host-side callers.
     """
+    has_nodata, nodata_value = _hk.out_nodata_code(dtype, nodata)   # refuses a nodata the dtype cannot hold (:357-358)
     invalid = np.isnan(array)
     out = array
     if np.issubdtype(np.dtype(dtype), np.integer):
@@ -748,6 +751,8 @@ def convert_dtype(array: np.ndarray, dtype: str, nodata: Optional[float]) -> np.
         out = np.clip(np.round(array.astype(np.promote_types(array.dtype, dtype))), info.min, info.max)
     with np.errstate(invalid='ignore', over='ignore'):
         out = out.astype(dtype, copy=(out is array))
-    if nodata is not None:
-        out[invalid] = nodata
+    if has_nodata:
+        out[invalid] = nodata_value
+    elif np.issubdtype(np.dtype(dtype), np.integer):
+        out[invalid] = 0   # the reference leaves NaN -> integer to the platform; the device's conversion gives 0 (hk_convert.hip)
     return out

@@ -100,6 +100,20 @@ int hk_debug_inpaint_plane_dev(hk_ctx* ctx, float* plane_dev, const uint8_t* fla
                                const float* r2_dev, float thresh, int32_t height, int32_t width, int64_t stride,
                                int32_t mode, int32_t stream);
 
+/* Test aid: one of the two dtype conversions of hk_convert.hip alone on device-resident planes, where hk_fit_apply_io and its kin
+ * only ever hand them their own staging buffers at one stride.  `to_typed` 0: cast_in, `src_dev` holds `dtype` samples
+ * (HK_DTYPE_U8 .. HK_DTYPE_F64; float32 has no input conversion) and `dst_dev` receives float32; 1: cast_out, `src_dev` holds
+ * float32 and `dst_dev` receives `dtype` samples (any hk_dtype), NaN becoming `nodata` when `has_nodata` (else staying NaN in a
+ * float type and becoming 0 in an integer type).  Rows are `src_stride` / `dst_stride` ELEMENTS of the respective type apart, the
+ * two independent of each other.  Both kernels work on whole groups of four columns: the group that holds column width - 1 is
+ * read and written to its end, so the up to three padding columns behind `width` in a destination row receive the conversion of
+ * the source row's padding; columns behind that group are not touched.  Runs on pooled stream `stream` and synchronises it before
+ * returning.  HK_ERR_ARG, before anything is launched, for what the kernels do not take: a shape below 1 x 1, a stride below the
+ * width or not a multiple of 4, a float32 plane that is not 16-byte aligned or a typed plane not aligned to its sample size, an
+ * unknown dtype, dtype 0 with to_typed 0, and (to_typed 1) a nodata the dtype cannot hold, as hk_fit_apply_io refuses it. */
+int hk_debug_cast_plane_dev(hk_ctx* ctx, int32_t to_typed, int32_t dtype, const void* src_dev, int64_t src_stride, void* dst_dev,
+                            int64_t dst_stride, int32_t height, int32_t width, int32_t has_nodata, double nodata, int32_t stream);
+
 #ifdef __cplusplus
 }
 #endif
