@@ -16,7 +16,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from homonim_amd.errors import DeviceError
+from homonim_amd.errors import DeviceError, IoError
 
 # HOMONIM_AMD_LIB overrides the library path (kernel-variant experiments); the default is the in-tree build.
 _LIB_PATH = os.environ.get('HOMONIM_AMD_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib',
@@ -70,6 +70,13 @@ class AffineWarpDesc(C.Structure):
 class OutWindow(C.Structure):
     _fields_ = [('stride', C.c_int64), ('band_stride', C.c_int64), ('row0', C.c_int32), ('col0', C.c_int32),
                 ('rows', C.c_int32), ('cols', C.c_int32), ('param_stride', C.c_int64)]
+
+
+class InflateLayout(C.Structure):
+    """ hk_inflate_layout: the blocks of one GeoTIFF image (the fields of ``tiff.BlockLayout``, in its order) """
+    _fields_ = [('sample_bytes', C.c_int32), ('spp', C.c_int32), ('height', C.c_int32), ('width', C.c_int32),
+                ('block_w', C.c_int32), ('block_h', C.c_int32), ('tiled', C.c_int32), ('separate', C.c_int32),
+                ('predictor', C.c_int32)]
 
 
 class DevJob(C.Structure):
@@ -129,6 +136,11 @@ SIGNATURES = {
                                    C.c_void_p, C.c_int64, _P(C.c_int64), _P(C.c_int64)]),
     'hk_deflate_tiles_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                        C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]),
+    'hk_inflate_bound': (C.c_int, [_P(InflateLayout), _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
+    'hk_inflate_image': (C.c_int, [C.c_void_p, _P(InflateLayout), C.c_void_p, _P(C.c_int64), _P(C.c_int64), C.c_void_p, C.c_int64,
+                                   C.c_int64, _P(C.c_int32)]),
+    'hk_inflate_image_dev': (C.c_int, [C.c_void_p, _P(InflateLayout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int64, C.c_int64, C.c_void_p, C.c_int32]),
     'hk_fit': (C.c_int, [C.c_void_p, _P(FitDesc), _f32p, C.c_int64, _f32p, C.c_int64, C.c_int32, C.c_int32, _f64p,
                          _f32p, C.c_int32, _f64p, _u64p]),
     'hk_apply': (C.c_int, [C.c_void_p, _f32p, C.c_int64, _f32p, C.c_int32, C.c_int32, _f32p]),
@@ -239,6 +251,26 @@ def deflate_bound(dtype, n_bands: int, height: int, width: int, tile: int):
     _check(load_library().hk_deflate_bound(DTYPE_CODES[np.dtype(dtype).name], n_bands, height, width, int(tile), C.byref(n_tiles),
                                            C.byref(cap)))
     return n_tiles.value, cap.value
+
+
+# HK_INFLATE_*: the status of a block of Context.inflate_image_packed
+(INFLATE_OK, INFLATE_TRUNCATED, INFLATE_BAD_HEADER, INFLATE_BAD_BLOCK, INFLATE_BAD_STORED, INFLATE_BAD_CODE, INFLATE_BAD_SYMBOL,
+ INFLATE_FAR, INFLATE_OVERRUN, INFLATE_SHORT, INFLATE_ADLER) = range(11)
+
+
+def _inflate_layout(layout) -> InflateLayout:
+    """ a ``tiff.BlockLayout`` (or anything with its fields, or an InflateLayout) as the C struct """
+    if isinstance(layout, InflateLayout):
+        return layout
+    return InflateLayout(*[int(getattr(layout, name)) for name, _ in InflateLayout._fields_])
+
+
+def inflate_bound(layout):
+    """ -> (number of blocks, raw bytes of a full block, bytes of device scratch of ``Context.inflate_image_dev``) for the
+    blocks of an image (hk_inflate_bound; no device needed). """
+    n_blocks, raw, work = C.c_int64(), C.c_int64(), C.c_int64()
+    _check(load_library().hk_inflate_bound(C.byref(_inflate_layout(layout)), C.byref(n_blocks), C.byref(raw), C.byref(work)))
+    return n_blocks.value, raw.value, work.value
 
 
 def comm_unique_id() -> bytes:
@@ -551,6 +583,46 @@ class Context:
         ``write_tiff`` accepts; rows and bands may be strided (unit column stride), anything else is copied first. """
         out, offsets, sizes = self.deflate_tiles_packed(array, tile)
         return [out[o:o + n].tobytes() for o, n in zip(offsets[:-1].tolist(), sizes.tolist())]
+
+    def inflate_image_packed(self, streams, offsets, sizes, layout, strict: bool = True):
+        """ The image of ``layout`` (a ``tiff.BlockLayout``) from the zlib streams of its blocks, inflated, un-predicted and put
+        in place on the device (hk_inflate_image): block b's stream is ``streams[offsets[b]:offsets[b] + sizes[b]]`` (``streams``:
+        bytes or a uint8 array).  -> (array (spp, height, width) of uint8 / 16 / 32 / 64, int32 status per block).  A block whose
+        stream is refused has a status other than 0 (``INFLATE_*``) and unspecified pixels; ``strict``: it raises ``IoError``
+        naming the first such block instead. """
+        lay = _inflate_layout(layout)
+        n_blocks, _, _ = inflate_bound(lay)
+        buf = np.frombuffer(streams, np.uint8) if isinstance(streams, (bytes, bytearray, memoryview)) else np.ascontiguousarray(streams, np.uint8)
+        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+        if offsets.shape != (n_blocks,) or sizes.shape != (n_blocks,):
+            raise ValueError(f'{offsets.size} offsets and {sizes.size} sizes for {n_blocks} blocks')
+        if n_blocks and ((offsets < 0).any() or (sizes < 0).any() or (offsets + sizes > buf.size).any()):
+            raise ValueError('a stream lies outside the buffer')
+        if buf.size == 0:
+            buf = np.zeros(1, np.uint8)   # (every stream is empty: a pointer all the same)
+        out = np.empty((lay.spp, lay.height, lay.width), np.dtype(f'u{lay.sample_bytes}'))
+        status = np.zeros(n_blocks, np.int32)
+        rc = self._lib.hk_inflate_image(self._h, C.byref(lay), buf.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(_P(C.c_int64)),
+                                        sizes.ctypes.data_as(_P(C.c_int64)), out.ctypes.data_as(C.c_void_p), lay.width,
+                                        lay.height * lay.width, status.ctypes.data_as(_P(C.c_int32)))
+        if rc == HK_ERR_ARG and status.any():
+            if strict:
+                raise IoError(self._lib.hk_last_error().decode('utf-8', 'replace'))
+            return out, status
+        _check(rc)
+        return out, status
+
+    def inflate_image(self, streams, layout) -> np.ndarray:
+        """ What ``tiff.read_tiff`` takes as ``inflater``: the zlib streams of an image's blocks (a list of ``bytes``, in the
+        file's block order) -> its (spp, height, width) array of uint8 / 16 / 32 / 64, inflated on the device
+        (``inflate_image_packed``).  ``IoError`` names the first block whose stream is refused, and why. """
+        sizes = np.array([len(s) for s in streams], np.int64)
+        padded = (sizes + 15) // 16 * 16
+        offsets = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64) if len(sizes) else np.zeros(0, np.int64)
+        buf = np.zeros(int(padded.sum()), np.uint8)
+        for o, s in zip(offsets.tolist(), streams):
+            buf[o:o + len(s)] = np.frombuffer(s, np.uint8)
+        return self.inflate_image_packed(buf, offsets, sizes, layout, strict=True)[0]
 
     def fit_apply(self, desc: FitDesc, src: np.ndarray, ref: np.ndarray, n_param_bands: int, want_params: bool,
                   want_corr: bool, norm_in: Optional[np.ndarray] = None, out_params: Optional[np.ndarray] = None,
@@ -1171,6 +1243,15 @@ class Context:
         _check(self._lib.hk_deflate_tiles_dev(self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height,
                                               width, stride, band_stride, tile, C.c_void_p(out_dptr), out_capacity,
                                               C.c_void_p(offsets_dptr), C.c_void_p(sizes_dptr), stream))
+
+    def inflate_image_dev(self, layout, streams_dptr: int, offsets_dptr: int, sizes_dptr: int, work_dptr: int, out_dptr: int,
+                          stride: int, band_stride: int, status_dptr: int, stream: int = 0):
+        """ Queue the inflation of an image's blocks from device-resident streams (``n_blocks`` int64 offsets and sizes) into the
+        raster at ``out_dptr`` (strides in elements) and ``n_blocks`` int32 statuses at ``status_dptr``; ``work_dptr``:
+        ``inflate_bound``'s scratch bytes (hk_inflate_image_dev; asynchronous). """
+        _check(self._lib.hk_inflate_image_dev(self._h, C.byref(_inflate_layout(layout)), C.c_void_p(streams_dptr), C.c_void_p(offsets_dptr),
+                                              C.c_void_p(sizes_dptr), C.c_void_p(work_dptr), C.c_void_p(out_dptr), stride, band_stride,
+                                              C.c_void_p(status_dptr), stream))
 
     def synth_fill_dev(self, src_dptr, ref_dptr, n_bands, height, width, stride, band_stride, seed=0, nodata_variant=0,
                        stream=0):

@@ -2666,6 +2666,200 @@ int hk_deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_b
     return HK_OK;
 }
 
+// INFLATE of a GeoTIFF image's blocks (hk_inflate.hip): see include/homonim_hk.h
+struct InflateShape {
+    int64_t planes, across, down, n_blocks, raw, slot;   // planes of blocks (spp if separate, else 1); full block raw bytes; its slot
+    int cspp;
+};
+
+static int inflate_shape(const hk_inflate_layout* l, InflateShape* s) {
+    if (!l) return fail(HK_ERR_ARG, "layout is NULL");
+    if (l->sample_bytes != 1 && l->sample_bytes != 2 && l->sample_bytes != 4 && l->sample_bytes != 8)
+        return fail(HK_ERR_ARG, "sample_bytes %d is not 1, 2, 4 or 8", l->sample_bytes);
+    if (l->spp < 1 || l->height < 1 || l->width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d x %d", l->spp, l->height, l->width);
+    if (l->block_w < 1 || l->block_h < 1) return fail(HK_ERR_ARG, "empty block %d x %d", l->block_h, l->block_w);
+    if (l->predictor != 1 && l->predictor != 2) return fail(HK_ERR_ARG, "predictor %d is not 1 or 2", l->predictor);
+    if ((l->tiled != 0 && l->tiled != 1) || (l->separate != 0 && l->separate != 1)) return fail(HK_ERR_ARG, "tiled and separate are 0 or 1");
+    if (!l->tiled && l->block_w != l->width) return fail(HK_ERR_ARG, "a strip is as wide as the image: block_w %d, width %d", l->block_w, l->width);
+    s->cspp = l->separate ? 1 : l->spp;
+    s->planes = l->separate ? l->spp : 1;
+    s->across = ((int64_t)l->width + l->block_w - 1) / l->block_w, s->down = ((int64_t)l->height + l->block_h - 1) / l->block_h;
+    // (four factors below 2^31: the first product fits, the second is checked before it is made)
+    const int64_t px = (int64_t)l->block_w * l->block_h;
+    if (px > HK_INFLATE_MAX_BLOCK || px * s->cspp > HK_INFLATE_MAX_BLOCK / l->sample_bytes)
+        return fail(HK_ERR_ARG, "a block of %d x %d x %d samples of %d bytes is more than %d bytes", l->block_h, l->block_w, s->cspp,
+                    l->sample_bytes, HK_INFLATE_MAX_BLOCK);
+    s->raw = px * s->cspp * l->sample_bytes;
+    s->slot = (s->raw + 15) / 16 * 16;
+    if (s->across * s->down > (1ll << 40) / s->planes || s->planes * s->across * s->down > (1ll << 62) / s->slot)
+        return fail(HK_ERR_ARG, "too many blocks: %lld x %lld x %lld of %lld bytes", (long long)s->planes, (long long)s->down,
+                    (long long)s->across, (long long)s->slot);
+    s->n_blocks = s->planes * s->across * s->down;
+    return HK_OK;
+}
+
+int hk_inflate_bound(const hk_inflate_layout* layout, int64_t* n_blocks, int64_t* raw_block_bytes, int64_t* work_bytes) {
+    if (!n_blocks || !raw_block_bytes || !work_bytes) return fail(HK_ERR_ARG, "NULL pointer argument");
+    InflateShape s;
+    const int rc = inflate_shape(layout, &s);
+    if (rc) return rc;
+    *n_blocks = s.n_blocks, *raw_block_bytes = s.raw, *work_bytes = s.n_blocks * s.slot;
+    return HK_OK;
+}
+
+static const char* inflate_status_text(int st) {
+    static const char* const text[] = {"ok", "the stream ends too soon", "bad zlib header", "invalid block type",
+                                       "invalid stored block lengths", "invalid code lengths in a dynamic header",
+                                       "invalid literal/length or distance code", "distance too far back",
+                                       "the stream holds more than the block's bytes", "the stream ends before the block's bytes are there",
+                                       "incorrect Adler-32 check"};
+    return st >= 0 && st <= HK_INFLATE_ADLER ? text[st] : "unknown status";
+}
+
+static hk::InflateArgs inflate_args(const hk_inflate_layout* l, const InflateShape& s, int32_t height) {
+    hk::InflateArgs a;
+    memset(&a, 0, sizeof(a));
+    a.es = l->sample_bytes, a.height = height, a.width = l->width, a.bw = l->block_w, a.bh = l->block_h;
+    a.tiled = l->tiled, a.separate = l->separate, a.predictor = l->predictor, a.cspp = s.cspp;
+    a.across = (int)s.across, a.down = (int)(((int64_t)height + l->block_h - 1) / l->block_h), a.slot = s.slot;
+    return a;
+}
+
+static int check_inflate(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
+                         const void* out, int64_t stride, int64_t band_stride, InflateShape* s) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    const int rc = inflate_shape(layout, s);
+    if (rc) return rc;
+    if (!streams || !offsets || !sizes || !out) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (stride < layout->width) return fail(HK_ERR_ARG, "row stride smaller than width");
+    if (band_stride < 0 || (layout->spp > 1 && band_stride < stride * (layout->height - 1) + layout->width))
+        return fail(HK_ERR_ARG, "band_stride %lld is smaller than a plane", (long long)band_stride);
+    return HK_OK;
+}
+
+int hk_inflate_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
+                         const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
+                         int32_t* status_dev, int32_t stream) {
+    InflateShape s;
+    int rc = check_inflate(ctx, layout, streams_dev, offsets_dev, sizes_dev, out_dev, stride, band_stride, &s);
+    if (rc) return rc;
+    if (!work_dev || !status_dev) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if ((uintptr_t)work_dev % 16) return fail(HK_ERR_ARG, "work_dev is not 16-byte aligned");
+    if ((uintptr_t)out_dev % layout->sample_bytes) return fail(HK_ERR_ARG, "out_dev is not aligned to its samples");
+    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (s.n_blocks > 0x7FFFFFFFll) return fail(HK_ERR_ARG, "%lld blocks are more than one launch takes", (long long)s.n_blocks);
+    DevEnter entered(ctx, stream);
+    HK_ENTER(ctx);
+    hk::InflateArgs a = inflate_args(layout, s, layout->height);
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "offsets, sizes and statuses are handed on as they are");
+    a.streams = streams_dev, a.offsets = reinterpret_cast<const long long*>(offsets_dev), a.sizes = reinterpret_cast<const long long*>(sizes_dev);
+    a.work = static_cast<unsigned char*>(work_dev), a.status = status_dev, a.out = out_dev, a.stride = stride, a.band_stride = band_stride;
+    HK_HIP(hk::launch_inflate_image(a, s.n_blocks, ctx->slots[stream].stream));
+    return HK_OK;
+}
+
+// block rows per group of the host path: whole block rows of ALL planes, at most INFLATE_GROUP_BYTES of raw bytes (at least one
+// block row); HK_INFLATE_GROUP_KB (read at every call) lowers the bound for tests of the group path.  Blocks are independent, so
+// the grouping cannot change a byte.  Per group and plane the compressed bytes travel as ONE span of the caller's buffer, from the
+// first byte of the group's first stream to the last byte of its last one (a TIFF writer lays the blocks of a plane down in order).
+constexpr size_t INFLATE_GROUP_BYTES = 64u << 20;
+
+int hk_inflate_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
+                     void* out, int64_t stride, int64_t band_stride, int32_t* status) {
+    InflateShape s;
+    int rc = check_inflate(ctx, layout, streams, offsets, sizes, out, stride, band_stride, &s);
+    if (rc) return rc;
+    for (int64_t b = 0; b < s.n_blocks; ++b)
+        if (offsets[b] < 0 || sizes[b] < 0) return fail(HK_ERR_ARG, "block %lld: offset %lld, size %lld", (long long)b, (long long)offsets[b], (long long)sizes[b]);
+    HK_ENTER(ctx);
+    const size_t es = (size_t)layout->sample_bytes;
+    const int64_t bh = layout->block_h, per = s.across * s.down;
+    const char* e = getenv("HK_INFLATE_GROUP_KB");
+    const size_t cap = (e && atol(e) > 0) ? (size_t)atol(e) << 10 : INFLATE_GROUP_BYTES;
+    const int64_t row_raw = s.planes * s.across * s.slot;   // slots of one block row
+    const int64_t g_down = std::max<int64_t>(1, std::min<int64_t>(s.down, (int64_t)(cap / (size_t)row_raw)));
+    const int64_t g_blocks = s.planes * g_down * s.across;
+    if (g_blocks > 0x7FFFFFFFll) return fail(HK_ERR_ARG, "%lld blocks are more than one launch takes", (long long)g_blocks);
+    // the spans of every group and plane: where they start in the caller's buffer and how long they are; the largest sum over a group
+    struct Span { int64_t lo, hi; };
+    auto span_of = [&](int64_t plane, int64_t by0, int64_t by1) {
+        Span sp{INT64_MAX, 0};
+        for (int64_t b = plane * per + by0 * s.across; b < plane * per + by1 * s.across; ++b)
+            if (sizes[b] > 0) sp.lo = std::min(sp.lo, offsets[b]), sp.hi = std::max(sp.hi, offsets[b] + sizes[b]);
+        if (sp.lo > sp.hi) sp.lo = sp.hi = 0;
+        sp.lo &= ~(int64_t)15;   // (the device copy keeps the streams' places within their 16-byte groups)
+        return sp;
+    };
+    size_t in_bytes = 0;
+    for (int64_t by0 = 0; by0 < s.down; by0 += g_down) {
+        size_t sum = 0;
+        for (int64_t p = 0; p < s.planes; ++p) {
+            const Span sp = span_of(p, by0, std::min(s.down, by0 + g_down));
+            sum += ((size_t)(sp.hi - sp.lo) + 255) / 256 * 256;
+        }
+        in_bytes = std::max(in_bytes, sum);
+    }
+    // device slab of one group: the compressed spans, offsets and sizes, the statuses, the slots, the group's rows of every band
+    // (padded to ROW_ALIGN elements: 16-byte stores are legal)
+    SlabLayout L;
+    const int64_t d_stride = (layout->width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    const int64_t g_rows = std::min<int64_t>(g_down * bh, layout->height);
+    const size_t o_in = L.take(in_bytes);
+    const size_t o_off = L.take((size_t)g_blocks * sizeof(int64_t));
+    const size_t o_siz = L.take((size_t)g_blocks * sizeof(int64_t));
+    const size_t o_st = L.take((size_t)g_blocks * sizeof(int32_t));
+    const size_t o_work = L.take((size_t)g_blocks * (size_t)s.slot);
+    const size_t o_out = L.take((size_t)layout->spp * g_rows * d_stride * es);
+    SlotLease lease(ctx);
+    Slot& sl = lease.slot();
+    if ((rc = ensure_dev(sl, L.total))) return rc;
+    char* base = static_cast<char*>(sl.dev);
+    const char* h_in = static_cast<const char*>(streams);
+    char* h_out = static_cast<char*>(out);
+    std::vector<int64_t> g_off((size_t)g_blocks), g_siz((size_t)g_blocks);
+    std::vector<int32_t> g_st((size_t)g_blocks);
+    int64_t first_bad = -1;
+    int32_t first_status = 0;
+    for (int64_t by0 = 0; by0 < s.down; by0 += g_down) {
+        const int64_t by1 = std::min(s.down, by0 + g_down), n_down = by1 - by0, nb = s.planes * n_down * s.across;
+        const int64_t r0 = by0 * bh, rows = std::min<int64_t>(n_down * bh, layout->height - r0);
+        size_t at = 0;
+        for (int64_t p = 0; p < s.planes; ++p) {
+            const Span sp = span_of(p, by0, by1);
+            if ((rc = stage_h2d(sl, base + o_in + at, 0, h_in + sp.lo, 0, (size_t)(sp.hi - sp.lo), 1))) return rc;
+            for (int64_t k = 0; k < n_down * s.across; ++k) {
+                const int64_t b = p * per + by0 * s.across + k;
+                g_off[(size_t)(p * n_down * s.across + k)] = sizes[b] > 0 ? (int64_t)at + offsets[b] - sp.lo : 0;
+                g_siz[(size_t)(p * n_down * s.across + k)] = sizes[b];
+            }
+            at += ((size_t)(sp.hi - sp.lo) + 255) / 256 * 256;
+        }
+        if ((rc = stage_h2d(sl, base + o_off, 0, g_off.data(), 0, (size_t)nb * sizeof(int64_t), 1))) return rc;
+        if ((rc = stage_h2d(sl, base + o_siz, 0, g_siz.data(), 0, (size_t)nb * sizeof(int64_t), 1))) return rc;
+        hk::InflateArgs a = inflate_args(layout, s, (int32_t)rows);
+        a.streams = base + o_in, a.offsets = reinterpret_cast<const long long*>(base + o_off), a.sizes = reinterpret_cast<const long long*>(base + o_siz);
+        a.work = reinterpret_cast<unsigned char*>(base + o_work), a.status = reinterpret_cast<int*>(base + o_st);
+        a.out = base + o_out, a.stride = d_stride, a.band_stride = rows * d_stride;
+        HK_HIP(hk::launch_inflate_image(a, nb, sl.stream));
+        if ((rc = stage_d2h(sl, g_st.data(), 0, base + o_st, 0, (size_t)nb * sizeof(int32_t), 1))) return rc;
+        for (int c = 0; c < layout->spp; ++c)
+            if ((rc = stage_d2h(sl, h_out + ((size_t)c * band_stride + (size_t)r0 * stride) * es, stride * es,
+                                base + o_out + (size_t)c * rows * d_stride * es, d_stride * es, (size_t)layout->width * es, rows)))
+                return rc;
+        if ((rc = stage_finish(sl))) return rc;
+        for (int64_t p = 0; p < s.planes; ++p)
+            for (int64_t k = 0; k < n_down * s.across; ++k) {
+                const int64_t b = p * per + by0 * s.across + k;
+                const int32_t st = g_st[(size_t)(p * n_down * s.across + k)];
+                if (status) status[b] = st;
+                if (st && (first_bad < 0 || b < first_bad)) first_bad = b, first_status = st;
+            }
+    }
+    if (first_bad >= 0)
+        return fail(HK_ERR_ARG, "inflate: block %lld is refused: %s (status %d)", (long long)first_bad, inflate_status_text(first_status), first_status);
+    return HK_OK;
+}
+
 int hk_block_norm_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_job* job, double* norm_dev) {
     int rc = validate_desc(desc);
     if (rc) return rc;

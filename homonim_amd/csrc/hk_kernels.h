@@ -283,6 +283,27 @@ hipError_t launch_deflate_tiles(const void* src, int esize, int n_bands, int hei
                                 long long band_stride, int tile, void* work, unsigned char* out, long long* tile_offsets,
                                 long long* tile_sizes, hipStream_t stream);
 
+// The DEFLATE blocks (tiles or strips) of a GeoTIFF image inflated into a (spp, height, width) raster (hk_inflate.hip, which states
+// the contract): block b's zlib stream is the sizes[b] bytes at streams + offsets[b]; blocks are ordered plane (separate only),
+// block row, block column.  `work`: n_blocks slots of `slot` bytes (the raw size of a full block rounded up to 16; 16-byte
+// aligned); status[b]: 0 or the HK_INFLATE_* code of a block that was refused and left out of the raster.  Strides in elements.
+// All pointers are device memory; everything is queued on `stream`.
+struct InflateArgs {
+    const void* streams;
+    const long long* offsets;
+    const long long* sizes;
+    unsigned char* work;
+    int* status;
+    void* out;
+    long long stride, band_stride, slot;
+    int es, height, width, bw, bh;   // sample bytes; the image; the block (a strip: bw = width)
+    int tiled, separate, predictor;  // as hk_inflate_layout
+    int cspp;                        // samples of a pixel in one block: spp of a pixel-interleaved image, else 1
+    int across, down;                // blocks per block row, block rows
+    int vec_ok;                      // set by the launcher: rows may move as 16-byte groups
+};
+hipError_t launch_inflate_image(InflateArgs a, long long n_blocks, hipStream_t stream);
+
 hipError_t launch_synth_fill(float* src, float* ref, int n_bands, int height, int width, long long stride,
                              long long band_stride, unsigned long long seed, int nodata_variant, hipStream_t stream);
 

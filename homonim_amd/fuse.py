@@ -269,8 +269,10 @@ class RasterFuse:
     def __init__(self, src: Union[np.ndarray, RasterArray], ref: Union[np.ndarray, RasterArray],
                  src_nodata: Optional[float] = float('nan'), ref_nodata: Optional[float] = float('nan'),
                  proc_crs: ProcCrs = ProcCrs.auto, crs: Optional[CRS] = None, transform: Optional[Affine] = None,
-                 ref_transform: Optional[Affine] = None, ref_crs: Optional[CRS] = None):
+                 ref_transform: Optional[Affine] = None, ref_crs: Optional[CRS] = None, inflate: str = 'host'):
         """
+        ``inflate``: who inflates the DEFLATE blocks of ``src`` / ``ref`` given as GeoTIFF paths: 'host' (default) -- zlib on
+        this thread, as ever; 'device' -- ``Context.inflate_image`` of the process-wide context: the same pixels.
         ``transform`` / ``ref_transform``: geo-transforms of the source / reference rasters (north-up).  When they (or the
         shapes) differ, blocks are cut on the processing grid and re-sampled on the device as the reference does through
         GDAL (RefSpaceModel / SrcSpaceModel); the reference must cover the source.  ``crs`` / ``ref_crs``: their CRSs (taken
@@ -278,17 +280,22 @@ class RasterFuse:
         image -- ``proc_crs=src``: the source, otherwise the reference -- is first warped into the other's CRS
         (``_to_one_crs``), with the reference's warning.
         """
+        if inflate not in ('host', 'device'):
+            raise ValueError(f"`inflate` must be 'host' or 'device', not {inflate!r}")
+        inflater = None
+        if inflate == 'device' and any(isinstance(x, (str, os.PathLike)) for x in (src, ref)):
+            inflater = _hk.default_context().inflate_image
         self._src_filename = self._ref_filename = None
         self._ref_descriptions = ()   # band descriptions of a reference opened from a file (name the parameter bands)
         if isinstance(src, (str, os.PathLike)):  # a GeoTIFF, as homonim.RasterFuse(src_filename, ref_filename, ...)
             from homonim_amd.tiff import read_tiff
             self._src_filename = os.fspath(src)
-            tif = read_tiff(src)
+            tif = read_tiff(src, inflater=inflater)
             src, src_nodata, crs, transform = tif.array, tif.nodata, tif.crs, tif.transform
         if isinstance(ref, (str, os.PathLike)):
             from homonim_amd.tiff import read_tiff
             self._ref_filename = os.fspath(ref)
-            tif = read_tiff(ref)
+            tif = read_tiff(ref, inflater=inflater)
             ref, ref_nodata, ref_transform, ref_crs = tif.array, tif.nodata, tif.transform, tif.crs
             self._ref_descriptions = tif.descriptions
         if isinstance(src, RasterArray):

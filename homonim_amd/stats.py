@@ -78,9 +78,13 @@ class ParamStats:
     )  # yapf: disable
 
     def __init__(self, param_filename: Union[str, os.PathLike], context: Optional['_hk.Context'] = None,
-                 strip_bytes: Optional[int] = None):
+                 strip_bytes: Optional[int] = None, inflate: str = 'host'):
         """ ``context``: the GPU context to reduce on (default: the process-wide one, created on first use).
-        ``strip_bytes``: see ``STRIP_BYTES``. """
+        ``strip_bytes``: see ``STRIP_BYTES``.  ``inflate``: who inflates the file's DEFLATE blocks: 'host' (default) -- zlib on
+        the reading thread; 'device' -- ``Context.inflate_image`` of the same context: the same pixels. """
+        if inflate not in ('host', 'device'):
+            raise ValueError(f"`inflate` must be 'host' or 'device', not {inflate!r}")
+        self._inflate = inflate
         self._param_filename = pathlib.Path(param_filename)
         header = utils.validate_param_image(self._param_filename)
         self._init(header.metadata, header.descriptions, context, strip_bytes)
@@ -162,7 +166,8 @@ class ParamStats:
             if not self._from_file:
                 raise IoError('The parameter raster has been closed')
             from homonim_amd.tiff import read_tiff
-            array = read_tiff(self._param_filename).array
+            inflater = self._get_context().inflate_image if getattr(self, '_inflate', 'host') == 'device' else None
+            array = read_tiff(self._param_filename, inflater=inflater).array
             self._array = np.ascontiguousarray(array, dtype=np.float32)
         return self
 
@@ -275,11 +280,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     parser = argparse.ArgumentParser(prog='python -m homonim_amd.stats', description='Report parameter statistics.')
     parser.add_argument('param_files', nargs='+', metavar='FILE', help='Path(s) to parameter image(s).')
     parser.add_argument('-o', '--output', metavar='FILE', default=None, help='Write results to this json file.')
+    parser.add_argument('--inflate', choices=('host', 'device'), default='host',
+                        help="Who inflates the files' DEFLATE blocks: zlib on the host (default) or the GPU.")
     args = parser.parse_args(argv)
     param_stats = []
     for name in args.param_files:
         try:
-            param_stats.append(ParamStats(name))
+            param_stats.append(ParamStats(name, inflate=args.inflate))
         except (FileNotFoundError, ImageFormatError) as ex:
             parser.error(f"Invalid value for 'FILE': {ex}")
     stats_dict = {}

@@ -57,6 +57,20 @@ class TiffHeader(NamedTuple):
     descriptions: Tuple[Optional[str], ...]
 
 
+class BlockLayout(NamedTuple):
+    """ How the blocks (tiles or strips) of one image lie in its raster: what an ``inflater`` of ``read_tiff`` is told (the
+    fields of hk_inflate_layout, include/homonim_hk.h, in its order). """
+    sample_bytes: int            # 1, 2, 4, 8; the samples are little-endian
+    spp: int
+    height: int
+    width: int
+    block_w: int                 # tile size; strips: the image's width and the rows per strip
+    block_h: int
+    tiled: int                   # 1: every block holds block_h rows; 0: the last strip is short
+    separate: int                # 1: one plane per block, blocks ordered plane, block row, block column; 0: pixel-interleaved
+    predictor: int               # 1 none, 2 horizontal differencing
+
+
 def _read_ifd(buf: bytes, offset: Optional[int] = None):
     """ -> (byte order, tags, offset of the next directory or 0) of the directory at ``offset`` (None: the file's first) """
     if buf[:2] == b'II':
@@ -191,19 +205,25 @@ def read_tiff_header(path) -> TiffHeader:
     return TiffHeader(spp, h, w, dtype, tf, crs, _nodata_tag(t), _metadata(t), _descriptions(t, spp))
 
 
-def read_tiff(path) -> TiffRaster:
-    """ Read the first image of a GeoTIFF into a (bands, height, width) array. """
+def read_tiff(path, inflater=None) -> TiffRaster:
+    """ Read the first image of a GeoTIFF into a (bands, height, width) array.  ``inflater``: a callable ``(streams, layout) ->
+    array`` that takes the zlib streams of ALL blocks of a DEFLATE image (a list of ``bytes`` in the file's block order) and
+    their ``BlockLayout`` and returns the image as a (spp, height, width) array of unsigned integers of the sample size, the
+    predictor undone, in place of ``zlib.decompress`` block after block on this thread (e.g. ``Context.inflate_image``: this
+    module itself imports no GPU code).  It is handed little-endian DEFLATE images only; anything else, and everything with
+    None, is decoded here as ever. """
     with open(path, 'rb') as f:
         buf = f.read()
     bo, t, _ = _read_ifd(buf)
-    out = _decode_image(buf, bo, t)
+    out = _decode_image(buf, bo, t, inflater)
     tf, crs = _geo(t, out.shape[1])
     return TiffRaster(out, tf, crs, _nodata_tag(t), _metadata(t), _descriptions(t, out.shape[0]))
 
 
-def read_tiff_overviews(path) -> List[np.ndarray]:
+def read_tiff_overviews(path, inflater=None) -> List[np.ndarray]:
     """ The internal overviews of a GeoTIFF: the reduced-resolution images (NewSubfileType bit 0) chained behind the first, in
-    file order, each as a (bands, height, width) array.  ``[]`` for a file without any. """
+    file order, each as a (bands, height, width) array.  ``[]`` for a file without any.  ``inflater``: as in ``read_tiff``, called
+    once per level. """
     with open(path, 'rb') as f:
         buf = f.read()
     bo, t, nxt = _read_ifd(buf)
@@ -212,12 +232,12 @@ def read_tiff_overviews(path) -> List[np.ndarray]:
         seen.add(nxt)
         bo, t, following = _read_ifd(buf, nxt)
         if t.get(T_SUBFILE, (0,))[0] & 1:
-            out.append(_decode_image(buf, bo, t))
+            out.append(_decode_image(buf, bo, t, inflater))
         nxt = following
     return out
 
 
-def _decode_image(buf, bo, t) -> np.ndarray:
+def _decode_image(buf, bo, t, inflater=None) -> np.ndarray:
     """ The pixels of the image a directory describes, (bands, height, width) in native byte order """
     w, h = t[T_WIDTH][0], t[T_HEIGHT][0]
     spp = t.get(T_SPP, (1,))[0]
@@ -241,6 +261,14 @@ def _decode_image(buf, bo, t) -> np.ndarray:
     across, down = -(-w // bw), -(-h // bh)
     chunk_spp = 1 if planar == 2 else spp
     tiled = T_TILE_OFFSETS in t
+    if inflater is not None and compression != 1 and bo == '<':
+        if len(offs) != len(cnts) or len(offs) != (spp if planar == 2 else 1) * across * down:
+            raise IoError(f'{len(offs)} block offsets and {len(cnts)} byte counts for {(spp if planar == 2 else 1) * across * down} blocks')
+        layout = BlockLayout(dtype.itemsize, spp, h, w, bw, bh, int(tiled), int(planar == 2), predictor)
+        got = np.asarray(inflater([bytes(buf[off:off + cnt]) for off, cnt in zip(offs, cnts)], layout))
+        if got.shape != (spp, h, w) or got.dtype.itemsize != dtype.itemsize:
+            raise IoError(f'the inflater returned {got.shape} of {got.dtype} for an image of {(spp, h, w)} of {dtype}')
+        return np.ascontiguousarray(got).view(dtype.newbyteorder('='))
     out = np.empty((spp, h, w), dtype.newbyteorder('='))
     for idx, (off, cnt) in enumerate(zip(offs, cnts)):
         plane, rem = divmod(idx, across * down) if planar == 2 else (0, idx)

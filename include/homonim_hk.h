@@ -75,7 +75,10 @@ typedef struct {
  * points (hk_warp_coords, hk_warp_coords_dev, hk_reproject_crs, hk_reproject_crs_dev, hk_reproject_dev); version 10 added
  * hk_affine_warp_desc and entry points (hk_warp_coords_affine, hk_warp_coords_affine_dev, hk_reproject_affine,
  * hk_reproject_affine_dev); version 11 added hk_srcspace_desc and the entry point hk_srcspace_fit_apply; version 12 added entry
- * points (hk_deflate_bound, hk_deflate_tiles, hk_deflate_tiles_dev).
+ * points (hk_deflate_bound, hk_deflate_tiles, hk_deflate_tiles_dev).  The inflate entry points (hk_inflate_bound,
+ * hk_inflate_image, hk_inflate_image_dev, with the new struct hk_inflate_layout) were added WITHOUT a new version: no existing
+ * layout or prototype changed, so a version-12 consumer runs unchanged against either library; a consumer that wants them looks
+ * them up by symbol (dlsym) and does without where they are absent.
  * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
 #define HK_ABI_VERSION 12
 int hk_abi_version(void);
@@ -155,6 +158,48 @@ int hk_deflate_bound(int32_t dtype, int32_t n_bands, int32_t height, int32_t wid
 int hk_deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
                      int64_t band_stride, int32_t tile, void* out, int64_t out_capacity, int64_t* tile_offsets /* n_tiles + 1 */,
                      int64_t* tile_sizes /* n_tiles */);
+
+/* INFLATE on the device: the DEFLATE blocks (tiles or strips) of one GeoTIFF image, compression 8 or 32946, inflated and put in
+ * their place in a (spp, height, width) raster, in place of zlib.decompress + the predictor + a slice copy per block on a host
+ * thread.  A block's stream may be any legal zlib stream (stored, fixed and dynamic blocks, 15-bit codes, distances to 32768,
+ * lengths to 258, overlapping copies) that inflates to exactly the block's raw size; bytes behind its Adler-32 are ignored.
+ * Every block gets a status: 0, or why its stream was refused -- such a block is left out of the raster (the device call does not
+ * write its pixels; the host call leaves them unspecified) and does not disturb the others.  Blocks are ordered plane (separate only), block row, block column, as TIFF
+ * orders them. */
+typedef struct hk_inflate_layout {
+    int32_t sample_bytes;      /* 1, 2, 4, 8; little-endian samples */
+    int32_t spp, height, width;
+    int32_t block_w, block_h;  /* tile size; strips: width, rows per strip */
+    int32_t tiled;             /* 1: every block holds block_h rows; 0: the last strip is short */
+    int32_t separate;          /* 1: one plane per block, blocks ordered plane, block row, block column; 0: pixel-interleaved */
+    int32_t predictor;         /* 1 none, 2 horizontal differencing */
+} hk_inflate_layout;
+enum {
+    HK_INFLATE_OK = 0,
+    HK_INFLATE_TRUNCATED = 1,   /* a bit past the stream's end was needed (an empty or missing stream too) */
+    HK_INFLATE_BAD_HEADER = 2,  /* zlib header: method not 8, window above 32 KiB, FCHECK, or a preset dictionary */
+    HK_INFLATE_BAD_BLOCK = 3,   /* block type 3 */
+    HK_INFLATE_BAD_STORED = 4,  /* stored block: LEN != ~NLEN */
+    HK_INFLATE_BAD_CODE = 5,    /* dynamic header: too many symbols, an over-subscribed or incomplete code, a bad repeat, no end-of-block code */
+    HK_INFLATE_BAD_SYMBOL = 6,  /* literal/length symbol 286 / 287, distance symbol 30 / 31, or bits that are no code of the set */
+    HK_INFLATE_FAR = 7,         /* a distance larger than the bytes produced so far */
+    HK_INFLATE_OVERRUN = 8,     /* the stream holds more than the block's raw size */
+    HK_INFLATE_SHORT = 9,       /* the stream ends before the block's raw size */
+    HK_INFLATE_ADLER = 10       /* the Adler-32 of the bytes is not the stream's */
+};
+#define HK_INFLATE_MAX_BLOCK (1 << 30)   /* largest raw size of one block, bytes */
+/* n_blocks = (separate ? spp : 1) x ceil(height / block_h) x ceil(width / block_w); raw_block_bytes = block_h x block_w x
+ * (separate ? 1 : spp) x sample_bytes, the raw size of a full block; work_bytes = n_blocks x raw_block_bytes rounded up to 16: the
+ * device scratch of hk_inflate_image_dev.  Plain host arithmetic (no device needed). */
+int hk_inflate_bound(const hk_inflate_layout* layout, int64_t* n_blocks, int64_t* raw_block_bytes, int64_t* work_bytes);
+/* The image of `layout` from block streams in host memory -- block b's stream is the sizes[b] bytes at streams + offsets[b] --
+ * into `out` (host; plane c at out + c * band_stride, `stride` elements between rows; elements of sample_bytes).  The compressed
+ * bytes go up and the raster comes down through the pinned staging ring, in groups of whole block rows of at most 64 MiB of raw
+ * bytes (HK_INFLATE_GROUP_KB lowers the bound, for tests).  `status`: n_blocks values or NULL.  If any block was refused the call
+ * returns HK_ERR_ARG, hk_last_error() names the first such block and the reason, `status` is filled all the same and every other
+ * block is in `out`. */
+int hk_inflate_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
+                     void* out, int64_t stride, int64_t band_stride, int32_t* status /* n_blocks or NULL */);
 
 /* KernelModel.fit (homonim/kernel_model.py:411-440 -> _fit_gain :231-274, _fit_gain_blk_offset :276-303,
  * _fit_gain_offset :305-373, _r2_array :142-214).
@@ -561,6 +606,14 @@ int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t
 int hk_deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
                          int64_t stride, int64_t band_stride, int32_t tile, void* out_dev, int64_t out_capacity,
                          int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream);
+
+/* hk_inflate_image for device-resident streams, offsets and sizes: the raster into out_dev, the statuses into status_dev (n_blocks
+ * int32, required: nothing comes back to the host, so the call cannot report a refused block itself); work_dev: hk_inflate_bound's
+ * work_bytes, 16-byte aligned.  A negative offset or a size below 1 gives the block HK_INFLATE_TRUNCATED; at most 256 MiB of a stream
+ * are looked at.  Queued on pooled stream `stream`; asynchronous.  One launch: at most 2^31 - 1 blocks. */
+int hk_inflate_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
+                         const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
+                         int32_t* status_dev, int32_t stream);
 
 /* HIP events on the pooled streams, so callers time exactly the stream the kernels run on. */
 int hk_event_create(hk_ctx* ctx, hk_event** ev);
