@@ -136,6 +136,10 @@ SIGNATURES = {
                                    C.c_void_p, C.c_int64, _P(C.c_int64), _P(C.c_int64)]),
     'hk_deflate_tiles_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                        C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]),
+    'hk_deflate_tiles_pred': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                        C.c_int32, C.c_void_p, C.c_int64, _P(C.c_int64), _P(C.c_int64), C.c_int32]),
+    'hk_deflate_tiles_pred_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                            C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     'hk_inflate_bound': (C.c_int, [_P(InflateLayout), _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     'hk_inflate_image': (C.c_int, [C.c_void_p, _P(InflateLayout), C.c_void_p, _P(C.c_int64), _P(C.c_int64), C.c_void_p, C.c_int64,
                                    C.c_int64, _P(C.c_int32)]),
@@ -546,10 +550,11 @@ class Context:
                                       strides, bstrides))
         return [o[0] for o in outs] if squeeze else outs
 
-    def deflate_tiles_packed(self, array: np.ndarray, tile: int):
+    def deflate_tiles_packed(self, array: np.ndarray, tile: int, predictor: int = 1):
         """ ``deflate_tiles`` as the library returns it: (uint8 array of the streams, int64 offsets [n_tiles + 1], int64 sizes
         [n_tiles]) -- tile t's stream is ``out[offsets[t]:offsets[t] + sizes[t]]``; offsets are even and ``offsets[-1]`` is the
-        number of bytes used. """
+        number of bytes used.  ``predictor``: 1 goes through hk_deflate_tiles as ever, anything else through
+        hk_deflate_tiles_pred. """
         arr = np.asarray(array)
         if arr.ndim == 2:
             arr = arr[None]
@@ -571,17 +576,24 @@ class Context:
         _check(self._lib.hk_deflate_bound(code, nb, h, w, tile, C.byref(n_tiles), C.byref(cap)))
         out = np.empty(cap.value, np.uint8)
         offsets, sizes = np.empty(n_tiles.value + 1, np.int64), np.empty(n_tiles.value, np.int64)
-        _check(self._lib.hk_deflate_tiles(self._h, arr.ctypes.data_as(C.c_void_p), code, nb, h, w, arr.strides[1] // it,
-                                          arr.strides[0] // it if nb > 1 else 0, tile, out.ctypes.data_as(C.c_void_p), cap.value,
-                                          offsets.ctypes.data_as(_P(C.c_int64)), sizes.ctypes.data_as(_P(C.c_int64))))
+        args = (self._h, arr.ctypes.data_as(C.c_void_p), code, nb, h, w, arr.strides[1] // it, arr.strides[0] // it if nb > 1 else 0,
+                tile, out.ctypes.data_as(C.c_void_p), cap.value, offsets.ctypes.data_as(_P(C.c_int64)),
+                sizes.ctypes.data_as(_P(C.c_int64)))
+        if predictor == 1:
+            _check(self._lib.hk_deflate_tiles(*args))
+        else:
+            _check(self._lib.hk_deflate_tiles_pred(*args, int(predictor)))
         return out, offsets, sizes
 
-    def deflate_tiles(self, array: np.ndarray, tile: int) -> list:
+    def deflate_tiles(self, array: np.ndarray, tile: int, predictor: int = 1) -> list:
         """ One zlib stream per ``tile`` x ``tile`` tile of a (bands, h, w) or (h, w) raster in host memory, made on the device
         (hk_deflate_tiles; the stream format: include/homonim_hk.h): ``bytes`` objects in the order band, tile row, tile column,
         edge tiles zero-padded, samples little-endian -- what ``tiff.write_tiff`` takes as ``compressor``.  Any dtype
-        ``write_tiff`` accepts; rows and bands may be strided (unit column stride), anything else is copied first. """
-        out, offsets, sizes = self.deflate_tiles_packed(array, tile)
+        ``write_tiff`` accepts; rows and bands may be strided (unit column stride), anything else is copied first.
+        ``predictor``: the TIFF predictor (tag 317) applied to every padded tile row before it is coded (hk_deflate_tiles_pred):
+        1 none, 2 horizontal differencing (integer dtypes), 3 the floating-point predictor (float32 / float64); a predictor the
+        dtype does not take is a ``ValueError``. """
+        out, offsets, sizes = self.deflate_tiles_packed(array, tile, predictor)
         return [out[o:o + n].tobytes() for o, n in zip(offsets[:-1].tolist(), sizes.tolist())]
 
     def inflate_image_packed(self, streams, offsets, sizes, layout, strict: bool = True):
@@ -1236,13 +1248,18 @@ class Context:
                                           (C.c_int64 * n)(*out_strides), (C.c_int64 * n)(*out_band_strides), stream))
 
     def deflate_tiles_dev(self, planes_dptr: int, dtype: str, n_bands: int, height: int, width: int, stride: int, band_stride: int,
-                          tile: int, out_dptr: int, out_capacity: int, offsets_dptr: int, sizes_dptr: int, stream: int = 0):
+                          tile: int, out_dptr: int, out_capacity: int, offsets_dptr: int, sizes_dptr: int, stream: int = 0,
+                          predictor: int = 1):
         """ Queue the zlib streams of the tiles of ``n_bands`` device-resident planes of dtype ``dtype`` (strides in elements):
         the streams into ``out_dptr`` (``deflate_bound`` bytes), ``n_tiles + 1`` int64 offsets into ``offsets_dptr``, ``n_tiles``
-        int64 sizes into ``sizes_dptr`` (hk_deflate_tiles_dev; asynchronous). """
-        _check(self._lib.hk_deflate_tiles_dev(self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height,
-                                              width, stride, band_stride, tile, C.c_void_p(out_dptr), out_capacity,
-                                              C.c_void_p(offsets_dptr), C.c_void_p(sizes_dptr), stream))
+        int64 sizes into ``sizes_dptr`` (hk_deflate_tiles_dev; asynchronous).  ``predictor``: as in ``deflate_tiles``; other
+        than 1 the call is hk_deflate_tiles_pred_dev. """
+        args = (self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height, width, stride, band_stride,
+                tile, C.c_void_p(out_dptr), out_capacity, C.c_void_p(offsets_dptr), C.c_void_p(sizes_dptr), stream)
+        if predictor == 1:
+            _check(self._lib.hk_deflate_tiles_dev(*args))
+        else:
+            _check(self._lib.hk_deflate_tiles_pred_dev(*args, int(predictor)))
 
     def inflate_image_dev(self, layout, streams_dptr: int, offsets_dptr: int, sizes_dptr: int, work_dptr: int, out_dptr: int,
                           stride: int, band_stride: int, status_dptr: int, stream: int = 0):

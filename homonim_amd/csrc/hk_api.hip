@@ -2570,6 +2570,16 @@ int hk_deflate_bound(int32_t dtype, int32_t n_bands, int32_t height, int32_t wid
     return deflate_shape(dtype, n_bands, height, width, tile, n_tiles, bytes, nullptr);
 }
 
+// the predictor of hk_deflate_tiles_pred / _pred_dev against the dtype: 2 differences integers, 3 is the floating-point predictor
+static int check_predictor(int32_t dtype, int32_t predictor) {
+    if (predictor < 1 || predictor > 3) return fail(HK_ERR_ARG, "predictor %d is not 1, 2 or 3", predictor);
+    if (!hk::dtype_size(dtype)) return fail(HK_ERR_ARG, "bad dtype %d", dtype);
+    const bool is_float = dtype == HK_DTYPE_F32 || dtype == HK_DTYPE_F64;
+    if (predictor == 2 && is_float) return fail(HK_ERR_ARG, "predictor 2 (horizontal differencing) is for integer samples, not dtype %d", dtype);
+    if (predictor == 3 && !is_float) return fail(HK_ERR_ARG, "predictor 3 (floating point) is for float samples, not dtype %d", dtype);
+    return HK_OK;
+}
+
 static int check_deflate(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
                          int64_t stride, int64_t band_stride, int32_t tile, const void* out, int64_t out_capacity,
                          const int64_t* tile_offsets, const int64_t* tile_sizes, int64_t* n_tiles, int64_t* n_chunks) {
@@ -2584,9 +2594,11 @@ static int check_deflate(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t
     return HK_OK;
 }
 
-int hk_deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
-                         int64_t stride, int64_t band_stride, int32_t tile, void* out_dev, int64_t out_capacity,
-                         int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream) {
+// the body of hk_deflate_tiles_dev and hk_deflate_tiles_pred_dev (which has checked the predictor): the checks of the former in
+// their order, then the launch
+static int deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                             int64_t stride, int64_t band_stride, int32_t tile, void* out_dev, int64_t out_capacity,
+                             int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream, int32_t predictor) {
     int64_t n_tiles = 0, n_chunks = 0;
     int rc = check_deflate(ctx, planes_dev, dtype, n_bands, height, width, stride, band_stride, tile, out_dev, out_capacity,
                            tile_offsets_dev, tile_sizes_dev, &n_tiles, &n_chunks);
@@ -2601,8 +2613,24 @@ int hk_deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int
     static_assert(sizeof(long long) == sizeof(int64_t), "offsets are handed on as they are");
     HK_HIP(hk::launch_deflate_tiles(planes_dev, hk::dtype_size(dtype), n_bands, height, width, stride, band_stride, tile, sl.norm_ws,
                                     static_cast<unsigned char*>(out_dev), reinterpret_cast<long long*>(tile_offsets_dev),
-                                    reinterpret_cast<long long*>(tile_sizes_dev), sl.stream));
+                                    reinterpret_cast<long long*>(tile_sizes_dev), sl.stream, predictor));
     return HK_OK;
+}
+
+int hk_deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                         int64_t stride, int64_t band_stride, int32_t tile, void* out_dev, int64_t out_capacity,
+                         int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream) {
+    return deflate_tiles_dev(ctx, planes_dev, dtype, n_bands, height, width, stride, band_stride, tile, out_dev, out_capacity,
+                             tile_offsets_dev, tile_sizes_dev, stream, 1);
+}
+
+int hk_deflate_tiles_pred_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                              int64_t stride, int64_t band_stride, int32_t tile, void* out_dev, int64_t out_capacity,
+                              int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream, int32_t predictor) {
+    const int rc = check_predictor(dtype, predictor);
+    if (rc) return rc;
+    return deflate_tiles_dev(ctx, planes_dev, dtype, n_bands, height, width, stride, band_stride, tile, out_dev, out_capacity,
+                             tile_offsets_dev, tile_sizes_dev, stream, predictor);
 }
 
 // tile rows per group of the host path: whole tile rows of ONE band of at most DEFLATE_GROUP_BYTES raw bytes (at least one tile
@@ -2610,8 +2638,10 @@ int hk_deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int
 // grouping cannot change a byte.
 constexpr size_t DEFLATE_GROUP_BYTES = 64u << 20;
 
-int hk_deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
-                     int64_t band_stride, int32_t tile, void* out, int64_t out_capacity, int64_t* tile_offsets, int64_t* tile_sizes) {
+// the body of hk_deflate_tiles and hk_deflate_tiles_pred (which has checked the predictor)
+static int deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                         int64_t stride, int64_t band_stride, int32_t tile, void* out, int64_t out_capacity, int64_t* tile_offsets,
+                         int64_t* tile_sizes, int32_t predictor) {
     int64_t n_tiles = 0, n_chunks = 0;
     int rc = check_deflate(ctx, planes, dtype, n_bands, height, width, stride, band_stride, tile, out, out_capacity, tile_offsets,
                            tile_sizes, &n_tiles, &n_chunks);
@@ -2651,7 +2681,7 @@ int hk_deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_b
                 return rc;
             HK_HIP(hk::launch_deflate_tiles(base + o_src, (int)es, 1, (int)rows, width, d_stride, 0, tile, base + o_work,
                                             reinterpret_cast<unsigned char*>(base + o_out), reinterpret_cast<long long*>(base + o_off),
-                                            reinterpret_cast<long long*>(base + o_siz), sl.stream));
+                                            reinterpret_cast<long long*>(base + o_siz), sl.stream, predictor));
             // the offsets first (they say how many bytes there are), then only the compressed bytes
             if ((rc = stage_d2h(sl, tile_offsets + t0, 0, base + o_off, 0, (size_t)(nt + 1) * sizeof(int64_t), 1))) return rc;
             if ((rc = stage_d2h(sl, tile_sizes + t0, 0, base + o_siz, 0, (size_t)nt * sizeof(int64_t), 1))) return rc;
@@ -2664,6 +2694,21 @@ int hk_deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_b
             used += got, t0 += nt;
         }
     return HK_OK;
+}
+
+int hk_deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                     int64_t band_stride, int32_t tile, void* out, int64_t out_capacity, int64_t* tile_offsets, int64_t* tile_sizes) {
+    return deflate_tiles(ctx, planes, dtype, n_bands, height, width, stride, band_stride, tile, out, out_capacity, tile_offsets,
+                         tile_sizes, 1);
+}
+
+int hk_deflate_tiles_pred(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                          int64_t stride, int64_t band_stride, int32_t tile, void* out, int64_t out_capacity, int64_t* tile_offsets,
+                          int64_t* tile_sizes, int32_t predictor) {
+    const int rc = check_predictor(dtype, predictor);
+    if (rc) return rc;
+    return deflate_tiles(ctx, planes, dtype, n_bands, height, width, stride, band_stride, tile, out, out_capacity, tile_offsets,
+                         tile_sizes, predictor);
 }
 
 // INFLATE of a GeoTIFF image's blocks (hk_inflate.hip): see include/homonim_hk.h

@@ -27,6 +27,15 @@
 // deflate_offsets_kernel (one workgroup): tile sizes and their even-aligned exclusive prefix sum.  deflate_gather_kernel (one
 // workgroup per chunk): the slots compacted into contiguous tile streams, zlib header, final block and combined Adler-32.
 // About 78 KiB of LDS per workgroup: two workgroups per CU.
+//
+// WITH A PREDICTOR (TIFF tag 317; launch_deflate_tiles(..., predictor)) all of the above holds for the tile's PREDICTED bytes: the
+// predictor runs over each zero-padded tile row on its own (deflate::predicted_byte in hk_deflate_core.h states both: 2, integer
+// differences modulo the sample's width; 3, libtiff's floating-point predictor -- byte planes, most significant first, differenced
+// modulo 256 over the whole row), the Adler-32 is taken over the predicted bytes, and the two candidate distances are the sample
+// size and the row length with predictors 1 and 2, and ONE and the row length with predictor 3: the bytes of a plane repeat at
+// distance 1.  Predictor 1 launches deflate_chunk_kernel and gives the bytes it always gave; 2 and 3 launch
+// deflate_pred_chunk_kernel (hk_deflate_pred.hip), whose phase 0 stages the whole raw rows under the chunk and its history and predicts from LDS (why
+// there and not in a pre-pass: DESIGN.md 5.4).
 #include <hip/hip_runtime.h>
 
 #include "hk_deflate_core.h"
@@ -233,7 +242,7 @@ size_t deflate_workspace_bytes(long long n_chunks) {
 
 hipError_t launch_deflate_tiles(const void* src, int esize, int n_bands, int height, int width, long long stride,
                                 long long band_stride, int tile, void* work, unsigned char* out, long long* tile_offsets,
-                                long long* tile_sizes, hipStream_t stream) {
+                                long long* tile_sizes, hipStream_t stream, int predictor) {
     DeflateArgs a;
     memset(&a, 0, sizeof(a));
     a.src = src, a.es = esize, a.height = height, a.width = width, a.stride = stride, a.band_stride = band_stride;
@@ -245,8 +254,13 @@ hipError_t launch_deflate_tiles(const void* src, int esize, int n_bands, int hei
     a.slots = static_cast<unsigned char*>(work);
     a.sizes = reinterpret_cast<unsigned*>(a.slots + (size_t)n_chunks * deflate::SLOT);
     a.adler = a.sizes + n_chunks;
-    HK_LAUNCH(deflate_chunk_kernel, dim3((unsigned)n_chunks), dim3(deflate::THREADS), 0, stream, a);
-    hipError_t e = hipGetLastError();
+    hipError_t e;
+    if (predictor == 1) {
+        HK_LAUNCH(deflate_chunk_kernel, dim3((unsigned)n_chunks), dim3(deflate::THREADS), 0, stream, a);
+        e = hipGetLastError();
+    } else {
+        e = launch_deflate_pred_chunks(a, predictor, n_chunks, stream);
+    }
     if (e != hipSuccess) return e;
     HK_LAUNCH(deflate_offsets_kernel, dim3(1), dim3(256), 0, stream, a, (int)n_tiles, tile_offsets, tile_sizes);
     if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -2,7 +2,8 @@
 // state.  A phase is a function of (shared state, chunk, thread index) that reads only what earlier phases wrote; the kernel
 // runs phase after phase with a barrier between two, and a host program can run the same phases with a loop over the thread
 // index in place of the workgroup (HKD_HOST: plain C++, no HIP), which is how the bit stream is tested against zlib without a GPU.
-// Nothing in here touches global memory.  The stream format is stated at the top of hk_deflate.hip.
+// Nothing in here touches global memory.  The stream format is stated at the top of hk_deflate.hip.  predicted_byte() is the TIFF
+// predictors as a byte mapping, for the kernel's staging and the host program alike (tests/c/deflate_pred_host.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -89,6 +90,38 @@ HKD_FN Chunk make_chunk(int start, int n, int sample_bytes, int row_bytes) {
     distance_code(c.d0, c.dcode0, c.dext0, c.dextv0);
     distance_code(c.d1, c.dcode1, c.dext1, c.dextv1);
     return c;
+}
+
+// ---- the TIFF predictors (tag 317) as a byte mapping: predicted byte j of ONE tile row from that row's raw bytes -- `tile`
+// little-endian samples of `es` bytes, B = tile x es bytes.  The coder compresses the predicted bytes; the kernel's staging
+// (deflate_pred_chunk_kernel) and the host build call this one function.
+//   1: the byte itself.
+//   2 (integers): p[i] = s[i] - s[i - 1] modulo 2^(8 es), p[0] = s[0]; samples stay little-endian.  Byte b of a difference needs
+//      bytes 0..b of both samples: the borrow runs upwards.
+//   3 (floats; libtiff's floating-point predictor): the row regrouped into `es` planes of `tile` bytes, most significant byte
+//      first -- q[p tile + i] = byte es - 1 - p of sample i -- then d[0] = q[0], d[j] = q[j] - q[j - 1] modulo 256 over all B
+//      bytes, across the plane boundaries.
+// predictor_distance: the first candidate distance of the parse that goes with a predictor (the second is always the row length);
+// under predictor 3 the bytes of a plane repeat at distance 1, not at the sample size.
+HKD_FN int predictor_distance(int predictor, int es) { return predictor == 3 ? 1 : es; }
+
+HKD_FN unsigned predicted_byte(const unsigned char* row, int j, int es, int tile, int predictor) {
+    if (predictor == 2) {
+        const int b = j & (es - 1), at = j - b;   // (es is a power of two)
+        int borrow = 0, v = 0;
+        for (int k = 0; k <= b; ++k) {
+            v = (int)row[at + k] - (at ? (int)row[at - es + k] : 0) - borrow;
+            borrow = v < 0;
+        }
+        return (unsigned)v & 0xFFu;
+    }
+    if (predictor == 3) {
+        const int p = j / tile, i = j - p * tile, at = es - 1 - p;
+        const unsigned cur = row[i * es + at];
+        const unsigned prev = j == 0 ? 0u : (i ? row[(i - 1) * es + at] : row[(tile - 1) * es + at + 1]);
+        return (cur - prev) & 0xFFu;
+    }
+    return row[j];
 }
 
 // length 3..258 -> (symbol - 257, number of extra bits, their value)

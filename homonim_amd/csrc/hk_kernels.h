@@ -281,7 +281,9 @@ struct DeflateArgs {
 size_t deflate_workspace_bytes(long long n_chunks);
 hipError_t launch_deflate_tiles(const void* src, int esize, int n_bands, int height, int width, long long stride,
                                 long long band_stride, int tile, void* work, unsigned char* out, long long* tile_offsets,
-                                long long* tile_sizes, hipStream_t stream);
+                                long long* tile_sizes, hipStream_t stream, int predictor = 1);
+// the chunk kernel of predictors 2 and 3 (hk_deflate_pred.hip), launched by launch_deflate_tiles in place of deflate_chunk_kernel
+hipError_t launch_deflate_pred_chunks(const DeflateArgs& a, int predictor, long long n_chunks, hipStream_t stream);
 
 // The DEFLATE blocks (tiles or strips) of a GeoTIFF image inflated into a (spp, height, width) raster (hk_inflate.hip, which states
 // the contract): block b's zlib stream is the sizes[b] bytes at streams + offsets[b]; blocks are ordered plane (separate only),

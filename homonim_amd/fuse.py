@@ -570,8 +570,15 @@ class RasterFuse:
         Same arguments as homonim.RasterFuse.process (fuse.py:321-332) plus ``device_config``.  Returns
         ``(corrected, params)``: float32 arrays (bands, H, W) and (n_param_bands * bands, H, W) or None.  When
         ``corr_filename`` / ``param_filename`` are paths the arrays are also written there: ``.tif`` as a tiled DEFLATE
-        GeoTIFF with the reference's FUSE_* provenance tags (homonim_amd/tiff.py), anything else with ``numpy.save``
-        (``out_profile['driver'|'creation_options']`` are accepted and ignored).  ``build_ovw`` (default, as in the reference:
+        GeoTIFF with the reference's FUSE_* provenance tags (homonim_amd/tiff.py), anything else with ``numpy.save``.
+        ``out_profile['creation_options']`` shape both ``.tif`` files: ``compress`` ('deflate', or None / 'none'), ``predictor``
+        (1, 2 or 3), ``blockxsize`` = ``blockysize`` (a multiple of 16 in 16..512), ``bigtiff`` ('yes', 'no', 'if_needed',
+        'if_safer': ``tiff.bigtiff_wanted``), ``tiled`` (True) and ``interleave`` ('band'); a key that is missing takes the
+        default profile's value, a value that cannot be written is a ``ValueError`` naming the key before any block is
+        processed, and ``driver``, ``photometric`` and every other key are accepted and ignored.  With no ``.tif`` to write
+        (arrays only, ``.npy``) all of them are ignored as before.  One profile shapes both files and the parameter file is
+        float32 whatever the output dtype, so the predictor is checked against each ``.tif`` that is written: an integer
+        corrected ``.tif`` beside a parameter ``.tif`` leaves predictor 1 only.  ``build_ovw`` (default, as in the reference:
         fuse.py:152-165): a ``.tif`` gets internal overviews -- ``overview_factors(shape)``: factors 2, 4, ... while the shorter
         side keeps 256 pixels, ``Resampling.average`` cascaded level to level, built on the GPU (``Context.overviews``) from the
         finished rasters under their own dtype and nodata; a raster too small for a level, ``build_ovw=False`` and ``.npy``
@@ -598,6 +605,10 @@ class RasterFuse:
         if out_dtype.name not in _hk.DTYPE_CODES:
             raise ValueError(f"unsupported output dtype '{out_profile['dtype']}'")
         _hk.out_nodata_code(out_dtype, nodata)  # a nodata the dtype cannot hold is refused (homonim/raster_array.py:357-358)
+        # the creation options shape .tif outputs only: with none to write they stay ignored
+        tiff_dtypes = ([('the corrected file', out_dtype)] if self._is_tiff(corr_filename) else []) + \
+                      ([('the parameter file', np.dtype(np.float32))] if want_params and self._is_tiff(param_filename) else [])
+        write_options = self._write_options(out_profile['creation_options'], tiff_dtypes) if tiff_dtypes else None
 
         model_cls = SrcSpaceModel if self._proc_crs == ProcCrs.src else RefSpaceModel
         devices = device_config['devices']
@@ -658,12 +669,61 @@ class RasterFuse:
                         FUSE_MODEL=model_type.name, FUSE_KERNEL_SHAPE=tuple(kernel_shape),
                         **{f'FUSE_{k.upper()}': getattr(v, 'name', v) for k, v in model_config.items()})
             if isinstance(corr_filename, (str, os.PathLike)):
-                self._save(corr_filename, corr, self._transform, nodata, meta, overviews=corr_ovw, compressor=compressor)
+                self._save(corr_filename, corr, self._transform, nodata, meta, overviews=corr_ovw, compressor=compressor,
+                           write_options=write_options)
             if want_params and isinstance(param_filename, (str, os.PathLike)):
                 param_tf = self._ref_transform if (self._proc_crs == ProcCrs.ref and not self._same_grid) else self._transform
                 self._save(param_filename, params, param_tf, float('nan'), meta, self._param_descriptions(n_param),
-                           overviews=param_ovw, compressor=compressor)
+                           overviews=param_ovw, compressor=compressor, write_options=write_options)
         return corr, params
+
+    @staticmethod
+    def _write_options(creation_options: Dict, tiff_dtypes: Sequence[Tuple[str, np.dtype]]) -> Dict:
+        """ ``out_profile['creation_options']`` as the keyword arguments of ``tiff.write_tiff``: ``tile``, ``compress``,
+        ``predictor``, ``bigtiff``.  Missing keys take the default profile's values (no predictor); a value of ``compress``,
+        ``predictor``, ``blockxsize`` / ``blockysize``, ``bigtiff``, ``tiled`` or ``interleave`` that the writer cannot honour
+        raises ``ValueError`` naming the key; every other key is ignored.  ``tiff_dtypes``: (name, sample dtype) of the files that are
+        written as ``.tif``.  One profile shapes both files, as in the reference, so the predictor has to suit each of them: the
+        parameter file is float32 whatever the output dtype, and an integer corrected file beside it leaves predictor 1 only. """
+        from homonim_amd.tiff import bigtiff_wanted
+        opts = dict(RasterFuse.create_out_profile()['creation_options'], predictor=1)
+        opts.update({str(k).lower(): v for k, v in (creation_options or {}).items()})
+
+        def refuse(key, what):
+            raise ValueError(f"creation option `{key}`={opts[key]!r} cannot be written: {what}")
+
+        compress = opts['compress']
+        compress = None if compress is None or str(compress).lower() == 'none' else str(compress).lower()
+        if compress not in (None, 'deflate'):
+            refuse('compress', "'deflate' and None / 'none' are")
+        try:
+            predictor = int(opts['predictor'])
+        except (TypeError, ValueError):
+            predictor = 0
+        if predictor not in (1, 2, 3):
+            refuse('predictor', '1, 2 and 3 are')
+        if predictor != 1 and compress is None:
+            refuse('predictor', 'a predictor needs compress=deflate')
+        for what, dt in tiff_dtypes:
+            if (predictor == 2 and dt.kind == 'f') or (predictor == 3 and dt.kind != 'f'):
+                refuse('predictor', f"2 is for integer samples and 3 for floats; {what} is '{dt.name}'")
+        try:
+            bx, by = int(opts['blockxsize']), int(opts['blockysize'])
+        except (TypeError, ValueError):
+            refuse('blockxsize', 'block sizes are integers')
+        if bx != by:
+            refuse('blockysize', f'tiles are square (blockxsize is {bx})')
+        if bx < 16 or bx > 512 or bx % 16:
+            refuse('blockxsize', 'a multiple of 16 in 16..512 is')
+        try:
+            bigtiff_wanted(opts['bigtiff'], 0, True, 0)
+        except ValueError:
+            refuse('bigtiff', "'yes', 'no', 'if_needed' and 'if_safer' are")
+        if opts['tiled'] is not True and str(opts['tiled']).lower() not in ('true', 'yes', '1'):
+            refuse('tiled', 'only tiled files are')
+        if str(opts['interleave']).lower() != 'band':
+            refuse('interleave', "only 'band' is")
+        return dict(tile=bx, compress=compress is not None, predictor=predictor, bigtiff=opts['bigtiff'])
 
     @staticmethod
     def _pin(ctx, arrays) -> List[np.ndarray]:
@@ -720,14 +780,16 @@ class RasterFuse:
         return ctx.overviews(array, nodata, n_levels) if n_levels else None
 
     def _save(self, filename, array: np.ndarray, transform: Affine, nodata, metadata: Dict,
-              descriptions: Optional[List[str]] = None, overviews: Optional[List[np.ndarray]] = None, compressor=None):
-        """ ``.tif`` / ``.tiff``: tiled DEFLATE GeoTIFF like the reference's default output profile, with ``overviews`` as its
-        internal overviews when given, its tiles compressed by ``compressor`` (``tiff.write_tiff``; None: host zlib); anything
-        else: ``numpy.save``. """
+              descriptions: Optional[List[str]] = None, overviews: Optional[List[np.ndarray]] = None, compressor=None,
+              write_options: Optional[Dict] = None):
+        """ ``.tif`` / ``.tiff``: tiled GeoTIFF as ``write_options`` say (``_write_options``; None: the reference's default output
+        profile), with ``overviews`` as its internal overviews when given, its tiles compressed by ``compressor``
+        (``tiff.write_tiff``; None: host zlib); anything else: ``numpy.save``. """
         if self._is_tiff(filename):
             from homonim_amd.tiff import write_tiff
             write_tiff(filename, array, transform, self._crs, nodata, {k: str(v) for k, v in metadata.items()},
-                       descriptions=descriptions, overviews=overviews, compressor=compressor)
+                       descriptions=descriptions, overviews=overviews,
+                       compressor=compressor if (write_options or {}).get('compress', True) else None, **(write_options or {}))
         else:
             np.save(filename, array)
 

@@ -3,12 +3,13 @@ Minimal GeoTIFF reader / writer for the rasters either side of the hot path (no 
 
 Covers what the reference reads and writes (all of homonim's test rasters and its own output
 profile, homonim/fuse.py:124-149): classic or BigTIFF, little / big endian, strips or tiles, planar ``separate`` or
-``contig``, uncompressed or DEFLATE (zlib) with predictor none / horizontal differencing, 8 / 16 / 32 / 64-bit integer
-and IEEE float samples; geo-referencing from ModelPixelScale + ModelTiepoint or ModelTransformation; nodata
+``contig``, uncompressed or DEFLATE (zlib) with predictor none / horizontal differencing / floating point (3), 8 / 16 / 32 /
+64-bit integer and IEEE float samples; geo-referencing from ModelPixelScale + ModelTiepoint or ModelTransformation; nodata
 from GDAL_NODATA; EPSG code / citation from the GeoKey directory; the ``<GDALMetadata>`` items (where the reference keeps
 its FUSE_* provenance, fuse.py:193-207) and the per-band ``DESCRIPTION`` items among them (the band names of a parameter
 file, fuse.py:241-248).  The writer produces tiled, DEFLATE, band-separate files like the reference's
-default output profile, with internal overviews (reduced-resolution images chained behind the first) on request;
+default output profile -- classic or BigTIFF, with predictor 2 or 3 on request -- with internal overviews (reduced-resolution
+images chained behind the first) on request;
 ``read_tiff_overviews`` reads those back.  A rotated or sheared grid is read from, and on request written as, a
 ModelTransformation matrix.  Everything else (other compressions, palettes) raises.
 """
@@ -250,8 +251,8 @@ def _decode_image(buf, bo, t, inflater=None) -> np.ndarray:
     if compression not in (1, 8, 32946):
         raise IoError(f'unsupported TIFF compression {compression} (none and DEFLATE are)')
     predictor = t.get(T_PREDICTOR, (1,))[0]
-    if predictor not in (1, 2) or (predictor == 2 and dtype.kind == 'f'):
-        raise IoError(f'unsupported TIFF predictor {predictor}')
+    if predictor not in (1, 2, 3) or (predictor == 2 and dtype.kind == 'f') or (predictor == 3 and dtype.kind != 'f'):
+        raise IoError(f'unsupported TIFF predictor {predictor} for samples of {dtype}')
     planar = t.get(T_PLANAR, (1,))[0]
     if T_TILE_OFFSETS in t:
         bw, bh, offs, cnts = t[T_TILE_W][0], t[T_TILE_H][0], t[T_TILE_OFFSETS], t[T_TILE_COUNTS]
@@ -261,7 +262,8 @@ def _decode_image(buf, bo, t, inflater=None) -> np.ndarray:
     across, down = -(-w // bw), -(-h // bh)
     chunk_spp = 1 if planar == 2 else spp
     tiled = T_TILE_OFFSETS in t
-    if inflater is not None and compression != 1 and bo == '<':
+    # (a floating-point predictor is undone here, hook or not: the hook's contract knows predictors 1 and 2)
+    if inflater is not None and compression != 1 and bo == '<' and predictor != 3:
         if len(offs) != len(cnts) or len(offs) != (spp if planar == 2 else 1) * across * down:
             raise IoError(f'{len(offs)} block offsets and {len(cnts)} byte counts for {(spp if planar == 2 else 1) * across * down} blocks')
         layout = BlockLayout(dtype.itemsize, spp, h, w, bw, bh, int(tiled), int(planar == 2), predictor)
@@ -277,7 +279,10 @@ def _decode_image(buf, bo, t, inflater=None) -> np.ndarray:
         raw = buf[off:off + cnt]
         if compression != 1:
             raw = zlib.decompress(raw)
-        block = np.frombuffer(raw, dtype, count=rows * bw * chunk_spp).reshape(rows, bw, chunk_spp)
+        if predictor == 3:
+            block = _unpredict_float(raw, rows, bw, chunk_spp, dtype.itemsize)
+        else:
+            block = np.frombuffer(raw, dtype, count=rows * bw * chunk_spp).reshape(rows, bw, chunk_spp)
         if predictor == 2:
             block = np.cumsum(block, axis=1, dtype=dtype.newbyteorder('='))
         y0, x0 = by * bh, bx * bw
@@ -289,11 +294,41 @@ def _decode_image(buf, bo, t, inflater=None) -> np.ndarray:
     return out
 
 
+def _unpredict_float(raw, rows: int, bw: int, cspp: int, es: int) -> np.ndarray:
+    """ libtiff's floating-point predictor (3) undone on a block of ``rows`` rows of ``bw`` pixels of ``cspp`` samples of ``es``
+    bytes: every row is differenced byte by byte at a distance of ``cspp`` bytes, and holds ``es`` planes of ``bw * cspp`` bytes,
+    the most significant byte of every sample first -- whatever the file's byte order.  -> (rows, bw, cspp), native floats """
+    n = bw * cspp
+    d = np.frombuffer(raw, np.uint8, count=rows * n * es).reshape(rows, n * es // cspp, cspp)
+    q = np.cumsum(d, axis=1, dtype=np.uint8).reshape(rows, es, n)
+    be = np.ascontiguousarray(q.transpose(0, 2, 1))   # per sample its bytes, most significant first
+    return be.view(f'>f{es}').reshape(rows, bw, cspp).astype(f'=f{es}')
+
+
+def _predict_rows(blk: np.ndarray, predictor: int) -> bytes:
+    """ The bytes of a block of little-endian samples (rows, samples) under TIFF predictor 2 (integers: every sample minus the one
+    before it in its row, modulo 2^bits) or 3 (floats: the row's bytes as planes, most significant byte first, then differenced
+    byte by byte over the whole row) -- what a DEFLATE tile of a file with tag 317 holds; 1: the bytes themselves """
+    if predictor == 1:
+        return blk.tobytes()
+    es = blk.dtype.itemsize
+    if predictor == 2:
+        u = blk.view(f'<u{es}')
+        out = u.copy()
+        out[:, 1:] = u[:, 1:] - u[:, :-1]
+        return out.tobytes()
+    q = np.ascontiguousarray(blk).view(np.uint8).reshape(blk.shape[0], blk.shape[1], es)[:, :, ::-1]
+    q = np.ascontiguousarray(q.transpose(0, 2, 1)).reshape(blk.shape[0], es * blk.shape[1])
+    out = q.copy()
+    out[:, 1:] = q[:, 1:] - q[:, :-1]
+    return out.tobytes()
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 OVERVIEW_TILE = 128   # GDAL's default block size of overviews (GDAL_TIFF_OVR_BLOCKSIZE)
 
 
-def _tile_chunks(a: np.ndarray, tile: int, compress: bool) -> List[bytes]:
+def _tile_chunks(a: np.ndarray, tile: int, compress: bool, predictor: int = 1) -> List[bytes]:
     nb, h, w = a.shape
     across, down = -(-w // tile), -(-h // tile)
     chunks = []
@@ -303,37 +338,78 @@ def _tile_chunks(a: np.ndarray, tile: int, compress: bool) -> List[bytes]:
                 blk = np.zeros((tile, tile), a.dtype)
                 part = a[b, by * tile:(by + 1) * tile, bx * tile:(bx + 1) * tile]
                 blk[:part.shape[0], :part.shape[1]] = part
-                raw = blk.tobytes()
+                raw = _predict_rows(blk, predictor)
                 chunks.append(zlib.compress(raw, 6) if compress else raw)
     return chunks
 
 
-def _directory(entries, chunks, ifd_off: int, has_next: bool) -> Tuple[bytes, int]:
-    """ One image of a classic TIFF placed at ``ifd_off``: directory, the values that do not fit an entry, tile data.
-    -> (bytes, offset just behind them: where the next directory goes) """
-    entries = sorted(entries, key=lambda e: e[0])
-    ifd_size = 2 + 12 * len(entries) + 4
-    extra_off = ifd_off + ifd_size
+BIGTIFF_SAFER_BYTES = 2_000_000_000    # 'if_safer': BigTIFF for a main image of more raw bytes than this
+BIGTIFF_NEEDED_BYTES = 4_200_000_000   # 'if_needed': ... for an uncompressed one of more raw bytes than this
+
+
+def bigtiff_wanted(mode, raw_bytes: int, compressed: bool, classic_end: int) -> bool:
+    """ Is the file written as BigTIFF?  ``mode``: the ``bigtiff`` creation option -- 'yes' / True, 'no' / False, 'if_needed',
+    'if_safer' in any case; ``raw_bytes``: bands x height x width x itemsize of the main image; ``classic_end``: where the
+    file would end in the classic layout (every size is known before the first byte is written).  'yes': BigTIFF.  'no':
+    classic, an ``IoError`` where that does not fit.  'if_needed': BigTIFF for an uncompressed file of more than 4 200 000 000
+    raw bytes.  'if_safer': BigTIFF for more than 2 000 000 000 raw bytes.  In both ``if_`` modes a file whose classic layout would
+    not fit is BigTIFF whatever its raw size (the thresholds restate GDAL's rule, the last clause is this
+    package's own). """
+    if isinstance(mode, bool):
+        mode = 'yes' if mode else 'no'
+    mode = str(mode).lower()
+    fits = classic_end < 2 ** 32
+    if mode == 'yes':
+        return True
+    if mode == 'no':
+        if not fits:
+            raise IoError("raster too large for a classic TIFF (bigtiff='no')")
+        return False
+    if mode == 'if_needed':
+        return (not compressed and raw_bytes > BIGTIFF_NEEDED_BYTES) or not fits
+    if mode == 'if_safer':
+        return raw_bytes > BIGTIFF_SAFER_BYTES or not fits
+    raise ValueError(f"`bigtiff` must be 'yes', 'no', 'if_needed' or 'if_safer', not {mode!r}")
+
+
+def _layout(entries, chunks, ifd_off: int, big: bool):
+    """ Where one image placed at ``ifd_off`` puts what.  ``entries``: its directory without the tile offsets and byte counts; they
+    are added here as LONG, or LONG8 in a BigTIFF.  -> (all entries in tag order, offsets of the values that do not fit an entry by
+    tag, tile offsets, offset just behind the image: where the next directory goes) """
+    inline, typ = (8, 16) if big else (4, 4)
+    counts = struct.pack('<' + _TYPES[typ] * len(chunks), *[len(c) for c in chunks])
+    entries = sorted(list(entries) + [(T_TILE_OFFSETS, typ, len(chunks), b'\0' * len(counts)), (T_TILE_COUNTS, typ, len(chunks), counts)],
+                     key=lambda e: e[0])
+    extra_off = ifd_off + ((8 + 20 * len(entries) + 8) if big else (2 + 12 * len(entries) + 4))
     placed = {}
-    for code, typ, count, payload in entries:
-        if len(payload) > 4:
+    for code, _, _, payload in entries:
+        if len(payload) > inline:
             placed[code] = extra_off
             extra_off += len(payload) + len(payload) % 2
     offsets, pos = [], extra_off
     for c in chunks:
         offsets.append(pos)
         pos += len(c) + (len(c) % 2)
-    if pos >= 2 ** 32:
-        raise IoError('raster too large for a classic TIFF (BigTIFF writing is not built)')
-    off_payload = struct.pack('<' + 'I' * len(offsets), *offsets)
+    return entries, placed, offsets, pos
+
+
+def _directory(entries, chunks, ifd_off: int, has_next: bool, big: bool = False) -> Tuple[bytes, int]:
+    """ One image of a classic TIFF (``big``: of a BigTIFF -- 64-bit entry count, 20-byte entries with up to 8 bytes inline,
+    64-bit next offset) placed at ``ifd_off``: directory, the values that do not fit an entry, tile data.  ``entries``: as in
+    ``_layout``.  -> (bytes, offset just behind them: where the next directory goes) """
+    entries, placed, offsets, pos = _layout(entries, chunks, ifd_off, big)
+    if not big and pos >= 2 ** 32:
+        raise IoError('raster too large for a classic TIFF')
+    inline, word = (8, 'Q') if big else (4, 'I')
+    off_payload = struct.pack('<' + word * len(offsets), *offsets)
     entries = [(code, typ, count, off_payload if code == T_TILE_OFFSETS else payload) for code, typ, count, payload in entries]
-    parts = [struct.pack('<H', len(entries))]
+    parts = [struct.pack('<' + ('Q' if big else 'H'), len(entries))]
     for code, typ, count, payload in entries:
-        parts.append(struct.pack('<HHI', code, typ, count))
-        parts.append(payload.ljust(4, b'\0') if len(payload) <= 4 else struct.pack('<I', placed[code]))
-    parts.append(struct.pack('<I', pos if has_next else 0))
+        parts.append(struct.pack('<HH' + word, code, typ, count))
+        parts.append(payload.ljust(inline, b'\0') if len(payload) <= inline else struct.pack('<' + word, placed[code]))
+    parts.append(struct.pack('<' + word, pos if has_next else 0))
     for code, typ, count, payload in entries:
-        if len(payload) > 4:
+        if len(payload) > inline:
             parts.append(payload + b'\0' * (len(payload) % 2))
     for c in chunks:
         parts.append(c + b'\0' * (len(c) % 2))
@@ -343,8 +419,8 @@ def _directory(entries, chunks, ifd_off: int, has_next: bool) -> Tuple[bytes, in
 def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = None, nodata: Optional[float] = None,
                metadata: Optional[Dict[str, str]] = None, tile: int = 512, compress: bool = True,
                descriptions: Optional[Sequence[Optional[str]]] = None, overviews: Optional[Sequence[np.ndarray]] = None,
-               rotated: bool = False, compressor=None):
-    """ Write (bands, height, width) as a classic little-endian GeoTIFF: tiled, DEFLATE, band-separate -- the reference's
+               rotated: bool = False, compressor=None, predictor: int = 1, bigtiff='if_safer'):
+    """ Write (bands, height, width) as a little-endian GeoTIFF: tiled, DEFLATE, band-separate -- the reference's
     default output profile (homonim/fuse.py:124-149: tiled 512 x 512, compress=deflate, interleave=band).  ``descriptions``:
     one band description per band (None: none for that band), written as GDAL writes them.  ``overviews``: the internal
     overviews (homonim/fuse.py:152-165), finest first, each (bands, h_m, w_m) of the raster's dtype: one directory per level
@@ -356,12 +432,26 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
     one zlib stream per tile of a (bands, h, w) array in this writer's tile order -- band, tile row, tile column; a tile is
     ``tile`` rows of ``tile`` little-endian samples, edge tiles zero-padded -- used for the main image (at ``tile``) and for every
     overview level (at 128) in place of ``zlib.compress`` (e.g. ``Context.deflate_tiles``: this module itself imports no GPU
-    code).  None: zlib level 6 on this thread, the same bytes as ever. """
+    code).  None: zlib level 6 on this thread, the same bytes as ever.  ``predictor``: TIFF tag 317 of the main image and of every
+    overview level -- 1 none (no tag), 2 horizontal differencing (integer dtypes), 3 the floating-point predictor (float dtypes):
+    every padded tile row is predicted before it is compressed (``_predict_rows``); a compressor is then called as
+    ``compressor(array3d, tile, predictor=predictor)`` and returns the streams of the predicted tiles; it needs ``compress``.
+    ``bigtiff``: 'yes', 'no', 'if_needed' or 'if_safer' (``bigtiff_wanted``): classic TIFF or BigTIFF (magic 43, 64-bit offsets,
+    tile offsets and byte counts as LONG8).  A main image of at most 2 000 000 000 raw bytes is, with the defaults, the classic
+    file this function always wrote. """
     if compressor is not None and not compress:
         raise ValueError('a compressor was given for an uncompressed file (compress=False)')
     a = np.asarray(array)
     if a.ndim == 2:
         a = a[None]
+    predictor = int(predictor)
+    if predictor not in (1, 2, 3):
+        raise ValueError(f'`predictor` must be 1, 2 or 3, not {predictor}')
+    if predictor != 1 and not compress:
+        raise ValueError(f'predictor {predictor} was given for an uncompressed file (compress=False)')
+    if (predictor == 2 and a.dtype.kind == 'f') or (predictor == 3 and a.dtype.kind != 'f'):
+        raise ValueError(f"predictor {predictor} does not apply to dtype '{a.dtype}' (2: integers, 3: floats)")
+    bigtiff_wanted(bigtiff, 0, compress, 0)   # (an unknown mode is refused before anything is compressed)
     key = {('u', 1): (1, 8), ('u', 2): (1, 16), ('u', 4): (1, 32), ('i', 1): (2, 8), ('i', 2): (2, 16), ('i', 4): (2, 32),
            ('f', 4): (3, 32), ('f', 8): (3, 64)}.get((a.dtype.kind, a.dtype.itemsize))
     if key is None:
@@ -383,7 +473,8 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
     def ascii_(s):
         return s.encode('latin-1', 'replace') + b'\0'
 
-    def image_entries(img, img_tile, chunks, reduced):
+    def image_entries(img, img_tile, reduced):
+        """ the directory of one image without its tile offsets and byte counts (``_directory`` adds those, in the layout's width) """
         entries = []  # (code, type, count, payload bytes)
 
         def add(code, typ, values):
@@ -398,61 +489,65 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
             add(T_SUBFILE, 4, [1])
         add(T_WIDTH, 4, [img.shape[2]]), add(T_HEIGHT, 4, [img.shape[1]]), add(T_BITS, 3, [bits] * nb)
         add(T_COMPRESSION, 3, [8 if compress else 1]), add(T_PHOTOMETRIC, 3, [1]), add(T_SPP, 3, [nb]), add(T_PLANAR, 3, [2])
+        if predictor != 1:
+            add(T_PREDICTOR, 3, [predictor])
         add(T_TILE_W, 4, [img_tile]), add(T_TILE_H, 4, [img_tile])
-        add(T_TILE_OFFSETS, 4, [0] * len(chunks)), add(T_TILE_COUNTS, 4, [len(c) for c in chunks])
         if nb > 1:
             add(T_EXTRA, 3, [0] * (nb - 1))
         add(T_FORMAT, 3, [fmt] * nb)
         if nodata is not None:
             add(T_GDAL_NODATA, 2, 'nan' if (isinstance(nodata, float) and np.isnan(nodata)) else repr(float(nodata)) if a.dtype.kind == 'f' else str(int(nodata)))
-        return entries, add
+        if not reduced:
+            geo_entries(add)
+        return entries
 
     def tile_streams(img, img_tile):
         if compressor is None:
-            return _tile_chunks(img, img_tile, compress)
-        streams = [bytes(c) for c in compressor(img, img_tile)]
+            return _tile_chunks(img, img_tile, compress, predictor)
+        streams = [bytes(c) for c in (compressor(img, img_tile) if predictor == 1 else compressor(img, img_tile, predictor=predictor))]
         expected = img.shape[0] * (-(-img.shape[1] // img_tile)) * (-(-img.shape[2] // img_tile))
         if len(streams) != expected:
             raise ValueError(f'the compressor returned {len(streams)} streams for {expected} tiles')
         return streams
 
-    chunks = tile_streams(a, tile)
-    entries, add = image_entries(a, tile, chunks, False)
-    if transform.b != 0 or transform.d != 0:   # a rotated / sheared grid: the full matrix instead of pixel scale + tie point
-        add(T_TRANSFORMATION, 12, [float(transform.a), float(transform.b), 0., float(transform.c),
-                                   float(transform.d), float(transform.e), 0., float(transform.f),
-                                   0., 0., 0., 0., 0., 0., 0., 1.])
-    else:
-        add(T_PIXEL_SCALE, 12, [float(transform.a), float(-transform.e), 0.])
-        add(T_TIEPOINT, 12, [0., 0., 0., float(transform.c), float(transform.f), 0.])
-    name = crs.to_string() if crs is not None else ''
-    m = re.fullmatch(r'EPSG:(\d+)', name or '')
-    if m:
-        geographic = int(m.group(1)) in (4326, 4269, 4258)
-        add(T_GEOKEYS, 3, [1, 1, 0, 3, 1024, 0, 1, 2 if geographic else 1, 1025, 0, 1, 1,
-                           2048 if geographic else 3072, 0, 1, int(m.group(1))])
-    elif name:
-        add(T_GEOKEYS, 3, [1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 1026, T_GEOASCII, len(name) + 1, 0])
-        add(T_GEOASCII, 2, name + '|')
     if descriptions is not None and len(descriptions) != nb:
         raise ValueError(f'{len(descriptions)} band descriptions for {nb} bands')
-    if metadata or (descriptions and any(d is not None for d in descriptions)):
-        items = ''.join(f'  <Item name="{escape(str(k), {chr(34): "&quot;"})}">{escape(str(v))}</Item>\n' for k, v in (metadata or {}).items())
-        items += ''.join(f'  <Item name="DESCRIPTION" sample="{i}" role="description">{escape(str(d))}</Item>\n'
-                         for i, d in enumerate(descriptions or ()) if d is not None)
-        add(T_GDAL_METADATA, 2, f'<GDALMetadata>\n{items}</GDALMetadata>\n')
 
-    # the images one behind the other, each directory in front of its own data: the main image lies where it does without
-    # overviews, and the 4 GiB bound of a classic TIFF is checked on every offset up to the file's end
-    blobs = []
-    blob, pos = _directory(entries, chunks, 8, bool(levels))
-    blobs.append(blob)
-    for k, lv in enumerate(levels):
-        lv_chunks = tile_streams(lv, OVERVIEW_TILE)
-        lv_entries, _ = image_entries(lv, OVERVIEW_TILE, lv_chunks, True)
-        blob, pos = _directory(lv_entries, lv_chunks, pos, k + 1 < len(levels))
-        blobs.append(blob)
+    def geo_entries(add):
+        if transform.b != 0 or transform.d != 0:   # a rotated / sheared grid: the full matrix instead of pixel scale + tie point
+            add(T_TRANSFORMATION, 12, [float(transform.a), float(transform.b), 0., float(transform.c),
+                                       float(transform.d), float(transform.e), 0., float(transform.f),
+                                       0., 0., 0., 0., 0., 0., 0., 1.])
+        else:
+            add(T_PIXEL_SCALE, 12, [float(transform.a), float(-transform.e), 0.])
+            add(T_TIEPOINT, 12, [0., 0., 0., float(transform.c), float(transform.f), 0.])
+        name = crs.to_string() if crs is not None else ''
+        m = re.fullmatch(r'EPSG:(\d+)', name or '')
+        if m:
+            geographic = int(m.group(1)) in (4326, 4269, 4258)
+            add(T_GEOKEYS, 3, [1, 1, 0, 3, 1024, 0, 1, 2 if geographic else 1, 1025, 0, 1, 1,
+                               2048 if geographic else 3072, 0, 1, int(m.group(1))])
+        elif name:
+            add(T_GEOKEYS, 3, [1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 1026, T_GEOASCII, len(name) + 1, 0])
+            add(T_GEOASCII, 2, name + '|')
+        if metadata or (descriptions and any(d is not None for d in descriptions)):
+            items = ''.join(f'  <Item name="{escape(str(k), {chr(34): "&quot;"})}">{escape(str(v))}</Item>\n' for k, v in (metadata or {}).items())
+            items += ''.join(f'  <Item name="DESCRIPTION" sample="{i}" role="description">{escape(str(d))}</Item>\n'
+                             for i, d in enumerate(descriptions or ()) if d is not None)
+            add(T_GDAL_METADATA, 2, f'<GDALMetadata>\n{items}</GDALMetadata>\n')
+
+    # every tile of every image is compressed first: then all sizes are known, the layout (classic or BigTIFF) is decided before a
+    # byte is written, and a raster past 4 GiB is never lost after the work is done.  The images lie one behind the other, each
+    # directory in front of its own data: the main image lies where it does without overviews.
+    images = [(image_entries(a, tile, False), tile_streams(a, tile))]
+    images += [(image_entries(lv, OVERVIEW_TILE, True), tile_streams(lv, OVERVIEW_TILE)) for lv in levels]
+    classic_end = 8
+    for entries, chunks in images:
+        classic_end = _layout(entries, chunks, classic_end, False)[3]
+    big = bigtiff_wanted(bigtiff, a.size * a.dtype.itemsize, compress, classic_end)
     with open(path, 'wb') as f:
-        f.write(b'II' + struct.pack('<HI', 42, 8))
-        for blob in blobs:
+        f.write(b'II' + (struct.pack('<HHHQ', 43, 8, 0, 16) if big else struct.pack('<HI', 42, 8)))
+        pos = 16 if big else 8
+        for k, (entries, chunks) in enumerate(images):
+            blob, pos = _directory(entries, chunks, pos, k + 1 < len(images), big)
             f.write(blob)

@@ -78,7 +78,8 @@ typedef struct {
  * points (hk_deflate_bound, hk_deflate_tiles, hk_deflate_tiles_dev).  The inflate entry points (hk_inflate_bound,
  * hk_inflate_image, hk_inflate_image_dev, with the new struct hk_inflate_layout) were added WITHOUT a new version: no existing
  * layout or prototype changed, so a version-12 consumer runs unchanged against either library; a consumer that wants them looks
- * them up by symbol (dlsym) and does without where they are absent.
+ * them up by symbol (dlsym) and does without where they are absent.  hk_deflate_tiles_pred and hk_deflate_tiles_pred_dev were
+ * added the same way.
  * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
 #define HK_ABI_VERSION 12
 int hk_abi_version(void);
@@ -158,6 +159,18 @@ int hk_deflate_bound(int32_t dtype, int32_t n_bands, int32_t height, int32_t wid
 int hk_deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
                      int64_t band_stride, int32_t tile, void* out, int64_t out_capacity, int64_t* tile_offsets /* n_tiles + 1 */,
                      int64_t* tile_sizes /* n_tiles */);
+/* hk_deflate_tiles over the PREDICTED bytes of every tile (TIFF tag 317), for a file that carries the Predictor tag.  The predictor
+ * runs over each zero-padded tile row of `tile` samples on its own.  1: none -- exactly the bytes of hk_deflate_tiles.  2 (integer
+ * dtypes): p[i] = s[i] - s[i - 1] modulo 2^(8 x sample size), p[0] = s[0], samples little-endian; the step from the last pixel into the
+ * padding is part of the row.  3 (HK_DTYPE_F32 / F64; libtiff's floating-point predictor): the row's bytes regrouped into planes of
+ * `tile` bytes, most significant byte of every sample first, then differenced byte by byte modulo 256 over the whole row.  The stream
+ * is the one described above with the predicted bytes in place of the raw ones (the Adler-32 too); the first match distance is the
+ * sample size with predictors 1 and 2 and ONE with predictor 3.  hk_deflate_bound holds unchanged.  Predictor 2 with a float dtype,
+ * 3 with an integer dtype and every other value: HK_ERR_ARG, before anything else is looked at.  Added to version 12 without a new
+ * version, like the inflate entry points: look the symbol up where an older library may be loaded. */
+int hk_deflate_tiles_pred(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                          int64_t stride, int64_t band_stride, int32_t tile, void* out, int64_t out_capacity,
+                          int64_t* tile_offsets /* n_tiles + 1 */, int64_t* tile_sizes /* n_tiles */, int32_t predictor);
 
 /* INFLATE on the device: the DEFLATE blocks (tiles or strips) of one GeoTIFF image, compression 8 or 32946, inflated and put in
  * their place in a (spp, height, width) raster, in place of zlib.decompress + the predictor + a slice copy per block on a host
@@ -606,6 +619,10 @@ int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t
 int hk_deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
                          int64_t stride, int64_t band_stride, int32_t tile, void* out_dev, int64_t out_capacity,
                          int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream);
+/* hk_deflate_tiles_dev with a predictor, as hk_deflate_tiles_pred states it; predictor 1 gives the bytes of hk_deflate_tiles_dev. */
+int hk_deflate_tiles_pred_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                              int64_t stride, int64_t band_stride, int32_t tile, void* out_dev, int64_t out_capacity,
+                              int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream, int32_t predictor);
 
 /* hk_inflate_image for device-resident streams, offsets and sizes: the raster into out_dev, the statuses into status_dev (n_blocks
  * int32, required: nothing comes back to the host, so the call cannot report a refused block itself); work_dev: hk_inflate_bound's

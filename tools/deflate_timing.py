@@ -8,6 +8,9 @@ uint8 in 3 bands (a real-imagery fixture of tests/golden/rasters tiled up).  Per
   * the kernels alone on device-resident planes (``hk_deflate_tiles_dev`` between two events; warm-up, median of >= 10);
   * the bytes that cross PCIe each way on the device path;
   * the file sizes, and the device's streams as a fraction of level 6's.
+``--predictor 2`` / ``3``: both paths write with that TIFF predictor (the host path predicts with numpy, the device path in
+deflate_pred_chunk_kernel); a raster the predictor does not apply to (2: the floats, 3: the integers) is left out, and the kernels
+are timed at predictor 1 as well, in the same process, for the cost of the predicted launch.
 The report goes to stdout and to ``--out``. """
 import argparse
 import os
@@ -38,7 +41,7 @@ def rasters(size):
     yield 'uint8 3 bands, sentinel2 fixture tiled up', np.ascontiguousarray(np.tile(fixture, reps)[:, :size, :size]), 0
 
 
-def kernels_ms(ctx, a, tile, reps):
+def kernels_ms(ctx, a, tile, reps, predictor=1):
     nb, h, w = a.shape
     n_tiles, cap = _hk.deflate_bound(a.dtype.name, nb, h, w, tile)
     d_src, d_out = ctx.dev_alloc(a.nbytes), ctx.dev_alloc(cap)
@@ -47,7 +50,7 @@ def kernels_ms(ctx, a, tile, reps):
         ctx.h2d(d_src, a)
 
         def launch():
-            ctx.deflate_tiles_dev(d_src, a.dtype.name, nb, h, w, w, h * w, tile, d_out, cap, d_off, d_siz, stream=0)
+            ctx.deflate_tiles_dev(d_src, a.dtype.name, nb, h, w, w, h * w, tile, d_out, cap, d_off, d_siz, stream=0, predictor=predictor)
 
         for _ in range(2):
             launch()
@@ -75,25 +78,29 @@ def main():
     ap.add_argument('--tile', type=int, default=512)
     ap.add_argument('--reps', type=int, default=3, help='timed write_tiff calls on the device path')
     ap.add_argument('--kernel-reps', type=int, default=10)
+    ap.add_argument('--predictor', type=int, choices=(1, 2, 3), default=1, help='TIFF predictor of both paths (2: integer rasters, 3: float rasters)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     ctx = _hk.default_context()
-    lines = [f'# tools/deflate_timing.py --size {a.size} --tile {a.tile}: write_tiff with host zlib level 6 against Context.deflate_tiles',
+    lines = [f'# tools/deflate_timing.py --size {a.size} --tile {a.tile} --predictor {a.predictor}: write_tiff with host zlib level 6 against Context.deflate_tiles',
              f'# device path: one warm-up, median of {a.reps}; kernels: two warm-ups, median of {max(10, a.kernel_reps)} event pairs']
     with tempfile.TemporaryDirectory() as tmp:
         for name, arr, nodata in rasters(a.size):
+            if (a.predictor == 2 and arr.dtype.kind == 'f') or (a.predictor == 3 and arr.dtype.kind != 'f'):
+                continue
             host_file, dev_file = os.path.join(tmp, 'host.tif'), os.path.join(tmp, 'dev.tif')
             t0 = time.perf_counter()
-            write_tiff(host_file, arr, TF, CRS('EPSG:32735'), nodata=nodata, tile=a.tile)
+            write_tiff(host_file, arr, TF, CRS('EPSG:32735'), nodata=nodata, tile=a.tile, predictor=a.predictor)
             host_s = time.perf_counter() - t0
             dev_s = []
             for k in range(a.reps + 1):
                 t0 = time.perf_counter()
-                write_tiff(dev_file, arr, TF, CRS('EPSG:32735'), nodata=nodata, tile=a.tile, compressor=ctx.deflate_tiles)
+                write_tiff(dev_file, arr, TF, CRS('EPSG:32735'), nodata=nodata, tile=a.tile, compressor=ctx.deflate_tiles,
+                           predictor=a.predictor)
                 dev_s.append(time.perf_counter() - t0)
             dev_med = float(np.median(dev_s[1:]))
             same = read_tiff(dev_file).array.tobytes() == arr.tobytes()
-            ms, stream_bytes, n_tiles = kernels_ms(ctx, arr, a.tile, max(10, a.kernel_reps))
+            ms, stream_bytes, n_tiles = kernels_ms(ctx, arr, a.tile, max(10, a.kernel_reps), a.predictor)
             host_size, dev_size = os.path.getsize(host_file), os.path.getsize(dev_file)
             lines += [
                 f'{name}: {arr.shape}, {arr.nbytes / 1e6:.1f} MB raw, {n_tiles} tiles',
@@ -105,6 +112,11 @@ def main():
                 f'  PCIe: {arr.nbytes} bytes to the device, {stream_bytes + 16 * n_tiles + 8} back ({stream_bytes} of streams, 16 per tile of offsets and sizes)',
                 f'  size: device / level 6 = {dev_size / host_size:.4f}',
             ]
+            if a.predictor != 1:
+                ms1, bytes1, _ = kernels_ms(ctx, arr, a.tile, max(10, a.kernel_reps), 1)
+                lines.append(f'  kernels alone at predictor 1       median {np.median(ms1):8.3f} ms, min {min(ms1):.3f}, max {max(ms1):.3f}'
+                             f'   ({bytes1} bytes of streams; predictor {a.predictor}: {stream_bytes}); predicted / predictor 1 = '
+                             f'{np.median(ms) / np.median(ms1):.3f}')
     text = '\n'.join(lines) + '\n'
     print(text, end='')
     if a.out:
