@@ -1,6 +1,10 @@
 // hk_resample_taps.h -- THE statement of what the re-samplers do with a continuous source coordinate (integers = pixel edges):
-// GDAL's published warp kernels (gdal/alg/gdalwarpkernel.cpp) restated, operation for operation the arithmetic of
-// oracle/oracle_np.py::reproject, which the tests hold the kernels to bit for bit.  hk_resample.hip (same-CRS scaled grids) and
+// GDAL's published warp kernels (gdal/alg/gdalwarpkernel.cpp) restated.  What this file is held to is the exact statement of
+// tests/_resample_exact.py -- the same rules in rational arithmetic, sharing no formula with this file -- for every method, on scaled
+// grids and on the per-pixel coordinates of hk_warp.hip: identical nodata pattern, the exact-valued methods to the bit, the weighted
+// ones within half a float32 ulp plus a derived 2^-40 float64 slack.  The arithmetic is, operation for operation, that of
+// oracle/oracle_np.py::reproject, which meets the same statement and to which the tests also hold the kernels bit for bit (lanczos:
+// 1e-6, the device's sin) at the large shapes.  hk_resample.hip (same-CRS scaled grids) and
 // hk_warp.hip (two CRSs, rotated grids) differ in where a destination pixel's source coordinate comes from and in how threads and
 // bands are laid out; what is done with the coordinate is written here only.  Every function takes plain values -- plane pointer,
 // stride, shape, nodata rule, coordinates -- and no kernel's argument struct.  (upsample_apply_kernel of hk_resample.hip mirrors

@@ -3,9 +3,12 @@ coordinates.
 
 ``oracle_np.reproject`` states GDAL's warp kernels for an affine mapping ``sx = kx * (j + .5) + ox``.  Across CRSs the only thing
 that changes is where ``sx, sy`` come from; this module restates the same arithmetic, operation for operation, with the
-coordinates handed in as planes.  tests/test_warp_reference_cpu.py pins it to the oracle bit for bit on affine planes; the GPU
-tests feed it the device's own coordinate planes.  ``kx, ky`` (source pixels per destination pixel) pick the stretched kernels
-and scale their support exactly as the oracle's mapping factors do. """
+coordinates handed in as planes.  It is held to the exact statement of tests/_resample_exact.py (rational arithmetic from GDAL's rule,
+no formula shared) on turned grids whose coordinates are arbitrary doubles, all five methods, by
+tests/test_resample_exact_cpu.py; tests/test_warp_reference_cpu.py pins it to the oracle bit for bit on affine planes.  The GPU tests
+hold the kernels to the exact statement directly on small grids, and feed this module the device's own coordinate planes for the
+bit-for-bit comparison at the large ones.  ``kx, ky`` (source pixels per destination pixel) pick the stretched kernels and scale
+their support exactly as the oracle's mapping factors do. """
 import math
 
 import numpy as np

@@ -1,9 +1,11 @@
 """ The generic re-samplers of hk_resample.hip (resample_kernel, resample_conv_kernel) through hk_reproject.
 
-* bilinear, cubic_spline (up-sampling) and average (down-sampling) held DIRECTLY to the exact statement of tests/_resample_exact.py
-  -- rational arithmetic written from GDAL's rule, sharing no formula with the kernel or with oracle_np --: identical nodata pattern
-  and every pixel within ``1/2 ulp32 + 2^-40 A`` of the exact value; no pixel exempt (a case with an accumulated weight within 1e-9
-  of a threshold of the rule fails as mis-designed);
+* every method of RESAMPLING_CODES held DIRECTLY to the exact statement of tests/_resample_exact.py -- rational arithmetic written
+  from GDAL's rule, sharing no formula with the kernel or with oracle_np --: the tap form up-sampling, the convolution form (cubic,
+  lanczos, stretched bilinear / cubic / cubic_spline) up, down and one axis each, nearest, and the nine footprint methods on a source
+  with ties; identical nodata pattern, the exact-valued methods to the bit, the others inside the enclosure stated there
+  (``1/2 ulp32 + 2^-40 A``; lanczos absolute, on signed sources); no pixel exempt (a case that breaks a guard of the statement fails
+  as mis-designed);
 * the edges, against oracle_np.reproject bit for bit (lanczos: the project's bar, same nodata pattern and 1e-6 relative, the
   device's ``sin`` differs from the host's in the last bit): several bands in one call, sources of one to nine pixels for every built
   method up and down, destinations wholly and partly outside the source, a numeric fill value, numeric nodata, destinations of one row
@@ -65,6 +67,38 @@ def test_device_upsamplers_inside_the_exact_enclosure(ctx, method, mapping, dst_
 @pytest.mark.parametrize('mapping, dst_shape', rx.DOWN_CASES)
 def test_device_average_inside_the_exact_enclosure(ctx, mapping, dst_shape, nodata):
     _hold(ctx, 'average', mapping, dst_shape, nodata, rx.AVG_SHAPE)
+
+
+def _hold_res(res, what, n_min):
+    rx.assert_held(res, f'device {what}', n_min)
+
+
+@pytest.mark.parametrize('nodata', [np.nan, -9999.])
+@pytest.mark.parametrize('half', [0, 1])
+@pytest.mark.parametrize('method', METHODS)
+def test_every_method_inside_the_exact_enclosure(ctx, method, nodata, half):
+    """ every method of RESAMPLING_CODES on every dyadic case the statement holds it on (in two halves, which keeps each test
+    short): the convolution form (cubic and lanczos at every scale, the stretched bilinear / cubic / cubic_spline, one axis up and
+    one down), nearest, and the footprint methods on a source with ties.  Signed sources throughout, lanczos included: its
+    enclosure is absolute.  The exact side is computed once for both nodata variants. """
+    cases = rx.scaled_cases(method)[half::2]
+    assert cases
+    for mapping, dst_shape, build in cases:
+        src = build(nodata)
+        got = ctx.reproject(src, nodata, mapping, dst_shape, CODES[method], np.nan)
+        _hold_res(rx.enclosure_failures(got, src, nodata, mapping, dst_shape, method), f'{method} {mapping} nodata {nodata}',
+                  0.4 * dst_shape[0] * dst_shape[1])
+
+
+@pytest.mark.parametrize('method', METHODS)
+def test_every_method_with_a_numeric_fill(ctx, method):
+    """ dst_fill = -9999 where the rule gives nothing: the pattern is read off the fill value, the values are held as before """
+    mapping, dst_shape, build = rx.scaled_cases(method)[-1]
+    src = build(np.nan)
+    got = ctx.reproject(src, np.nan, mapping, dst_shape, CODES[method], -9999.)
+    assert not np.isnan(got).any() and (got == -9999.).any()
+    _hold_res(rx.enclosure_failures(got, src, np.nan, mapping, dst_shape, method, fill=-9999.), f'{method} {mapping} fill -9999',
+              0.4 * dst_shape[0] * dst_shape[1])
 
 
 # -- edges -----------------------------------------------------------------------------------------------------------

@@ -3,8 +3,13 @@
 * coordinates within one CRS: ``Context.warp_coords_affine`` against exact rational arithmetic on the five grid pairs of
   tests/_rotated_grids.py, under the bar stated there; across two CRSs against the 40-digit evaluation (tests/_crs_mp.py) composed
   with the exact affines, below the project's 1e-6 m;
-* re-samplers: the device's own coordinate planes fed to the numpy restatement (tests/_warp_reference.py): bit for bit for nearest /
-  bilinear / cubic / cubic_spline, the project's lanczos bar for lanczos; no pixel is exempt;
+* re-samplers, what they are held to: the exact statement of tests/_resample_exact.py (rational arithmetic from GDAL's rule, sharing
+  no formula with the kernels) on the device's own coordinate planes -- all five methods on both affine paths, unit scale, up and
+  3:1 down, on 24 x 36 sources: identical nodata pattern, nearest bit for bit, the rest inside the enclosure stated there; no pixel
+  is exempt;
+* re-samplers, large shapes and workgroup boundaries: the same planes fed to the numpy restatement (tests/_warp_reference.py, itself
+  held to the exact statement by tests/test_resample_exact_cpu.py): bit for bit for nearest / bilinear / cubic / cubic_spline, the
+  project's lanczos bar for lanczos;
 * exact turns: a raster stored turned by 90 / 180 / 270 degrees, south-up or not, comes back bit for bit;
 * the device entry points equal the host ones, three bands equal three single bands;
 * the pipeline: ``RasterFuse`` / ``RasterCompare`` on rotated GeoTIFFs equal the same classes on the hand-warped rasters;
@@ -19,6 +24,7 @@ import numpy as np
 import pytest
 
 import _crs_mp
+import _resample_exact as rx
 import _rotated_grids as rg
 import _warp_reference as wr
 from conftest import assert_same_f32
@@ -224,6 +230,71 @@ def test_affine_resamplers_equal_the_restatement_on_the_devices_coordinates(ctx,
 @pytest.mark.parametrize('nodata', [None, -9999.], ids=['none', 'number'])
 def test_bilinear_at_30_degrees_with_nodata_none_and_number(ctx, nodata):
     _resample_case(ctx, 'rot30', 'bilinear', nodata)
+
+
+# -- 3b. re-samplers against the exact statement --------------------------------------------------------------------------------------
+SMALL_SHAPE = (24, 36)
+SMALL_CASES = ('rot30', 'rot30-up', 'rot30-down3', 'sheared', 'rotated-dst', 'two-crs', 'two-crs-up', 'two-crs-down3')
+
+
+def small_case(name):
+    """ WARP_AFFINE_SAME and WARP_AFFINE on a 24 x 36 source: grids small enough for rational arithmetic at every pixel.  The source
+    turned by 30 degrees spans 43.2 x 38.8 pixels of its own size """
+    def centred(tf, res, shape, shift=(0., 0.)):
+        d = _centred(tf, res, shape, SMALL_SHAPE)
+        return Case(WEB, tf, WEB, Affine(d.a, 0., d.c + shift[0], 0., d.e, d.f + shift[1]), shape, src_shape=SMALL_SHAPE)
+    if name == 'rot30':           # unit scale, wider than the turned source
+        return centred(ROT30, 30., (36, 52))
+    if name == 'rot30-up':        # 0.4 source pixels per pixel: the tap form of bilinear and cubic_spline
+        return centred(ROT30, 12., (40, 56))
+    if name == 'rot30-down3':     # three times coarser, 48 x 54 source pixels: overhangs the turned source on all sides
+        return centred(ROT30, 90., (16, 18))
+    if name == 'sheared':         # off the lattice on which this shear's coordinates are whole numbers (guard 2 of the statement)
+        return centred(Affine(30., 3., X0, -2., -30., Y0), 30., (30, 44), shift=(7.3, -4.1))
+    if name == 'rotated-dst':     # a north-up source onto a destination turned by 15 degrees
+        tf, shape = Affine(30., 0., X0, 0., -30., Y0), (30, 44)
+        xc, yc = tf * (SMALL_SHAPE[1] / 2, SMALL_SHAPE[0] / 2)
+        dst = Affine.translation(xc, yc) * Affine.rotation(15.) * Affine.scale(30., -30.) * Affine.translation(-shape[1] / 2,
+                                                                                                          -shape[0] / 2)
+        return Case(WEB, tf, WEB, dst, shape, src_shape=SMALL_SHAPE)
+    tf, (h, w) = suggested_warp_grid(TM25, TM_ROT30, SMALL_SHAPE, UTM35S)
+    if name == 'two-crs':         # a turned Transverse Mercator source onto the suggested UTM grid
+        return Case(TM25, TM_ROT30, UTM35S, tf, (h, w), src_shape=SMALL_SHAPE)
+    if name == 'two-crs-up':      # 30 m -> 12 m about the source's centre
+        x, y = crs.transform_coords(TM25, UTM35S, *(TM_ROT30 * (SMALL_SHAPE[1] / 2, SMALL_SHAPE[0] / 2)))
+        return Case(TM25, TM_ROT30, UTM35S, Affine(12., 0., float(x) - 12. * 28, 0., -12., float(y) + 12. * 20), (40, 56),
+                    src_shape=SMALL_SHAPE)
+    if name == 'two-crs-down3':
+        return Case(TM25, TM_ROT30, UTM35S, Affine(tf.a * 3, 0., tf.c, 0., tf.e * 3, tf.f), (h // 3 + 2, w // 3 + 2),
+                    src_shape=SMALL_SHAPE)
+    raise KeyError(name)
+
+
+@pytest.mark.oracle
+@pytest.mark.parametrize('nodata', [np.nan, -9999.], ids=['nan', 'number'])
+@pytest.mark.parametrize('resampling', wr.MODES)
+@pytest.mark.parametrize('case_name', SMALL_CASES)
+def test_affine_resamplers_inside_the_exact_enclosure(ctx, case_name, resampling, nodata):
+    """ the affine builds of hk_warp.hip held DIRECTLY to the exact statement of tests/_resample_exact.py on the device's own
+    coordinate planes, which are arbitrary doubles: identical nodata pattern, bit-equal for nearest, inside the enclosure for the
+    rest; the guards of the statement make a case that would exempt a pixel fail as mis-designed.  The exact side is computed once
+    per (case, method) and serves both nodata variants. """
+    c = small_case(case_name)
+    assert max(c.dst_shape) <= 60 and c.same == (not case_name.startswith('two-crs'))
+    src = source(nodata, shape=SMALL_SHAPE)
+    got = ctx.reproject_affine(src, nodata, c.warp, c.scale, c.dst_shape, onp.RESAMPLING_CODES[resampling], np.nan)
+    sx, sy = ctx.warp_coords_affine(c.warp, c.dst_shape)
+    inside = (sx >= 0) & (sx < SMALL_SHAPE[1]) & (sy >= 0) & (sy < SMALL_SHAPE[0])
+    res = rx.enclosure_failures_at(got, src, nodata, sx, sy, c.scale[0], c.scale[1], resampling)
+    rx.assert_held(res, f'device affine {case_name} {resampling} nodata {nodata}', 0.3 * inside.sum())
+    if not case_name.endswith('-up'):
+        assert (~inside).any()
+    if case_name == 'rot30-down3':      # overhangs the source on all four sides
+        assert not inside[0].any() and not inside[-1].any() and not inside[:, 0].any() and not inside[:, -1].any()
+    expected = 3. if case_name.endswith('down3') else 0.4 if case_name.endswith('-up') else 1.
+    tol = 0.02 if case_name == 'sheared' else 1e-3 if case_name.startswith('two-crs') else 1e-12
+    assert abs(c.scale[0] / expected - 1.) < tol and abs(c.scale[1] / expected - 1.) < tol
+    assert rx.uses_conv('bilinear', *c.scale) == (max(c.scale) > 1 + 1e-9)
 
 
 # -- 4. exact turns -----------------------------------------------------------------------------------------------------------------

@@ -2,9 +2,14 @@
 
 * coordinates: ``Context.warp_coords`` against the 40-digit mpmath evaluation of the same CRS definitions (tests/_crs_mp.py), below
   1e-6 m, converted to source pixels -- centres and corners of a 97 x 131 lattice, four CRS pairs;
-* re-samplers: the device's own coordinate planes fed to the numpy restatement (tests/_warp_reference.py, pinned to the oracle by
-  tests/test_warp_reference_cpu.py): bit for bit for nearest / bilinear / cubic / cubic_spline, the project's lanczos bar (same
-  NaN pattern, < 1e-6 relative: the device's ``sin`` differs from the host's in the last bit) for lanczos; no pixel is exempt;
+* re-samplers, what they are held to: the exact statement of tests/_resample_exact.py (rational arithmetic from GDAL's rule, sharing
+  no formula with the kernels) on the device's own coordinate planes -- all five methods, tap and convolution form, unit scale, up
+  and 3:1 down, on 24 x 36 sources: identical nodata pattern, nearest bit for bit, the rest inside the enclosure stated there; no
+  pixel is exempt;
+* re-samplers, large shapes: the same planes fed to the numpy restatement (tests/_warp_reference.py, itself held to the exact
+  statement by tests/test_resample_exact_cpu.py and pinned to the oracle by tests/test_warp_reference_cpu.py): bit for bit for
+  nearest / bilinear / cubic / cubic_spline, the project's lanczos bar (same NaN pattern, < 1e-6 relative: the device's ``sin``
+  differs from the host's in the last bit) for lanczos;
 * a geometry check that does not go through the restatement: a plane in UTM coordinates must come back as the same plane of the
   exactly transformed pixel centres;
 * the pipeline: ``RasterFuse`` / ``RasterCompare`` on files of two CRSs equal the same classes on the hand-warped pair;
@@ -17,6 +22,7 @@ import numpy as np
 import pytest
 
 import _crs_mp
+import _resample_exact as rx
 import _warp_reference as wr
 from conftest import assert_same_f32
 from homonim_amd import (Affine, CRS, DeviceError, Model, RasterArray, RasterCompare, RasterFuse, RefSpaceModel, Resampling,
@@ -247,6 +253,69 @@ def test_three_bands_on_a_pitched_layout(ctx, resampling):
         check_band(got[b], exp, resampling, f'band {b} {resampling}')
     host = ctx.reproject_crs(src, np.nan, c.warp, c.scale, c.dst_shape, code, np.nan)
     assert_same_f32(host, got, f'host against device entry point, {resampling}')
+
+
+# -- 2b. re-samplers against the exact statement ------------------------------------------------------------------------------------
+SMALL_SHAPE = (24, 36)
+SMALL_CASES = ('unit', 'up', 'down3', 'utm-geo')
+
+
+def small_case(name):
+    """ the WARP_AXIS path on a 24 x 36 source: grids small enough for rational arithmetic at every pixel """
+    if name == 'unit':        # 30 m Transverse Mercator -> 30 m UTM, the suggested grid and 2 pixels more on every side
+        return Case(TM25, TM_TF, UTM35S, *_grown(*suggested_warp_grid(TM25, TM_TF, SMALL_SHAPE, UTM35S), 2), src_shape=SMALL_SHAPE)
+    if name == 'up':          # 30 m -> 12 m about the source's centre: 0.4 source pixels per pixel, the tap form
+        xc, yc = TM_TF.c + TM_TF.a * SMALL_SHAPE[1] / 2, TM_TF.f + TM_TF.e * SMALL_SHAPE[0] / 2
+        x, y = crs.transform_coords(TM25, UTM35S, xc, yc)
+        return Case(TM25, TM_TF, UTM35S, Affine(12., 0., float(x) - 12. * 28, 0., -12., float(y) + 12. * 20), (40, 56),
+                    src_shape=SMALL_SHAPE)
+    if name == 'down3':       # 10 m -> 30 m: the stretched kernels
+        tf, (h, w) = suggested_warp_grid(TM25, _scaled(TM_TF, 1 / 3), SMALL_SHAPE, UTM35S)
+        return Case(TM25, _scaled(TM_TF, 1 / 3), UTM35S, _scaled(tf, 3.), (h // 3 + 2, w // 3 + 2), src_shape=SMALL_SHAPE)
+    if name == 'utm-geo':
+        return Case(UTM35S, UTM_TF, WGS84, *suggested_warp_grid(UTM35S, UTM_TF, SMALL_SHAPE, WGS84), src_shape=SMALL_SHAPE)
+    raise KeyError(name)
+
+
+def small_source(nodata, seed=14):
+    a, _ = onp.synth_pair(*SMALL_SHAPE, seed, 'frame+holes')
+    if not np.isnan(nodata):
+        a[np.isnan(a)] = nodata
+    return a
+
+
+@pytest.mark.oracle
+@pytest.mark.parametrize('nodata', [np.nan, -9999.], ids=['nan', 'number'])
+@pytest.mark.parametrize('resampling', wr.MODES)
+@pytest.mark.parametrize('case_name', SMALL_CASES)
+def test_warp_resamplers_inside_the_exact_enclosure(ctx, case_name, resampling, nodata):
+    """ hk_warp.hip held DIRECTLY to the exact statement of tests/_resample_exact.py on the device's own coordinate planes, which
+    are arbitrary doubles: identical nodata pattern, bit-equal for nearest, inside the enclosure for the rest; the guards of the
+    statement make a case that would exempt a pixel fail as mis-designed.  The exact side is computed once per (case, method) and
+    serves both nodata variants and the bands of the second one. """
+    c = small_case(case_name)
+    assert max(c.dst_shape) <= 60
+    src = small_source(nodata)
+    code = onp.RESAMPLING_CODES[resampling]
+    got = ctx.reproject_crs(src, nodata, c.warp, c.scale, c.dst_shape, code, np.nan)
+    sx, sy = ctx.warp_coords(c.warp, c.dst_shape)
+    inside = (sx >= 0) & (sx < SMALL_SHAPE[1]) & (sy >= 0) & (sy < SMALL_SHAPE[0])
+    res = rx.enclosure_failures_at(got, src, nodata, sx, sy, c.scale[0], c.scale[1], resampling)
+    rx.assert_held(res, f'device warp {case_name} {resampling} nodata {nodata}', 0.3 * inside.sum())
+    if case_name == 'unit':       # overhangs the source on all four sides
+        assert not inside[:2].any() and not inside[-2:].any() and not inside[:, :2].any() and not inside[:, -2:].any()
+        assert 0.99 < c.scale[0] < 1.01 and 0.99 < c.scale[1] < 1.01
+    if case_name == 'up':
+        assert 0.39 < c.scale[0] < 0.41 and 0.39 < c.scale[1] < 0.41 and not rx.uses_conv('bilinear', *c.scale)
+    if case_name == 'down3':
+        assert (~inside).any() and 2.9 < c.scale[0] < 3.1 and 2.9 < c.scale[1] < 3.1 and rx.uses_conv('bilinear', *c.scale)
+    if not np.isnan(nodata):      # three bands in one call, the first and the last the same raster
+        other = small_source(nodata, seed=15)
+        three = ctx.reproject_crs(np.stack([src, other, src]), nodata, c.warp, c.scale, c.dst_shape, code, np.nan)
+        for b in (0, 2):
+            res = rx.enclosure_failures_at(three[b], src, nodata, sx, sy, c.scale[0], c.scale[1], resampling)
+            rx.assert_held(res, f'device warp {case_name} {resampling} band {b} of three', 0.3 * inside.sum())
+        assert not np.array_equal(three[1], three[0], equal_nan=True)
 
 
 @pytest.mark.oracle
