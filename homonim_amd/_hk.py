@@ -145,6 +145,12 @@ SIGNATURES = {
                                    C.c_int64, _P(C.c_int32)]),
     'hk_inflate_image_dev': (C.c_int, [C.c_void_p, _P(InflateLayout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int64, C.c_int64, C.c_void_p, C.c_int32]),
+    'hk_lzw_image': (C.c_int, [C.c_void_p, _P(InflateLayout), C.c_void_p, _P(C.c_int64), _P(C.c_int64), C.c_void_p, C.c_int64,
+                               C.c_int64, _P(C.c_int32)]),
+    'hk_lzw_image_host': (C.c_int, [_P(InflateLayout), C.c_void_p, _P(C.c_int64), _P(C.c_int64), C.c_void_p, C.c_int64, C.c_int64,
+                                    _P(C.c_int32)]),
+    'hk_lzw_image_dev': (C.c_int, [C.c_void_p, _P(InflateLayout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int64, C.c_int64, C.c_void_p, C.c_int32]),
     'hk_fit': (C.c_int, [C.c_void_p, _P(FitDesc), _f32p, C.c_int64, _f32p, C.c_int64, C.c_int32, C.c_int32, _f64p,
                          _f32p, C.c_int32, _f64p, _u64p]),
     'hk_apply': (C.c_int, [C.c_void_p, _f32p, C.c_int64, _f32p, C.c_int32, C.c_int32, _f32p]),
@@ -275,6 +281,60 @@ def inflate_bound(layout):
     n_blocks, raw, work = C.c_int64(), C.c_int64(), C.c_int64()
     _check(load_library().hk_inflate_bound(C.byref(_inflate_layout(layout)), C.byref(n_blocks), C.byref(raw), C.byref(work)))
     return n_blocks.value, raw.value, work.value
+
+
+# HK_LZW_*: the status of a block of Context.lzw_image_packed / lzw_image_host_packed
+LZW_OK, LZW_TRUNCATED, LZW_OLD_STYLE, LZW_BAD_FIRST, LZW_BAD_CODE, LZW_SHORT = range(6)
+
+
+def _packed_blocks(streams, offsets, sizes, lay):
+    """ the arguments of the block-image calls checked and as arrays: -> (uint8 buffer, int64 offsets, int64 sizes, out, status) """
+    n_blocks, _, _ = inflate_bound(lay)
+    buf = np.frombuffer(streams, np.uint8) if isinstance(streams, (bytes, bytearray, memoryview)) else np.ascontiguousarray(streams, np.uint8)
+    offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+    if offsets.shape != (n_blocks,) or sizes.shape != (n_blocks,):
+        raise ValueError(f'{offsets.size} offsets and {sizes.size} sizes for {n_blocks} blocks')
+    if n_blocks and ((offsets < 0).any() or (sizes < 0).any() or (offsets + sizes > buf.size).any()):
+        raise ValueError('a stream lies outside the buffer')
+    if buf.size == 0:
+        buf = np.zeros(1, np.uint8)   # (every stream is empty: a pointer all the same)
+    out = np.empty((lay.spp, lay.height, lay.width), np.dtype(f'u{lay.sample_bytes}'))
+    return buf, offsets, sizes, out, np.zeros(n_blocks, np.int32)
+
+
+def _pack_streams(streams):
+    """ a list of ``bytes`` as one buffer, every stream at a multiple of 16: -> (buffer, offsets, sizes) """
+    sizes = np.array([len(s) for s in streams], np.int64)
+    padded = (sizes + 15) // 16 * 16
+    offsets = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64) if len(sizes) else np.zeros(0, np.int64)
+    buf = np.zeros(int(padded.sum()), np.uint8)
+    for o, s in zip(offsets.tolist(), streams):
+        buf[o:o + len(s)] = np.frombuffer(s, np.uint8)
+    return buf, offsets, sizes
+
+
+def lzw_image_host_packed(streams, offsets, sizes, layout, strict: bool = True):
+    """ ``Context.lzw_image_packed`` on the calling thread (hk_lzw_image_host: the kernel's decoder compiled for the host; no
+    context, no device): the same arguments, the same (array, status per block), the same ``IoError``. """
+    lay = _inflate_layout(layout)
+    lib = load_library()
+    buf, offsets, sizes, out, status = _packed_blocks(streams, offsets, sizes, lay)
+    rc = lib.hk_lzw_image_host(C.byref(lay), buf.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(_P(C.c_int64)),
+                               sizes.ctypes.data_as(_P(C.c_int64)), out.ctypes.data_as(C.c_void_p), lay.width, lay.height * lay.width,
+                               status.ctypes.data_as(_P(C.c_int32)))
+    if rc == HK_ERR_ARG and status.any():
+        if strict:
+            raise IoError(lib.hk_last_error().decode('utf-8', 'replace'))
+        return out, status
+    _check(rc)
+    return out, status
+
+
+def lzw_image_host(streams, layout) -> np.ndarray:
+    """ What ``tiff.read_tiff`` takes as ``lzw``, without a device: the LZW streams of an image's blocks (a list of ``bytes``, in
+    the file's block order) -> its (spp, height, width) array of uint8 / 16 / 32 / 64, decoded by the library on this thread.
+    ``IoError`` names the first block whose stream is refused, and why. """
+    return lzw_image_host_packed(*_pack_streams(streams), layout, strict=True)[0]
 
 
 def comm_unique_id() -> bytes:
@@ -603,17 +663,7 @@ class Context:
         stream is refused has a status other than 0 (``INFLATE_*``) and unspecified pixels; ``strict``: it raises ``IoError``
         naming the first such block instead. """
         lay = _inflate_layout(layout)
-        n_blocks, _, _ = inflate_bound(lay)
-        buf = np.frombuffer(streams, np.uint8) if isinstance(streams, (bytes, bytearray, memoryview)) else np.ascontiguousarray(streams, np.uint8)
-        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
-        if offsets.shape != (n_blocks,) or sizes.shape != (n_blocks,):
-            raise ValueError(f'{offsets.size} offsets and {sizes.size} sizes for {n_blocks} blocks')
-        if n_blocks and ((offsets < 0).any() or (sizes < 0).any() or (offsets + sizes > buf.size).any()):
-            raise ValueError('a stream lies outside the buffer')
-        if buf.size == 0:
-            buf = np.zeros(1, np.uint8)   # (every stream is empty: a pointer all the same)
-        out = np.empty((lay.spp, lay.height, lay.width), np.dtype(f'u{lay.sample_bytes}'))
-        status = np.zeros(n_blocks, np.int32)
+        buf, offsets, sizes, out, status = _packed_blocks(streams, offsets, sizes, lay)
         rc = self._lib.hk_inflate_image(self._h, C.byref(lay), buf.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(_P(C.c_int64)),
                                         sizes.ctypes.data_as(_P(C.c_int64)), out.ctypes.data_as(C.c_void_p), lay.width,
                                         lay.height * lay.width, status.ctypes.data_as(_P(C.c_int32)))
@@ -628,13 +678,28 @@ class Context:
         """ What ``tiff.read_tiff`` takes as ``inflater``: the zlib streams of an image's blocks (a list of ``bytes``, in the
         file's block order) -> its (spp, height, width) array of uint8 / 16 / 32 / 64, inflated on the device
         (``inflate_image_packed``).  ``IoError`` names the first block whose stream is refused, and why. """
-        sizes = np.array([len(s) for s in streams], np.int64)
-        padded = (sizes + 15) // 16 * 16
-        offsets = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64) if len(sizes) else np.zeros(0, np.int64)
-        buf = np.zeros(int(padded.sum()), np.uint8)
-        for o, s in zip(offsets.tolist(), streams):
-            buf[o:o + len(s)] = np.frombuffer(s, np.uint8)
-        return self.inflate_image_packed(buf, offsets, sizes, layout, strict=True)[0]
+        return self.inflate_image_packed(*_pack_streams(streams), layout, strict=True)[0]
+
+    def lzw_image_packed(self, streams, offsets, sizes, layout, strict: bool = True):
+        """ ``inflate_image_packed`` for the LZW streams (TIFF compression 5) of an image's blocks (hk_lzw_image): the same
+        arguments and results; the statuses are ``LZW_*``. """
+        lay = _inflate_layout(layout)
+        buf, offsets, sizes, out, status = _packed_blocks(streams, offsets, sizes, lay)
+        rc = self._lib.hk_lzw_image(self._h, C.byref(lay), buf.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(_P(C.c_int64)),
+                                    sizes.ctypes.data_as(_P(C.c_int64)), out.ctypes.data_as(C.c_void_p), lay.width,
+                                    lay.height * lay.width, status.ctypes.data_as(_P(C.c_int32)))
+        if rc == HK_ERR_ARG and status.any():
+            if strict:
+                raise IoError(self._lib.hk_last_error().decode('utf-8', 'replace'))
+            return out, status
+        _check(rc)
+        return out, status
+
+    def lzw_image(self, streams, layout) -> np.ndarray:
+        """ What ``tiff.read_tiff`` takes as ``lzw``: the LZW streams of an image's blocks (a list of ``bytes``, in the file's
+        block order) -> its (spp, height, width) array of uint8 / 16 / 32 / 64, decoded on the device (``lzw_image_packed``).
+        ``IoError`` names the first block whose stream is refused, and why. """
+        return self.lzw_image_packed(*_pack_streams(streams), layout, strict=True)[0]
 
     def fit_apply(self, desc: FitDesc, src: np.ndarray, ref: np.ndarray, n_param_bands: int, want_params: bool,
                   want_corr: bool, norm_in: Optional[np.ndarray] = None, out_params: Optional[np.ndarray] = None,
@@ -1269,6 +1334,13 @@ class Context:
         _check(self._lib.hk_inflate_image_dev(self._h, C.byref(_inflate_layout(layout)), C.c_void_p(streams_dptr), C.c_void_p(offsets_dptr),
                                               C.c_void_p(sizes_dptr), C.c_void_p(work_dptr), C.c_void_p(out_dptr), stride, band_stride,
                                               C.c_void_p(status_dptr), stream))
+
+    def lzw_image_dev(self, layout, streams_dptr: int, offsets_dptr: int, sizes_dptr: int, work_dptr: int, out_dptr: int,
+                      stride: int, band_stride: int, status_dptr: int, stream: int = 0):
+        """ ``inflate_image_dev`` for device-resident LZW streams (hk_lzw_image_dev; asynchronous): the statuses are ``LZW_*``. """
+        _check(self._lib.hk_lzw_image_dev(self._h, C.byref(_inflate_layout(layout)), C.c_void_p(streams_dptr), C.c_void_p(offsets_dptr),
+                                          C.c_void_p(sizes_dptr), C.c_void_p(work_dptr), C.c_void_p(out_dptr), stride, band_stride,
+                                          C.c_void_p(status_dptr), stream))
 
     def synth_fill_dev(self, src_dptr, ref_dptr, n_bands, height, width, stride, band_stride, seed=0, nodata_variant=0,
                        stream=0):

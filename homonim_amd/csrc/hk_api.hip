@@ -2761,6 +2761,13 @@ static const char* inflate_status_text(int st) {
     return st >= 0 && st <= HK_INFLATE_ADLER ? text[st] : "unknown status";
 }
 
+static const char* lzw_status_text(int st) {
+    static const char* const text[] = {"ok", "the stream ends too soon", "old-style (pre-6.0) LZW bit order",
+                                       "the first code after a Clear is no byte", "a code beyond the table",
+                                       "end of information before the block's bytes are there"};
+    return st >= 0 && st <= HK_LZW_SHORT ? text[st] : "unknown status";
+}
+
 static hk::InflateArgs inflate_args(const hk_inflate_layout* l, const InflateShape& s, int32_t height) {
     hk::InflateArgs a;
     memset(&a, 0, sizeof(a));
@@ -2782,9 +2789,10 @@ static int check_inflate(hk_ctx* ctx, const hk_inflate_layout* layout, const voi
     return HK_OK;
 }
 
-int hk_inflate_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
-                         const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
-                         int32_t* status_dev, int32_t stream) {
+// hk_inflate_image_dev and hk_lzw_image_dev: the same call with another first kernel
+static int blocks_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
+                            const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
+                            int32_t* status_dev, int32_t stream, bool lzw) {
     InflateShape s;
     int rc = check_inflate(ctx, layout, streams_dev, offsets_dev, sizes_dev, out_dev, stride, band_stride, &s);
     if (rc) return rc;
@@ -2799,8 +2807,20 @@ int hk_inflate_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const voi
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "offsets, sizes and statuses are handed on as they are");
     a.streams = streams_dev, a.offsets = reinterpret_cast<const long long*>(offsets_dev), a.sizes = reinterpret_cast<const long long*>(sizes_dev);
     a.work = static_cast<unsigned char*>(work_dev), a.status = status_dev, a.out = out_dev, a.stride = stride, a.band_stride = band_stride;
-    HK_HIP(hk::launch_inflate_image(a, s.n_blocks, ctx->slots[stream].stream));
+    HK_HIP(lzw ? hk::launch_lzw_image(a, s.n_blocks, ctx->slots[stream].stream) : hk::launch_inflate_image(a, s.n_blocks, ctx->slots[stream].stream));
     return HK_OK;
+}
+
+int hk_inflate_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
+                         const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
+                         int32_t* status_dev, int32_t stream) {
+    return blocks_image_dev(ctx, layout, streams_dev, offsets_dev, sizes_dev, work_dev, out_dev, stride, band_stride, status_dev, stream, false);
+}
+
+int hk_lzw_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
+                     const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
+                     int32_t* status_dev, int32_t stream) {
+    return blocks_image_dev(ctx, layout, streams_dev, offsets_dev, sizes_dev, work_dev, out_dev, stride, band_stride, status_dev, stream, true);
 }
 
 // block rows per group of the host path: whole block rows of ALL planes, at most INFLATE_GROUP_BYTES of raw bytes (at least one
@@ -2809,8 +2829,9 @@ int hk_inflate_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const voi
 // first byte of the group's first stream to the last byte of its last one (a TIFF writer lays the blocks of a plane down in order).
 constexpr size_t INFLATE_GROUP_BYTES = 64u << 20;
 
-int hk_inflate_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
-                     void* out, int64_t stride, int64_t band_stride, int32_t* status) {
+// (hk_inflate_image and hk_lzw_image: the same call with another first kernel)
+static int blocks_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
+                        void* out, int64_t stride, int64_t band_stride, int32_t* status, bool lzw) {
     InflateShape s;
     int rc = check_inflate(ctx, layout, streams, offsets, sizes, out, stride, band_stride, &s);
     if (rc) return rc;
@@ -2885,7 +2906,7 @@ int hk_inflate_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* s
         a.streams = base + o_in, a.offsets = reinterpret_cast<const long long*>(base + o_off), a.sizes = reinterpret_cast<const long long*>(base + o_siz);
         a.work = reinterpret_cast<unsigned char*>(base + o_work), a.status = reinterpret_cast<int*>(base + o_st);
         a.out = base + o_out, a.stride = d_stride, a.band_stride = rows * d_stride;
-        HK_HIP(hk::launch_inflate_image(a, nb, sl.stream));
+        HK_HIP(lzw ? hk::launch_lzw_image(a, nb, sl.stream) : hk::launch_inflate_image(a, nb, sl.stream));
         if ((rc = stage_d2h(sl, g_st.data(), 0, base + o_st, 0, (size_t)nb * sizeof(int32_t), 1))) return rc;
         for (int c = 0; c < layout->spp; ++c)
             if ((rc = stage_d2h(sl, h_out + ((size_t)c * band_stride + (size_t)r0 * stride) * es, stride * es,
@@ -2901,7 +2922,42 @@ int hk_inflate_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* s
             }
     }
     if (first_bad >= 0)
-        return fail(HK_ERR_ARG, "inflate: block %lld is refused: %s (status %d)", (long long)first_bad, inflate_status_text(first_status), first_status);
+        return fail(HK_ERR_ARG, "%s: block %lld is refused: %s (status %d)", lzw ? "lzw" : "inflate", (long long)first_bad,
+                    lzw ? lzw_status_text(first_status) : inflate_status_text(first_status), first_status);
+    return HK_OK;
+}
+
+int hk_inflate_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
+                     void* out, int64_t stride, int64_t band_stride, int32_t* status) {
+    return blocks_image(ctx, layout, streams, offsets, sizes, out, stride, band_stride, status, false);
+}
+
+int hk_lzw_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
+                 void* out, int64_t stride, int64_t band_stride, int32_t* status) {
+    return blocks_image(ctx, layout, streams, offsets, sizes, out, stride, band_stride, status, true);
+}
+
+// the same image on the calling thread (hk_lzw_host.hip): no context, no device
+int hk_lzw_image_host(const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes, void* out,
+                      int64_t stride, int64_t band_stride, int32_t* status) {
+    InflateShape s;
+    const int rc = inflate_shape(layout, &s);
+    if (rc) return rc;
+    if (!streams || !offsets || !sizes || !out) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (stride < layout->width) return fail(HK_ERR_ARG, "row stride smaller than width");
+    if (band_stride < 0 || (layout->spp > 1 && band_stride < stride * (layout->height - 1) + layout->width))
+        return fail(HK_ERR_ARG, "band_stride %lld is smaller than a plane", (long long)band_stride);
+    if ((uintptr_t)out % layout->sample_bytes) return fail(HK_ERR_ARG, "out is not aligned to its samples");
+    for (int64_t b = 0; b < s.n_blocks; ++b)
+        if (offsets[b] < 0 || sizes[b] < 0) return fail(HK_ERR_ARG, "block %lld: offset %lld, size %lld", (long long)b, (long long)offsets[b], (long long)sizes[b]);
+    std::vector<uint64_t> slot((size_t)s.slot / 8 + 2);   // (8-byte aligned for every sample size; the slot is a multiple of 16)
+    hk::InflateArgs a = inflate_args(layout, s, layout->height);
+    a.streams = streams, a.offsets = reinterpret_cast<const long long*>(offsets), a.sizes = reinterpret_cast<const long long*>(sizes);
+    a.work = reinterpret_cast<unsigned char*>(slot.data()), a.status = status, a.out = out, a.stride = stride, a.band_stride = band_stride;
+    int first_status = 0;
+    const long long first_bad = hk::lzw_image_host(a, s.n_blocks, &first_status);
+    if (first_bad >= 0)
+        return fail(HK_ERR_ARG, "lzw: block %lld is refused: %s (status %d)", first_bad, lzw_status_text(first_status), first_status);
     return HK_OK;
 }
 

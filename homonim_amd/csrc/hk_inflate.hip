@@ -117,11 +117,17 @@ __global__ void __launch_bounds__(256) untile_kernel(const InflateArgs a) {
 
 hipError_t launch_inflate_image(InflateArgs a, long long n_blocks, hipStream_t stream) {
     if (n_blocks < 1 || n_blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    HK_LAUNCH(inflate_block_kernel, dim3((unsigned)n_blocks), dim3(inflate::WAVE), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_untile(a, n_blocks, stream);
+}
+
+// the second stage, behind whatever filled the slots and the statuses (hk_lzw.hip launches it too)
+hipError_t launch_untile(InflateArgs a, long long n_blocks, hipStream_t stream) {
+    if (n_blocks < 1 || n_blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
     a.vec_ok = a.cspp == 1 && ((uintptr_t)a.out % 16 == 0) && ((uintptr_t)a.work % 16 == 0) && ((a.stride * a.es) % 16 == 0) &&
                ((a.band_stride * a.es) % 16 == 0) && (((long long)a.bw * a.es) % 16 == 0);
-    HK_LAUNCH(inflate_block_kernel, dim3((unsigned)n_blocks), dim3(inflate::WAVE), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
     const int rows = a.bh < a.height ? a.bh : a.height;
     const dim3 grid((unsigned)n_blocks, (unsigned)((rows + 3) / 4 < 64 ? (rows + 3) / 4 : 64));
     switch (a.es) {

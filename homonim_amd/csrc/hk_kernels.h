@@ -305,6 +305,13 @@ struct InflateArgs {
     int vec_ok;                      // set by the launcher: rows may move as 16-byte groups
 };
 hipError_t launch_inflate_image(InflateArgs a, long long n_blocks, hipStream_t stream);
+// its second stage alone: the slots of the blocks with status 0 to the raster (untile_kernel<ES>)
+hipError_t launch_untile(InflateArgs a, long long n_blocks, hipStream_t stream);
+// The same for LZW blocks, TIFF compression 5 (hk_lzw.hip): status[b] is 0 or an HK_LZW_* code.
+hipError_t launch_lzw_image(InflateArgs a, long long n_blocks, hipStream_t stream);
+// ... and decoded on the calling thread (hk_lzw_host.hip: the host build of hk_lzw_core.h): every pointer is host memory,
+// `work` is ONE slot, `status` may be NULL.  -> the first refused block (its status in *first_status), or -1.
+long long lzw_image_host(const InflateArgs& a, long long n_blocks, int* first_status);
 
 hipError_t launch_synth_fill(float* src, float* ref, int n_bands, int height, int width, long long stride,
                              long long band_stride, unsigned long long seed, int nodata_variant, hipStream_t stream);

@@ -272,7 +272,8 @@ class RasterFuse:
                  ref_transform: Optional[Affine] = None, ref_crs: Optional[CRS] = None, inflate: str = 'host'):
         """
         ``inflate``: who inflates the DEFLATE blocks of ``src`` / ``ref`` given as GeoTIFF paths: 'host' (default) -- zlib on
-        this thread, as ever; 'device' -- ``Context.inflate_image`` of the process-wide context: the same pixels.
+        this thread, as ever; 'device' -- ``Context.inflate_image`` of the process-wide context: the same pixels.  LZW blocks go
+        to the library's host decoder (``_hk.lzw_image_host``) under 'host' and to ``Context.lzw_image`` under 'device'.
         ``transform`` / ``ref_transform``: geo-transforms of the source / reference rasters (north-up).  When they (or the
         shapes) differ, blocks are cut on the processing grid and re-sampled on the device as the reference does through
         GDAL (RefSpaceModel / SrcSpaceModel); the reference must cover the source.  ``crs`` / ``ref_crs``: their CRSs (taken
@@ -282,20 +283,20 @@ class RasterFuse:
         """
         if inflate not in ('host', 'device'):
             raise ValueError(f"`inflate` must be 'host' or 'device', not {inflate!r}")
-        inflater = None
+        inflater, lzw = None, _hk.lzw_image_host
         if inflate == 'device' and any(isinstance(x, (str, os.PathLike)) for x in (src, ref)):
-            inflater = _hk.default_context().inflate_image
+            inflater, lzw = _hk.default_context().inflate_image, _hk.default_context().lzw_image
         self._src_filename = self._ref_filename = None
         self._ref_descriptions = ()   # band descriptions of a reference opened from a file (name the parameter bands)
         if isinstance(src, (str, os.PathLike)):  # a GeoTIFF, as homonim.RasterFuse(src_filename, ref_filename, ...)
             from homonim_amd.tiff import read_tiff
             self._src_filename = os.fspath(src)
-            tif = read_tiff(src, inflater=inflater)
+            tif = read_tiff(src, inflater=inflater, lzw=lzw)
             src, src_nodata, crs, transform = tif.array, tif.nodata, tif.crs, tif.transform
         if isinstance(ref, (str, os.PathLike)):
             from homonim_amd.tiff import read_tiff
             self._ref_filename = os.fspath(ref)
-            tif = read_tiff(ref, inflater=inflater)
+            tif = read_tiff(ref, inflater=inflater, lzw=lzw)
             ref, ref_nodata, ref_transform, ref_crs = tif.array, tif.nodata, tif.transform, tif.crs
             self._ref_descriptions = tif.descriptions
         if isinstance(src, RasterArray):

@@ -81,7 +81,8 @@ class ParamStats:
                  strip_bytes: Optional[int] = None, inflate: str = 'host'):
         """ ``context``: the GPU context to reduce on (default: the process-wide one, created on first use).
         ``strip_bytes``: see ``STRIP_BYTES``.  ``inflate``: who inflates the file's DEFLATE blocks: 'host' (default) -- zlib on
-        the reading thread; 'device' -- ``Context.inflate_image`` of the same context: the same pixels. """
+        the reading thread; 'device' -- ``Context.inflate_image`` of the same context: the same pixels.  The LZW blocks of a file
+        go to the library's host decoder (``_hk.lzw_image_host``) under 'host' and to ``Context.lzw_image`` under 'device'. """
         if inflate not in ('host', 'device'):
             raise ValueError(f"`inflate` must be 'host' or 'device', not {inflate!r}")
         self._inflate = inflate
@@ -166,8 +167,10 @@ class ParamStats:
             if not self._from_file:
                 raise IoError('The parameter raster has been closed')
             from homonim_amd.tiff import read_tiff
-            inflater = self._get_context().inflate_image if getattr(self, '_inflate', 'host') == 'device' else None
-            array = read_tiff(self._param_filename, inflater=inflater).array
+            device = getattr(self, '_inflate', 'host') == 'device'
+            inflater = self._get_context().inflate_image if device else None
+            lzw = self._get_context().lzw_image if device else _hk.lzw_image_host
+            array = read_tiff(self._param_filename, inflater=inflater, lzw=lzw).array
             self._array = np.ascontiguousarray(array, dtype=np.float32)
         return self
 
@@ -281,7 +284,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     parser.add_argument('param_files', nargs='+', metavar='FILE', help='Path(s) to parameter image(s).')
     parser.add_argument('-o', '--output', metavar='FILE', default=None, help='Write results to this json file.')
     parser.add_argument('--inflate', choices=('host', 'device'), default='host',
-                        help="Who inflates the files' DEFLATE blocks: zlib on the host (default) or the GPU.")
+                        help="Who decodes the files' DEFLATE and LZW blocks: the host (default) or the GPU.")
     args = parser.parse_args(argv)
     param_stats = []
     for name in args.param_files:

@@ -3,15 +3,16 @@ Minimal GeoTIFF reader / writer for the rasters either side of the hot path (no 
 
 Covers what the reference reads and writes (all of homonim's test rasters and its own output
 profile, homonim/fuse.py:124-149): classic or BigTIFF, little / big endian, strips or tiles, planar ``separate`` or
-``contig``, uncompressed or DEFLATE (zlib) with predictor none / horizontal differencing / floating point (3), 8 / 16 / 32 /
-64-bit integer and IEEE float samples; geo-referencing from ModelPixelScale + ModelTiepoint or ModelTransformation; nodata
+``contig``, uncompressed, DEFLATE (zlib) or LZW with predictor none / horizontal differencing / floating point (3), 8 / 16 /
+32 / 64-bit integer and IEEE float samples; geo-referencing from ModelPixelScale + ModelTiepoint or ModelTransformation; nodata
 from GDAL_NODATA; EPSG code / citation from the GeoKey directory; the ``<GDALMetadata>`` items (where the reference keeps
 its FUSE_* provenance, fuse.py:193-207) and the per-band ``DESCRIPTION`` items among them (the band names of a parameter
 file, fuse.py:241-248).  The writer produces tiled, DEFLATE, band-separate files like the reference's
 default output profile -- classic or BigTIFF, with predictor 2 or 3 on request -- with internal overviews (reduced-resolution
 images chained behind the first) on request;
 ``read_tiff_overviews`` reads those back.  A rotated or sheared grid is read from, and on request written as, a
-ModelTransformation matrix.  Everything else (other compressions, palettes) raises.
+ModelTransformation matrix.  LZW is read only (``lzw_decode``, or a hook of ``read_tiff``).  Everything else (other
+compressions, palettes) raises.
 """
 import mmap
 import re
@@ -60,7 +61,7 @@ class TiffHeader(NamedTuple):
 
 class BlockLayout(NamedTuple):
     """ How the blocks (tiles or strips) of one image lie in its raster: what an ``inflater`` of ``read_tiff`` is told (the
-    fields of hk_inflate_layout, include/homonim_hk.h, in its order). """
+    fields of hk_inflate_layout, include/homonim_hk.h, in its order).  An ``lzw`` hook is told the same. """
     sample_bytes: int            # 1, 2, 4, 8; the samples are little-endian
     spp: int
     height: int
@@ -206,25 +207,27 @@ def read_tiff_header(path) -> TiffHeader:
     return TiffHeader(spp, h, w, dtype, tf, crs, _nodata_tag(t), _metadata(t), _descriptions(t, spp))
 
 
-def read_tiff(path, inflater=None) -> TiffRaster:
+def read_tiff(path, inflater=None, lzw=None) -> TiffRaster:
     """ Read the first image of a GeoTIFF into a (bands, height, width) array.  ``inflater``: a callable ``(streams, layout) ->
     array`` that takes the zlib streams of ALL blocks of a DEFLATE image (a list of ``bytes`` in the file's block order) and
     their ``BlockLayout`` and returns the image as a (spp, height, width) array of unsigned integers of the sample size, the
     predictor undone, in place of ``zlib.decompress`` block after block on this thread (e.g. ``Context.inflate_image``: this
     module itself imports no GPU code).  It is handed little-endian DEFLATE images only; anything else, and everything with
-    None, is decoded here as ever. """
+    None, is decoded here as ever.  ``lzw``: the same hook for LZW images (compression 5), under the same contract: the LZW
+    streams of all blocks of a little-endian image with predictor 1 or 2 (e.g. ``Context.lzw_image`` or ``_hk.lzw_image_host``).
+    With None, and for big-endian and predictor-3 images, the blocks go through ``lzw_decode``, which is slow. """
     with open(path, 'rb') as f:
         buf = f.read()
     bo, t, _ = _read_ifd(buf)
-    out = _decode_image(buf, bo, t, inflater)
+    out = _decode_image(buf, bo, t, inflater, lzw)
     tf, crs = _geo(t, out.shape[1])
     return TiffRaster(out, tf, crs, _nodata_tag(t), _metadata(t), _descriptions(t, out.shape[0]))
 
 
-def read_tiff_overviews(path, inflater=None) -> List[np.ndarray]:
+def read_tiff_overviews(path, inflater=None, lzw=None) -> List[np.ndarray]:
     """ The internal overviews of a GeoTIFF: the reduced-resolution images (NewSubfileType bit 0) chained behind the first, in
-    file order, each as a (bands, height, width) array.  ``[]`` for a file without any.  ``inflater``: as in ``read_tiff``, called
-    once per level. """
+    file order, each as a (bands, height, width) array.  ``[]`` for a file without any.  ``inflater``, ``lzw``: as in ``read_tiff``,
+    called once per level. """
     with open(path, 'rb') as f:
         buf = f.read()
     bo, t, nxt = _read_ifd(buf)
@@ -233,12 +236,66 @@ def read_tiff_overviews(path, inflater=None) -> List[np.ndarray]:
         seen.add(nxt)
         bo, t, following = _read_ifd(buf, nxt)
         if t.get(T_SUBFILE, (0,))[0] & 1:
-            out.append(_decode_image(buf, bo, t, inflater))
+            out.append(_decode_image(buf, bo, t, inflater, lzw))
         nxt = following
     return out
 
 
-def _decode_image(buf, bo, t, inflater=None) -> np.ndarray:
+# why ``lzw_decode`` refuses a stream: the texts of HK_LZW_* (include/homonim_hk.h), by status
+LZW_REASONS = ('ok', 'the stream ends too soon', 'old-style (pre-6.0) LZW bit order', 'the first code after a Clear is no byte',
+               'a code beyond the table', "end of information before the block's bytes are there")
+
+
+def lzw_decode(stream, raw_size: int) -> bytes:
+    """ The ``raw_size`` bytes of one TIFF LZW stream (compression 5), in plain Python: SLOW (well below 1 MB/s) -- the product
+    reads whole rasters through the library (``_hk.lzw_image_host``, ``Context.lzw_image``); this one reads a file where there
+    is no library, and is what the tests hold those two to.  Codes of 9..12 bits, most significant bit first; 256 Clear, 257 end
+    of information, entries from 258; the width grows once the next free entry is 2^width - 1 (libtiff's early change); a full
+    table adds nothing more; the stream starts as if behind a Clear; decoding ends with the raw size, a last string is cut.
+    ``IoError`` with one of ``LZW_REASONS`` otherwise. """
+    data = bytes(stream)
+    if not data:
+        raise IoError(f'LZW: {LZW_REASONS[1]}')
+    if len(data) >= 2 and data[0] == 0 and data[1] & 1:
+        raise IoError(f'LZW: {LZW_REASONS[2]}')
+    table = [bytes([i]) for i in range(256)] + [b'', b'']
+    out = bytearray()
+    acc = nacc = pos = used = 0
+    width, prev, limit = 9, None, 8 * len(data)
+    while len(out) < raw_size:
+        while nacc < width:   # (bits past the end are zero bits, and taking one is refused below)
+            acc = (acc << 8) | (data[pos] if pos < len(data) else 0)
+            pos, nacc = pos + 1, nacc + 8
+        nacc, used = nacc - width, used + width
+        if used > limit:
+            raise IoError(f'LZW: {LZW_REASONS[1]}')
+        c = acc >> nacc
+        acc &= (1 << nacc) - 1
+        if c == 256:
+            del table[258:]
+            width, prev = 9, None
+            continue
+        if c == 257:
+            raise IoError(f'LZW: {LZW_REASONS[5]}')
+        if prev is None:
+            if c > 255:
+                raise IoError(f'LZW: {LZW_REASONS[3]}')
+            s = table[c]
+        else:
+            n = len(table)
+            if c > n:
+                raise IoError(f'LZW: {LZW_REASONS[4]}')
+            s = table[c] if c < n else prev + prev[:1]
+            if n < 4096:
+                table.append(prev + s[:1])
+                if n + 1 == (1 << width) - 1 and width < 12:
+                    width += 1
+        out += s
+        prev = s
+    return bytes(out[:raw_size])
+
+
+def _decode_image(buf, bo, t, inflater=None, lzw=None) -> np.ndarray:
     """ The pixels of the image a directory describes, (bands, height, width) in native byte order """
     w, h = t[T_WIDTH][0], t[T_HEIGHT][0]
     spp = t.get(T_SPP, (1,))[0]
@@ -248,8 +305,8 @@ def _decode_image(buf, bo, t, inflater=None) -> np.ndarray:
         raise IoError(f'unsupported sample layout: bits {bits}, format {fmt}')
     dtype = np.dtype(bo + _SAMPLE_DTYPES[(fmt[0], bits[0])])
     compression = t.get(T_COMPRESSION, (1,))[0]
-    if compression not in (1, 8, 32946):
-        raise IoError(f'unsupported TIFF compression {compression} (none and DEFLATE are)')
+    if compression not in (1, 5, 8, 32946):
+        raise IoError(f'unsupported TIFF compression {compression} (none, LZW and DEFLATE are)')
     predictor = t.get(T_PREDICTOR, (1,))[0]
     if predictor not in (1, 2, 3) or (predictor == 2 and dtype.kind == 'f') or (predictor == 3 and dtype.kind != 'f'):
         raise IoError(f'unsupported TIFF predictor {predictor} for samples of {dtype}')
@@ -263,6 +320,8 @@ def _decode_image(buf, bo, t, inflater=None) -> np.ndarray:
     chunk_spp = 1 if planar == 2 else spp
     tiled = T_TILE_OFFSETS in t
     # (a floating-point predictor is undone here, hook or not: the hook's contract knows predictors 1 and 2)
+    if compression == 5:
+        inflater = lzw
     if inflater is not None and compression != 1 and bo == '<' and predictor != 3:
         if len(offs) != len(cnts) or len(offs) != (spp if planar == 2 else 1) * across * down:
             raise IoError(f'{len(offs)} block offsets and {len(cnts)} byte counts for {(spp if planar == 2 else 1) * across * down} blocks')
@@ -277,7 +336,12 @@ def _decode_image(buf, bo, t, inflater=None) -> np.ndarray:
         by, bx = divmod(rem, across)
         rows = bh if tiled else min(bh, h - by * bh)
         raw = buf[off:off + cnt]
-        if compression != 1:
+        if compression == 5:
+            try:
+                raw = lzw_decode(raw, rows * bw * chunk_spp * dtype.itemsize)
+            except IoError as ex:
+                raise IoError(f'block {idx} is refused: {ex}') from None
+        elif compression != 1:
             raw = zlib.decompress(raw)
         if predictor == 3:
             block = _unpredict_float(raw, rows, bw, chunk_spp, dtype.itemsize)

@@ -214,6 +214,29 @@ int hk_inflate_bound(const hk_inflate_layout* layout, int64_t* n_blocks, int64_t
 int hk_inflate_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
                      void* out, int64_t stride, int64_t band_stride, int32_t* status /* n_blocks or NULL */);
 
+/* LZW on the device and on the host: the LZW blocks (tiles or strips) of one GeoTIFF image, compression 5, decoded and put in their
+ * place like the DEFLATE ones above -- same layout struct, same hk_inflate_bound, same block order, slots and staging groups
+ * (HK_INFLATE_GROUP_KB), same error convention.  A block's stream is TIFF 6.0 LZW: codes of 9 to 12 bits, most significant bit
+ * first; 0..255 bytes, 256 Clear, 257 end of information, entries from 258; the width grows once the next free entry is
+ * 2^width - 1 (libtiff's early change); a full table adds nothing more; the stream starts as if behind a Clear.  Decoding ends
+ * with the block's raw size: a last string is cut and nothing behind it is looked at (a missing end code is fine).  Every block
+ * gets a status, with the same meaning in all three calls.  Added to version 12 without a new version: look the symbols up. */
+enum {
+    HK_LZW_OK = 0,
+    HK_LZW_TRUNCATED = 1,   /* a bit past the stream's end was needed (an empty or missing stream too) */
+    HK_LZW_OLD_STYLE = 2,   /* the pre-6.0 bit order (libtiff's test: first byte 0, bit 0 of the second set): not decoded */
+    HK_LZW_BAD_FIRST = 3,   /* the first code after a Clear is above 257 */
+    HK_LZW_BAD_CODE = 4,    /* a code above the next free entry */
+    HK_LZW_SHORT = 5        /* end of information before the block's raw size */
+};
+/* hk_inflate_image for LZW streams. */
+int hk_lzw_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
+                 void* out, int64_t stride, int64_t band_stride, int32_t* status /* n_blocks or NULL */);
+/* The same image from the same arguments decoded on the calling thread: the decoder of the kernel compiled for the host, then crop,
+ * de-interleaving and predictor 2 in plain C++.  No context, no device (like hk_inflate_bound); `out` aligned to its samples. */
+int hk_lzw_image_host(const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes, void* out,
+                      int64_t stride, int64_t band_stride, int32_t* status /* n_blocks or NULL */);
+
 /* KernelModel.fit (homonim/kernel_model.py:411-440 -> _fit_gain :231-274, _fit_gain_blk_offset :276-303,
  * _fit_gain_offset :305-373, _r2_array :142-214).
  *   params_out : n_param_bands x height x width float32, band 0 gain, 1 offset, 2 R2 (iff n_param_bands == 3;
@@ -631,6 +654,10 @@ int hk_deflate_tiles_pred_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype
 int hk_inflate_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
                          const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
                          int32_t* status_dev, int32_t stream);
+/* hk_inflate_image_dev for LZW streams (hk_lzw_image): the statuses are HK_LZW_*, a stream that is not there HK_LZW_TRUNCATED. */
+int hk_lzw_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
+                     const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
+                     int32_t* status_dev, int32_t stream);
 
 /* HIP events on the pooled streams, so callers time exactly the stream the kernels run on. */
 int hk_event_create(hk_ctx* ctx, hk_event** ev);
