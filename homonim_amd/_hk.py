@@ -302,6 +302,21 @@ def _packed_blocks(streams, offsets, sizes, lay):
     return buf, offsets, sizes, out, np.zeros(n_blocks, np.int32)
 
 
+def _blocks_image(fn, handle, streams, offsets, sizes, layout, strict):
+    """ the block-image entry point ``fn`` of the context ``handle`` (None: the host decoder) -> (array, status per block) """
+    lay = _inflate_layout(layout)
+    buf, offsets, sizes, out, status = _packed_blocks(streams, offsets, sizes, lay)
+    rc = fn(*(() if handle is None else (handle,)), C.byref(lay), buf.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(_P(C.c_int64)),
+            sizes.ctypes.data_as(_P(C.c_int64)), out.ctypes.data_as(C.c_void_p), lay.width, lay.height * lay.width,
+            status.ctypes.data_as(_P(C.c_int32)))
+    if rc == HK_ERR_ARG and status.any():
+        if strict:
+            raise IoError(load_library().hk_last_error().decode('utf-8', 'replace'))
+        return out, status
+    _check(rc)
+    return out, status
+
+
 def _pack_streams(streams):
     """ a list of ``bytes`` as one buffer, every stream at a multiple of 16: -> (buffer, offsets, sizes) """
     sizes = np.array([len(s) for s in streams], np.int64)
@@ -316,18 +331,7 @@ def _pack_streams(streams):
 def lzw_image_host_packed(streams, offsets, sizes, layout, strict: bool = True):
     """ ``Context.lzw_image_packed`` on the calling thread (hk_lzw_image_host: the kernel's decoder compiled for the host; no
     context, no device): the same arguments, the same (array, status per block), the same ``IoError``. """
-    lay = _inflate_layout(layout)
-    lib = load_library()
-    buf, offsets, sizes, out, status = _packed_blocks(streams, offsets, sizes, lay)
-    rc = lib.hk_lzw_image_host(C.byref(lay), buf.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(_P(C.c_int64)),
-                               sizes.ctypes.data_as(_P(C.c_int64)), out.ctypes.data_as(C.c_void_p), lay.width, lay.height * lay.width,
-                               status.ctypes.data_as(_P(C.c_int32)))
-    if rc == HK_ERR_ARG and status.any():
-        if strict:
-            raise IoError(lib.hk_last_error().decode('utf-8', 'replace'))
-        return out, status
-    _check(rc)
-    return out, status
+    return _blocks_image(load_library().hk_lzw_image_host, None, streams, offsets, sizes, layout, strict)
 
 
 def lzw_image_host(streams, layout) -> np.ndarray:
@@ -335,6 +339,18 @@ def lzw_image_host(streams, layout) -> np.ndarray:
     the file's block order) -> its (spp, height, width) array of uint8 / 16 / 32 / 64, decoded by the library on this thread.
     ``IoError`` names the first block whose stream is refused, and why. """
     return lzw_image_host_packed(*_pack_streams(streams), layout, strict=True)[0]
+
+
+def block_decoders(inflate, get_context=None):
+    """ The ``inflate`` option of ``RasterFuse`` / ``ParamStats`` -> (inflater, lzw) as ``tiff.read_tiff`` takes them: 'host' -- zlib
+    on the reading thread (no inflater) and the library's host LZW decoder; 'device' -- ``inflate_image`` / ``lzw_image`` of
+    ``get_context()``, which is called only then (None: the option is only checked). """
+    if inflate not in ('host', 'device'):
+        raise ValueError(f"`inflate` must be 'host' or 'device', not {inflate!r}")
+    if inflate == 'device' and get_context is not None:
+        ctx = get_context()
+        return ctx.inflate_image, ctx.lzw_image
+    return None, lzw_image_host
 
 
 def comm_unique_id() -> bytes:
@@ -488,6 +504,14 @@ def _as_2d_native(a: np.ndarray, name: str) -> np.ndarray:
     return a
 
 
+def _unit_column_stride(arr: np.ndarray):
+    """ a (bands, h, w) raster as the strided entry points take it (unit column stride), copied if it is not: -> (array, itemsize) """
+    it = arr.dtype.itemsize
+    if arr.strides[2] != it or arr.strides[1] % it or arr.strides[1] < arr.shape[2] * it or arr.strides[0] % it or arr.strides[0] < 0:
+        arr = np.ascontiguousarray(arr)
+    return arr, it
+
+
 def _ptr(a: np.ndarray, typ=_f32p):
     return a.ctypes.data_as(typ)
 
@@ -592,10 +616,7 @@ class Context:
             raise ValueError('`array` must be a non-empty 2-D or 3-D raster')
         if arr.dtype.name not in DTYPE_CODES:
             raise ValueError(f"unsupported dtype '{arr.dtype}'")
-        it = arr.dtype.itemsize
-        if (arr.strides[2] != it or arr.strides[1] % it or arr.strides[1] < arr.shape[2] * it or arr.strides[0] % it
-                or arr.strides[0] < 0):
-            arr = np.ascontiguousarray(arr)
+        arr, it = _unit_column_stride(arr)
         nb, h, w = arr.shape
         n_levels = int(n_levels)
         if n_levels < 1:
@@ -626,10 +647,7 @@ class Context:
             raise ValueError(f"unsupported dtype '{arr.dtype}'")
         if arr.dtype.byteorder == '>':
             arr = arr.astype(arr.dtype.newbyteorder('<'))
-        it = arr.dtype.itemsize
-        if (arr.strides[2] != it or arr.strides[1] % it or arr.strides[1] < arr.shape[2] * it or arr.strides[0] % it
-                or arr.strides[0] < 0):
-            arr = np.ascontiguousarray(arr)
+        arr, it = _unit_column_stride(arr)
         nb, h, w = arr.shape
         code, tile = DTYPE_CODES[arr.dtype.name], int(tile)
         n_tiles, cap = C.c_int64(), C.c_int64()
@@ -662,17 +680,7 @@ class Context:
         bytes or a uint8 array).  -> (array (spp, height, width) of uint8 / 16 / 32 / 64, int32 status per block).  A block whose
         stream is refused has a status other than 0 (``INFLATE_*``) and unspecified pixels; ``strict``: it raises ``IoError``
         naming the first such block instead. """
-        lay = _inflate_layout(layout)
-        buf, offsets, sizes, out, status = _packed_blocks(streams, offsets, sizes, lay)
-        rc = self._lib.hk_inflate_image(self._h, C.byref(lay), buf.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(_P(C.c_int64)),
-                                        sizes.ctypes.data_as(_P(C.c_int64)), out.ctypes.data_as(C.c_void_p), lay.width,
-                                        lay.height * lay.width, status.ctypes.data_as(_P(C.c_int32)))
-        if rc == HK_ERR_ARG and status.any():
-            if strict:
-                raise IoError(self._lib.hk_last_error().decode('utf-8', 'replace'))
-            return out, status
-        _check(rc)
-        return out, status
+        return _blocks_image(self._lib.hk_inflate_image, self._h, streams, offsets, sizes, layout, strict)
 
     def inflate_image(self, streams, layout) -> np.ndarray:
         """ What ``tiff.read_tiff`` takes as ``inflater``: the zlib streams of an image's blocks (a list of ``bytes``, in the
@@ -683,17 +691,7 @@ class Context:
     def lzw_image_packed(self, streams, offsets, sizes, layout, strict: bool = True):
         """ ``inflate_image_packed`` for the LZW streams (TIFF compression 5) of an image's blocks (hk_lzw_image): the same
         arguments and results; the statuses are ``LZW_*``. """
-        lay = _inflate_layout(layout)
-        buf, offsets, sizes, out, status = _packed_blocks(streams, offsets, sizes, lay)
-        rc = self._lib.hk_lzw_image(self._h, C.byref(lay), buf.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(_P(C.c_int64)),
-                                    sizes.ctypes.data_as(_P(C.c_int64)), out.ctypes.data_as(C.c_void_p), lay.width,
-                                    lay.height * lay.width, status.ctypes.data_as(_P(C.c_int32)))
-        if rc == HK_ERR_ARG and status.any():
-            if strict:
-                raise IoError(self._lib.hk_last_error().decode('utf-8', 'replace'))
-            return out, status
-        _check(rc)
-        return out, status
+        return _blocks_image(self._lib.hk_lzw_image, self._h, streams, offsets, sizes, layout, strict)
 
     def lzw_image(self, streams, layout) -> np.ndarray:
         """ What ``tiff.read_tiff`` takes as ``lzw``: the LZW streams of an image's blocks (a list of ``bytes``, in the file's

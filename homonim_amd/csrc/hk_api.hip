@@ -298,6 +298,7 @@ struct Slot {
 };
 
 constexpr int64_t ROW_ALIGN = 64;  // device rows padded to 64 elements (256 B)
+int64_t row_align(int64_t w) { return (w + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN; }
 
 // The launch switches of the environment (README "Environment switches"), read once per context by hk_ctx_create.
 struct LaunchPolicy {
@@ -470,6 +471,33 @@ struct SlabLayout {
         return off;
     }
 };
+
+// How a host-pointer call opens: a leased slot whose staging slab holds `bytes` (rc says whether it does), and the buffers of
+// the call's layout inside it.
+struct HostCall {
+    SlotLease lease;
+    Slot& sl;
+    const int rc;
+    HostCall(hk_ctx* ctx, size_t bytes) : lease(ctx), sl(lease.slot()), rc(ensure_dev(sl, bytes)) {}
+    template <class T = char> T* at(size_t off) const { return reinterpret_cast<T*>(static_cast<char*>(sl.dev) + off); }
+};
+
+// refusals that many entry points share
+int null_arg() { return fail(HK_ERR_ARG, "NULL pointer argument"); }
+int check_stream(const hk_ctx* ctx, int stream) {
+    return (stream < 0 || stream >= (int)ctx->slots.size()) ? fail(HK_ERR_ARG, "bad stream index") : HK_OK;
+}
+int check_strides(int64_t stride_a, int64_t width_a, int64_t stride_b = 0, int64_t width_b = 0) {
+    return (stride_a < width_a || stride_b < width_b) ? fail(HK_ERR_ARG, "row stride smaller than width") : HK_OK;
+}
+int check_band_strides(int64_t a, int64_t b = 0) { return (a < 0 || b < 0) ? fail(HK_ERR_ARG, "band_stride is negative") : HK_OK; }
+int check_nodata_mode(int32_t mode, int32_t last = HK_NODATA_VALUE) {  // (`last` = 3 where the coverage-fraction mode is legal)
+    return (mode < 0 || mode > last) ? fail(HK_ERR_ARG, "bad nodata mode %d", mode) : HK_OK;
+}
+int check_nodata_modes(int32_t src_mode, int32_t ref_mode) {
+    const int rc = check_nodata_mode(src_mode);
+    return rc ? rc : check_nodata_mode(ref_mode);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Host staging.  BASELINE.json north_star: "blocks stream ... into pinned host buffers and hipMemcpyAsync to HBM".  The HIP
@@ -778,9 +806,7 @@ int validate_desc(const hk_fit_desc* d) {
         return fail(HK_ERR_ARG, "`kernel_shape` area should contain at least 2 elements for the gain-offset model.");
     if (d->kh > 255) return fail(HK_ERR_UNSUPPORTED, "kernel height %d > 255 not supported", d->kh);
     if (hk::overlap_lanes_for(d->kw / 2) > 24) return fail(HK_ERR_UNSUPPORTED, "kernel width %d too large", d->kw);
-    for (int m : {d->src_nodata_mode, d->ref_nodata_mode})
-        if (m < 0 || m > 2) return fail(HK_ERR_ARG, "bad nodata mode %d", m);
-    return HK_OK;
+    return check_nodata_modes(d->src_nodata_mode, d->ref_nodata_mode);
 }
 
 // RasterArray._convert_array_dtype refuses an output nodata that does not survive the cast to the output dtype
@@ -1190,6 +1216,114 @@ int fit_on_device(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, const double* 
     return fit_finish(ctx, sl, desc, p, *sl.fail_host, &requeued);
 }
 
+// What hk_io_desc (nullable: float32 everywhere) and the model say about a host-pointer fit's inputs and outputs
+struct FitIo {
+    int sdt = 0, rdt = 0, odt = 0, out_has_nodata = 0;
+    double out_nodata = 0;
+    bool out_cast = false, r2 = false;  // out_cast: the corrected plane goes through cast_out (another dtype, or an output nodata)
+};
+int check_fit_io(const hk_fit_desc* desc, const hk_io_desc* io, const float* params_out, int32_t n_param_bands, FitIo* f) {
+    if (io) f->sdt = io->src_dtype, f->rdt = io->ref_dtype, f->odt = io->out_dtype;
+    if (!hk::dtype_size(f->sdt) || !hk::dtype_size(f->rdt) || !hk::dtype_size(f->odt)) return fail(HK_ERR_ARG, "unknown dtype");
+    if (io) {
+        const int rc = validate_out_nodata(f->odt, io->out_has_nodata, io->out_nodata);
+        if (rc) return rc;
+        f->out_cast = f->odt != 0 || io->out_has_nodata;
+        f->out_has_nodata = io->out_has_nodata, f->out_nodata = io->out_nodata;
+    }
+    f->r2 = needs_r2(desc);
+    if (params_out && n_param_bands != (f->r2 ? 3 : 2))
+        return fail(HK_ERR_ARG, "n_param_bands must be %d for this model configuration", f->r2 ? 3 : 2);
+    return HK_OK;
+}
+
+// the whole block of `rows` x `cols`, written packed
+hk_out_window whole_block(int32_t rows, int32_t cols) { return {cols, (int64_t)rows * cols, 0, 0, rows, cols, cols}; }
+
+// How a host-pointer fit hands its results back.  The parameter planes (nullable params_out; d_par_band elements apart on the
+// device, rows d_par_stride apart), their window `pw` into the caller's planes; the corrected plane of height x width (nullable
+// corr_out; through d_raw and the cast where the output has one), its window `cw`; the r2-mask failure counter behind them
+// (nullable d_fail) into the slot's pinned word.  A window's param_stride is the row stride of params_out.
+int stage_fit_results(Slot& sl, const FitIo& f, float* params_out, int32_t n_param_bands, const float* d_par, int64_t d_par_stride,
+                      int64_t d_par_band, const hk_out_window& pw, void* corr_out, const float* d_corr, void* d_raw, int64_t d_stride,
+                      int32_t height, int32_t width, const hk_out_window& cw, const unsigned long long* d_fail) {
+    int rc;
+    if (params_out)
+        for (int b = 0; b < n_param_bands; ++b)
+            if ((rc = stage_d2h(sl, params_out + (size_t)b * pw.band_stride, pw.param_stride * sizeof(float),
+                                d_par + (size_t)b * d_par_band + (size_t)pw.row0 * d_par_stride + pw.col0, d_par_stride * sizeof(float),
+                                (size_t)pw.cols * sizeof(float), pw.rows)))
+                return rc;
+    if (corr_out) {
+        const size_t es = hk::dtype_size(f.odt);  // (4 without a cast: the output is float32 then)
+        const char* d_out = reinterpret_cast<const char*>(d_corr);
+        if (f.out_cast) {
+            HK_HIP(hk::launch_cast_out(f.odt, d_corr, d_stride, d_raw, d_stride, height, width, f.out_has_nodata, f.out_nodata, sl.stream));
+            d_out = static_cast<const char*>(d_raw);
+        }
+        if ((rc = stage_d2h(sl, corr_out, cw.stride * es, d_out + ((size_t)cw.row0 * d_stride + cw.col0) * es, d_stride * es,
+                            (size_t)cw.cols * es, cw.rows)))
+            return rc;
+    }
+    if (d_fail) HK_HIP(hipMemcpyAsync(sl.fail_host, d_fail, sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
+    return HK_OK;
+}
+
+// mask_partial counts the valid pixels of a (kh+2) x (kw+2) window in an unsigned short (hk_mask.hip)
+int check_mask_kernel(int kh, int kw) {
+    return (kh + 2) * (kw + 2) > 65535 ? fail(HK_ERR_UNSUPPORTED, "kernel too large for mask_partial") : HK_OK;
+}
+
+// What hk_refspace_fit_apply and hk_srcspace_fit_apply ask alike of a source block and a reference block on another grid.
+// (The mask_partial refusal cannot be reached today: validate_desc keeps kh <= 255 and kw <= 193, 257 * 195 counts fit.)
+template <class Space>
+int check_two_grids(const hk_ctx* ctx, const hk_fit_desc* desc, const Space* space, const void* src, int64_t src_stride,
+                    int32_t src_height, int32_t src_width, const void* ref, int64_t ref_stride, int32_t ref_height, int32_t ref_width,
+                    const void* corr_out) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    int rc = validate_desc(desc);
+    if (rc) return rc;
+    if (!space || !src || !ref || !corr_out) return null_arg();
+    if (src_height < 1 || src_width < 1 || ref_height < 1 || ref_width < 1) return fail(HK_ERR_ARG, "empty raster");
+    if ((rc = check_strides(src_stride, src_width, ref_stride, ref_width))) return rc;
+    if (src_height > 65535 || ref_height > 65535) return fail(HK_ERR_UNSUPPORTED, "block taller than 65535 rows");
+    return space->mask_partial ? check_mask_kernel(desc->kh, desc->kw) : HK_OK;
+}
+
+// `n_bands` planes of sh x sw re-sampled into planes of dh x dw (strides in elements)
+hk::ResamplePlanes resample_planes(const float* src, int sh, int sw, int64_t src_stride, int64_t src_band_stride, float* dst, int dh,
+                                   int dw, int64_t dst_stride, int64_t dst_band_stride, int n_bands, int nd_mode, float nodata,
+                                   float dst_fill) {
+    return {src, dst, src_stride, src_band_stride, dst_stride, dst_band_stride, sh, sw, dh, dw, n_bands, nd_mode, nodata, dst_fill};
+}
+
+// The host form of a re-projection keeps its bands packed in the slab: the source at 0, the destination behind it
+struct PackedBands {
+    size_t sbytes, o_dst, dbytes;
+};
+PackedBands packed_bands(int n_bands, int sh, int sw, int dh, int dw) {
+    const size_t sbytes = (size_t)n_bands * sh * sw * 4, dbytes = (size_t)n_bands * dh * dw * 4;
+    return {sbytes, (sbytes + 255) / 256 * 256, dbytes};
+}
+
+// hk_reproject and hk_reproject_dev ask the same of a re-projection between two axis-aligned grids of one CRS; the band count is
+// gridDim.z of the launch.  `host_form`: hk_reproject's wording for a resampling that is not built.
+int check_reproject(const hk_ctx* ctx, const float* src, int32_t n_bands, int32_t src_height, int32_t src_width, int32_t src_nodata_mode,
+                    double kx, double ky, int32_t resampling, const float* dst, int32_t dst_height, int32_t dst_width, bool host_form) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    if (!src || !dst) return null_arg();
+    if (n_bands < 1 || src_height < 1 || src_width < 1 || dst_height < 1 || dst_width < 1)
+        return fail(HK_ERR_ARG, "empty raster");
+    if (n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", n_bands);
+    if (!(kx > 0.0) || !(ky > 0.0)) return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
+    if (!resampling_built(resampling))
+        return fail(HK_ERR_UNSUPPORTED, host_form ? "resampling %d is not a warp method (GRA_* codes 0..6 and 8..14 are built; 7 = gauss is "
+                                                    "an overview-only method in GDAL / rasterio as well)"
+                                                  : "resampling %d is not a warp method", resampling);
+    if (dst_height > 65535) return fail(HK_ERR_UNSUPPORTED, "destination taller than 65535 rows");
+    return check_nodata_mode(src_nodata_mode);
+}
+
 // The whole host-pointer path: stage in (+ typed -> float32), (norm), fused kernel, (float32 -> typed) stage out.
 // `corr_out` / `params_out` nullable; `io` nullable (float32 everywhere); `ow` nullable: window of the block that is
 // written to corr_out / params_out and their row / plane strides (hk_out_window), else the whole block, packed.
@@ -1202,73 +1336,53 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
     if (rc) return rc;
     if (!src || !ref) return fail(HK_ERR_ARG, "src/ref is NULL");
     if (height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d", height, width);
-    if (src_stride < width || ref_stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
-    const int sdt = io ? io->src_dtype : 0, rdt = io ? io->ref_dtype : 0, odt = io ? io->out_dtype : 0;
-    if (!hk::dtype_size(sdt) || !hk::dtype_size(rdt) || !hk::dtype_size(odt)) return fail(HK_ERR_ARG, "unknown dtype");
-    if (io && (rc = validate_out_nodata(odt, io->out_has_nodata, io->out_nodata))) return rc;
-    const bool out_cast = io && (odt != 0 || io->out_has_nodata);
-    const bool r2 = needs_r2(desc);
-    if (!norm_only) {
-        if (params_out && n_param_bands != (r2 ? 3 : 2))
-            return fail(HK_ERR_ARG, "n_param_bands must be %d for this model configuration", r2 ? 3 : 2);
-        if (!params_out && !corr_out) return fail(HK_ERR_ARG, "nothing to compute: params_out and corr_out are NULL");
-    }
-    // output window (defaults: the whole block, written packed)
-    int wr0 = 0, wc0 = 0, wrows = height, wcols = width;
-    int64_t out_stride = width, par_stride = width, out_band_stride = (int64_t)height * width;
+    if ((rc = check_strides(src_stride, width, ref_stride, width))) return rc;
+    FitIo f;
+    if ((rc = check_fit_io(desc, io, params_out, n_param_bands, &f))) return rc;
+    if (!norm_only && !params_out && !corr_out) return fail(HK_ERR_ARG, "nothing to compute: params_out and corr_out are NULL");
+    // output window (defaults: the whole block, written packed); param_stride is resolved to the row stride of params_out
+    hk_out_window win = ow ? *ow : whole_block(height, width);
     if (ow) {
-        wr0 = ow->row0, wc0 = ow->col0, wrows = ow->rows, wcols = ow->cols;
-        out_stride = ow->stride, out_band_stride = ow->band_stride;
-        par_stride = ow->param_stride > 0 ? ow->param_stride : ow->stride;
-        if (wr0 < 0 || wc0 < 0 || wrows < 1 || wcols < 1 || wr0 + wrows > height || wc0 + wcols > width)
+        if (win.param_stride <= 0) win.param_stride = win.stride;
+        if (win.row0 < 0 || win.col0 < 0 || win.rows < 1 || win.cols < 1 || win.row0 + win.rows > height || win.col0 + win.cols > width)
             return fail(HK_ERR_ARG, "output window outside the block");
-        if ((corr_out && out_stride < wcols) || (params_out && par_stride < wcols))
+        if ((corr_out && win.stride < win.cols) || (params_out && win.param_stride < win.cols))
             return fail(HK_ERR_ARG, "output row stride smaller than the window");
-        if (params_out && n_param_bands > 1 && out_band_stride < (int64_t)(wrows - 1) * par_stride + wcols)
+        if (params_out && n_param_bands > 1 && win.band_stride < (int64_t)(win.rows - 1) * win.param_stride + win.cols)
             return fail(HK_ERR_ARG, "output band stride smaller than a plane of the window");
     }
     HK_ENTER(ctx);
 
-    const int64_t stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    const int64_t stride = row_align(width);
     const size_t plane = (size_t)stride * height * sizeof(float);
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
     const bool want_norm = blk || norm_only;
+    const bool want_par = !norm_only && params_out, want_corr = !norm_only && corr_out;
 
     SlabLayout L;
     const size_t o_src = L.take(plane), o_ref = L.take(plane);
-    size_t o_gain = 0, o_off = 0, o_r2 = 0, o_corr = 0, o_raw_s = 0, o_raw_r = 0, o_raw_o = 0;
-    if (!norm_only) {
-        if (params_out) {
-            o_gain = L.take(plane), o_off = L.take(plane);
-            if (n_param_bands == 3) o_r2 = L.take(plane);
-        }
-        if (corr_out) o_corr = L.take(plane);
-        if (corr_out && out_cast) o_raw_o = L.take((size_t)stride * height * hk::dtype_size(odt));
-    }
-    if (sdt) o_raw_s = L.take((size_t)stride * height * hk::dtype_size(sdt));
-    if (rdt) o_raw_r = L.take((size_t)stride * height * hk::dtype_size(rdt));
+    const size_t o_gain = want_par ? L.take(plane) : 0, o_off = want_par ? L.take(plane) : 0;
+    const size_t o_r2 = (want_par && n_param_bands == 3) ? L.take(plane) : 0;
+    const size_t o_corr = want_corr ? L.take(plane) : 0;
+    const size_t o_raw_o = (want_corr && f.out_cast) ? L.take((size_t)stride * height * hk::dtype_size(f.odt)) : 0;
+    const size_t o_raw_s = f.sdt ? L.take((size_t)stride * height * hk::dtype_size(f.sdt)) : 0;
+    const size_t o_raw_r = f.rdt ? L.take((size_t)stride * height * hk::dtype_size(f.rdt)) : 0;
     const size_t o_aux = L.take(256);
     const size_t o_ws = want_norm ? L.take(hk::norm_workspace_bytes(1, height, width)) : 0;
 
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    rc = ensure_dev(sl, L.total);
-    if (rc) return rc;
-    char* base = static_cast<char*>(sl.dev);
-    float* d_src = reinterpret_cast<float*>(base + o_src);
-    float* d_ref = reinterpret_cast<float*>(base + o_ref);
-    float* d_gain = (!norm_only && params_out) ? reinterpret_cast<float*>(base + o_gain) : nullptr;
-    float* d_off = (!norm_only && params_out) ? reinterpret_cast<float*>(base + o_off) : nullptr;
-    float* d_r2 = (!norm_only && params_out && n_param_bands == 3) ? reinterpret_cast<float*>(base + o_r2) : nullptr;
-    float* d_corr = (!norm_only && corr_out) ? reinterpret_cast<float*>(base + o_corr) : nullptr;
-    double* d_norm = reinterpret_cast<double*>(base + o_aux);  // 2 doubles
-    unsigned long long* d_fail = reinterpret_cast<unsigned long long*>(base + o_aux + 64);
-    void* d_ws = base + o_ws;
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
+    Slot& sl = hc.sl;
+    float *d_src = hc.at<float>(o_src), *d_ref = hc.at<float>(o_ref);
+    float *d_gain = want_par ? hc.at<float>(o_gain) : nullptr, *d_off = want_par ? hc.at<float>(o_off) : nullptr;
+    float* d_r2 = (want_par && n_param_bands == 3) ? hc.at<float>(o_r2) : nullptr;
+    float* d_corr = want_corr ? hc.at<float>(o_corr) : nullptr;
+    double* d_norm = hc.at<double>(o_aux);  // 2 doubles
+    unsigned long long* d_fail = hc.at<unsigned long long>(o_aux + 64);
+    void* d_ws = hc.at(o_ws);
 
-    rc = stage_in(sl, src, src_stride, sdt, d_src, base + o_raw_s, stride, height, width);
-    if (rc) return rc;
-    rc = stage_in(sl, ref, ref_stride, rdt, d_ref, base + o_raw_r, stride, height, width);
-    if (rc) return rc;
+    if ((rc = stage_in(sl, src, src_stride, f.sdt, d_src, hc.at(o_raw_s), stride, height, width))) return rc;
+    if ((rc = stage_in(sl, ref, ref_stride, f.rdt, d_ref, hc.at(o_raw_r), stride, height, width))) return rc;
     if (norm_only) {
         HK_HIP(hk::launch_block_norm(norm_args(desc, d_src, d_ref, height, width, stride), d_ws, d_norm, sl.stream));
         HK_HIP(hipMemcpyAsync(sl.pin<double>(Slot::PIN_NORM), d_norm, 2 * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
@@ -1277,40 +1391,23 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
         return HK_OK;
     }
 
-    // stage out: the window of the block the caller wants, straight into its (strided) arrays
-    const size_t win_off = (size_t)wr0 * stride + wc0;  // elements
-    auto stage_out = [&]() -> int {
-        const size_t wbytes = (size_t)wcols * sizeof(float);
-        float* outs[3] = {d_gain, d_off, d_r2};
-        if (params_out)
-            for (int b = 0; b < n_param_bands; ++b) {
-                const int prc = stage_d2h(sl, params_out + (size_t)b * out_band_stride, par_stride * sizeof(float),
-                                          outs[b] + win_off, stride * sizeof(float), wbytes, wrows);
-                if (prc) return prc;
-            }
-        if (corr_out) {
-            if (out_cast) {
-                const size_t es = hk::dtype_size(odt);
-                char* d_raw = base + o_raw_o;
-                HK_HIP(hk::launch_cast_out(odt, d_corr, stride, d_raw, stride, height, width, io->out_has_nodata,
-                                           io->out_nodata, sl.stream));
-                return stage_d2h(sl, corr_out, out_stride * es, d_raw + win_off * es, stride * es, (size_t)wcols * es, wrows);
-            }
-            return stage_d2h(sl, corr_out, out_stride * sizeof(float), d_corr + win_off, stride * sizeof(float), wbytes, wrows);
-        }
-        return HK_OK;
+    // stage out: the window of the block the caller wants, straight into its (strided) arrays; the parameter planes lie one
+    // plane apart in the slab
+    auto stage_out = [&](const unsigned long long* fail_counter) {
+        return stage_fit_results(sl, f, params_out, n_param_bands, d_gain, stride, (int64_t)(o_off - o_gain) / 4, win, corr_out, d_corr,
+                                 hc.at(o_raw_o), stride, height, width, win, fail_counter);
     };
 
     // The fit, its outputs and its r2-mask counter are queued back to back and the stream is synchronised ONCE; only
     // when pixels failed the mask do the in-painting passes follow, and the outputs are copied again behind them.
     FitPending pending;
-    const int kwin[4] = {wr0, wr0 + wrows, wc0 / hk::PX * hk::PX, width};  // rows exactly, columns from the window's first quad
+    const int kwin[4] = {win.row0, win.row0 + win.rows, win.col0 / hk::PX * hk::PX, width};  // rows exactly, columns from the window's first quad
     rc = fit_on_device(ctx, sl, desc, norm_in, d_src, d_ref, height, width, stride, d_gain, d_off, d_r2, d_corr, d_norm,
-                       d_fail, d_ws, &pending, (ow && !out_cast) ? kwin : nullptr);
+                       d_fail, d_ws, &pending, (ow && !f.out_cast) ? kwin : nullptr);
     if (rc) return rc;
     if (norm_out && blk)
         HK_HIP(hipMemcpyAsync(sl.pin<double>(Slot::PIN_NORM), d_norm, 2 * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
-    if ((rc = stage_out())) return rc;
+    if ((rc = stage_out(nullptr))) return rc;
     // hk_debug_fail_after_d2h(1) (homonim_hk_devtools.h): the call fails HERE, its result copies queued and not yet unpacked --
     // the state every HIP error between a stage_d2h and stage_finish leaves (tests/test_gpu_staging.py)
     if (g_fail_after_d2h.load(std::memory_order_relaxed))
@@ -1325,8 +1422,7 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
         rc = fit_finish(ctx, sl, desc, pending, n_fail, &requeued);
         if (rc) return rc;
         if (requeued) {
-            if ((rc = stage_out())) return rc;
-            HK_HIP(hipMemcpyAsync(sl.fail_host, d_fail, sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
+            if ((rc = stage_out(d_fail))) return rc;
             if ((rc = stage_finish(sl))) return rc;
             n_fail = *sl.fail_host;  // (the in-painting passes do not count)
         }
@@ -1473,62 +1569,46 @@ int hk_fit_apply_block(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* i
 int hk_apply(hk_ctx* ctx, const float* src, int64_t src_stride, const float* params, int32_t height, int32_t width,
              float* out) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!src || !params || !out) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!src || !params || !out) return null_arg();
     if (height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d", height, width);
-    if (src_stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
+    int rc = check_strides(src_stride, width);
+    if (rc) return rc;
     HK_ENTER(ctx);
-    const int64_t stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    const int64_t stride = row_align(width);
     const size_t plane = (size_t)stride * height * sizeof(float);
     SlabLayout L;
     const size_t o_src = L.take(plane), o_gain = L.take(plane), o_off = L.take(plane), o_out = L.take(plane);
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    int rc = ensure_dev(sl, L.total);
-    if (rc) return rc;
-    char* base = static_cast<char*>(sl.dev);
-    float* d_src = reinterpret_cast<float*>(base + o_src);
-    float* d_gain = reinterpret_cast<float*>(base + o_gain);
-    float* d_off = reinterpret_cast<float*>(base + o_off);
-    float* d_out = reinterpret_cast<float*>(base + o_out);
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
+    float *d_src = hc.at<float>(o_src), *d_gain = hc.at<float>(o_gain), *d_off = hc.at<float>(o_off), *d_out = hc.at<float>(o_out);
     const size_t wbytes = (size_t)width * sizeof(float);
-    if ((rc = stage_h2d(sl, d_src, stride * 4, src, src_stride * 4, wbytes, height))) return rc;
-    if ((rc = stage_h2d(sl, d_gain, stride * 4, params, wbytes, wbytes, height))) return rc;
-    if ((rc = stage_h2d(sl, d_off, stride * 4, params + (size_t)height * width, wbytes, wbytes, height))) return rc;
-    HK_HIP(hk::launch_apply(d_src, d_gain, d_off, d_out, height, width, stride, sl.stream));
-    if ((rc = stage_d2h(sl, out, wbytes, d_out, stride * 4, wbytes, height))) return rc;
-    return stage_finish(sl);
+    if ((rc = stage_h2d(hc.sl, d_src, stride * 4, src, src_stride * 4, wbytes, height))) return rc;
+    if ((rc = stage_h2d(hc.sl, d_gain, stride * 4, params, wbytes, wbytes, height))) return rc;
+    if ((rc = stage_h2d(hc.sl, d_off, stride * 4, params + (size_t)height * width, wbytes, wbytes, height))) return rc;
+    HK_HIP(hk::launch_apply(d_src, d_gain, d_off, d_out, height, width, stride, hc.sl.stream));
+    if ((rc = stage_d2h(hc.sl, out, wbytes, d_out, stride * 4, wbytes, height))) return rc;
+    return stage_finish(hc.sl);
 }
 
 int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_space_desc* space,
                           const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
                           int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
                           int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count) {
-    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    int rc = validate_desc(desc);
+    int rc = check_two_grids(ctx, desc, space, src, src_stride, src_height, src_width, ref, ref_stride, ref_height, ref_width, corr_out);
     if (rc) return rc;
-    if (!space || !src || !ref || !corr_out) return fail(HK_ERR_ARG, "NULL pointer argument");
-    if (src_height < 1 || src_width < 1 || ref_height < 1 || ref_width < 1) return fail(HK_ERR_ARG, "empty raster");
-    if (src_stride < src_width || ref_stride < ref_width) return fail(HK_ERR_ARG, "row stride smaller than width");
     for (int m : {space->down_resampling, space->up_resampling})
         if (!resampling_built(m)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not built", m);
     if (!(space->down[0] > 0 && space->down[2] > 0 && space->up[0] > 0 && space->up[2] > 0))
         return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
-    if (src_height > 65535 || ref_height > 65535) return fail(HK_ERR_UNSUPPORTED, "block taller than 65535 rows");
-    const int sdt = io ? io->src_dtype : 0, rdt = io ? io->ref_dtype : 0, odt = io ? io->out_dtype : 0;
-    if (!hk::dtype_size(sdt) || !hk::dtype_size(rdt) || !hk::dtype_size(odt)) return fail(HK_ERR_ARG, "unknown dtype");
-    if (io && (rc = validate_out_nodata(odt, io->out_has_nodata, io->out_nodata))) return rc;
-    const bool out_cast = io && (odt != 0 || io->out_has_nodata);
-    const bool r2 = needs_r2(desc);
-    if (params_out && n_param_bands != (r2 ? 3 : 2))
-        return fail(HK_ERR_ARG, "n_param_bands must be %d for this model configuration", r2 ? 3 : 2);
+    FitIo f;
+    if ((rc = check_fit_io(desc, io, params_out, n_param_bands, &f))) return rc;
     HK_ENTER(ctx);
 
-    const int64_t ss = (src_width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;  // source-grid row stride
-    const int64_t rs = (ref_width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;  // reference-grid row stride
+    const int64_t ss = row_align(src_width), rs = row_align(ref_width);  // row strides of the source and the reference grid
     const size_t splane = (size_t)ss * src_height * 4, rplane = (size_t)rs * ref_height * 4;
     SlabLayout L;
     const size_t o_src = L.take(splane), o_ref = L.take(rplane), o_ds = L.take(rplane);
-    const size_t o_gain = L.take(rplane), o_off = L.take(rplane), o_r2 = r2 ? L.take(rplane) : 0;
+    const size_t o_gain = L.take(rplane), o_off = L.take(rplane), o_r2 = f.r2 ? L.take(rplane) : 0;
     // bilinear / cubic_spline parameters are up-sampled inside the apply kernel (no full-resolution parameter planes)
     const bool fused_up = (space->up_resampling == 1 || space->up_resampling == 3) && ref_width >= 4 &&
                           space->up[0] <= 1.0 + 1e-9 && space->up[2] <= 1.0 + 1e-9 &&
@@ -1539,32 +1619,30 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     const size_t o_mk = space->mask_partial ? L.take((size_t)rs * ref_height) : 0;
     const size_t o_mkf = space->mask_partial ? L.take(rplane) : 0, o_keep = space->mask_partial ? L.take(splane) : 0;
     const size_t o_cnt = space->mask_partial ? L.take((size_t)rs * ref_height * 2) : 0;
-    const size_t o_raw_s = sdt ? L.take((size_t)ss * src_height * hk::dtype_size(sdt)) : 0;
-    const size_t o_raw_r = rdt ? L.take((size_t)rs * ref_height * hk::dtype_size(rdt)) : 0;
-    const size_t o_raw_o = out_cast ? L.take((size_t)ss * src_height * hk::dtype_size(odt)) : 0;
+    const size_t o_raw_s = f.sdt ? L.take((size_t)ss * src_height * hk::dtype_size(f.sdt)) : 0;
+    const size_t o_raw_r = f.rdt ? L.take((size_t)rs * ref_height * hk::dtype_size(f.rdt)) : 0;
+    const size_t o_raw_o = f.out_cast ? L.take((size_t)ss * src_height * hk::dtype_size(f.odt)) : 0;
     const size_t o_aux = L.take(256);
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
     const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, ref_height, ref_width)) : 0;
 
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    rc = ensure_dev(sl, L.total);
-    if (rc) return rc;
-    char* base = static_cast<char*>(sl.dev);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
+    Slot& sl = hc.sl;
+    auto F = [&](size_t off) { return hc.at<float>(off); };
     float *d_src = F(o_src), *d_ref = F(o_ref), *d_ds = F(o_ds), *d_gain = F(o_gain), *d_off = F(o_off);
-    float *d_r2 = r2 ? F(o_r2) : nullptr, *d_gus = F(o_gus), *d_ous = F(o_ous), *d_corr = F(o_corr);
-    double* d_norm = reinterpret_cast<double*>(base + o_aux);
-    unsigned long long* d_fail = reinterpret_cast<unsigned long long*>(base + o_aux + 64);
+    float *d_r2 = f.r2 ? F(o_r2) : nullptr, *d_gus = F(o_gus), *d_ous = F(o_ous), *d_corr = F(o_corr);
+    double* d_norm = hc.at<double>(o_aux);
+    unsigned long long* d_fail = hc.at<unsigned long long>(o_aux + 64);
     const float nan = std::nanf("");
 
-    if ((rc = stage_in(sl, src, src_stride, sdt, d_src, base + o_raw_s, ss, src_height, src_width))) return rc;
-    if ((rc = stage_in(sl, ref, ref_stride, rdt, d_ref, base + o_raw_r, rs, ref_height, ref_width))) return rc;
+    if ((rc = stage_in(sl, src, src_stride, f.sdt, d_src, hc.at(o_raw_s), ss, src_height, src_width))) return rc;
+    if ((rc = stage_in(sl, ref, ref_stride, f.rdt, d_ref, hc.at(o_raw_r), rs, ref_height, ref_width))) return rc;
 
     // one plane from the source grid down to the reference grid, or from there up to the source grid
     auto resample = [&](int mode, bool down, const float* from, int nd_mode, float nodata, float* to, float fill) {
-        hk::ResamplePlanes p = {from, to, ss, 0, rs, 0, src_height, src_width, ref_height, ref_width, 1, nd_mode, nodata, fill};
-        if (!down) std::swap(p.src_stride, p.dst_stride), std::swap(p.sh, p.dh), std::swap(p.sw, p.dw);
+        const hk::ResamplePlanes p = down ? resample_planes(from, src_height, src_width, ss, 0, to, ref_height, ref_width, rs, 0, 1, nd_mode, nodata, fill)
+                                          : resample_planes(from, ref_height, ref_width, rs, 0, to, src_height, src_width, ss, 0, 1, nd_mode, nodata, fill);
         const double* m = down ? space->down : space->up;
         return hk::launch_resample(mode, p, m[0], m[1], m[2], m[3], sl.stream);
     };
@@ -1574,7 +1652,7 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     hk_fit_desc fd = *desc;
     fd.src_nodata_mode = HK_NODATA_NAN, fd.src_nodata = nan;
     rc = fit_on_device(ctx, sl, &fd, nullptr, d_ds, d_ref, ref_height, ref_width, rs, d_gain, d_off, d_r2, nullptr, d_norm,
-                       d_fail, base + o_ws);
+                       d_fail, hc.at(o_ws));
     if (rc) return rc;
 
     // RefSpaceModel.apply (:484-503): gain / offset -> source grid, re-mask, apply
@@ -1588,11 +1666,11 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
         HK_HIP(hk::launch_valid_plane(d_src, ss, desc->src_nodata_mode, desc->src_nodata, F(o_vs), ss, src_height,
                                       src_width, sl.stream));
         HK_HIP(resample(5, true, F(o_vs), HK_NODATA_NONE, 0.f, F(o_cov), 0.f));
-        unsigned char* d_mk = reinterpret_cast<unsigned char*>(base + o_mk);
+        unsigned char* d_mk = hc.at<unsigned char>(o_mk);
         // the parameters as two bands: gain, and offset one band stride further on
         HK_HIP(hk::launch_partial_mask(F(o_cov), 3, 0.f, d_gain, 2, (long long)(o_off - o_gain) / 4, nullptr,
                                        ref_height, ref_width, rs, desc->kh, desc->kw,
-                                       reinterpret_cast<unsigned short*>(base + o_cnt), nullptr, nullptr, d_mk, sl.stream));
+                                       hc.at<unsigned short>(o_cnt), nullptr, nullptr, d_mk, sl.stream));
         HK_HIP(hk::launch_cast_in(1, d_mk, rs, F(o_mkf), rs, ref_height, ref_width, sl.stream));
         HK_HIP(resample(0, false, F(o_mkf), HK_NODATA_NONE, 0.f, F(o_keep), 0.f));
         d_keep = F(o_keep);
@@ -1600,28 +1678,16 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     if (fused_up) {
         HK_HIP(hk::launch_upsample_apply(space->up_resampling, d_src, ss, desc->src_nodata_mode, desc->src_nodata, d_gain,
                                          d_off, rs, ref_height, ref_width, d_keep, ss, d_corr, ss, src_height, src_width,
-                                         space->up[0], space->up[1], space->up[2], space->up[3], base + o_rowtab, sl.stream));
+                                         space->up[0], space->up[1], space->up[2], space->up[3], hc.at(o_rowtab), sl.stream));
     } else {
         HK_HIP(hk::launch_apply_space(d_src, ss, desc->src_nodata_mode, desc->src_nodata, d_gus, d_ous, ss, d_keep, d_corr,
                                       ss, src_height, src_width, sl.stream));
     }
 
-    if (params_out) {
-        float* outs[3] = {d_gain, d_off, d_r2};
-        const size_t wb = (size_t)ref_width * 4;
-        for (int b = 0; b < n_param_bands; ++b)
-            if ((rc = stage_d2h(sl, params_out + (size_t)b * ref_height * ref_width, wb, outs[b], rs * 4, wb, ref_height))) return rc;
-    }
-    if (out_cast) {
-        const size_t es = hk::dtype_size(odt);
-        void* d_raw = base + o_raw_o;
-        HK_HIP(hk::launch_cast_out(odt, d_corr, ss, d_raw, ss, src_height, src_width, io->out_has_nodata, io->out_nodata,
-                                   sl.stream));
-        if ((rc = stage_d2h(sl, corr_out, (size_t)src_width * es, d_raw, ss * es, (size_t)src_width * es, src_height))) return rc;
-    } else {
-        if ((rc = stage_d2h(sl, corr_out, (size_t)src_width * 4, d_corr, ss * 4, (size_t)src_width * 4, src_height))) return rc;
-    }
-    HK_HIP(hipMemcpyAsync(sl.fail_host, d_fail, sizeof(uint64_t), hipMemcpyDeviceToHost, sl.stream));
+    // the parameters on the reference grid, the corrected block on the source grid, both whole and packed
+    if ((rc = stage_fit_results(sl, f, params_out, n_param_bands, d_gain, rs, (int64_t)(o_off - o_gain) / 4, whole_block(ref_height, ref_width),
+                                corr_out, d_corr, hc.at(o_raw_o), ss, src_height, src_width, whole_block(src_height, src_width), d_fail)))
+        return rc;
     if ((rc = stage_finish(sl))) return rc;
     if (r2_fail_count) *r2_fail_count = *sl.fail_host;
     return HK_OK;
@@ -1631,28 +1697,16 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
                           const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
                           int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
                           int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count) {
-    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    int rc = validate_desc(desc);
+    int rc = check_two_grids(ctx, desc, space, src, src_stride, src_height, src_width, ref, ref_stride, ref_height, ref_width, corr_out);
     if (rc) return rc;
-    if (!space || !src || !ref || !corr_out) return fail(HK_ERR_ARG, "NULL pointer argument");
-    if (src_height < 1 || src_width < 1 || ref_height < 1 || ref_width < 1) return fail(HK_ERR_ARG, "empty raster");
-    if (src_stride < src_width || ref_stride < ref_width) return fail(HK_ERR_ARG, "row stride smaller than width");
     if (!resampling_built(space->resampling)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not built", space->resampling);
     if (!(space->map[0] > 0 && space->map[2] > 0)) return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
-    if (src_height > 65535 || ref_height > 65535) return fail(HK_ERR_UNSUPPORTED, "block taller than 65535 rows");
-    const int sdt = io ? io->src_dtype : 0, rdt = io ? io->ref_dtype : 0, odt = io ? io->out_dtype : 0;
-    if (!hk::dtype_size(sdt) || !hk::dtype_size(rdt) || !hk::dtype_size(odt)) return fail(HK_ERR_ARG, "unknown dtype");
-    if (io && (rc = validate_out_nodata(odt, io->out_has_nodata, io->out_nodata))) return rc;
-    const bool out_cast = io && (odt != 0 || io->out_has_nodata);
-    const bool r2 = needs_r2(desc);
-    if (params_out && n_param_bands != (r2 ? 3 : 2))
-        return fail(HK_ERR_ARG, "n_param_bands must be %d for this model configuration", r2 ? 3 : 2);
-    const bool partial = space->mask_partial != 0;
-    if (partial && (desc->kh + 2) * (desc->kw + 2) > 65535) return fail(HK_ERR_UNSUPPORTED, "kernel too large for mask_partial");
+    FitIo f;
+    if ((rc = check_fit_io(desc, io, params_out, n_param_bands, &f))) return rc;
+    const bool r2 = f.r2, partial = space->mask_partial != 0;
     HK_ENTER(ctx);
 
-    const int64_t ss = (src_width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;  // source-grid row stride
-    const int64_t rs = (ref_width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;  // reference-grid row stride
+    const int64_t ss = row_align(src_width), rs = row_align(ref_width);  // row strides of the source and the reference grid
     const size_t splane = (size_t)ss * src_height * 4, rplane = (size_t)rs * ref_height * 4;
     const int n_par = r2 ? 3 : 2;
     // `average` reads the reference as it was uploaded (footprint_typed_kernel): no float32 copy, no valid plane
@@ -1666,44 +1720,42 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     const size_t o_mpar = (partial && params_out) ? L.take(splane) : 0;  // the masked parameters
     if (partial && params_out)
         for (int b = 1; b < n_par; ++b) L.take(splane);
-    const size_t o_ref = (!typed_foot || !rdt) ? L.take(rplane) : 0, o_vr = (partial && !typed_foot) ? L.take(rplane) : 0;
-    const size_t o_raw_s = sdt ? L.take((size_t)ss * src_height * hk::dtype_size(sdt)) : 0;
-    const size_t o_raw_r = rdt ? L.take((size_t)rs * ref_height * hk::dtype_size(rdt)) : 0;
-    const size_t o_raw_o = out_cast ? L.take((size_t)ss * src_height * hk::dtype_size(odt)) : 0;
+    const size_t o_ref = (!typed_foot || !f.rdt) ? L.take(rplane) : 0, o_vr = (partial && !typed_foot) ? L.take(rplane) : 0;
+    const size_t o_raw_s = f.sdt ? L.take((size_t)ss * src_height * hk::dtype_size(f.sdt)) : 0;
+    const size_t o_raw_r = f.rdt ? L.take((size_t)rs * ref_height * hk::dtype_size(f.rdt)) : 0;
+    const size_t o_raw_o = f.out_cast ? L.take((size_t)ss * src_height * hk::dtype_size(f.odt)) : 0;
     const size_t o_aux = L.take(256);
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
     const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, src_height, src_width)) : 0;
 
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    rc = ensure_dev(sl, L.total);
-    if (rc) return rc;
-    char* base = static_cast<char*>(sl.dev);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
+    Slot& sl = hc.sl;
+    auto F = [&](size_t off) { return hc.at<float>(off); };
     const long long pbs = (long long)((splane + 255) / 256 * 256 / 4);  // band stride of the parameter planes, elements
     float *d_src = F(o_src), *d_rus = F(o_rus), *d_gain = F(o_par), *d_off = d_gain + pbs, *d_r2 = r2 ? d_gain + 2 * pbs : nullptr;
     float* d_corr = F(o_corr);
-    double* d_norm = reinterpret_cast<double*>(base + o_aux);
-    unsigned long long* d_fail = reinterpret_cast<unsigned long long*>(base + o_aux + 64);
+    double* d_norm = hc.at<double>(o_aux);
+    unsigned long long* d_fail = hc.at<unsigned long long>(o_aux + 64);
     const float nan = std::nanf("");
     const double* m = space->map;
 
-    if ((rc = stage_in(sl, src, src_stride, sdt, d_src, base + o_raw_s, ss, src_height, src_width))) return rc;
+    if ((rc = stage_in(sl, src, src_stride, f.sdt, d_src, hc.at(o_raw_s), ss, src_height, src_width))) return rc;
 
     // SrcSpaceModel.fit (:520): reference -> source grid (nodata nan), and for mask_partial the coverage of its valid mask
     // (_full_coverage_mask, :375-399: mask_ra re-projected with `average`, no nodata)
     if (typed_foot) {
-        const size_t es = hk::dtype_size(rdt);
-        void* d_raw = rdt ? static_cast<void*>(base + o_raw_r) : static_cast<void*>(base + o_ref);
+        const size_t es = hk::dtype_size(f.rdt);
+        void* d_raw = hc.at(f.rdt ? o_raw_r : o_ref);
         if ((rc = stage_h2d(sl, d_raw, rs * es, ref, ref_stride * es, (size_t)ref_width * es, ref_height))) return rc;
-        HK_HIP(hk::launch_footprint_typed(rdt, d_raw, rs, ref_height, ref_width, desc->ref_nodata_mode, desc->ref_nodata, d_rus,
+        HK_HIP(hk::launch_footprint_typed(f.rdt, d_raw, rs, ref_height, ref_width, desc->ref_nodata_mode, desc->ref_nodata, d_rus,
                                           partial ? F(o_cov) : nullptr, ss, src_height, src_width, nan, m[0], m[1], m[2], m[3],
                                           sl.stream));
     } else {
         float* d_ref = F(o_ref);
-        if ((rc = stage_in(sl, ref, ref_stride, rdt, d_ref, base + o_raw_r, rs, ref_height, ref_width))) return rc;
-        hk::ResamplePlanes p = {d_ref, d_rus, rs, 0, ss, 0, ref_height, ref_width, src_height, src_width, 1,
-                                desc->ref_nodata_mode, desc->ref_nodata, nan};
+        if ((rc = stage_in(sl, ref, ref_stride, f.rdt, d_ref, hc.at(o_raw_r), rs, ref_height, ref_width))) return rc;
+        hk::ResamplePlanes p = resample_planes(d_ref, ref_height, ref_width, rs, 0, d_rus, src_height, src_width, ss, 0, 1,
+                                               desc->ref_nodata_mode, desc->ref_nodata, nan);
         HK_HIP(hk::launch_resample(space->resampling, p, m[0], m[1], m[2], m[3], sl.stream));
         if (partial) {
             HK_HIP(hk::launch_valid_plane(d_ref, rs, desc->ref_nodata_mode, desc->ref_nodata, F(o_vr), rs, ref_height, ref_width,
@@ -1718,7 +1770,7 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     hk_fit_desc fd = *desc;
     fd.ref_nodata_mode = HK_NODATA_NAN, fd.ref_nodata = nan;
     rc = fit_on_device(ctx, sl, &fd, nullptr, d_src, d_rus, src_height, src_width, ss, d_gain, d_off, d_r2,
-                       partial ? nullptr : d_corr, d_norm, d_fail, base + o_ws);
+                       partial ? nullptr : d_corr, d_norm, d_fail, hc.at(o_ws));
     if (rc) return rc;
 
     float* d_pout = d_gain;
@@ -1726,25 +1778,12 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
         // :526-531: coverage >= 1 & "has gain or offset", eroded by (kh+2) x (kw+2), on ALL parameter bands; then KernelModel.apply
         d_pout = params_out ? F(o_mpar) : nullptr;
         HK_HIP(hk::launch_partial_mask(F(o_cov), 3, 0.f, d_gain, n_par, pbs, d_src, src_height, src_width, ss, desc->kh, desc->kw,
-                                       reinterpret_cast<unsigned short*>(base + o_cnt), d_pout, d_corr, nullptr, sl.stream));
+                                       hc.at<unsigned short>(o_cnt), d_pout, d_corr, nullptr, sl.stream));
     }
 
-    if (params_out) {
-        const size_t wb = (size_t)src_width * 4;
-        for (int b = 0; b < n_param_bands; ++b)
-            if ((rc = stage_d2h(sl, params_out + (size_t)b * src_height * src_width, wb, d_pout + (size_t)b * pbs, ss * 4, wb, src_height)))
-                return rc;
-    }
-    if (out_cast) {
-        const size_t es = hk::dtype_size(odt);
-        void* d_raw = base + o_raw_o;
-        HK_HIP(hk::launch_cast_out(odt, d_corr, ss, d_raw, ss, src_height, src_width, io->out_has_nodata, io->out_nodata,
-                                   sl.stream));
-        if ((rc = stage_d2h(sl, corr_out, (size_t)src_width * es, d_raw, ss * es, (size_t)src_width * es, src_height))) return rc;
-    } else {
-        if ((rc = stage_d2h(sl, corr_out, (size_t)src_width * 4, d_corr, ss * 4, (size_t)src_width * 4, src_height))) return rc;
-    }
-    HK_HIP(hipMemcpyAsync(sl.fail_host, d_fail, sizeof(uint64_t), hipMemcpyDeviceToHost, sl.stream));
+    const hk_out_window whole = whole_block(src_height, src_width);
+    if ((rc = stage_fit_results(sl, f, params_out, n_param_bands, d_pout, ss, pbs, whole, corr_out, d_corr, hc.at(o_raw_o), ss, src_height, src_width, whole, d_fail)))
+        return rc;
     if ((rc = stage_finish(sl))) return rc;
     if (r2_fail_count) *r2_fail_count = *sl.fail_host;
     return HK_OK;
@@ -1753,55 +1792,36 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
 int hk_reproject(hk_ctx* ctx, const float* src, int32_t n_bands, int32_t src_height, int32_t src_width,
                  int32_t src_nodata_mode, float src_nodata, double kx, double ox, double ky, double oy, int32_t resampling,
                  float* dst, int32_t dst_height, int32_t dst_width, float dst_fill) {
-    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!src || !dst) return fail(HK_ERR_ARG, "NULL pointer argument");
-    if (n_bands < 1 || src_height < 1 || src_width < 1 || dst_height < 1 || dst_width < 1)
-        return fail(HK_ERR_ARG, "empty raster");
-    if (!(kx > 0.0) || !(ky > 0.0)) return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
-    if (!resampling_built(resampling))
-        return fail(HK_ERR_UNSUPPORTED, "resampling %d is not a warp method (GRA_* codes 0..6 and 8..14 are built; 7 = gauss is "
-                                        "an overview-only method in GDAL / rasterio as well)", resampling);
-    if (dst_height > 65535) return fail(HK_ERR_UNSUPPORTED, "destination taller than 65535 rows");
-    HK_ENTER(ctx);
-    const size_t sbytes = (size_t)n_bands * src_height * src_width * 4, dbytes = (size_t)n_bands * dst_height * dst_width * 4;
-    const size_t o_dst = (sbytes + 255) / 256 * 256;
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    int rc = ensure_dev(sl, o_dst + dbytes);
+    int rc = check_reproject(ctx, src, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst, dst_height, dst_width,
+                             /*host_form=*/true);
     if (rc) return rc;
-    float* d_src = static_cast<float*>(sl.dev);
-    float* d_dst = reinterpret_cast<float*>(static_cast<char*>(sl.dev) + o_dst);
-    if ((rc = stage_h2d(sl, d_src, sbytes, src, sbytes, sbytes, 1))) return rc;
-    const hk::ResamplePlanes p = {d_src, d_dst, src_width, (long long)src_height * src_width, dst_width, (long long)dst_height * dst_width,
-                                  src_height, src_width, dst_height, dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill};
-    HK_HIP(hk::launch_resample(resampling, p, kx, ox, ky, oy, sl.stream));
-    if ((rc = stage_d2h(sl, dst, dbytes, d_dst, dbytes, dbytes, 1))) return rc;
-    return stage_finish(sl);
+    HK_ENTER(ctx);
+    const PackedBands pk = packed_bands(n_bands, src_height, src_width, dst_height, dst_width);
+    HostCall hc(ctx, pk.o_dst + pk.dbytes);
+    if (hc.rc) return hc.rc;
+    float *d_src = hc.at<float>(0), *d_dst = hc.at<float>(pk.o_dst);
+    if ((rc = stage_h2d(hc.sl, d_src, pk.sbytes, src, pk.sbytes, pk.sbytes, 1))) return rc;
+    const hk::ResamplePlanes p = resample_planes(d_src, src_height, src_width, src_width, (int64_t)src_height * src_width, d_dst, dst_height, dst_width,
+                                                 dst_width, (int64_t)dst_height * dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill);
+    HK_HIP(hk::launch_resample(resampling, p, kx, ox, ky, oy, hc.sl.stream));
+    if ((rc = stage_d2h(hc.sl, dst, pk.dbytes, d_dst, pk.dbytes, pk.dbytes, 1))) return rc;
+    return stage_finish(hc.sl);
 }
-
-static int check_nodata_mode(int32_t mode);
 
 int hk_reproject_dev(hk_ctx* ctx, const float* src_dev, int32_t n_bands, int32_t src_height, int32_t src_width,
                      int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode, float src_nodata, double kx, double ox,
                      double ky, double oy, int32_t resampling, float* dst_dev, int32_t dst_height, int32_t dst_width,
                      int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream) {
-    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!src_dev || !dst_dev) return fail(HK_ERR_ARG, "NULL pointer argument");
-    if (n_bands < 1 || src_height < 1 || src_width < 1 || dst_height < 1 || dst_width < 1)
-        return fail(HK_ERR_ARG, "empty raster");
-    if (n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", n_bands);
-    if (src_stride < src_width || dst_stride < dst_width) return fail(HK_ERR_ARG, "row stride smaller than width");
-    if (src_band_stride < 0 || dst_band_stride < 0) return fail(HK_ERR_ARG, "band_stride is negative");
-    if (!(kx > 0.0) || !(ky > 0.0)) return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
-    if (!resampling_built(resampling)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not a warp method", resampling);
-    if (dst_height > 65535) return fail(HK_ERR_UNSUPPORTED, "destination taller than 65535 rows");
-    int rc = check_nodata_mode(src_nodata_mode);
+    int rc = check_reproject(ctx, src_dev, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst_dev, dst_height,
+                             dst_width, /*host_form=*/false);
     if (rc) return rc;
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if ((rc = check_strides(src_stride, src_width, dst_stride, dst_width)) || (rc = check_band_strides(src_band_stride, dst_band_stride)) ||
+        (rc = check_stream(ctx, stream)))
+        return rc;
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
-    const hk::ResamplePlanes p = {src_dev, dst_dev, src_stride, src_band_stride, dst_stride, dst_band_stride,
-                                  src_height, src_width, dst_height, dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill};
+    const hk::ResamplePlanes p = resample_planes(src_dev, src_height, src_width, src_stride, src_band_stride, dst_dev, dst_height, dst_width,
+                                                 dst_stride, dst_band_stride, n_bands, src_nodata_mode, src_nodata, dst_fill);
     HK_HIP(hk::launch_resample(resampling, p, kx, ox, ky, oy, ctx->slots[stream].stream));
     return HK_OK;
 }
@@ -1811,11 +1831,10 @@ int hk_reproject_dev(hk_ctx* ctx, const float* src_dev, int32_t n_bands, int32_t
 static int check_warp_lattice(hk_ctx* ctx, const void* warp, int32_t height, int32_t width, const void* x, const void* y,
                               int64_t stride) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!warp || !x || !y) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!warp || !x || !y) return null_arg();
     if (height < 1 || width < 1) return fail(HK_ERR_ARG, "empty lattice %d x %d", height, width);
     if (height > 65535) return fail(HK_ERR_UNSUPPORTED, "lattice taller than 65535 rows");
-    if (stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
-    return HK_OK;
+    return check_strides(stride, width);
 }
 
 // hipErrorInvalidValue of the warp launchers carries a reason: an unusable descriptor (HK_ERR_ARG), or CRSs the warp is not
@@ -1832,8 +1851,7 @@ extern "C++" template <typename Desc>
 static int warp_coords_dev(hk_ctx* ctx, const Desc* warp, double off_row, double off_col, int32_t height, int32_t width,
                            double* x_dev, double* y_dev, int64_t stride, int32_t stream) {
     int rc = check_warp_lattice(ctx, warp, height, width, x_dev, y_dev, stride);
-    if (rc) return rc;
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (rc || (rc = check_stream(ctx, stream))) return rc;
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
     const char* why = nullptr;
@@ -1847,21 +1865,18 @@ static int warp_coords_host(hk_ctx* ctx, const Desc* warp, double off_row, doubl
     int rc = check_warp_lattice(ctx, warp, height, width, x_out, y_out, stride);
     if (rc) return rc;
     HK_ENTER(ctx);
-    const int64_t d_stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    const int64_t d_stride = row_align(width);
     SlabLayout L;
     const size_t plane = (size_t)d_stride * height * sizeof(double);
     const size_t o_x = L.take(plane), o_y = L.take(plane);
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    if ((rc = ensure_dev(sl, L.total))) return rc;
-    char* base = static_cast<char*>(sl.dev);
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
     const char* why = nullptr;
-    const hk::WarpLattice l = {reinterpret_cast<double*>(base + o_x), reinterpret_cast<double*>(base + o_y), d_stride, height, width,
-                               off_row, off_col};
-    if ((rc = warp_launch_status(hk::launch_warp_coords(warp, l, sl.stream, &why), why))) return rc;
-    if ((rc = stage_d2h(sl, x_out, (size_t)stride * 8, base + o_x, (size_t)d_stride * 8, (size_t)width * 8, height))) return rc;
-    if ((rc = stage_d2h(sl, y_out, (size_t)stride * 8, base + o_y, (size_t)d_stride * 8, (size_t)width * 8, height))) return rc;
-    return stage_finish(sl);
+    const hk::WarpLattice l = {hc.at<double>(o_x), hc.at<double>(o_y), d_stride, height, width, off_row, off_col};
+    if ((rc = warp_launch_status(hk::launch_warp_coords(warp, l, hc.sl.stream, &why), why))) return rc;
+    if ((rc = stage_d2h(hc.sl, x_out, (size_t)stride * 8, l.x, (size_t)d_stride * 8, (size_t)width * 8, height))) return rc;
+    if ((rc = stage_d2h(hc.sl, y_out, (size_t)stride * 8, l.y, (size_t)d_stride * 8, (size_t)width * 8, height))) return rc;
+    return stage_finish(hc.sl);
 }
 
 int hk_warp_coords_dev(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double off_col, int32_t height, int32_t width,
@@ -1888,7 +1903,7 @@ static int check_reproject_crs(hk_ctx* ctx, const void* warp, bool affine, const
                                int32_t src_width, int32_t src_nodata_mode, double kx, double ky, int32_t resampling,
                                const float* dst, int32_t dst_height, int32_t dst_width) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!warp || !src || !dst) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!warp || !src || !dst) return null_arg();
     if (n_bands < 1 || src_height < 1 || src_width < 1 || dst_height < 1 || dst_width < 1)
         return fail(HK_ERR_ARG, "empty raster");
     if (!(kx > 0.0) || !(ky > 0.0) || !std::isfinite(kx) || !std::isfinite(ky))
@@ -1912,14 +1927,14 @@ static int reproject_warp_dev(hk_ctx* ctx, const Desc* warp, const float* src_de
     int rc = check_reproject_crs(ctx, warp, std::is_same<Desc, hk_affine_warp_desc>::value, src_dev, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst_dev,
                                  dst_height, dst_width);
     if (rc) return rc;
-    if (src_stride < src_width || dst_stride < dst_width) return fail(HK_ERR_ARG, "row stride smaller than width");
-    if (src_band_stride < 0 || dst_band_stride < 0) return fail(HK_ERR_ARG, "band_stride is negative");
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if ((rc = check_strides(src_stride, src_width, dst_stride, dst_width)) || (rc = check_band_strides(src_band_stride, dst_band_stride)) ||
+        (rc = check_stream(ctx, stream)))
+        return rc;
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
     const char* why = nullptr;
-    const hk::ResamplePlanes p = {src_dev, dst_dev, src_stride, src_band_stride, dst_stride, dst_band_stride,
-                                  src_height, src_width, dst_height, dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill};
+    const hk::ResamplePlanes p = resample_planes(src_dev, src_height, src_width, src_stride, src_band_stride, dst_dev, dst_height, dst_width,
+                                                 dst_stride, dst_band_stride, n_bands, src_nodata_mode, src_nodata, dst_fill);
     return warp_launch_status(hk::launch_warp_resample(resampling, warp, p, kx, ky, ctx->slots[stream].stream, &why), why);
 }
 
@@ -1931,20 +1946,17 @@ static int reproject_warp_host(hk_ctx* ctx, const Desc* warp, const float* src, 
                                  dst_height, dst_width);
     if (rc) return rc;
     HK_ENTER(ctx);
-    const size_t sbytes = (size_t)n_bands * src_height * src_width * 4, dbytes = (size_t)n_bands * dst_height * dst_width * 4;
-    const size_t o_dst = (sbytes + 255) / 256 * 256;
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    if ((rc = ensure_dev(sl, o_dst + dbytes))) return rc;
-    float* d_src = static_cast<float*>(sl.dev);
-    float* d_dst = reinterpret_cast<float*>(static_cast<char*>(sl.dev) + o_dst);
-    if ((rc = stage_h2d(sl, d_src, sbytes, src, sbytes, sbytes, 1))) return rc;
+    const PackedBands pk = packed_bands(n_bands, src_height, src_width, dst_height, dst_width);
+    HostCall hc(ctx, pk.o_dst + pk.dbytes);
+    if (hc.rc) return hc.rc;
+    float *d_src = hc.at<float>(0), *d_dst = hc.at<float>(pk.o_dst);
+    if ((rc = stage_h2d(hc.sl, d_src, pk.sbytes, src, pk.sbytes, pk.sbytes, 1))) return rc;
     const char* why = nullptr;
-    const hk::ResamplePlanes p = {d_src, d_dst, src_width, (long long)src_height * src_width, dst_width, (long long)dst_height * dst_width,
-                                  src_height, src_width, dst_height, dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill};
-    if ((rc = warp_launch_status(hk::launch_warp_resample(resampling, warp, p, kx, ky, sl.stream, &why), why))) return rc;
-    if ((rc = stage_d2h(sl, dst, dbytes, d_dst, dbytes, dbytes, 1))) return rc;
-    return stage_finish(sl);
+    const hk::ResamplePlanes p = resample_planes(d_src, src_height, src_width, src_width, (int64_t)src_height * src_width, d_dst, dst_height, dst_width,
+                                                 dst_width, (int64_t)dst_height * dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill);
+    if ((rc = warp_launch_status(hk::launch_warp_resample(resampling, warp, p, kx, ky, hc.sl.stream, &why), why))) return rc;
+    if ((rc = stage_d2h(hc.sl, dst, pk.dbytes, d_dst, pk.dbytes, pk.dbytes, 1))) return rc;
+    return stage_finish(hc.sl);
 }
 
 int hk_reproject_crs_dev(hk_ctx* ctx, const hk_warp_desc* warp, const float* src_dev, int32_t n_bands, int32_t src_height,
@@ -1984,31 +1996,28 @@ int hk_partial_mask(hk_ctx* ctx, const float* in, int64_t in_stride, int32_t in_
                     const float* params, int32_t n_param_bands, const float* src, int64_t src_stride, int32_t height,
                     int32_t width, int32_t kh, int32_t kw, float* params_out, float* corr_out, uint8_t* mask_out) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!in || !params) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!in || !params) return null_arg();
     if (height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d", height, width);
     if (n_param_bands < 2 || n_param_bands > 3) return fail(HK_ERR_ARG, "params must have 2 or 3 bands");
     if (kh < 1 || kw < 1 || !(kh & 1) || !(kw & 1)) return fail(HK_ERR_ARG, "`kernel_shape` must be odd in both dimensions.");
-    if ((kh + 2) * (kw + 2) > 65535) return fail(HK_ERR_UNSUPPORTED, "kernel too large for mask_partial");
+    int rc = check_mask_kernel(kh, kw);
+    if (rc) return rc;
     if (corr_out && !src) return fail(HK_ERR_ARG, "corr_out needs src");
-    if (in_stride < width || (src && src_stride < width)) return fail(HK_ERR_ARG, "row stride smaller than width");
+    if ((rc = check_strides(in_stride, width)) || (src && (rc = check_strides(src_stride, width)))) return rc;
+    if ((rc = check_nodata_mode(in_nodata_mode, 3))) return rc;  // 3: `in` is a coverage fraction, valid from 1 (include/homonim_hk.h)
     HK_ENTER(ctx);
-    const int64_t stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    const int64_t stride = row_align(width);
     const size_t plane = (size_t)stride * height * sizeof(float);
     SlabLayout L;
     const size_t o_in = L.take(plane), o_par = L.take(plane * n_param_bands), o_src = src ? L.take(plane) : 0;
     const size_t o_pout = params_out ? L.take(plane * n_param_bands) : 0, o_corr = corr_out ? L.take(plane) : 0;
     const size_t o_mask = mask_out ? L.take((size_t)stride * height) : 0, o_cnt = L.take((size_t)stride * height * 2);
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    int rc = ensure_dev(sl, L.total);
-    if (rc) return rc;
-    char* base = static_cast<char*>(sl.dev);
-    float* d_in = reinterpret_cast<float*>(base + o_in);
-    float* d_par = reinterpret_cast<float*>(base + o_par);
-    float* d_src = src ? reinterpret_cast<float*>(base + o_src) : nullptr;
-    float* d_pout = params_out ? reinterpret_cast<float*>(base + o_pout) : nullptr;
-    float* d_corr = corr_out ? reinterpret_cast<float*>(base + o_corr) : nullptr;
-    unsigned char* d_mask = mask_out ? reinterpret_cast<unsigned char*>(base + o_mask) : nullptr;
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
+    Slot& sl = hc.sl;
+    float *d_in = hc.at<float>(o_in), *d_par = hc.at<float>(o_par), *d_src = src ? hc.at<float>(o_src) : nullptr;
+    float *d_pout = params_out ? hc.at<float>(o_pout) : nullptr, *d_corr = corr_out ? hc.at<float>(o_corr) : nullptr;
+    unsigned char* d_mask = mask_out ? hc.at<unsigned char>(o_mask) : nullptr;
     const size_t wb = (size_t)width * 4, sb = (size_t)stride * 4;
     if ((rc = stage_h2d(sl, d_in, sb, in, in_stride * 4, wb, height))) return rc;
     for (int b = 0; b < n_param_bands; ++b)
@@ -2016,7 +2025,7 @@ int hk_partial_mask(hk_ctx* ctx, const float* in, int64_t in_stride, int32_t in_
             return rc;
     if (src && (rc = stage_h2d(sl, d_src, sb, src, src_stride * 4, wb, height))) return rc;
     HK_HIP(hk::launch_partial_mask(d_in, in_nodata_mode, in_nodata, d_par, n_param_bands, stride * height, d_src, height,
-                                   width, stride, kh, kw, reinterpret_cast<unsigned short*>(base + o_cnt), d_pout, d_corr,
+                                   width, stride, kh, kw, hc.at<unsigned short>(o_cnt), d_pout, d_corr,
                                    d_mask, sl.stream));
     if (params_out)
         for (int b = 0; b < n_param_bands; ++b)
@@ -2102,7 +2111,7 @@ int hk_dev_free(hk_ctx* ctx, void* dptr) {
 int hk_memcpy_h2d(hk_ctx* ctx, void* dst, const void* src, size_t bytes) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
     if (!bytes) return HK_OK;
-    if (!dst || !src) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!dst || !src) return null_arg();
     HK_ENTER(ctx);
     std::lock_guard<std::mutex> lk(ctx->xfer_mu);
     int rc = stage_h2d(ctx->xfer, dst, bytes, src, bytes, bytes, 1);
@@ -2113,7 +2122,7 @@ int hk_memcpy_h2d(hk_ctx* ctx, void* dst, const void* src, size_t bytes) {
 int hk_memcpy_d2h(hk_ctx* ctx, void* dst, const void* src, size_t bytes) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
     if (!bytes) return HK_OK;
-    if (!dst || !src) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!dst || !src) return null_arg();
     HK_ENTER(ctx);
     std::lock_guard<std::mutex> lk(ctx->xfer_mu);
     int rc = stage_d2h(ctx->xfer, dst, bytes, src, bytes, bytes, 1);
@@ -2155,7 +2164,7 @@ static int check_job(hk_ctx* ctx, const hk_dev_job* job, bool allow_no_rows = fa
     if (((uintptr_t)job->src | (uintptr_t)job->ref | (uintptr_t)job->gain | (uintptr_t)job->offset |
          (uintptr_t)job->r2 | (uintptr_t)job->corr) & 15)
         return fail(HK_ERR_ARG, "device planes must be 16-byte aligned");
-    if (job->stream < 0 || job->stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (const int bad = check_stream(ctx, job->stream)) return bad;
     if (job->scratch) {
         if ((uintptr_t)job->scratch & 15) return fail(HK_ERR_ARG, "job scratch must be 16-byte aligned");
         if (job->scratch_bytes < hk_dev_job_scratch_bytes(job->n_bands, job->height, job->stride, job->band_stride))
@@ -2305,10 +2314,15 @@ static int ensure_stream_ws(hk_ctx* ctx, Slot& sl, size_t need) {
     return grow_slot_buf(sl, sl.norm_ws, sl.norm_ws_bytes, need);
 }
 
-static int check_nodata_mode(int32_t mode) {
-    return (mode == HK_NODATA_NONE || mode == HK_NODATA_NAN || mode == HK_NODATA_VALUE)
-               ? HK_OK
-               : fail(HK_ERR_ARG, "bad nodata mode %d", mode);
+// n_bands pairs of planes with the same strides on both sides
+static hk::CompareArgs compare_args(const float* src, const float* ref, int32_t height, int32_t width, int64_t stride, int64_t band_stride,
+                                    int32_t n_bands, int32_t src_nodata_mode, float src_nodata, int32_t ref_nodata_mode, float ref_nodata) {
+    hk::CompareArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.src = src, ca.ref = ref, ca.height = height, ca.width = width;
+    ca.src_stride = ca.ref_stride = stride, ca.src_band_stride = ca.ref_band_stride = band_stride, ca.n_bands = n_bands;
+    ca.src_nd_mode = src_nodata_mode, ca.ref_nd_mode = ref_nodata_mode, ca.src_nodata = src_nodata, ca.ref_nodata = ref_nodata;
+    return ca;
 }
 
 int hk_compare_sums_dev(hk_ctx* ctx, const hk_dev_job* job, int32_t src_nodata_mode, float src_nodata,
@@ -2317,17 +2331,13 @@ int hk_compare_sums_dev(hk_ctx* ctx, const hk_dev_job* job, int32_t src_nodata_m
     if (rc) return rc;
     DevEnter entered(ctx, job->stream);
     if (!sums_dev) return fail(HK_ERR_ARG, "sums_dev is NULL");
-    if ((rc = check_nodata_mode(src_nodata_mode)) || (rc = check_nodata_mode(ref_nodata_mode))) return rc;
+    if ((rc = check_nodata_modes(src_nodata_mode, ref_nodata_mode))) return rc;
     HK_ENTER(ctx);
     Slot& sl = ctx->slots[job->stream];
     rc = ensure_stream_ws(ctx, sl, hk::compare_workspace_bytes(job->n_bands));
     if (rc) return rc;
-    hk::CompareArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.src = job->src, ca.ref = job->ref, ca.height = job->height, ca.width = job->width;
-    ca.src_stride = ca.ref_stride = job->stride, ca.src_band_stride = ca.ref_band_stride = job->band_stride;
-    ca.n_bands = job->n_bands;
-    ca.src_nd_mode = src_nodata_mode, ca.ref_nd_mode = ref_nodata_mode, ca.src_nodata = src_nodata, ca.ref_nodata = ref_nodata;
+    const hk::CompareArgs ca = compare_args(job->src, job->ref, job->height, job->width, job->stride, job->band_stride, job->n_bands,
+                                            src_nodata_mode, src_nodata, ref_nodata_mode, ref_nodata);
     HK_HIP(hk::launch_compare_sums(ca, sl.norm_ws, sums_dev, sl.stream));
     return HK_OK;
 }
@@ -2336,37 +2346,27 @@ int hk_compare_sums(hk_ctx* ctx, const float* src, int64_t src_stride, int32_t s
                     const float* ref, int64_t ref_stride, int32_t ref_nodata_mode, float ref_nodata, int32_t height,
                     int32_t width, double sums_out[7]) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!src || !ref || !sums_out) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!src || !ref || !sums_out) return null_arg();
     if (height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d", height, width);
-    if (src_stride < width || ref_stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
-    int rc;
-    if ((rc = check_nodata_mode(src_nodata_mode)) || (rc = check_nodata_mode(ref_nodata_mode))) return rc;
+    int rc = check_strides(src_stride, width, ref_stride, width);
+    if (rc || (rc = check_nodata_modes(src_nodata_mode, ref_nodata_mode))) return rc;
     HK_ENTER(ctx);
-    const int64_t stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    const int64_t stride = row_align(width);
     const size_t plane = (size_t)stride * height * sizeof(float);
     SlabLayout L;
     const size_t o_src = L.take(plane), o_ref = L.take(plane), o_ws = L.take(hk::compare_workspace_bytes(1)), o_sums = L.take(256);
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    rc = ensure_dev(sl, L.total);
-    if (rc) return rc;
-    char* base = static_cast<char*>(sl.dev);
-    float* d_src = reinterpret_cast<float*>(base + o_src);
-    float* d_ref = reinterpret_cast<float*>(base + o_ref);
-    void* d_ws = base + o_ws;
-    double* d_sums = reinterpret_cast<double*>(base + o_sums);
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
+    float *d_src = hc.at<float>(o_src), *d_ref = hc.at<float>(o_ref);
+    double* d_sums = hc.at<double>(o_sums);
     const size_t wbytes = (size_t)width * sizeof(float);
-    if ((rc = stage_h2d(sl, d_src, stride * 4, src, src_stride * 4, wbytes, height))) return rc;
-    if ((rc = stage_h2d(sl, d_ref, stride * 4, ref, ref_stride * 4, wbytes, height))) return rc;
-    hk::CompareArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.src = d_src, ca.ref = d_ref, ca.height = height, ca.width = width;
-    ca.src_stride = ca.ref_stride = stride, ca.src_band_stride = ca.ref_band_stride = 0, ca.n_bands = 1;
-    ca.src_nd_mode = src_nodata_mode, ca.ref_nd_mode = ref_nodata_mode, ca.src_nodata = src_nodata, ca.ref_nodata = ref_nodata;
-    HK_HIP(hk::launch_compare_sums(ca, d_ws, d_sums, sl.stream));
-    HK_HIP(hipMemcpyAsync(sl.pin<double>(Slot::PIN_SUMS), d_sums, 7 * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
-    if ((rc = stage_finish(sl))) return rc;
-    memcpy(sums_out, sl.pin<double>(Slot::PIN_SUMS), 7 * sizeof(double));
+    if ((rc = stage_h2d(hc.sl, d_src, stride * 4, src, src_stride * 4, wbytes, height))) return rc;
+    if ((rc = stage_h2d(hc.sl, d_ref, stride * 4, ref, ref_stride * 4, wbytes, height))) return rc;
+    const hk::CompareArgs ca = compare_args(d_src, d_ref, height, width, stride, 0, 1, src_nodata_mode, src_nodata, ref_nodata_mode, ref_nodata);
+    HK_HIP(hk::launch_compare_sums(ca, hc.at(o_ws), d_sums, hc.sl.stream));
+    HK_HIP(hipMemcpyAsync(hc.sl.pin<double>(Slot::PIN_SUMS), d_sums, 7 * sizeof(double), hipMemcpyDeviceToHost, hc.sl.stream));
+    if ((rc = stage_finish(hc.sl))) return rc;
+    memcpy(sums_out, hc.sl.pin<double>(Slot::PIN_SUMS), 7 * sizeof(double));
     return HK_OK;
 }
 
@@ -2374,28 +2374,32 @@ int hk_compare_sums(hk_ctx* ctx, const float* src, int64_t src_stride, int32_t s
 static int check_param_stats(hk_ctx* ctx, const void* planes, const void* out, int32_t n_bands, int32_t height, int32_t width,
                              int64_t stride, int32_t nodata_mode) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!planes || !out) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!planes || !out) return null_arg();
     if (n_bands < 1 || height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d x %d", n_bands, height, width);
     if (n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", n_bands);
-    if (stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
-    return check_nodata_mode(nodata_mode);
+    const int rc = check_strides(stride, width);
+    return rc ? rc : check_nodata_mode(nodata_mode);
+}
+
+static hk::ParamStatsArgs param_stats_args(const float* planes, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                                           int64_t band_stride, int32_t nodata_mode, float nodata, double thresh) {
+    hk::ParamStatsArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.planes = planes, pa.height = height, pa.width = width, pa.stride = stride, pa.band_stride = band_stride;
+    pa.n_bands = n_bands, pa.nd_mode = nodata_mode, pa.nodata = nodata, pa.thresh = thresh;
+    return pa;
 }
 
 int hk_param_stats_dev(hk_ctx* ctx, const float* planes_dev, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
                        int64_t band_stride, int32_t stream, int32_t nodata_mode, float nodata, double thresh, double* stats_dev) {
     int rc = check_param_stats(ctx, planes_dev, stats_dev, n_bands, height, width, stride, nodata_mode);
-    if (rc) return rc;
-    if (band_stride < 0) return fail(HK_ERR_ARG, "band_stride is negative");
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (rc || (rc = check_band_strides(band_stride)) || (rc = check_stream(ctx, stream))) return rc;
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
     Slot& sl = ctx->slots[stream];
     rc = ensure_stream_ws(ctx, sl, hk::param_stats_workspace_bytes(n_bands));
     if (rc) return rc;
-    hk::ParamStatsArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.planes = planes_dev, pa.height = height, pa.width = width, pa.stride = stride, pa.band_stride = band_stride;
-    pa.n_bands = n_bands, pa.nd_mode = nodata_mode, pa.nodata = nodata, pa.thresh = thresh;
+    const hk::ParamStatsArgs pa = param_stats_args(planes_dev, n_bands, height, width, stride, band_stride, nodata_mode, nodata, thresh);
     HK_HIP(hk::launch_param_stats(pa, sl.norm_ws, stats_dev, sl.stream));
     return HK_OK;
 }
@@ -2406,27 +2410,21 @@ int hk_param_stats(hk_ctx* ctx, const float* plane, int64_t stride, int32_t noda
     int rc = check_param_stats(ctx, plane, stats_out, 1, height, width, stride, nodata_mode);
     if (rc) return rc;
     HK_ENTER(ctx);
-    const int64_t d_stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    const int64_t d_stride = row_align(width);
     SlabLayout L;
     const size_t o_plane = L.take((size_t)d_stride * height * sizeof(float)), o_ws = L.take(hk::param_stats_workspace_bytes(1)),
                  o_stats = L.take(256);
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    rc = ensure_dev(sl, L.total);
-    if (rc) return rc;
-    char* base = static_cast<char*>(sl.dev);
-    float* d_plane = reinterpret_cast<float*>(base + o_plane);
-    double* d_stats = reinterpret_cast<double*>(base + o_stats);
-    if ((rc = stage_h2d(sl, d_plane, d_stride * 4, plane, stride * 4, (size_t)width * sizeof(float), height))) return rc;
-    hk::ParamStatsArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.planes = d_plane, pa.height = height, pa.width = width, pa.stride = d_stride, pa.band_stride = 0, pa.n_bands = 1;
-    pa.nd_mode = nodata_mode, pa.nodata = nodata, pa.thresh = thresh;
-    HK_HIP(hk::launch_param_stats(pa, base + o_ws, d_stats, sl.stream));
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
+    float* d_plane = hc.at<float>(o_plane);
+    double* d_stats = hc.at<double>(o_stats);
+    if ((rc = stage_h2d(hc.sl, d_plane, d_stride * 4, plane, stride * 4, (size_t)width * sizeof(float), height))) return rc;
+    const hk::ParamStatsArgs pa = param_stats_args(d_plane, 1, height, width, d_stride, 0, nodata_mode, nodata, thresh);
+    HK_HIP(hk::launch_param_stats(pa, hc.at(o_ws), d_stats, hc.sl.stream));
     const size_t bytes = hk::PARAM_STATS_N * sizeof(double);
-    HK_HIP(hipMemcpyAsync(sl.pin<double>(Slot::PIN_STATS), d_stats, bytes, hipMemcpyDeviceToHost, sl.stream));
-    if ((rc = stage_finish(sl))) return rc;
-    memcpy(stats_out, sl.pin<double>(Slot::PIN_STATS), bytes);
+    HK_HIP(hipMemcpyAsync(hc.sl.pin<double>(Slot::PIN_STATS), d_stats, bytes, hipMemcpyDeviceToHost, hc.sl.stream));
+    if ((rc = stage_finish(hc.sl))) return rc;
+    memcpy(stats_out, hc.sl.pin<double>(Slot::PIN_STATS), bytes);
     return HK_OK;
 }
 
@@ -2446,12 +2444,12 @@ static int check_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32
                            int64_t stride, int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels,
                            void* const out[], const int64_t out_stride[], const int64_t out_band_stride[]) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!planes || !out || !out_stride || !out_band_stride) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!planes || !out || !out_stride || !out_band_stride) return null_arg();
     if (!hk::dtype_size(dtype)) return fail(HK_ERR_ARG, "bad dtype %d", dtype);
     if (n_bands < 1 || height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d x %d", n_bands, height, width);
     if (n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", n_bands);
-    if (stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
-    if (band_stride < 0) return fail(HK_ERR_ARG, "band_stride is negative");
+    int rc = check_strides(stride, width);
+    if (rc || (rc = check_band_strides(band_stride))) return rc;
     if (n_levels < 1 || n_levels > OVERVIEW_MAX_LEVELS) return fail(HK_ERR_ARG, "n_levels %d outside 1..%d", n_levels, OVERVIEW_MAX_LEVELS);
     for (int m = 1; m <= n_levels; ++m) {
         const int64_t wm = ((int64_t)width + (1ll << m) - 1) >> m;
@@ -2459,8 +2457,7 @@ static int check_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32
         if (out_stride[m - 1] < wm) return fail(HK_ERR_ARG, "level %d: row stride smaller than its width %lld", m, (long long)wm);
         if (out_band_stride[m - 1] < 0) return fail(HK_ERR_ARG, "level %d: band_stride is negative", m);
     }
-    int rc = check_nodata_mode(nodata_mode);
-    if (rc) return rc;
+    if ((rc = check_nodata_mode(nodata_mode))) return rc;
     if (nodata_mode == HK_NODATA_VALUE && dtype != HK_DTYPE_F32 && dtype != HK_DTYPE_F64) {
         const double lo[7] = {0, 0, 0, -32768.0, 0, -2147483648.0, 0}, hi[7] = {0, 255.0, 65535.0, 32767.0, 4294967295.0, 2147483647.0, 0};
         if (!(nodata >= lo[dtype] && nodata <= hi[dtype]) || nodata != floor(nodata))
@@ -2474,8 +2471,7 @@ int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t
                      void* const out_dev[], const int64_t out_stride[], const int64_t out_band_stride[], int32_t stream) {
     int rc = check_overviews(ctx, planes_dev, dtype, n_bands, height, width, stride, band_stride, nodata_mode, nodata, n_levels,
                              out_dev, out_stride, out_band_stride);
-    if (rc) return rc;
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (rc || (rc = check_stream(ctx, stream))) return rc;
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
     static_assert(sizeof(long long) == sizeof(int64_t), "strides are handed on as they are");
@@ -2509,7 +2505,6 @@ int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands
     const int64_t strip = overview_strip_rows(n_bands, height, width, (int)es, n_levels);
     const int64_t rows_max = strip < height ? strip : height;
     auto ceil_shift = [](int64_t v, int m) { return (v + ((int64_t)1 << m) - 1) >> m; };
-    auto row_align = [](int64_t w) { return (w + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN; };
     // device slab of one strip: the source planes, then every level's planes, rows padded to ROW_ALIGN elements
     SlabLayout L;
     const int64_t d_stride = row_align(width);
@@ -2521,11 +2516,10 @@ int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands
         l_band[m - 1] = l_stride[m - 1] * ceil_shift(rows_max, m);
         o_lev[m - 1] = L.take((size_t)n_bands * l_band[m - 1] * es);
     }
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    rc = ensure_dev(sl, L.total);
-    if (rc) return rc;
-    char* base = static_cast<char*>(sl.dev);
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
+    Slot& sl = hc.sl;
+    char* const base = hc.at(0);
     void* d_out[OVERVIEW_MAX_LEVELS];
     for (int m = 1; m <= n_levels; ++m) d_out[m - 1] = base + o_lev[m - 1];
     const char* h_src = static_cast<const char*>(planes);
@@ -2566,7 +2560,7 @@ static int deflate_shape(int32_t dtype, int32_t n_bands, int32_t height, int32_t
 }
 
 int hk_deflate_bound(int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int32_t tile, int64_t* n_tiles, int64_t* bytes) {
-    if (!n_tiles || !bytes) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!n_tiles || !bytes) return null_arg();
     return deflate_shape(dtype, n_bands, height, width, tile, n_tiles, bytes, nullptr);
 }
 
@@ -2584,12 +2578,10 @@ static int check_deflate(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t
                          int64_t stride, int64_t band_stride, int32_t tile, const void* out, int64_t out_capacity,
                          const int64_t* tile_offsets, const int64_t* tile_sizes, int64_t* n_tiles, int64_t* n_chunks) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!planes || !out || !tile_offsets || !tile_sizes) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!planes || !out || !tile_offsets || !tile_sizes) return null_arg();
     int64_t bytes = 0;
-    const int rc = deflate_shape(dtype, n_bands, height, width, tile, n_tiles, &bytes, n_chunks);
-    if (rc) return rc;
-    if (stride < width) return fail(HK_ERR_ARG, "row stride smaller than width");
-    if (band_stride < 0) return fail(HK_ERR_ARG, "band_stride is negative");
+    int rc = deflate_shape(dtype, n_bands, height, width, tile, n_tiles, &bytes, n_chunks);
+    if (rc || (rc = check_strides(stride, width)) || (rc = check_band_strides(band_stride))) return rc;
     if (out_capacity < bytes) return fail(HK_ERR_ARG, "out_capacity %lld is below hk_deflate_bound's %lld", (long long)out_capacity, (long long)bytes);
     return HK_OK;
 }
@@ -2602,8 +2594,7 @@ static int deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype,
     int64_t n_tiles = 0, n_chunks = 0;
     int rc = check_deflate(ctx, planes_dev, dtype, n_bands, height, width, stride, band_stride, tile, out_dev, out_capacity,
                            tile_offsets_dev, tile_sizes_dev, &n_tiles, &n_chunks);
-    if (rc) return rc;
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (rc || (rc = check_stream(ctx, stream))) return rc;
     if (n_chunks > 0x7FFFFFFFll) return fail(HK_ERR_ARG, "%lld chunks are more than one launch takes", (long long)n_chunks);
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
@@ -2658,17 +2649,17 @@ static int deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t
     // device slab of one group: its rows (padded to ROW_ALIGN elements: 16-byte loads are legal), the chunk slots, the streams,
     // offsets and sizes
     SlabLayout L;
-    const int64_t d_stride = (width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    const int64_t d_stride = row_align(width);
     const int64_t g_rows = std::min<int64_t>(g_down * tile, height);
     const size_t o_src = L.take((size_t)g_rows * d_stride * es);
     const size_t o_work = L.take(hk::deflate_workspace_bytes(g_chunks));
     const size_t o_out = L.take((size_t)g_bytes);
     const size_t o_off = L.take((size_t)(g_tiles + 1) * sizeof(int64_t));
     const size_t o_siz = L.take((size_t)g_tiles * sizeof(int64_t));
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    if ((rc = ensure_dev(sl, L.total))) return rc;
-    char* base = static_cast<char*>(sl.dev);
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
+    Slot& sl = hc.sl;
+    char* const base = hc.at(0);
     const char* h_src = static_cast<const char*>(planes);
     char* h_out = static_cast<char*>(out);
     int64_t used = 0, t0 = 0;
@@ -2680,8 +2671,8 @@ static int deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t
                                 stride * es, (size_t)width * es, rows)))
                 return rc;
             HK_HIP(hk::launch_deflate_tiles(base + o_src, (int)es, 1, (int)rows, width, d_stride, 0, tile, base + o_work,
-                                            reinterpret_cast<unsigned char*>(base + o_out), reinterpret_cast<long long*>(base + o_off),
-                                            reinterpret_cast<long long*>(base + o_siz), sl.stream, predictor));
+                                            hc.at<unsigned char>(o_out), hc.at<long long>(o_off), hc.at<long long>(o_siz), sl.stream,
+                                            predictor));
             // the offsets first (they say how many bytes there are), then only the compressed bytes
             if ((rc = stage_d2h(sl, tile_offsets + t0, 0, base + o_off, 0, (size_t)(nt + 1) * sizeof(int64_t), 1))) return rc;
             if ((rc = stage_d2h(sl, tile_sizes + t0, 0, base + o_siz, 0, (size_t)nt * sizeof(int64_t), 1))) return rc;
@@ -2744,7 +2735,7 @@ static int inflate_shape(const hk_inflate_layout* l, InflateShape* s) {
 }
 
 int hk_inflate_bound(const hk_inflate_layout* layout, int64_t* n_blocks, int64_t* raw_block_bytes, int64_t* work_bytes) {
-    if (!n_blocks || !raw_block_bytes || !work_bytes) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!n_blocks || !raw_block_bytes || !work_bytes) return null_arg();
     InflateShape s;
     const int rc = inflate_shape(layout, &s);
     if (rc) return rc;
@@ -2777,15 +2768,27 @@ static hk::InflateArgs inflate_args(const hk_inflate_layout* l, const InflateSha
     return a;
 }
 
+// what every form of a block image asks of its layout, pointers and strides: the part that needs no context ...
+static int check_blocks_image(const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
+                              const void* out, int64_t stride, int64_t band_stride, InflateShape* s) {
+    int rc = inflate_shape(layout, s);
+    if (rc) return rc;
+    if (!streams || !offsets || !sizes || !out) return null_arg();
+    if ((rc = check_strides(stride, layout->width))) return rc;
+    if (band_stride < 0 || (layout->spp > 1 && band_stride < stride * (layout->height - 1) + layout->width))
+        return fail(HK_ERR_ARG, "band_stride %lld is smaller than a plane", (long long)band_stride);
+    return HK_OK;
+}
+// ... behind the context, for the forms that run on the device
 static int check_inflate(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
                          const void* out, int64_t stride, int64_t band_stride, InflateShape* s) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    const int rc = inflate_shape(layout, s);
-    if (rc) return rc;
-    if (!streams || !offsets || !sizes || !out) return fail(HK_ERR_ARG, "NULL pointer argument");
-    if (stride < layout->width) return fail(HK_ERR_ARG, "row stride smaller than width");
-    if (band_stride < 0 || (layout->spp > 1 && band_stride < stride * (layout->height - 1) + layout->width))
-        return fail(HK_ERR_ARG, "band_stride %lld is smaller than a plane", (long long)band_stride);
+    return check_blocks_image(layout, streams, offsets, sizes, out, stride, band_stride, s);
+}
+// the block table of the host forms (host memory): no negative offset or size
+static int check_block_table(const int64_t* offsets, const int64_t* sizes, int64_t n_blocks) {
+    for (int64_t b = 0; b < n_blocks; ++b)
+        if (offsets[b] < 0 || sizes[b] < 0) return fail(HK_ERR_ARG, "block %lld: offset %lld, size %lld", (long long)b, (long long)offsets[b], (long long)sizes[b]);
     return HK_OK;
 }
 
@@ -2796,10 +2799,10 @@ static int blocks_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const 
     InflateShape s;
     int rc = check_inflate(ctx, layout, streams_dev, offsets_dev, sizes_dev, out_dev, stride, band_stride, &s);
     if (rc) return rc;
-    if (!work_dev || !status_dev) return fail(HK_ERR_ARG, "NULL pointer argument");
+    if (!work_dev || !status_dev) return null_arg();
     if ((uintptr_t)work_dev % 16) return fail(HK_ERR_ARG, "work_dev is not 16-byte aligned");
     if ((uintptr_t)out_dev % layout->sample_bytes) return fail(HK_ERR_ARG, "out_dev is not aligned to its samples");
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if ((rc = check_stream(ctx, stream))) return rc;
     if (s.n_blocks > 0x7FFFFFFFll) return fail(HK_ERR_ARG, "%lld blocks are more than one launch takes", (long long)s.n_blocks);
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
@@ -2834,9 +2837,7 @@ static int blocks_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void
                         void* out, int64_t stride, int64_t band_stride, int32_t* status, bool lzw) {
     InflateShape s;
     int rc = check_inflate(ctx, layout, streams, offsets, sizes, out, stride, band_stride, &s);
-    if (rc) return rc;
-    for (int64_t b = 0; b < s.n_blocks; ++b)
-        if (offsets[b] < 0 || sizes[b] < 0) return fail(HK_ERR_ARG, "block %lld: offset %lld, size %lld", (long long)b, (long long)offsets[b], (long long)sizes[b]);
+    if (rc || (rc = check_block_table(offsets, sizes, s.n_blocks))) return rc;
     HK_ENTER(ctx);
     const size_t es = (size_t)layout->sample_bytes;
     const int64_t bh = layout->block_h, per = s.across * s.down;
@@ -2868,7 +2869,7 @@ static int blocks_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void
     // device slab of one group: the compressed spans, offsets and sizes, the statuses, the slots, the group's rows of every band
     // (padded to ROW_ALIGN elements: 16-byte stores are legal)
     SlabLayout L;
-    const int64_t d_stride = (layout->width + ROW_ALIGN - 1) / ROW_ALIGN * ROW_ALIGN;
+    const int64_t d_stride = row_align(layout->width);
     const int64_t g_rows = std::min<int64_t>(g_down * bh, layout->height);
     const size_t o_in = L.take(in_bytes);
     const size_t o_off = L.take((size_t)g_blocks * sizeof(int64_t));
@@ -2876,10 +2877,10 @@ static int blocks_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void
     const size_t o_st = L.take((size_t)g_blocks * sizeof(int32_t));
     const size_t o_work = L.take((size_t)g_blocks * (size_t)s.slot);
     const size_t o_out = L.take((size_t)layout->spp * g_rows * d_stride * es);
-    SlotLease lease(ctx);
-    Slot& sl = lease.slot();
-    if ((rc = ensure_dev(sl, L.total))) return rc;
-    char* base = static_cast<char*>(sl.dev);
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
+    Slot& sl = hc.sl;
+    char* const base = hc.at(0);
     const char* h_in = static_cast<const char*>(streams);
     char* h_out = static_cast<char*>(out);
     std::vector<int64_t> g_off((size_t)g_blocks), g_siz((size_t)g_blocks);
@@ -2903,8 +2904,8 @@ static int blocks_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void
         if ((rc = stage_h2d(sl, base + o_off, 0, g_off.data(), 0, (size_t)nb * sizeof(int64_t), 1))) return rc;
         if ((rc = stage_h2d(sl, base + o_siz, 0, g_siz.data(), 0, (size_t)nb * sizeof(int64_t), 1))) return rc;
         hk::InflateArgs a = inflate_args(layout, s, (int32_t)rows);
-        a.streams = base + o_in, a.offsets = reinterpret_cast<const long long*>(base + o_off), a.sizes = reinterpret_cast<const long long*>(base + o_siz);
-        a.work = reinterpret_cast<unsigned char*>(base + o_work), a.status = reinterpret_cast<int*>(base + o_st);
+        a.streams = base + o_in, a.offsets = hc.at<long long>(o_off), a.sizes = hc.at<long long>(o_siz);
+        a.work = hc.at<unsigned char>(o_work), a.status = hc.at<int>(o_st);
         a.out = base + o_out, a.stride = d_stride, a.band_stride = rows * d_stride;
         HK_HIP(lzw ? hk::launch_lzw_image(a, nb, sl.stream) : hk::launch_inflate_image(a, nb, sl.stream));
         if ((rc = stage_d2h(sl, g_st.data(), 0, base + o_st, 0, (size_t)nb * sizeof(int32_t), 1))) return rc;
@@ -2941,15 +2942,10 @@ int hk_lzw_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* strea
 int hk_lzw_image_host(const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes, void* out,
                       int64_t stride, int64_t band_stride, int32_t* status) {
     InflateShape s;
-    const int rc = inflate_shape(layout, &s);
+    int rc = check_blocks_image(layout, streams, offsets, sizes, out, stride, band_stride, &s);
     if (rc) return rc;
-    if (!streams || !offsets || !sizes || !out) return fail(HK_ERR_ARG, "NULL pointer argument");
-    if (stride < layout->width) return fail(HK_ERR_ARG, "row stride smaller than width");
-    if (band_stride < 0 || (layout->spp > 1 && band_stride < stride * (layout->height - 1) + layout->width))
-        return fail(HK_ERR_ARG, "band_stride %lld is smaller than a plane", (long long)band_stride);
     if ((uintptr_t)out % layout->sample_bytes) return fail(HK_ERR_ARG, "out is not aligned to its samples");
-    for (int64_t b = 0; b < s.n_blocks; ++b)
-        if (offsets[b] < 0 || sizes[b] < 0) return fail(HK_ERR_ARG, "block %lld: offset %lld, size %lld", (long long)b, (long long)offsets[b], (long long)sizes[b]);
+    if ((rc = check_block_table(offsets, sizes, s.n_blocks))) return rc;
     std::vector<uint64_t> slot((size_t)s.slot / 8 + 2);   // (8-byte aligned for every sample size; the slot is a multiple of 16)
     hk::InflateArgs a = inflate_args(layout, s, layout->height);
     a.streams = streams, a.offsets = reinterpret_cast<const long long*>(offsets), a.sizes = reinterpret_cast<const long long*>(sizes);
@@ -3234,7 +3230,7 @@ int hk_comm_info(hk_ctx* ctx, int32_t* rank, int32_t* world_size) {
 
 int hk_comm_allreduce_f64_dev(hk_ctx* ctx, double* buf_dev, uint64_t count, int32_t stream) {
     if (!ctx || !buf_dev) return fail(HK_ERR_ARG, "NULL argument");
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (const int bad = check_stream(ctx, stream)) return bad;
     std::lock_guard<std::mutex> lk(ctx->comm_mu);
     if (!ctx->comm) return fail(HK_ERR_ARG, "the context has no communicator (hk_comm_init)");
     HK_ENTER(ctx);
@@ -3271,7 +3267,7 @@ int hk_block_norm_split_comm_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_
 int hk_synth_fill_dev(hk_ctx* ctx, float* src, float* ref, int32_t n_bands, int32_t height, int32_t width,
                       int64_t stride, int64_t band_stride, uint64_t seed, int32_t nodata_variant, int32_t stream) {
     if (!ctx || !src || !ref) return fail(HK_ERR_ARG, "NULL argument");
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (const int bad = check_stream(ctx, stream)) return bad;
     HK_ENTER(ctx);
     HK_HIP(hk::launch_synth_fill(src, ref, n_bands, height, width, stride, band_stride, seed, nodata_variant,
                                  ctx->slots[stream].stream));
@@ -3281,7 +3277,7 @@ int hk_synth_fill_dev(hk_ctx* ctx, float* src, float* ref, int32_t n_bands, int3
 int hk_stream_probe_dev(hk_ctx* ctx, const void* a, const void* b, void* out, size_t n_bytes, int32_t stream) {
     if (!ctx || !a || !b || !out) return fail(HK_ERR_ARG, "NULL argument");
     if (n_bytes % 16) return fail(HK_ERR_ARG, "n_bytes must be a multiple of 16");
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (const int bad = check_stream(ctx, stream)) return bad;
     HK_ENTER(ctx);
     HK_HIP(hk::launch_stream_probe(a, b, out, n_bytes, ctx->slots[stream].stream));
     return HK_OK;
@@ -3291,7 +3287,7 @@ int hk_debug_checksum_dev(hk_ctx* ctx, const float* plane, int64_t stride, int32
                           uint64_t* sum_out) {
     if (!ctx || !plane || !sum_out) return fail(HK_ERR_ARG, "NULL argument");
     if (height < 1 || width < 1 || stride < width) return fail(HK_ERR_ARG, "bad window %d x %d, stride %lld", height, width, (long long)stride);
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (const int bad = check_stream(ctx, stream)) return bad;
     HK_ENTER(ctx);
     DevEnter enter(ctx, stream);
     Slot& sl = ctx->slots[stream];
@@ -3313,7 +3309,7 @@ int hk_debug_checksum_dev(hk_ctx* ctx, const float* plane, int64_t stride, int32
 int hk_debug_inpaint_plane_dev(hk_ctx* ctx, float* plane_dev, const uint8_t* flags_dev, const float* gain_dev, const float* r2_dev,
                                float thresh, int32_t height, int32_t width, int64_t stride, int32_t mode, int32_t stream) {
     if (!ctx || !plane_dev) return fail(HK_ERR_ARG, "NULL argument");
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (const int bad = check_stream(ctx, stream)) return bad;
     if (mode < 0 || mode > 3) return fail(HK_ERR_ARG, "mode %d: 0 (the library's choice), 1 / 2 (packed search by rows / columns), 3 (general search only)", mode);
     // the bit planes' launches take one grid row per 64 raster rows
     if (height < 1 || width < 1 || height > 65535 * 64) return fail(HK_ERR_ARG, "bad shape %d x %d", height, width);
@@ -3368,7 +3364,7 @@ int hk_debug_inpaint_plane_dev(hk_ctx* ctx, float* plane_dev, const uint8_t* fla
 int hk_debug_cast_plane_dev(hk_ctx* ctx, int32_t to_typed, int32_t dtype, const void* src_dev, int64_t src_stride, void* dst_dev,
                             int64_t dst_stride, int32_t height, int32_t width, int32_t has_nodata, double nodata, int32_t stream) {
     if (!ctx || !src_dev || !dst_dev) return fail(HK_ERR_ARG, "NULL argument");
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (const int bad = check_stream(ctx, stream)) return bad;
     if (to_typed != 0 && to_typed != 1) return fail(HK_ERR_ARG, "to_typed %d: 0 (cast_in) or 1 (cast_out)", to_typed);
     const size_t es = hk::dtype_size(dtype);
     if (!es) return fail(HK_ERR_ARG, "unknown dtype %d", dtype);
@@ -3417,13 +3413,13 @@ int hk_event_destroy(hk_ctx* ctx, hk_event* ev) {
 }
 int hk_event_record(hk_ctx* ctx, hk_event* ev, int32_t stream) {
     if (!ctx || !ev) return fail(HK_ERR_ARG, "NULL argument");
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (const int bad = check_stream(ctx, stream)) return bad;
     HK_HIP(hipEventRecord(ev->ev, ctx->slots[stream].stream));
     return HK_OK;
 }
 int hk_stream_wait_event(hk_ctx* ctx, int32_t stream, hk_event* ev) {
     if (!ctx || !ev) return fail(HK_ERR_ARG, "NULL argument");
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (const int bad = check_stream(ctx, stream)) return bad;
     HK_ENTER(ctx);
     HK_HIP(hipStreamWaitEvent(ctx->slots[stream].stream, ev->ev, 0));
     return HK_OK;
@@ -3436,7 +3432,7 @@ int hk_event_elapsed_ms(hk_ctx* ctx, hk_event* start, hk_event* stop, float* ms)
 }
 int hk_stream_sync(hk_ctx* ctx, int32_t stream) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (stream < 0 || stream >= (int)ctx->slots.size()) return fail(HK_ERR_ARG, "bad stream index");
+    if (const int bad = check_stream(ctx, stream)) return bad;
     HK_HIP(hipStreamSynchronize(ctx->slots[stream].stream));
     return HK_OK;
 }

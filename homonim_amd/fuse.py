@@ -281,11 +281,8 @@ class RasterFuse:
         image -- ``proc_crs=src``: the source, otherwise the reference -- is first warped into the other's CRS
         (``_to_one_crs``), with the reference's warning.
         """
-        if inflate not in ('host', 'device'):
-            raise ValueError(f"`inflate` must be 'host' or 'device', not {inflate!r}")
-        inflater, lzw = None, _hk.lzw_image_host
-        if inflate == 'device' and any(isinstance(x, (str, os.PathLike)) for x in (src, ref)):
-            inflater, lzw = _hk.default_context().inflate_image, _hk.default_context().lzw_image
+        from_file = any(isinstance(x, (str, os.PathLike)) for x in (src, ref))
+        inflater, lzw = _hk.block_decoders(inflate, _hk.default_context if from_file else None)
         self._src_filename = self._ref_filename = None
         self._ref_descriptions = ()   # band descriptions of a reference opened from a file (name the parameter bands)
         if isinstance(src, (str, os.PathLike)):  # a GeoTIFF, as homonim.RasterFuse(src_filename, ref_filename, ...)

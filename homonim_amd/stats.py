@@ -83,8 +83,7 @@ class ParamStats:
         ``strip_bytes``: see ``STRIP_BYTES``.  ``inflate``: who inflates the file's DEFLATE blocks: 'host' (default) -- zlib on
         the reading thread; 'device' -- ``Context.inflate_image`` of the same context: the same pixels.  The LZW blocks of a file
         go to the library's host decoder (``_hk.lzw_image_host``) under 'host' and to ``Context.lzw_image`` under 'device'. """
-        if inflate not in ('host', 'device'):
-            raise ValueError(f"`inflate` must be 'host' or 'device', not {inflate!r}")
+        _hk.block_decoders(inflate)   # (refuses anything but 'host' and 'device')
         self._inflate = inflate
         self._param_filename = pathlib.Path(param_filename)
         header = utils.validate_param_image(self._param_filename)
@@ -167,9 +166,7 @@ class ParamStats:
             if not self._from_file:
                 raise IoError('The parameter raster has been closed')
             from homonim_amd.tiff import read_tiff
-            device = getattr(self, '_inflate', 'host') == 'device'
-            inflater = self._get_context().inflate_image if device else None
-            lzw = self._get_context().lzw_image if device else _hk.lzw_image_host
+            inflater, lzw = _hk.block_decoders(getattr(self, '_inflate', 'host'), self._get_context)
             array = read_tiff(self._param_filename, inflater=inflater, lzw=lzw).array
             self._array = np.ascontiguousarray(array, dtype=np.float32)
         return self

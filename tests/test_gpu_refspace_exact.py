@@ -288,6 +288,17 @@ def test_fused_upsample_apply_typed_io(ctx, src_dtype, nodata, out_dtype, method
          what=f'{src_dtype} -> {out_dtype} {method}')
 
 
+@pytest.mark.oracle
+def test_cast_output_and_parameters_leave_one_small_call_together(ctx):
+    """ a 12 x 20 source and a 6 x 10 reference, uint16 output with an output nodata and the parameters asked for (as _run always
+    does): the cast-out branch and the parameter branch of the call's tail in one call """
+    src_shape, down, ref_shape = (12, 20), (2., 0., 2., 0.), (6, 10)
+    src, ref = _pair(src_shape, down, ref_shape, 'small')
+    _, corr, valid, _ = _run(ctx, src * np.float32(200.), ref * np.float32(200.), down, 'bilinear', kernel_shape=(3, 3),
+                             out_dtype='uint16', out_nodata=65535, what='12x20 over 6x10 -> uint16')
+    assert (corr == 65535).sum() >= (~valid).sum() > 0
+
+
 # -- fused against unfused, many alignments --------------------------------------------------------------------------------
 def test_fused_equals_unfused_over_random_geometries(ctx):
     """ Device against device (hk_reproject is pinned to the oracle and to the exact statement elsewhere), so it is cheap: 30 random

@@ -221,6 +221,33 @@ def test_typed_source_and_output_equal_their_float32_casts(ctx, dtype):
     _typed_case(ctx, 'uint16', dtype, dtype, 0, True)
 
 
+def test_cast_output_and_parameters_leave_one_small_call_together(ctx):
+    """ A 12 x 20 source and a 6 x 10 reference, uint16 output with an output nodata AND the parameters asked for: the cast-out branch
+    and the parameter branch of the call's tail in one call.  The parameters and the float32 call are held to the oracle as in (2),
+    the uint16 block to the float32 call converted on the host as in (3). """
+    rng = np.random.default_rng(12)
+    src = rng.uniform(50., 200., (12, 20)).astype(np.float32)
+    ref = (1.25 * src.reshape(6, 2, 10, 2).mean(axis=(1, 3)) + 20. + rng.normal(0., 1., (6, 10))).astype(np.float32)
+    src[3, 4] = src[8, 15:17] = ref[4, 7] = 0.
+    mapping, kernel = (.5, 0., .5, 0.), (3, 3)
+    desc = _hk.make_desc('gain-offset', kernel, True, None, 0., 0.)
+    code = onp.RESAMPLING_CODES['cubic_spline']
+    params, corr, _ = ctx.srcspace_fit_apply(desc, src, ref, mapping, code, False, 3, True, out_dtype='uint16', out_nodata=65535)
+    params32, corr32, _ = ctx.srcspace_fit_apply(desc, src, ref, mapping, code, False, 3, True)
+    ref_us = onp.reproject(ref, 0., mapping, src.shape, dst_nodata=np.nan, resampling='cubic_spline')
+    exp_params, _ = onp.fit('gain-offset', src, 0., ref_us, np.nan, kernel, True, None)
+    exp_params = exp_params.copy()
+    exp_params[:, ~onp.mask_of(src, 0.)] = np.nan
+    exp_corr = onp.apply(src, exp_params)
+    assert (np.isnan(params32) == np.isnan(exp_params)).all() and (np.isnan(corr32) == np.isnan(exp_corr)).all()
+    ok = ~np.isnan(exp_corr)
+    assert ok.sum() > 0.9 * ok.size
+    assert np.max(np.abs(corr32[ok] - exp_corr[ok]) / np.maximum(np.abs(exp_corr[ok]), 1e-6)) < 1e-5
+    assert params.shape == (3, 12, 20) and np.array_equal(params, params32, equal_nan=True)
+    assert corr.dtype == np.uint16 and np.array_equal(corr, convert_dtype(corr32, 'uint16', 65535))
+    assert (corr == 65535).sum() == np.isnan(corr32).sum() >= 3
+
+
 # -- 4 -------------------------------------------------------------------------------------------------------------------------------
 def test_raster_fuse_process_across_blocks(ctx):
     """ RasterFuse.process(proc_crs=src) on a uint16 pair cut into blocks with halos: the blocks travel in the rasters' own dtype,

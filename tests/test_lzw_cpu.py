@@ -247,6 +247,44 @@ def test_bad_arguments_are_refused_before_anything_else_is_looked_at(lib):
     assert lib.hk_lzw_image_host(C.byref(lay), None, off, siz, buf, 270, 300 * 270, status) == _hk.HK_ERR_ARG and b'NULL' in lib.hk_last_error()
     assert lib.hk_lzw_image_host(C.byref(lay), buf, off, siz, buf, 269, 300 * 270, status) == _hk.HK_ERR_ARG and b'stride' in lib.hk_last_error()
 
+    # The host decoder has no context in front of its checks: every refusal of a layout, a pointer, a stride or a band stride, one
+    # wrong thing at a time, with the status and the whole text (the checks it shares with hk_lzw_image / hk_inflate_image)
+    def refused(layout, streams=buf, offsets=off, sizes=siz, out=buf, stride=270, band_stride=300 * 270):
+        lay = None if layout is None else C.byref(_hk._inflate_layout(layout))
+        assert lib.hk_lzw_image_host(lay, streams, offsets, sizes, out, stride, band_stride, status) == _hk.HK_ERR_ARG
+        return lib.hk_last_error().decode()
+
+    assert refused(None) == 'layout is NULL'
+    assert refused(good._replace(sample_bytes=3)) == 'sample_bytes 3 is not 1, 2, 4 or 8'
+    assert refused(good._replace(spp=0)) == 'empty raster 0 x 300 x 270'
+    assert refused(good._replace(height=0)) == 'empty raster 3 x 0 x 270'
+    assert refused(good._replace(block_w=0)) == 'empty block 256 x 0'
+    assert refused(good._replace(predictor=3)) == 'predictor 3 is not 1 or 2'
+    assert refused(good._replace(tiled=2)) == 'tiled and separate are 0 or 1'
+    assert refused(good._replace(separate=-1)) == 'tiled and separate are 0 or 1'
+    assert refused(good._replace(tiled=0)) == 'a strip is as wide as the image: block_w 256, width 270'
+    assert refused(good._replace(block_w=65536, block_h=32768)) == \
+        'a block of 32768 x 65536 x 1 samples of 1 bytes is more than 1073741824 bytes'
+    assert refused(good._replace(height=2**31 - 1, width=2**31 - 1, block_w=1, block_h=1)) == \
+        'too many blocks: 3 x 2147483647 x 2147483647 of 16 bytes'
+    for null in ('streams', 'offsets', 'sizes', 'out'):
+        assert refused(good, **{null: None}) == 'NULL pointer argument'
+    assert refused(good, stride=269) == 'row stride smaller than width'
+    assert refused(good, band_stride=-1) == 'band_stride -1 is smaller than a plane'
+    assert refused(good, band_stride=300 * 270 - 1) == 'band_stride 80999 is smaller than a plane'
+    assert refused(good, stride=280, band_stride=299 * 280 + 269) == 'band_stride 83989 is smaller than a plane'
+    wide = np.zeros(3 * 300 * 270 + 1, np.uint16)
+    assert refused(good._replace(sample_bytes=2), out=C.c_void_p(wide.ctypes.data + 1)) == 'out is not aligned to its samples'
+    off[5] = -1
+    assert refused(good) == 'block 5: offset -1, size 0'
+    off[5], siz[7] = 0, -2
+    assert refused(good) == 'block 7: offset 0, size -2'
+    siz[7] = 0
+    # ... and with nothing wrong the same arguments decode: twelve empty streams are twelve refused blocks, not refused arguments
+    out = np.zeros(3 * 300 * 270, np.uint8)
+    assert lib.hk_lzw_image_host(C.byref(lay), buf, off, siz, out.ctypes.data_as(C.c_void_p), 270, 300 * 270, status) == _hk.HK_ERR_ARG
+    assert lib.hk_last_error().startswith(b'lzw: block 0 is refused') and all(status)
+
 
 # ---- 5. files outside the hook's contract, and the product's switch ----------------------------------------------------------
 def test_big_endian_and_predictor_3_files_are_read_here_hook_or_not(tmp_path):

@@ -27,15 +27,15 @@ def code_object(obj, tmp):
         if f.startswith(os.path.basename(obj) + '.0.'):
             os.replace(os.path.join(src_dir, f), os.path.join(tmp, f))
     cos = [f for f in os.listdir(tmp) if 'gfx950' in f]
-    if not cos:
-        raise RuntimeError(f'no gfx950 code object in {obj}')
-    return os.path.join(tmp, cos[0])
+    return os.path.join(tmp, cos[0]) if cos else None   # (None: a host-only object, hk_api.o)
 
 
 def symbols(obj):
-    """ {symbol: instruction text}, {kernel: figures line} of the gfx950 code object of `obj` """
+    """ {symbol: instruction text}, {kernel: figures line} of the gfx950 code object of `obj`; both empty for an object without one """
     with tempfile.TemporaryDirectory() as tmp:
         co = code_object(obj, tmp)
+        if co is None:
+            return {}, {}
         dis = subprocess.run([f'{LLVM}/llvm-objdump', '-d', co], capture_output=True, text=True, check=True).stdout
         notes = subprocess.run([f'{LLVM}/llvm-readelf', '--notes', co], capture_output=True, text=True, check=True).stdout
     text, name = {}, None
