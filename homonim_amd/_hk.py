@@ -99,7 +99,9 @@ ABI_VERSION = 12  # HK_ABI_VERSION of the include/homonim_hk.h these mirrors wer
 # entry points declared in include/homonim_hk_devtools.h (measurement / test aids), the rest in include/homonim_hk.h
 DEVTOOLS = ('hk_synth_fill_dev', 'hk_stream_probe_dev', 'hk_debug_stage_stamps', 'hk_r2_certificate_constants', 'hk_debug_staging_counters',
             'hk_debug_build_ledger', 'hk_debug_checksum_dev', 'hk_debug_fail_after_d2h', 'hk_debug_inpaint_plane_dev',
-            'hk_debug_cast_plane_dev')
+            'hk_debug_cast_plane_dev', 'hk_debug_fit_build')
+# HK_FIT_PLANE_*: the planes a fused launch is handed (hk_debug_fit_build)
+FIT_PLANES = {'gain': 1, 'offset': 2, 'r2': 4, 'corr': 8, 'fail_count': 16, 'flags': 32, 'offset_in': 64, 'jobs': 128}
 
 SIGNATURES = {
     'hk_abi_version': (C.c_int, []),
@@ -223,6 +225,8 @@ SIGNATURES = {
     'hk_debug_stage_stamps': (C.c_int, [C.c_void_p, _P(C.c_uint64), C.c_int32]),
     'hk_debug_staging_counters': (C.c_int, [_P(C.c_uint64), C.c_int32]),
     'hk_debug_build_ledger': (C.c_int, [C.c_char_p, C.c_size_t, _P(C.c_size_t), C.c_int32]),
+    'hk_debug_fit_build': (C.c_int, [_P(FitDesc), C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_char_p, C.c_size_t]),
     'hk_debug_fail_after_d2h': (C.c_int, [C.c_int32]),
     'hk_debug_checksum_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint64)]),
     'hk_debug_inpaint_plane_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
@@ -1429,6 +1433,17 @@ def build_ledger(reset: bool = False) -> dict:
         name, _, count = line.rpartition('\t')
         out[name] = out.get(name, 0) + int(count)
     return out
+
+
+def fit_build(desc, shape, planes, phase: int = 0, force_ring=None, force_general: bool = False) -> str:
+    """ The ledger name of the build of the fused kernel a launch gets (hk_debug_fit_build; test aid, no device): ``shape`` =
+    (bands, height, width) of the job, ``planes`` = names out of FIT_PLANES, ``phase`` 0 the one launch / 1 the certificate build /
+    2 its list launch.  ValueError where the launch has no build. """
+    name = C.create_string_buffer(88)
+    bits = sum(FIT_PLANES[p] for p in planes)
+    _check(load_library().hk_debug_fit_build(C.byref(desc), int(shape[1]), int(shape[2]), int(shape[0]), bits, int(phase),
+                                             -1 if force_ring is None else int(force_ring), int(bool(force_general)), name, len(name)))
+    return name.value.decode()
 
 
 def device_pci_bus_id(device: int) -> str:

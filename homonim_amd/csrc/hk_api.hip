@@ -915,7 +915,7 @@ void fill_args(hk::FitArgs& a, const hk_fit_desc* d, const LaunchPolicy& lp) {
     // ring mode (hk_fit_kernel.h): full LDS ring while it leaves room for >= 11 waves per CU (kh <= 5), centre-only ring up
     // to kh = 39 (1 KB per wave and row of the half-height; 33 - 39 rows: 3 - 13 % faster than re-loading, from 41 rows
     // slower -- headline workload, round 5), everything re-loaded beyond -- that path exists
-    // for kernels from 9 wide only (launch_rw), narrower ones keep the centre ring whatever their height (kh <= 255: 128 KB)
+    // for kernels from 9 wide only (hk_kernels.h fit_build_exists), narrower ones keep the centre ring whatever their height (kh <= 255: 128 KB)
     a.use_ring = (d->kh <= 5 && d->kw <= 7) ? 1 : ((d->kh <= 39 || d->kw <= 7) ? 2 : 0);
     // The memory-bound builds (no R2) prefer the full ring well beyond that: re-loading the leaving rows costs them more than
     // the waves the ring displaces -- gain 7x7 / 9x9 / 11x11 / 15x15 at 16384^2 x 4: 3.25 / 3.40 / 3.45 / 3.95 -> 2.54 / 2.58 /
@@ -1016,16 +1016,18 @@ static int ensure_inpaint_scratch(Slot& sl, size_t plane, int height, long long 
 // failing pixel once; an empty bit plane (clean rasters) costs the list launch a few microseconds.  (The certificate has builds for
 // the full and the centre ring, its constants assume window counts below 2^16, and the in-painting's source flags do not fit its
 // registers: other shapes, R2 / gain output and launches that leave the in-painting's inputs run the complete build over the
-// whole grid.)
-static bool cert_list_eligible(const hk::FitArgs& a, const hk_fit_desc* desc) {
-    return desc->model == HK_MODEL_GAIN_OFFSET && a.has_thresh && a.fail_count && !a.r2 && !a.gain && !a.flag && !a.offset_in &&
-           !a.jobs && (a.use_ring == 1 || a.use_ring == 2) && (long long)desc->kh * desc->kw <= 65535;
+// whole grid: hk::choose_fit_build says which.)
+static bool cert_list_eligible(hk::FitArgs a, const hk_fit_desc* desc, bool r2) {
+    a.cert_only = 1, a.list_mode = 0;
+    const bool cert = hk::fit_build_exists(hk::choose_fit_build(a, desc->model, r2));
+    a.cert_only = 0, a.list_mode = 1;
+    return cert && hk::fit_build_exists(hk::choose_fit_build(a, desc->model, r2));
 }
 
 // the fused launch of one job (fill_args + fill_grid done): certificate build + list launch where they apply, the one build otherwise
 static int launch_fit(hk_ctx* ctx, Slot& sl, hk::FitArgs& a, const hk_fit_desc* desc, bool r2) {
     a.cert_only = 0, a.open_rows = nullptr, a.list_mode = 0;
-    if (!cert_list_eligible(a, desc)) {
+    if (!cert_list_eligible(a, desc, r2)) {
         HK_HIP(hk::launch_fit_apply(a, desc->model, r2, sl.stream));
         return HK_OK;
     }
@@ -2096,6 +2098,34 @@ int hk_debug_build_ledger(char* buf, size_t len, size_t* needed, int32_t reset) 
     return HK_OK;
 }
 
+int hk_debug_fit_build(const hk_fit_desc* desc, int32_t height, int32_t width, int32_t n_bands, uint32_t planes, int32_t phase,
+                       int32_t force_ring, int32_t force_general, char* name, size_t len) {
+    const int rc = validate_desc(desc);
+    if (rc) return rc;
+    if (!name || height < 1 || width < 1 || n_bands < 1 || planes > 255u || phase < 0 || phase > 2 || force_ring < -1 || force_ring > 3)
+        return fail(HK_ERR_ARG, "hk_debug_fit_build: NULL name, empty job, or unknown planes / phase / ring");
+    LaunchPolicy lp;
+    lp.force_general = force_general != 0;
+    if (force_ring >= 0) lp.use_ring = force_ring;
+    float* const set = reinterpret_cast<float*>(sizeof(float4));  // (never read: the chooser asks which planes there are)
+    auto plane = [&](unsigned bit) { return (planes & bit) ? set : nullptr; };
+    hk::FitArgs a;
+    memset(&a, 0, sizeof(a));
+    a.gain = plane(1), a.offset = plane(2), a.r2 = plane(4), a.corr = plane(8), a.offset_in = plane(64);
+    a.fail_count = reinterpret_cast<unsigned long long*>(plane(16)), a.flag = reinterpret_cast<unsigned char*>(plane(32));
+    a.flag_in = a.offset_in ? reinterpret_cast<const unsigned char*>(set) : nullptr;
+    a.jobs = reinterpret_cast<const hk::FitJob*>(plane(128));
+    a.height = height, a.width = width, a.n_bands = n_bands;
+    fill_args(a, desc, lp);
+    const bool r2 = needs_r2(desc) && !a.offset_in;  // (the closing pass runs the build without the R2 work: inpaint_band)
+    if (phase && !cert_list_eligible(a, desc, r2)) return fail(HK_ERR_ARG, "this launch has no certificate build + list launch");
+    a.cert_only = phase == 1, a.list_mode = phase == 2;
+    const hk::FitBuild b = hk::choose_fit_build(a, desc->model, r2);
+    if (!hk::fit_build_exists(b)) return fail(HK_ERR_ARG, "this launch has no build of the fused kernel");
+    hk::fit_build_name(name, len, b);
+    return HK_OK;
+}
+
 int hk_dev_alloc(hk_ctx* ctx, size_t bytes, void** dptr) {
     if (!ctx || !dptr) return fail(HK_ERR_ARG, "NULL argument");
     HK_ENTER(ctx);
@@ -3070,7 +3100,7 @@ int hk_fit_apply_batch_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_jo
             (!job->corr) != (!jobs[0].corr) || (!job->fail_count) != (!jobs[0].fail_count) || (!job->scratch) != (!jobs[0].scratch))
             return fail(HK_ERR_ARG, "the jobs of a batch ask for the same set of outputs (job %d differs from job 0)", j);
     }
-    if (!hk::fit_batch_supported(desc->model, needs_r2(desc))) {
+    if (!hk::fit_batch_build(desc->model, needs_r2(desc))) {
         // builds without the job-table look-up (hk_kernels.h fit_batch_build): one launch per job, in order, same results
         for (int32_t j = 0; j < n_jobs; ++j) {
             rc = hk_fit_apply_dev(ctx, desc, &jobs[j]);
@@ -3103,7 +3133,7 @@ int hk_fit_apply_batch_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_jo
         }
     }
     // (only models without the r2 mask have builds with the job-table look-up: no certificate, no in-painting inputs here)
-    const int wpb = hk::fit_lockstep_waves();
+    const int wpb = hk::WPB_MEM;
     std::vector<hk::FitJob> table((size_t)n_jobs);
     long long groups[2] = {0, 0}, total_px = 0;
     for (int32_t j = 0; j < n_jobs; ++j) {

@@ -1,5 +1,5 @@
 // hk_fit_kernel.h -- the fused fit(+apply) kernel template of the homonim kernel-model hot path (gfx950 / CDNA4) and its launch
-// ladder.  Included by hk_fit_tu.hip (one translation unit per MODEL x R2, compiled in parallel by homonim_amd/build.py) and by
+// table.  Included by hk_fit_tu.hip (one translation unit per MODEL x R2, compiled in parallel by homonim_amd/build.py) and by
 // hk_kernels.hip (dispatch, self-test; with -DHK_FIT_ONE_TU every instantiation -- the A/B tooling under tools/).
 //
 // Reference behaviour being reproduced: homonim/kernel_model.py (v0.4.3)
@@ -21,6 +21,7 @@
 #include "hk_kernels.h"
 
 #include <type_traits>
+#include <utility>
 
 namespace hk {
 
@@ -28,7 +29,7 @@ namespace hk {
 // HISTORY.md), not kept behind a macro:
 //   HK_STAMPS                        in-kernel stage stamps (below; tools/stage_stamps.py)
 //   HK_ABLATE=bits                   timing builds with one ingredient taken out (below; FLOOR.md section 3)
-//   HK_DEV_SUBSET, HK_DEV_SUBSET15   development builds that instantiate a few kernels only (launch_rw)
+//   HK_DEV_SUBSET, HK_DEV_SUBSET15   development builds that instantiate a few kernels only (hk_kernels.h fit_build_exists)
 //   HK_FIT_ONE_TU                    every instantiation in the translation unit of hk_kernels.hip (the A/B tooling under tools/)
 //   HK_TU_MODEL, HK_TU_R2            the MODEL x R2 that one translation unit of hk_fit_tu.hip instantiates (homonim_amd/build.py)
 
@@ -291,7 +292,7 @@ __device__ __forceinline__ double bperm_at(double v, int addr) {
 // instead of 2 W - 2 (31 wide: 16 ds_bpermute instead of 20 per float64 quantity).  31 wide 6.55 -> 6.28 ms, on NaN-nodata rasters
 // 7.05 -> 6.77, 33 - 37 wide -7 ... -8 %; even W gains nothing (the pairs save little and A delays the first fetch), and with the
 // decision taken inside the row loop the widths that do not pair ran 2 - 3 % slower (profiles/r06b_ab_pairs.txt): the paired
-// form is a BUILD of its own (RW = -5 - E instead of -1 - E; the centre-ring builds of every model, launch_wide).  As builds of
+// form is a BUILD of its own (RW = -5 - E instead of -1 - E; the centre-ring builds of every model, choose_fit_build).  As builds of
 // their own (profiles/r06b_ab_pair_builds.txt): gain-offset + r2 mask 31 wide 6.28 -> 5.88 ms, on NaN-nodata rasters 6.89 -> 6.41,
 // 33 / 35 wide 6.92 / 7.72 -> 6.25 / 6.79; without the r2 mask 31 wide 5.65 -> 5.19; gain-blk-offset 31 wide -3 %, gain 35 wide -6 %.
 __host__ __device__ constexpr int wide_e(int rw_code) { return rw_code >= -PX ? -1 - rw_code : -1 - PX - rw_code; }  // rw mod 4 of a wide build
@@ -789,7 +790,7 @@ constexpr int FIT_MIN_WAVES = 3;       // waves per SIMD the register allocator 
 // 2.70 -> 2.55 ms, gain-blk-offset 5x5 4.57 -> 4.34 ms (8 waves: 2.51 / 4.38; configs[1]'s smaller raster prefers 4).
 // Not for the VALU-bound gain-offset builds with the R2 work (their waves would only wait for each other: 0 to +2 %) and not for the tall
 // kernels that re-load their leaving rows (15x15: +14 %, the re-loads of a whole workgroup then collide).
-constexpr int WPB_MEM = 4;
+// (WPB_MEM = 4: hk_kernels.h)
 // (SPLIT_RING_ROWS / SPLIT_RING_ROWS_BLK, hk_kernels.h: register rows of the split ring -- 7 = kernels up to 15 rows tall; the
 // gain-blk-offset builds use the mode up to 11 rows only (hk_api.hip fill_args) and hold 5: 16 VGPRs less, no spill)
 
@@ -916,7 +917,7 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
     // The HBM-bound kernels without R2 (gain, gain-blk-offset) read the leaving row from LDS one iteration AHEAD (its
     // latency leaves the loop-carried path), which also frees its slot before the entering row is written: their ring has
     // kh - 1 rows (8 KB instead of 10 KB per wave at 5x5 = 20 instead of 16 waves per CU).
-    constexpr bool RING_AHEAD = ring && MODEL != 2 && !R2;
+    constexpr bool RING_AHEAD = fit_ring_ahead(MODEL, R2, RING);
     const int ring_rows = ring ? (RING_AHEAD ? (kh > 1 ? kh - 1 : 1) : kh) : ((cring || sring) ? rh + 1 : 0);
     constexpr bool ring2p = ring || sring;   // the LDS ring holds both planes (source + reference) of its rows
     // RING 1: [slot][s|r][lane]; RING 2: [slot][lane] (s only); one ring per wave of the workgroup
@@ -1129,7 +1130,7 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
 #define HK_RG_SWAP(k) mid_s = rg_s[k], mid_r = rg_r[k], rg_s[k] = ns, rg_r[k] = nr
 #define HK_RG_CASE(k) case k: HK_RG_SWAP(k); break;
             static_assert(SRING_MAX >= 5 && SRING_MAX <= 8, "register slots of the split ring");
-            switch (slot_r) {   // slot_r < rh <= SRING_MAX (launch_rw); the last slot is the default
+            switch (slot_r) {   // slot_r < rh <= SRING_MAX (choose_fit_build); the last slot is the default
                 HK_RG_CASE(0) HK_RG_CASE(1) HK_RG_CASE(2) HK_RG_CASE(3)
                 case 4: if constexpr (SRING_MAX > 5) { HK_RG_SWAP(4); break; }
                 case 5: if constexpr (SRING_MAX > 6) { HK_RG_SWAP(5 < SRING_MAX ? 5 : 0); break; }
@@ -1581,7 +1582,7 @@ __device__ __forceinline__ void fit_unit(const FitArgs& a, const int band, const
                         else return reinterpret_cast<float4*>(reinterpret_cast<char*>(plane + row_off) + xbytes);
                     };
                     if (a.corr && !((HK_ABLATE & 8) && c[0] != 123.456f)) store4_nt(at(a.corr), make_float4(c[0], c[1], c[2], c[3]));
-                    if constexpr (!CERT_ONLY) {  // (the certificate build serves launches without a gain / R2 plane: launch_one)
+                    if constexpr (!CERT_ONLY) {  // (the certificate build serves launches without a gain / R2 plane: choose_fit_build)
                         if (a.gain) store4_nt(at(a.gain), masked4(g));
                     }
                     if (a.offset) store4_nt(at(a.offset), masked4(o));
@@ -1727,7 +1728,6 @@ fit_list_kernel(const FitArgs a) {
     }
 }
 
-
 // LDS bytes of one wave: the row ring of the mode (see fit_apply_kernel).  Validity travels inside the source plane
 // (RING_SENTINEL) and the 1/N table sits in global memory, so every build of a kernel shape needs the same amount: 10 KB at
 // 5x5 = 16 waves per CU (8 KB = 20 waves for the kernels that read the leaving row one iteration ahead).
@@ -1739,187 +1739,76 @@ inline size_t fit_lds_bytes_of(int kh, int ring_mode, bool ahead) {
 }
 
 // launch ledger (hk_kernels.h): one record per build of the fused kernel, on the list from the moment the library is loaded
-template <int MODEL, bool R2, int RW, bool DENSE, int RING, bool CERT_ONLY, int WPB, bool BATCH>
+template <int MODEL, bool R2, int RW, bool DENSE, int RING, bool CERT_ONLY, int WPB, bool BATCH, bool LIST>
 struct FitBuildRecord {
     static BuildRecord rec;
 };
-template <int MODEL, bool R2, int RW, bool DENSE, int RING, bool CERT_ONLY, int WPB, bool BATCH>
-BuildRecord FitBuildRecord<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, BATCH>::rec{MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, BATCH};
+template <int MODEL, bool R2, int RW, bool DENSE, int RING, bool CERT_ONLY, int WPB, bool BATCH, bool LIST>
+BuildRecord FitBuildRecord<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, BATCH, LIST>::rec{
+    FitBuild{MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, BATCH, LIST}};
 
-template <int MODEL, bool R2, int RW, bool DENSE, int RING>
-struct ListBuildRecord {
-    static BuildRecord rec;
-};
-template <int MODEL, bool R2, int RW, bool DENSE, int RING>
-BuildRecord ListBuildRecord<MODEL, R2, RW, DENSE, RING>::rec{"fit_list_kernel", MODEL, R2, RW, DENSE, RING};
-
-template <int MODEL, bool R2, int RW, bool DENSE, int RING, bool CERT_ONLY, int WPB>
-static hipError_t launch_wpb(const FitArgs& a, size_t lds, hipStream_t stream) {
-    if (lds * WPB > 64 * 1024) {  // forced LDS ring on a tall kernel (testing): raise the 64 KiB dynamic-LDS default
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_apply_kernel<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+// The launch of every build: raise the 64 KiB dynamic-LDS default where the shape needs more (a forced LDS ring on a tall kernel:
+// testing), count the launch, launch
+template <typename K>
+static hipError_t launch_counted(K kernel, BuildRecord& rec, int grid, int block, size_t lds, const FitArgs& a, hipStream_t stream) {
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
     }
-    if constexpr (MODEL == 2 && R2 && !CERT_ONLY && WPB == 1 && (RING == 1 || RING == 2)) {
-        // list launch (the rows the certificate build marked): a persistent grid of single waves; an empty bit plane costs microseconds
-        if (a.list_mode) {
-            if (lds > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_list_kernel<MODEL, R2, RW, DENSE, RING>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return e;
-            }
-            ListBuildRecord<MODEL, R2, RW, DENSE, RING>::rec.hit();
-            hipLaunchKernelGGL((fit_list_kernel<MODEL, R2, RW, DENSE, RING>), dim3(256 * 8), dim3(WAVE), lds, stream, a);
-            return hipGetLastError();
-        }
-    }
-    if (a.list_mode) return hipErrorInvalidValue;  // (hk_api.hip asks for a list launch only where the certificate build exists)
-    int grid = (a.n_strips + WPB - 1) / WPB * a.n_segs * a.n_bands;  // workgroups of WPB adjacent strips
-    constexpr bool CAN_BATCH = fit_batch_build(MODEL, R2) && !CERT_ONLY;
-    if (a.jobs) {
-        if (!CAN_BATCH) return hipErrorInvalidValue;  // hk_api.hip asks fit_batch_build() first
-        grid = a.batch_groups[WPB > 1 ? 1 : 0];
-    }
-    if (a.xcd_remap) {
-        const int g = a.xcd_remap / WPB > 0 ? a.xcd_remap / WPB : 1;
-        grid = (grid + 8 * g - 1) / (8 * g) * (8 * g);
-    }
-    // a.lds_pad: extra dynamic LDS per wave that nothing uses -- it only lowers the number of resident waves per CU
-    if constexpr (CAN_BATCH) {
-        if (a.jobs) {
-            if (lds * WPB > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_apply_kernel<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return e;
-            }
-            FitBuildRecord<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, true>::rec.hit();
-            hipLaunchKernelGGL((fit_apply_kernel<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, true>), dim3(grid), dim3(WAVE * WPB),
-                               (lds + (size_t)a.lds_pad) * WPB, stream, a);
-            return hipGetLastError();
-        }
-    }
-    FitBuildRecord<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, false>::rec.hit();
-    hipLaunchKernelGGL((fit_apply_kernel<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB>), dim3(grid), dim3(WAVE * WPB),
-                       (lds + (size_t)a.lds_pad) * WPB, stream, a);
+    rec.hit();
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, stream, a);
     return hipGetLastError();
 }
 
-template <int MODEL, bool R2, int RW, bool DENSE, int RING, bool CERT_ONLY>
-static hipError_t launch_build(const FitArgs& a, hipStream_t stream) {
-    const size_t lds = fit_lds_bytes_of(2 * a.rh + 1, RING, RING == 1 && MODEL != 2 && !R2);
-    // every build without the R2 work (gain-offset without a threshold gains 3 % as well: 2.77 -> 2.68 ms)
-    constexpr bool LOCKSTEP = !R2 && RING == 1 && WPB_MEM > 1;
-    if constexpr (LOCKSTEP) {
-        if (lds * WPB_MEM <= 64 * 1024) return launch_wpb<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB_MEM>(a, lds, stream);
-    }
-    return launch_wpb<MODEL, R2, RW, DENSE, RING, CERT_ONLY, 1>(a, lds + (use_wline<RW, RING>() ? WLINE_BYTES : 0), stream);
-}
-
-// gain-offset with the r2 mask exists in two builds.  The FULL one carries the reference's R2 expression inline for the
-// wave-rows the float32 certificate cannot settle (and for R2 output): 154 VGPRs, 3 waves per SIMD.  The CERTIFICATE-ONLY
-// one (a.cert_only, chosen by the host when the failures are counted and neither R2, gain nor the in-painting's flags are
-// written) has nothing but the certificate: 128 VGPRs and no LDS table = 4 waves per SIMD (-5 % on clean rasters); a
-// wave-row it cannot settle is marked in a.open_rows, and the host's LIST launch of the full build (a.list_mode) follows
-// on the same stream and does those rows (hk_api.hip launch_fit).
-template <int MODEL, bool R2, int RW, bool DENSE, int RING>
-static hipError_t launch_one(const FitArgs& a, hipStream_t stream) {
-    if constexpr (MODEL == 2 && R2 && (RING == 1 || RING == 2)) {
-        if (a.cert_only && a.has_thresh && a.fail_count && a.open_rows && !a.r2 && !a.gain && !a.flag && !a.offset_in && !a.list_mode)
-            return launch_build<MODEL, R2, RW, DENSE, RING, true>(a, stream);
-    }
-    return launch_build<MODEL, R2, RW, DENSE, RING, false>(a, stream);
-}
-
-// kernels wider than 15 (and the everything-re-loaded path from 9 wide): rw mod 4 picks the build, rw / 4 is a launch argument
-template <int MODEL, bool R2, bool DENSE, int RING>
-static hipError_t launch_wide(const FitArgs& a, hipStream_t stream) {
-    // the paired form of the whole-lane sums (hsum_wide): builds of their own on the centre ring (kernels up to 39 rows tall; the
-    // LDS-line variant of the taller ones reads the same number of entries either way)
-    if constexpr (RING == 2) {
-        if (wide_pairs(a.rw & 3, a.rw / PX)) {
-            switch (a.rw & 3) {
-                case 0: return launch_one<MODEL, R2, -5, DENSE, RING>(a, stream);
-                case 1: return launch_one<MODEL, R2, -6, DENSE, RING>(a, stream);
-                case 2: return launch_one<MODEL, R2, -7, DENSE, RING>(a, stream);
-                default: return launch_one<MODEL, R2, -8, DENSE, RING>(a, stream);
+// One point of the build table: instantiates the build if fit_build_exists() says it is one and launches it if it is `b`.
+// -> whether it was; `e` then holds the launch's result.
+template <int MODEL, bool R2, int RW, bool DENSE, int RING, bool CERT_ONLY, int WPB, bool BATCH, bool LIST>
+static bool launch_if(const FitBuild& b, const FitArgs& a, hipStream_t stream, hipError_t& e) {
+    if constexpr (fit_build_exists(MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, BATCH, LIST)) {
+        if (b.cert_only != CERT_ONLY || b.wpb != WPB || b.batch != BATCH || b.list != LIST) return false;
+        BuildRecord& rec = FitBuildRecord<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, BATCH, LIST>::rec;
+        // per wave: the ring of the mode that runs, and the exchange lines of the builds that use them
+        const size_t lds = fit_lds_bytes_of(2 * a.rh + 1, RING, fit_ring_ahead(MODEL, R2, RING)) + (use_wline<RW, RING>() ? WLINE_BYTES : 0);
+        if constexpr (LIST) {  // a persistent grid of single waves; an empty bit plane costs microseconds
+            e = launch_counted(&fit_list_kernel<MODEL, R2, RW, DENSE, RING>, rec, 256 * 8, WAVE, lds, a, stream);
+        } else {
+            // workgroups of WPB adjacent strips
+            int grid = BATCH ? a.batch_groups[WPB > 1 ? 1 : 0] : (a.n_strips + WPB - 1) / WPB * a.n_segs * a.n_bands;
+            if (a.xcd_remap) {
+                const int g = a.xcd_remap / WPB > 0 ? a.xcd_remap / WPB : 1;
+                grid = (grid + 8 * g - 1) / (8 * g) * (8 * g);
             }
+            // a.lds_pad: extra dynamic LDS per wave that nothing uses -- it only lowers the number of resident waves per CU
+            e = launch_counted(&fit_apply_kernel<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, BATCH>, rec, grid, WAVE * WPB,
+                               (lds + (size_t)a.lds_pad) * WPB, a, stream);
         }
+        return true;
     }
-    switch (a.rw & 3) {
-        case 0: return launch_one<MODEL, R2, -1, DENSE, RING>(a, stream);
-        case 1: return launch_one<MODEL, R2, -2, DENSE, RING>(a, stream);
-        case 2: return launch_one<MODEL, R2, -3, DENSE, RING>(a, stream);
-        default: return launch_one<MODEL, R2, -4, DENSE, RING>(a, stream);
-    }
+    return false;
 }
 
-template <int MODEL, bool R2, bool DENSE>
-static hipError_t launch_rw(const FitArgs& a, hipStream_t stream) {
-#ifdef HK_DEV_SUBSET  // development builds: only the 5x5 kernels with the full LDS ring (seconds instead of a minute)
-#ifdef HK_DEV_SUBSET15   // ... or only the 15-wide kernels with the centre / split ring
-    if constexpr (MODEL != 2 && !R2) {
-        if (a.use_ring == 3) return launch_one<MODEL, R2, 7, DENSE, 3>(a, stream);
-    }
-    return launch_one<MODEL, R2, 7, DENSE, 2>(a, stream);
-#else
-    return launch_one<MODEL, R2, 2, DENSE, 1>(a, stream);
-#endif
-#else
-    // a.use_ring (hk_api.hip): 1 full LDS ring (short, narrow kernels only), 2 centre ring + re-loaded leaving row,
-    // 0 everything re-loaded (very tall kernels; wide-kernel builds only, to bound the number of instantiations)
-    if (a.use_ring == 1) {
-        switch (a.rw) {
-            case 0: return launch_one<MODEL, R2, 0, DENSE, 1>(a, stream);
-            case 1: return launch_one<MODEL, R2, 1, DENSE, 1>(a, stream);
-            case 2: return launch_one<MODEL, R2, 2, DENSE, 1>(a, stream);
-            case 3: return launch_one<MODEL, R2, 3, DENSE, 1>(a, stream);
-            default: break;
-        }
-        if constexpr (MODEL != 2 && !R2) {  // the memory-bound builds keep the full ring for wider kernels too (hk_api.hip)
-            switch (a.rw) {
-                case 4: return launch_one<MODEL, R2, 4, DENSE, 1>(a, stream);
-                case 5: return launch_one<MODEL, R2, 5, DENSE, 1>(a, stream);
-                case 6: return launch_one<MODEL, R2, 6, DENSE, 1>(a, stream);
-                case 7: return launch_one<MODEL, R2, 7, DENSE, 1>(a, stream);
-                default: break;
-            }
-        }
-    }
-    if (a.use_ring == 0 && a.rw >= PX) return launch_wide<MODEL, R2, DENSE, 0>(a, stream);  // (narrower: centre ring, below)
-    if constexpr (MODEL != 2 && !R2) {  // split ring (hk_api.hip fill_args): rh rows in registers
-        if (a.use_ring == 3 && a.rh <= split_ring_rows(MODEL)) {
-            switch (a.rw) {
-                case 2: return launch_one<MODEL, R2, 2, DENSE, 3>(a, stream);
-                case 3: return launch_one<MODEL, R2, 3, DENSE, 3>(a, stream);
-                case 4: return launch_one<MODEL, R2, 4, DENSE, 3>(a, stream);
-                case 5: return launch_one<MODEL, R2, 5, DENSE, 3>(a, stream);
-                case 6: return launch_one<MODEL, R2, 6, DENSE, 3>(a, stream);
-                case 7: return launch_one<MODEL, R2, 7, DENSE, 3>(a, stream);
-                default: break;   // other widths: centre ring
-            }
-        }
-    }
-    switch (a.rw) {
-        case 0: return launch_one<MODEL, R2, 0, DENSE, 2>(a, stream);
-        case 1: return launch_one<MODEL, R2, 1, DENSE, 2>(a, stream);
-        case 2: return launch_one<MODEL, R2, 2, DENSE, 2>(a, stream);
-        case 3: return launch_one<MODEL, R2, 3, DENSE, 2>(a, stream);
-        case 4: return launch_one<MODEL, R2, 4, DENSE, 2>(a, stream);
-        case 5: return launch_one<MODEL, R2, 5, DENSE, 2>(a, stream);
-        case 6: return launch_one<MODEL, R2, 6, DENSE, 2>(a, stream);
-        case 7: return launch_one<MODEL, R2, 7, DENSE, 2>(a, stream);
-        default: return launch_wide<MODEL, R2, DENSE, 2>(a, stream);
-    }
-#endif
+// The build table of one translation unit (MODEL, R2): the compile-time range of DENSE x RING x RW (S) and, per shape, of
+// CERT_ONLY x WPB x BATCH x LIST (V).  The walk both instantiates the builds and dispatches to them; no allocation, no lock.
+// Its ORDER is the order of the kernels in the code object, whose code reaches the 1/N table at a distance from where it lies:
+// keep it and the object stays the same bit for bit (tools/same_isa.py) -- dense first; full ring, re-loaded, split, centre
+// ring; half-widths 0..7, then the paired and the plain wide builds; certificate before complete, lock-step before single waves.
+constexpr int table_ring(int s) { return s / 16 % 4 == 0 ? 1 : s / 16 % 4 == 1 ? 0 : s / 16 % 4 == 2 ? 3 : 2; }
+constexpr int table_rw(int s) { return s % 16 < 8 ? s % 16 : s % 16 < 12 ? 3 - s % 16 : 11 - s % 16; }  // 0..7, -5..-8, -1..-4
+template <int MODEL, bool R2, int RW, bool DENSE, int RING, int... V>
+static bool launch_shape(const FitBuild& b, const FitArgs& a, hipStream_t stream, hipError_t& e, std::integer_sequence<int, V...>) {
+    if (b.rw != RW || b.dense != DENSE || b.ring != RING) return false;
+    return (... || launch_if<MODEL, R2, RW, DENSE, RING, V / 8 == 0, V / 4 % 2 == 0 ? WPB_MEM : 1, V % 4 >= 2, V % 2 != 0>(b, a, stream, e));
 }
-
+template <int MODEL, bool R2, int... S>
+static hipError_t launch_table(const FitBuild& b, const FitArgs& a, hipStream_t stream, std::integer_sequence<int, S...>) {
+    hipError_t e = hipErrorInvalidValue;  // (not a build of this translation unit)
+    (void)(... || launch_shape<MODEL, R2, table_rw(S), S / 64 == 0, table_ring(S)>(b, a, stream, e, std::make_integer_sequence<int, 16>{}));
+    return e;
+}
 template <int MODEL, bool R2>
-static hipError_t launch_dense(const FitArgs& a, hipStream_t stream) {
-    // nodata None on both rasters (and not gain-blk-offset, whose mask depends on the normalised values)
-    if constexpr (MODEL != 1) {
-        if (a.src_nd_mode == 0 && a.ref_nd_mode == 0 && !a.force_general) return launch_rw<MODEL, R2, true>(a, stream);
-    }
-    return launch_rw<MODEL, R2, false>(a, stream);
+static hipError_t launch_fit_build(const FitBuild& b, const FitArgs& a, hipStream_t stream) {
+    if (b.model != MODEL || b.r2 != R2) return hipErrorInvalidValue;
+    return launch_table<MODEL, R2>(b, a, stream, std::make_integer_sequence<int, 2 * 4 * 16>{});
 }
 
 }  // namespace hk

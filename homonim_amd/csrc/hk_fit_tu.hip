@@ -12,8 +12,8 @@ namespace hk {
 #define HK_TU_CAT2(p, m, r) p##m##_r##r
 #define HK_TU_CAT(p, m, r) HK_TU_CAT2(p, m, r)
 
-hipError_t HK_TU_CAT(launch_fit_m, HK_TU_MODEL, HK_TU_R2)(const FitArgs& a, hipStream_t stream) {
-    return launch_dense<HK_TU_MODEL, HK_TU_R2 != 0>(a, stream);
+hipError_t HK_TU_CAT(launch_fit_m, HK_TU_MODEL, HK_TU_R2)(const FitBuild& b, const FitArgs& a, hipStream_t stream) {
+    return launch_fit_build<HK_TU_MODEL, HK_TU_R2 != 0>(b, a, stream);
 }
 hipError_t HK_TU_CAT(read_stamps_m, HK_TU_MODEL, HK_TU_R2)(unsigned long long* acc16, bool reset) { return read_stamps_tu(acc16, reset); }
 

@@ -18,15 +18,13 @@ constexpr int WAVE = 64;   // gfx950 wavefront
 // itself on a process-wide list when the library is loaded (so a build nothing ever launched is on the list too) and counts
 // its launches.  The test-suite reads the list around every test and keeps a ledger of which builds were launched by a test
 // that compared its results with the oracle (tests/conftest.py, tests/test_zz_build_ledger.py).  One relaxed atomic add per launch.
+struct FitBuild;
 struct BuildRecord {
     char name[88];
     unsigned long long launches;  // (atomic adds; read by ledger_text)
     BuildRecord* next;
     explicit BuildRecord(const char* kernel_name);
-    // the fused kernel: "fit_apply_kernel<MODEL,R2,RW,DENSE,RING,CERT_ONLY,WPB,BATCH>"
-    BuildRecord(int model, bool r2, int rw, bool dense, int ring, bool cert_only, int wpb, bool batch);
-    // its list-launch twin: "fit_list_kernel<MODEL,R2,RW,DENSE,RING>"
-    BuildRecord(const char* kernel_name, int model, bool r2, int rw, bool dense, int ring);
+    explicit BuildRecord(const FitBuild& build);  // a build of the fused kernel, under fit_build_name()
     void hit() { __atomic_fetch_add(&launches, 1ull, __ATOMIC_RELAXED); }
 };
 // one record per launch SITE of a kernel outside the fused template: the site's local tag type names the kernel
@@ -102,8 +100,8 @@ struct FitArgs {
     float src_nodata, ref_nodata;
     int has_thresh;
     float r2_thresh;
-    int cert_only;          // gain-offset + r2 mask, no R2 plane, fail_count and open_rows set: run the CERTIFICATE build (launch_one),
-                            // which settles a wave-row by the two-sided float32 certificate or marks it in `open_rows`
+    int cert_only;          // gain-offset + r2 mask, no R2 plane, fail_count and open_rows set: run the CERTIFICATE build
+                            // (choose_fit_build), which settles a wave-row by the two-sided float32 certificate or marks it in `open_rows`
     // The wave-rows the certificate build cannot settle: one bit per (band, strip, row), 32 rows per word, word index
     // (band * n_strips + strip) * ceil(height / 32) + row / 32 (zeroed before the certificate launch).
     // list_mode != 0: THIS launch is the list launch -- the complete build on a persistent grid over the runs of marked rows.
@@ -118,7 +116,8 @@ struct FitArgs {
     double inv_n_full;      // RN64(1 / (kh * kw)) -- the 1/N table entry (hk_fit_kernel.h)
     int force_general;      // 1: never take the dense (nodata None) specialisation (testing)
     int seg_rows_pref;      // > 0: the build's preferred uniform segment height (hk_api.hip fill_args / fill_grid), 0: the default policy
-    int use_ring;           // ring mode of fit_apply_kernel: 1 full LDS ring, 2 centre ring + re-loaded leaving row, 0 re-load both
+    int use_ring;           // the ring mode ASKED for (hk_api.hip fill_args): 1 full LDS ring, 2 centre ring + re-loaded leaving row,
+                            // 3 split ring (registers + LDS), 0 re-load both; choose_fit_build() resolves it to the ring that RUNS
     int xcd_remap;          // G > 0: blockIdx -> unit remap handing each XCD runs of G consecutive units (0: round-robin)
     int lds_pad;            // unused dynamic LDS bytes per wave: fewer resident waves per CU (hk_api.hip fill_args)
     // store window: only rows [out_y0, out_y1) x columns [out_x0, out_x1) of the job are written / counted (the halo crop of
@@ -139,32 +138,81 @@ inline void fit_job_of(FitJob& e, const FitArgs& a) {
     e.out_y0 = a.out_y0, e.out_y1 = a.out_y1, e.out_x0 = a.out_x0, e.out_x1 = a.out_x1;
 }
 
-// model: 0 gain, 1 gain-blk-offset, 2 gain-offset.  with_r2: compute the R2 quantity set.
+// ---------------------------------------------------------------------------------------------------------------------
+// Which build of the fused kernel a launch gets.  A build is one instantiation of fit_apply_kernel<MODEL, R2, RW, DENSE, RING,
+// CERT_ONLY, WPB, BATCH> or, `list`, of fit_list_kernel<MODEL, R2, RW, DENSE, RING> (hk_fit_kernel.h, which explains the
+// parameters).  fit_build_exists() is the one statement of which are instantiated, choose_fit_build() the one place that picks
+// one for a launch, launch_fit_build() (hk_fit_kernel.h) the one table that instantiates and launches them.
+struct FitBuild {
+    int model;       // 0 gain, 1 gain-blk-offset, 2 gain-offset
+    bool r2;         // with the R2 quantity set
+    int rw;          // kernel half-width 0..7; -1 - E: wider, half-width 4 F + E; -5 - E: the same with the whole lanes summed as pairs
+    bool dense;      // both rasters have nodata None
+    int ring;        // the ring mode that runs (FitArgs::use_ring is the one asked for)
+    bool cert_only;  // the certificate build of gain-offset with the r2 mask
+    int wpb;         // strips per workgroup: 1, or WPB_MEM in lock-step; 0: no build (choose_fit_build refused the launch)
+    bool batch;      // with the job-table look-up of a batched launch (FitArgs::jobs)
+    bool list;       // the list launch's kernel: the complete build over the rows the certificate build marked
+};
+constexpr int WPB_MEM = 4;  // strips per workgroup of the lock-step builds (hk_fit_kernel.h; FitJob::first_group[1] counts those)
+// Register rows of the split ring (ring mode 3) a build holds = the largest kernel half-height it serves.
+constexpr int SPLIT_RING_ROWS = 7, SPLIT_RING_ROWS_BLK = 5;  // (_BLK: the gain-blk-offset builds)
+__host__ __device__ constexpr int split_ring_rows(int model) { return model == 1 ? SPLIT_RING_ROWS_BLK : SPLIT_RING_ROWS; }
+// The builds with the job-table look-up: gain-blk-offset without R2 -- the fused RasterFuse path of a block-partitioned mosaic,
+// where one launch for all blocks pays (profiles/r03_batch.txt).  The batched entry points run every other model as one launch
+// per job (bit-identical either way).
+constexpr bool fit_batch_build(int model, bool with_r2) { return model == 1 && !with_r2; }
+// The full-ring builds that read the leaving row one iteration ahead (their ring holds a row less): the memory-bound ones
+__host__ __device__ constexpr bool fit_ring_ahead(int model, bool r2, int ring) { return ring == 1 && model != 2 && !r2; }
+
+constexpr bool fit_build_exists(int model, bool r2, int rw, bool dense, int ring, bool cert_only, int wpb, bool batch, bool list) {
+    [[maybe_unused]] const bool mem_bound = model != 2 && !r2;  // gain, gain-blk-offset without the R2 work
+    // kernel width x ring mode: the full ring up to 7 wide (the memory-bound builds: up to 15), the split ring 5 - 15 wide on the
+    // memory-bound builds, everything re-loaded on the wide builds only, the centre ring at every width (wide: plain and paired)
+#if defined(HK_DEV_SUBSET) && defined(HK_DEV_SUBSET15)  // development: only the 15-wide kernels with the centre / split ring
+    const bool shape = rw == 7 && (ring == 2 || (ring == 3 && mem_bound));
+#elif defined(HK_DEV_SUBSET)                             // development: only the 5x5 kernels with the full LDS ring
+    const bool shape = rw == 2 && ring == 1;
+#else
+    const bool shape = ring == 1 ? rw >= 0 && rw <= (mem_bound ? 7 : 3)
+                     : ring == 3 ? mem_bound && rw >= 2 && rw <= 7
+                     : ring == 0 ? rw >= -4 && rw <= -1
+                                 : ring == 2 && rw >= -8 && rw <= 7;
+#endif
+    if (model < 0 || model > 2 || !shape) return false;
+    if (dense && model == 1) return false;  // gain-blk-offset's mask depends on the normalised values
+    // certificate and list: gain-offset with the R2 work on the full and the centre ring, single waves, never batched
+    if ((cert_only || list) && !(model == 2 && r2 && (ring == 1 || ring == 2) && wpb == 1 && !batch && !(cert_only && list))) return false;
+    if (batch && !fit_batch_build(model, r2)) return false;
+    // lock-step workgroups: every build without the R2 work on the full ring (gain-offset without a threshold gains 3 % as well)
+    return wpb == 1 || (wpb == WPB_MEM && !r2 && ring == 1);
+}
+constexpr bool fit_build_exists(const FitBuild& b) {
+    return fit_build_exists(b.model, b.r2, b.rw, b.dense, b.ring, b.cert_only, b.wpb, b.batch, b.list);
+}
+// The build for the launch `a` describes -- a.cert_only: the certificate build, a.list_mode: the list launch, a.jobs: batched --
+// or, where that launch has no build (a certificate or list launch whose planes or ring have none, a job table on a model
+// without the look-up), one with wpb == 0.  Plain host arithmetic.
+FitBuild choose_fit_build(const FitArgs& a, int model, bool r2);
+// "fit_apply_kernel<MODEL,R2,RW,DENSE,RING,CERT_ONLY,WPB,BATCH>" / "fit_list_kernel<MODEL,R2,RW,DENSE,RING>": the ledger's name
+void fit_build_name(char* buf, size_t len, const FitBuild& b);
+// choose_fit_build() + the launch; hipErrorInvalidValue where there is no build
 hipError_t launch_fit_apply(const FitArgs& a, int model, bool with_r2, hipStream_t stream);
-// ... which dispatches to one translation unit per (model, with_r2) (hk_fit_tu.hip)
-hipError_t launch_fit_m0_r0(const FitArgs& a, hipStream_t stream);
-hipError_t launch_fit_m0_r1(const FitArgs& a, hipStream_t stream);
-hipError_t launch_fit_m1_r0(const FitArgs& a, hipStream_t stream);
-hipError_t launch_fit_m1_r1(const FitArgs& a, hipStream_t stream);
-hipError_t launch_fit_m2_r0(const FitArgs& a, hipStream_t stream);
-hipError_t launch_fit_m2_r1(const FitArgs& a, hipStream_t stream);
+// ... through the table of the build's translation unit, one per (model, with_r2) (hk_fit_tu.hip)
+hipError_t launch_fit_m0_r0(const FitBuild& b, const FitArgs& a, hipStream_t stream);
+hipError_t launch_fit_m0_r1(const FitBuild& b, const FitArgs& a, hipStream_t stream);
+hipError_t launch_fit_m1_r0(const FitBuild& b, const FitArgs& a, hipStream_t stream);
+hipError_t launch_fit_m1_r1(const FitBuild& b, const FitArgs& a, hipStream_t stream);
+hipError_t launch_fit_m2_r0(const FitBuild& b, const FitArgs& a, hipStream_t stream);
+hipError_t launch_fit_m2_r1(const FitBuild& b, const FitArgs& a, hipStream_t stream);
 hipError_t read_stamps_m0_r0(unsigned long long* acc16, bool reset);
 hipError_t read_stamps_m0_r1(unsigned long long* acc16, bool reset);
 hipError_t read_stamps_m1_r0(unsigned long long* acc16, bool reset);
 hipError_t read_stamps_m1_r1(unsigned long long* acc16, bool reset);
 hipError_t read_stamps_m2_r0(unsigned long long* acc16, bool reset);
 hipError_t read_stamps_m2_r1(unsigned long long* acc16, bool reset);
-// Which builds of the fused kernel exist with the job-table look-up of a batched launch (FitArgs::jobs): gain-blk-offset without
-// R2 -- the fused RasterFuse path of a block-partitioned mosaic, where one launch for all blocks pays (profiles/r03_batch.txt).
-// The batched entry points run every other model as one launch per job (bit-identical either way).
-constexpr bool fit_batch_build(int model, bool with_r2) { return model == 1 && !with_r2; }
-bool fit_batch_supported(int model, bool with_r2);
 // stage stamps of a -DHK_STAMPS build of the fused kernel (all zero otherwise): 16 counters, optionally cleared after reading
 hipError_t read_stamps(unsigned long long* out16, bool reset);
-// strips per workgroup of the lock-step builds (WPB_MEM): FitJob::first_group[1] / FitArgs::batch_groups[1] count those
-int fit_lockstep_waves();
-// LDS bytes one wave needs (its row ring; hk_fit_kernel.h)
-size_t fit_lds_bytes(int kh, int ring_mode, bool ahead);
 // lanes per side that overlap with the neighbouring strip for kernel half-width rw
 inline int overlap_lanes_for(int rw) { return (rw + PX - 1) / PX; }
 
@@ -179,10 +227,6 @@ struct NormPlane {
     long long stride;
     int height, width;
 };
-// Register rows of the split ring (ring mode 3 of the fused kernel) a build holds = the largest kernel half-height it serves.
-constexpr int SPLIT_RING_ROWS = 7, SPLIT_RING_ROWS_BLK = 5;  // (_BLK: the gain-blk-offset builds)
-__host__ __device__ constexpr int split_ring_rows(int model) { return model == 1 ? SPLIT_RING_ROWS_BLK : SPLIT_RING_ROWS; }
-
 struct NormArgs {
     const NormPlane* planes = nullptr;  // batched launch: n_bands entries (device), else NULL -- the planes are then src/ref + band * band_stride
     const float* src;

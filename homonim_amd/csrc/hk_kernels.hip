@@ -30,13 +30,12 @@ BuildRecord::BuildRecord(const char* kernel_name) {
     snprintf(name, sizeof(name), "%s", kernel_name);
     ledger_add(this);
 }
-BuildRecord::BuildRecord(int model, bool r2, int rw, bool dense, int ring, bool cert_only, int wpb, bool batch) {
-    snprintf(name, sizeof(name), "fit_apply_kernel<%d,%d,%d,%d,%d,%d,%d,%d>", model, (int)r2, rw, (int)dense, ring, (int)cert_only, wpb,
-             (int)batch);
-    ledger_add(this);
+void fit_build_name(char* buf, size_t len, const FitBuild& b) {
+    if (b.list) snprintf(buf, len, "fit_list_kernel<%d,%d,%d,%d,%d>", b.model, (int)b.r2, b.rw, (int)b.dense, b.ring);
+    else snprintf(buf, len, "fit_apply_kernel<%d,%d,%d,%d,%d,%d,%d,%d>", b.model, (int)b.r2, b.rw, (int)b.dense, b.ring, (int)b.cert_only, b.wpb, (int)b.batch);
 }
-BuildRecord::BuildRecord(const char* kernel_name, int model, bool r2, int rw, bool dense, int ring) {
-    snprintf(name, sizeof(name), "%s<%d,%d,%d,%d,%d>", kernel_name, model, (int)r2, rw, (int)dense, ring);
+BuildRecord::BuildRecord(const FitBuild& build) {
+    fit_build_name(name, sizeof(name), build);
     ledger_add(this);
 }
 size_t ledger_text(char* buf, size_t len, bool reset) {
@@ -56,12 +55,10 @@ size_t ledger_text(char* buf, size_t len, bool reset) {
 
 
 #ifdef HK_FIT_ONE_TU  // A/B tooling (tools/mkvariant*.sh): every instantiation in this translation unit
-hipError_t launch_fit_m0_r0(const FitArgs& a, hipStream_t stream) { return launch_dense<0, false>(a, stream); }
-hipError_t launch_fit_m0_r1(const FitArgs& a, hipStream_t stream) { return launch_dense<0, true>(a, stream); }
-hipError_t launch_fit_m1_r0(const FitArgs& a, hipStream_t stream) { return launch_dense<1, false>(a, stream); }
-hipError_t launch_fit_m1_r1(const FitArgs& a, hipStream_t stream) { return launch_dense<1, true>(a, stream); }
-hipError_t launch_fit_m2_r0(const FitArgs& a, hipStream_t stream) { return launch_dense<2, false>(a, stream); }
-hipError_t launch_fit_m2_r1(const FitArgs& a, hipStream_t stream) { return launch_dense<2, true>(a, stream); }
+#define HK_ONE_TU(m, r) \
+    hipError_t launch_fit_m##m##_r##r(const FitBuild& b, const FitArgs& a, hipStream_t stream) { return launch_fit_build<m, r != 0>(b, a, stream); }
+HK_ONE_TU(0, 0) HK_ONE_TU(0, 1) HK_ONE_TU(1, 0) HK_ONE_TU(1, 1) HK_ONE_TU(2, 0) HK_ONE_TU(2, 1)
+#undef HK_ONE_TU
 hipError_t read_stamps(unsigned long long* out16, bool reset) {
     for (int k = 0; k < 16; ++k) out16[k] = 0;
     return read_stamps_tu(out16, reset);
@@ -79,21 +76,43 @@ hipError_t read_stamps(unsigned long long* out16, bool reset) {
 }
 #endif
 
-hipError_t launch_fit_apply(const FitArgs& a, int model, bool with_r2, hipStream_t stream) {
-    switch (model * 2 + (with_r2 ? 1 : 0)) {
-        case 0: return launch_fit_m0_r0(a, stream);
-        case 1: return launch_fit_m0_r1(a, stream);
-        case 2: return launch_fit_m1_r0(a, stream);
-        case 3: return launch_fit_m1_r1(a, stream);
-        case 4: return launch_fit_m2_r0(a, stream);
-        case 5: return launch_fit_m2_r1(a, stream);
-    }
-    return hipErrorInvalidValue;
+// Which build a launch gets (hk_kernels.h).  The ring mode asked for (hk_api.hip fill_args: measured thresholds, testing switch)
+// is resolved to the ring that has a build at this width and model; everything else follows from the arguments.
+FitBuild choose_fit_build(const FitArgs& a, int model, bool r2) {
+    FitBuild b = {};  // (wpb 0: no build)
+    b.model = model, b.r2 = r2;
+    // nodata None on both rasters (and not gain-blk-offset, whose mask depends on the normalised values)
+    b.dense = model != 1 && a.src_nd_mode == 0 && a.ref_nd_mode == 0 && !a.force_general;
+    const bool mem_bound = model != 2 && !r2;
+    if (a.use_ring == 1 && a.rw <= (mem_bound ? 7 : 3)) b.ring = 1;   // full ring: up to 7 wide, the memory-bound builds up to 15
+    else if (a.use_ring == 0 && a.rw >= PX) b.ring = 0;               // everything re-loaded: the wide builds only (from 9 wide)
+    else if (a.use_ring == 3 && mem_bound && a.rh <= split_ring_rows(model) && a.rw >= 2 && a.rw <= 7) b.ring = 3;  // split ring
+    else b.ring = 2;                                                  // every other request runs on the centre ring
+    // kernels wider than 15 (and the everything-re-loaded path from 9 wide): rw mod 4 picks the build, rw / 4 is a launch argument;
+    // on the centre ring the widths whose whole lanes pair (wide_pairs) have builds of their own
+    if (b.ring == 0 || a.rw > 7) b.rw = (b.ring == 2 && wide_pairs(a.rw & 3, a.rw / PX) ? -1 - PX : -1) - (a.rw & 3);
+    else b.rw = a.rw;
+    // Certificate / list (hk_api.hip launch_fit): only where nothing but the corrected block is written and the failures are
+    // counted -- the certificate build has no registers for R2, gain or the in-painting's flags, and its constants assume
+    // window counts below 2^16 -- and never batched
+    b.cert_only = a.cert_only != 0, b.list = a.list_mode != 0, b.batch = a.jobs != nullptr;
+    if ((b.cert_only || b.list) && !(a.has_thresh && a.fail_count && !a.r2 && !a.gain && !a.flag && !a.offset_in &&
+                                     (2ll * a.rh + 1) * (2ll * a.rw + 1) <= 65535))
+        return b;
+    // lock-step workgroups while the LDS holds WPB_MEM rings
+    const size_t lds = fit_lds_bytes_of(2 * a.rh + 1, b.ring, fit_ring_ahead(model, r2, b.ring));
+    const int wpb = !r2 && b.ring == 1 && lds * WPB_MEM <= 64 * 1024 ? WPB_MEM : 1;
+    if (fit_build_exists(model, r2, b.rw, b.dense, b.ring, b.cert_only, wpb, b.batch, b.list)) b.wpb = wpb;
+    return b;
 }
 
-int fit_lockstep_waves() { return WPB_MEM; }
-bool fit_batch_supported(int model, bool with_r2) { return fit_batch_build(model, with_r2); }
-size_t fit_lds_bytes(int kh, int ring_mode, bool ahead) { return fit_lds_bytes_of(kh, ring_mode, ahead); }
+hipError_t launch_fit_apply(const FitArgs& a, int model, bool with_r2, hipStream_t stream) {
+    const FitBuild b = choose_fit_build(a, model, with_r2);
+    if (!fit_build_exists(b)) return hipErrorInvalidValue;
+    hipError_t (*const tus[6])(const FitBuild&, const FitArgs&, hipStream_t) = {launch_fit_m0_r0, launch_fit_m0_r1, launch_fit_m1_r0,
+                                                                                launch_fit_m1_r1, launch_fit_m2_r0, launch_fit_m2_r1};
+    return tus[model * 2 + (with_r2 ? 1 : 0)](b, a, stream);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // KernelModel.apply alone (kernel_model.py:461): used after parameters were re-sampled / in-painted on another grid.

@@ -84,6 +84,24 @@ int hk_debug_fail_after_d2h(int32_t on);
  * comparing with the oracle ever launched. */
 int hk_debug_build_ledger(char* buf, size_t len, size_t* needed, int32_t reset);
 
+/* Test aid: WHICH build of the fused kernel a launch gets -- its ledger name, NUL-terminated, into name[len] (88 bytes hold any).
+ * Host-only: no context, no device.  The launch is described as the entry points build it: the fit (`desc`), the job's shape,
+ * `planes` = which planes the launch is handed, as a sum of HK_FIT_PLANE_*; `phase` 0: the one launch, 1: the certificate build,
+ * 2: its list launch (hk_fit_apply_dev on gain-offset with the r2 mask: both, one after the other); and the two testing
+ * switches, `force_ring` -1 (none) or 0..3 as HK_USE_RING, `force_general` as HK_FORCE_GENERAL.  HK_FIT_PLANE_OFFSET_IN makes it
+ * the closing pass of the in-painting branch (the build without the R2 work), HK_FIT_PLANE_JOBS a batched launch.  HK_ERR_ARG for a
+ * launch that has no build: phase 1 / 2 unless BOTH builds exist for it, a job table on a model without the look-up. */
+#define HK_FIT_PLANE_GAIN 1u
+#define HK_FIT_PLANE_OFFSET 2u
+#define HK_FIT_PLANE_R2 4u
+#define HK_FIT_PLANE_CORR 8u
+#define HK_FIT_PLANE_FAIL_COUNT 16u
+#define HK_FIT_PLANE_FLAGS 32u
+#define HK_FIT_PLANE_OFFSET_IN 64u
+#define HK_FIT_PLANE_JOBS 128u
+int hk_debug_fit_build(const hk_fit_desc* desc, int32_t height, int32_t width, int32_t n_bands, uint32_t planes, int32_t phase,
+                       int32_t force_ring, int32_t force_general, char* name, size_t len);
+
 /* Test aid: the in-painting step alone (hk_inpaint.hip; kernel_model.py:366) on a source mask of the caller's choosing, where
  * hk_fit_apply* only ever hands it the mask its own fit produced.  `plane_dev`: height x stride float32, device-resident; its
  * targets are filled in place, everything else stays as it is.  The mask comes EITHER from `flags_dev` -- one byte per pixel at

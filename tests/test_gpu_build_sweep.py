@@ -5,8 +5,9 @@ had launched 178 of the 332 builds).
 The fused kernel `hk::fit_apply_kernel<MODEL, R2, RW, DENSE, RING, CERT_ONLY, WPB, BATCH>` exists in one build per model x R2
 quantity set x kernel half-width (0..7 at compile time, four residues beyond) x nodata specialisation x ring mode x
 certificate-only x lock-step workgroup x batched launch; which one a call gets is decided by hk_api.hip `fill_args` from the model
-configuration, the kernel shape and the raster's nodata (thresholds measured on MI355X, moved every round) and by `launch_build` from
-the LDS the shape needs.  The tests here walk that decision space -- every model configuration over a grid of kernel heights and
+configuration and the kernel shape (the ring mode asked for: thresholds measured on MI355X, moved every round) and by
+hk_kernels.hip `choose_fit_build` from that request, the raster's nodata, the planes of the launch and the LDS the shape needs
+(tests/test_fit_build_cpu.py: it only ever names a build that exists; tests/test_gpu_fit_build_choices.py: which one, case by case).  The tests here walk that decision space -- every model configuration over a grid of kernel heights and
 widths on either side of each threshold, through the three entry points that differ in builds (parameters out; corrected block
 only = the RasterFuse path, certificate-only first; batched jobs) -- on a raster of two strips, and hold EVERY launch to the C
 oracle.  The ring modes and segment policies a shape does not get by default are forced through the library's testing switches

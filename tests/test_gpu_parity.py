@@ -1176,7 +1176,7 @@ def _dev_job_corr_only(c, src, ref, thresh, kernel_shape=(5, 5)):
 @pytest.mark.oracle
 @pytest.mark.parametrize('kernel_shape, nodata', [((5, 5), None), ((5, 5), np.nan), ((3, 7), None), ((15, 15), np.nan), ((9, 5), None), ((31, 31), np.nan)])
 def test_certificate_build_and_its_list_launch(oc, kernel_shape, nodata):
-    """ Gain-offset jobs that keep nothing but the corrected block start with the CERTIFICATE build (hk_fit_kernel.h launch_one:
+    """ Gain-offset jobs that keep nothing but the corrected block start with the CERTIFICATE build (hk_kernels.hip choose_fit_build:
     a wave-row whose every valid pixel certainly passes the r2 mask is settled without the reference's R2 expression); the wave-rows
     it cannot settle are marked in a bit plane and done by the LIST launch that follows -- the complete build over the runs of
     marked rows.  Whatever the share of open rows -- none (clean), a patch, scattered failures, nearly all (noise) -- the two
