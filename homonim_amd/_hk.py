@@ -345,10 +345,16 @@ def lzw_image_host(streams, layout) -> np.ndarray:
     return lzw_image_host_packed(*_pack_streams(streams), layout, strict=True)[0]
 
 
+# The TIFF predictors the block decoders undo, as ``tiff.read_tiff`` asks a hook: 3, the floating-point predictor, goes only to a
+# hook that says so in its ``predictors`` (a hook without the attribute knows 1 and 2).
+PREDICTORS = (1, 2, 3)
+lzw_image_host_packed.predictors = lzw_image_host.predictors = PREDICTORS
+
+
 def block_decoders(inflate, get_context=None):
     """ The ``inflate`` option of ``RasterFuse`` / ``ParamStats`` -> (inflater, lzw) as ``tiff.read_tiff`` takes them: 'host' -- zlib
     on the reading thread (no inflater) and the library's host LZW decoder; 'device' -- ``inflate_image`` / ``lzw_image`` of
-    ``get_context()``, which is called only then (None: the option is only checked). """
+    ``get_context()``, which is called only then (None: the option is only checked).  All of them undo predictors 1, 2 and 3. """
     if inflate not in ('host', 'device'):
         raise ValueError(f"`inflate` must be 'host' or 'device', not {inflate!r}")
     if inflate == 'device' and get_context is not None:
@@ -702,6 +708,9 @@ class Context:
         block order) -> its (spp, height, width) array of uint8 / 16 / 32 / 64, decoded on the device (``lzw_image_packed``).
         ``IoError`` names the first block whose stream is refused, and why. """
         return self.lzw_image_packed(*_pack_streams(streams), layout, strict=True)[0]
+
+    # (what ``tiff.read_tiff`` looks at before it hands a predictor-3 image to a hook)
+    inflate_image_packed.predictors = inflate_image.predictors = lzw_image_packed.predictors = lzw_image.predictors = PREDICTORS
 
     def fit_apply(self, desc: FitDesc, src: np.ndarray, ref: np.ndarray, n_param_bands: int, want_params: bool,
                   want_corr: bool, norm_in: Optional[np.ndarray] = None, out_params: Optional[np.ndarray] = None,
@@ -1343,6 +1352,8 @@ class Context:
         _check(self._lib.hk_lzw_image_dev(self._h, C.byref(_inflate_layout(layout)), C.c_void_p(streams_dptr), C.c_void_p(offsets_dptr),
                                           C.c_void_p(sizes_dptr), C.c_void_p(work_dptr), C.c_void_p(out_dptr), stride, band_stride,
                                           C.c_void_p(status_dptr), stream))
+
+    inflate_image_dev.predictors = lzw_image_dev.predictors = PREDICTORS
 
     def synth_fill_dev(self, src_dptr, ref_dptr, n_bands, height, width, stride, band_stride, seed=0, nodata_variant=0,
                        stream=0):

@@ -2744,7 +2744,9 @@ static int inflate_shape(const hk_inflate_layout* l, InflateShape* s) {
         return fail(HK_ERR_ARG, "sample_bytes %d is not 1, 2, 4 or 8", l->sample_bytes);
     if (l->spp < 1 || l->height < 1 || l->width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d x %d", l->spp, l->height, l->width);
     if (l->block_w < 1 || l->block_h < 1) return fail(HK_ERR_ARG, "empty block %d x %d", l->block_h, l->block_w);
-    if (l->predictor != 1 && l->predictor != 2) return fail(HK_ERR_ARG, "predictor %d is not 1 or 2", l->predictor);
+    // (3, the floating-point predictor, is for samples of 4 and 8 bytes; those of 1 and 2 bytes have 1 and 2 alone)
+    if (l->sample_bytes < 4 && l->predictor != 1 && l->predictor != 2) return fail(HK_ERR_ARG, "predictor %d is not 1 or 2", l->predictor);
+    if (l->predictor < 1 || l->predictor > 3) return fail(HK_ERR_ARG, "predictor %d is not 1, 2 or 3", l->predictor);
     if ((l->tiled != 0 && l->tiled != 1) || (l->separate != 0 && l->separate != 1)) return fail(HK_ERR_ARG, "tiled and separate are 0 or 1");
     if (!l->tiled && l->block_w != l->width) return fail(HK_ERR_ARG, "a strip is as wide as the image: block_w %d, width %d", l->block_w, l->width);
     s->cspp = l->separate ? 1 : l->spp;

@@ -14,8 +14,10 @@
 // the image's edge, pixel-interleaved samples to their planes; predictor 2 (horizontal differencing) is undone by a wave scan of
 // 64 samples with a carry from step to step -- a modular sum in the sample's width.  Rows of one-sample blocks without a
 // predictor move as 16-byte groups where everything is 16-byte aligned.  Blocks with a status are skipped.
+// untile_fp_kernel<ES>, ES = 4 or 8: the same second stage for predictor 3 (the floating-point predictor; hk_fpred_core.h).
 #include <hip/hip_runtime.h>
 
+#include "hk_fpred_core.h"
 #include "hk_inflate_core.h"
 #include "hk_kernels.h"
 
@@ -115,6 +117,69 @@ __global__ void __launch_bounds__(256) untile_kernel(const InflateArgs a) {
     }
 }
 
+// untile_kernel<ES> for predictor 3 (hk_fpred_core.h states it): the same wave per block row and sample of a pixel, the same crop,
+// de-interleaving and strides.  A first sweep over the row's bw pixels sums every plane's bytes of the sample's chain (one byte-wise
+// wave reduction per four planes) and gives each plane what it starts from; a second sweep in steps of 64 pixels over [0, cols)
+// scans the ES planes in lock-step, four to a word, with lane 63's word carried from step to step as in the predictor-2 path; the
+// scanned words are the sample.  Nothing is sized by the row: a strip's row is as wide as the image.  Every byte read is at
+// k * n + x * cspp + c with k < ES, x < bw, c < cspp: inside the row's n * ES bytes of the slot.
+template <int ES>
+__global__ void __launch_bounds__(256) untile_fp_kernel(const InflateArgs a) {
+    typedef typename Sample<ES>::type T;
+    typedef __attribute__((address_space(1))) T g_T;
+    constexpr int W = ES / 4;   // words of four planes
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long b = blockIdx.x;
+    if (((g_cint*)a.status)[b] != 0) return;
+    int plane, by, bx;
+    block_place(a, b, plane, by, bx);
+    const int y0 = by * a.bh, x0 = bx * a.bw;
+    const int rows = a.bh < a.height - y0 ? a.bh : a.height - y0, cols = a.bw < a.width - x0 ? a.bw : a.width - x0;
+    const fpred::in_ptr src = (fpred::in_ptr)a.work + b * a.slot;
+    const long long n = (long long)a.bw * a.cspp;
+    for (int r = blockIdx.y * 4 + wave; r < rows; r += gridDim.y * 4) {
+        const fpred::in_ptr row = src + (long long)r * n * ES;
+        for (int c = 0; c < a.cspp; ++c) {
+            g_T* const dst = (g_T*)a.out + (long long)(a.separate ? plane : c) * a.band_stride + (long long)(y0 + r) * a.stride + x0;
+            unsigned carry[W];
+#pragma unroll
+            for (int w = 0; w < W; ++w) carry[w] = 0;
+            for (int x = lane; x < a.bw; x += 64) {
+#pragma unroll
+                for (int w = 0; w < W; ++w) carry[w] = fpred::add4(carry[w], fpred::load4(row, n, (long long)x * a.cspp + c, 4 * w));
+            }
+            unsigned before = 0;
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                unsigned t = carry[w];
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) t = fpred::add4(t, __shfl_xor(t, d, 64));
+                carry[w] = fpred::carries4(t, before);
+                before = (before + fpred::total4(t)) & 255u;
+            }
+            for (int xs = 0; xs < cols; xs += 64) {
+                const int x = xs + lane;
+                unsigned v[W];
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    v[w] = x < cols ? fpred::load4(row, n, (long long)x * a.cspp + c, 4 * w) : 0u;
+#pragma unroll
+                    for (int d = 1; d < 64; d <<= 1) {
+                        const unsigned o = __shfl_up(v[w], d, 64);
+                        if (lane >= d) v[w] = fpred::add4(v[w], o);
+                    }
+                    v[w] = fpred::add4(v[w], carry[w]);
+                    carry[w] = __shfl(v[w], 63, 64);
+                }
+                if (x < cols) {
+                    if constexpr (W == 1) dst[x] = v[0];
+                    else dst[x] = ((unsigned long long)v[0] << 32) | v[W - 1];
+                }
+            }
+        }
+    }
+}
+
 hipError_t launch_inflate_image(InflateArgs a, long long n_blocks, hipStream_t stream) {
     if (n_blocks < 1 || n_blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
     HK_LAUNCH(inflate_block_kernel, dim3((unsigned)n_blocks), dim3(inflate::WAVE), 0, stream, a);
@@ -130,6 +195,14 @@ hipError_t launch_untile(InflateArgs a, long long n_blocks, hipStream_t stream) 
                ((a.band_stride * a.es) % 16 == 0) && (((long long)a.bw * a.es) % 16 == 0);
     const int rows = a.bh < a.height ? a.bh : a.height;
     const dim3 grid((unsigned)n_blocks, (unsigned)((rows + 3) / 4 < 64 ? (rows + 3) / 4 : 64));
+    if (a.predictor == 3) {
+        switch (a.es) {
+            case 4: HK_LAUNCH(untile_fp_kernel<4>, grid, dim3(256), 0, stream, a); break;
+            case 8: HK_LAUNCH(untile_fp_kernel<8>, grid, dim3(256), 0, stream, a); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     switch (a.es) {
         case 1: HK_LAUNCH(untile_kernel<1>, grid, dim3(256), 0, stream, a); break;
         case 2: HK_LAUNCH(untile_kernel<2>, grid, dim3(256), 0, stream, a); break;

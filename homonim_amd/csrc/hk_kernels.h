@@ -349,7 +349,7 @@ struct InflateArgs {
     int vec_ok;                      // set by the launcher: rows may move as 16-byte groups
 };
 hipError_t launch_inflate_image(InflateArgs a, long long n_blocks, hipStream_t stream);
-// its second stage alone: the slots of the blocks with status 0 to the raster (untile_kernel<ES>)
+// its second stage alone: the slots of the blocks with status 0 to the raster (untile_kernel<ES>; predictor 3: untile_fp_kernel<ES>)
 hipError_t launch_untile(InflateArgs a, long long n_blocks, hipStream_t stream);
 // The same for LZW blocks, TIFF compression 5 (hk_lzw.hip): status[b] is 0 or an HK_LZW_* code.
 hipError_t launch_lzw_image(InflateArgs a, long long n_blocks, hipStream_t stream);

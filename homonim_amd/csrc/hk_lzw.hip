@@ -10,7 +10,8 @@
 // lzw_block_kernel: one wave per workgroup, one workgroup per block; hk_lzw_core.h is the decoder (and says why it stays inside
 // its memory, why it stops and how it is tested without a GPU).  The 32 KiB output ring, the 36 KiB string table and a 1 KiB input
 // window are 69 KiB of LDS: two workgroups per CU.  The raw bytes go to the block's slot in `work` (raw size rounded up to 16),
-// the status to status[block]; untile_kernel<ES> of hk_inflate.hip follows as it does there (launch_untile).
+// the status to status[block]; untile_kernel<ES> of hk_inflate.hip (untile_fp_kernel<ES> for predictor 3) follows as it does there
+// (launch_untile).
 #include <hip/hip_runtime.h>
 
 #include "hk_lzw_core.h"

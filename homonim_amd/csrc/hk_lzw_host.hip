@@ -1,8 +1,10 @@
 // hk_lzw_host.hip -- hk_lzw_image_host: the LZW blocks of a GeoTIFF image decoded on the calling thread, for callers without a
 // device at hand and as the default of the product's `inflate` switch.  The decoder is the HOST build of hk_lzw_core.h -- the
 // functions of lzw_block_kernel with a loop over the lane index in place of the wave -- and what untile_kernel<ES> does behind it
-// (crop, de-interleave, predictor 2) is plain C++ here.  No kernel, no HIP call.
+// (crop, de-interleave, predictor 2) is plain C++ here, and what untile_fp_kernel<ES> does for predictor 3 is the row function of
+// hk_fpred_core.h.  No kernel, no HIP call.
 #define HKI_HOST
+#include "hk_fpred_core.h"
 #include "hk_lzw_core.h"
 #include "hk_kernels.h"
 
@@ -22,6 +24,12 @@ void untile_block(const InflateArgs& a, int plane, int by, int bx, const unsigne
         const T* const row = src + (long long)r * a.bw * a.cspp;
         for (int c = 0; c < a.cspp; ++c) {
             T* const dst = static_cast<T*>(a.out) + (long long)(a.separate ? plane : c) * a.band_stride + (long long)(y0 + r) * a.stride + x0;
+            if constexpr (sizeof(T) >= 4) {
+                if (a.predictor == 3) {   // (4- and 8-byte samples only: the caller's check)
+                    fpred::unpredict_row<(int)sizeof(T), T>(reinterpret_cast<const unsigned char*>(row), a.bw, a.cspp, c, cols, dst);
+                    continue;
+                }
+            }
             T sum = 0;   // (predictor 2: a modular sum in the sample's width)
             for (int x = 0; x < cols; ++x) {
                 const T v = row[(long long)x * a.cspp + c];

@@ -70,7 +70,7 @@ class BlockLayout(NamedTuple):
     block_h: int
     tiled: int                   # 1: every block holds block_h rows; 0: the last strip is short
     separate: int                # 1: one plane per block, blocks ordered plane, block row, block column; 0: pixel-interleaved
-    predictor: int               # 1 none, 2 horizontal differencing
+    predictor: int               # 1 none, 2 horizontal differencing, 3 floating point (only for a hook whose ``predictors`` has 3)
 
 
 def _read_ifd(buf: bytes, offset: Optional[int] = None):
@@ -215,7 +215,10 @@ def read_tiff(path, inflater=None, lzw=None) -> TiffRaster:
     module itself imports no GPU code).  It is handed little-endian DEFLATE images only; anything else, and everything with
     None, is decoded here as ever.  ``lzw``: the same hook for LZW images (compression 5), under the same contract: the LZW
     streams of all blocks of a little-endian image with predictor 1 or 2 (e.g. ``Context.lzw_image`` or ``_hk.lzw_image_host``).
-    With None, and for big-endian and predictor-3 images, the blocks go through ``lzw_decode``, which is slow. """
+    With None, and for big-endian images, the blocks go through ``lzw_decode``, which is slow.  Predictor 3 (floating point): a
+    hook of either kind is handed such an image only if it has an attribute ``predictors`` that holds 3, as those of
+    ``homonim_amd._hk`` have -- it then undoes the predictor as ``_unpredict_float`` states it and returns the samples' bit
+    patterns; for a hook without the attribute the image is decoded here as with None. """
     with open(path, 'rb') as f:
         buf = f.read()
     bo, t, _ = _read_ifd(buf)
@@ -319,10 +322,11 @@ def _decode_image(buf, bo, t, inflater=None, lzw=None) -> np.ndarray:
     across, down = -(-w // bw), -(-h // bh)
     chunk_spp = 1 if planar == 2 else spp
     tiled = T_TILE_OFFSETS in t
-    # (a floating-point predictor is undone here, hook or not: the hook's contract knows predictors 1 and 2)
+    # (a hook's contract knows predictors 1 and 2; the floating-point predictor goes to a hook that names 3 in its ``predictors``
+    # and is undone here for every other)
     if compression == 5:
         inflater = lzw
-    if inflater is not None and compression != 1 and bo == '<' and predictor != 3:
+    if inflater is not None and compression != 1 and bo == '<' and (predictor != 3 or 3 in getattr(inflater, 'predictors', (1, 2))):
         if len(offs) != len(cnts) or len(offs) != (spp if planar == 2 else 1) * across * down:
             raise IoError(f'{len(offs)} block offsets and {len(cnts)} byte counts for {(spp if planar == 2 else 1) * across * down} blocks')
         layout = BlockLayout(dtype.itemsize, spp, h, w, bw, bh, int(tiled), int(planar == 2), predictor)

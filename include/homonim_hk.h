@@ -178,14 +178,20 @@ int hk_deflate_tiles_pred(hk_ctx* ctx, const void* planes, int32_t dtype, int32_
  * lengths to 258, overlapping copies) that inflates to exactly the block's raw size; bytes behind its Adler-32 are ignored.
  * Every block gets a status: 0, or why its stream was refused -- such a block is left out of the raster (the device call does not
  * write its pixels; the host call leaves them unspecified) and does not disturb the others.  Blocks are ordered plane (separate only), block row, block column, as TIFF
- * orders them. */
+ * orders them.
+ * The predictor (TIFF tag 317) is undone behind the decoder, row by block row.  2: s[i] = p[i] + s[i - 1] per sample of a pixel,
+ * modulo 2^(8 x sample_bytes).  3 (sample_bytes 4 and 8 only; libtiff's floating-point predictor): the row's block_w x (separate ?
+ * 1 : spp) x sample_bytes bytes are summed byte by byte modulo 256 at a distance of (separate ? 1 : spp) over the WHOLE row,
+ * straight across the plane boundaries; the summed row is sample_bytes planes of block_w x (separate ? 1 : spp) bytes, the most
+ * significant byte of every sample first, and the sample that is stored is little-endian.  The row is block_w wide in an edge
+ * tile too.  (The field took 1 and 2 at first; 3 was admitted later without a new version: an older library refuses it.) */
 typedef struct hk_inflate_layout {
     int32_t sample_bytes;      /* 1, 2, 4, 8; little-endian samples */
     int32_t spp, height, width;
     int32_t block_w, block_h;  /* tile size; strips: width, rows per strip */
     int32_t tiled;             /* 1: every block holds block_h rows; 0: the last strip is short */
     int32_t separate;          /* 1: one plane per block, blocks ordered plane, block row, block column; 0: pixel-interleaved */
-    int32_t predictor;         /* 1 none, 2 horizontal differencing */
+    int32_t predictor;         /* 1 none, 2 horizontal differencing, 3 floating point (sample_bytes 4 and 8 only) */
 } hk_inflate_layout;
 enum {
     HK_INFLATE_OK = 0,
@@ -233,7 +239,7 @@ enum {
 int hk_lzw_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
                  void* out, int64_t stride, int64_t band_stride, int32_t* status /* n_blocks or NULL */);
 /* The same image from the same arguments decoded on the calling thread: the decoder of the kernel compiled for the host, then crop,
- * de-interleaving and predictor 2 in plain C++.  No context, no device (like hk_inflate_bound); `out` aligned to its samples. */
+ * de-interleaving and predictors 2 and 3 in plain C++.  No context, no device (like hk_inflate_bound); `out` aligned to its samples. */
 int hk_lzw_image_host(const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes, void* out,
                       int64_t stride, int64_t band_stride, int32_t* status /* n_blocks or NULL */);
 

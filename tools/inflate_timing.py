@@ -9,6 +9,10 @@ this package and GDAL write by default) and with the device compressor (``Contex
   * the two kernels alone on device-resident streams (``hk_inflate_image_dev`` between two events; warm-ups, median of >= 10),
     as decoded GB/s;
   * whether the two arrays are equal.
+``--predictor`` 2 or 3 writes the files with that TIFF predictor (tag 317): the rasters whose samples it applies to -- for 3 the
+float32 one and a 3-band float32 parameter raster (``param_raster``) -- and the host path then is zlib + the predictor in numpy.
+The kernels of the predictor-1 twin of the same raster are timed in the same run, so that a ``rocprofv3 --kernel-trace --stats``
+run of this script (a run of its own) shows the second stage with and without the predictor side by side.
 The host time of the same file on the same box is what the device time is compared with.  The report goes to stdout and to
 ``--out``. """
 import argparse
@@ -26,6 +30,29 @@ from homonim_amd.tiff import read_tiff, write_tiff  # noqa: E402
 from tools.deflate_timing import TF, rasters  # noqa: E402
 
 
+def param_raster(size):
+    """ a parameter image as the product writes it: gains, offsets and r2 of one band, float32, NaN where nothing was fitted """
+    rng = np.random.default_rng(1)
+    y, x = np.mgrid[0:size, 0:size].astype(np.float32)
+    gain = 1.0 + 0.2 * np.sin(x / 97.0) * np.cos(y / 131.0) + rng.normal(0, 0.01, (size, size))
+    offset = 5.0 + 3.0 * np.cos(x / 211.0) + rng.normal(0, 0.05, (size, size))
+    r2 = np.clip(0.8 + rng.normal(0, 0.1, (size, size)), 0, 1)
+    p = np.stack([gain, offset, r2]).astype(np.float32)
+    frame = max(1, size // 32)
+    p[:, :frame] = p[:, -frame:] = np.nan
+    p[:, :, :frame] = p[:, :, -frame:] = np.nan
+    return 'float32 3 bands, parameter raster', p, float('nan')
+
+
+def rasters_for(size, predictor):
+    """ the rasters of tools/deflate_timing.py that ``predictor`` applies to; with 3 the parameter raster too """
+    for name, arr, nodata in rasters(size):
+        if predictor == 1 or (predictor == 3) == (arr.dtype.kind == 'f'):
+            yield name, arr, nodata
+    if predictor == 3:
+        yield param_raster(size)
+
+
 def file_blocks(path):
     """ (streams, layout) of a file, as read_tiff hands them to its hook """
     seen = []
@@ -34,6 +61,7 @@ def file_blocks(path):
         seen.append((streams, layout))
         raise StopIteration
 
+    grab.predictors = _hk.PREDICTORS   # (asked for predictor-3 files too)
     try:
         read_tiff(path, inflater=grab)
     except StopIteration:
@@ -84,18 +112,25 @@ def main():
     ap.add_argument('--tile', type=int, default=512)
     ap.add_argument('--reps', type=int, default=3, help='timed read_tiff calls per path')
     ap.add_argument('--kernel-reps', type=int, default=10)
+    ap.add_argument('--predictor', type=int, default=1, choices=(1, 2, 3), help='TIFF predictor of the files (2: the integer rasters, 3: the float ones)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     ctx = _hk.default_context()
     k_reps = max(10, a.kernel_reps)
-    lines = [f'# tools/inflate_timing.py --size {a.size} --tile {a.tile}: read_tiff with host zlib against Context.inflate_image',
+    lines = [f'# tools/inflate_timing.py --size {a.size} --tile {a.tile} --predictor {a.predictor}: read_tiff with host zlib against Context.inflate_image',
              f'# host path: median of {a.reps}; device path: one warm-up, median of {a.reps}; kernels: two warm-ups, median of {k_reps} event pairs']
     with tempfile.TemporaryDirectory() as tmp:
-        for name, arr, nodata in rasters(a.size):
+        for name, arr, nodata in rasters_for(a.size, a.predictor):
             lines.append(f'{name}: {arr.shape}, {arr.nbytes / 1e6:.1f} MB raw')
+            if a.predictor != 1:   # the predictor-1 twin's kernels: the same raster through the second stage without a predictor
+                twin = os.path.join(tmp, 'twin.tif')
+                write_tiff(twin, arr, TF, CRS('EPSG:32735'), nodata=nodata, tile=a.tile, compressor=ctx.deflate_tiles)
+                ms, _, all_ok = kernels_ms(ctx, *file_blocks(twin), k_reps)
+                lines.append(f'  predictor-1 twin (the device compressor): kernels alone  median {np.median(ms):8.3f} ms, min {min(ms):.3f}, max {max(ms):.3f}'
+                             f'   ({arr.nbytes / 1e6 / np.median(ms):7.2f} GB/s decoded; every status 0: {all_ok})')
             for written, compressor in (('host zlib level 6', None), ('the device compressor', ctx.deflate_tiles)):
                 path = os.path.join(tmp, 'f.tif')
-                write_tiff(path, arr, TF, CRS('EPSG:32735'), nodata=nodata, tile=a.tile, compressor=compressor)
+                write_tiff(path, arr, TF, CRS('EPSG:32735'), nodata=nodata, tile=a.tile, compressor=compressor, predictor=a.predictor)
                 host_s, dev_s = [], []
                 for _ in range(a.reps):
                     t0 = time.perf_counter()

@@ -12,6 +12,9 @@ it is plain Python).  Per raster:
   * the kernels alone on device-resident streams (``hk_lzw_image_dev`` between two events; warm-ups, median of >= 10), as decoded
     GB/s -- per-kernel times come from a ``rocprofv3 --kernel-trace --stats`` run of this script, a run of its own;
   * whether all arrays are equal.
+``--predictor`` 2 or 3 writes both files with that TIFF predictor (tag 317; the re-coding keeps it): the rasters whose samples it
+applies to, as in tools/inflate_timing.py.  ``--python-crop N``: the plain-Python reader (``tiff.lzw_decode``, what reads an LZW
+file where no hook takes it) is timed once on the LZW file of the N x N pixels in the middle of the first band.
 The report goes to stdout and to ``--out``. """
 import argparse
 import os
@@ -29,7 +32,8 @@ import _lzw_streams as st  # noqa: E402
 from homonim_amd import _hk  # noqa: E402
 from homonim_amd.geo import CRS  # noqa: E402
 from homonim_amd.tiff import read_tiff, write_tiff  # noqa: E402
-from tools.deflate_timing import TF, rasters  # noqa: E402
+from tools.deflate_timing import TF  # noqa: E402
+from tools.inflate_timing import rasters_for  # noqa: E402
 
 
 def file_blocks(path):
@@ -40,6 +44,7 @@ def file_blocks(path):
         seen.append((streams, layout))
         raise StopIteration
 
+    grab.predictors = _hk.PREDICTORS   # (asked for predictor-3 files too)
     try:
         read_tiff(path, lzw=grab)
     except StopIteration:
@@ -79,6 +84,12 @@ def kernels_ms(ctx, streams, lay, reps):
             ctx.dev_free(p)
 
 
+def middle(arr, n):
+    """ the n x n pixels in the middle of the first band """
+    y0, x0 = (arr.shape[1] - n) // 2, (arr.shape[2] - n) // 2
+    return np.ascontiguousarray(arr[:1, y0:y0 + n, x0:x0 + n])
+
+
 def timed(f, reps):
     runs = []
     for _ in range(reps):
@@ -95,24 +106,35 @@ def main():
     ap.add_argument('--reps', type=int, default=3, help='timed read_tiff calls per path')
     ap.add_argument('--kernel-reps', type=int, default=10)
     ap.add_argument('--workers', type=int, default=16, help='processes of the test encoder')
+    ap.add_argument('--predictor', type=int, default=1, choices=(1, 2, 3), help='TIFF predictor of the files (2: the integer rasters, 3: the float ones)')
+    ap.add_argument('--python-crop', type=int, default=0, help='time the plain-Python reader on a crop of this many pixels a side (0: not)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     k_reps = max(10, a.kernel_reps)
-    lines = [f'# tools/lzw_timing.py --size {a.size} --tile {a.tile}: read_tiff of an LZW file through Context.lzw_image and through '
+    lines = [f'# tools/lzw_timing.py --size {a.size} --tile {a.tile} --predictor {a.predictor}: read_tiff of an LZW file through Context.lzw_image and through '
              '_hk.lzw_image_host, and of its DEFLATE twin through host zlib',
              f'# host paths: median of {a.reps}; device path: one warm-up, median of {a.reps}; kernels: two warm-ups, median of {k_reps} event pairs']
     with tempfile.TemporaryDirectory() as tmp, ProcessPoolExecutor(a.workers) as pool:
         # (the files first: the encoder's processes are forked before this one opens the device)
         made = []
-        for name, arr, nodata in rasters(a.size):
-            deflate, lzw = os.path.join(tmp, name.split()[0] + '_deflate.tif'), os.path.join(tmp, name.split()[0] + '_lzw.tif')
-            write_tiff(deflate, arr, TF, CRS('EPSG:32735'), nodata=nodata, tile=a.tile, bigtiff='no')
+        for k, (name, arr, nodata) in enumerate(rasters_for(a.size, a.predictor)):
+            deflate, lzw = os.path.join(tmp, f'{k}_deflate.tif'), os.path.join(tmp, f'{k}_lzw.tif')
+            write_tiff(deflate, arr, TF, CRS('EPSG:32735'), nodata=nodata, tile=a.tile, bigtiff='no', predictor=a.predictor)
             t0 = time.perf_counter()
             with open(deflate, 'rb') as f, open(lzw, 'wb') as g:
                 g.write(st.lzw_copy(f.read(), mapper=lambda fn, items: pool.map(fn, items, chunksize=1)))
-            made.append((name, arr, deflate, lzw, time.perf_counter() - t0))
+            crop = None
+            if a.python_crop:
+                crop = os.path.join(tmp, f'{k}_crop_lzw.tif')
+                write_tiff(crop, middle(arr, a.python_crop), TF, CRS('EPSG:32735'), nodata=nodata, tile=min(a.tile, 256),
+                           bigtiff='no', predictor=a.predictor)
+                with open(crop, 'rb') as f:
+                    data = st.lzw_copy(f.read(), mapper=lambda fn, items: pool.map(fn, items, chunksize=1))
+                with open(crop, 'wb') as g:
+                    g.write(data)
+            made.append((name, arr, deflate, lzw, time.perf_counter() - t0, crop))
         ctx = _hk.default_context()
-        for name, arr, deflate, lzw, enc_s in made:
+        for name, arr, deflate, lzw, enc_s, crop in made:
             zlib_out, zlib_s = timed(lambda: read_tiff(deflate).array, a.reps)
             host_out, host_s = timed(lambda: read_tiff(lzw, lzw=_hk.lzw_image_host).array, a.reps)
             dev_out, dev_s = timed(lambda: read_tiff(lzw, lzw=ctx.lzw_image).array, a.reps + 1)
@@ -131,6 +153,11 @@ def main():
                 f'    kernels alone (device-resident)  median {np.median(ms):8.3f} ms, min {min(ms):.3f}, max {max(ms):.3f}'
                 f'   ({mb / np.median(ms):7.2f} GB/s decoded; every status 0: {all_ok})',
             ]
+            if crop:
+                part = middle(arr, a.python_crop)
+                py_out, py_s = timed(lambda: read_tiff(crop).array, 1)
+                lines.append(f'    read_tiff LZW, plain Python (tiff.lzw_decode) on the crop {part.shape}, {part.nbytes / 1e6:.1f} MB raw: {py_s[0]:8.2f} s'
+                             f'   ({part.nbytes / 1e6 / py_s[0]:7.2f} MB/s)   equal to the crop: {py_out.tobytes() == part.tobytes()}')
     text = '\n'.join(lines) + '\n'
     print(text, end='')
     if a.out:
