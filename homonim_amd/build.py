@@ -56,7 +56,7 @@ def _run(cmd):
 def build_hip(force: bool = False, verbose: bool = True) -> str:
     """ Compile homonim_amd/csrc/*.hip for gfx950 into homonim_amd/lib/libhomonim_hk.so (in-tree). """
     os.makedirs(LIB_DIR, exist_ok=True)
-    headers = [os.path.join(CSRC, 'hk_kernels.h'), os.path.join(CSRC, 'hk_fit_kernel.h'), os.path.join(CSRC, 'hk_resample_taps.h'), os.path.join(CSRC, 'hk_deflate_core.h'),
+    headers = [os.path.join(CSRC, 'hk_kernels.h'), os.path.join(CSRC, 'hk_layout.h'), os.path.join(CSRC, 'hk_fit_kernel.h'), os.path.join(CSRC, 'hk_resample_taps.h'), os.path.join(CSRC, 'hk_deflate_core.h'),
                os.path.join(CSRC, 'hk_inflate_core.h'), os.path.join(CSRC, 'hk_lzw_core.h'), os.path.join(CSRC, 'hk_fpred_core.h'),
                os.path.join(REPO, 'include', 'homonim_hk.h'),
                os.path.join(REPO, 'include', 'homonim_hk_devtools.h')]

@@ -462,15 +462,8 @@ int grow_slot_buf(Slot& s, T*& buf, size_t& have, size_t need, size_t slack = 0)
 // the staging slab of the host-pointer calls (an eighth to spare)
 int ensure_dev(Slot& s, size_t bytes) { return grow_slot_buf(s, s.dev, s.dev_bytes, bytes, bytes / 8); }
 
-// Bump allocation inside the staging slab: every buffer at a 256-byte aligned offset, in the order it is taken.
-struct SlabLayout {
-    size_t total = 0;
-    size_t take(size_t bytes) {
-        const size_t off = total;
-        total += (bytes + 255) / 256 * 256;
-        return off;
-    }
-};
+// Bump allocation inside the staging slab: every buffer at a 256-byte aligned offset, in the order it is taken (hk_layout.h).
+using hk::SlabLayout;
 
 // How a host-pointer call opens: a leased slot whose staging slab holds `bytes` (rc says whether it does), and the buffers of
 // the call's layout inside it.
@@ -1003,10 +996,29 @@ void fill_grid(hk::FitArgs& a, int seg_rows, const LaunchPolicy& lp) {
     if (a.lds_pad < 0) a.lds_pad = lds_pad_of((long long)a.height * a.width * a.n_bands);
 }
 
-// scratch of the in-painting branch: [offset | column tables]
-static int ensure_inpaint_scratch(Slot& sl, size_t plane, int height, long long stride) {
-    return grow_slot_buf(sl, sl.aux, sl.aux_bytes, plane + hk::inpaint_workspace_bytes(height, stride));
+// The slot's scratch of the in-painting branch for a height x stride plane, [offset plane | workspace of launch_inpaint_offsets]:
+// the one place that knows it.  Grows sl.aux as needed (which lock covers that is the caller's business).  Rows are padded
+// to quads (stride % 4 == 0), so the workspace's base is 16-byte aligned behind the plane.
+struct InpaintScratch {
+    float* offset;        // an offset plane for a pass whose caller keeps none
+    unsigned char* flag;  // the workspace's source-flag plane, for a fit to write (FitArgs::flag)
+    void* ws;             // the workspace
+};
+static int inpaint_scratch(Slot& sl, int height, long long stride, InpaintScratch& s) {
+    const size_t plane = (size_t)stride * height * sizeof(float);
+    const int rc = grow_slot_buf(sl, sl.aux, sl.aux_bytes, plane + hk::inpaint_workspace_bytes(height, stride));
+    if (rc) return rc;
+    s.offset = static_cast<float*>(sl.aux);
+    s.ws = static_cast<char*>(sl.aux) + plane;
+    s.flag = hk::inpaint_flag_plane(s.ws, height, stride);
+    return HK_OK;
 }
+// What the in-painting of a band reads, where a pass has left it ready: the offsets and the source flags (r2 > thresh) & (gain > 0)
+// & valid that the fused kernel writes beside them (FitArgs::flag)
+struct InpaintInputs {
+    float* offset;
+    const unsigned char* flag;
+};
 
 // gain-offset with the r2 mask when nothing but the corrected block (and, from scratch, the offsets) is asked for and the failures
 // are counted: the CERTIFICATE build runs first (118 - 126 registers, four waves per SIMD: the division-free float32 certificate of
@@ -1050,44 +1062,44 @@ static int launch_fit(hk_ctx* ctx, Slot& sl, hk::FitArgs& a, const hk_fit_desc* 
 // kernel_model.py:364-371 for ONE band whose first pass counted failing pixels: in-paint the offsets of the failing
 // pixels from the passing ones (restated GDALFillNodata) and run the fit again with `offset_in`, which recomputes their
 // gains and re-applies.  `a` is the first pass's argument block (n_bands == 1).
-// `n_fail`: the band's r2-mask failure count.  `pre_offset` / `pre_flag` (both or neither): offsets and source flags (r2 > thresh) & (gain > 0) & valid left by the pass
-// that counted the failures (FitArgs::flag) -- the in-painting then starts right away.  `drop_params`: the parameter
-// planes in `a` are scratch, the closing pass need not write them.
-static int inpaint_band(Slot& sl, const hk::FitArgs& a, const hk_fit_desc* desc, bool r2, size_t plane,
-                        unsigned long long n_fail, bool drop_params = false, float* pre_offset = nullptr,
-                        const unsigned char* pre_flag = nullptr) {
+// `n_fail`: the band's r2-mask failure count.  `ready` (nullable): the in-painting's inputs as the pass that counted the failures
+// left them -- the in-painting then starts right away.  `drop_params`: the parameter planes in `a` are scratch, the closing pass
+// need not write them.
+static int inpaint_band(Slot& sl, const hk::FitArgs& a, const hk_fit_desc* desc, bool r2, unsigned long long n_fail,
+                        const InpaintInputs* ready, bool drop_params = false) {
+    InpaintScratch s;
     {
-        const int rc = ensure_inpaint_scratch(sl, plane, a.height, a.stride);
+        const int rc = inpaint_scratch(sl, a.height, a.stride, s);
         if (rc) return rc;
     }
     const hipStream_t stream = sl.stream;
-    char* aux = static_cast<char*>(sl.aux);
-    const float *pg = a.gain, *pr = a.r2;
-    float* po = a.offset;
-    const unsigned char* flags = nullptr;
-    if (pre_offset && pre_flag) {
-        po = pre_offset, flags = pre_flag;
-    } else if (!pg || !po || !pr) {
+    InpaintInputs in = {a.offset, nullptr};  // the caller's own planes: the in-painting makes the flags from gain / r2
+    if (ready) {
+        in = *ready;
+    } else if (!a.gain || !a.offset || !a.r2) {
         // parameters were not materialised by the first pass: run it again for what the in-painting reads -- the offsets
         // and the source flags, which the kernel writes itself (1 byte per pixel)
-        float* scratch_off = reinterpret_cast<float*>(aux);
         hk::FitArgs b = a;
-        b.gain = nullptr, b.r2 = nullptr, b.offset = scratch_off, b.corr = nullptr, b.fail_count = nullptr;
-        b.flag = hk::inpaint_flag_plane(aux + plane, a.height, a.stride);
+        b.gain = nullptr, b.r2 = nullptr, b.offset = s.offset, b.corr = nullptr, b.fail_count = nullptr;
+        b.flag = s.flag;
         b.cert_only = 0, b.open_rows = nullptr, b.list_mode = 0;
         HK_HIP(hk::launch_fit_apply(b, desc->model, r2, stream));
-        po = scratch_off, flags = b.flag;
+        in = {s.offset, s.flag};  // the slot's scratch, written by the pass just queued
     }
     // The failing pixels' offsets are in-painted IN PLACE (round 5; a separate `filled` plane cost a pass-through of every source
     // pixel): sources are read only where the flag is 1, targets written only where it is 0, and the closing pass -- which reads the
     // plane at the failing pixels only -- rewrites the caller's offset plane whole when there is one.
-    HK_HIP(hk::launch_inpaint_offsets(po, pg, pr, desc->r2_thresh, a.stride, a.height, a.width, aux + plane, stream, flags, n_fail));
+    hk::InpaintArgs ia;
+    ia.offset = in.offset, ia.stride = a.stride, ia.height = a.height, ia.width = a.width;
+    ia.flag_ready = in.flag, ia.gain = a.gain, ia.r2 = a.r2, ia.thresh = desc->r2_thresh;
+    ia.n_targets = n_fail;
+    HK_HIP(hk::launch_inpaint_offsets(ia, s.ws, stream));
     // closing pass: the failing pixels take the in-painted offsets and recomputed gains (kernel_model.py:370-371).  Which
     // pixels failed is in the flag plane the in-painting just used, so the build WITHOUT the R2 work runs (the R2 plane, if
     // the caller keeps one, was written by the pass that counted and is not changed by the branch)
     hk::FitArgs c = a;
-    c.offset_in = po;
-    c.flag_in = flags ? flags : hk::inpaint_flag_plane(aux + plane, a.height, a.stride);
+    c.offset_in = in.offset;
+    c.flag_in = in.flag ? in.flag : s.flag;
     c.fail_count = nullptr;  // already counted
     c.flag = nullptr;
     c.r2 = nullptr;
@@ -1148,10 +1160,10 @@ int fit_finish(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, FitPending& p, un
     if (!p.active) return HK_OK;
     hk::FitArgs& a = p.a;
     const bool r2 = needs_r2(desc);
-    const size_t plane = (size_t)a.stride * a.height * sizeof(float);
     ctx->expect_r2_failures.store(n_fail > 0 ? 1 : 0);
     if (n_fail > 0) {
-        const int rc = inpaint_band(sl, a, desc, r2, plane, n_fail, p.scratch_params, a.flag ? a.offset : nullptr, a.flag);
+        const InpaintInputs first_pass = {a.offset, a.flag};  // written by fit_on_device's pass where it expected failures (a.flag set)
+        const int rc = inpaint_band(sl, a, desc, r2, n_fail, a.flag ? &first_pass : nullptr, p.scratch_params);
         if (rc) return rc;
         *requeued = true;
     }
@@ -1169,7 +1181,6 @@ int fit_on_device(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, const double* 
                   const int* win = nullptr) {
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
     const bool r2 = needs_r2(desc);
-    const size_t plane = (size_t)stride * height * sizeof(float);
     HK_HIP(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), sl.stream));
     if (blk) {
         if (norm_in) {
@@ -1194,14 +1205,14 @@ int fit_on_device(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, const double* 
     if (rc) return rc;
     p.scratch_params = false;
     if (a.has_thresh && desc->model == HK_MODEL_GAIN_OFFSET && ctx->expect_r2_failures.load()) {
-        // what the in-painting reads -- offsets and source flags -- into the slot's scratch right away (layout of
-        // inpaint_band): no second "first pass".  With the caller's own offset plane only the flags are scratch.
-        rc = ensure_inpaint_scratch(sl, plane, height, stride);
+        // what the in-painting reads -- offsets and source flags -- into the slot's scratch right away: no second "first
+        // pass" (fit_finish hands them to inpaint_band).  With the caller's own offset plane only the flags are scratch.
+        InpaintScratch s;
+        rc = inpaint_scratch(sl, height, stride, s);
         if (rc) return rc;
-        char* aux = static_cast<char*>(sl.aux);
-        a.flag = hk::inpaint_flag_plane(aux + plane, height, stride);
+        a.flag = s.flag;
         if (!d_off) {
-            a.offset = reinterpret_cast<float*>(aux);
+            a.offset = s.offset;
             p.scratch_params = !d_gain && !d_r2;
         }
     }
@@ -2290,7 +2301,6 @@ int hk_inpaint_dev_counts(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_job
     HK_ENTER(ctx);
     Slot& sl = ctx->slots[job->stream];
     const bool r2 = needs_r2(desc);
-    const size_t plane = (size_t)job->stride * job->height * sizeof(float);
     unsigned long long total = 0;
     for (int b = 0; b < job->n_bands; ++b) {
         unsigned long long n_fail = counts[b];
@@ -2300,14 +2310,10 @@ int hk_inpaint_dev_counts(hk_ctx* ctx, const hk_fit_desc* desc, const hk_dev_job
         if ((rc = job_fit_args(a, ctx, desc, *job, b))) return rc;
         std::unique_lock<std::mutex> lk(ctx->mu);  // the slot's scratch may be (re)allocated
         // offsets + source flags left by the pass that counted, which writes them whenever the job carries scratch (hk_fit_apply_dev)
-        float* pre_off = nullptr;
-        const unsigned char* pre_flag = nullptr;
-        if (job->scratch) {
-            pre_flag = job_scratch_flag(job) + off;
-            pre_off = a.offset ? a.offset : job_scratch_offset(job) + off;
-        }
+        InpaintInputs left = {};
+        if (job->scratch) left = {a.offset ? a.offset : job_scratch_offset(job) + off, job_scratch_flag(job) + off};
         total += n_fail;
-        rc = inpaint_band(sl, a, desc, r2, plane, n_fail, false, pre_off, pre_flag);
+        rc = inpaint_band(sl, a, desc, r2, n_fail, job->scratch ? &left : nullptr);
         if (rc) return rc;
     }
     if (n_fail_out) *n_fail_out = total;
@@ -3358,9 +3364,10 @@ int hk_debug_inpaint_plane_dev(hk_ctx* ctx, float* plane_dev, const uint8_t* fla
     HK_ENTER(ctx);
     DevEnter entered(ctx, stream);
     Slot& sl = ctx->slots[stream];
+    InpaintScratch s;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);  // the slot's scratch may be (re)allocated
-        const int rc = ensure_inpaint_scratch(sl, 0, height, stride);
+        const int rc = inpaint_scratch(sl, height, stride, s);
         if (rc) return rc;
     }
     unsigned long long n_targets = 0;  // mode 1: unknown -> row order
@@ -3387,8 +3394,11 @@ int hk_debug_inpaint_plane_dev(hk_ctx* ctx, float* plane_dev, const uint8_t* fla
                 n_targets += flags_dev ? hf[i] == 0 : !((hr[i] > thresh) && (hg[i] > 0.f));
             }
     }
-    HK_HIP(hk::launch_inpaint_offsets(plane_dev, gain_dev, r2_dev, thresh, stride, height, width, sl.aux, sl.stream, flags_dev,
-                                      n_targets, mode != 3));
+    hk::InpaintArgs ia;
+    ia.offset = plane_dev, ia.stride = stride, ia.height = height, ia.width = width;
+    ia.flag_ready = flags_dev, ia.gain = gain_dev, ia.r2 = r2_dev, ia.thresh = thresh;
+    ia.n_targets = n_targets, ia.packed_search = mode != 3;
+    HK_HIP(hk::launch_inpaint_offsets(ia, s.ws, sl.stream));
     HK_HIP(hipStreamSynchronize(sl.stream));
     return HK_OK;
 }

@@ -4,18 +4,22 @@
 // smoothing_iterations = 0).  GDAL is not part of /root/reference (rasterio>=1.1, un-pinned) and not installed here,
 // so its published algorithm (gdal/alg/rasterfill.cpp) is RESTATED -- parity with GDAL itself is unpinned:
 //   * two column scans give, for every pixel, the nearest source pixel (mask != 0) at-or-above it and strictly below
-//     it in its own column, carried at most `max_dist` rows (kept here as uint16 row distances);
+//     it in its own column, carried at most `max_dist` rows (kept here squared, two 15-bit halves of a 32-bit table entry);
 //   * a target pixel (mask == 0) steps left and right one column at a time (0..max_dist) and keeps, per quadrant
 //     (top-left and bottom-left include the pixel's own column, the right quadrants do not), the closest source found
 //     through those column tables -- strict `<` on the squared distance, so the first one met wins ties;
 //   * value = sum(v_q / d_q) / sum(1 / d_q) over the quadrants with d_q <= max_dist, in float64, cast to float32;
 //     targets without any source keep their value.  Filled pixels never act as sources.
-// GDAL runs this sequentially line by line; every target is independent given the column tables.  Here:
-//   inpaint_bits_kernel   the flags of a column as 64-row bit words (sources; targets)
-//   inpaint_table_kernel  the column table: squared row distances up / down per pixel, from the bit words
-//   inpaint_fill_fast_kernel     the PACKED search (16-bit keys on a table tile staged in LDS) for the targets with sources nearby
-//                                -- the usual case; what it cannot settle it marks in a third bit plane
-//   inpaint_fill_general_kernel  GDAL's search as it stands (32-bit keys, up to max_dist columns) for the marked targets
+// GDAL runs this sequentially line by line; every target is independent given the column tables.  Here, per call, the pieces of
+// the workspace (csrc/hk_layout.h inpaint_layout(): where each lies and how large it is) and the kernels that write them, in launch order:
+//   tie bitmap, weight table      tie_kernel            which squared distances GDAL's float comparison ties on; 1 / sqrt(n)
+//   flag plane                    inpaint_flag_kernel   1 byte per pixel: 1 source, 0 target, else neither (or the fit kernel wrote it)
+//   packed search's tables        fast_table_kernel     the finish of the packed search: signed weights and small square roots
+//   bit planes: sources, targets  inpaint_bits_kernel   the flags of a column as 64-row bit words
+//   distance table                inpaint_table_kernel  squared row distances up / down per pixel, from the source bit words
+//   bit plane: left-over targets  inpaint_fill_fast_kernel     the PACKED search (16-bit keys on a table tile staged in LDS) for the
+//                                 targets with sources nearby -- the usual case; what it cannot settle it marks in this plane
+//   (the offset plane)            inpaint_fill_general_kernel  GDAL's search as it stands (32-bit keys, up to max_dist columns) for them
 // The filled values are written in place (sources are read where the flag is 1 only).
 #include "hk_kernels.h"
 
@@ -54,7 +58,7 @@ __global__ void __launch_bounds__(256) inpaint_flag_kernel(const float* __restri
 // band whatever its chunk height, load width or unrolling: its loads sit behind data-dependent state updates.
 constexpr unsigned NONE_B = 0xffu;      // (row-distance byte of the table kernel's sweeps: none in reach)
 constexpr unsigned NONE_SQ = 0x7fffu;  // squared-distance half of a table entry: none in reach (beats nothing: > 2 * 101^2)
-constexpr int WORD_ROWS = 64;
+// (WORD_ROWS, the rows of a bit word: hk_layout.h)
 
 __global__ void __launch_bounds__(256) inpaint_bits_kernel(const unsigned char* __restrict__ flag, long long stride, int height,
                                                            int width, unsigned long long* __restrict__ bits,
@@ -92,7 +96,7 @@ __global__ void __launch_bounds__(256) inpaint_table_kernel(const unsigned long 
                                                             int height, int width, int max_dist,
                                                             unsigned* __restrict__ tb) {
     // a thread makes the entries of TWO adjacent columns and stores them as one 8-byte pair per row (rows are padded: stride % 4 == 0;
-    // the table starts 256-byte aligned)
+    // the table starts 16-byte aligned: the workspace's base, hk_layout.h)
     const int x = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
     if (x >= width) return;
     const int wb = blockIdx.y, n_words = (height + WORD_ROWS - 1) / WORD_ROWS;
@@ -149,9 +153,10 @@ __global__ void __launch_bounds__(256) inpaint_table_kernel(const unsigned long 
 // so a candidate at the SAME squared distance n replaces the current source exactly when fl(fl(sqrt(n))^2) > n.  That is a
 // property of n alone: tie_kernel tabulates it as a bitmap (TIE_N bits), and the search itself runs on integers -- no
 // sqrt and no float64 in the loop, same decisions.
-constexpr int TIE_N = 2 * 102 * 102;  // > the largest squared distance the search can meet (100^2 + 101^2)
 constexpr int FILL_MAX_DIST = 100;  // rasterio.fill.fillnodata default max_search_distance (kernel_model.py:366)
-constexpr int WTAB_N = FILL_MAX_DIST * FILL_MAX_DIST + 1;  // weights 1 / qd of the accepted distances (qd <= max_dist = 100)
+// (TIE_N and WTAB_N size pieces of the workspace: hk_layout.h)
+static_assert(TIE_N > FILL_MAX_DIST * FILL_MAX_DIST + (FILL_MAX_DIST + 1) * (FILL_MAX_DIST + 1) && WTAB_N == FILL_MAX_DIST * FILL_MAX_DIST + 1,
+              "the tie bitmap and the weight table cover the search distance");
 __global__ void __launch_bounds__(256) tie_kernel(unsigned* __restrict__ tie, double* __restrict__ wtab) {
     const int word = blockIdx.x * blockDim.x + threadIdx.x;
     // the inverse-distance weights GDAL forms as 1.0 / qd with qd = sqrt(n): a table instead of a sqrt and a division
@@ -197,150 +202,150 @@ template <bool INTERIOR = false>
 __device__ __forceinline__ float fill_one(int x, int y, long long row, const float* offset, long long stride, int width,
                                           int max_dist, const unsigned* __restrict__ tb, const unsigned* __restrict__ tie,
                                           const double* __restrict__ wtab, bool no_below = false) {
-        const long long i = row + x;
-        float out = offset[i];  // a target without any source in reach keeps its value
-        const int none2 = (max_dist + 1) * (max_dist + 1);  // qd = max_dist + 1: "nothing found yet" (a perfect square: no tie)
-        // Per quadrant the search state is two KEYS (round 4): (squared distance << 15) | (column distance << 8).  The smallest key
-        // is the FIRST candidate met at the best distance (steps ascend, so among equal distances the smallest column distance came
-        // first), the smallest key with the low 15 bits inverted is the LAST one: two unsigned minima per candidate instead of two
-        // compares and three selects.  A candidate that does not beat "nothing found yet" leaves the initial keys in place; quadrants
-        // whose best distance exceeds max_dist are dropped at the end as before.  (Round 5: the table holds SQUARED row distances, so a
-        // candidate's key is one shift-add of its table half and the step's constant; the row distance of the winner is the exact
-        // square root of what is left of its squared distance at the finish.)
-        constexpr unsigned SRC_BITS = 15u, SRC_MASK = (1u << SRC_BITS) - 1u;
-        unsigned kf[4], kl[4];
+    const long long i = row + x;
+    float out = offset[i];  // a target without any source in reach keeps its value
+    const int none2 = (max_dist + 1) * (max_dist + 1);  // qd = max_dist + 1: "nothing found yet" (a perfect square: no tie)
+    // Per quadrant the search state is two KEYS (round 4): (squared distance << 15) | (column distance << 8).  The smallest key
+    // is the FIRST candidate met at the best distance (steps ascend, so among equal distances the smallest column distance came
+    // first), the smallest key with the low 15 bits inverted is the LAST one: two unsigned minima per candidate instead of two
+    // compares and three selects.  A candidate that does not beat "nothing found yet" leaves the initial keys in place; quadrants
+    // whose best distance exceeds max_dist are dropped at the end as before.  (Round 5: the table holds SQUARED row distances, so a
+    // candidate's key is one shift-add of its table half and the step's constant; the row distance of the winner is the exact
+    // square root of what is left of its squared distance at the finish.)
+    constexpr unsigned SRC_BITS = 15u, SRC_MASK = (1u << SRC_BITS) - 1u;
+    unsigned kf[4], kl[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) kf[q] = kl[q] = ((unsigned)none2 << SRC_BITS) | SRC_MASK;
-        const unsigned* __restrict__ trow = tb + row;
-        // GDAL's QUAD_CHECK on squared integer distances.  `sq` is the column table's half word: NONE_SQ (no source in reach) is more
-        // than any squared distance the search accepts and more than the initial (max_dist + 1)^2, so it never wins.
-        // A candidate at the SAME squared distance replaces the holder iff GDAL's float comparison says so for that distance (the
-        // `tie` bit of c) -- a property of c alone: with the bit set the last candidate met at the best distance wins, without it
-        // the first.  So the search keeps both, branch-free, and the bit is looked up once per quadrant at the end instead of behind
-        // a divergent branch in every one of the 34 candidate tests.
-        // dxk = (dx^2 << 15) | (dx << 8): the step's share of the key (wave-uniform away from the raster's edge columns)
-        auto consider = [&](int q, unsigned sq, unsigned dxk) {
-            const unsigned key = (sq << SRC_BITS) + dxk;
-            kf[q] = min(kf[q], key);
-            kl[q] = min(kl[q], key ^ SRC_MASK);
-        };
-        // `no_below` (the raster's last row): no source lies strictly below, the bottom quadrants stay empty whatever is searched --
-        // GDAL walks all max_dist columns for them; the top quadrants' bound ends the search with the same result (25 dependent
-        // round trips per pass at the very end of the launch otherwise: 0.2 ms per 16384^2 band)
-        auto worst_qd2 = [&]() {
-            const unsigned top = max(kf[0], kf[2]);
-            return (int)((no_below ? top : max(top, max(kf[1], kf[3]))) >> SRC_BITS);
-        };
-        // Steps are taken in groups that end where GDAL re-derives its search bound (after steps 4, 8, 12, ...): the
-        // bound is constant inside a group, so all of the group's table look-ups are issued before the checks, which then
-        // run in the original order (ascending step; left quadrants before right ones).  The look-ups of the NEXT group are
-        // issued before the checks of the current one (their latency hides behind the checks; a group that turns out not to be
-        // needed costs two cached loads and nothing else).
-        // Round 3: a group's table words are consecutive 16-bit entries of one row, so they are fetched by two wide loads
-        // (2-byte aligned; steps 0..4: the ten entries around x as 16 + 4 bytes; later groups: 8 bytes per side) instead of
-        // ten / eight 2-byte gathers -- the search was bound by the look-ups' issue and latency, not by its arithmetic.
-        // Lanes whose group reaches past the raster's edge columns assemble the same words entry by entry with GDAL's clamp
-        // (it re-checks the edge column).
-        {
-            struct __attribute__((packed, aligned(4))) W4 { unsigned w[4]; };
-            // entry j of a run of table words: low half = squared distance up, high half = squared distance down
-            auto up = [](const unsigned* d, int j) { return d[j] & 0xffffu; };
-            auto dn = [](const unsigned* d, int j) { return d[j] >> 16; };
-            unsigned d0[10];                 // entries 0..9 <-> columns x - 4 .. x + 5 (steps 0..4: left step k = entry 4 - k, right = 4 + k)
-            fill_load_d0<INTERIOR>(trow, x, width, d0);
-            // later groups (steps first .. first + 3): left entries 0..3 <-> columns x - first - 3 .. x - first (step first + k = entry
-            // 3 - k), right entries 0..3 <-> columns x + first .. x + first + 3 (step first + k = entry k)
-            auto fetch4 = [&](int first, unsigned (&l)[4], unsigned (&r)[4]) {
-                if (INTERIOR || (x - first - 3 >= 0 && x + first + 3 < width)) {
-                    const W4 lv = *reinterpret_cast<const W4*>(trow + x - first - 3);
-                    const W4 rv = *reinterpret_cast<const W4*>(trow + x + first);
+    for (int q = 0; q < 4; ++q) kf[q] = kl[q] = ((unsigned)none2 << SRC_BITS) | SRC_MASK;
+    const unsigned* __restrict__ trow = tb + row;
+    // GDAL's QUAD_CHECK on squared integer distances.  `sq` is the column table's half word: NONE_SQ (no source in reach) is more
+    // than any squared distance the search accepts and more than the initial (max_dist + 1)^2, so it never wins.
+    // A candidate at the SAME squared distance replaces the holder iff GDAL's float comparison says so for that distance (the
+    // `tie` bit of c) -- a property of c alone: with the bit set the last candidate met at the best distance wins, without it
+    // the first.  So the search keeps both, branch-free, and the bit is looked up once per quadrant at the end instead of behind
+    // a divergent branch in every one of the 34 candidate tests.
+    // dxk = (dx^2 << 15) | (dx << 8): the step's share of the key (wave-uniform away from the raster's edge columns)
+    auto consider = [&](int q, unsigned sq, unsigned dxk) {
+        const unsigned key = (sq << SRC_BITS) + dxk;
+        kf[q] = min(kf[q], key);
+        kl[q] = min(kl[q], key ^ SRC_MASK);
+    };
+    // `no_below` (the raster's last row): no source lies strictly below, the bottom quadrants stay empty whatever is searched --
+    // GDAL walks all max_dist columns for them; the top quadrants' bound ends the search with the same result (25 dependent
+    // round trips per pass at the very end of the launch otherwise: 0.2 ms per 16384^2 band)
+    auto worst_qd2 = [&]() {
+        const unsigned top = max(kf[0], kf[2]);
+        return (int)((no_below ? top : max(top, max(kf[1], kf[3]))) >> SRC_BITS);
+    };
+    // Steps are taken in groups that end where GDAL re-derives its search bound (after steps 4, 8, 12, ...): the
+    // bound is constant inside a group, so all of the group's table look-ups are issued before the checks, which then
+    // run in the original order (ascending step; left quadrants before right ones).  The look-ups of the NEXT group are
+    // issued before the checks of the current one (their latency hides behind the checks; a group that turns out not to be
+    // needed costs two cached loads and nothing else).
+    // Round 3: a group's table words are consecutive 32-bit entries of one row, so they are fetched by wide loads
+    // (4-byte aligned; steps 0..4: the ten entries around x as 40 bytes; later groups: 16 bytes per side) instead of
+    // ten / eight 4-byte gathers -- the search was bound by the look-ups' issue and latency, not by its arithmetic.
+    // Lanes whose group reaches past the raster's edge columns assemble the same words entry by entry with GDAL's clamp
+    // (it re-checks the edge column).
+    {
+        struct __attribute__((packed, aligned(4))) W4 { unsigned w[4]; };
+        // entry j of a run of table words: low half = squared distance up, high half = squared distance down
+        auto up = [](const unsigned* d, int j) { return d[j] & 0xffffu; };
+        auto dn = [](const unsigned* d, int j) { return d[j] >> 16; };
+        unsigned d0[10];                 // entries 0..9 <-> columns x - 4 .. x + 5 (steps 0..4: left step k = entry 4 - k, right = 4 + k)
+        fill_load_d0<INTERIOR>(trow, x, width, d0);
+        // later groups (steps first .. first + 3): left entries 0..3 <-> columns x - first - 3 .. x - first (step first + k = entry
+        // 3 - k), right entries 0..3 <-> columns x + first .. x + first + 3 (step first + k = entry k)
+        auto fetch4 = [&](int first, unsigned (&l)[4], unsigned (&r)[4]) {
+            if (INTERIOR || (x - first - 3 >= 0 && x + first + 3 < width)) {
+                const W4 lv = *reinterpret_cast<const W4*>(trow + x - first - 3);
+                const W4 rv = *reinterpret_cast<const W4*>(trow + x + first);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) l[j] = lv.w[j], r[j] = rv.w[j];
-                } else {
+                for (int j = 0; j < 4; ++j) l[j] = lv.w[j], r[j] = rv.w[j];
+            } else {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        l[j] = trow[max(0, x - first - 3 + j)];
-                        r[j] = trow[min(width - 1, x + first + j)];
-                    }
+                for (int j = 0; j < 4; ++j) {
+                    l[j] = trow[max(0, x - first - 3 + j)];
+                    r[j] = trow[min(width - 1, x + first + j)];
                 }
-            };
-            unsigned nl[4], nr[4];
-            fetch4(5, nl, nr);
-            int this_max = max_dist;
-            {   // steps 0 .. 4
-                const int last = min(this_max, 4);
-#pragma unroll
-                for (int k = 0; k < 5; ++k) {
-                    if (k <= last) {
-                        const int dl = INTERIOR ? k : min(k, x), dr = INTERIOR ? k : min(k, width - 1 - x);  // clamped columns: the distance to the edge column
-                        const unsigned dlk = ((unsigned)HK_SQ(dl) << SRC_BITS) | ((unsigned)dl << 8);
-                        const unsigned drk = ((unsigned)HK_SQ(dr) << SRC_BITS) | ((unsigned)dr << 8);
-                        consider(0, up(d0, 4 - k), dlk);  // top left
-                        consider(1, dn(d0, 4 - k), dlk);  // bottom left
-                        if (k != 0) {
-                            consider(2, up(d0, 4 + k), drk);  // top right
-                            consider(3, dn(d0, 4 + k), drk);  // bottom right
-                        }
-                    }
-                }
-                // no farther column can beat every quadrant's current distance: floor(max qd) = floor(sqrt(max qd2))
-                if (last == 4) this_max = isqrt_floor(worst_qd2());
             }
-            int first = 5;
-            while (first <= this_max) {
-                // The whole group is tested even when the bound falls inside it: a column farther than floor(sqrt(worst
-                // quadrant distance^2)) cannot beat or tie any quadrant (its squared column distance alone exceeds every best),
-                // so GDAL's bound only ever decides when to STOP, and a per-step predicate (an exec-mask round trip per step) buys
-                // nothing.  Groups start at 5, 9, ..., 97: no step beyond max_dist = 100.
-                const int last = first + 3;
-                const unsigned cl[4] = {nl[0], nl[1], nl[2], nl[3]}, cr[4] = {nr[0], nr[1], nr[2], nr[3]};
-                fetch4(first + 4, nl, nr);
+        };
+        unsigned nl[4], nr[4];
+        fetch4(5, nl, nr);
+        int this_max = max_dist;
+        {   // steps 0 .. 4
+            const int last = min(this_max, 4);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int step = first + k;
-                    {
-                        const int dl = INTERIOR ? step : min(step, x), dr = INTERIOR ? step : min(step, width - 1 - x);
-                        const unsigned dlk = ((unsigned)HK_SQ(dl) << SRC_BITS) | ((unsigned)dl << 8);
-                        const unsigned drk = ((unsigned)HK_SQ(dr) << SRC_BITS) | ((unsigned)dr << 8);
-                        consider(0, up(cl, 3 - k), dlk);
-                        consider(1, dn(cl, 3 - k), dlk);
-                        consider(2, up(cr, k), drk);
-                        consider(3, dn(cr, k), drk);
+            for (int k = 0; k < 5; ++k) {
+                if (k <= last) {
+                    const int dl = INTERIOR ? k : min(k, x), dr = INTERIOR ? k : min(k, width - 1 - x);  // clamped columns: the distance to the edge column
+                    const unsigned dlk = ((unsigned)HK_SQ(dl) << SRC_BITS) | ((unsigned)dl << 8);
+                    const unsigned drk = ((unsigned)HK_SQ(dr) << SRC_BITS) | ((unsigned)dr << 8);
+                    consider(0, up(d0, 4 - k), dlk);  // top left
+                    consider(1, dn(d0, 4 - k), dlk);  // bottom left
+                    if (k != 0) {
+                        consider(2, up(d0, 4 + k), drk);  // top right
+                        consider(3, dn(d0, 4 + k), drk);  // bottom right
                     }
                 }
-                this_max = min(this_max, isqrt_floor(worst_qd2()));
-                first = last + 1;
             }
+            // no farther column can beat every quadrant's current distance: floor(max qd) = floor(sqrt(max qd2))
+            if (last == 4) this_max = isqrt_floor(worst_qd2());
         }
-        // The four quadrants' weights and source values are fetched WITHOUT branches -- a quadrant without a source in reach reads
-        // entry 0 of the weight table (0.0) and the pixel's own value, and its terms are selected away -- so that the eight look-ups
-        // go out together: as `if (found) { load; load; accumulate }` per quadrant they made four dependent round trips at the end of
-        // every search (profiles/r03_fill_tile.txt).  The sums run in the same order over the same terms.
-        double w4[4];
-        float v4[4];
-        bool ok4[4];
+        int first = 5;
+        while (first <= this_max) {
+            // The whole group is tested even when the bound falls inside it: a column farther than floor(sqrt(worst
+            // quadrant distance^2)) cannot beat or tie any quadrant (its squared column distance alone exceeds every best),
+            // so GDAL's bound only ever decides when to STOP, and a per-step predicate (an exec-mask round trip per step) buys
+            // nothing.  Groups start at 5, 9, ..., 97: no step beyond max_dist = 100.
+            const int last = first + 3;
+            const unsigned cl[4] = {nl[0], nl[1], nl[2], nl[3]}, cr[4] = {nr[0], nr[1], nr[2], nr[3]};
+            fetch4(first + 4, nl, nr);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int qd2 = (int)(kf[q] >> SRC_BITS);
-            ok4[q] = qd2 <= max_dist * max_dist;  // qd <= max_dist
-            const int cq = ok4[q] ? qd2 : 0;
-            const unsigned src = ((tie[cq >> 5] >> (cq & 31)) & 1u) ? ((kl[q] & SRC_MASK) ^ SRC_MASK) : (kf[q] & SRC_MASK);  // (the 1.3 KB bitmap stays in cache)
-            const int dx = ok4[q] ? (int)(src >> 8) : 0;
-            const int dy = (int)__fsqrt_rn((float)(cq - dx * dx));  // exact: a perfect square <= 101^2 (0 for a quadrant that is dropped)
-            const int sx = q < 2 ? x - dx : x + dx, sy = (q & 1) ? y + dy : y - dy;
-            w4[q] = wtab[cq];
-            v4[q] = offset[(long long)sy * stride + sx];
+            for (int k = 0; k < 4; ++k) {
+                const int step = first + k;
+                {
+                    const int dl = INTERIOR ? step : min(step, x), dr = INTERIOR ? step : min(step, width - 1 - x);
+                    const unsigned dlk = ((unsigned)HK_SQ(dl) << SRC_BITS) | ((unsigned)dl << 8);
+                    const unsigned drk = ((unsigned)HK_SQ(dr) << SRC_BITS) | ((unsigned)dr << 8);
+                    consider(0, up(cl, 3 - k), dlk);
+                    consider(1, dn(cl, 3 - k), dlk);
+                    consider(2, up(cr, k), drk);
+                    consider(3, dn(cr, k), drk);
+                }
+            }
+            this_max = min(this_max, isqrt_floor(worst_qd2()));
+            first = last + 1;
         }
-        double wsum = 0.0, vsum = 0.0;
-        bool has = false;
+    }
+    // The four quadrants' weights and source values are fetched WITHOUT branches -- a quadrant without a source in reach reads
+    // entry 0 of the weight table (0.0) and the pixel's own value, and its terms are selected away -- so that the eight look-ups
+    // go out together: as `if (found) { load; load; accumulate }` per quadrant they made four dependent round trips at the end of
+    // every search (profiles/r03_fill_tile.txt).  The sums run in the same order over the same terms.
+    double w4[4];
+    float v4[4];
+    bool ok4[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            has = ok4[q] ? (w4[q] != 0.0) : has;
-            wsum = ok4[q] ? wsum + w4[q] : wsum;
-            vsum = ok4[q] ? vsum + (double)v4[q] * w4[q] : vsum;
-        }
-        if (has) out = (float)(vsum / wsum);
-        return out;
+    for (int q = 0; q < 4; ++q) {
+        const int qd2 = (int)(kf[q] >> SRC_BITS);
+        ok4[q] = qd2 <= max_dist * max_dist;  // qd <= max_dist
+        const int cq = ok4[q] ? qd2 : 0;
+        const unsigned src = ((tie[cq >> 5] >> (cq & 31)) & 1u) ? ((kl[q] & SRC_MASK) ^ SRC_MASK) : (kf[q] & SRC_MASK);  // (the 1.3 KB bitmap stays in cache)
+        const int dx = ok4[q] ? (int)(src >> 8) : 0;
+        const int dy = (int)__fsqrt_rn((float)(cq - dx * dx));  // exact: a perfect square <= 101^2 (0 for a quadrant that is dropped)
+        const int sx = q < 2 ? x - dx : x + dx, sy = (q & 1) ? y + dy : y - dy;
+        w4[q] = wtab[cq];
+        v4[q] = offset[(long long)sy * stride + sx];
+    }
+    double wsum = 0.0, vsum = 0.0;
+    bool has = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        has = ok4[q] ? (w4[q] != 0.0) : has;
+        wsum = ok4[q] ? wsum + w4[q] : wsum;
+        vsum = ok4[q] ? vsum + (double)v4[q] * w4[q] : vsum;
+    }
+    if (has) out = (float)(vsum / wsum);
+    return out;
 }
 
 // ---- The PACKED search (round 5) ------------------------------------------------------------------------------------------
@@ -360,9 +365,6 @@ __device__ __forceinline__ float fill_one(int x, int y, long long row, const flo
 // there.  The finish reads the weight 1 / sqrt(n) (n's tie bit is its sign) and a square root from small LDS tables, and the
 // source's value from the plane; all four quadrants of a settled target hold a source within max_dist, so GDAL's acceptance tests are true by
 // construction.
-#ifndef HK_FAST_LAST
-#define HK_FAST_LAST 24
-#endif
 typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pk_min_u16(unsigned a, unsigned b) {
     return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(us2_t, a), __builtin_bit_cast(us2_t, b)));
@@ -373,13 +375,15 @@ __device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
 __device__ __forceinline__ unsigned pk_add_u16(unsigned a, unsigned b) {  // (no carry between the halves; the callers keep every half below 2^16)
     return __builtin_bit_cast(unsigned, __builtin_bit_cast(us2_t, a) + __builtin_bit_cast(us2_t, b));
 }
-constexpr int FAST_LAST = HK_FAST_LAST;        // last column distance of the packed search (groups end at 4, 8, ..., 24)
+// last column distance of the packed search (groups end at 4, 8, ..., 24); settled by "reach of the packed search",
+// profiles/r05b_inpaint_packed.txt
+constexpr int FAST_LAST = 24;
 constexpr unsigned FAST_CLIP = 1263; // row distances squared are clipped here: (1263 + 24^2) * 32 + 31 < 65536, and 1263 > 25^2
-constexpr int FAST_HALO = HK_FAST_LAST;        // table columns staged either side of a workgroup's 256 (>= FAST_LAST, a multiple of 4)
-#ifndef HK_FAST_PITCH_PAD
-#define HK_FAST_PITCH_PAD 4
-#endif
-constexpr int FAST_COLS = 256 + 2 * FAST_HALO, FAST_PITCH = FAST_COLS + HK_FAST_PITCH_PAD;  // (the rows of a pass spread over the banks)
+constexpr int FAST_HALO = FAST_LAST;  // table columns staged either side of a workgroup's 256 (>= FAST_LAST, a multiple of 4)
+// words between the rows of the staged table: 4 more than it has columns, so that the rows of a pass spread over the banks (wider
+// pitches, 316 / 328 words: no difference, profiles/r05b_inpaint_packed.txt)
+constexpr int FAST_PITCH_PAD = 4;
+constexpr int FAST_COLS = 256 + 2 * FAST_HALO, FAST_PITCH = FAST_COLS + FAST_PITCH_PAD;
 static_assert((FAST_CLIP + FAST_LAST * FAST_LAST) * 32 + 31 <= 0xffffu, "a packed key overflows its half");
 static_assert(FAST_CLIP > (FAST_LAST + 1) * (FAST_LAST + 1), "a clipped candidate could settle a quadrant");
 static_assert(FAST_HALO >= FAST_LAST && FAST_HALO % 4 == 0, "the staged halo");
@@ -396,6 +400,7 @@ struct FastTables {
     unsigned char root[FTAB_N + 7];
 };
 static_assert(sizeof(FastTables) % 8 == 0, "copied in 8-byte pieces");
+static_assert(sizeof(FastTables) == FAST_TABLES_BYTES, "the workspace's piece (hk_layout.h)");
 
 __global__ void __launch_bounds__(256) fast_table_kernel(FastTables* __restrict__ ft) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -501,8 +506,9 @@ inpaint_fill_fast_kernel(float* plane, const unsigned long long* __restrict__ tb
     __shared__ unsigned slow_rows[256 / WAVE][WAVE / 4];  // per column of the wave's tile one byte: its rows that did not settle
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
     const int xb = blockIdx.x * blockDim.x, x0 = xb + wv * WAVE, x_own = x0 + lane;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    (void)lt;
+    // the lanes below this one, for the row-order listing (declared beside that loop the compiler schedules the kernel's head
+    // differently: the statement stays here, where the measured code has it)
+    [[maybe_unused]] const unsigned long long lt = (1ull << lane) - 1ull;
     // Columns outside the raster are staged as "no source in reach": GDAL re-checks the edge column there, which changes nothing (the
     // edge column was the farthest candidate of its side already) -- except for the right quadrants of the LAST column, whose first
     // and only candidate is the re-checked own column: they find nothing here, do not settle and go to the general search.
@@ -575,14 +581,14 @@ inpaint_fill_fast_kernel(float* plane, const unsigned long long* __restrict__ tb
 
 // The general search (fill_one) of the targets marked in `bits` -- what the packed search left over, or every target when the
 // packed search is off: 64 columns x ROWS rows per wave, its targets compacted into an LDS list, 64 per pass.
-#ifndef HK_FILL_TILE_WAVES
-#define HK_FILL_TILE_WAVES 8
-#endif
+// ROWS = 32 is the one tile height (tiles divide the 64-row words of the bit planes), built for FILL_TILE_WAVES waves per SIMD:
+// "waves 8 tile 32" of profiles/r03_fill_tile.txt against 5 - 7 waves and 16-row tiles.
+constexpr int FILL_TILE_WAVES = 8;
 template <int ROWS>
-__global__ void __launch_bounds__(256, (ROWS <= 32 ? HK_FILL_TILE_WAVES : 5))
+__global__ void __launch_bounds__(256, FILL_TILE_WAVES)
 inpaint_fill_general_kernel(float* plane, const unsigned long long* __restrict__ bits, long long stride, int height, int width,
                             const unsigned* __restrict__ tb, const unsigned* __restrict__ tie, const double* __restrict__ wtab) {
-    static_assert(ROWS == 16 || ROWS == 32 || ROWS == 64, "tiles divide the 64-row words of the bit planes");
+    static_assert(ROWS == 32, "the one instance");
     __shared__ unsigned short lst[256 / WAVE][ROWS * WAVE];
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
     const int x0 = blockIdx.x * blockDim.x + wv * WAVE, x_own = x0 + lane;
@@ -604,6 +610,8 @@ inpaint_fill_general_kernel(float* plane, const unsigned long long* __restrict__
             tgt_rows &= rows_in >= 64 ? ~0ull : (1ull << rows_in) - 1ull;
         }
         if (__ballot(tgt_rows != 0ull) == 0ull) continue;  // (wave-uniform; nothing of this wave's tile is left over: the usual case)
+        // (the row-order listing of the packed kernel, 32 rows; as ONE shared routine both kernels came out with other register
+        // assignments and an instruction order of their own -- profiles/inpaint_layout_same_isa.txt -- so the loop stands twice)
         int n = 0;  // wave-uniform: targets of the tile so far
 #pragma unroll 4
         for (int r = 0; r < ROWS; ++r) {
@@ -629,41 +637,34 @@ inpaint_fill_general_kernel(float* plane, const unsigned long long* __restrict__
     }
 }
 
-// workspace: the distance table + source flags (1 byte per pixel) + the tie bitmap + the weight table
-// + the column bit words of sources, targets and the targets the packed search left over (one 64-bit word each per column and
-// 64 rows; a plane of a few rows has more of those than spare table bytes) + the packed search's tables
-static size_t bit_words(int height, long long stride) { return (size_t)((height + WORD_ROWS - 1) / WORD_ROWS) * (size_t)stride; }
-size_t inpaint_workspace_bytes(int height, long long stride) {
-    return (size_t)height * stride * 5 + 1024 + TIE_N / 8 + 256 + WTAB_N * 8 + 256 + 3 * (bit_words(height, stride) * 8 + 256)
-           + sizeof(FastTables) + 256;
-}
-
+// The workspace: every piece where inpaint_layout() says (hk_layout.h), as a pointer from `workspace`.
+template <class T>
+static T* piece(void* workspace, size_t offset) { return reinterpret_cast<T*>(static_cast<char*>(workspace) + offset); }
+size_t inpaint_workspace_bytes(int height, long long stride) { return inpaint_layout(height, stride).total; }
 // the workspace's source-flag plane: the fit kernel can write it itself (FitArgs::flag), then gain / r2 are not needed here
 unsigned char* inpaint_flag_plane(void* workspace, int height, long long stride) {
-    return reinterpret_cast<unsigned char*>(static_cast<unsigned short*>(workspace) + 2 * (size_t)height * stride);
+    return piece<unsigned char>(workspace, inpaint_layout(height, stride).flag);
 }
 
-hipError_t launch_inpaint_offsets(float* offset, const float* gain, const float* r2, float thresh, long long stride,
-                                  int height, int width, void* workspace, hipStream_t stream,
-                                  const unsigned char* flag_ready, unsigned long long n_targets, bool packed_search) {
-    const size_t plane = (size_t)height * stride;
-    unsigned* tb = static_cast<unsigned*>(workspace);  // (down^2 << 16) | up^2 row distances, 4 bytes per pixel
-    unsigned char* ws_flag = inpaint_flag_plane(workspace, height, stride);
-    const unsigned char* flag = flag_ready ? flag_ready : ws_flag;
-    unsigned* tie = reinterpret_cast<unsigned*>(ws_flag + (plane + 255) / 256 * 256);
-    double* wtab = reinterpret_cast<double*>(tie + (TIE_N / 32 + 64) / 64 * 64);
+hipError_t launch_inpaint_offsets(const InpaintArgs& a, void* workspace, hipStream_t stream) {
+    // the one requirement on the base (every piece lies at a multiple of 16 from it): the table's 16-byte staging loads, 8-byte pair stores
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return hipErrorInvalidValue;
+    const int height = a.height, width = a.width;
+    const long long stride = a.stride;
+    const InpaintLayout lay = inpaint_layout(height, stride);
+    using u64 = unsigned long long;
+    unsigned *tb = piece<unsigned>(workspace, lay.table), *tie = piece<unsigned>(workspace, lay.tie);
+    unsigned char* ws_flag = piece<unsigned char>(workspace, lay.flag);
+    const unsigned char* flag = a.flag_ready ? a.flag_ready : ws_flag;
+    double* wtab = piece<double>(workspace, lay.wtab);
+    u64 *bits = piece<u64>(workspace, lay.bits), *tbits = piece<u64>(workspace, lay.tbits), *sbits = piece<u64>(workspace, lay.sbits);
+    FastTables* ftab = piece<FastTables>(workspace, lay.ftab);
     HK_LAUNCH(tie_kernel, dim3((TIE_N / 32 + 255) / 256), dim3(256), 0, stream, tie, wtab);
     const int max_dist = FILL_MAX_DIST;
     static_assert(100 + 1 < (int)NONE_B, "the table's distance bytes");
-    if (!flag_ready)  // else: the flag plane was written by the fit kernel (FitArgs::flag)
+    if (!a.flag_ready)  // else: the flag plane was written by the fit kernel (FitArgs::flag)
         HK_LAUNCH(inpaint_flag_kernel, dim3((width + 255) / 256, height < 1024 ? height : 1024), dim3(256), 0, stream,
-                           gain, r2, thresh, stride, height, width, ws_flag);
-    // column bit words behind the weight table (256-byte aligned): sources, then targets; the packed search's table behind them
-    auto align256 = [](void* p) { return reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(p) + 255) / 256 * 256); };
-    unsigned long long* bits = static_cast<unsigned long long*>(align256(wtab + WTAB_N));
-    unsigned long long* tbits = static_cast<unsigned long long*>(align256(bits + bit_words(height, stride)));
-    unsigned long long* sbits = static_cast<unsigned long long*>(align256(tbits + bit_words(height, stride)));
-    FastTables* ftab = static_cast<FastTables*>(align256(sbits + bit_words(height, stride)));
+                           a.gain, a.r2, a.thresh, stride, height, width, ws_flag);
     HK_LAUNCH(fast_table_kernel, dim3((FTAB_N + 7 + 255) / 256), dim3(256), 0, stream, ftab);
     const dim3 gbits((width + 1023) / 1024, (height + WORD_ROWS - 1) / WORD_ROWS);  // four columns per thread
     HK_LAUNCH(inpaint_bits_kernel, gbits, dim3(256), 0, stream, flag, stride, height, width, bits, tbits);
@@ -671,22 +672,22 @@ hipError_t launch_inpaint_offsets(float* offset, const float* gain, const float*
     HK_LAUNCH(inpaint_table_kernel, gtable, dim3(256), 0, stream, bits, stride, height, width, max_dist, tb);
     // The packed search on 8-row tiles, then the general one (32-row tiles) over what it left.  The targets of a tile are listed
     // column by column where more than 60 % of the pixels fail, row by row otherwise (HISTORY.md 53).
-    const bool by_column = (double)n_targets > 0.6 * (double)height * (double)width;
+    const bool by_column = (double)a.n_targets > 0.6 * (double)height * (double)width;
     // the packed search addresses the plane through 32-bit offsets from its tile and 24-bit multiplies by the row stride
     // (`packed_search` false: a test asks for the general search of every target, hk_debug_inpaint_plane_dev)
-    const bool fast = packed_search && stride < (1ll << 23);
+    const bool fast = a.packed_search && stride < (1ll << 23);
     if (fast) {
         const int n_tiles8 = (height + 7) / 8, wgs_y = (n_tiles8 + 3) / 4;  // a workgroup takes four tiles (it copies the finish tables into LDS once)
         const dim3 gf((width + 255) / 256, wgs_y < 65535 ? wgs_y : 65535);
         if (by_column)
-            HK_LAUNCH(inpaint_fill_fast_kernel<true>, gf, dim3(256), 0, stream, offset, tbits, sbits, stride, height, width, tb, ftab, 1);
+            HK_LAUNCH(inpaint_fill_fast_kernel<true>, gf, dim3(256), 0, stream, a.offset, tbits, sbits, stride, height, width, tb, ftab, 1);
         else
-            HK_LAUNCH(inpaint_fill_fast_kernel<false>, gf, dim3(256), 0, stream, offset, tbits, sbits, stride, height, width, tb, ftab, 1);
+            HK_LAUNCH(inpaint_fill_fast_kernel<false>, gf, dim3(256), 0, stream, a.offset, tbits, sbits, stride, height, width, tb, ftab, 1);
     }
     const unsigned long long* todo = fast ? sbits : tbits;
     const int n_tiles = (height + 31) / 32;
     const dim3 gt((width + 255) / 256, n_tiles < 65535 ? n_tiles : 65535);
-    HK_LAUNCH(inpaint_fill_general_kernel<32>, gt, dim3(256), 0, stream, offset, todo, stride, height, width, tb, tie, wtab);
+    HK_LAUNCH(inpaint_fill_general_kernel<32>, gt, dim3(256), 0, stream, a.offset, todo, stride, height, width, tb, tie, wtab);
     return hipGetLastError();
 }
 

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "hk_layout.h"  // where the pieces of the in-painting's and the block statistics' workspaces lie; SlabLayout
+
 struct hk_warp_desc;         // include/homonim_hk.h
 struct hk_affine_warp_desc;  // include/homonim_hk.h
 
@@ -242,7 +244,7 @@ struct NormArgs {
 };
 // waves per plane of the streaming pass (a function of the plane's shape only)
 int norm_pass_waves(int height, int width);
-// workspace: see norm_workspace_bytes(); norm_out: n_bands x 2 float64 on device.
+// workspace: norm_workspace_bytes() of device memory, laid out by norm_layout() (hk_layout.h); norm_out: n_bands x 2 float64 on device.
 size_t norm_workspace_bytes(int n_bands, int height, int width);
 // batched: a.planes set, a.n_bands planes, a.height x a.width = the LARGEST plane (sizes the workspace and the grid)
 hipError_t launch_block_norm(const NormArgs& a, void* workspace, double* norm_out, hipStream_t stream);
@@ -376,17 +378,25 @@ hipError_t launch_partial_mask(const float* in, int nd_mode, float nodata, const
 
 // In-painting of the offset band (hk_inpaint.hip; GDALFillNodata restated): sources are pixels with r2 > thresh and
 // gain > 0 (flag 1), flag 0 pixels are targets and are filled IN PLACE (a filled pixel never acts as a source: sources are read
-// where the flag is 1 only), any other flag value is neither.  workspace: inpaint_workspace_bytes().
+// where the flag is 1 only), any other flag value is neither.
+struct InpaintArgs {
+    float* offset;     // the plane, filled in place
+    long long stride;  // elements between rows: a multiple of 4 (the flag plane's and the table's rows move as quads)
+    int height, width;
+    // the source flags: either ready -- written by the fit kernel (FitArgs::flag; 1 byte per pixel, row stride `stride`), into
+    // inpaint_flag_plane() of this workspace or anywhere else -- or NULL: made here from gain / r2 / thresh
+    const unsigned char* flag_ready = nullptr;
+    const float* gain = nullptr;
+    const float* r2 = nullptr;
+    float thresh = 0.f;
+    unsigned long long n_targets = 0;  // failing pixels if the caller knows (0 = unknown): picks the order in which a tile's targets are searched
+    bool packed_search = true;         // false (test aid only): the packed search is left out and the general one takes every target
+};
+// The workspace: inpaint_workspace_bytes() of device memory whose base is 16-byte aligned (hipErrorInvalidValue otherwise, nothing
+// queued).  hk_layout.h inpaint_layout() states its pieces; inpaint_flag_plane() is the one a fit may write before the launch.
 size_t inpaint_workspace_bytes(int height, long long stride);
-// `flag_ready` (nullable): source flags already written by the fit kernel (FitArgs::flag; 1 byte per pixel, row stride
-// `stride`) -- gain / r2 are then not read.  inpaint_flag_plane(): the workspace's own flag plane, for a fit to write into.
-// `n_targets`: the number of failing pixels if the caller knows it (0 = unknown): picks the order in which a tile's targets are searched.
-// `packed_search` false (test aid only): the packed search is left out and the general one takes every target.
 unsigned char* inpaint_flag_plane(void* workspace, int height, long long stride);
-hipError_t launch_inpaint_offsets(float* offset, const float* gain, const float* r2, float thresh, long long stride,
-                                  int height, int width, void* workspace, hipStream_t stream,
-                                  const unsigned char* flag_ready = nullptr, unsigned long long n_targets = 0,
-                                  bool packed_search = true);
+hipError_t launch_inpaint_offsets(const InpaintArgs& a, void* workspace, hipStream_t stream);
 
 // What every re-sampling launch carries, whatever maps a destination pixel to the source (hk_resample.hip, hk_warp.hip): hk_api.hip
 // fills one per entry point, the kernels' argument structs embed it.  Strides in elements.

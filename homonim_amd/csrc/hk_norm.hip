@@ -35,16 +35,11 @@ constexpr int NORM_THREADS = 256;
 constexpr int L1_BITS = 11, L2_BITS = 11, L3_BITS = 10;
 constexpr int L1_BINS = 1 << L1_BITS, L2_BINS = 1 << L2_BITS, L3_BINS = 1 << L3_BITS;
 constexpr int SAMPLE_N = 4096;     // sample size per band
-#ifndef HK_NORM_LDS_PAD_DEFAULT
-#define HK_NORM_LDS_PAD_DEFAULT 0
-#endif
 #ifndef HK_NORM_ABLATE
 #define HK_NORM_ABLATE 0  // timing experiments only (wrong results): 1 no moments, 2 no compaction queues
 #endif
-#ifndef HK_PASS_WAVES
-#define HK_PASS_WAVES 2048
-#endif
-constexpr int PASS_WAVES = HK_PASS_WAVES;  // most waves per band in the streaming pass (= the number of partial sums kept)
+// most waves per band in the streaming pass (= the number of partial sums kept); 1280 - 5120 waves measured: profiles/r03_norm_ablation.txt
+constexpr int PASS_WAVES = 2048;
 constexpr int FB_BLOCKS = 512;     // workgroups per band of the fallback passes
 constexpr int MID_BLOCKS = 256;    // workgroups per compacted buffer of the regular select passes
 
@@ -77,13 +72,11 @@ struct NormWS {  // one per band
     unsigned hist1[2][2][L1_BINS], hist2[2][2][L2_BINS], hist3[2][2][L3_BINS];
 };
 
-static size_t mid_capacity(long long n_px) { return (size_t)(n_px / 25 + 8192); }  // 4 % of the block + slack
-static size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+static_assert(sizeof(NormWS) == NORM_WS_BYTES, "the workspace's per-band piece (hk_layout.h)");
 
-size_t norm_workspace_bytes(int n_bands, int height, int width) {
-    return align256(sizeof(NormWS) * (size_t)n_bands) +
-           (size_t)n_bands * 2 * align256(mid_capacity((long long)height * width) * sizeof(float));
-}
+// the workspace: norm_layout() (hk_layout.h) -- the bands' NormWS, then their compacted buffers
+size_t norm_workspace_bytes(int n_bands, int height, int width) { return norm_layout(n_bands, height, width).total; }
+static float* mid_buffers(void* workspace, const NormLayout& l) { return reinterpret_cast<float*>(static_cast<char*>(workspace) + l.mid); }
 
 __device__ __forceinline__ unsigned f2key(float f) {  // order-preserving float -> uint32
     const unsigned u = __float_as_uint(f);
@@ -285,8 +278,8 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) norm_sample_kernel(const NormA
 }
 
 // Unused dynamic LDS per wave of the streaming pass: it only lowers the number of resident waves per CU (8 KB of queues per wave
-// = 20 waves per CU otherwise).
-static size_t norm_stream_lds_pad() { return (size_t)HK_NORM_LDS_PAD_DEFAULT; }
+// = 20 waves per CU otherwise).  None: 2 - 12 KB gained nothing (profiles/r03_norm_lds_pad.txt).
+constexpr size_t NORM_STREAM_LDS_PAD = 0;
 
 // Waves per band of the streaming pass: a function of the block SHAPE only (never of the batch size), so a block's
 // statistics are the same bits whichever launch it travels in; >= 16 chunks of 1 KB per raster per wave.
@@ -301,10 +294,8 @@ __host__ __device__ static inline int pass_waves(int height, int width) {
 // written unconditionally to the slot behind the queue's end and the end moves by the compare result, so the loop body
 // has no branch per pixel -- one wave-uniform test per 1 KB chunk asks whether any queue could overflow in the next chunk.
 // The order of the compacted values is irrelevant (the select is a histogram).
-#ifndef HK_NORM_QCAP
-#define HK_NORM_QCAP 16
-#endif
-constexpr int QCAP = HK_NORM_QCAP;  // (8 slots = 4 KB of LDS per wave was measured slower, alone and beside other streams' kernels)
+constexpr int QCAP = 16;  // (8 slots = 4 KB of LDS per wave was measured slower, alone and beside other streams' kernels; 10 - 14
+                          // within 2 % of 16: profiles/r03_norm_qcap.txt)
 
 // DENSE: neither raster has a nodata value (no validity test at all); otherwise the test is branch-free: `cmp` is the
 // numeric nodata value or NaN (never equal), `nan` says that NaN is the nodata value.
@@ -420,12 +411,9 @@ __global__ void __launch_bounds__(WAVE) norm_stream_kernel(const NormArgs a, Nor
         else process(s4, r4, x, std::false_type{});
     };
 
-    // HK_NORM_SETS register sets in rotation (no copies between them: a copy would wait for the load it copies), so
-    // HK_NORM_SETS - 1 chunks per raster are in flight while one is processed
-#ifndef HK_NORM_SETS
-#define HK_NORM_SETS 3
-#endif
-    constexpr int NS = HK_NORM_SETS;
+    // NS register sets in rotation (no copies between them: a copy would wait for the load it copies), so NS - 1 chunks per raster
+    // are in flight while one is processed (3 .. 8 sets: no difference, profiles/r03_norm_ablation.txt)
+    constexpr int NS = 3;
     float4 sQ[NS], rQ[NS];
     int xQ[NS];
 #pragma unroll
@@ -781,12 +769,13 @@ hipError_t launch_block_norm_split(const NormArgs& a, void* workspace, double* x
         HK_LAUNCH(split_get_shift_kernel, bands, dim3(WAVE), 0, stream, ws, xchg);
         if (rows) {
             const dim3 gstream(pass_waves(a.height, a.width), a.n_bands);
-            float* mid = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256(sizeof(NormWS) * (size_t)a.n_bands));
-            const size_t cap_al = align256(mid_capacity((long long)a.height * a.width) * sizeof(float)) / sizeof(float);
+            const NormLayout lay = norm_layout(a.n_bands, a.height, a.width);
+            float* mid = mid_buffers(workspace, lay);
+            const size_t cap_al = lay.cap_al;
             if (a.src_nd_mode == 0 && a.ref_nd_mode == 0)
-                HK_LAUNCH(norm_stream_kernel<true>, gstream, dim3(WAVE), norm_stream_lds_pad(), stream, a, ws, mid, cap_al);
+                HK_LAUNCH(norm_stream_kernel<true>, gstream, dim3(WAVE), NORM_STREAM_LDS_PAD, stream, a, ws, mid, cap_al);
             else
-                HK_LAUNCH(norm_stream_kernel<false>, gstream, dim3(WAVE), norm_stream_lds_pad(), stream, a, ws, mid, cap_al);
+                HK_LAUNCH(norm_stream_kernel<false>, gstream, dim3(WAVE), NORM_STREAM_LDS_PAD, stream, a, ws, mid, cap_al);
         }
         HK_LAUNCH(split_put_moments_kernel, bands, dim3(WAVE), 0, stream, ws, xchg);
         break;
@@ -822,18 +811,18 @@ int norm_pass_waves(int height, int width) { return pass_waves(height, width); }
 
 hipError_t launch_block_norm(const NormArgs& a, void* workspace, double* norm_out, hipStream_t stream) {
     NormWS* ws = reinterpret_cast<NormWS*>(workspace);
-    const size_t cap = mid_capacity((long long)a.height * a.width);
-    const size_t cap_al = align256(cap * sizeof(float)) / sizeof(float);
-    float* mid = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256(sizeof(NormWS) * (size_t)a.n_bands));
+    const NormLayout lay = norm_layout(a.n_bands, a.height, a.width);
+    float* mid = mid_buffers(workspace, lay);
+    const size_t cap_al = lay.cap_al;
     hipError_t e = hipMemsetAsync(ws, 0, sizeof(NormWS) * (size_t)a.n_bands, stream);
     if (e != hipSuccess) return e;
     const dim3 bands(a.n_bands), block(NORM_THREADS);
     HK_LAUNCH(norm_sample_kernel, bands, dim3(SAMPLE_THREADS), 0, stream, a, ws);
     const dim3 gstream(a.grid_waves > 0 ? a.grid_waves : pass_waves(a.height, a.width), a.n_bands);
     if (a.src_nd_mode == 0 && a.ref_nd_mode == 0)
-        HK_LAUNCH(norm_stream_kernel<true>, gstream, dim3(WAVE), norm_stream_lds_pad(), stream, a, ws, mid, cap_al);
+        HK_LAUNCH(norm_stream_kernel<true>, gstream, dim3(WAVE), NORM_STREAM_LDS_PAD, stream, a, ws, mid, cap_al);
     else
-        HK_LAUNCH(norm_stream_kernel<false>, gstream, dim3(WAVE), norm_stream_lds_pad(), stream, a, ws, mid, cap_al);
+        HK_LAUNCH(norm_stream_kernel<false>, gstream, dim3(WAVE), NORM_STREAM_LDS_PAD, stream, a, ws, mid, cap_al);
     HK_LAUNCH(norm_stats_kernel, bands, dim3(STATS_THREADS), 0, stream, ws, norm_out, cap_al);
     // workgroups per compacted buffer: at least 8 float4 per thread of a full buffer (a 4096^2 block's buffers hold ~0.2 M values:
     // 256 workgroups would spend their time zeroing and merging 16 KB histograms -- 0.40 -> 0.15 ms for configs[3]'s 128 blocks)

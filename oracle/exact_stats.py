@@ -37,7 +37,7 @@ F32 = np.float32
 EPS64 = float(np.finfo(np.float64).eps)  # 2**-52
 U64 = EPS64 / 2                          # unit roundoff of float64 round-to-nearest
 SAMPLE_N = 4096                          # hk_norm.hip SAMPLE_N
-PASS_WAVES = 2048                        # hk_norm.hip PASS_WAVES (HK_PASS_WAVES default)
+PASS_WAVES = 2048                        # hk_norm.hip PASS_WAVES
 WAVE, PX = 64, 4
 
 

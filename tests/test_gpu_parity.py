@@ -1156,6 +1156,70 @@ def test_device_resident_job_with_inpainting(ctx, oc, with_params, split_api, sc
             ctx.dev_free(v)
 
 
+@pytest.mark.oracle
+def test_device_resident_job_with_inpainting_behind_a_plane_that_is_no_multiple_of_256_bytes(ctx, oc):
+    """ A 2-band job of 70 x 300 at stride 300: a plane is 84 000 bytes, so the in-painting's workspace -- which lies behind one
+    plane of the slot's scratch -- starts 16-byte aligned and no better, and so does band 1 (every other device job of the suite has
+    a stride that is a multiple of 64: bases 256-byte aligned).  Band 0 is clean, band 1 carries the two defects of
+    test_device_resident_job_with_inpainting.  With and without hk_dev_job.scratch, through hk_inpaint_dev: counts and corrected
+    planes against the oracle, and the corrected bytes against the same job laid out at stride 320. """
+    h, w, nb = 70, 300, 2
+    srcs, refs = [], []
+    for b in range(nb):
+        s_, r_ = onp.synth_pair(h, w, 40 + b, 'frame+holes')
+        r_ = r_.copy()
+        if b == 1:
+            r_[30:36, 100:112] = -3.0
+            r_[60, 200] = 9.0
+        srcs.append(s_), refs.append(r_)
+    exp = [oc.fit_apply('gain-offset', srcs[b], np.nan, refs[b], np.nan, (5, 5), False, 0.25) for b in range(nb)]
+    assert [e[2] > 0 for e in exp] == [False, True]
+    desc = _hk.make_desc('gain-offset', (5, 5), False, 0.25, np.nan, np.nan)
+
+    def run(stride, scratch):
+        """ -> per-band counts of the first pass, hk_inpaint_dev's total, the corrected planes (nb, h, w) """
+        band_stride = stride * h
+        pad = lambda planes: np.stack([np.pad(p, ((0, 0), (0, stride - w))) for p in planes]).astype(np.float32)  # noqa: E731
+        nbytes = 4 * band_stride * nb
+        d = {k: ctx.dev_alloc(nbytes) for k in ('src', 'ref', 'corr')}
+        d['fail'] = ctx.dev_alloc(8 * nb)
+        try:
+            ctx.h2d(d['src'], pad(srcs)), ctx.h2d(d['ref'], pad(refs))
+            ctx.memset(d['fail'], 0, 8 * nb), ctx.memset(d['corr'], 0, nbytes)
+            job = _hk.DevJob()
+            job.src, job.ref, job.corr, job.fail_count = d['src'], d['ref'], d['corr'], d['fail']
+            job.gain = job.offset = job.r2 = job.norm = None
+            job.n_bands, job.height, job.width, job.stride, job.band_stride = nb, h, w, stride, band_stride
+            job.seg_rows, job.stream = 0, 0
+            if scratch:
+                job.scratch_bytes = ctx.job_scratch_bytes(job)
+                d['scratch'] = ctx.dev_alloc(job.scratch_bytes)
+                job.scratch = d['scratch']
+            ctx.fit_apply_dev(desc, job)
+            ctx.stream_sync(0)
+            counts = np.zeros(nb, np.uint64)
+            ctx.d2h(counts, d['fail'])
+            n_fail = ctx.inpaint_dev(desc, job)
+            ctx.stream_sync(0)
+            corr = np.empty((nb, h, stride), np.float32)
+            ctx.d2h(corr, d['corr'])
+            return counts, n_fail, np.ascontiguousarray(corr[:, :, :w])
+        finally:
+            for v in d.values():
+                ctx.dev_free(v)
+
+    for scratch in (False, True):
+        counts, n_fail, corr = run(300, scratch)
+        assert 4 * 300 * h % 256 != 0
+        for b in range(nb):
+            assert int(counts[b]) == exp[b][2], f'band {b}, scratch {scratch}'
+            assert_close_ulp(corr[b], exp[b][1], f'band {b} corrected, scratch {scratch}', max_frac=1e-3)
+        assert n_fail == exp[0][2] + exp[1][2]
+        counts320, n_fail320, corr320 = run(320, scratch)
+        assert (counts320 == counts).all() and n_fail320 == n_fail
+        assert corr.tobytes() == corr320.tobytes(), f'scratch {scratch}: stride 300 and stride 320 give different corrected bytes'
+
+
 def _dev_job_corr_only(c, src, ref, thresh, kernel_shape=(5, 5)):
     """ one single-band device-resident gain-offset job keeping only the corrected plane; returns (job, buffers) """
     h, w = src.shape
