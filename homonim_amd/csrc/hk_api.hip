@@ -758,7 +758,9 @@ int stage_in(Slot& s, const void* host, int64_t hstride, int dt, float* dplane, 
     void* dst = dt ? raw : static_cast<void*>(dplane);
     const int rc = stage_h2d(s, dst, dstride * es, host, hstride * es, (size_t)w * es, h);
     if (rc) return rc;
-    if (dt) HK_HIP(hk::launch_cast_in(dt, dst, dstride, dplane, dstride, h, w, s.stream));
+    if (dt)
+        HK_HIP(hk::launch_cast_in(dt, {.in = dst, .in_stride = dstride, .out = dplane, .out_stride = dstride, .height = h, .width = w},
+                                  s.stream));
     return HK_OK;
 }
 
@@ -1170,34 +1172,30 @@ int fit_finish(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, FitPending& p, un
     return HK_OK;
 }
 
-// Device-side KernelModel.fit (+ apply when d_corr) of one float32 block already in HBM: block statistics for
+// Device-side KernelModel.fit (+ apply when job.corr) of one float32 block already in HBM: block statistics for
 // gain-blk-offset (or the caller's norm), the fused kernel, and the in-painting branch of gain-offset
-// (kernel_model.py:361-371) when valid pixels fail the r2 mask.  d_gain / d_off / d_r2 / d_corr are nullable planes.
+// (kernel_model.py:361-371) when valid pixels fail the r2 mask.  `job`: the block as a one-band job on the slot's stream --
+// gain / offset / r2 / corr nullable; norm: two device words that receive the statistics here (used by gain-blk-offset only);
+// fail_count: cleared here; out_row0 .. out_cols: the store window of the kernel, all zero = the whole block.
 // `defer` (nullable): only queue the first pass and leave the r2-mask outcome to the caller (fit_finish); otherwise the
-// stream is synchronised here to read the counter.  `win` (nullable): store window {y0, y1, x0, x1} of the kernel.
-int fit_on_device(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, const double* norm_in, float* d_src, float* d_ref,
-                  int32_t height, int32_t width, int64_t stride, float* d_gain, float* d_off, float* d_r2, float* d_corr,
-                  double* d_norm, unsigned long long* d_fail, void* d_norm_ws, FitPending* defer = nullptr,
-                  const int* win = nullptr) {
+// stream is synchronised here to read the counter.
+int fit_on_device(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, hk_dev_job job, void* d_norm_ws, const double* norm_in = nullptr,
+                  FitPending* defer = nullptr) {
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
     const bool r2 = needs_r2(desc);
+    unsigned long long* const d_fail = reinterpret_cast<unsigned long long*>(job.fail_count);
+    double* const d_norm = const_cast<double*>(job.norm);  // (the job's view of it is the kernel's: read-only)
     HK_HIP(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), sl.stream));
-    if (blk) {
-        if (norm_in) {
-            memcpy(sl.pin<double>(Slot::PIN_NORM_IN), norm_in, 2 * sizeof(double));  // (caller memory -> pinned words)
-            HK_HIP(hipMemcpyAsync(d_norm, sl.pin<double>(Slot::PIN_NORM_IN), 2 * sizeof(double), hipMemcpyHostToDevice, sl.stream));
-        } else {
-            HK_HIP(hk::launch_block_norm(norm_args(desc, d_src, d_ref, height, width, stride), d_norm_ws, d_norm, sl.stream));
-        }
+    if (!blk) {
+        job.norm = nullptr;
+    } else if (norm_in) {
+        memcpy(sl.pin<double>(Slot::PIN_NORM_IN), norm_in, 2 * sizeof(double));  // (caller memory -> pinned words)
+        HK_HIP(hipMemcpyAsync(d_norm, sl.pin<double>(Slot::PIN_NORM_IN), 2 * sizeof(double), hipMemcpyHostToDevice, sl.stream));
+    } else {
+        HK_HIP(hk::launch_block_norm(norm_args(desc, job.src, job.ref, job.height, job.width, job.stride), d_norm_ws, d_norm, sl.stream));
     }
-    hk_dev_job job = {};
-    job.src = d_src, job.ref = d_ref, job.gain = d_gain, job.offset = d_off, job.r2 = d_r2, job.corr = d_corr;
-    job.norm = blk ? d_norm : nullptr;
-    job.fail_count = reinterpret_cast<uint64_t*>(d_fail);
-    job.n_bands = 1, job.height = height, job.width = width, job.stride = stride;
     // the in-painting branch needs the parameters of the whole block: the store window only narrows the other models
-    if (win && !(desc->model == HK_MODEL_GAIN_OFFSET && desc->has_r2_thresh))
-        job.out_row0 = win[0], job.out_rows = win[1] - win[0], job.out_col0 = win[2], job.out_cols = win[3] - win[2];
+    if (desc->model == HK_MODEL_GAIN_OFFSET && desc->has_r2_thresh) job.out_row0 = job.out_rows = job.out_col0 = job.out_cols = 0;
     FitPending local;
     FitPending& p = defer ? *defer : local;
     hk::FitArgs& a = p.a;
@@ -1208,12 +1206,12 @@ int fit_on_device(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, const double* 
         // what the in-painting reads -- offsets and source flags -- into the slot's scratch right away: no second "first
         // pass" (fit_finish hands them to inpaint_band).  With the caller's own offset plane only the flags are scratch.
         InpaintScratch s;
-        rc = inpaint_scratch(sl, height, stride, s);
+        rc = inpaint_scratch(sl, job.height, job.stride, s);
         if (rc) return rc;
         a.flag = s.flag;
-        if (!d_off) {
+        if (!job.offset) {
             a.offset = s.offset;
-            p.scratch_params = !d_gain && !d_r2;
+            p.scratch_params = !job.gain && !job.r2;
         }
     }
     rc = launch_fit(ctx, sl, a, desc, r2);
@@ -1253,28 +1251,41 @@ int check_fit_io(const hk_fit_desc* desc, const hk_io_desc* io, const float* par
 // the whole block of `rows` x `cols`, written packed
 hk_out_window whole_block(int32_t rows, int32_t cols) { return {cols, (int64_t)rows * cols, 0, 0, rows, cols, cols}; }
 
-// How a host-pointer fit hands its results back.  The parameter planes (nullable params_out; d_par_band elements apart on the
-// device, rows d_par_stride apart), their window `pw` into the caller's planes; the corrected plane of height x width (nullable
-// corr_out; through d_raw and the cast where the output has one), its window `cw`; the r2-mask failure counter behind them
-// (nullable d_fail) into the slot's pinned word.  A window's param_stride is the row stride of params_out.
-int stage_fit_results(Slot& sl, const FitIo& f, float* params_out, int32_t n_param_bands, const float* d_par, int64_t d_par_stride,
-                      int64_t d_par_band, const hk_out_window& pw, void* corr_out, const float* d_corr, void* d_raw, int64_t d_stride,
-                      int32_t height, int32_t width, const hk_out_window& cw, const unsigned long long* d_fail) {
+// Where a host-pointer fit's results lie on the device and where they go in the caller's memory.  A window's param_stride is the
+// row stride of params_out.
+struct FitResults {
+    float* params_out;        // nullable: n_param_bands planes, ...
+    int32_t n_param_bands;
+    const float* d_par;       // ... on the device d_par_band elements apart, rows d_par_stride apart, ...
+    int64_t d_par_stride, d_par_band;
+    hk_out_window pw;         // ... and their window into the caller's planes
+    void* corr_out;           // nullable: the corrected plane, ...
+    const float* d_corr;      // ... on the device height x width, rows d_stride apart, ...
+    void* d_raw;              // ... through here and the cast where the output has one (FitIo::out_cast), ...
+    int64_t d_stride;
+    int32_t height, width;
+    hk_out_window cw;         // ... and its window into corr_out
+};
+// queues the copies of both, and behind them the r2-mask failure counter (nullable d_fail) into the slot's pinned word
+int stage_fit_results(Slot& sl, const FitIo& f, const FitResults& r, const unsigned long long* d_fail) {
     int rc;
-    if (params_out)
-        for (int b = 0; b < n_param_bands; ++b)
-            if ((rc = stage_d2h(sl, params_out + (size_t)b * pw.band_stride, pw.param_stride * sizeof(float),
-                                d_par + (size_t)b * d_par_band + (size_t)pw.row0 * d_par_stride + pw.col0, d_par_stride * sizeof(float),
-                                (size_t)pw.cols * sizeof(float), pw.rows)))
+    const hk_out_window &pw = r.pw, &cw = r.cw;
+    if (r.params_out)
+        for (int b = 0; b < r.n_param_bands; ++b)
+            if ((rc = stage_d2h(sl, r.params_out + (size_t)b * pw.band_stride, pw.param_stride * sizeof(float),
+                                r.d_par + (size_t)b * r.d_par_band + (size_t)pw.row0 * r.d_par_stride + pw.col0,
+                                r.d_par_stride * sizeof(float), (size_t)pw.cols * sizeof(float), pw.rows)))
                 return rc;
-    if (corr_out) {
+    if (r.corr_out) {
         const size_t es = hk::dtype_size(f.odt);  // (4 without a cast: the output is float32 then)
-        const char* d_out = reinterpret_cast<const char*>(d_corr);
+        const char* d_out = reinterpret_cast<const char*>(r.d_corr);
         if (f.out_cast) {
-            HK_HIP(hk::launch_cast_out(f.odt, d_corr, d_stride, d_raw, d_stride, height, width, f.out_has_nodata, f.out_nodata, sl.stream));
-            d_out = static_cast<const char*>(d_raw);
+            HK_HIP(hk::launch_cast_out(f.odt, {.in = r.d_corr, .in_stride = r.d_stride, .out = r.d_raw, .out_stride = r.d_stride,
+                                               .height = r.height, .width = r.width, .has_nodata = f.out_has_nodata, .nodata = f.out_nodata},
+                                       sl.stream));
+            d_out = static_cast<const char*>(r.d_raw);
         }
-        if ((rc = stage_d2h(sl, corr_out, cw.stride * es, d_out + ((size_t)cw.row0 * d_stride + cw.col0) * es, d_stride * es,
+        if ((rc = stage_d2h(sl, r.corr_out, cw.stride * es, d_out + ((size_t)cw.row0 * r.d_stride + cw.col0) * es, r.d_stride * es,
                             (size_t)cw.cols * es, cw.rows)))
             return rc;
     }
@@ -1406,21 +1417,24 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
 
     // stage out: the window of the block the caller wants, straight into its (strided) arrays; the parameter planes lie one
     // plane apart in the slab
-    auto stage_out = [&](const unsigned long long* fail_counter) {
-        return stage_fit_results(sl, f, params_out, n_param_bands, d_gain, stride, (int64_t)(o_off - o_gain) / 4, win, corr_out, d_corr,
-                                 hc.at(o_raw_o), stride, height, width, win, fail_counter);
-    };
+    const FitResults res = {.params_out = params_out, .n_param_bands = n_param_bands, .d_par = d_gain, .d_par_stride = stride,
+                            .d_par_band = (int64_t)(o_off - o_gain) / 4, .pw = win, .corr_out = corr_out, .d_corr = d_corr,
+                            .d_raw = hc.at(o_raw_o), .d_stride = stride, .height = height, .width = width, .cw = win};
 
     // The fit, its outputs and its r2-mask counter are queued back to back and the stream is synchronised ONCE; only
     // when pixels failed the mask do the in-painting passes follow, and the outputs are copied again behind them.
     FitPending pending;
-    const int kwin[4] = {win.row0, win.row0 + win.rows, win.col0 / hk::PX * hk::PX, width};  // rows exactly, columns from the window's first quad
-    rc = fit_on_device(ctx, sl, desc, norm_in, d_src, d_ref, height, width, stride, d_gain, d_off, d_r2, d_corr, d_norm,
-                       d_fail, d_ws, &pending, (ow && !f.out_cast) ? kwin : nullptr);
+    hk_dev_job job = {.src = d_src, .ref = d_ref, .gain = d_gain, .offset = d_off, .r2 = d_r2, .corr = d_corr, .norm = d_norm,
+                      .fail_count = reinterpret_cast<uint64_t*>(d_fail), .n_bands = 1, .height = height, .width = width, .stride = stride};
+    if (ow && !f.out_cast) {  // the kernel's store window: the rows exactly, the columns from the window's first quad to the last column
+        job.out_row0 = win.row0, job.out_rows = win.rows;
+        job.out_col0 = win.col0 / hk::PX * hk::PX, job.out_cols = width - job.out_col0;
+    }
+    rc = fit_on_device(ctx, sl, desc, job, d_ws, norm_in, &pending);
     if (rc) return rc;
     if (norm_out && blk)
         HK_HIP(hipMemcpyAsync(sl.pin<double>(Slot::PIN_NORM), d_norm, 2 * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
-    if ((rc = stage_out(nullptr))) return rc;
+    if ((rc = stage_fit_results(sl, f, res, /*d_fail=*/nullptr))) return rc;
     // hk_debug_fail_after_d2h(1) (homonim_hk_devtools.h): the call fails HERE, its result copies queued and not yet unpacked --
     // the state every HIP error between a stage_d2h and stage_finish leaves (tests/test_gpu_staging.py)
     if (g_fail_after_d2h.load(std::memory_order_relaxed))
@@ -1435,7 +1449,7 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
         rc = fit_finish(ctx, sl, desc, pending, n_fail, &requeued);
         if (rc) return rc;
         if (requeued) {
-            if ((rc = stage_out(d_fail))) return rc;
+            if ((rc = stage_fit_results(sl, f, res, d_fail))) return rc;
             if ((rc = stage_finish(sl))) return rc;
             n_fail = *sl.fail_host;  // (the in-painting passes do not count)
         }
@@ -1645,6 +1659,7 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     auto F = [&](size_t off) { return hc.at<float>(off); };
     float *d_src = F(o_src), *d_ref = F(o_ref), *d_ds = F(o_ds), *d_gain = F(o_gain), *d_off = F(o_off);
     float *d_r2 = f.r2 ? F(o_r2) : nullptr, *d_gus = F(o_gus), *d_ous = F(o_ous), *d_corr = F(o_corr);
+    const int64_t par_band = (int64_t)(o_off - o_gain) / 4;  // gain -> offset plane, elements
     double* d_norm = hc.at<double>(o_aux);
     unsigned long long* d_fail = hc.at<unsigned long long>(o_aux + 64);
     const float nan = std::nanf("");
@@ -1664,9 +1679,10 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     HK_HIP(resample(space->down_resampling, true, d_src, desc->src_nodata_mode, desc->src_nodata, d_ds, nan));
     hk_fit_desc fd = *desc;
     fd.src_nodata_mode = HK_NODATA_NAN, fd.src_nodata = nan;
-    rc = fit_on_device(ctx, sl, &fd, nullptr, d_ds, d_ref, ref_height, ref_width, rs, d_gain, d_off, d_r2, nullptr, d_norm,
-                       d_fail, hc.at(o_ws));
-    if (rc) return rc;
+    const hk_dev_job job = {.src = d_ds, .ref = d_ref, .gain = d_gain, .offset = d_off, .r2 = d_r2, .norm = d_norm,
+                            .fail_count = reinterpret_cast<uint64_t*>(d_fail), .n_bands = 1, .height = ref_height, .width = ref_width,
+                            .stride = rs};
+    if ((rc = fit_on_device(ctx, sl, &fd, job, hc.at(o_ws)))) return rc;
 
     // RefSpaceModel.apply (:484-503): gain / offset -> source grid, re-mask, apply
     if (!fused_up)
@@ -1676,31 +1692,38 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     if (space->mask_partial) {
         // _full_coverage_mask (:375-409): source mask --average--> reference grid (>= 1) & parameter mask, eroded by
         // (kh+2) x (kw+2); back to the source grid with `nearest` (nodata 0)
-        HK_HIP(hk::launch_valid_plane(d_src, ss, desc->src_nodata_mode, desc->src_nodata, F(o_vs), ss, src_height,
-                                      src_width, sl.stream));
-        HK_HIP(resample(5, true, F(o_vs), HK_NODATA_NONE, 0.f, F(o_cov), 0.f));
+        HK_HIP(hk::launch_valid_plane({.in = d_src, .in_stride = ss, .nd_mode = desc->src_nodata_mode, .nodata = desc->src_nodata,
+                                       .out = F(o_vs), .out_stride = ss, .height = src_height, .width = src_width}, sl.stream));
+        HK_HIP(resample(hk::RS_AVERAGE, true, F(o_vs), HK_NODATA_NONE, 0.f, F(o_cov), 0.f));
         unsigned char* d_mk = hc.at<unsigned char>(o_mk);
         // the parameters as two bands: gain, and offset one band stride further on
-        HK_HIP(hk::launch_partial_mask(F(o_cov), 3, 0.f, d_gain, 2, (long long)(o_off - o_gain) / 4, nullptr,
-                                       ref_height, ref_width, rs, desc->kh, desc->kw,
-                                       hc.at<unsigned short>(o_cnt), nullptr, nullptr, d_mk, sl.stream));
-        HK_HIP(hk::launch_cast_in(1, d_mk, rs, F(o_mkf), rs, ref_height, ref_width, sl.stream));
-        HK_HIP(resample(0, false, F(o_mkf), HK_NODATA_NONE, 0.f, F(o_keep), 0.f));
+        HK_HIP(hk::launch_partial_mask({.in = F(o_cov), .nd_mode = hk::ND_COVERAGE, .params = d_gain, .n_bands = 2, .band_stride = par_band,
+                                        .height = ref_height, .width = ref_width, .stride = rs, .kh = desc->kh, .kw = desc->kw, .mask_out = d_mk},
+                                       hc.at<unsigned short>(o_cnt), sl.stream));
+        HK_HIP(hk::launch_cast_in(HK_DTYPE_U8, {.in = d_mk, .in_stride = rs, .out = F(o_mkf), .out_stride = rs, .height = ref_height,
+                                                .width = ref_width}, sl.stream));
+        HK_HIP(resample(hk::RS_NEAREST, false, F(o_mkf), HK_NODATA_NONE, 0.f, F(o_keep), 0.f));
         d_keep = F(o_keep);
     }
     if (fused_up) {
-        HK_HIP(hk::launch_upsample_apply(space->up_resampling, d_src, ss, desc->src_nodata_mode, desc->src_nodata, d_gain,
-                                         d_off, rs, ref_height, ref_width, d_keep, ss, d_corr, ss, src_height, src_width,
-                                         space->up[0], space->up[1], space->up[2], space->up[3], hc.at(o_rowtab), sl.stream));
+        const double* up = space->up;
+        HK_HIP(hk::launch_upsample_apply(space->up_resampling, {.src = d_src, .src_stride = ss, .nd_mode = desc->src_nodata_mode,
+                                         .nodata = desc->src_nodata, .gain = d_gain, .offset = d_off, .par_stride = rs, .ph = ref_height,
+                                         .pw = ref_width, .keep = d_keep, .keep_stride = ss, .out = d_corr, .out_stride = ss,
+                                         .height = src_height, .width = src_width, .kx = up[0], .ox = up[1], .ky = up[2], .oy = up[3]},
+                                         hc.at(o_rowtab), sl.stream));
     } else {
-        HK_HIP(hk::launch_apply_space(d_src, ss, desc->src_nodata_mode, desc->src_nodata, d_gus, d_ous, ss, d_keep, d_corr,
-                                      ss, src_height, src_width, sl.stream));
+        HK_HIP(hk::launch_apply_space({.src = d_src, .src_stride = ss, .nd_mode = desc->src_nodata_mode, .nodata = desc->src_nodata,
+                                       .gain = d_gus, .offset = d_ous, .par_stride = ss, .keep = d_keep, .out = d_corr, .out_stride = ss,
+                                       .height = src_height, .width = src_width}, sl.stream));
     }
 
     // the parameters on the reference grid, the corrected block on the source grid, both whole and packed
-    if ((rc = stage_fit_results(sl, f, params_out, n_param_bands, d_gain, rs, (int64_t)(o_off - o_gain) / 4, whole_block(ref_height, ref_width),
-                                corr_out, d_corr, hc.at(o_raw_o), ss, src_height, src_width, whole_block(src_height, src_width), d_fail)))
-        return rc;
+    const FitResults res = {.params_out = params_out, .n_param_bands = n_param_bands, .d_par = d_gain, .d_par_stride = rs,
+                            .d_par_band = par_band, .pw = whole_block(ref_height, ref_width), .corr_out = corr_out, .d_corr = d_corr,
+                            .d_raw = hc.at(o_raw_o), .d_stride = ss, .height = src_height, .width = src_width,
+                            .cw = whole_block(src_height, src_width)};
+    if ((rc = stage_fit_results(sl, f, res, d_fail))) return rc;
     if ((rc = stage_finish(sl))) return rc;
     if (r2_fail_count) *r2_fail_count = *sl.fail_host;
     return HK_OK;
@@ -1723,7 +1746,7 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     const size_t splane = (size_t)ss * src_height * 4, rplane = (size_t)rs * ref_height * 4;
     const int n_par = r2 ? 3 : 2;
     // `average` reads the reference as it was uploaded (footprint_typed_kernel): no float32 copy, no valid plane
-    const bool typed_foot = space->resampling == 5;
+    const bool typed_foot = space->resampling == hk::RS_AVERAGE;
     SlabLayout L;
     const size_t o_src = L.take(splane), o_rus = L.take(splane);
     const size_t o_par = L.take(splane);  // gain, offset, (r2): planes of one size, one band stride apart
@@ -1761,8 +1784,10 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
         const size_t es = hk::dtype_size(f.rdt);
         void* d_raw = hc.at(f.rdt ? o_raw_r : o_ref);
         if ((rc = stage_h2d(sl, d_raw, rs * es, ref, ref_stride * es, (size_t)ref_width * es, ref_height))) return rc;
-        HK_HIP(hk::launch_footprint_typed(f.rdt, d_raw, rs, ref_height, ref_width, desc->ref_nodata_mode, desc->ref_nodata, d_rus,
-                                          partial ? F(o_cov) : nullptr, ss, src_height, src_width, nan, m[0], m[1], m[2], m[3],
+        HK_HIP(hk::launch_footprint_typed(f.rdt, {.src = d_raw, .src_stride = rs, .sh = ref_height, .sw = ref_width,
+                                                  .nd_mode = desc->ref_nodata_mode, .nodata = desc->ref_nodata, .value = d_rus,
+                                                  .coverage = partial ? F(o_cov) : nullptr, .dst_stride = ss, .dh = src_height,
+                                                  .dw = src_width, .fill = nan, .kx = m[0], .ox = m[1], .ky = m[2], .oy = m[3]},
                                           sl.stream));
     } else {
         float* d_ref = F(o_ref);
@@ -1771,10 +1796,10 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
                                                desc->ref_nodata_mode, desc->ref_nodata, nan);
         HK_HIP(hk::launch_resample(space->resampling, p, m[0], m[1], m[2], m[3], sl.stream));
         if (partial) {
-            HK_HIP(hk::launch_valid_plane(d_ref, rs, desc->ref_nodata_mode, desc->ref_nodata, F(o_vr), rs, ref_height, ref_width,
-                                          sl.stream));
+            HK_HIP(hk::launch_valid_plane({.in = d_ref, .in_stride = rs, .nd_mode = desc->ref_nodata_mode, .nodata = desc->ref_nodata,
+                                           .out = F(o_vr), .out_stride = rs, .height = ref_height, .width = ref_width}, sl.stream));
             p.src = F(o_vr), p.dst = F(o_cov), p.nd_mode = HK_NODATA_NONE, p.nodata = 0.f, p.dst_fill = 0.f;
-            HK_HIP(hk::launch_resample(5, p, m[0], m[1], m[2], m[3], sl.stream));
+            HK_HIP(hk::launch_resample(hk::RS_AVERAGE, p, m[0], m[1], m[2], m[3], sl.stream));
         }
     }
 
@@ -1782,21 +1807,26 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     // wherever the source is, so that masking them with the source mask (:533) changes nothing
     hk_fit_desc fd = *desc;
     fd.ref_nodata_mode = HK_NODATA_NAN, fd.ref_nodata = nan;
-    rc = fit_on_device(ctx, sl, &fd, nullptr, d_src, d_rus, src_height, src_width, ss, d_gain, d_off, d_r2,
-                       partial ? nullptr : d_corr, d_norm, d_fail, hc.at(o_ws));
-    if (rc) return rc;
+    const hk_dev_job job = {.src = d_src, .ref = d_rus, .gain = d_gain, .offset = d_off, .r2 = d_r2, .corr = partial ? nullptr : d_corr,
+                            .norm = d_norm, .fail_count = reinterpret_cast<uint64_t*>(d_fail), .n_bands = 1, .height = src_height,
+                            .width = src_width, .stride = ss};
+    if ((rc = fit_on_device(ctx, sl, &fd, job, hc.at(o_ws)))) return rc;
 
     float* d_pout = d_gain;
     if (partial) {
         // :526-531: coverage >= 1 & "has gain or offset", eroded by (kh+2) x (kw+2), on ALL parameter bands; then KernelModel.apply
         d_pout = params_out ? F(o_mpar) : nullptr;
-        HK_HIP(hk::launch_partial_mask(F(o_cov), 3, 0.f, d_gain, n_par, pbs, d_src, src_height, src_width, ss, desc->kh, desc->kw,
-                                       hc.at<unsigned short>(o_cnt), d_pout, d_corr, nullptr, sl.stream));
+        HK_HIP(hk::launch_partial_mask({.in = F(o_cov), .nd_mode = hk::ND_COVERAGE, .params = d_gain, .n_bands = n_par, .band_stride = pbs,
+                                        .src = d_src, .height = src_height, .width = src_width, .stride = ss, .kh = desc->kh,
+                                        .kw = desc->kw, .params_out = d_pout, .corr_out = d_corr},
+                                       hc.at<unsigned short>(o_cnt), sl.stream));
     }
 
     const hk_out_window whole = whole_block(src_height, src_width);
-    if ((rc = stage_fit_results(sl, f, params_out, n_param_bands, d_pout, ss, pbs, whole, corr_out, d_corr, hc.at(o_raw_o), ss, src_height, src_width, whole, d_fail)))
-        return rc;
+    const FitResults res = {.params_out = params_out, .n_param_bands = n_param_bands, .d_par = d_pout, .d_par_stride = ss,
+                            .d_par_band = pbs, .pw = whole, .corr_out = corr_out, .d_corr = d_corr, .d_raw = hc.at(o_raw_o),
+                            .d_stride = ss, .height = src_height, .width = src_width, .cw = whole};
+    if ((rc = stage_fit_results(sl, f, res, d_fail))) return rc;
     if ((rc = stage_finish(sl))) return rc;
     if (r2_fail_count) *r2_fail_count = *sl.fail_host;
     return HK_OK;
@@ -2017,7 +2047,7 @@ int hk_partial_mask(hk_ctx* ctx, const float* in, int64_t in_stride, int32_t in_
     if (rc) return rc;
     if (corr_out && !src) return fail(HK_ERR_ARG, "corr_out needs src");
     if ((rc = check_strides(in_stride, width)) || (src && (rc = check_strides(src_stride, width)))) return rc;
-    if ((rc = check_nodata_mode(in_nodata_mode, 3))) return rc;  // 3: `in` is a coverage fraction, valid from 1 (include/homonim_hk.h)
+    if ((rc = check_nodata_mode(in_nodata_mode, hk::ND_COVERAGE))) return rc;  // (include/homonim_hk.h states it as 3)
     HK_ENTER(ctx);
     const int64_t stride = row_align(width);
     const size_t plane = (size_t)stride * height * sizeof(float);
@@ -2037,9 +2067,10 @@ int hk_partial_mask(hk_ctx* ctx, const float* in, int64_t in_stride, int32_t in_
         if ((rc = stage_h2d(sl, d_par + (size_t)b * stride * height, sb, params + (size_t)b * height * width, wb, wb, height)))
             return rc;
     if (src && (rc = stage_h2d(sl, d_src, sb, src, src_stride * 4, wb, height))) return rc;
-    HK_HIP(hk::launch_partial_mask(d_in, in_nodata_mode, in_nodata, d_par, n_param_bands, stride * height, d_src, height,
-                                   width, stride, kh, kw, hc.at<unsigned short>(o_cnt), d_pout, d_corr,
-                                   d_mask, sl.stream));
+    HK_HIP(hk::launch_partial_mask({.in = d_in, .nd_mode = in_nodata_mode, .nodata = in_nodata, .params = d_par, .n_bands = n_param_bands,
+                                    .band_stride = stride * height, .src = d_src, .height = height, .width = width, .stride = stride,
+                                    .kh = kh, .kw = kw, .params_out = d_pout, .corr_out = d_corr, .mask_out = d_mask},
+                                   hc.at<unsigned short>(o_cnt), sl.stream));
     if (params_out)
         for (int b = 0; b < n_param_bands; ++b)
             if ((rc = stage_d2h(sl, params_out + (size_t)b * height * width, wb, d_pout + (size_t)b * stride * height, sb, wb, height)))
@@ -2511,9 +2542,10 @@ int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
     static_assert(sizeof(long long) == sizeof(int64_t), "strides are handed on as they are");
-    HK_HIP(hk::launch_overviews(dtype, planes_dev, height, width, stride, band_stride, n_bands, nodata_mode, nodata, n_levels,
-                                out_dev, reinterpret_cast<const long long*>(out_stride),
-                                reinterpret_cast<const long long*>(out_band_stride), ctx->slots[stream].stream));
+    const hk::BandPlanes planes = {.src = planes_dev, .n_bands = n_bands, .height = height, .width = width, .stride = stride, .band_stride = band_stride};
+    HK_HIP(hk::launch_overviews(dtype, {.planes = planes, .nd_mode = nodata_mode, .nodata = nodata, .n_levels = n_levels, .out = out_dev,
+                                        .out_stride = reinterpret_cast<const long long*>(out_stride),
+                                        .out_band_stride = reinterpret_cast<const long long*>(out_band_stride)}, ctx->slots[stream].stream));
     return HK_OK;
 }
 
@@ -2565,8 +2597,10 @@ int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands
             if ((rc = stage_h2d(sl, base + o_src + (size_t)b * rows_max * d_stride * es, d_stride * es,
                                 h_src + ((size_t)b * band_stride + (size_t)r0 * stride) * es, stride * es, (size_t)width * es, rows)))
                 return rc;
-        HK_HIP(hk::launch_overviews(dtype, base + o_src, (int)rows, width, d_stride, rows_max * d_stride, n_bands, nodata_mode,
-                                    nodata, n_levels, d_out, l_stride, l_band, sl.stream));
+        const hk::BandPlanes slab = {.src = base + o_src, .n_bands = n_bands, .height = (int)rows, .width = width, .stride = d_stride,
+                                     .band_stride = rows_max * d_stride};
+        HK_HIP(hk::launch_overviews(dtype, {.planes = slab, .nd_mode = nodata_mode, .nodata = nodata, .n_levels = n_levels, .out = d_out,
+                                            .out_stride = l_stride, .out_band_stride = l_band}, sl.stream));
         for (int m = 1; m <= n_levels; ++m) {
             char* h_out = static_cast<char*>(out[m - 1]);
             for (int b = 0; b < n_bands; ++b)
@@ -2638,9 +2672,10 @@ static int deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype,
     rc = ensure_stream_ws(ctx, sl, hk::deflate_workspace_bytes(n_chunks));
     if (rc) return rc;
     static_assert(sizeof(long long) == sizeof(int64_t), "offsets are handed on as they are");
-    HK_HIP(hk::launch_deflate_tiles(planes_dev, hk::dtype_size(dtype), n_bands, height, width, stride, band_stride, tile, sl.norm_ws,
-                                    static_cast<unsigned char*>(out_dev), reinterpret_cast<long long*>(tile_offsets_dev),
-                                    reinterpret_cast<long long*>(tile_sizes_dev), sl.stream, predictor));
+    const hk::BandPlanes planes = {.src = planes_dev, .n_bands = n_bands, .height = height, .width = width, .stride = stride, .band_stride = band_stride};
+    HK_HIP(hk::launch_deflate_tiles(predictor, {.planes = planes, .esize = hk::dtype_size(dtype), .tile = tile, .out = static_cast<unsigned char*>(out_dev),
+                                                .tile_offsets = reinterpret_cast<long long*>(tile_offsets_dev),
+                                                .tile_sizes = reinterpret_cast<long long*>(tile_sizes_dev)}, sl.norm_ws, sl.stream));
     return HK_OK;
 }
 
@@ -2706,9 +2741,10 @@ static int deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t
             if ((rc = stage_h2d(sl, base + o_src, d_stride * es, h_src + ((size_t)b * band_stride + (size_t)r0 * stride) * es,
                                 stride * es, (size_t)width * es, rows)))
                 return rc;
-            HK_HIP(hk::launch_deflate_tiles(base + o_src, (int)es, 1, (int)rows, width, d_stride, 0, tile, base + o_work,
-                                            hc.at<unsigned char>(o_out), hc.at<long long>(o_off), hc.at<long long>(o_siz), sl.stream,
-                                            predictor));
+            const hk::BandPlanes slab = {.src = base + o_src, .n_bands = 1, .height = (int)rows, .width = width, .stride = d_stride, .band_stride = 0};
+            HK_HIP(hk::launch_deflate_tiles(predictor, {.planes = slab, .esize = (int)es, .tile = tile, .out = hc.at<unsigned char>(o_out),
+                                                        .tile_offsets = hc.at<long long>(o_off), .tile_sizes = hc.at<long long>(o_siz)},
+                                            base + o_work, sl.stream));
             // the offsets first (they say how many bytes there are), then only the compressed bytes
             if ((rc = stage_d2h(sl, tile_offsets + t0, 0, base + o_off, 0, (size_t)(nt + 1) * sizeof(int64_t), 1))) return rc;
             if ((rc = stage_d2h(sl, tile_sizes + t0, 0, base + o_siz, 0, (size_t)nt * sizeof(int64_t), 1))) return rc;
@@ -3307,7 +3343,8 @@ int hk_synth_fill_dev(hk_ctx* ctx, float* src, float* ref, int32_t n_bands, int3
     if (!ctx || !src || !ref) return fail(HK_ERR_ARG, "NULL argument");
     if (const int bad = check_stream(ctx, stream)) return bad;
     HK_ENTER(ctx);
-    HK_HIP(hk::launch_synth_fill(src, ref, n_bands, height, width, stride, band_stride, seed, nodata_variant,
+    HK_HIP(hk::launch_synth_fill({.src = src, .ref = ref, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
+                                  .band_stride = band_stride, .seed = seed, .nodata_variant = nodata_variant},
                                  ctx->slots[stream].stream));
     return HK_OK;
 }
@@ -3426,10 +3463,11 @@ int hk_debug_cast_plane_dev(hk_ctx* ctx, int32_t to_typed, int32_t dtype, const 
     DevEnter entered(ctx, stream);
     Slot& sl = ctx->slots[stream];
     if (to_typed)
-        HK_HIP(hk::launch_cast_out(dtype, static_cast<const float*>(src_dev), src_stride, dst_dev, dst_stride, height, width, has_nodata,
-                                   nodata, sl.stream));
+        HK_HIP(hk::launch_cast_out(dtype, {.in = src_dev, .in_stride = src_stride, .out = dst_dev, .out_stride = dst_stride,
+                                           .height = height, .width = width, .has_nodata = has_nodata, .nodata = nodata}, sl.stream));
     else
-        HK_HIP(hk::launch_cast_in(dtype, src_dev, src_stride, static_cast<float*>(dst_dev), dst_stride, height, width, sl.stream));
+        HK_HIP(hk::launch_cast_in(dtype, {.in = src_dev, .in_stride = src_stride, .out = dst_dev, .out_stride = dst_stride,
+                                          .height = height, .width = width}, sl.stream));
     HK_HIP(hipStreamSynchronize(sl.stream));
     return HK_OK;
 }

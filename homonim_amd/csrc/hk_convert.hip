@@ -73,10 +73,10 @@ static dim3 cast_grid(int height, int width) {
     return dim3((width + 256 * PX - 1) / (256 * PX), height < 2048 ? height : 2048);
 }
 
-hipError_t launch_cast_in(int dtype, const void* in, long long in_stride, float* out, long long out_stride, int height,
-                          int width, hipStream_t stream) {
-    const dim3 g = cast_grid(height, width), b(256);
-#define HK_CAST_IN(T) HK_LAUNCH(cast_in_kernel<T>, g, b, 0, stream, static_cast<const T*>(in), in_stride, out, out_stride, height, width)
+hipError_t launch_cast_in(int dtype, const CastPlane& r, hipStream_t stream) {
+    const dim3 g = cast_grid(r.height, r.width), b(256);
+#define HK_CAST_IN(T) \
+    HK_LAUNCH(cast_in_kernel<T>, g, b, 0, stream, static_cast<const T*>(r.in), r.in_stride, static_cast<float*>(r.out), r.out_stride, r.height, r.width)
     switch (dtype) {
         case 1: HK_CAST_IN(unsigned char); break;
         case 2: HK_CAST_IN(unsigned short); break;
@@ -90,10 +90,11 @@ hipError_t launch_cast_in(int dtype, const void* in, long long in_stride, float*
     return hipGetLastError();
 }
 
-hipError_t launch_cast_out(int dtype, const float* in, long long in_stride, void* out, long long out_stride, int height,
-                           int width, int has_nodata, double nodata, hipStream_t stream) {
-    const dim3 g = cast_grid(height, width), b(256);
-#define HK_CAST_OUT(T) HK_LAUNCH(cast_out_kernel<T>, g, b, 0, stream, in, in_stride, static_cast<T*>(out), out_stride, height, width, has_nodata, nodata)
+hipError_t launch_cast_out(int dtype, const CastPlane& r, hipStream_t stream) {
+    const dim3 g = cast_grid(r.height, r.width), b(256);
+#define HK_CAST_OUT(T)                                                                                                                      \
+    HK_LAUNCH(cast_out_kernel<T>, g, b, 0, stream, static_cast<const float*>(r.in), r.in_stride, static_cast<T*>(r.out), r.out_stride, r.height, \
+              r.width, r.has_nodata, r.nodata)
     switch (dtype) {
         case 0: HK_CAST_OUT(float); break;
         case 1: HK_CAST_OUT(unsigned char); break;

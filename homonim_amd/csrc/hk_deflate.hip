@@ -28,7 +28,7 @@
 // workgroup per chunk): the slots compacted into contiguous tile streams, zlib header, final block and combined Adler-32.
 // About 78 KiB of LDS per workgroup: two workgroups per CU.
 //
-// WITH A PREDICTOR (TIFF tag 317; launch_deflate_tiles(..., predictor)) all of the above holds for the tile's PREDICTED bytes: the
+// WITH A PREDICTOR (TIFF tag 317; launch_deflate_tiles(predictor, ...)) all of the above holds for the tile's PREDICTED bytes: the
 // predictor runs over each zero-padded tile row on its own (deflate::predicted_byte in hk_deflate_core.h states both: 2, integer
 // differences modulo the sample's width; 3, libtiff's floating-point predictor -- byte planes, most significant first, differenced
 // modulo 256 over the whole row), the Adler-32 is taken over the predicted bytes, and the two candidate distances are the sample
@@ -240,17 +240,17 @@ size_t deflate_workspace_bytes(long long n_chunks) {
     return (size_t)n_chunks * deflate::SLOT + ((size_t)n_chunks * 8 + 255) / 256 * 256;
 }
 
-hipError_t launch_deflate_tiles(const void* src, int esize, int n_bands, int height, int width, long long stride,
-                                long long band_stride, int tile, void* work, unsigned char* out, long long* tile_offsets,
-                                long long* tile_sizes, hipStream_t stream, int predictor) {
+hipError_t launch_deflate_tiles(int predictor, const DeflateTiles& r, void* work, hipStream_t stream) {
+    const BandPlanes& p = r.planes;
+    const int esize = r.esize, tile = r.tile;
     DeflateArgs a;
     memset(&a, 0, sizeof(a));
-    a.src = src, a.es = esize, a.height = height, a.width = width, a.stride = stride, a.band_stride = band_stride;
-    a.tile = tile, a.across = (width + tile - 1) / tile, a.down = (height + tile - 1) / tile;
+    a.src = p.src, a.es = esize, a.height = p.height, a.width = p.width, a.stride = p.stride, a.band_stride = p.band_stride;
+    a.tile = tile, a.across = (p.width + tile - 1) / tile, a.down = (p.height + tile - 1) / tile;
     a.tile_bytes = tile * tile * esize, a.cpt = (a.tile_bytes + deflate::CHUNK - 1) / deflate::CHUNK;
-    const long long n_tiles = (long long)n_bands * a.across * a.down, n_chunks = n_tiles * a.cpt;
+    const long long n_tiles = (long long)p.n_bands * a.across * a.down, n_chunks = n_tiles * a.cpt;
     if (n_chunks > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    a.vec_ok = ((uintptr_t)src % 16 == 0) && ((stride * esize) % 16 == 0) && ((band_stride * esize) % 16 == 0);
+    a.vec_ok = ((uintptr_t)p.src % 16 == 0) && ((p.stride * esize) % 16 == 0) && ((p.band_stride * esize) % 16 == 0);
     a.slots = static_cast<unsigned char*>(work);
     a.sizes = reinterpret_cast<unsigned*>(a.slots + (size_t)n_chunks * deflate::SLOT);
     a.adler = a.sizes + n_chunks;
@@ -262,9 +262,9 @@ hipError_t launch_deflate_tiles(const void* src, int esize, int n_bands, int hei
         e = launch_deflate_pred_chunks(a, predictor, n_chunks, stream);
     }
     if (e != hipSuccess) return e;
-    HK_LAUNCH(deflate_offsets_kernel, dim3(1), dim3(256), 0, stream, a, (int)n_tiles, tile_offsets, tile_sizes);
+    HK_LAUNCH(deflate_offsets_kernel, dim3(1), dim3(256), 0, stream, a, (int)n_tiles, r.tile_offsets, r.tile_sizes);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    HK_LAUNCH(deflate_gather_kernel, dim3((unsigned)n_chunks), dim3(256), 0, stream, a, tile_offsets, out);
+    HK_LAUNCH(deflate_gather_kernel, dim3((unsigned)n_chunks), dim3(256), 0, stream, a, r.tile_offsets, r.out);
     return hipGetLastError();
 }
 

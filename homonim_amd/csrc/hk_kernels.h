@@ -290,10 +290,26 @@ struct ParamStatsArgs {
 size_t param_stats_workspace_bytes(int n_bands);
 hipError_t launch_param_stats(const ParamStatsArgs& a, void* workspace, double* stats_out, hipStream_t stream);
 
+// The raster that the overview and the DEFLATE launchers read: n_bands planes of height x width samples, strides in elements.
+struct BandPlanes {
+    const void* src;
+    int n_bands, height, width;
+    long long stride, band_stride;
+};
+
 // Average overviews (hk_overview.hip; homonim/fuse.py:152-165): level m = 1..n_levels of shape (ceil(height / 2^m),
 // ceil(width / 2^m)), each the clipped 2 x 2 mean of the valid pixels of the level before it, all bands, OVERVIEW_PASS_LEVELS
 // levels per launch.  dtype = hk_dtype; strides in elements; out[m - 1] / out_stride / out_band_stride describe level m.
 constexpr int OVERVIEW_PASS_LEVELS = 6;
+struct OverviewLevels {
+    BandPlanes planes;
+    int nd_mode;
+    double nodata;
+    int n_levels;  // any number: the launcher slices them into passes
+    void* const* out;
+    const long long* out_stride;
+    const long long* out_band_stride;
+};
 struct OverviewArgs {
     const void* src;
     int height, width;
@@ -305,14 +321,19 @@ struct OverviewArgs {
     long long out_stride[OVERVIEW_PASS_LEVELS], out_band_stride[OVERVIEW_PASS_LEVELS];
     int vec_ok, out_vec_ok;  // set by the launcher: 16-byte row loads / 8-byte level-1 stores are legal
 };
-hipError_t launch_overviews(int dtype, const void* src, int height, int width, long long stride, long long band_stride,
-                            int n_bands, int nd_mode, double nodata, int n_levels, void* const* out, const long long* out_stride,
-                            const long long* out_band_stride, hipStream_t stream);
+hipError_t launch_overviews(int dtype, const OverviewLevels& r, hipStream_t stream);
 
 // DEFLATE streams of the tiles of a tiled GeoTIFF (hk_deflate.hip, which states the stream format): the raster's tiles of
 // `tile` x `tile` samples of `esize` bytes, edge tiles zero-padded, in the order band, tile row, tile column; one zlib stream per
 // tile into `out` at tile_offsets[t] (even), tile_sizes[t] bytes long; tile_offsets[n_tiles] = the bytes used.  Strides in
 // elements.  `work`: deflate_workspace_bytes(number of chunks) of device memory; everything is queued on `stream`.
+struct DeflateTiles {
+    BandPlanes planes;
+    int esize, tile;
+    unsigned char* out;
+    long long* tile_offsets;
+    long long* tile_sizes;
+};
 struct DeflateArgs {
     const void* src;
     int es, height, width;
@@ -325,9 +346,7 @@ struct DeflateArgs {
     unsigned* adler;          // per chunk: (sum of bytes mod 65521) | (weighted sum mod 65521) << 16
 };
 size_t deflate_workspace_bytes(long long n_chunks);
-hipError_t launch_deflate_tiles(const void* src, int esize, int n_bands, int height, int width, long long stride,
-                                long long band_stride, int tile, void* work, unsigned char* out, long long* tile_offsets,
-                                long long* tile_sizes, hipStream_t stream, int predictor = 1);
+hipError_t launch_deflate_tiles(int predictor, const DeflateTiles& r, void* work, hipStream_t stream);
 // the chunk kernel of predictors 2 and 3 (hk_deflate_pred.hip), launched by launch_deflate_tiles in place of deflate_chunk_kernel
 hipError_t launch_deflate_pred_chunks(const DeflateArgs& a, int predictor, long long n_chunks, hipStream_t stream);
 
@@ -359,22 +378,53 @@ hipError_t launch_lzw_image(InflateArgs a, long long n_blocks, hipStream_t strea
 // `work` is ONE slot, `status` may be NULL.  -> the first refused block (its status in *first_status), or -1.
 long long lzw_image_host(const InflateArgs& a, long long n_blocks, int* first_status);
 
-hipError_t launch_synth_fill(float* src, float* ref, int n_bands, int height, int width, long long stride,
-                             long long band_stride, unsigned long long seed, int nodata_variant, hipStream_t stream);
+// the synthetic source / reference pair of the benchmark and the self-checks (hk_kernels.hip synth_kernel states the variants)
+struct SynthFill {
+    float* src;
+    float* ref;
+    int n_bands, height, width;
+    long long stride, band_stride;
+    unsigned long long seed;
+    int nodata_variant;
+};
+hipError_t launch_synth_fill(const SynthFill& r, hipStream_t stream);
 
 // Typed IO (hk_convert.hip).  dtype codes = hk_dtype of include/homonim_hk.h: 0 f32, 1 u8, 2 u16, 3 i16, 4 u32, 5 i32, 6 f64.
-hipError_t launch_cast_in(int dtype, const void* in, long long in_stride, float* out, long long out_stride, int height,
-                          int width, hipStream_t stream);
-hipError_t launch_cast_out(int dtype, const float* in, long long in_stride, void* out, long long out_stride, int height,
-                           int width, int has_nodata, double nodata, hipStream_t stream);
+// One plane between `dtype` and float32: cast_in reads `in` as dtype and writes float32, cast_out reads float32 and writes dtype
+// (NaN -> nodata when has_nodata, which cast_in does not read).  Strides in elements of each side's own type.
+struct CastPlane {
+    const void* in;
+    long long in_stride;
+    void* out;
+    long long out_stride;
+    int height, width;
+    int has_nodata = 0;
+    double nodata = 0.;
+};
+hipError_t launch_cast_in(int dtype, const CastPlane& r, hipStream_t stream);
+hipError_t launch_cast_out(int dtype, const CastPlane& r, hipStream_t stream);
 inline int dtype_size(int dtype) { const int sz[7] = {4, 1, 2, 2, 4, 4, 8}; return dtype >= 0 && dtype < 7 ? sz[dtype] : 0; }
 
 // mask_partial on a shared grid (hk_mask.hip): full-coverage mask from valid(in) & params, eroded by (kh+2) x (kw+2);
 // writes masked parameters and/or the corrected block and/or the uint8 mask.  rowcnt_ws: height x stride uint16.
-hipError_t launch_partial_mask(const float* in, int nd_mode, float nodata, const float* params, int n_bands,
-                               long long band_stride, const float* src, int height, int width, long long stride, int kh,
-                               int kw, unsigned short* rowcnt_ws, float* params_out, float* corr_out,
-                               unsigned char* mask_out, hipStream_t stream);
+constexpr int ND_COVERAGE = 3;  // PartialMask::nd_mode: `in` is a coverage fraction, valid where it is >= 1 (nodata unused)
+struct PartialMask {
+    const float* in;
+    int nd_mode;
+    float nodata = 0.f;
+    const float* params;  // n_bands planes band_stride apart, gain and offset first
+    int n_bands;
+    long long band_stride;
+    const float* src = nullptr;  // read for corr_out only
+    int height, width;
+    long long stride;            // of every plane, the workspace included
+    int kh, kw;
+    // what to write, each or NULL: the masked parameters (n_bands planes), gain * src + offset under the mask, the mask as bytes
+    float* params_out = nullptr;
+    float* corr_out = nullptr;
+    unsigned char* mask_out = nullptr;
+};
+hipError_t launch_partial_mask(const PartialMask& r, unsigned short* rowcnt_ws, hipStream_t stream);
 
 // In-painting of the offset band (hk_inpaint.hip; GDALFillNodata restated): sources are pixels with r2 > thresh and
 // gain > 0 (flag 1), flag 0 pixels are targets and are filled IN PLACE (a filled pixel never acts as a source: sources are read
@@ -416,13 +466,26 @@ inline bool resample_stretched(double kx, double ky) { return kx > 1.0 + 1e-9 ||
 // Re-sampling between same-CRS axis-aligned grids (hk_resample.hip): src_col = kx * dst_col + ox, src_row = ky * dst_row + oy.
 // mode = rasterio.enums.Resampling value (0..6, 8..14).
 hipError_t launch_resample(int mode, const ResamplePlanes& p, double kx, double ox, double ky, double oy, hipStream_t stream);
+constexpr int RS_NEAREST = 0, RS_AVERAGE = 5;  // the two modes that hk_api.hip asks for by itself
 // `average` (mode 5) of ONE plane of sample type `dtype` (hk_dtype) read as it was uploaded: bit for bit launch_cast_in followed by
 // launch_resample(5, ...) into `value` (pixels that receive nothing: `fill`) and, when `coverage` is not NULL, launch_valid_plane
 // followed by launch_resample(5, ...) without nodata and fill 0 into it -- the typed pixels are read once.  Both destination planes
-// have row stride dst_stride.
-hipError_t launch_footprint_typed(int dtype, const void* src, long long src_stride, int sh, int sw, int nd_mode, float nodata,
-                                  float* value, float* coverage, long long dst_stride, int dh, int dw, float fill, double kx,
-                                  double ox, double ky, double oy, hipStream_t stream);
+// have row stride dst_stride.  The kernel of sample type T receives FootTypedArgs<T>; the launcher takes FootTypedArgs<void>.
+template <typename T>
+struct FootTypedArgs {
+    const T* src;
+    long long src_stride;
+    int sh, sw;
+    int nd_mode;
+    float nodata;
+    float* value;
+    float* coverage;  // nullable
+    long long dst_stride;
+    int dh, dw;
+    float fill;
+    double kx, ox, ky, oy;
+};
+hipError_t launch_footprint_typed(int dtype, const FootTypedArgs<void>& r, hipStream_t stream);
 
 // Re-sampling between grids of two CRSs (hk_warp.hip): the continuous source pixel coordinates of the destination positions
 // (row + off_row, col + off_col) of an h x w lattice, and launch_resample's modes 0..4 on them (kx, ky: the mean step, which picks
@@ -443,15 +506,53 @@ hipError_t launch_warp_resample(int mode, const hk_affine_warp_desc* desc, const
                                 hipStream_t stream, const char** why);
 
 size_t upsample_apply_workspace_bytes(int height);
-hipError_t launch_upsample_apply(int mode, const float* src, long long src_stride, int nd_mode, float nodata,
-                                 const float* gain, const float* offset, long long par_stride, int ph, int pw,
-                                 const float* keep, long long keep_stride, float* out, long long out_stride, int height,
-                                 int width, double kx, double ox, double ky, double oy, void* workspace, hipStream_t stream);
-hipError_t launch_valid_plane(const float* in, long long in_stride, int nd_mode, float nodata, float* out,
-                              long long out_stride, int height, int width, hipStream_t stream);
-hipError_t launch_apply_space(const float* src, long long src_stride, int nd_mode, float nodata, const float* gain,
-                              const float* offset, long long par_stride, const float* keep, float* out,
-                              long long out_stride, int height, int width, hipStream_t stream);
+// RefSpaceModel.apply fused with the up-sampling of its parameters (hk_resample.hip): out = gain * src + offset on the height x
+// width source grid, gain / offset bilinear (mode 1) or cubic_spline (3) values of the coarse ph x pw planes under launch_resample's
+// mapping, masked by `keep` where given, else by valid(src).  These are UpApplyArgs' fields, which the kernel receives, and the
+// row axis (ky, oy) of the table that the launcher makes in `workspace`.
+struct UpsampleApply {
+    const float* src;
+    long long src_stride;
+    int nd_mode;
+    float nodata;
+    const float* gain;  // coarse parameter planes, NaN = nodata
+    const float* offset;
+    long long par_stride;
+    int ph, pw;
+    const float* keep = nullptr;  // full-resolution 0/1 plane (mask_partial)
+    long long keep_stride = 0;
+    float* out;
+    long long out_stride;
+    int height, width;
+    double kx, ox, ky, oy;
+};
+hipError_t launch_upsample_apply(int mode, const UpsampleApply& r, void* workspace, hipStream_t stream);
+// ... with the parameters already on the source grid: gain, offset and `keep` share par_stride
+struct ApplySpace {
+    const float* src;
+    long long src_stride;
+    int nd_mode;
+    float nodata;
+    const float* gain;
+    const float* offset;
+    long long par_stride;
+    const float* keep = nullptr;
+    float* out;
+    long long out_stride;
+    int height, width;
+};
+hipError_t launch_apply_space(const ApplySpace& r, hipStream_t stream);
+// valid(in) as a float32 0/1 plane
+struct ValidPlane {
+    const float* in;
+    long long in_stride;
+    int nd_mode;
+    float nodata;
+    float* out;  // 1.f where `in` is valid, else 0.f
+    long long out_stride;
+    int height, width;
+};
+hipError_t launch_valid_plane(const ValidPlane& r, hipStream_t stream);
 
 // flat 2-read 1-write float4 stream (measurement aid: what the HBM gives the fused kernel's byte mix without its stencil)
 hipError_t launch_stream_probe(const void* a, const void* b, void* out, size_t n_bytes, hipStream_t stream);

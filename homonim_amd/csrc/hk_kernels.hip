@@ -217,12 +217,11 @@ __global__ void __launch_bounds__(256) synth_kernel(float* __restrict__ src, flo
     }
 }
 
-hipError_t launch_synth_fill(float* src, float* ref, int n_bands, int height, int width, long long stride,
-                             long long band_stride, unsigned long long seed, int nodata_variant, hipStream_t stream) {
+hipError_t launch_synth_fill(const SynthFill& r, hipStream_t stream) {
     const int threads = 256;
-    const int gy = height < 2048 ? height : 2048;
-    HK_LAUNCH(synth_kernel, dim3((width + threads - 1) / threads, gy, n_bands), dim3(threads), 0, stream, src,
-                       ref, n_bands, height, width, stride, band_stride, seed, nodata_variant);
+    const int gy = r.height < 2048 ? r.height : 2048;
+    HK_LAUNCH(synth_kernel, dim3((r.width + threads - 1) / threads, gy, r.n_bands), dim3(threads), 0, stream, r.src,
+                       r.ref, r.n_bands, r.height, r.width, r.stride, r.band_stride, r.seed, r.nodata_variant);
     return hipGetLastError();
 }
 

@@ -59,16 +59,13 @@ __global__ void __launch_bounds__(256) mask_cols_kernel(const unsigned short* __
     }
 }
 
-hipError_t launch_partial_mask(const float* in, int nd_mode, float nodata, const float* params, int n_bands,
-                               long long band_stride, const float* src, int height, int width, long long stride, int kh,
-                               int kw, unsigned short* rowcnt_ws, float* params_out, float* corr_out,
-                               unsigned char* mask_out, hipStream_t stream) {
-    const dim3 block(256), grid((width + 255) / 256, height < 1024 ? height : 1024);
-    const int rhe = kh / 2 + 1, rwe = kw / 2 + 1;  // structuring element (kh + 2) x (kw + 2)
-    HK_LAUNCH(mask_rows_kernel, grid, block, 0, stream, in, nd_mode, nodata, params, params + band_stride, stride,
-                       height, width, rwe, rowcnt_ws);
-    HK_LAUNCH(mask_cols_kernel, grid, block, 0, stream, rowcnt_ws, stride, height, width, rhe,
-                       (kh + 2) * (kw + 2), params, band_stride, n_bands, src, params_out, corr_out, mask_out);
+hipError_t launch_partial_mask(const PartialMask& r, unsigned short* rowcnt_ws, hipStream_t stream) {
+    const dim3 block(256), grid((r.width + 255) / 256, r.height < 1024 ? r.height : 1024);
+    const int rhe = r.kh / 2 + 1, rwe = r.kw / 2 + 1;  // structuring element (kh + 2) x (kw + 2)
+    HK_LAUNCH(mask_rows_kernel, grid, block, 0, stream, r.in, r.nd_mode, r.nodata, r.params, r.params + r.band_stride, r.stride,
+                       r.height, r.width, rwe, rowcnt_ws);
+    HK_LAUNCH(mask_cols_kernel, grid, block, 0, stream, rowcnt_ws, r.stride, r.height, r.width, rhe,
+                       (r.kh + 2) * (r.kw + 2), r.params, r.band_stride, r.n_bands, r.src, r.params_out, r.corr_out, r.mask_out);
     return hipGetLastError();
 }
 

@@ -213,25 +213,24 @@ bool aligned_to(const void* p, long long stride, long long band_stride, int esiz
 
 }  // namespace
 
-hipError_t launch_overviews(int dtype, const void* src, int height, int width, long long stride, long long band_stride,
-                            int n_bands, int nd_mode, double nodata, int n_levels, void* const* out, const long long* out_stride,
-                            const long long* out_band_stride, hipStream_t stream) {
+hipError_t launch_overviews(int dtype, const OverviewLevels& r, hipStream_t stream) {
     const int esize = dtype_size(dtype);
     if (!esize) return hipErrorInvalidValue;
     const bool is_float = dtype == 0 || dtype == 6;
-    for (int l0 = 0; l0 < n_levels; l0 += OVERVIEW_PASS_LEVELS) {
+    BandPlanes p = r.planes;  // what a pass reads: the raster, then the coarsest level of the pass before
+    for (int l0 = 0; l0 < r.n_levels; l0 += OVERVIEW_PASS_LEVELS) {
         OverviewArgs a;
         memset(&a, 0, sizeof(a));
-        a.src = src, a.height = height, a.width = width, a.stride = stride, a.band_stride = band_stride;
-        a.nd_mode = (!is_float && nd_mode == 1) ? 0 : nd_mode;  // an integer never is NaN
-        a.nodata = dtype == 0 ? (double)(float)nodata : nodata;
-        a.n_levels = n_levels - l0 < OVERVIEW_PASS_LEVELS ? n_levels - l0 : OVERVIEW_PASS_LEVELS;
+        a.src = p.src, a.height = p.height, a.width = p.width, a.stride = p.stride, a.band_stride = p.band_stride;
+        a.nd_mode = (!is_float && r.nd_mode == 1) ? 0 : r.nd_mode;  // an integer never is NaN
+        a.nodata = dtype == 0 ? (double)(float)r.nodata : r.nodata;
+        a.n_levels = r.n_levels - l0 < OVERVIEW_PASS_LEVELS ? r.n_levels - l0 : OVERVIEW_PASS_LEVELS;
         for (int k = 0; k < a.n_levels; ++k)
-            a.out[k] = out[l0 + k], a.out_stride[k] = out_stride[l0 + k], a.out_band_stride[k] = out_band_stride[l0 + k];
-        a.vec_ok = aligned_to(src, stride, band_stride, esize, 16);
+            a.out[k] = r.out[l0 + k], a.out_stride[k] = r.out_stride[l0 + k], a.out_band_stride[k] = r.out_band_stride[l0 + k];
+        a.vec_ok = aligned_to(p.src, p.stride, p.band_stride, esize, 16);
         a.out_vec_ok = aligned_to(a.out[0], a.out_stride[0], a.out_band_stride[0], esize, 8);
         const int tw = esize >= 4 ? tile_width<float>() : (esize == 2 ? tile_width<short>() : tile_width<unsigned char>());
-        const dim3 grid((width + tw - 1) / tw, (height + OVW_ROWS - 1) / OVW_ROWS, n_bands), block(OVW_THREADS);
+        const dim3 grid((p.width + tw - 1) / tw, (p.height + OVW_ROWS - 1) / OVW_ROWS, p.n_bands), block(OVW_THREADS);
         switch (dtype) {
             case 0: HK_LAUNCH(overview_kernel<float>, grid, block, 0, stream, a); break;
             case 1: HK_LAUNCH(overview_kernel<unsigned char>, grid, block, 0, stream, a); break;
@@ -243,9 +242,9 @@ hipError_t launch_overviews(int dtype, const void* src, int height, int width, l
         }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        const int k = a.n_levels;  // the next pass reads the coarsest level of this one
-        src = a.out[k - 1], stride = a.out_stride[k - 1], band_stride = a.out_band_stride[k - 1];
-        height = (int)(((long long)height + (1 << k) - 1) >> k), width = (int)(((long long)width + (1 << k) - 1) >> k);
+        const int k = a.n_levels;
+        p.src = a.out[k - 1], p.stride = a.out_stride[k - 1], p.band_stride = a.out_band_stride[k - 1];
+        p.height = (int)(((long long)p.height + (1 << k) - 1) >> k), p.width = (int)(((long long)p.width + (1 << k) - 1) >> k);
     }
     return hipSuccess;
 }

@@ -155,21 +155,6 @@ __global__ void __launch_bounds__(256) resample_conv_kernel(const ResampleArgs a
 // valid one adds w * 1.0 = w, so the numerator is `wsum`, the weight sum of the value, bit for bit; only the denominator `wall`
 // is new.  A footprint that shares no area with the plane gets `fill` and coverage 0.
 template <typename T>
-struct FootTypedArgs {
-    const T* src;
-    long long src_stride;
-    int sh, sw;
-    int nd_mode;
-    float nodata;
-    float* value;
-    float* coverage;  // nullable
-    long long dst_stride;
-    int dh, dw;
-    float fill;
-    double kx, ox, ky, oy;
-};
-
-template <typename T>
 __global__ void __launch_bounds__(256) footprint_typed_kernel(const FootTypedArgs<T> a) {
     typedef __attribute__((address_space(1))) const T gT;
     typedef __attribute__((address_space(1))) float gfloat;
@@ -387,41 +372,34 @@ __global__ void __launch_bounds__(256) upsample_apply_kernel(const UpApplyArgs a
 size_t upsample_apply_workspace_bytes(int height) { return (size_t)height * sizeof(RowTab); }
 
 // mode: 1 bilinear, 3 cubic_spline (anything else: hipErrorInvalidValue -- the caller keeps the unfused path)
-hipError_t launch_upsample_apply(int mode, const float* src, long long src_stride, int nd_mode, float nodata,
-                                 const float* gain, const float* offset, long long par_stride, int ph, int pw,
-                                 const float* keep, long long keep_stride, float* out, long long out_stride, int height,
-                                 int width, double kx, double ox, double ky, double oy, void* workspace, hipStream_t stream) {
+hipError_t launch_upsample_apply(int mode, const UpsampleApply& r, void* workspace, hipStream_t stream) {
     if (mode != 1 && mode != 3) return hipErrorInvalidValue;
-    if ((long long)ph * par_stride >= 0x7fffffffLL) return hipErrorInvalidValue;  // 32-bit tap offsets
-    if (pw < 4) return hipErrorInvalidValue;                                       // row loads of 4 consecutive taps
+    if ((long long)r.ph * r.par_stride >= 0x7fffffffLL) return hipErrorInvalidValue;  // 32-bit tap offsets
+    if (r.pw < 4) return hipErrorInvalidValue;                                         // row loads of 4 consecutive taps
     RowTab* tab = static_cast<RowTab*>(workspace);
-    UpApplyArgs a;
-    a.src = src, a.src_stride = src_stride, a.nd_mode = nd_mode, a.nodata = nodata, a.gain = gain, a.offset = offset;
-    a.par_stride = par_stride, a.ph = ph, a.pw = pw, a.keep = keep, a.keep_stride = keep_stride, a.out = out;
-    a.out_stride = out_stride, a.height = height, a.width = width, a.kx = kx, a.ox = ox, a.rows = tab;
-    const dim3 tgrid((height + 255) / 256), grid((width + 255) / 256, (height + UP_ROWS - 1) / UP_ROWS), block(256);
+    const UpApplyArgs a = {r.src, r.src_stride, r.nd_mode, r.nodata, r.gain, r.offset, r.par_stride, r.ph, r.pw, r.keep, r.keep_stride,
+                           r.out, r.out_stride, r.height, r.width, r.kx, r.ox, tab};
+    const dim3 tgrid((r.height + 255) / 256), grid((r.width + 255) / 256, (r.height + UP_ROWS - 1) / UP_ROWS), block(256);
     if (mode == 1) {
-        HK_LAUNCH(row_table_kernel<1>, tgrid, block, 0, stream, tab, height, ph, ky, oy);
+        HK_LAUNCH(row_table_kernel<1>, tgrid, block, 0, stream, tab, r.height, r.ph, r.ky, r.oy);
         HK_LAUNCH(upsample_apply_kernel<1>, grid, block, 0, stream, a);
     } else {
-        HK_LAUNCH(row_table_kernel<3>, tgrid, block, 0, stream, tab, height, ph, ky, oy);
+        HK_LAUNCH(row_table_kernel<3>, tgrid, block, 0, stream, tab, r.height, r.ph, r.ky, r.oy);
         HK_LAUNCH(upsample_apply_kernel<3>, grid, block, 0, stream, a);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_valid_plane(const float* in, long long in_stride, int nd_mode, float nodata, float* out,
-                              long long out_stride, int height, int width, hipStream_t stream) {
-    HK_LAUNCH(valid_plane_kernel, dim3((width + 255) / 256, height < 1024 ? height : 1024), dim3(256), 0, stream,
-                       in, in_stride, nd_mode, nodata, out, out_stride, height, width);
+hipError_t launch_valid_plane(const ValidPlane& r, hipStream_t stream) {
+    HK_LAUNCH(valid_plane_kernel, dim3((r.width + 255) / 256, r.height < 1024 ? r.height : 1024), dim3(256), 0, stream,
+                       r.in, r.in_stride, r.nd_mode, r.nodata, r.out, r.out_stride, r.height, r.width);
     return hipGetLastError();
 }
 
-hipError_t launch_apply_space(const float* src, long long src_stride, int nd_mode, float nodata, const float* gain,
-                              const float* offset, long long par_stride, const float* keep, float* out,
-                              long long out_stride, int height, int width, hipStream_t stream) {
-    HK_LAUNCH(apply_space_kernel, dim3((width + 255) / 256, height < 1024 ? height : 1024), dim3(256), 0, stream,
-                       src, src_stride, nd_mode, nodata, gain, offset, par_stride, keep, out, out_stride, height, width);
+hipError_t launch_apply_space(const ApplySpace& r, hipStream_t stream) {
+    HK_LAUNCH(apply_space_kernel, dim3((r.width + 255) / 256, r.height < 1024 ? r.height : 1024), dim3(256), 0, stream,
+                       r.src, r.src_stride, r.nd_mode, r.nodata, r.gain, r.offset, r.par_stride, r.keep, r.out, r.out_stride, r.height,
+                       r.width);
     return hipGetLastError();
 }
 
@@ -455,20 +433,16 @@ hipError_t launch_resample(int mode, const ResamplePlanes& p, double kx, double 
     return hipGetLastError();
 }
 
+// the request with its plane typed: what footprint_typed_kernel<T> receives
 template <typename T>
-static FootTypedArgs<T> foot_typed_args(const void* src, long long src_stride, int sh, int sw, int nd_mode, float nodata, float* value,
-                                        float* coverage, long long dst_stride, int dh, int dw, float fill, double kx, double ox,
-                                        double ky, double oy) {
-    return {static_cast<const T*>(src), src_stride, sh, sw, nd_mode, nodata, value, coverage, dst_stride, dh, dw, fill, kx, ox, ky, oy};
+static FootTypedArgs<T> foot_typed_args(const FootTypedArgs<void>& r) {
+    return {static_cast<const T*>(r.src), r.src_stride, r.sh, r.sw, r.nd_mode, r.nodata, r.value, r.coverage, r.dst_stride, r.dh, r.dw,
+            r.fill, r.kx, r.ox, r.ky, r.oy};
 }
 
-hipError_t launch_footprint_typed(int dtype, const void* src, long long src_stride, int sh, int sw, int nd_mode, float nodata,
-                                  float* value, float* coverage, long long dst_stride, int dh, int dw, float fill, double kx,
-                                  double ox, double ky, double oy, hipStream_t stream) {
-    const dim3 grid((dw + 255) / 256, dh), block(256);
-#define HK_FOOT_TYPED(T)                                                                                                          \
-    HK_LAUNCH(footprint_typed_kernel<T>, grid, block, 0, stream,                                                                  \
-              foot_typed_args<T>(src, src_stride, sh, sw, nd_mode, nodata, value, coverage, dst_stride, dh, dw, fill, kx, ox, ky, oy))
+hipError_t launch_footprint_typed(int dtype, const FootTypedArgs<void>& r, hipStream_t stream) {
+    const dim3 grid((r.dw + 255) / 256, r.dh), block(256);
+#define HK_FOOT_TYPED(T) HK_LAUNCH(footprint_typed_kernel<T>, grid, block, 0, stream, foot_typed_args<T>(r))
     switch (dtype) {
         case 0: HK_FOOT_TYPED(float); break;
         case 1: HK_FOOT_TYPED(unsigned char); break;
