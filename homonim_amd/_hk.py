@@ -133,6 +133,10 @@ SIGNATURES = {
                                C.c_double, C.c_int32, _P(C.c_void_p), _P(C.c_int64), _P(C.c_int64)]),
     'hk_overviews_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                    C.c_int32, C.c_double, C.c_int32, _P(C.c_void_p), _P(C.c_int64), _P(C.c_int64), C.c_int32]),
+    'hk_dataset_mask': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
+                                  C.c_int64, _f32p, C.c_int64]),
+    'hk_dataset_mask_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                      C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]),
     'hk_deflate_bound': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int64), _P(C.c_int64)]),
     'hk_deflate_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
                                    C.c_void_p, C.c_int64, _P(C.c_int64), _P(C.c_int64)]),
@@ -235,6 +239,7 @@ SIGNATURES = {
                                           C.c_int32, C.c_int32, C.c_double, C.c_int32]),
 }  # yapf: disable
 
+MASK_BITS, MASK_ALPHA = 0, 1   # HK_MASK_BITS, HK_MASK_ALPHA: the mask_kind of hk_dataset_mask / hk_dataset_mask_dev
 PARAM_STATS_N = 10    # values per band of hk_param_stats / hk_param_stats_dev
 COMM_ID_BYTES = 128   # HK_COMM_ID_BYTES = sizeof(ncclUniqueId)
 
@@ -640,6 +645,48 @@ class Context:
                                       arr.strides[1] // it, arr.strides[0] // it if nb > 1 else 0, mode, value, n_levels, ptrs,
                                       strides, bstrides))
         return [o[0] for o in outs] if squeeze else outs
+
+    def dataset_mask(self, array: np.ndarray, mask: Optional[np.ndarray] = None, alpha: Optional[np.ndarray] = None) -> np.ndarray:
+        """ The per-dataset mask of a GeoTIFF applied to its bands (hk_dataset_mask): a (bands, h, w) or (h, w) raster of any
+        DTYPE_CODES dtype in host memory -> float32 of the same shape, ``float32(array)`` where the pixel is valid and NaN
+        (0x7FC00000) elsewhere, every band alike.  Exactly one of ``mask``: the packed bits of an internal mask as
+        ``tiff.TiffRaster.mask`` holds them, (h, ceil(w / 8)) uint8, most significant bit first, 1 = valid; ``alpha``: an (h, w)
+        plane of the raster's dtype, which must be uint8 or uint16, valid where it is not 0 (it may be a band of a larger array:
+        rows may be strided).  Rows of ``array`` may be strided (unit column stride); anything else is copied first. """
+        arr = np.asarray(array)
+        squeeze = arr.ndim == 2
+        if squeeze:
+            arr = arr[None]
+        if arr.ndim != 3 or arr.size == 0:
+            raise ValueError('`array` must be a non-empty 2-D or 3-D raster')
+        if arr.dtype.name not in DTYPE_CODES:
+            raise ValueError(f"unsupported dtype '{arr.dtype}'")
+        if (mask is None) == (alpha is None):
+            raise ValueError('exactly one of `mask` and `alpha` must be given')
+        nb, h, w = arr.shape
+        it = arr.dtype.itemsize
+        # (the host entry takes the bands one behind the other: band stride = height x row stride)
+        if arr.strides[2] != it or arr.strides[1] % it or arr.strides[1] < w * it or (nb > 1 and arr.strides[0] != h * arr.strides[1]):
+            arr = np.ascontiguousarray(arr)
+        if mask is not None:
+            kind, m = MASK_BITS, np.asarray(mask)
+            if m.dtype != np.uint8 or m.shape != (h, (w + 7) // 8):
+                raise ValueError(f'`mask` must be uint8 of shape {(h, (w + 7) // 8)}: the packed bits of a {h} x {w} mask, not '
+                                 f'{m.dtype} of shape {m.shape}')
+            mit = 1
+        else:
+            kind, m = MASK_ALPHA, np.asarray(alpha)
+            if arr.dtype.name not in ('uint8', 'uint16'):
+                raise ValueError(f"an alpha band masks uint8 and uint16 rasters, not '{arr.dtype}'")
+            if m.dtype != arr.dtype or m.shape != (h, w):
+                raise ValueError(f'`alpha` must be {arr.dtype} of shape {(h, w)}, not {m.dtype} of shape {m.shape}')
+            mit = it
+        if m.strides[1] != mit or m.strides[0] % mit or m.strides[0] < m.shape[1] * mit:
+            m = np.ascontiguousarray(m)
+        out = np.empty((nb, h, w), np.float32)
+        _check(self._lib.hk_dataset_mask(self._h, arr.ctypes.data_as(C.c_void_p), DTYPE_CODES[arr.dtype.name], nb, h, w,
+                                         arr.strides[1] // it, m.ctypes.data_as(C.c_void_p), kind, m.strides[0] // mit, _ptr(out), w))
+        return out[0] if squeeze else out
 
     def deflate_tiles_packed(self, array: np.ndarray, tile: int, predictor: int = 1):
         """ ``deflate_tiles`` as the library returns it: (uint8 array of the streams, int64 offsets [n_tiles + 1], int64 sizes
@@ -1322,6 +1369,16 @@ class Context:
         _check(self._lib.hk_overviews_dev(self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height,
                                           width, stride, band_stride, mode, value, n, (C.c_void_p * n)(*out_dptrs),
                                           (C.c_int64 * n)(*out_strides), (C.c_int64 * n)(*out_band_strides), stream))
+
+    def dataset_mask_dev(self, planes_dptr: int, dtype: str, n_bands: int, height: int, width: int, stride: int, band_stride: int,
+                         mask_dptr: int, mask_kind: int, mask_stride: int, out_dptr: int, out_stride: int, out_band_stride: int,
+                         stream: int = 0):
+        """ Queue the per-dataset mask of ``n_bands`` device-resident planes of dtype ``dtype``: float32 planes into ``out_dptr``
+        (``mask_kind``: MASK_BITS -- packed rows, ``mask_stride`` in bytes -- or MASK_ALPHA -- a plane of ``dtype``, ``mask_stride``
+        in elements; the other strides in elements; hk_dataset_mask_dev; asynchronous). """
+        _check(self._lib.hk_dataset_mask_dev(self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height,
+                                             width, stride, band_stride, C.c_void_p(mask_dptr), int(mask_kind), mask_stride,
+                                             C.c_void_p(out_dptr), out_stride, out_band_stride, stream))
 
     def deflate_tiles_dev(self, planes_dptr: int, dtype: str, n_bands: int, height: int, width: int, stride: int, band_stride: int,
                           tile: int, out_dptr: int, out_capacity: int, offsets_dptr: int, sizes_dptr: int, stream: int = 0,

@@ -15,7 +15,7 @@ REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, 'csrc')
 LIB_DIR = os.path.join(PKG, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libhomonim_hk.so')
-HIP_SOURCES = ['hk_kernels.hip', 'hk_norm.hip', 'hk_convert.hip', 'hk_mask.hip', 'hk_inpaint.hip', 'hk_resample.hip', 'hk_warp.hip', 'hk_compare.hip', 'hk_param_stats.hip', 'hk_overview.hip', 'hk_deflate.hip', 'hk_deflate_pred.hip', 'hk_inflate.hip', 'hk_lzw.hip', 'hk_lzw_host.hip', 'hk_api.hip']
+HIP_SOURCES = ['hk_kernels.hip', 'hk_norm.hip', 'hk_convert.hip', 'hk_dataset_mask.hip', 'hk_mask.hip', 'hk_inpaint.hip', 'hk_resample.hip', 'hk_warp.hip', 'hk_compare.hip', 'hk_param_stats.hip', 'hk_overview.hip', 'hk_deflate.hip', 'hk_deflate_pred.hip', 'hk_inflate.hip', 'hk_lzw.hip', 'hk_lzw_host.hip', 'hk_api.hip']
 # The fused fit(+apply) kernel (template: csrc/hk_fit_kernel.h) is instantiated in one translation unit per MODEL x R2: the same
 # source compiled six times side by side (object name, extra flags).  The heaviest first, so that it does not start last.
 FIT_TUS = [(f'hk_fit_m{m}_r{r}.o', [f'-DHK_TU_MODEL={m}', f'-DHK_TU_R2={r}']) for m, r in ((2, 1), (0, 1), (1, 1), (2, 0), (0, 0), (1, 0))]
@@ -57,7 +57,7 @@ def build_hip(force: bool = False, verbose: bool = True) -> str:
     """ Compile homonim_amd/csrc/*.hip for gfx950 into homonim_amd/lib/libhomonim_hk.so (in-tree). """
     os.makedirs(LIB_DIR, exist_ok=True)
     headers = [os.path.join(CSRC, 'hk_kernels.h'), os.path.join(CSRC, 'hk_layout.h'), os.path.join(CSRC, 'hk_fit_kernel.h'), os.path.join(CSRC, 'hk_resample_taps.h'), os.path.join(CSRC, 'hk_deflate_core.h'),
-               os.path.join(CSRC, 'hk_inflate_core.h'), os.path.join(CSRC, 'hk_lzw_core.h'), os.path.join(CSRC, 'hk_fpred_core.h'),
+               os.path.join(CSRC, 'hk_inflate_core.h'), os.path.join(CSRC, 'hk_lzw_core.h'), os.path.join(CSRC, 'hk_fpred_core.h'), os.path.join(CSRC, 'hk_maskbits_core.h'),
                os.path.join(REPO, 'include', 'homonim_hk.h'),
                os.path.join(REPO, 'include', 'homonim_hk_devtools.h')]
     objs = []

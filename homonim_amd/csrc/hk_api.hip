@@ -2613,6 +2613,103 @@ int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands
     return stage_finish(sl);
 }
 
+// The per-dataset mask of a GeoTIFF applied to its bands (hk_dataset_mask.hip): see include/homonim_hk.h
+static int check_dataset_mask(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                              int64_t stride, const void* mask, int32_t mask_kind, int64_t mask_stride, const void* out,
+                              int64_t out_stride) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    if (!planes) return fail(HK_ERR_ARG, "planes is NULL");
+    if (!mask) return fail(HK_ERR_ARG, "mask is NULL");
+    if (!out) return fail(HK_ERR_ARG, "out is NULL");
+    if (!hk::dtype_size(dtype)) return fail(HK_ERR_ARG, "bad dtype %d", dtype);
+    if (mask_kind != HK_MASK_BITS && mask_kind != HK_MASK_ALPHA)
+        return fail(HK_ERR_ARG, "bad mask_kind %d: %d (bits) or %d (alpha)", mask_kind, HK_MASK_BITS, HK_MASK_ALPHA);
+    if (mask_kind == HK_MASK_ALPHA && dtype != HK_DTYPE_U8 && dtype != HK_DTYPE_U16)
+        return fail(HK_ERR_ARG, "mask_kind alpha takes dtype uint8 or uint16, not dtype %d", dtype);
+    if (n_bands < 1) return fail(HK_ERR_ARG, "n_bands %d is below 1", n_bands);
+    if (height < 1) return fail(HK_ERR_ARG, "height %d is below 1", height);
+    if (width < 1) return fail(HK_ERR_ARG, "width %d is below 1", width);
+    if (stride < width) return fail(HK_ERR_ARG, "stride %lld is smaller than the width %d", (long long)stride, width);
+    if (out_stride < width) return fail(HK_ERR_ARG, "out_stride %lld is smaller than the width %d", (long long)out_stride, width);
+    const int64_t mask_min = mask_kind == HK_MASK_BITS ? ((int64_t)width + 7) / 8 : (int64_t)width;
+    if (mask_stride < mask_min)
+        return fail(HK_ERR_ARG, "mask_stride %lld is smaller than the %lld %s of a mask row", (long long)mask_stride, (long long)mask_min,
+                    mask_kind == HK_MASK_BITS ? "bytes" : "samples");
+    return HK_OK;
+}
+
+// the body of both entries: the launch, on planes, mask and output that are on the device
+static int dataset_mask_on_device(hipStream_t stream, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height,
+                                  int32_t width, int64_t stride, int64_t band_stride, const void* mask_dev, int32_t mask_kind,
+                                  int64_t mask_stride, float* out_dev, int64_t out_stride, int64_t out_band_stride) {
+    const hk::BandPlanes planes = {.src = planes_dev, .n_bands = n_bands, .height = height, .width = width, .stride = stride, .band_stride = band_stride};
+    HK_HIP(hk::launch_dataset_mask(dtype, {.planes = planes, .mask = mask_dev, .kind = mask_kind, .mask_stride = mask_stride, .out = out_dev,
+                                           .out_stride = out_stride, .out_band_stride = out_band_stride}, stream));
+    return HK_OK;
+}
+
+int hk_dataset_mask_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                        int64_t stride, int64_t band_stride, const void* mask_dev, int32_t mask_kind, int64_t mask_stride,
+                        float* out_dev, int64_t out_stride, int64_t out_band_stride, int32_t stream) {
+    int rc = check_dataset_mask(ctx, planes_dev, dtype, n_bands, height, width, stride, mask_dev, mask_kind, mask_stride, out_dev, out_stride);
+    if (rc || (rc = check_band_strides(band_stride, out_band_stride)) || (rc = check_stream(ctx, stream))) return rc;
+    const uintptr_t es = hk::dtype_size(dtype);
+    if (reinterpret_cast<uintptr_t>(planes_dev) % es || (reinterpret_cast<uintptr_t>(out_dev) & 3u) ||
+        (mask_kind == HK_MASK_ALPHA && reinterpret_cast<uintptr_t>(mask_dev) % es))
+        return fail(HK_ERR_ARG, "planes_dev / mask_dev / out_dev: not aligned to the sample size");
+    DevEnter entered(ctx, stream);
+    HK_ENTER(ctx);
+    return dataset_mask_on_device(ctx->slots[stream].stream, planes_dev, dtype, n_bands, height, width, stride, band_stride, mask_dev,
+                                  mask_kind, mask_stride, out_dev, out_stride, out_band_stride);
+}
+
+// device bytes of one chunk of the host path (rows are independent: the chunking cannot change a bit)
+constexpr size_t DATASET_MASK_CHUNK_BYTES = 64u << 20;
+
+int hk_dataset_mask(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                    const void* mask, int32_t mask_kind, int64_t mask_stride, float* out, int64_t out_stride) {
+    int rc = check_dataset_mask(ctx, planes, dtype, n_bands, height, width, stride, mask, mask_kind, mask_stride, out, out_stride);
+    if (rc) return rc;
+    HK_ENTER(ctx);
+    const size_t es = hk::dtype_size(dtype);
+    // device rows: samples and results padded to ROW_ALIGN elements, a row of mask bits to 16 bytes: every row may go wide
+    const int64_t d_stride = row_align(width);
+    const size_t ms = mask_kind == HK_MASK_BITS ? 1 : es;   // bytes per unit of mask_stride
+    const int64_t d_mstride = mask_kind == HK_MASK_BITS ? (((int64_t)width + 7) / 8 + 15) / 16 * 16 : d_stride;
+    const size_t m_row = mask_kind == HK_MASK_BITS ? (size_t)(((int64_t)width + 7) / 8) : (size_t)width * es;
+    // whole rows per chunk: samples, mask and results of all bands within DATASET_MASK_CHUNK_BYTES (at least one row);
+    // HK_STAGE_CHUNK_KB (read at every call here) lowers the bound for tests of the chunked path
+    const char* e = getenv("HK_STAGE_CHUNK_KB");
+    const size_t cap = (e && atol(e) > 0) ? (size_t)atol(e) << 10 : DATASET_MASK_CHUNK_BYTES;
+    const size_t per_row = (size_t)n_bands * d_stride * (es + sizeof(float)) + (size_t)d_mstride * ms;
+    const int64_t rows_max = std::max<int64_t>(1, std::min<int64_t>(height, (int64_t)(cap / per_row)));
+    SlabLayout L;
+    const size_t o_in = L.take((size_t)n_bands * rows_max * d_stride * es), o_mask = L.take((size_t)rows_max * d_mstride * ms),
+                 o_out = L.take((size_t)n_bands * rows_max * d_stride * sizeof(float));
+    HostCall hc(ctx, L.total);
+    if (hc.rc) return hc.rc;
+    Slot& sl = hc.sl;
+    char* const base = hc.at(0);
+    const char *h_in = static_cast<const char*>(planes), *h_mask = static_cast<const char*>(mask);
+    for (int64_t r0 = 0; r0 < height; r0 += rows_max) {
+        const int64_t rows = std::min<int64_t>(rows_max, height - r0);
+        for (int b = 0; b < n_bands; ++b)
+            if ((rc = stage_h2d(sl, base + o_in + (size_t)b * rows_max * d_stride * es, d_stride * es,
+                                h_in + ((size_t)b * height + (size_t)r0) * stride * es, stride * es, (size_t)width * es, rows)))
+                return rc;
+        if ((rc = stage_h2d(sl, base + o_mask, d_mstride * ms, h_mask + (size_t)r0 * mask_stride * ms, mask_stride * ms, m_row, rows))) return rc;
+        if ((rc = dataset_mask_on_device(sl.stream, base + o_in, dtype, n_bands, (int32_t)rows, width, d_stride, rows_max * d_stride,
+                                         base + o_mask, mask_kind, d_mstride, hc.at<float>(o_out), d_stride, rows_max * d_stride)))
+            return rc;
+        for (int b = 0; b < n_bands; ++b)
+            if ((rc = stage_d2h(sl, out + ((size_t)b * height + (size_t)r0) * out_stride, out_stride * sizeof(float),
+                                hc.at<float>(o_out) + (size_t)b * rows_max * d_stride, d_stride * sizeof(float),
+                                (size_t)width * sizeof(float), rows)))
+                return rc;
+    }
+    return stage_finish(sl);
+}
+
 // DEFLATE streams of a raster's tiles (hk_deflate.hip): see include/homonim_hk.h
 static int deflate_shape(int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int32_t tile, int64_t* n_tiles, int64_t* bytes,
                          int64_t* n_chunks) {

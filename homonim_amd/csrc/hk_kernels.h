@@ -405,6 +405,20 @@ hipError_t launch_cast_in(int dtype, const CastPlane& r, hipStream_t stream);
 hipError_t launch_cast_out(int dtype, const CastPlane& r, hipStream_t stream);
 inline int dtype_size(int dtype) { const int sz[7] = {4, 1, 2, 2, 4, 4, 8}; return dtype >= 0 && dtype < 7 ? sz[dtype] : 0; }
 
+// The per-dataset mask of a GeoTIFF applied to its bands (hk_dataset_mask.hip; homonim/raster_array.py:161-197): float32 planes
+// `out` = valid ? (float)planes : NaN (0x7FC00000), the same validity for every band.  kind 0 (BITS): `mask` are packed rows of
+// bits, most significant first, 1 = valid, mask_stride BYTES apart; kind 1 (ALPHA): a plane of the bands' sample type (uint8 /
+// uint16 only), valid where it is not 0, mask_stride ELEMENTS apart.  dtype = hk_dtype; the other strides in elements.
+struct DatasetMask {
+    BandPlanes planes;
+    const void* mask;
+    int kind;
+    long long mask_stride;
+    float* out;
+    long long out_stride, out_band_stride;
+};
+hipError_t launch_dataset_mask(int dtype, const DatasetMask& a, hipStream_t stream);
+
 // mask_partial on a shared grid (hk_mask.hip): full-coverage mask from valid(in) & params, eroded by (kh+2) x (kw+2);
 // writes masked parameters and/or the corrected block and/or the uint8 mask.  rowcnt_ws: height x stride uint16.
 constexpr int ND_COVERAGE = 3;  // PartialMask::nd_mode: `in` is a coverage fraction, valid where it is >= 1 (nodata unused)

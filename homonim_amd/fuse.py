@@ -243,6 +243,28 @@ def north_up(array: np.ndarray, transform: Optional[Affine]):
     return array, Affine(a, b, c, d, e, f)
 
 
+def dataset_masked(tif):
+    """ A raster ``tiff.read_tiff`` returned as the reference reads it (``RasterArray.from_rio_dataset``, homonim/raster_array.py:
+    161-197): -> (array, nodata, descriptions) without the alpha bands and, where the dataset has a mask, as float32 with NaN
+    wherever it is false -- every band alike.  The rule: an internal mask masks the image and the nodata tag is
+    ignored; otherwise the nodata tag stands; otherwise the trailing alpha band of a 2- or 4-band uint8 / uint16 file masks it
+    (``tif.mask_band``), valid where it is not 0; otherwise every pixel is valid.  The mask is applied by
+    ``Context.dataset_mask`` of the process-wide context.  A file without mask or alpha band comes back as it is. """
+    if tif.mask is None and not tif.alpha_bands:
+        return tif.array, tif.nodata, tif.descriptions
+    keep = [b for b in range(tif.array.shape[0]) if b not in tif.alpha_bands]
+    if not keep:
+        raise ValueError('the raster has alpha bands only')
+    # (alpha bands usually trail: the bands that stay are then a view of the file's array)
+    bands = tif.array if not tif.alpha_bands else tif.array[:len(keep)] if keep == list(range(len(keep))) else tif.array[keep]
+    descriptions = tuple(tif.descriptions[b] for b in keep) if len(tif.descriptions) == tif.array.shape[0] else tif.descriptions
+    if tif.mask is not None:
+        return _hk.default_context().dataset_mask(bands, mask=tif.mask), float('nan'), descriptions
+    if tif.mask_band is not None:
+        return _hk.default_context().dataset_mask(bands, alpha=tif.array[tif.mask_band]), float('nan'), descriptions
+    return bands, tif.nodata, descriptions
+
+
 def shard(items: Sequence, index: int, count: int, contiguous: bool = False) -> List:
     """ The work items of shard ``index`` of ``count``: round-robin, or -- ``contiguous`` -- consecutive runs of (almost)
     equal length, which keeps a shard inside as few bands as possible (the block list is band-major,
@@ -260,7 +282,9 @@ class RasterFuse:
     Correct a source raster to surface reflectance by fusion with a reference raster.
 
     src, ref : float32 arrays (bands, height, width) or (height, width), ``RasterArray`` instances, or GeoTIFF paths
-    (nodata, CRS and geo-transform then come from the files; bands are paired in file order).
+    (nodata, CRS and geo-transform then come from the files; bands are paired in file order, alpha bands left out; a file with
+    an internal mask, or with an alpha band and no nodata tag, is read as float32 with NaN outside its mask: ``dataset_masked``.
+    A masked uint8 raster so occupies four times its file size on the host, as it does in the reference).
     The other constructor arguments mirror homonim.RasterFuse / RasterPairReader where they make sense in memory.
     """
 
@@ -289,13 +313,14 @@ class RasterFuse:
             from homonim_amd.tiff import read_tiff
             self._src_filename = os.fspath(src)
             tif = read_tiff(src, inflater=inflater, lzw=lzw)
-            src, src_nodata, crs, transform = tif.array, tif.nodata, tif.crs, tif.transform
+            src, src_nodata, _ = dataset_masked(tif)
+            crs, transform = tif.crs, tif.transform
         if isinstance(ref, (str, os.PathLike)):
             from homonim_amd.tiff import read_tiff
             self._ref_filename = os.fspath(ref)
             tif = read_tiff(ref, inflater=inflater, lzw=lzw)
-            ref, ref_nodata, ref_transform, ref_crs = tif.array, tif.nodata, tif.transform, tif.crs
-            self._ref_descriptions = tif.descriptions
+            ref, ref_nodata, self._ref_descriptions = dataset_masked(tif)
+            ref_transform, ref_crs = tif.transform, tif.crs
         if isinstance(src, RasterArray):
             src, src_nodata, crs, transform = src.array, src.nodata, src.crs, src.transform
         if isinstance(ref, RasterArray):

@@ -11,7 +11,9 @@ file, fuse.py:241-248).  The writer produces tiled, DEFLATE, band-separate files
 default output profile -- classic or BigTIFF, with predictor 2 or 3 on request -- with internal overviews (reduced-resolution
 images chained behind the first) on request;
 ``read_tiff_overviews`` reads those back.  A rotated or sheared grid is read from, and on request written as, a
-ModelTransformation matrix.  LZW is read only (``lzw_decode``, or a hook of ``read_tiff``).  Everything else (other
+ModelTransformation matrix.  Alpha bands (ExtraSamples 1 / 2) are named and an internal 1-bit mask directory (NewSubfileType 4) is
+decoded to its packed bits (``TiffRaster.alpha_bands``, ``mask_band``, ``mask``; applying them is ``fuse.dataset_masked``'s); masks of
+overviews are skipped, masks are not written.  LZW is read only (``lzw_decode``, or a hook of ``read_tiff``).  Everything else (other
 compressions, palettes) raises.
 """
 import mmap
@@ -31,7 +33,8 @@ _TYPES = {1: 'B', 2: 'c', 3: 'H', 4: 'I', 5: 'II', 6: 'b', 7: 'B', 8: 'h', 9: 'i
 _SAMPLE_DTYPES = {(1, 8): 'u1', (1, 16): 'u2', (1, 32): 'u4', (1, 64): 'u8', (2, 8): 'i1', (2, 16): 'i2', (2, 32): 'i4',
                   (2, 64): 'i8', (3, 32): 'f4', (3, 64): 'f8'}
 
-T_SUBFILE = 254   # NewSubfileType: bit 0 = reduced-resolution version of another image of the file
+T_SUBFILE = 254   # NewSubfileType: bit 0 = reduced-resolution version of another image of the file, bit 2 = transparency mask of one
+T_FILL_ORDER = 266
 T_WIDTH, T_HEIGHT, T_BITS, T_COMPRESSION, T_PHOTOMETRIC, T_STRIP_OFFSETS, T_SPP, T_ROWS_PER_STRIP = 256, 257, 258, 259, 262, 273, 277, 278
 T_STRIP_COUNTS, T_PLANAR, T_PREDICTOR, T_TILE_W, T_TILE_H, T_TILE_OFFSETS, T_TILE_COUNTS, T_EXTRA, T_FORMAT = 279, 284, 317, 322, 323, 324, 325, 338, 339
 T_PIXEL_SCALE, T_TIEPOINT, T_TRANSFORMATION, T_GEOKEYS, T_GEODOUBLES, T_GEOASCII, T_GDAL_METADATA, T_GDAL_NODATA = 33550, 33922, 34264, 34735, 34736, 34737, 42112, 42113
@@ -44,6 +47,9 @@ class TiffRaster(NamedTuple):
     nodata: Optional[float]
     metadata: Dict[str, str]     # dataset-level <GDALMetadata> items
     descriptions: Tuple[Optional[str], ...] = ()   # per band: GDAL's band description, None where the file has none
+    mask: Optional[np.ndarray] = None              # the internal mask as stored: packed bits (height, ceil(width / 8)) uint8, most significant bit first, 1 = valid
+    alpha_bands: Tuple[int, ...] = ()              # 0-based: the bands whose ExtraSamples entry is 1 or 2
+    mask_band: Optional[int] = None                # the alpha band that acts as the mask (no internal mask, no nodata tag)
 
 
 class TiffHeader(NamedTuple):
@@ -57,6 +63,8 @@ class TiffHeader(NamedTuple):
     nodata: Optional[float]
     metadata: Dict[str, str]
     descriptions: Tuple[Optional[str], ...]
+    alpha_bands: Tuple[int, ...] = ()   # as in TiffRaster
+    has_mask: bool = False              # an internal mask directory is chained behind the first image
 
 
 class BlockLayout(NamedTuple):
@@ -185,6 +193,65 @@ def _nodata_tag(t) -> Optional[float]:
         return None
 
 
+def _alpha_bands(t) -> Tuple[int, ...]:
+    """ The bands ExtraSamples (338) calls alpha, associated (1) or not (2): its entries describe the LAST len(extra) samples """
+    spp, extra = t.get(T_SPP, (1,))[0], t.get(T_EXTRA, ())
+    first = spp - len(extra)
+    return tuple(first + i for i, e in enumerate(extra) if e in (1, 2) and 0 <= first + i < spp)
+
+
+def _is_mask(t) -> bool:
+    """ Is this directory a transparency mask (NewSubfileType bit 2), of the main image or of an overview? """
+    return bool(t.get(T_SUBFILE, (0,))[0] & 4)
+
+
+def _mask_directory(buf, t0, nxt):
+    """ The tags of the internal mask of the first image (tags ``t0``; ``nxt``: the offset of the directory behind it), or None: the
+    first directory of the chain with NewSubfileType bit 2 set and bit 0 clear, 1 bit per sample and 1 sample per pixel.  It has
+    the first image's size, or the file is refused. """
+    seen = set()
+    while nxt and nxt not in seen:
+        seen.add(nxt)
+        _, t, following = _read_ifd(buf, nxt)
+        sub = t.get(T_SUBFILE, (0,))[0]
+        if sub & 4 and not sub & 1 and tuple(t.get(T_BITS, (1,))) == (1,) and t.get(T_SPP, (1,))[0] == 1 and T_WIDTH in t and T_HEIGHT in t:
+            shape, main = (t[T_HEIGHT][0], t[T_WIDTH][0]), (t0[T_HEIGHT][0], t0[T_WIDTH][0])
+            if shape != main:
+                raise IoError(f'the internal mask is {shape[0]} x {shape[1]}, the image {main[0]} x {main[1]}')
+            return t
+        nxt = following
+    return None
+
+
+def _decode_mask(buf, bo, t, inflater=None, lzw=None) -> np.ndarray:
+    """ The packed bits of a 1-bit mask directory, (height, ceil(width / 8)) uint8 as stored: the directory is decoded as the BYTE
+    image it is -- a block row of ``bw`` pixels is ``bw / 8`` bytes (tile widths are multiples of 16), a strip row ceil(width / 8) --
+    so the block decoders and the hooks of ``read_tiff`` take it as they are. """
+    predictor, order = t.get(T_PREDICTOR, (1,))[0], t.get(T_FILL_ORDER, (1,))[0]
+    if predictor != 1:
+        raise IoError(f'unsupported TIFF predictor {predictor} for a 1-bit mask (none is)')
+    if order != 1:
+        raise IoError(f'unsupported FillOrder {order} for a 1-bit mask (1, most significant bit first, is)')
+    w = t[T_WIDTH][0]
+    as_bytes = dict(t)
+    as_bytes[T_WIDTH], as_bytes[T_BITS], as_bytes[T_SPP], as_bytes[T_FORMAT] = (-(-w // 8),), (8,), (1,), (1,)
+    as_bytes.pop(T_EXTRA, None)
+    if T_TILE_OFFSETS in t:
+        if t[T_TILE_W][0] % 8:
+            raise IoError(f'unsupported tile width {t[T_TILE_W][0]} for a 1-bit mask (a multiple of 8 is)')
+        as_bytes[T_TILE_W] = (t[T_TILE_W][0] // 8,)
+    return _decode_image(buf, bo, as_bytes, inflater, lzw)[0]
+
+
+def _mask_band(t, dtype, nodata, has_mask: bool, alpha: Tuple[int, ...]) -> Optional[int]:
+    """ The alpha band that masks the image: no internal mask, no nodata tag, exactly 2 or 4 bands, the last one alpha, uint8 or
+    uint16 samples (GDAL's GetMaskBand order as its documentation gives it) """
+    spp = t.get(T_SPP, (1,))[0]
+    if has_mask or nodata is not None or spp not in (2, 4) or (spp - 1) not in alpha or str(dtype) not in ('uint8', 'uint16'):
+        return None
+    return spp - 1
+
+
 def read_tiff_header(path) -> TiffHeader:
     """ Shape, geo-referencing, nodata, ``<GDALMetadata>`` items and band descriptions of the first image of a GeoTIFF.  Only
     the directory and the values it points to are read (the file is mapped, not loaded): validating a parameter file does not
@@ -195,16 +262,17 @@ def read_tiff_header(path) -> TiffHeader:
         except ValueError:   # an empty file cannot be mapped
             raise IoError('not a TIFF file')
         with buf:
-            bo, t, _ = _read_ifd(buf)
-    if T_WIDTH not in t or T_HEIGHT not in t:
-        raise IoError('not a TIFF file')
+            bo, t, nxt = _read_ifd(buf)
+            if T_WIDTH not in t or T_HEIGHT not in t:
+                raise IoError('not a TIFF file')
+            has_mask = _mask_directory(buf, t, nxt) is not None
     w, h = t[T_WIDTH][0], t[T_HEIGHT][0]
     spp = t.get(T_SPP, (1,))[0]
     bits, fmt = t.get(T_BITS, (1,)), t.get(T_FORMAT, (1,) * spp)
     uniform = len(set(bits)) == 1 and len(set(fmt)) == 1 and (fmt[0], bits[0]) in _SAMPLE_DTYPES
     dtype = np.dtype(_SAMPLE_DTYPES[(fmt[0], bits[0])]).name if uniform else ''
     tf, crs = _geo(t, h)
-    return TiffHeader(spp, h, w, dtype, tf, crs, _nodata_tag(t), _metadata(t), _descriptions(t, spp))
+    return TiffHeader(spp, h, w, dtype, tf, crs, _nodata_tag(t), _metadata(t), _descriptions(t, spp), _alpha_bands(t), has_mask)
 
 
 def read_tiff(path, inflater=None, lzw=None) -> TiffRaster:
@@ -221,10 +289,14 @@ def read_tiff(path, inflater=None, lzw=None) -> TiffRaster:
     patterns; for a hook without the attribute the image is decoded here as with None. """
     with open(path, 'rb') as f:
         buf = f.read()
-    bo, t, _ = _read_ifd(buf)
+    bo, t, nxt = _read_ifd(buf)
     out = _decode_image(buf, bo, t, inflater, lzw)
     tf, crs = _geo(t, out.shape[1])
-    return TiffRaster(out, tf, crs, _nodata_tag(t), _metadata(t), _descriptions(t, out.shape[0]))
+    mt = _mask_directory(buf, t, nxt)
+    mask = None if mt is None else _decode_mask(buf, bo, mt, inflater, lzw)
+    nodata, alpha = _nodata_tag(t), _alpha_bands(t)
+    return TiffRaster(out, tf, crs, nodata, _metadata(t), _descriptions(t, out.shape[0]), mask, alpha,
+                      _mask_band(t, out.dtype, nodata, mask is not None, alpha))
 
 
 def read_tiff_overviews(path, inflater=None, lzw=None) -> List[np.ndarray]:
@@ -238,7 +310,7 @@ def read_tiff_overviews(path, inflater=None, lzw=None) -> List[np.ndarray]:
     while nxt and nxt not in seen:
         seen.add(nxt)
         bo, t, following = _read_ifd(buf, nxt)
-        if t.get(T_SUBFILE, (0,))[0] & 1:
+        if t.get(T_SUBFILE, (0,))[0] & 1 and not _is_mask(t):   # (a mask of an overview is no overview)
             out.append(_decode_image(buf, bo, t, inflater, lzw))
         nxt = following
     return out

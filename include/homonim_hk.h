@@ -79,7 +79,7 @@ typedef struct {
  * hk_inflate_image, hk_inflate_image_dev, with the new struct hk_inflate_layout) were added WITHOUT a new version: no existing
  * layout or prototype changed, so a version-12 consumer runs unchanged against either library; a consumer that wants them looks
  * them up by symbol (dlsym) and does without where they are absent.  hk_deflate_tiles_pred and hk_deflate_tiles_pred_dev were
- * added the same way.
+ * added the same way, and so were hk_dataset_mask and hk_dataset_mask_dev (plain scalar arguments, no struct).
  * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
 #define HK_ABI_VERSION 12
 int hk_abi_version(void);
@@ -139,6 +139,24 @@ int hk_overview_count(int32_t height, int32_t width, int32_t* n);
 int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
                  int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels, void* const out[],
                  const int64_t out_stride[], const int64_t out_band_stride[]);
+
+/* The per-dataset mask of a GeoTIFF -- an internal 1-bit mask or an alpha band -- applied to its bands, as
+ * RasterArray.from_rio_dataset reads such a file (homonim/raster_array.py:161-197): out[b][y][x] = valid(y, x) ?
+ * (float)planes[b][y][x] : NaN (bit pattern 0x7FC00000), the same validity for every band; the conversion is the plain value
+ * conversion of every other input (exact for 8/16-bit integers, round to nearest for 32-bit integers and float64; a valid float32
+ * keeps its bits).  `planes`: n_bands x height x width samples of `dtype` (hk_dtype, below) in host memory, `stride` elements
+ * between rows, band b at planes + b * height * stride; `out`: float32, out_stride elements between rows, band b at out + b *
+ * height * out_stride.  mask_kind HK_MASK_BITS: `mask` are `height` rows of packed bits, the most significant bit of a byte first,
+ * 1 = valid, mask_stride BYTES apart (>= ceil(width / 8); the pad bits of a row's last byte are not looked at); HK_MASK_ALPHA:
+ * a plane of the SAME sample type as the bands, which must be HK_DTYPE_U8 or HK_DTYPE_U16, mask_stride ELEMENTS apart (>= width),
+ * a pixel being valid where its alpha sample is not 0.  Nothing outside [row, row + width) of any plane and outside ceil(width / 8)
+ * bytes of a mask row is read or written.  The raster travels in chunks of whole rows of at most 64 MiB on the device
+ * (HK_STAGE_CHUNK_KB, read at every call, lowers the bound for tests); rows are independent, so the chunking cannot change a bit.  See hk_dataset_mask_dev.
+ * HK_ERR_ARG, naming the argument: an unknown dtype or mask_kind, HK_MASK_ALPHA with another dtype, a NULL pointer, a size below
+ * 1, stride or out_stride < width, mask_stride too small. */
+enum { HK_MASK_BITS = 0, HK_MASK_ALPHA = 1 };
+int hk_dataset_mask(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                    const void* mask, int32_t mask_kind, int64_t mask_stride, float* out, int64_t out_stride);
 
 /* DEFLATE on the device: one zlib stream per tile of a tiled, band-separate GeoTIFF (homonim/fuse.py:124-149: tiled, compress =
  * deflate, interleave = band), in place of zlib.compress on a host thread.  A tile is `tile` x `tile` samples (`tile` a multiple of
@@ -641,6 +659,15 @@ int hk_param_stats_dev(hk_ctx* ctx, const float* planes_dev, int32_t n_bands, in
 int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
                      int64_t stride, int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels,
                      void* const out_dev[], const int64_t out_stride[], const int64_t out_band_stride[], int32_t stream);
+
+/* hk_dataset_mask for device-resident planes (band b at planes_dev + b * band_stride elements, out_dev + b * out_band_stride),
+ * mask and output: one launch for all bands -- a lane reads the validity of 8 consecutive pixels once and loops the bands inside.
+ * Whole groups of 8 pixels move as 8- / 16-byte loads and 16-byte stores where a plane row starts at a multiple of min(16, 8 x
+ * sample size) bytes and the output row at a multiple of 16; any other layout gives the same bits pixel by pixel.  planes_dev and
+ * an alpha plane are aligned to their sample size, out_dev to 4.  Queued on pooled stream `stream`; asynchronous. */
+int hk_dataset_mask_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                        int64_t stride, int64_t band_stride, const void* mask_dev, int32_t mask_kind, int64_t mask_stride,
+                        float* out_dev, int64_t out_stride, int64_t out_band_stride, int32_t stream);
 
 /* hk_deflate_tiles for device-resident planes: streams, offsets and sizes stay on the device (out_dev of out_capacity >=
  * hk_deflate_bound's bytes; tile_offsets_dev: n_tiles + 1, tile_sizes_dev: n_tiles int64).  Queued on pooled stream `stream`;
