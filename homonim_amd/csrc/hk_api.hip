@@ -593,12 +593,16 @@ int stage_drain(Slot& s) {
     return HK_OK;
 }
 
+// A byte cap of a chunked path: the environment variable `name_kb`, in KiB, sets it for the tests of that path; unset, empty
+// or not positive: `dflt`
+size_t cap_from_env(const char* name_kb, size_t dflt) {
+    const char* e = getenv(name_kb);
+    return (e && atol(e) > 0) ? (size_t)atol(e) << 10 : dflt;
+}
+
 int ensure_stage(Slot& s, size_t min_chunk) {
     // HK_STAGE_CHUNK_KB: chunk size for tests of the chunked paths (default 8 MB; never below one device row)
-    static const size_t chunk_min = [] {
-        const char* e = getenv("HK_STAGE_CHUNK_KB");
-        return (e && atol(e) > 0) ? (size_t)atol(e) << 10 : STAGE_CHUNK_MIN;
-    }();
+    static const size_t chunk_min = cap_from_env("HK_STAGE_CHUNK_KB", STAGE_CHUNK_MIN);
     const size_t want = std::max(min_chunk, chunk_min);
     if (s.stage && s.stage_chunk >= want) return HK_OK;
     int rc = stage_drain(s);
@@ -629,102 +633,64 @@ int stage_take(Slot& s, int* chunk) {
 // `rows` rows of `row_bytes` from the host (rows h_pitch bytes apart) to the device (rows d_pitch bytes apart), queued on the
 // slot's stream.  The host side may be released when the call returns (pageable memory: it has been packed; page-locked
 // memory: the caller keeps it until the stream has been synchronised, as the entry points do before they return).
-int stage_h2d(Slot& s, void* d_dst, size_t d_pitch, const void* h_src, size_t h_pitch, size_t row_bytes, size_t rows) {
+// The reverse (TO_DEVICE false): the caller's array is final after stage_drain() (pageable) / after the stream has been
+// synchronised (pinned).  One body for both directions; only the side that is written differs.
+template <bool TO_DEVICE>
+int stage_copy(Slot& s, char* d, size_t d_pitch, char* h, size_t h_pitch, size_t row_bytes, size_t rows) {
+    constexpr hipMemcpyKind kind = TO_DEVICE ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
     if (rows == 0 || row_bytes == 0) return HK_OK;
     if (rows == 1) h_pitch = d_pitch = row_bytes;
     const bool flat = h_pitch == row_bytes && d_pitch == row_bytes;
-    if (host_is_pinned(h_src, (rows - 1) * h_pitch + row_bytes)) {
+    if (host_is_pinned(h, (rows - 1) * h_pitch + row_bytes)) {
         if (assert_pinned_on()) {
-            const int rc = check_rows_pinned(h_src, h_pitch, row_bytes, rows);
+            const int rc = check_rows_pinned(h, h_pitch, row_bytes, rows);
             if (rc) return rc;
         }
         g_direct_copies.fetch_add(1, std::memory_order_relaxed);
         s.direct_pending = true;
-        if (flat) HK_HIP(hipMemcpyAsync(d_dst, h_src, rows * row_bytes, hipMemcpyHostToDevice, s.stream));
-        else HK_HIP(hipMemcpy2DAsync(d_dst, d_pitch, h_src, h_pitch, row_bytes, rows, hipMemcpyHostToDevice, s.stream));
+        if (flat) HK_HIP(hipMemcpyAsync(TO_DEVICE ? d : h, TO_DEVICE ? h : d, rows * row_bytes, kind, s.stream));
+        else
+            HK_HIP(hipMemcpy2DAsync(TO_DEVICE ? d : h, TO_DEVICE ? d_pitch : h_pitch, TO_DEVICE ? h : d, TO_DEVICE ? h_pitch : d_pitch,
+                                    row_bytes, rows, kind, s.stream));
         return HK_OK;
     }
     int rc = ensure_stage(s, flat ? 0 : d_pitch);
     if (rc) return rc;
-    const char* h = static_cast<const char*>(h_src);
-    char* d = static_cast<char*>(d_dst);
-    if (flat) {  // a byte stream
+    // one chunk of the ring: `n` rows of `rb` bytes, c_pitch apart in the chunk and on the device (ONE contiguous copy), hp apart
+    // on the host -- packed here on the way to the device, unpacked by stage_settle() on the way back
+    auto chunk = [&s](char* dc, char* hc, size_t hp, size_t c_pitch, size_t rb, size_t n) -> int {
+        int i;
+        const int rc = stage_take(s, &i);
+        if (rc) return rc;
+        char* c = s.stage + (size_t)i * s.stage_chunk;
+        if (TO_DEVICE)
+            for (size_t r = 0; r < n; ++r) memcpy(c + r * c_pitch, hc + r * hp, rb);
+        HK_HIP(hipMemcpyAsync(TO_DEVICE ? dc : c, TO_DEVICE ? c : dc, (n - 1) * c_pitch + rb, kind, s.stream));
+        HK_HIP(hipEventRecord(s.stage_ev[i], s.stream));
+        s.stage_state[i] = TO_DEVICE ? 1 : 2;
+        if (!TO_DEVICE) s.stage_out[i] = {.h_dst = hc, .h_pitch = hp, .row_bytes = rb, .c_pitch = c_pitch, .rows = n};
+        return HK_OK;
+    };
+    if (flat) {  // a byte stream: every chunk is one row of up to stage_chunk bytes
         const size_t total = rows * row_bytes;
         for (size_t off = 0; off < total; off += s.stage_chunk) {
             const size_t n = std::min(s.stage_chunk, total - off);
-            int i;
-            if ((rc = stage_take(s, &i))) return rc;
-            char* c = s.stage + (size_t)i * s.stage_chunk;
-            memcpy(c, h + off, n);
-            HK_HIP(hipMemcpyAsync(d + off, c, n, hipMemcpyHostToDevice, s.stream));
-            HK_HIP(hipEventRecord(s.stage_ev[i], s.stream));
-            s.stage_state[i] = 1;
+            if ((rc = chunk(d + off, h + off, n, n, n, 1))) return rc;
         }
         return HK_OK;
     }
     // packed at the DEVICE pitch: the chunk maps onto the device rows with one contiguous copy (the padding between two
     // rows travels along; it belongs to the plane and nobody reads it)
     const size_t per = std::max<size_t>(s.stage_chunk / d_pitch, 1);
-    for (size_t r0 = 0; r0 < rows; r0 += per) {
-        const size_t n = std::min(per, rows - r0);
-        int i;
-        if ((rc = stage_take(s, &i))) return rc;
-        char* c = s.stage + (size_t)i * s.stage_chunk;
-        for (size_t r = 0; r < n; ++r) memcpy(c + r * d_pitch, h + (r0 + r) * h_pitch, row_bytes);
-        HK_HIP(hipMemcpyAsync(d + r0 * d_pitch, c, (n - 1) * d_pitch + row_bytes, hipMemcpyHostToDevice, s.stream));
-        HK_HIP(hipEventRecord(s.stage_ev[i], s.stream));
-        s.stage_state[i] = 1;
-    }
+    for (size_t r0 = 0; r0 < rows; r0 += per)
+        if ((rc = chunk(d + r0 * d_pitch, h + r0 * h_pitch, h_pitch, d_pitch, row_bytes, std::min(per, rows - r0)))) return rc;
     return HK_OK;
 }
-
-// the reverse; the caller's array is final after stage_drain() (pageable) / after the stream has been synchronised (pinned)
+int stage_h2d(Slot& s, void* d_dst, size_t d_pitch, const void* h_src, size_t h_pitch, size_t row_bytes, size_t rows) {
+    return stage_copy<true>(s, static_cast<char*>(d_dst), d_pitch, const_cast<char*>(static_cast<const char*>(h_src)), h_pitch, row_bytes, rows);
+}
 int stage_d2h(Slot& s, void* h_dst, size_t h_pitch, const void* d_src, size_t d_pitch, size_t row_bytes, size_t rows) {
-    if (rows == 0 || row_bytes == 0) return HK_OK;
-    if (rows == 1) h_pitch = d_pitch = row_bytes;
-    const bool flat = h_pitch == row_bytes && d_pitch == row_bytes;
-    if (host_is_pinned(h_dst, (rows - 1) * h_pitch + row_bytes)) {
-        if (assert_pinned_on()) {
-            const int rc = check_rows_pinned(h_dst, h_pitch, row_bytes, rows);
-            if (rc) return rc;
-        }
-        g_direct_copies.fetch_add(1, std::memory_order_relaxed);
-        s.direct_pending = true;
-        if (flat) HK_HIP(hipMemcpyAsync(h_dst, d_src, rows * row_bytes, hipMemcpyDeviceToHost, s.stream));
-        else HK_HIP(hipMemcpy2DAsync(h_dst, h_pitch, d_src, d_pitch, row_bytes, rows, hipMemcpyDeviceToHost, s.stream));
-        return HK_OK;
-    }
-    int rc = ensure_stage(s, flat ? 0 : d_pitch);
-    if (rc) return rc;
-    char* h = static_cast<char*>(h_dst);
-    const char* d = static_cast<const char*>(d_src);
-    if (flat) {
-        const size_t total = rows * row_bytes;
-        for (size_t off = 0; off < total; off += s.stage_chunk) {
-            const size_t n = std::min(s.stage_chunk, total - off);
-            int i;
-            if ((rc = stage_take(s, &i))) return rc;
-            HK_HIP(hipMemcpyAsync(s.stage + (size_t)i * s.stage_chunk, d + off, n, hipMemcpyDeviceToHost, s.stream));
-            HK_HIP(hipEventRecord(s.stage_ev[i], s.stream));
-            s.stage_state[i] = 2;
-            s.stage_out[i].h_dst = h + off, s.stage_out[i].h_pitch = n, s.stage_out[i].row_bytes = n;
-            s.stage_out[i].c_pitch = n, s.stage_out[i].rows = 1;
-        }
-        return HK_OK;
-    }
-    const size_t per = std::max<size_t>(s.stage_chunk / d_pitch, 1);
-    for (size_t r0 = 0; r0 < rows; r0 += per) {
-        const size_t n = std::min(per, rows - r0);
-        int i;
-        if ((rc = stage_take(s, &i))) return rc;
-        HK_HIP(hipMemcpyAsync(s.stage + (size_t)i * s.stage_chunk, d + r0 * d_pitch, (n - 1) * d_pitch + row_bytes,
-                              hipMemcpyDeviceToHost, s.stream));
-        HK_HIP(hipEventRecord(s.stage_ev[i], s.stream));
-        s.stage_state[i] = 2;
-        s.stage_out[i].h_dst = h + r0 * h_pitch, s.stage_out[i].h_pitch = h_pitch, s.stage_out[i].row_bytes = row_bytes;
-        s.stage_out[i].c_pitch = d_pitch, s.stage_out[i].rows = n;
-    }
-    return HK_OK;
+    return stage_copy<false>(s, const_cast<char*>(static_cast<const char*>(d_src)), d_pitch, static_cast<char*>(h_dst), h_pitch, row_bytes, rows);
 }
 
 // A host-pointer call is ending WITHOUT stage_finish (an error return somewhere behind a stage_d2h): its queued chunks still name
@@ -751,16 +717,23 @@ int stage_finish(Slot& s) {
     return HK_OK;
 }
 
+// One plane of a caller's host raster: rows `stride` elements apart
+struct HostGrid {
+    const void* data;
+    int64_t stride;
+    int32_t height, width;
+};
+
 // A host raster into the float32 device plane `dplane` (row stride `dstride` elements): float32 directly, other dtypes through
 // the raw plane `raw` (the same stride, in elements of the dtype) and the on-device conversion
-int stage_in(Slot& s, const void* host, int64_t hstride, int dt, float* dplane, void* raw, int64_t dstride, int h, int w) {
+int stage_in(Slot& s, const HostGrid& g, int dt, float* dplane, void* raw, int64_t dstride) {
     const size_t es = hk::dtype_size(dt);
     void* dst = dt ? raw : static_cast<void*>(dplane);
-    const int rc = stage_h2d(s, dst, dstride * es, host, hstride * es, (size_t)w * es, h);
+    const int rc = stage_h2d(s, dst, dstride * es, g.data, g.stride * es, (size_t)g.width * es, g.height);
     if (rc) return rc;
     if (dt)
-        HK_HIP(hk::launch_cast_in(dt, {.in = dst, .in_stride = dstride, .out = dplane, .out_stride = dstride, .height = h, .width = w},
-                                  s.stream));
+        HK_HIP(hk::launch_cast_in(dt, {.in = dst, .in_stride = dstride, .out = dplane, .out_stride = dstride, .height = g.height,
+                                       .width = g.width}, s.stream));
     return HK_OK;
 }
 
@@ -808,15 +781,16 @@ int validate_desc(const hk_fit_desc* d) {
 // (raster_array.py:357-358, rasterio.dtypes.can_cast_dtype); cast_out_kernel converts it with `(T)nodata`, which is undefined for
 // a value the type cannot hold.  Integer types: an integer of the type's range (NaN and +-inf are none); float32: anything that
 // does not overflow it (can_cast_dtype compares floats with np.allclose); float64: anything.  `dtype` is a valid hk_dtype.
+// int_sample_holds: is `v` a value of the integer sample type `dtype` (NaN and +-inf fail both comparisons)?
+bool int_sample_holds(int dtype, double v) {
+    static const double lo[7] = {0, 0, 0, -32768.0, 0, -2147483648.0, 0}, hi[7] = {0, 255.0, 65535.0, 32767.0, 4294967295.0, 2147483647.0, 0};
+    return v >= lo[dtype] && v <= hi[dtype] && v == std::floor(v);
+}
 int validate_out_nodata(int dtype, int has_nodata, double nodata) {
     if (!has_nodata || dtype == HK_DTYPE_F64) return HK_OK;
     static const char* const names[7] = {"float32", "uint8", "uint16", "int16", "uint32", "int32", "float64"};
-    static const double lo[7] = {0, 0, 0, -32768.0, 0, -2147483648.0, 0}, hi[7] = {0, 255.0, 65535.0, 32767.0, 4294967295.0, 2147483647.0, 0};
-    bool ok;
-    if (dtype == HK_DTYPE_F32)
-        ok = !std::isfinite(nodata) || std::fabs(nodata) < 0x1.ffffffp127;  // below the midpoint of FLT_MAX and 2^128
-    else
-        ok = std::isfinite(nodata) && nodata >= lo[dtype] && nodata <= hi[dtype] && nodata == std::floor(nodata);
+    // float32: below the midpoint of FLT_MAX and 2^128
+    const bool ok = dtype == HK_DTYPE_F32 ? !std::isfinite(nodata) || std::fabs(nodata) < 0x1.ffffffp127 : int_sample_holds(dtype, nodata);
     if (!ok) return fail(HK_ERR_ARG, "'nodata' value: %.17g cannot be safely cast to '%s'", nodata, names[dtype]);
     return HK_OK;
 }
@@ -1301,78 +1275,98 @@ int check_mask_kernel(int kh, int kw) {
 // What hk_refspace_fit_apply and hk_srcspace_fit_apply ask alike of a source block and a reference block on another grid.
 // (The mask_partial refusal cannot be reached today: validate_desc keeps kh <= 255 and kw <= 193, 257 * 195 counts fit.)
 template <class Space>
-int check_two_grids(const hk_ctx* ctx, const hk_fit_desc* desc, const Space* space, const void* src, int64_t src_stride,
-                    int32_t src_height, int32_t src_width, const void* ref, int64_t ref_stride, int32_t ref_height, int32_t ref_width,
+int check_two_grids(const hk_ctx* ctx, const hk_fit_desc* desc, const Space* space, const HostGrid& src, const HostGrid& ref,
                     const void* corr_out) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
     int rc = validate_desc(desc);
     if (rc) return rc;
-    if (!space || !src || !ref || !corr_out) return null_arg();
-    if (src_height < 1 || src_width < 1 || ref_height < 1 || ref_width < 1) return fail(HK_ERR_ARG, "empty raster");
-    if ((rc = check_strides(src_stride, src_width, ref_stride, ref_width))) return rc;
-    if (src_height > 65535 || ref_height > 65535) return fail(HK_ERR_UNSUPPORTED, "block taller than 65535 rows");
+    if (!space || !src.data || !ref.data || !corr_out) return null_arg();
+    if (src.height < 1 || src.width < 1 || ref.height < 1 || ref.width < 1) return fail(HK_ERR_ARG, "empty raster");
+    if ((rc = check_strides(src.stride, src.width, ref.stride, ref.width))) return rc;
+    if (src.height > 65535 || ref.height > 65535) return fail(HK_ERR_UNSUPPORTED, "block taller than 65535 rows");
     return space->mask_partial ? check_mask_kernel(desc->kh, desc->kw) : HK_OK;
-}
-
-// `n_bands` planes of sh x sw re-sampled into planes of dh x dw (strides in elements)
-hk::ResamplePlanes resample_planes(const float* src, int sh, int sw, int64_t src_stride, int64_t src_band_stride, float* dst, int dh,
-                                   int dw, int64_t dst_stride, int64_t dst_band_stride, int n_bands, int nd_mode, float nodata,
-                                   float dst_fill) {
-    return {src, dst, src_stride, src_band_stride, dst_stride, dst_band_stride, sh, sw, dh, dw, n_bands, nd_mode, nodata, dst_fill};
-}
-
-// The host form of a re-projection keeps its bands packed in the slab: the source at 0, the destination behind it
-struct PackedBands {
-    size_t sbytes, o_dst, dbytes;
-};
-PackedBands packed_bands(int n_bands, int sh, int sw, int dh, int dw) {
-    const size_t sbytes = (size_t)n_bands * sh * sw * 4, dbytes = (size_t)n_bands * dh * dw * 4;
-    return {sbytes, (sbytes + 255) / 256 * 256, dbytes};
 }
 
 // hk_reproject and hk_reproject_dev ask the same of a re-projection between two axis-aligned grids of one CRS; the band count is
 // gridDim.z of the launch.  `host_form`: hk_reproject's wording for a resampling that is not built.
-int check_reproject(const hk_ctx* ctx, const float* src, int32_t n_bands, int32_t src_height, int32_t src_width, int32_t src_nodata_mode,
-                    double kx, double ky, int32_t resampling, const float* dst, int32_t dst_height, int32_t dst_width, bool host_form) {
+int check_reproject(const hk_ctx* ctx, const hk::ResamplePlanes& p, double kx, double ky, int32_t resampling, bool host_form) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!src || !dst) return null_arg();
-    if (n_bands < 1 || src_height < 1 || src_width < 1 || dst_height < 1 || dst_width < 1)
-        return fail(HK_ERR_ARG, "empty raster");
-    if (n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", n_bands);
+    if (!p.src || !p.dst) return null_arg();
+    if (p.n_bands < 1 || p.sh < 1 || p.sw < 1 || p.dh < 1 || p.dw < 1) return fail(HK_ERR_ARG, "empty raster");
+    if (p.n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", p.n_bands);
     if (!(kx > 0.0) || !(ky > 0.0)) return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
     if (!resampling_built(resampling))
         return fail(HK_ERR_UNSUPPORTED, host_form ? "resampling %d is not a warp method (GRA_* codes 0..6 and 8..14 are built; 7 = gauss is "
                                                     "an overview-only method in GDAL / rasterio as well)"
                                                   : "resampling %d is not a warp method", resampling);
-    if (dst_height > 65535) return fail(HK_ERR_UNSUPPORTED, "destination taller than 65535 rows");
-    return check_nodata_mode(src_nodata_mode);
+    if (p.dh > 65535) return fail(HK_ERR_UNSUPPORTED, "destination taller than 65535 rows");
+    return check_nodata_mode(p.nd_mode);
+}
+// ... and the device forms, whose planes carry strides, of those
+int check_resample_strides(const hk::ResamplePlanes& p) {
+    const int rc = check_strides(p.src_stride, p.sw, p.dst_stride, p.dw);
+    return rc ? rc : check_band_strides(p.src_band_stride, p.dst_band_stride);
 }
 
+// The host form of a re-projection: `p` names the caller's packed arrays (its strides are not read).  The bands stay packed
+// in the slab, the source at 0 and the destination behind it; `launch(planes, stream)` -> status runs on the slab's planes.
+template <class Launch>
+int reproject_packed(hk_ctx* ctx, const hk::ResamplePlanes& p, Launch launch) {
+    HK_ENTER(ctx);
+    const size_t sbytes = (size_t)p.n_bands * p.sh * p.sw * 4, dbytes = (size_t)p.n_bands * p.dh * p.dw * 4;
+    const size_t o_dst = (sbytes + 255) / 256 * 256;
+    HostCall hc(ctx, o_dst + dbytes);
+    if (hc.rc) return hc.rc;
+    hk::ResamplePlanes d = p;
+    d.src = hc.at<float>(0), d.dst = hc.at<float>(o_dst);
+    d.src_stride = p.sw, d.src_band_stride = (long long)p.sh * p.sw, d.dst_stride = p.dw, d.dst_band_stride = (long long)p.dh * p.dw;
+    int rc = stage_h2d(hc.sl, hc.at(0), sbytes, p.src, sbytes, sbytes, 1);
+    if (rc || (rc = launch(d, hc.sl.stream))) return rc;
+    if ((rc = stage_d2h(hc.sl, p.dst, dbytes, d.dst, dbytes, dbytes, 1))) return rc;
+    return stage_finish(hc.sl);
+}
+
+// A host-pointer fit as its entry point received it: one source and one reference block of height x width on the same grid.
+// `corr_out` / `params_out` nullable; `window` nullable: the window of the block that is written to corr_out / params_out and
+// their row / plane strides (hk_out_window), else the whole block, packed.
+struct HostFit {
+    const void* src;
+    int64_t src_stride;
+    const void* ref;
+    int64_t ref_stride;
+    int32_t height, width;
+    const double* norm_in = nullptr;
+    float* params_out = nullptr;
+    int32_t n_param_bands = 0;
+    void* corr_out = nullptr;
+    double* norm_out = nullptr;
+    uint64_t* r2_fail_count = nullptr;
+    bool norm_only = false;  // hk_block_norm: the block statistics alone
+    const hk_out_window* window = nullptr;
+};
+
 // The whole host-pointer path: stage in (+ typed -> float32), (norm), fused kernel, (float32 -> typed) stage out.
-// `corr_out` / `params_out` nullable; `io` nullable (float32 everywhere); `ow` nullable: window of the block that is
-// written to corr_out / params_out and their row / plane strides (hk_out_window), else the whole block, packed.
-int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const void* src, int64_t src_stride,
-             const void* ref, int64_t ref_stride, int32_t height, int32_t width, const double* norm_in, float* params_out,
-             int32_t n_param_bands, void* corr_out, double* norm_out, uint64_t* r2_fail_count, bool norm_only,
-             const hk_out_window* ow = nullptr) {
+// `io` nullable (float32 everywhere).
+int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const HostFit& c) {
+    const int32_t height = c.height, width = c.width;
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
     int rc = validate_desc(desc);
     if (rc) return rc;
-    if (!src || !ref) return fail(HK_ERR_ARG, "src/ref is NULL");
+    if (!c.src || !c.ref) return fail(HK_ERR_ARG, "src/ref is NULL");
     if (height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d", height, width);
-    if ((rc = check_strides(src_stride, width, ref_stride, width))) return rc;
+    if ((rc = check_strides(c.src_stride, width, c.ref_stride, width))) return rc;
     FitIo f;
-    if ((rc = check_fit_io(desc, io, params_out, n_param_bands, &f))) return rc;
-    if (!norm_only && !params_out && !corr_out) return fail(HK_ERR_ARG, "nothing to compute: params_out and corr_out are NULL");
+    if ((rc = check_fit_io(desc, io, c.params_out, c.n_param_bands, &f))) return rc;
+    if (!c.norm_only && !c.params_out && !c.corr_out) return fail(HK_ERR_ARG, "nothing to compute: params_out and corr_out are NULL");
     // output window (defaults: the whole block, written packed); param_stride is resolved to the row stride of params_out
-    hk_out_window win = ow ? *ow : whole_block(height, width);
-    if (ow) {
+    hk_out_window win = c.window ? *c.window : whole_block(height, width);
+    if (c.window) {
         if (win.param_stride <= 0) win.param_stride = win.stride;
         if (win.row0 < 0 || win.col0 < 0 || win.rows < 1 || win.cols < 1 || win.row0 + win.rows > height || win.col0 + win.cols > width)
             return fail(HK_ERR_ARG, "output window outside the block");
-        if ((corr_out && win.stride < win.cols) || (params_out && win.param_stride < win.cols))
+        if ((c.corr_out && win.stride < win.cols) || (c.params_out && win.param_stride < win.cols))
             return fail(HK_ERR_ARG, "output row stride smaller than the window");
-        if (params_out && n_param_bands > 1 && win.band_stride < (int64_t)(win.rows - 1) * win.param_stride + win.cols)
+        if (c.params_out && c.n_param_bands > 1 && win.band_stride < (int64_t)(win.rows - 1) * win.param_stride + win.cols)
             return fail(HK_ERR_ARG, "output band stride smaller than a plane of the window");
     }
     HK_ENTER(ctx);
@@ -1380,13 +1374,13 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
     const int64_t stride = row_align(width);
     const size_t plane = (size_t)stride * height * sizeof(float);
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
-    const bool want_norm = blk || norm_only;
-    const bool want_par = !norm_only && params_out, want_corr = !norm_only && corr_out;
+    const bool want_norm = blk || c.norm_only;
+    const bool want_par = !c.norm_only && c.params_out, want_corr = !c.norm_only && c.corr_out;
 
     SlabLayout L;
     const size_t o_src = L.take(plane), o_ref = L.take(plane);
     const size_t o_gain = want_par ? L.take(plane) : 0, o_off = want_par ? L.take(plane) : 0;
-    const size_t o_r2 = (want_par && n_param_bands == 3) ? L.take(plane) : 0;
+    const size_t o_r2 = (want_par && c.n_param_bands == 3) ? L.take(plane) : 0;
     const size_t o_corr = want_corr ? L.take(plane) : 0;
     const size_t o_raw_o = (want_corr && f.out_cast) ? L.take((size_t)stride * height * hk::dtype_size(f.odt)) : 0;
     const size_t o_raw_s = f.sdt ? L.take((size_t)stride * height * hk::dtype_size(f.sdt)) : 0;
@@ -1399,26 +1393,26 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
     Slot& sl = hc.sl;
     float *d_src = hc.at<float>(o_src), *d_ref = hc.at<float>(o_ref);
     float *d_gain = want_par ? hc.at<float>(o_gain) : nullptr, *d_off = want_par ? hc.at<float>(o_off) : nullptr;
-    float* d_r2 = (want_par && n_param_bands == 3) ? hc.at<float>(o_r2) : nullptr;
+    float* d_r2 = (want_par && c.n_param_bands == 3) ? hc.at<float>(o_r2) : nullptr;
     float* d_corr = want_corr ? hc.at<float>(o_corr) : nullptr;
     double* d_norm = hc.at<double>(o_aux);  // 2 doubles
     unsigned long long* d_fail = hc.at<unsigned long long>(o_aux + 64);
     void* d_ws = hc.at(o_ws);
 
-    if ((rc = stage_in(sl, src, src_stride, f.sdt, d_src, hc.at(o_raw_s), stride, height, width))) return rc;
-    if ((rc = stage_in(sl, ref, ref_stride, f.rdt, d_ref, hc.at(o_raw_r), stride, height, width))) return rc;
-    if (norm_only) {
+    if ((rc = stage_in(sl, {c.src, c.src_stride, height, width}, f.sdt, d_src, hc.at(o_raw_s), stride))) return rc;
+    if ((rc = stage_in(sl, {c.ref, c.ref_stride, height, width}, f.rdt, d_ref, hc.at(o_raw_r), stride))) return rc;
+    if (c.norm_only) {
         HK_HIP(hk::launch_block_norm(norm_args(desc, d_src, d_ref, height, width, stride), d_ws, d_norm, sl.stream));
         HK_HIP(hipMemcpyAsync(sl.pin<double>(Slot::PIN_NORM), d_norm, 2 * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
         if ((rc = stage_finish(sl))) return rc;
-        if (norm_out) memcpy(norm_out, sl.pin<double>(Slot::PIN_NORM), 2 * sizeof(double));
+        if (c.norm_out) memcpy(c.norm_out, sl.pin<double>(Slot::PIN_NORM), 2 * sizeof(double));
         return HK_OK;
     }
 
     // stage out: the window of the block the caller wants, straight into its (strided) arrays; the parameter planes lie one
     // plane apart in the slab
-    const FitResults res = {.params_out = params_out, .n_param_bands = n_param_bands, .d_par = d_gain, .d_par_stride = stride,
-                            .d_par_band = (int64_t)(o_off - o_gain) / 4, .pw = win, .corr_out = corr_out, .d_corr = d_corr,
+    const FitResults res = {.params_out = c.params_out, .n_param_bands = c.n_param_bands, .d_par = d_gain, .d_par_stride = stride,
+                            .d_par_band = (int64_t)(o_off - o_gain) / 4, .pw = win, .corr_out = c.corr_out, .d_corr = d_corr,
                             .d_raw = hc.at(o_raw_o), .d_stride = stride, .height = height, .width = width, .cw = win};
 
     // The fit, its outputs and its r2-mask counter are queued back to back and the stream is synchronised ONCE; only
@@ -1426,13 +1420,13 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
     FitPending pending;
     hk_dev_job job = {.src = d_src, .ref = d_ref, .gain = d_gain, .offset = d_off, .r2 = d_r2, .corr = d_corr, .norm = d_norm,
                       .fail_count = reinterpret_cast<uint64_t*>(d_fail), .n_bands = 1, .height = height, .width = width, .stride = stride};
-    if (ow && !f.out_cast) {  // the kernel's store window: the rows exactly, the columns from the window's first quad to the last column
+    if (c.window && !f.out_cast) {  // the kernel's store window: the rows exactly, the columns from the window's first quad to the last column
         job.out_row0 = win.row0, job.out_rows = win.rows;
         job.out_col0 = win.col0 / hk::PX * hk::PX, job.out_cols = width - job.out_col0;
     }
-    rc = fit_on_device(ctx, sl, desc, job, d_ws, norm_in, &pending);
+    rc = fit_on_device(ctx, sl, desc, job, d_ws, c.norm_in, &pending);
     if (rc) return rc;
-    if (norm_out && blk)
+    if (c.norm_out && blk)
         HK_HIP(hipMemcpyAsync(sl.pin<double>(Slot::PIN_NORM), d_norm, 2 * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
     if ((rc = stage_fit_results(sl, f, res, /*d_fail=*/nullptr))) return rc;
     // hk_debug_fail_after_d2h(1) (homonim_hk_devtools.h): the call fails HERE, its result copies queued and not yet unpacked --
@@ -1442,7 +1436,7 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
     *sl.fail_host = 0;
     if (pending.active) HK_HIP(hipMemcpyAsync(sl.fail_host, d_fail, sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
     if ((rc = stage_finish(sl))) return rc;
-    if (norm_out && blk) memcpy(norm_out, sl.pin<double>(Slot::PIN_NORM), 2 * sizeof(double));
+    if (c.norm_out && blk) memcpy(c.norm_out, sl.pin<double>(Slot::PIN_NORM), 2 * sizeof(double));
     unsigned long long n_fail = *sl.fail_host;
     if (pending.active) {
         bool requeued = false;
@@ -1454,7 +1448,7 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const v
             n_fail = *sl.fail_host;  // (the in-painting passes do not count)
         }
     }
-    if (r2_fail_count) *r2_fail_count = n_fail;
+    if (c.r2_fail_count) *c.r2_fail_count = n_fail;
     return HK_OK;
 }
 
@@ -1558,39 +1552,43 @@ int hk_ctx_sync(hk_ctx* ctx) {
 int hk_block_norm(hk_ctx* ctx, const hk_fit_desc* desc, const float* src, int64_t src_stride, const float* ref,
                   int64_t ref_stride, int32_t height, int32_t width, double norm_out[2]) {
     if (!norm_out) return fail(HK_ERR_ARG, "norm_out is NULL");
-    return run_host(ctx, desc, nullptr, src, src_stride, ref, ref_stride, height, width, nullptr, nullptr, 0, nullptr,
-                    norm_out, nullptr, true);
+    return run_host(ctx, desc, nullptr, {.src = src, .src_stride = src_stride, .ref = ref, .ref_stride = ref_stride, .height = height,
+                                         .width = width, .norm_out = norm_out, .norm_only = true});
 }
 
 int hk_fit(hk_ctx* ctx, const hk_fit_desc* desc, const float* src, int64_t src_stride, const float* ref,
            int64_t ref_stride, int32_t height, int32_t width, const double* norm_in, float* params_out,
            int32_t n_param_bands, double* norm_out, uint64_t* r2_fail_count) {
     if (!params_out) return fail(HK_ERR_ARG, "params_out is NULL");
-    return run_host(ctx, desc, nullptr, src, src_stride, ref, ref_stride, height, width, norm_in, params_out,
-                    n_param_bands, nullptr, norm_out, r2_fail_count, false);
+    return run_host(ctx, desc, nullptr, {.src = src, .src_stride = src_stride, .ref = ref, .ref_stride = ref_stride, .height = height,
+                                         .width = width, .norm_in = norm_in, .params_out = params_out, .n_param_bands = n_param_bands,
+                                         .norm_out = norm_out, .r2_fail_count = r2_fail_count});
 }
 
 int hk_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const float* src, int64_t src_stride, const float* ref,
                  int64_t ref_stride, int32_t height, int32_t width, const double* norm_in, float* params_out,
                  int32_t n_param_bands, float* corr_out, double* norm_out, uint64_t* r2_fail_count) {
     if (!corr_out) return fail(HK_ERR_ARG, "corr_out is NULL");
-    return run_host(ctx, desc, nullptr, src, src_stride, ref, ref_stride, height, width, norm_in, params_out,
-                    n_param_bands, corr_out, norm_out, r2_fail_count, false);
+    return run_host(ctx, desc, nullptr, {.src = src, .src_stride = src_stride, .ref = ref, .ref_stride = ref_stride, .height = height,
+                                         .width = width, .norm_in = norm_in, .params_out = params_out, .n_param_bands = n_param_bands,
+                                         .corr_out = corr_out, .norm_out = norm_out, .r2_fail_count = r2_fail_count});
 }
 
 int hk_fit_apply_io(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const void* src, int64_t src_stride,
                     const void* ref, int64_t ref_stride, int32_t height, int32_t width, const double* norm_in,
                     float* params_out, int32_t n_param_bands, void* corr_out, double* norm_out, uint64_t* r2_fail_count) {
-    return run_host(ctx, desc, io, src, src_stride, ref, ref_stride, height, width, norm_in, params_out, n_param_bands,
-                    corr_out, norm_out, r2_fail_count, false);
+    return run_host(ctx, desc, io, {.src = src, .src_stride = src_stride, .ref = ref, .ref_stride = ref_stride, .height = height,
+                                    .width = width, .norm_in = norm_in, .params_out = params_out, .n_param_bands = n_param_bands,
+                                    .corr_out = corr_out, .norm_out = norm_out, .r2_fail_count = r2_fail_count});
 }
 
 int hk_fit_apply_block(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const void* src, int64_t src_stride,
                        const void* ref, int64_t ref_stride, int32_t height, int32_t width, const double* norm_in,
                        float* params_out, int32_t n_param_bands, void* corr_out, const hk_out_window* window,
                        double* norm_out, uint64_t* r2_fail_count) {
-    return run_host(ctx, desc, io, src, src_stride, ref, ref_stride, height, width, norm_in, params_out, n_param_bands,
-                    corr_out, norm_out, r2_fail_count, false, window);
+    return run_host(ctx, desc, io, {.src = src, .src_stride = src_stride, .ref = ref, .ref_stride = ref_stride, .height = height,
+                                    .width = width, .norm_in = norm_in, .params_out = params_out, .n_param_bands = n_param_bands,
+                                    .corr_out = corr_out, .norm_out = norm_out, .r2_fail_count = r2_fail_count, .window = window});
 }
 
 int hk_apply(hk_ctx* ctx, const float* src, int64_t src_stride, const float* params, int32_t height, int32_t width,
@@ -1621,7 +1619,8 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
                           const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
                           int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
                           int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count) {
-    int rc = check_two_grids(ctx, desc, space, src, src_stride, src_height, src_width, ref, ref_stride, ref_height, ref_width, corr_out);
+    const HostGrid sg = {src, src_stride, src_height, src_width}, rg = {ref, ref_stride, ref_height, ref_width};
+    int rc = check_two_grids(ctx, desc, space, sg, rg, corr_out);
     if (rc) return rc;
     for (int m : {space->down_resampling, space->up_resampling})
         if (!resampling_built(m)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not built", m);
@@ -1631,27 +1630,27 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     if ((rc = check_fit_io(desc, io, params_out, n_param_bands, &f))) return rc;
     HK_ENTER(ctx);
 
-    const int64_t ss = row_align(src_width), rs = row_align(ref_width);  // row strides of the source and the reference grid
-    const size_t splane = (size_t)ss * src_height * 4, rplane = (size_t)rs * ref_height * 4;
+    const int64_t ss = row_align(sg.width), rs = row_align(rg.width);  // row strides of the source and the reference grid
+    const size_t splane = (size_t)ss * sg.height * 4, rplane = (size_t)rs * rg.height * 4;
     SlabLayout L;
     const size_t o_src = L.take(splane), o_ref = L.take(rplane), o_ds = L.take(rplane);
     const size_t o_gain = L.take(rplane), o_off = L.take(rplane), o_r2 = f.r2 ? L.take(rplane) : 0;
     // bilinear / cubic_spline parameters are up-sampled inside the apply kernel (no full-resolution parameter planes)
-    const bool fused_up = (space->up_resampling == 1 || space->up_resampling == 3) && ref_width >= 4 &&
+    const bool fused_up = (space->up_resampling == 1 || space->up_resampling == 3) && rg.width >= 4 &&
                           space->up[0] <= 1.0 + 1e-9 && space->up[2] <= 1.0 + 1e-9 &&
-                          (long long)ref_height * rs < 0x7fffffffLL;
+                          (long long)rg.height * rs < 0x7fffffffLL;
     const size_t o_gus = fused_up ? 0 : L.take(splane), o_ous = fused_up ? 0 : L.take(splane), o_corr = L.take(splane);
-    const size_t o_rowtab = fused_up ? L.take(hk::upsample_apply_workspace_bytes(src_height)) : 0;
+    const size_t o_rowtab = fused_up ? L.take(hk::upsample_apply_workspace_bytes(sg.height)) : 0;
     const size_t o_vs = space->mask_partial ? L.take(splane) : 0, o_cov = space->mask_partial ? L.take(rplane) : 0;
-    const size_t o_mk = space->mask_partial ? L.take((size_t)rs * ref_height) : 0;
+    const size_t o_mk = space->mask_partial ? L.take((size_t)rs * rg.height) : 0;
     const size_t o_mkf = space->mask_partial ? L.take(rplane) : 0, o_keep = space->mask_partial ? L.take(splane) : 0;
-    const size_t o_cnt = space->mask_partial ? L.take((size_t)rs * ref_height * 2) : 0;
-    const size_t o_raw_s = f.sdt ? L.take((size_t)ss * src_height * hk::dtype_size(f.sdt)) : 0;
-    const size_t o_raw_r = f.rdt ? L.take((size_t)rs * ref_height * hk::dtype_size(f.rdt)) : 0;
-    const size_t o_raw_o = f.out_cast ? L.take((size_t)ss * src_height * hk::dtype_size(f.odt)) : 0;
+    const size_t o_cnt = space->mask_partial ? L.take((size_t)rs * rg.height * 2) : 0;
+    const size_t o_raw_s = f.sdt ? L.take((size_t)ss * sg.height * hk::dtype_size(f.sdt)) : 0;
+    const size_t o_raw_r = f.rdt ? L.take((size_t)rs * rg.height * hk::dtype_size(f.rdt)) : 0;
+    const size_t o_raw_o = f.out_cast ? L.take((size_t)ss * sg.height * hk::dtype_size(f.odt)) : 0;
     const size_t o_aux = L.take(256);
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
-    const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, ref_height, ref_width)) : 0;
+    const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, rg.height, rg.width)) : 0;
 
     HostCall hc(ctx, L.total);
     if (hc.rc) return hc.rc;
@@ -1664,13 +1663,15 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     unsigned long long* d_fail = hc.at<unsigned long long>(o_aux + 64);
     const float nan = std::nanf("");
 
-    if ((rc = stage_in(sl, src, src_stride, f.sdt, d_src, hc.at(o_raw_s), ss, src_height, src_width))) return rc;
-    if ((rc = stage_in(sl, ref, ref_stride, f.rdt, d_ref, hc.at(o_raw_r), rs, ref_height, ref_width))) return rc;
+    if ((rc = stage_in(sl, sg, f.sdt, d_src, hc.at(o_raw_s), ss))) return rc;
+    if ((rc = stage_in(sl, rg, f.rdt, d_ref, hc.at(o_raw_r), rs))) return rc;
 
     // one plane from the source grid down to the reference grid, or from there up to the source grid
     auto resample = [&](int mode, bool down, const float* from, int nd_mode, float nodata, float* to, float fill) {
-        const hk::ResamplePlanes p = down ? resample_planes(from, src_height, src_width, ss, 0, to, ref_height, ref_width, rs, 0, 1, nd_mode, nodata, fill)
-                                          : resample_planes(from, ref_height, ref_width, rs, 0, to, src_height, src_width, ss, 0, 1, nd_mode, nodata, fill);
+        const HostGrid &a = down ? sg : rg, &b = down ? rg : sg;  // from a's shape to b's, on the slab's strides
+        const hk::ResamplePlanes p = {.src = from, .dst = to, .src_stride = down ? ss : rs, .src_band_stride = 0, .dst_stride = down ? rs : ss,
+                                      .dst_band_stride = 0, .sh = a.height, .sw = a.width, .dh = b.height, .dw = b.width, .n_bands = 1,
+                                      .nd_mode = nd_mode, .nodata = nodata, .dst_fill = fill};
         const double* m = down ? space->down : space->up;
         return hk::launch_resample(mode, p, m[0], m[1], m[2], m[3], sl.stream);
     };
@@ -1733,7 +1734,8 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
                           const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
                           int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
                           int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count) {
-    int rc = check_two_grids(ctx, desc, space, src, src_stride, src_height, src_width, ref, ref_stride, ref_height, ref_width, corr_out);
+    const HostGrid sg = {src, src_stride, src_height, src_width}, rg = {ref, ref_stride, ref_height, ref_width};
+    int rc = check_two_grids(ctx, desc, space, sg, rg, corr_out);
     if (rc) return rc;
     if (!resampling_built(space->resampling)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not built", space->resampling);
     if (!(space->map[0] > 0 && space->map[2] > 0)) return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
@@ -1742,8 +1744,8 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     const bool r2 = f.r2, partial = space->mask_partial != 0;
     HK_ENTER(ctx);
 
-    const int64_t ss = row_align(src_width), rs = row_align(ref_width);  // row strides of the source and the reference grid
-    const size_t splane = (size_t)ss * src_height * 4, rplane = (size_t)rs * ref_height * 4;
+    const int64_t ss = row_align(sg.width), rs = row_align(rg.width);  // row strides of the source and the reference grid
+    const size_t splane = (size_t)ss * sg.height * 4, rplane = (size_t)rs * rg.height * 4;
     const int n_par = r2 ? 3 : 2;
     // `average` reads the reference as it was uploaded (footprint_typed_kernel): no float32 copy, no valid plane
     const bool typed_foot = space->resampling == hk::RS_AVERAGE;
@@ -1752,17 +1754,17 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     const size_t o_par = L.take(splane);  // gain, offset, (r2): planes of one size, one band stride apart
     for (int b = 1; b < n_par; ++b) L.take(splane);
     const size_t o_corr = L.take(splane);
-    const size_t o_cov = partial ? L.take(splane) : 0, o_cnt = partial ? L.take((size_t)ss * src_height * 2) : 0;
+    const size_t o_cov = partial ? L.take(splane) : 0, o_cnt = partial ? L.take((size_t)ss * sg.height * 2) : 0;
     const size_t o_mpar = (partial && params_out) ? L.take(splane) : 0;  // the masked parameters
     if (partial && params_out)
         for (int b = 1; b < n_par; ++b) L.take(splane);
     const size_t o_ref = (!typed_foot || !f.rdt) ? L.take(rplane) : 0, o_vr = (partial && !typed_foot) ? L.take(rplane) : 0;
-    const size_t o_raw_s = f.sdt ? L.take((size_t)ss * src_height * hk::dtype_size(f.sdt)) : 0;
-    const size_t o_raw_r = f.rdt ? L.take((size_t)rs * ref_height * hk::dtype_size(f.rdt)) : 0;
-    const size_t o_raw_o = f.out_cast ? L.take((size_t)ss * src_height * hk::dtype_size(f.odt)) : 0;
+    const size_t o_raw_s = f.sdt ? L.take((size_t)ss * sg.height * hk::dtype_size(f.sdt)) : 0;
+    const size_t o_raw_r = f.rdt ? L.take((size_t)rs * rg.height * hk::dtype_size(f.rdt)) : 0;
+    const size_t o_raw_o = f.out_cast ? L.take((size_t)ss * sg.height * hk::dtype_size(f.odt)) : 0;
     const size_t o_aux = L.take(256);
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
-    const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, src_height, src_width)) : 0;
+    const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, sg.height, sg.width)) : 0;
 
     HostCall hc(ctx, L.total);
     if (hc.rc) return hc.rc;
@@ -1776,7 +1778,7 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     const float nan = std::nanf("");
     const double* m = space->map;
 
-    if ((rc = stage_in(sl, src, src_stride, f.sdt, d_src, hc.at(o_raw_s), ss, src_height, src_width))) return rc;
+    if ((rc = stage_in(sl, sg, f.sdt, d_src, hc.at(o_raw_s), ss))) return rc;
 
     // SrcSpaceModel.fit (:520): reference -> source grid (nodata nan), and for mask_partial the coverage of its valid mask
     // (_full_coverage_mask, :375-399: mask_ra re-projected with `average`, no nodata)
@@ -1791,9 +1793,10 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
                                           sl.stream));
     } else {
         float* d_ref = F(o_ref);
-        if ((rc = stage_in(sl, ref, ref_stride, f.rdt, d_ref, hc.at(o_raw_r), rs, ref_height, ref_width))) return rc;
-        hk::ResamplePlanes p = resample_planes(d_ref, ref_height, ref_width, rs, 0, d_rus, src_height, src_width, ss, 0, 1,
-                                               desc->ref_nodata_mode, desc->ref_nodata, nan);
+        if ((rc = stage_in(sl, rg, f.rdt, d_ref, hc.at(o_raw_r), rs))) return rc;
+        hk::ResamplePlanes p = {.src = d_ref, .dst = d_rus, .src_stride = rs, .src_band_stride = 0, .dst_stride = ss, .dst_band_stride = 0,
+                                .sh = rg.height, .sw = rg.width, .dh = sg.height, .dw = sg.width, .n_bands = 1,
+                                .nd_mode = desc->ref_nodata_mode, .nodata = desc->ref_nodata, .dst_fill = nan};
         HK_HIP(hk::launch_resample(space->resampling, p, m[0], m[1], m[2], m[3], sl.stream));
         if (partial) {
             HK_HIP(hk::launch_valid_plane({.in = d_ref, .in_stride = rs, .nd_mode = desc->ref_nodata_mode, .nodata = desc->ref_nodata,
@@ -1835,49 +1838,41 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
 int hk_reproject(hk_ctx* ctx, const float* src, int32_t n_bands, int32_t src_height, int32_t src_width,
                  int32_t src_nodata_mode, float src_nodata, double kx, double ox, double ky, double oy, int32_t resampling,
                  float* dst, int32_t dst_height, int32_t dst_width, float dst_fill) {
-    int rc = check_reproject(ctx, src, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst, dst_height, dst_width,
-                             /*host_form=*/true);
+    const hk::ResamplePlanes p = {.src = src, .dst = dst, .sh = src_height, .sw = src_width, .dh = dst_height, .dw = dst_width,
+                                  .n_bands = n_bands, .nd_mode = src_nodata_mode, .nodata = src_nodata, .dst_fill = dst_fill};
+    const int rc = check_reproject(ctx, p, kx, ky, resampling, /*host_form=*/true);
     if (rc) return rc;
-    HK_ENTER(ctx);
-    const PackedBands pk = packed_bands(n_bands, src_height, src_width, dst_height, dst_width);
-    HostCall hc(ctx, pk.o_dst + pk.dbytes);
-    if (hc.rc) return hc.rc;
-    float *d_src = hc.at<float>(0), *d_dst = hc.at<float>(pk.o_dst);
-    if ((rc = stage_h2d(hc.sl, d_src, pk.sbytes, src, pk.sbytes, pk.sbytes, 1))) return rc;
-    const hk::ResamplePlanes p = resample_planes(d_src, src_height, src_width, src_width, (int64_t)src_height * src_width, d_dst, dst_height, dst_width,
-                                                 dst_width, (int64_t)dst_height * dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill);
-    HK_HIP(hk::launch_resample(resampling, p, kx, ox, ky, oy, hc.sl.stream));
-    if ((rc = stage_d2h(hc.sl, dst, pk.dbytes, d_dst, pk.dbytes, pk.dbytes, 1))) return rc;
-    return stage_finish(hc.sl);
+    return reproject_packed(ctx, p, [&](const hk::ResamplePlanes& slab, hipStream_t stream) {
+        HK_HIP(hk::launch_resample(resampling, slab, kx, ox, ky, oy, stream));
+        return (int)HK_OK;
+    });
 }
 
 int hk_reproject_dev(hk_ctx* ctx, const float* src_dev, int32_t n_bands, int32_t src_height, int32_t src_width,
                      int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode, float src_nodata, double kx, double ox,
                      double ky, double oy, int32_t resampling, float* dst_dev, int32_t dst_height, int32_t dst_width,
                      int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream) {
-    int rc = check_reproject(ctx, src_dev, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst_dev, dst_height,
-                             dst_width, /*host_form=*/false);
+    const hk::ResamplePlanes p = {.src = src_dev, .dst = dst_dev, .src_stride = src_stride, .src_band_stride = src_band_stride,
+                                  .dst_stride = dst_stride, .dst_band_stride = dst_band_stride, .sh = src_height, .sw = src_width,
+                                  .dh = dst_height, .dw = dst_width, .n_bands = n_bands, .nd_mode = src_nodata_mode, .nodata = src_nodata,
+                                  .dst_fill = dst_fill};
+    int rc = check_reproject(ctx, p, kx, ky, resampling, /*host_form=*/false);
     if (rc) return rc;
-    if ((rc = check_strides(src_stride, src_width, dst_stride, dst_width)) || (rc = check_band_strides(src_band_stride, dst_band_stride)) ||
-        (rc = check_stream(ctx, stream)))
-        return rc;
+    if ((rc = check_resample_strides(p)) || (rc = check_stream(ctx, stream))) return rc;
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
-    const hk::ResamplePlanes p = resample_planes(src_dev, src_height, src_width, src_stride, src_band_stride, dst_dev, dst_height, dst_width,
-                                                 dst_stride, dst_band_stride, n_bands, src_nodata_mode, src_nodata, dst_fill);
     HK_HIP(hk::launch_resample(resampling, p, kx, ox, ky, oy, ctx->slots[stream].stream));
     return HK_OK;
 }
 
 // Re-sampling between grids of two CRSs and between rotated / sheared grids (hk_warp.hip): see include/homonim_hk.h.  The entry
 // points of hk_warp_desc and of hk_affine_warp_desc share their bodies; hk::launch_warp_* is overloaded on the descriptor.
-static int check_warp_lattice(hk_ctx* ctx, const void* warp, int32_t height, int32_t width, const void* x, const void* y,
-                              int64_t stride) {
+static int check_warp_lattice(hk_ctx* ctx, const void* warp, const hk::WarpLattice& l) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!warp || !x || !y) return null_arg();
-    if (height < 1 || width < 1) return fail(HK_ERR_ARG, "empty lattice %d x %d", height, width);
-    if (height > 65535) return fail(HK_ERR_UNSUPPORTED, "lattice taller than 65535 rows");
-    return check_strides(stride, width);
+    if (!warp || !l.x || !l.y) return null_arg();
+    if (l.h < 1 || l.w < 1) return fail(HK_ERR_ARG, "empty lattice %d x %d", l.h, l.w);
+    if (l.h > 65535) return fail(HK_ERR_UNSUPPORTED, "lattice taller than 65535 rows");
+    return check_strides(l.stride, l.w);
 }
 
 // hipErrorInvalidValue of the warp launchers carries a reason: an unusable descriptor (HK_ERR_ARG), or CRSs the warp is not
@@ -1891,64 +1886,61 @@ static int warp_launch_status(hipError_t e, const char* why) {
 }
 
 extern "C++" template <typename Desc>
-static int warp_coords_dev(hk_ctx* ctx, const Desc* warp, double off_row, double off_col, int32_t height, int32_t width,
-                           double* x_dev, double* y_dev, int64_t stride, int32_t stream) {
-    int rc = check_warp_lattice(ctx, warp, height, width, x_dev, y_dev, stride);
+static int warp_coords_dev(hk_ctx* ctx, const Desc* warp, const hk::WarpLattice& l, int32_t stream) {
+    int rc = check_warp_lattice(ctx, warp, l);
     if (rc || (rc = check_stream(ctx, stream))) return rc;
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
     const char* why = nullptr;
-    const hk::WarpLattice l = {x_dev, y_dev, stride, height, width, off_row, off_col};
     return warp_launch_status(hk::launch_warp_coords(warp, l, ctx->slots[stream].stream, &why), why);
 }
 
+// (`out`: the caller's host planes; the lattice is computed into the slab at the device row stride and copied there)
 extern "C++" template <typename Desc>
-static int warp_coords_host(hk_ctx* ctx, const Desc* warp, double off_row, double off_col, int32_t height, int32_t width,
-                            double* x_out, double* y_out, int64_t stride) {
-    int rc = check_warp_lattice(ctx, warp, height, width, x_out, y_out, stride);
+static int warp_coords_host(hk_ctx* ctx, const Desc* warp, const hk::WarpLattice& out) {
+    int rc = check_warp_lattice(ctx, warp, out);
     if (rc) return rc;
     HK_ENTER(ctx);
-    const int64_t d_stride = row_align(width);
+    const int64_t d_stride = row_align(out.w);
     SlabLayout L;
-    const size_t plane = (size_t)d_stride * height * sizeof(double);
+    const size_t plane = (size_t)d_stride * out.h * sizeof(double);
     const size_t o_x = L.take(plane), o_y = L.take(plane);
     HostCall hc(ctx, L.total);
     if (hc.rc) return hc.rc;
     const char* why = nullptr;
-    const hk::WarpLattice l = {hc.at<double>(o_x), hc.at<double>(o_y), d_stride, height, width, off_row, off_col};
+    hk::WarpLattice l = out;
+    l.x = hc.at<double>(o_x), l.y = hc.at<double>(o_y), l.stride = d_stride;
     if ((rc = warp_launch_status(hk::launch_warp_coords(warp, l, hc.sl.stream, &why), why))) return rc;
-    if ((rc = stage_d2h(hc.sl, x_out, (size_t)stride * 8, l.x, (size_t)d_stride * 8, (size_t)width * 8, height))) return rc;
-    if ((rc = stage_d2h(hc.sl, y_out, (size_t)stride * 8, l.y, (size_t)d_stride * 8, (size_t)width * 8, height))) return rc;
+    if ((rc = stage_d2h(hc.sl, out.x, (size_t)out.stride * 8, l.x, (size_t)d_stride * 8, (size_t)out.w * 8, out.h))) return rc;
+    if ((rc = stage_d2h(hc.sl, out.y, (size_t)out.stride * 8, l.y, (size_t)d_stride * 8, (size_t)out.w * 8, out.h))) return rc;
     return stage_finish(hc.sl);
 }
 
 int hk_warp_coords_dev(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double off_col, int32_t height, int32_t width,
                        double* x_dev, double* y_dev, int64_t stride, int32_t stream) {
-    return warp_coords_dev(ctx, warp, off_row, off_col, height, width, x_dev, y_dev, stride, stream);
+    return warp_coords_dev(ctx, warp, {.x = x_dev, .y = y_dev, .stride = stride, .h = height, .w = width, .off_row = off_row, .off_col = off_col}, stream);
 }
 
 int hk_warp_coords(hk_ctx* ctx, const hk_warp_desc* warp, double off_row, double off_col, int32_t height, int32_t width,
                    double* x_out, double* y_out, int64_t stride) {
-    return warp_coords_host(ctx, warp, off_row, off_col, height, width, x_out, y_out, stride);
+    return warp_coords_host(ctx, warp, {.x = x_out, .y = y_out, .stride = stride, .h = height, .w = width, .off_row = off_row, .off_col = off_col});
 }
 
 int hk_warp_coords_affine_dev(hk_ctx* ctx, const hk_affine_warp_desc* warp, double off_row, double off_col, int32_t height,
                               int32_t width, double* x_dev, double* y_dev, int64_t stride, int32_t stream) {
-    return warp_coords_dev(ctx, warp, off_row, off_col, height, width, x_dev, y_dev, stride, stream);
+    return warp_coords_dev(ctx, warp, {.x = x_dev, .y = y_dev, .stride = stride, .h = height, .w = width, .off_row = off_row, .off_col = off_col}, stream);
 }
 
 int hk_warp_coords_affine(hk_ctx* ctx, const hk_affine_warp_desc* warp, double off_row, double off_col, int32_t height,
                           int32_t width, double* x_out, double* y_out, int64_t stride) {
-    return warp_coords_host(ctx, warp, off_row, off_col, height, width, x_out, y_out, stride);
+    return warp_coords_host(ctx, warp, {.x = x_out, .y = y_out, .stride = stride, .h = height, .w = width, .off_row = off_row, .off_col = off_col});
 }
 
-static int check_reproject_crs(hk_ctx* ctx, const void* warp, bool affine, const float* src, int32_t n_bands, int32_t src_height,
-                               int32_t src_width, int32_t src_nodata_mode, double kx, double ky, int32_t resampling,
-                               const float* dst, int32_t dst_height, int32_t dst_width) {
+static int check_reproject_crs(hk_ctx* ctx, const void* warp, bool affine, const hk::ResamplePlanes& p, double kx, double ky,
+                               int32_t resampling) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!warp || !src || !dst) return null_arg();
-    if (n_bands < 1 || src_height < 1 || src_width < 1 || dst_height < 1 || dst_width < 1)
-        return fail(HK_ERR_ARG, "empty raster");
+    if (!warp || !p.src || !p.dst) return null_arg();
+    if (p.n_bands < 1 || p.sh < 1 || p.sw < 1 || p.dh < 1 || p.dw < 1) return fail(HK_ERR_ARG, "empty raster");
     if (!(kx > 0.0) || !(ky > 0.0) || !std::isfinite(kx) || !std::isfinite(ky))
         return fail(HK_ERR_ARG, "kx, ky must be positive and finite");
     if (!resampling_built(resampling))
@@ -1958,64 +1950,49 @@ static int check_reproject_crs(hk_ctx* ctx, const void* warp, bool affine, const
                                                  "rotated / sheared grids (nearest, bilinear, cubic, cubic_spline and lanczos are)"
                                                : "resampling %d works on a destination pixel's footprint, which is not built across CRSs "
                                                  "(nearest, bilinear, cubic, cubic_spline and lanczos are)", resampling);
-    if (dst_height > 65535) return fail(HK_ERR_UNSUPPORTED, "destination taller than 65535 rows");
-    return check_nodata_mode(src_nodata_mode);
+    if (p.dh > 65535) return fail(HK_ERR_UNSUPPORTED, "destination taller than 65535 rows");
+    return check_nodata_mode(p.nd_mode);
 }
 
 extern "C++" template <typename Desc>
-static int reproject_warp_dev(hk_ctx* ctx, const Desc* warp, const float* src_dev, int32_t n_bands, int32_t src_height,
-                              int32_t src_width, int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode,
-                              float src_nodata, double kx, double ky, int32_t resampling, float* dst_dev, int32_t dst_height,
-                              int32_t dst_width, int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream) {
-    int rc = check_reproject_crs(ctx, warp, std::is_same<Desc, hk_affine_warp_desc>::value, src_dev, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst_dev,
-                                 dst_height, dst_width);
+static int reproject_warp_dev(hk_ctx* ctx, const Desc* warp, const hk::ResamplePlanes& p, double kx, double ky, int32_t resampling,
+                              int32_t stream) {
+    int rc = check_reproject_crs(ctx, warp, std::is_same<Desc, hk_affine_warp_desc>::value, p, kx, ky, resampling);
     if (rc) return rc;
-    if ((rc = check_strides(src_stride, src_width, dst_stride, dst_width)) || (rc = check_band_strides(src_band_stride, dst_band_stride)) ||
-        (rc = check_stream(ctx, stream)))
-        return rc;
+    if ((rc = check_resample_strides(p)) || (rc = check_stream(ctx, stream))) return rc;
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
     const char* why = nullptr;
-    const hk::ResamplePlanes p = resample_planes(src_dev, src_height, src_width, src_stride, src_band_stride, dst_dev, dst_height, dst_width,
-                                                 dst_stride, dst_band_stride, n_bands, src_nodata_mode, src_nodata, dst_fill);
     return warp_launch_status(hk::launch_warp_resample(resampling, warp, p, kx, ky, ctx->slots[stream].stream, &why), why);
 }
 
 extern "C++" template <typename Desc>
-static int reproject_warp_host(hk_ctx* ctx, const Desc* warp, const float* src, int32_t n_bands, int32_t src_height,
-                               int32_t src_width, int32_t src_nodata_mode, float src_nodata, double kx, double ky,
-                               int32_t resampling, float* dst, int32_t dst_height, int32_t dst_width, float dst_fill) {
-    int rc = check_reproject_crs(ctx, warp, std::is_same<Desc, hk_affine_warp_desc>::value, src, n_bands, src_height, src_width, src_nodata_mode, kx, ky, resampling, dst,
-                                 dst_height, dst_width);
+static int reproject_warp_host(hk_ctx* ctx, const Desc* warp, const hk::ResamplePlanes& p, double kx, double ky, int32_t resampling) {
+    const int rc = check_reproject_crs(ctx, warp, std::is_same<Desc, hk_affine_warp_desc>::value, p, kx, ky, resampling);
     if (rc) return rc;
-    HK_ENTER(ctx);
-    const PackedBands pk = packed_bands(n_bands, src_height, src_width, dst_height, dst_width);
-    HostCall hc(ctx, pk.o_dst + pk.dbytes);
-    if (hc.rc) return hc.rc;
-    float *d_src = hc.at<float>(0), *d_dst = hc.at<float>(pk.o_dst);
-    if ((rc = stage_h2d(hc.sl, d_src, pk.sbytes, src, pk.sbytes, pk.sbytes, 1))) return rc;
-    const char* why = nullptr;
-    const hk::ResamplePlanes p = resample_planes(d_src, src_height, src_width, src_width, (int64_t)src_height * src_width, d_dst, dst_height, dst_width,
-                                                 dst_width, (int64_t)dst_height * dst_width, n_bands, src_nodata_mode, src_nodata, dst_fill);
-    if ((rc = warp_launch_status(hk::launch_warp_resample(resampling, warp, p, kx, ky, hc.sl.stream, &why), why))) return rc;
-    if ((rc = stage_d2h(hc.sl, dst, pk.dbytes, d_dst, pk.dbytes, pk.dbytes, 1))) return rc;
-    return stage_finish(hc.sl);
+    return reproject_packed(ctx, p, [&](const hk::ResamplePlanes& slab, hipStream_t stream) {
+        const char* why = nullptr;
+        return warp_launch_status(hk::launch_warp_resample(resampling, warp, slab, kx, ky, stream, &why), why);
+    });
 }
 
 int hk_reproject_crs_dev(hk_ctx* ctx, const hk_warp_desc* warp, const float* src_dev, int32_t n_bands, int32_t src_height,
                          int32_t src_width, int64_t src_stride, int64_t src_band_stride, int32_t src_nodata_mode,
                          float src_nodata, double kx, double ky, int32_t resampling, float* dst_dev, int32_t dst_height,
                          int32_t dst_width, int64_t dst_stride, int64_t dst_band_stride, float dst_fill, int32_t stream) {
-    return reproject_warp_dev(ctx, warp, src_dev, n_bands, src_height, src_width, src_stride, src_band_stride, src_nodata_mode,
-                              src_nodata, kx, ky, resampling, dst_dev, dst_height, dst_width, dst_stride, dst_band_stride, dst_fill,
-                              stream);
+    const hk::ResamplePlanes p = {.src = src_dev, .dst = dst_dev, .src_stride = src_stride, .src_band_stride = src_band_stride,
+                                  .dst_stride = dst_stride, .dst_band_stride = dst_band_stride, .sh = src_height, .sw = src_width,
+                                  .dh = dst_height, .dw = dst_width, .n_bands = n_bands, .nd_mode = src_nodata_mode, .nodata = src_nodata,
+                                  .dst_fill = dst_fill};
+    return reproject_warp_dev(ctx, warp, p, kx, ky, resampling, stream);
 }
 
 int hk_reproject_crs(hk_ctx* ctx, const hk_warp_desc* warp, const float* src, int32_t n_bands, int32_t src_height,
                      int32_t src_width, int32_t src_nodata_mode, float src_nodata, double kx, double ky, int32_t resampling,
                      float* dst, int32_t dst_height, int32_t dst_width, float dst_fill) {
-    return reproject_warp_host(ctx, warp, src, n_bands, src_height, src_width, src_nodata_mode, src_nodata, kx, ky, resampling, dst,
-                               dst_height, dst_width, dst_fill);
+    const hk::ResamplePlanes p = {.src = src, .dst = dst, .sh = src_height, .sw = src_width, .dh = dst_height, .dw = dst_width,
+                                  .n_bands = n_bands, .nd_mode = src_nodata_mode, .nodata = src_nodata, .dst_fill = dst_fill};
+    return reproject_warp_host(ctx, warp, p, kx, ky, resampling);
 }
 
 int hk_reproject_affine_dev(hk_ctx* ctx, const hk_affine_warp_desc* warp, const float* src_dev, int32_t n_bands,
@@ -2023,16 +2000,19 @@ int hk_reproject_affine_dev(hk_ctx* ctx, const hk_affine_warp_desc* warp, const 
                             int32_t src_nodata_mode, float src_nodata, double kx, double ky, int32_t resampling, float* dst_dev,
                             int32_t dst_height, int32_t dst_width, int64_t dst_stride, int64_t dst_band_stride, float dst_fill,
                             int32_t stream) {
-    return reproject_warp_dev(ctx, warp, src_dev, n_bands, src_height, src_width, src_stride, src_band_stride, src_nodata_mode,
-                              src_nodata, kx, ky, resampling, dst_dev, dst_height, dst_width, dst_stride, dst_band_stride, dst_fill,
-                              stream);
+    const hk::ResamplePlanes p = {.src = src_dev, .dst = dst_dev, .src_stride = src_stride, .src_band_stride = src_band_stride,
+                                  .dst_stride = dst_stride, .dst_band_stride = dst_band_stride, .sh = src_height, .sw = src_width,
+                                  .dh = dst_height, .dw = dst_width, .n_bands = n_bands, .nd_mode = src_nodata_mode, .nodata = src_nodata,
+                                  .dst_fill = dst_fill};
+    return reproject_warp_dev(ctx, warp, p, kx, ky, resampling, stream);
 }
 
 int hk_reproject_affine(hk_ctx* ctx, const hk_affine_warp_desc* warp, const float* src, int32_t n_bands, int32_t src_height,
                         int32_t src_width, int32_t src_nodata_mode, float src_nodata, double kx, double ky, int32_t resampling,
                         float* dst, int32_t dst_height, int32_t dst_width, float dst_fill) {
-    return reproject_warp_host(ctx, warp, src, n_bands, src_height, src_width, src_nodata_mode, src_nodata, kx, ky, resampling, dst,
-                               dst_height, dst_width, dst_fill);
+    const hk::ResamplePlanes p = {.src = src, .dst = dst, .sh = src_height, .sw = src_width, .dh = dst_height, .dw = dst_width,
+                                  .n_bands = n_bands, .nd_mode = src_nodata_mode, .nodata = src_nodata, .dst_fill = dst_fill};
+    return reproject_warp_host(ctx, warp, p, kx, ky, resampling);
 }
 
 int hk_partial_mask(hk_ctx* ctx, const float* in, int64_t in_stride, int32_t in_nodata_mode, float in_nodata,
@@ -2381,17 +2361,6 @@ static int ensure_stream_ws(hk_ctx* ctx, Slot& sl, size_t need) {
     return grow_slot_buf(sl, sl.norm_ws, sl.norm_ws_bytes, need);
 }
 
-// n_bands pairs of planes with the same strides on both sides
-static hk::CompareArgs compare_args(const float* src, const float* ref, int32_t height, int32_t width, int64_t stride, int64_t band_stride,
-                                    int32_t n_bands, int32_t src_nodata_mode, float src_nodata, int32_t ref_nodata_mode, float ref_nodata) {
-    hk::CompareArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.src = src, ca.ref = ref, ca.height = height, ca.width = width;
-    ca.src_stride = ca.ref_stride = stride, ca.src_band_stride = ca.ref_band_stride = band_stride, ca.n_bands = n_bands;
-    ca.src_nd_mode = src_nodata_mode, ca.ref_nd_mode = ref_nodata_mode, ca.src_nodata = src_nodata, ca.ref_nodata = ref_nodata;
-    return ca;
-}
-
 int hk_compare_sums_dev(hk_ctx* ctx, const hk_dev_job* job, int32_t src_nodata_mode, float src_nodata,
                         int32_t ref_nodata_mode, float ref_nodata, double* sums_dev) {
     int rc = check_job(ctx, job);
@@ -2403,8 +2372,10 @@ int hk_compare_sums_dev(hk_ctx* ctx, const hk_dev_job* job, int32_t src_nodata_m
     Slot& sl = ctx->slots[job->stream];
     rc = ensure_stream_ws(ctx, sl, hk::compare_workspace_bytes(job->n_bands));
     if (rc) return rc;
-    const hk::CompareArgs ca = compare_args(job->src, job->ref, job->height, job->width, job->stride, job->band_stride, job->n_bands,
-                                            src_nodata_mode, src_nodata, ref_nodata_mode, ref_nodata);
+    const hk::CompareArgs ca = {.src = job->src, .ref = job->ref, .height = job->height, .width = job->width, .src_stride = job->stride,
+                                .ref_stride = job->stride, .src_band_stride = job->band_stride, .ref_band_stride = job->band_stride,
+                                .n_bands = job->n_bands, .src_nd_mode = src_nodata_mode, .ref_nd_mode = ref_nodata_mode,
+                                .src_nodata = src_nodata, .ref_nodata = ref_nodata};
     HK_HIP(hk::launch_compare_sums(ca, sl.norm_ws, sums_dev, sl.stream));
     return HK_OK;
 }
@@ -2429,7 +2400,9 @@ int hk_compare_sums(hk_ctx* ctx, const float* src, int64_t src_stride, int32_t s
     const size_t wbytes = (size_t)width * sizeof(float);
     if ((rc = stage_h2d(hc.sl, d_src, stride * 4, src, src_stride * 4, wbytes, height))) return rc;
     if ((rc = stage_h2d(hc.sl, d_ref, stride * 4, ref, ref_stride * 4, wbytes, height))) return rc;
-    const hk::CompareArgs ca = compare_args(d_src, d_ref, height, width, stride, 0, 1, src_nodata_mode, src_nodata, ref_nodata_mode, ref_nodata);
+    const hk::CompareArgs ca = {.src = d_src, .ref = d_ref, .height = height, .width = width, .src_stride = stride, .ref_stride = stride,
+                                .n_bands = 1, .src_nd_mode = src_nodata_mode, .ref_nd_mode = ref_nodata_mode, .src_nodata = src_nodata,
+                                .ref_nodata = ref_nodata};
     HK_HIP(hk::launch_compare_sums(ca, hc.at(o_ws), d_sums, hc.sl.stream));
     HK_HIP(hipMemcpyAsync(hc.sl.pin<double>(Slot::PIN_SUMS), d_sums, 7 * sizeof(double), hipMemcpyDeviceToHost, hc.sl.stream));
     if ((rc = stage_finish(hc.sl))) return rc;
@@ -2438,35 +2411,26 @@ int hk_compare_sums(hk_ctx* ctx, const float* src, int64_t src_stride, int32_t s
 }
 
 // ParamStats.stats / get_block_sums (homonim/stats.py:217-229): see include/homonim_hk.h
-static int check_param_stats(hk_ctx* ctx, const void* planes, const void* out, int32_t n_bands, int32_t height, int32_t width,
-                             int64_t stride, int32_t nodata_mode) {
+static int check_param_stats(hk_ctx* ctx, const hk::ParamStatsArgs& pa, const void* out) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!planes || !out) return null_arg();
-    if (n_bands < 1 || height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d x %d", n_bands, height, width);
-    if (n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", n_bands);
-    const int rc = check_strides(stride, width);
-    return rc ? rc : check_nodata_mode(nodata_mode);
-}
-
-static hk::ParamStatsArgs param_stats_args(const float* planes, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
-                                           int64_t band_stride, int32_t nodata_mode, float nodata, double thresh) {
-    hk::ParamStatsArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.planes = planes, pa.height = height, pa.width = width, pa.stride = stride, pa.band_stride = band_stride;
-    pa.n_bands = n_bands, pa.nd_mode = nodata_mode, pa.nodata = nodata, pa.thresh = thresh;
-    return pa;
+    if (!pa.planes || !out) return null_arg();
+    if (pa.n_bands < 1 || pa.height < 1 || pa.width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d x %d", pa.n_bands, pa.height, pa.width);
+    if (pa.n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", pa.n_bands);
+    const int rc = check_strides(pa.stride, pa.width);
+    return rc ? rc : check_nodata_mode(pa.nd_mode);
 }
 
 int hk_param_stats_dev(hk_ctx* ctx, const float* planes_dev, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
                        int64_t band_stride, int32_t stream, int32_t nodata_mode, float nodata, double thresh, double* stats_dev) {
-    int rc = check_param_stats(ctx, planes_dev, stats_dev, n_bands, height, width, stride, nodata_mode);
+    const hk::ParamStatsArgs pa = {.planes = planes_dev, .height = height, .width = width, .stride = stride, .band_stride = band_stride,
+                                   .n_bands = n_bands, .nd_mode = nodata_mode, .nodata = nodata, .thresh = thresh};
+    int rc = check_param_stats(ctx, pa, stats_dev);
     if (rc || (rc = check_band_strides(band_stride)) || (rc = check_stream(ctx, stream))) return rc;
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
     Slot& sl = ctx->slots[stream];
     rc = ensure_stream_ws(ctx, sl, hk::param_stats_workspace_bytes(n_bands));
     if (rc) return rc;
-    const hk::ParamStatsArgs pa = param_stats_args(planes_dev, n_bands, height, width, stride, band_stride, nodata_mode, nodata, thresh);
     HK_HIP(hk::launch_param_stats(pa, sl.norm_ws, stats_dev, sl.stream));
     return HK_OK;
 }
@@ -2474,7 +2438,9 @@ int hk_param_stats_dev(hk_ctx* ctx, const float* planes_dev, int32_t n_bands, in
 int hk_param_stats(hk_ctx* ctx, const float* plane, int64_t stride, int32_t nodata_mode, float nodata, double thresh,
                    int32_t height, int32_t width, double stats_out[10]) {
     static_assert(hk::PARAM_STATS_N == 10, "stats_out[10] of include/homonim_hk.h");
-    int rc = check_param_stats(ctx, plane, stats_out, 1, height, width, stride, nodata_mode);
+    hk::ParamStatsArgs pa = {.planes = plane, .height = height, .width = width, .stride = stride, .n_bands = 1, .nd_mode = nodata_mode,
+                             .nodata = nodata, .thresh = thresh};
+    int rc = check_param_stats(ctx, pa, stats_out);
     if (rc) return rc;
     HK_ENTER(ctx);
     const int64_t d_stride = row_align(width);
@@ -2486,7 +2452,7 @@ int hk_param_stats(hk_ctx* ctx, const float* plane, int64_t stride, int32_t noda
     float* d_plane = hc.at<float>(o_plane);
     double* d_stats = hc.at<double>(o_stats);
     if ((rc = stage_h2d(hc.sl, d_plane, d_stride * 4, plane, stride * 4, (size_t)width * sizeof(float), height))) return rc;
-    const hk::ParamStatsArgs pa = param_stats_args(d_plane, 1, height, width, d_stride, 0, nodata_mode, nodata, thresh);
+    pa.planes = d_plane, pa.stride = d_stride;  // the plane in the slab
     HK_HIP(hk::launch_param_stats(pa, hc.at(o_ws), d_stats, hc.sl.stream));
     const size_t bytes = hk::PARAM_STATS_N * sizeof(double);
     HK_HIP(hipMemcpyAsync(hc.sl.pin<double>(Slot::PIN_STATS), d_stats, bytes, hipMemcpyDeviceToHost, hc.sl.stream));
@@ -2507,45 +2473,43 @@ int hk_overview_count(int32_t height, int32_t width, int32_t* n) {
 
 constexpr int OVERVIEW_MAX_LEVELS = 31;
 
-static int check_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
-                           int64_t stride, int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels,
-                           void* const out[], const int64_t out_stride[], const int64_t out_band_stride[]) {
+static_assert(sizeof(long long) == sizeof(int64_t), "strides, offsets and sizes of the ABI are handed on as they are");
+
+static int check_overviews(hk_ctx* ctx, int32_t dtype, const hk::OverviewLevels& r) {
+    const hk::BandPlanes& p = r.planes;
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!planes || !out || !out_stride || !out_band_stride) return null_arg();
+    if (!p.src || !r.out || !r.out_stride || !r.out_band_stride) return null_arg();
     if (!hk::dtype_size(dtype)) return fail(HK_ERR_ARG, "bad dtype %d", dtype);
-    if (n_bands < 1 || height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d x %d", n_bands, height, width);
-    if (n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", n_bands);
-    int rc = check_strides(stride, width);
-    if (rc || (rc = check_band_strides(band_stride))) return rc;
-    if (n_levels < 1 || n_levels > OVERVIEW_MAX_LEVELS) return fail(HK_ERR_ARG, "n_levels %d outside 1..%d", n_levels, OVERVIEW_MAX_LEVELS);
-    for (int m = 1; m <= n_levels; ++m) {
-        const int64_t wm = ((int64_t)width + (1ll << m) - 1) >> m;
-        if (!out[m - 1]) return fail(HK_ERR_ARG, "level %d: NULL plane", m);
-        if (out_stride[m - 1] < wm) return fail(HK_ERR_ARG, "level %d: row stride smaller than its width %lld", m, (long long)wm);
-        if (out_band_stride[m - 1] < 0) return fail(HK_ERR_ARG, "level %d: band_stride is negative", m);
+    if (p.n_bands < 1 || p.height < 1 || p.width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d x %d", p.n_bands, p.height, p.width);
+    if (p.n_bands > 65535) return fail(HK_ERR_ARG, "too many bands for one launch (%d > 65535)", p.n_bands);
+    int rc = check_strides(p.stride, p.width);
+    if (rc || (rc = check_band_strides(p.band_stride))) return rc;
+    if (r.n_levels < 1 || r.n_levels > OVERVIEW_MAX_LEVELS) return fail(HK_ERR_ARG, "n_levels %d outside 1..%d", r.n_levels, OVERVIEW_MAX_LEVELS);
+    for (int m = 1; m <= r.n_levels; ++m) {
+        const int64_t wm = ((int64_t)p.width + (1ll << m) - 1) >> m;
+        if (!r.out[m - 1]) return fail(HK_ERR_ARG, "level %d: NULL plane", m);
+        if (r.out_stride[m - 1] < wm) return fail(HK_ERR_ARG, "level %d: row stride smaller than its width %lld", m, (long long)wm);
+        if (r.out_band_stride[m - 1] < 0) return fail(HK_ERR_ARG, "level %d: band_stride is negative", m);
     }
-    if ((rc = check_nodata_mode(nodata_mode))) return rc;
-    if (nodata_mode == HK_NODATA_VALUE && dtype != HK_DTYPE_F32 && dtype != HK_DTYPE_F64) {
-        const double lo[7] = {0, 0, 0, -32768.0, 0, -2147483648.0, 0}, hi[7] = {0, 255.0, 65535.0, 32767.0, 4294967295.0, 2147483647.0, 0};
-        if (!(nodata >= lo[dtype] && nodata <= hi[dtype]) || nodata != floor(nodata))
-            return fail(HK_ERR_ARG, "nodata %g is not a value of the integer sample type", nodata);
-    }
+    if ((rc = check_nodata_mode(r.nd_mode))) return rc;
+    if (r.nd_mode == HK_NODATA_VALUE && dtype != HK_DTYPE_F32 && dtype != HK_DTYPE_F64 && !int_sample_holds(dtype, r.nodata))
+        return fail(HK_ERR_ARG, "nodata %g is not a value of the integer sample type", r.nodata);
     return HK_OK;
 }
 
 int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
                      int64_t stride, int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels,
                      void* const out_dev[], const int64_t out_stride[], const int64_t out_band_stride[], int32_t stream) {
-    int rc = check_overviews(ctx, planes_dev, dtype, n_bands, height, width, stride, band_stride, nodata_mode, nodata, n_levels,
-                             out_dev, out_stride, out_band_stride);
+    const hk::OverviewLevels r = {.planes = {.src = planes_dev, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
+                                             .band_stride = band_stride},
+                                  .nd_mode = nodata_mode, .nodata = nodata, .n_levels = n_levels, .out = out_dev,
+                                  .out_stride = reinterpret_cast<const long long*>(out_stride),
+                                  .out_band_stride = reinterpret_cast<const long long*>(out_band_stride)};
+    int rc = check_overviews(ctx, dtype, r);
     if (rc || (rc = check_stream(ctx, stream))) return rc;
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
-    static_assert(sizeof(long long) == sizeof(int64_t), "strides are handed on as they are");
-    const hk::BandPlanes planes = {.src = planes_dev, .n_bands = n_bands, .height = height, .width = width, .stride = stride, .band_stride = band_stride};
-    HK_HIP(hk::launch_overviews(dtype, {.planes = planes, .nd_mode = nodata_mode, .nodata = nodata, .n_levels = n_levels, .out = out_dev,
-                                        .out_stride = reinterpret_cast<const long long*>(out_stride),
-                                        .out_band_stride = reinterpret_cast<const long long*>(out_band_stride)}, ctx->slots[stream].stream));
+    HK_HIP(hk::launch_overviews(dtype, r, ctx->slots[stream].stream));
     return HK_OK;
 }
 
@@ -2555,8 +2519,7 @@ int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t
 constexpr size_t OVERVIEW_STRIP_BYTES = 64u << 20;
 static int64_t overview_strip_rows(int32_t n_bands, int32_t height, int32_t width, int esize, int32_t n_levels) {
     if (n_levels >= 31 || ((int64_t)1 << n_levels) >= height) return height;
-    const char* e = getenv("HK_OVERVIEW_STRIP_KB");
-    const size_t cap = (e && atol(e) > 0) ? (size_t)atol(e) << 10 : OVERVIEW_STRIP_BYTES;
+    const size_t cap = cap_from_env("HK_OVERVIEW_STRIP_KB", OVERVIEW_STRIP_BYTES);
     const int64_t unit = (int64_t)1 << n_levels;
     const int64_t rows = (int64_t)(cap / ((size_t)n_bands * width * esize)) / unit * unit;
     return rows < unit ? unit : rows;
@@ -2565,8 +2528,12 @@ static int64_t overview_strip_rows(int32_t n_bands, int32_t height, int32_t widt
 int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
                  int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels, void* const out[],
                  const int64_t out_stride[], const int64_t out_band_stride[]) {
-    int rc = check_overviews(ctx, planes, dtype, n_bands, height, width, stride, band_stride, nodata_mode, nodata, n_levels, out,
-                             out_stride, out_band_stride);
+    const hk::OverviewLevels host = {.planes = {.src = planes, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
+                                                .band_stride = band_stride},
+                                     .nd_mode = nodata_mode, .nodata = nodata, .n_levels = n_levels, .out = out,
+                                     .out_stride = reinterpret_cast<const long long*>(out_stride),
+                                     .out_band_stride = reinterpret_cast<const long long*>(out_band_stride)};
+    int rc = check_overviews(ctx, dtype, host);
     if (rc) return rc;
     HK_ENTER(ctx);
     const size_t es = hk::dtype_size(dtype);
@@ -2597,10 +2564,11 @@ int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands
             if ((rc = stage_h2d(sl, base + o_src + (size_t)b * rows_max * d_stride * es, d_stride * es,
                                 h_src + ((size_t)b * band_stride + (size_t)r0 * stride) * es, stride * es, (size_t)width * es, rows)))
                 return rc;
-        const hk::BandPlanes slab = {.src = base + o_src, .n_bands = n_bands, .height = (int)rows, .width = width, .stride = d_stride,
-                                     .band_stride = rows_max * d_stride};
-        HK_HIP(hk::launch_overviews(dtype, {.planes = slab, .nd_mode = nodata_mode, .nodata = nodata, .n_levels = n_levels, .out = d_out,
-                                            .out_stride = l_stride, .out_band_stride = l_band}, sl.stream));
+        hk::OverviewLevels slab = host;  // this strip on the device
+        slab.planes = {.src = base + o_src, .n_bands = n_bands, .height = (int)rows, .width = width, .stride = d_stride,
+                       .band_stride = rows_max * d_stride};
+        slab.out = d_out, slab.out_stride = l_stride, slab.out_band_stride = l_band;
+        HK_HIP(hk::launch_overviews(dtype, slab, sl.stream));
         for (int m = 1; m <= n_levels; ++m) {
             char* h_out = static_cast<char*>(out[m - 1]);
             for (int b = 0; b < n_bands; ++b)
@@ -2614,44 +2582,37 @@ int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands
 }
 
 // The per-dataset mask of a GeoTIFF applied to its bands (hk_dataset_mask.hip): see include/homonim_hk.h
-static int check_dataset_mask(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
-                              int64_t stride, const void* mask, int32_t mask_kind, int64_t mask_stride, const void* out,
-                              int64_t out_stride) {
+static int check_dataset_mask(hk_ctx* ctx, int32_t dtype, const hk::DatasetMask& a) {
+    const hk::BandPlanes& p = a.planes;
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!planes) return fail(HK_ERR_ARG, "planes is NULL");
-    if (!mask) return fail(HK_ERR_ARG, "mask is NULL");
-    if (!out) return fail(HK_ERR_ARG, "out is NULL");
+    if (!p.src) return fail(HK_ERR_ARG, "planes is NULL");
+    if (!a.mask) return fail(HK_ERR_ARG, "mask is NULL");
+    if (!a.out) return fail(HK_ERR_ARG, "out is NULL");
     if (!hk::dtype_size(dtype)) return fail(HK_ERR_ARG, "bad dtype %d", dtype);
-    if (mask_kind != HK_MASK_BITS && mask_kind != HK_MASK_ALPHA)
-        return fail(HK_ERR_ARG, "bad mask_kind %d: %d (bits) or %d (alpha)", mask_kind, HK_MASK_BITS, HK_MASK_ALPHA);
-    if (mask_kind == HK_MASK_ALPHA && dtype != HK_DTYPE_U8 && dtype != HK_DTYPE_U16)
+    if (a.kind != HK_MASK_BITS && a.kind != HK_MASK_ALPHA)
+        return fail(HK_ERR_ARG, "bad mask_kind %d: %d (bits) or %d (alpha)", a.kind, HK_MASK_BITS, HK_MASK_ALPHA);
+    if (a.kind == HK_MASK_ALPHA && dtype != HK_DTYPE_U8 && dtype != HK_DTYPE_U16)
         return fail(HK_ERR_ARG, "mask_kind alpha takes dtype uint8 or uint16, not dtype %d", dtype);
-    if (n_bands < 1) return fail(HK_ERR_ARG, "n_bands %d is below 1", n_bands);
-    if (height < 1) return fail(HK_ERR_ARG, "height %d is below 1", height);
-    if (width < 1) return fail(HK_ERR_ARG, "width %d is below 1", width);
-    if (stride < width) return fail(HK_ERR_ARG, "stride %lld is smaller than the width %d", (long long)stride, width);
-    if (out_stride < width) return fail(HK_ERR_ARG, "out_stride %lld is smaller than the width %d", (long long)out_stride, width);
-    const int64_t mask_min = mask_kind == HK_MASK_BITS ? ((int64_t)width + 7) / 8 : (int64_t)width;
-    if (mask_stride < mask_min)
-        return fail(HK_ERR_ARG, "mask_stride %lld is smaller than the %lld %s of a mask row", (long long)mask_stride, (long long)mask_min,
-                    mask_kind == HK_MASK_BITS ? "bytes" : "samples");
-    return HK_OK;
-}
-
-// the body of both entries: the launch, on planes, mask and output that are on the device
-static int dataset_mask_on_device(hipStream_t stream, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height,
-                                  int32_t width, int64_t stride, int64_t band_stride, const void* mask_dev, int32_t mask_kind,
-                                  int64_t mask_stride, float* out_dev, int64_t out_stride, int64_t out_band_stride) {
-    const hk::BandPlanes planes = {.src = planes_dev, .n_bands = n_bands, .height = height, .width = width, .stride = stride, .band_stride = band_stride};
-    HK_HIP(hk::launch_dataset_mask(dtype, {.planes = planes, .mask = mask_dev, .kind = mask_kind, .mask_stride = mask_stride, .out = out_dev,
-                                           .out_stride = out_stride, .out_band_stride = out_band_stride}, stream));
+    if (p.n_bands < 1) return fail(HK_ERR_ARG, "n_bands %d is below 1", p.n_bands);
+    if (p.height < 1) return fail(HK_ERR_ARG, "height %d is below 1", p.height);
+    if (p.width < 1) return fail(HK_ERR_ARG, "width %d is below 1", p.width);
+    if (p.stride < p.width) return fail(HK_ERR_ARG, "stride %lld is smaller than the width %d", p.stride, p.width);
+    if (a.out_stride < p.width) return fail(HK_ERR_ARG, "out_stride %lld is smaller than the width %d", a.out_stride, p.width);
+    const long long mask_min = a.kind == HK_MASK_BITS ? ((long long)p.width + 7) / 8 : (long long)p.width;
+    if (a.mask_stride < mask_min)
+        return fail(HK_ERR_ARG, "mask_stride %lld is smaller than the %lld %s of a mask row", a.mask_stride, mask_min,
+                    a.kind == HK_MASK_BITS ? "bytes" : "samples");
     return HK_OK;
 }
 
 int hk_dataset_mask_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
                         int64_t stride, int64_t band_stride, const void* mask_dev, int32_t mask_kind, int64_t mask_stride,
                         float* out_dev, int64_t out_stride, int64_t out_band_stride, int32_t stream) {
-    int rc = check_dataset_mask(ctx, planes_dev, dtype, n_bands, height, width, stride, mask_dev, mask_kind, mask_stride, out_dev, out_stride);
+    const hk::DatasetMask a = {.planes = {.src = planes_dev, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
+                                          .band_stride = band_stride},
+                               .mask = mask_dev, .kind = mask_kind, .mask_stride = mask_stride, .out = out_dev, .out_stride = out_stride,
+                               .out_band_stride = out_band_stride};
+    int rc = check_dataset_mask(ctx, dtype, a);
     if (rc || (rc = check_band_strides(band_stride, out_band_stride)) || (rc = check_stream(ctx, stream))) return rc;
     const uintptr_t es = hk::dtype_size(dtype);
     if (reinterpret_cast<uintptr_t>(planes_dev) % es || (reinterpret_cast<uintptr_t>(out_dev) & 3u) ||
@@ -2659,8 +2620,8 @@ int hk_dataset_mask_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int3
         return fail(HK_ERR_ARG, "planes_dev / mask_dev / out_dev: not aligned to the sample size");
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
-    return dataset_mask_on_device(ctx->slots[stream].stream, planes_dev, dtype, n_bands, height, width, stride, band_stride, mask_dev,
-                                  mask_kind, mask_stride, out_dev, out_stride, out_band_stride);
+    HK_HIP(hk::launch_dataset_mask(dtype, a, ctx->slots[stream].stream));
+    return HK_OK;
 }
 
 // device bytes of one chunk of the host path (rows are independent: the chunking cannot change a bit)
@@ -2668,7 +2629,10 @@ constexpr size_t DATASET_MASK_CHUNK_BYTES = 64u << 20;
 
 int hk_dataset_mask(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
                     const void* mask, int32_t mask_kind, int64_t mask_stride, float* out, int64_t out_stride) {
-    int rc = check_dataset_mask(ctx, planes, dtype, n_bands, height, width, stride, mask, mask_kind, mask_stride, out, out_stride);
+    // (the caller's bands lie `height` rows apart on both sides: the band strides are not read)
+    const hk::DatasetMask host = {.planes = {.src = planes, .n_bands = n_bands, .height = height, .width = width, .stride = stride},
+                                  .mask = mask, .kind = mask_kind, .mask_stride = mask_stride, .out = out, .out_stride = out_stride};
+    int rc = check_dataset_mask(ctx, dtype, host);
     if (rc) return rc;
     HK_ENTER(ctx);
     const size_t es = hk::dtype_size(dtype);
@@ -2679,8 +2643,7 @@ int hk_dataset_mask(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_ba
     const size_t m_row = mask_kind == HK_MASK_BITS ? (size_t)(((int64_t)width + 7) / 8) : (size_t)width * es;
     // whole rows per chunk: samples, mask and results of all bands within DATASET_MASK_CHUNK_BYTES (at least one row);
     // HK_STAGE_CHUNK_KB (read at every call here) lowers the bound for tests of the chunked path
-    const char* e = getenv("HK_STAGE_CHUNK_KB");
-    const size_t cap = (e && atol(e) > 0) ? (size_t)atol(e) << 10 : DATASET_MASK_CHUNK_BYTES;
+    const size_t cap = cap_from_env("HK_STAGE_CHUNK_KB", DATASET_MASK_CHUNK_BYTES);
     const size_t per_row = (size_t)n_bands * d_stride * (es + sizeof(float)) + (size_t)d_mstride * ms;
     const int64_t rows_max = std::max<int64_t>(1, std::min<int64_t>(height, (int64_t)(cap / per_row)));
     SlabLayout L;
@@ -2698,9 +2661,11 @@ int hk_dataset_mask(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_ba
                                 h_in + ((size_t)b * height + (size_t)r0) * stride * es, stride * es, (size_t)width * es, rows)))
                 return rc;
         if ((rc = stage_h2d(sl, base + o_mask, d_mstride * ms, h_mask + (size_t)r0 * mask_stride * ms, mask_stride * ms, m_row, rows))) return rc;
-        if ((rc = dataset_mask_on_device(sl.stream, base + o_in, dtype, n_bands, (int32_t)rows, width, d_stride, rows_max * d_stride,
-                                         base + o_mask, mask_kind, d_mstride, hc.at<float>(o_out), d_stride, rows_max * d_stride)))
-            return rc;
+        const hk::DatasetMask slab = {.planes = {.src = base + o_in, .n_bands = n_bands, .height = (int)rows, .width = width, .stride = d_stride,
+                                                 .band_stride = rows_max * d_stride},
+                                      .mask = base + o_mask, .kind = mask_kind, .mask_stride = d_mstride, .out = hc.at<float>(o_out),
+                                      .out_stride = d_stride, .out_band_stride = rows_max * d_stride};
+        HK_HIP(hk::launch_dataset_mask(dtype, slab, sl.stream));
         for (int b = 0; b < n_bands; ++b)
             if ((rc = stage_d2h(sl, out + ((size_t)b * height + (size_t)r0) * out_stride, out_stride * sizeof(float),
                                 hc.at<float>(o_out) + (size_t)b * rows_max * d_stride, d_stride * sizeof(float),
@@ -2741,26 +2706,23 @@ static int check_predictor(int32_t dtype, int32_t predictor) {
     return HK_OK;
 }
 
-static int check_deflate(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
-                         int64_t stride, int64_t band_stride, int32_t tile, const void* out, int64_t out_capacity,
-                         const int64_t* tile_offsets, const int64_t* tile_sizes, int64_t* n_tiles, int64_t* n_chunks) {
+// (r.esize is not read: the dtype says it, and the dtype may be a bad one)
+static int check_deflate(hk_ctx* ctx, int32_t dtype, const hk::DeflateTiles& r, int64_t out_capacity, int64_t* n_tiles, int64_t* n_chunks) {
+    const hk::BandPlanes& p = r.planes;
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    if (!planes || !out || !tile_offsets || !tile_sizes) return null_arg();
+    if (!p.src || !r.out || !r.tile_offsets || !r.tile_sizes) return null_arg();
     int64_t bytes = 0;
-    int rc = deflate_shape(dtype, n_bands, height, width, tile, n_tiles, &bytes, n_chunks);
-    if (rc || (rc = check_strides(stride, width)) || (rc = check_band_strides(band_stride))) return rc;
+    int rc = deflate_shape(dtype, p.n_bands, p.height, p.width, r.tile, n_tiles, &bytes, n_chunks);
+    if (rc || (rc = check_strides(p.stride, p.width)) || (rc = check_band_strides(p.band_stride))) return rc;
     if (out_capacity < bytes) return fail(HK_ERR_ARG, "out_capacity %lld is below hk_deflate_bound's %lld", (long long)out_capacity, (long long)bytes);
     return HK_OK;
 }
 
 // the body of hk_deflate_tiles_dev and hk_deflate_tiles_pred_dev (which has checked the predictor): the checks of the former in
 // their order, then the launch
-static int deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
-                             int64_t stride, int64_t band_stride, int32_t tile, void* out_dev, int64_t out_capacity,
-                             int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream, int32_t predictor) {
+static int deflate_tiles_dev(hk_ctx* ctx, int32_t dtype, const hk::DeflateTiles& r, int64_t out_capacity, int32_t stream, int32_t predictor) {
     int64_t n_tiles = 0, n_chunks = 0;
-    int rc = check_deflate(ctx, planes_dev, dtype, n_bands, height, width, stride, band_stride, tile, out_dev, out_capacity,
-                           tile_offsets_dev, tile_sizes_dev, &n_tiles, &n_chunks);
+    int rc = check_deflate(ctx, dtype, r, out_capacity, &n_tiles, &n_chunks);
     if (rc || (rc = check_stream(ctx, stream))) return rc;
     if (n_chunks > 0x7FFFFFFFll) return fail(HK_ERR_ARG, "%lld chunks are more than one launch takes", (long long)n_chunks);
     DevEnter entered(ctx, stream);
@@ -2768,19 +2730,19 @@ static int deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype,
     Slot& sl = ctx->slots[stream];
     rc = ensure_stream_ws(ctx, sl, hk::deflate_workspace_bytes(n_chunks));
     if (rc) return rc;
-    static_assert(sizeof(long long) == sizeof(int64_t), "offsets are handed on as they are");
-    const hk::BandPlanes planes = {.src = planes_dev, .n_bands = n_bands, .height = height, .width = width, .stride = stride, .band_stride = band_stride};
-    HK_HIP(hk::launch_deflate_tiles(predictor, {.planes = planes, .esize = hk::dtype_size(dtype), .tile = tile, .out = static_cast<unsigned char*>(out_dev),
-                                                .tile_offsets = reinterpret_cast<long long*>(tile_offsets_dev),
-                                                .tile_sizes = reinterpret_cast<long long*>(tile_sizes_dev)}, sl.norm_ws, sl.stream));
+    HK_HIP(hk::launch_deflate_tiles(predictor, r, sl.norm_ws, sl.stream));
     return HK_OK;
 }
 
 int hk_deflate_tiles_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
                          int64_t stride, int64_t band_stride, int32_t tile, void* out_dev, int64_t out_capacity,
                          int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream) {
-    return deflate_tiles_dev(ctx, planes_dev, dtype, n_bands, height, width, stride, band_stride, tile, out_dev, out_capacity,
-                             tile_offsets_dev, tile_sizes_dev, stream, 1);
+    const hk::DeflateTiles r = {.planes = {.src = planes_dev, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
+                                           .band_stride = band_stride},
+                                .esize = hk::dtype_size(dtype), .tile = tile, .out = static_cast<unsigned char*>(out_dev),
+                                .tile_offsets = reinterpret_cast<long long*>(tile_offsets_dev),
+                                .tile_sizes = reinterpret_cast<long long*>(tile_sizes_dev)};
+    return deflate_tiles_dev(ctx, dtype, r, out_capacity, stream, 1);
 }
 
 int hk_deflate_tiles_pred_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
@@ -2788,8 +2750,12 @@ int hk_deflate_tiles_pred_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype
                               int64_t* tile_offsets_dev, int64_t* tile_sizes_dev, int32_t stream, int32_t predictor) {
     const int rc = check_predictor(dtype, predictor);
     if (rc) return rc;
-    return deflate_tiles_dev(ctx, planes_dev, dtype, n_bands, height, width, stride, band_stride, tile, out_dev, out_capacity,
-                             tile_offsets_dev, tile_sizes_dev, stream, predictor);
+    const hk::DeflateTiles r = {.planes = {.src = planes_dev, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
+                                           .band_stride = band_stride},
+                                .esize = hk::dtype_size(dtype), .tile = tile, .out = static_cast<unsigned char*>(out_dev),
+                                .tile_offsets = reinterpret_cast<long long*>(tile_offsets_dev),
+                                .tile_sizes = reinterpret_cast<long long*>(tile_sizes_dev)};
+    return deflate_tiles_dev(ctx, dtype, r, out_capacity, stream, predictor);
 }
 
 // tile rows per group of the host path: whole tile rows of ONE band of at most DEFLATE_GROUP_BYTES raw bytes (at least one tile
@@ -2798,18 +2764,18 @@ int hk_deflate_tiles_pred_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype
 constexpr size_t DEFLATE_GROUP_BYTES = 64u << 20;
 
 // the body of hk_deflate_tiles and hk_deflate_tiles_pred (which has checked the predictor)
-static int deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
-                         int64_t stride, int64_t band_stride, int32_t tile, void* out, int64_t out_capacity, int64_t* tile_offsets,
-                         int64_t* tile_sizes, int32_t predictor) {
+// (`host`: the caller's raster, streams and tables, all host memory)
+static int deflate_tiles(hk_ctx* ctx, int32_t dtype, const hk::DeflateTiles& host, int64_t out_capacity, int32_t predictor) {
     int64_t n_tiles = 0, n_chunks = 0;
-    int rc = check_deflate(ctx, planes, dtype, n_bands, height, width, stride, band_stride, tile, out, out_capacity, tile_offsets,
-                           tile_sizes, &n_tiles, &n_chunks);
+    int rc = check_deflate(ctx, dtype, host, out_capacity, &n_tiles, &n_chunks);
     if (rc) return rc;
     HK_ENTER(ctx);
+    const int n_bands = host.planes.n_bands, height = host.planes.height, width = host.planes.width, tile = host.tile;
+    const long long stride = host.planes.stride, band_stride = host.planes.band_stride;
+    long long* const tile_offsets = host.tile_offsets;
     const size_t es = hk::dtype_size(dtype);
     const int64_t across = ((int64_t)width + tile - 1) / tile, down = ((int64_t)height + tile - 1) / tile;
-    const char* e = getenv("HK_DEFLATE_GROUP_KB");
-    const size_t cap = (e && atol(e) > 0) ? (size_t)atol(e) << 10 : DEFLATE_GROUP_BYTES;
+    const size_t cap = cap_from_env("HK_DEFLATE_GROUP_KB", DEFLATE_GROUP_BYTES);
     const int64_t row_raw = across * tile * tile * (int64_t)es;   // raw bytes of one tile row
     const int64_t g_down = std::max<int64_t>(1, std::min<int64_t>(down, (int64_t)(cap / (size_t)row_raw)));
     int64_t g_tiles = 0, g_bytes = 0, g_chunks = 0;
@@ -2828,8 +2794,8 @@ static int deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t
     if (hc.rc) return hc.rc;
     Slot& sl = hc.sl;
     char* const base = hc.at(0);
-    const char* h_src = static_cast<const char*>(planes);
-    char* h_out = static_cast<char*>(out);
+    const char* h_src = static_cast<const char*>(host.planes.src);
+    unsigned char* h_out = host.out;
     int64_t used = 0, t0 = 0;
     for (int b = 0; b < n_bands; ++b)
         for (int64_t ty = 0; ty < down; ty += g_down) {
@@ -2838,13 +2804,14 @@ static int deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t
             if ((rc = stage_h2d(sl, base + o_src, d_stride * es, h_src + ((size_t)b * band_stride + (size_t)r0 * stride) * es,
                                 stride * es, (size_t)width * es, rows)))
                 return rc;
-            const hk::BandPlanes slab = {.src = base + o_src, .n_bands = 1, .height = (int)rows, .width = width, .stride = d_stride, .band_stride = 0};
-            HK_HIP(hk::launch_deflate_tiles(predictor, {.planes = slab, .esize = (int)es, .tile = tile, .out = hc.at<unsigned char>(o_out),
-                                                        .tile_offsets = hc.at<long long>(o_off), .tile_sizes = hc.at<long long>(o_siz)},
-                                            base + o_work, sl.stream));
+            const hk::DeflateTiles slab = {.planes = {.src = base + o_src, .n_bands = 1, .height = (int)rows, .width = width, .stride = d_stride,
+                                                      .band_stride = 0},
+                                           .esize = (int)es, .tile = tile, .out = hc.at<unsigned char>(o_out),
+                                           .tile_offsets = hc.at<long long>(o_off), .tile_sizes = hc.at<long long>(o_siz)};
+            HK_HIP(hk::launch_deflate_tiles(predictor, slab, base + o_work, sl.stream));
             // the offsets first (they say how many bytes there are), then only the compressed bytes
             if ((rc = stage_d2h(sl, tile_offsets + t0, 0, base + o_off, 0, (size_t)(nt + 1) * sizeof(int64_t), 1))) return rc;
-            if ((rc = stage_d2h(sl, tile_sizes + t0, 0, base + o_siz, 0, (size_t)nt * sizeof(int64_t), 1))) return rc;
+            if ((rc = stage_d2h(sl, host.tile_sizes + t0, 0, base + o_siz, 0, (size_t)nt * sizeof(int64_t), 1))) return rc;
             if ((rc = stage_finish(sl))) return rc;
             const int64_t got = tile_offsets[t0 + nt];
             if (got < 0 || got > out_capacity - used) return fail(HK_ERR_HIP, "deflate: a group reports %lld bytes, %lld are left", (long long)got, (long long)(out_capacity - used));
@@ -2858,8 +2825,12 @@ static int deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t
 
 int hk_deflate_tiles(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
                      int64_t band_stride, int32_t tile, void* out, int64_t out_capacity, int64_t* tile_offsets, int64_t* tile_sizes) {
-    return deflate_tiles(ctx, planes, dtype, n_bands, height, width, stride, band_stride, tile, out, out_capacity, tile_offsets,
-                         tile_sizes, 1);
+    const hk::DeflateTiles r = {.planes = {.src = planes, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
+                                           .band_stride = band_stride},
+                                .esize = hk::dtype_size(dtype), .tile = tile, .out = static_cast<unsigned char*>(out),
+                                .tile_offsets = reinterpret_cast<long long*>(tile_offsets),
+                                .tile_sizes = reinterpret_cast<long long*>(tile_sizes)};
+    return deflate_tiles(ctx, dtype, r, out_capacity, 1);
 }
 
 int hk_deflate_tiles_pred(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
@@ -2867,8 +2838,12 @@ int hk_deflate_tiles_pred(hk_ctx* ctx, const void* planes, int32_t dtype, int32_
                           int64_t* tile_sizes, int32_t predictor) {
     const int rc = check_predictor(dtype, predictor);
     if (rc) return rc;
-    return deflate_tiles(ctx, planes, dtype, n_bands, height, width, stride, band_stride, tile, out, out_capacity, tile_offsets,
-                         tile_sizes, predictor);
+    const hk::DeflateTiles r = {.planes = {.src = planes, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
+                                           .band_stride = band_stride},
+                                .esize = hk::dtype_size(dtype), .tile = tile, .out = static_cast<unsigned char*>(out),
+                                .tile_offsets = reinterpret_cast<long long*>(tile_offsets),
+                                .tile_sizes = reinterpret_cast<long long*>(tile_sizes)};
+    return deflate_tiles(ctx, dtype, r, out_capacity, predictor);
 }
 
 // INFLATE of a GeoTIFF image's blocks (hk_inflate.hip): see include/homonim_hk.h
@@ -2930,57 +2905,50 @@ static const char* lzw_status_text(int st) {
     return st >= 0 && st <= HK_LZW_SHORT ? text[st] : "unknown status";
 }
 
-static hk::InflateArgs inflate_args(const hk_inflate_layout* l, const InflateShape& s, int32_t height) {
-    hk::InflateArgs a;
-    memset(&a, 0, sizeof(a));
+// A block image reaches the functions below as the launcher's hk::InflateArgs with the caller's part filled in by the entry: the
+// streams and their table, work, status, out and the two strides.  inflate_layout_args adds the layout's part for `height` rows.
+static_assert(sizeof(int) == sizeof(int32_t), "statuses are handed on as they are");
+static void inflate_layout_args(hk::InflateArgs& a, const hk_inflate_layout* l, const InflateShape& s, int32_t height) {
     a.es = l->sample_bytes, a.height = height, a.width = l->width, a.bw = l->block_w, a.bh = l->block_h;
     a.tiled = l->tiled, a.separate = l->separate, a.predictor = l->predictor, a.cspp = s.cspp;
     a.across = (int)s.across, a.down = (int)(((int64_t)height + l->block_h - 1) / l->block_h), a.slot = s.slot;
-    return a;
 }
 
 // what every form of a block image asks of its layout, pointers and strides: the part that needs no context ...
-static int check_blocks_image(const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
-                              const void* out, int64_t stride, int64_t band_stride, InflateShape* s) {
+static int check_blocks_image(const hk_inflate_layout* layout, const hk::InflateArgs& io, InflateShape* s) {
     int rc = inflate_shape(layout, s);
     if (rc) return rc;
-    if (!streams || !offsets || !sizes || !out) return null_arg();
-    if ((rc = check_strides(stride, layout->width))) return rc;
-    if (band_stride < 0 || (layout->spp > 1 && band_stride < stride * (layout->height - 1) + layout->width))
-        return fail(HK_ERR_ARG, "band_stride %lld is smaller than a plane", (long long)band_stride);
+    if (!io.streams || !io.offsets || !io.sizes || !io.out) return null_arg();
+    if ((rc = check_strides(io.stride, layout->width))) return rc;
+    if (io.band_stride < 0 || (layout->spp > 1 && io.band_stride < io.stride * (layout->height - 1) + layout->width))
+        return fail(HK_ERR_ARG, "band_stride %lld is smaller than a plane", io.band_stride);
     return HK_OK;
 }
 // ... behind the context, for the forms that run on the device
-static int check_inflate(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
-                         const void* out, int64_t stride, int64_t band_stride, InflateShape* s) {
+static int check_inflate(hk_ctx* ctx, const hk_inflate_layout* layout, const hk::InflateArgs& io, InflateShape* s) {
     if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
-    return check_blocks_image(layout, streams, offsets, sizes, out, stride, band_stride, s);
+    return check_blocks_image(layout, io, s);
 }
 // the block table of the host forms (host memory): no negative offset or size
-static int check_block_table(const int64_t* offsets, const int64_t* sizes, int64_t n_blocks) {
+static int check_block_table(const long long* offsets, const long long* sizes, int64_t n_blocks) {
     for (int64_t b = 0; b < n_blocks; ++b)
-        if (offsets[b] < 0 || sizes[b] < 0) return fail(HK_ERR_ARG, "block %lld: offset %lld, size %lld", (long long)b, (long long)offsets[b], (long long)sizes[b]);
+        if (offsets[b] < 0 || sizes[b] < 0) return fail(HK_ERR_ARG, "block %lld: offset %lld, size %lld", (long long)b, offsets[b], sizes[b]);
     return HK_OK;
 }
 
 // hk_inflate_image_dev and hk_lzw_image_dev: the same call with another first kernel
-static int blocks_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
-                            const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
-                            int32_t* status_dev, int32_t stream, bool lzw) {
+static int blocks_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, hk::InflateArgs a, int32_t stream, bool lzw) {
     InflateShape s;
-    int rc = check_inflate(ctx, layout, streams_dev, offsets_dev, sizes_dev, out_dev, stride, band_stride, &s);
+    int rc = check_inflate(ctx, layout, a, &s);
     if (rc) return rc;
-    if (!work_dev || !status_dev) return null_arg();
-    if ((uintptr_t)work_dev % 16) return fail(HK_ERR_ARG, "work_dev is not 16-byte aligned");
-    if ((uintptr_t)out_dev % layout->sample_bytes) return fail(HK_ERR_ARG, "out_dev is not aligned to its samples");
+    if (!a.work || !a.status) return null_arg();
+    if ((uintptr_t)a.work % 16) return fail(HK_ERR_ARG, "work_dev is not 16-byte aligned");
+    if ((uintptr_t)a.out % layout->sample_bytes) return fail(HK_ERR_ARG, "out_dev is not aligned to its samples");
     if ((rc = check_stream(ctx, stream))) return rc;
     if (s.n_blocks > 0x7FFFFFFFll) return fail(HK_ERR_ARG, "%lld blocks are more than one launch takes", (long long)s.n_blocks);
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
-    hk::InflateArgs a = inflate_args(layout, s, layout->height);
-    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "offsets, sizes and statuses are handed on as they are");
-    a.streams = streams_dev, a.offsets = reinterpret_cast<const long long*>(offsets_dev), a.sizes = reinterpret_cast<const long long*>(sizes_dev);
-    a.work = static_cast<unsigned char*>(work_dev), a.status = status_dev, a.out = out_dev, a.stride = stride, a.band_stride = band_stride;
+    inflate_layout_args(a, layout, s, layout->height);
     HK_HIP(lzw ? hk::launch_lzw_image(a, s.n_blocks, ctx->slots[stream].stream) : hk::launch_inflate_image(a, s.n_blocks, ctx->slots[stream].stream));
     return HK_OK;
 }
@@ -2988,13 +2956,17 @@ static int blocks_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const 
 int hk_inflate_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
                          const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
                          int32_t* status_dev, int32_t stream) {
-    return blocks_image_dev(ctx, layout, streams_dev, offsets_dev, sizes_dev, work_dev, out_dev, stride, band_stride, status_dev, stream, false);
+    return blocks_image_dev(ctx, layout, {.streams = streams_dev, .offsets = reinterpret_cast<const long long*>(offsets_dev),
+                                          .sizes = reinterpret_cast<const long long*>(sizes_dev), .work = static_cast<unsigned char*>(work_dev),
+                                          .status = status_dev, .out = out_dev, .stride = stride, .band_stride = band_stride}, stream, false);
 }
 
 int hk_lzw_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
                      const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
                      int32_t* status_dev, int32_t stream) {
-    return blocks_image_dev(ctx, layout, streams_dev, offsets_dev, sizes_dev, work_dev, out_dev, stride, band_stride, status_dev, stream, true);
+    return blocks_image_dev(ctx, layout, {.streams = streams_dev, .offsets = reinterpret_cast<const long long*>(offsets_dev),
+                                          .sizes = reinterpret_cast<const long long*>(sizes_dev), .work = static_cast<unsigned char*>(work_dev),
+                                          .status = status_dev, .out = out_dev, .stride = stride, .band_stride = band_stride}, stream, true);
 }
 
 // block rows per group of the host path: whole block rows of ALL planes, at most INFLATE_GROUP_BYTES of raw bytes (at least one
@@ -3004,22 +2976,23 @@ int hk_lzw_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* s
 constexpr size_t INFLATE_GROUP_BYTES = 64u << 20;
 
 // (hk_inflate_image and hk_lzw_image: the same call with another first kernel)
-static int blocks_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
-                        void* out, int64_t stride, int64_t band_stride, int32_t* status, bool lzw) {
+// `host`: the caller's streams, table, raster and statuses (nullable), all host memory
+static int blocks_image(hk_ctx* ctx, const hk_inflate_layout* layout, const hk::InflateArgs& host, bool lzw) {
     InflateShape s;
-    int rc = check_inflate(ctx, layout, streams, offsets, sizes, out, stride, band_stride, &s);
-    if (rc || (rc = check_block_table(offsets, sizes, s.n_blocks))) return rc;
+    int rc = check_inflate(ctx, layout, host, &s);
+    if (rc || (rc = check_block_table(host.offsets, host.sizes, s.n_blocks))) return rc;
     HK_ENTER(ctx);
+    const long long *const offsets = host.offsets, *const sizes = host.sizes, stride = host.stride, band_stride = host.band_stride;
+    int* const status = host.status;
     const size_t es = (size_t)layout->sample_bytes;
     const int64_t bh = layout->block_h, per = s.across * s.down;
-    const char* e = getenv("HK_INFLATE_GROUP_KB");
-    const size_t cap = (e && atol(e) > 0) ? (size_t)atol(e) << 10 : INFLATE_GROUP_BYTES;
+    const size_t cap = cap_from_env("HK_INFLATE_GROUP_KB", INFLATE_GROUP_BYTES);
     const int64_t row_raw = s.planes * s.across * s.slot;   // slots of one block row
     const int64_t g_down = std::max<int64_t>(1, std::min<int64_t>(s.down, (int64_t)(cap / (size_t)row_raw)));
     const int64_t g_blocks = s.planes * g_down * s.across;
     if (g_blocks > 0x7FFFFFFFll) return fail(HK_ERR_ARG, "%lld blocks are more than one launch takes", (long long)g_blocks);
     // the spans of every group and plane: where they start in the caller's buffer and how long they are; the largest sum over a group
-    struct Span { int64_t lo, hi; };
+    struct Span { long long lo, hi; };
     auto span_of = [&](int64_t plane, int64_t by0, int64_t by1) {
         Span sp{INT64_MAX, 0};
         for (int64_t b = plane * per + by0 * s.across; b < plane * per + by1 * s.across; ++b)
@@ -3052,8 +3025,8 @@ static int blocks_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void
     if (hc.rc) return hc.rc;
     Slot& sl = hc.sl;
     char* const base = hc.at(0);
-    const char* h_in = static_cast<const char*>(streams);
-    char* h_out = static_cast<char*>(out);
+    const char* h_in = static_cast<const char*>(host.streams);
+    char* h_out = static_cast<char*>(host.out);
     std::vector<int64_t> g_off((size_t)g_blocks), g_siz((size_t)g_blocks);
     std::vector<int32_t> g_st((size_t)g_blocks);
     int64_t first_bad = -1;
@@ -3074,10 +3047,10 @@ static int blocks_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void
         }
         if ((rc = stage_h2d(sl, base + o_off, 0, g_off.data(), 0, (size_t)nb * sizeof(int64_t), 1))) return rc;
         if ((rc = stage_h2d(sl, base + o_siz, 0, g_siz.data(), 0, (size_t)nb * sizeof(int64_t), 1))) return rc;
-        hk::InflateArgs a = inflate_args(layout, s, (int32_t)rows);
-        a.streams = base + o_in, a.offsets = hc.at<long long>(o_off), a.sizes = hc.at<long long>(o_siz);
-        a.work = hc.at<unsigned char>(o_work), a.status = hc.at<int>(o_st);
-        a.out = base + o_out, a.stride = d_stride, a.band_stride = rows * d_stride;
+        hk::InflateArgs a = {.streams = base + o_in, .offsets = hc.at<long long>(o_off), .sizes = hc.at<long long>(o_siz),
+                             .work = hc.at<unsigned char>(o_work), .status = hc.at<int>(o_st), .out = base + o_out, .stride = d_stride,
+                             .band_stride = rows * d_stride};
+        inflate_layout_args(a, layout, s, (int32_t)rows);
         HK_HIP(lzw ? hk::launch_lzw_image(a, nb, sl.stream) : hk::launch_inflate_image(a, nb, sl.stream));
         if ((rc = stage_d2h(sl, g_st.data(), 0, base + o_st, 0, (size_t)nb * sizeof(int32_t), 1))) return rc;
         for (int c = 0; c < layout->spp; ++c)
@@ -3101,26 +3074,32 @@ static int blocks_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void
 
 int hk_inflate_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
                      void* out, int64_t stride, int64_t band_stride, int32_t* status) {
-    return blocks_image(ctx, layout, streams, offsets, sizes, out, stride, band_stride, status, false);
+    return blocks_image(ctx, layout, {.streams = streams, .offsets = reinterpret_cast<const long long*>(offsets),
+                                      .sizes = reinterpret_cast<const long long*>(sizes), .status = status, .out = out, .stride = stride,
+                                      .band_stride = band_stride}, false);
 }
 
 int hk_lzw_image(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes,
                  void* out, int64_t stride, int64_t band_stride, int32_t* status) {
-    return blocks_image(ctx, layout, streams, offsets, sizes, out, stride, band_stride, status, true);
+    return blocks_image(ctx, layout, {.streams = streams, .offsets = reinterpret_cast<const long long*>(offsets),
+                                      .sizes = reinterpret_cast<const long long*>(sizes), .status = status, .out = out, .stride = stride,
+                                      .band_stride = band_stride}, true);
 }
 
 // the same image on the calling thread (hk_lzw_host.hip): no context, no device
 int hk_lzw_image_host(const hk_inflate_layout* layout, const void* streams, const int64_t* offsets, const int64_t* sizes, void* out,
                       int64_t stride, int64_t band_stride, int32_t* status) {
     InflateShape s;
-    int rc = check_blocks_image(layout, streams, offsets, sizes, out, stride, band_stride, &s);
+    hk::InflateArgs a = {.streams = streams, .offsets = reinterpret_cast<const long long*>(offsets),
+                         .sizes = reinterpret_cast<const long long*>(sizes), .status = status, .out = out, .stride = stride,
+                         .band_stride = band_stride};
+    int rc = check_blocks_image(layout, a, &s);
     if (rc) return rc;
     if ((uintptr_t)out % layout->sample_bytes) return fail(HK_ERR_ARG, "out is not aligned to its samples");
-    if ((rc = check_block_table(offsets, sizes, s.n_blocks))) return rc;
+    if ((rc = check_block_table(a.offsets, a.sizes, s.n_blocks))) return rc;
     std::vector<uint64_t> slot((size_t)s.slot / 8 + 2);   // (8-byte aligned for every sample size; the slot is a multiple of 16)
-    hk::InflateArgs a = inflate_args(layout, s, layout->height);
-    a.streams = streams, a.offsets = reinterpret_cast<const long long*>(offsets), a.sizes = reinterpret_cast<const long long*>(sizes);
-    a.work = reinterpret_cast<unsigned char*>(slot.data()), a.status = status, a.out = out, a.stride = stride, a.band_stride = band_stride;
+    inflate_layout_args(a, layout, s, layout->height);
+    a.work = reinterpret_cast<unsigned char*>(slot.data());
     int first_status = 0;
     const long long first_bad = hk::lzw_image_host(a, s.n_blocks, &first_status);
     if (first_bad >= 0)
