@@ -20,7 +20,8 @@ pytestmark = [pytest.mark.gpu, pytest.mark.oracle]
 
 MASK_DIR = os.path.join(GOLDEN_DIR, 'tiff', 'mask')
 SHAPES = [(1, 1, 1), (3, 3, 7), (3, 2, 8), (1, 3, 9), (2, 3, 63), (2, 2, 64), (3, 2, 65), (1, 4, 130), (4, 5, 515),
-          (2, 3, 1100)]   # (the last one: two whole waves of 64 groups -- the path that exchanges a wave's halves -- and a part of one)
+          (2, 3, 1100),   # (two whole waves of 64 groups -- the path that exchanges a wave's halves -- and a part of one)
+          (2, 2051, 9), (1, 4100, 515)]   # (taller than the 2048 grid rows of launch_dataset_mask: a workgroup walks 2 and 3 rows)
 MASKS = ['all', 'none', 'random', 'last', 'alternating']
 BUILDS = [(d, 'bits') for d in _hk.DTYPE_CODES] + [('uint8', 'alpha'), ('uint16', 'alpha')]
 CANARY = 0xC3

@@ -70,9 +70,12 @@ def check_vector(got, x, nodata, thresh, what):
 
 
 # -- the cases ----------------------------------------------------------------------------------------------------------------
-SHAPES = [(1, 1, None), (1, 7, None), (513, 3, None), (97, 1031, None), (2048, 2050, 2112)]   # (height, width, row stride)
+# (height, width, row stride); the last two are taller than the 2048 workgroups a band gets, so that a workgroup walks a second and a
+# third row: the per-row reset of the column maximum and the folds of the row range and of the 64-bit counts carried across rows
+SHAPES = [(1, 1, None), (1, 7, None), (513, 3, None), (97, 1031, None), (2048, 2050, 2112), (4100, 9, None), (2049, 1031, 1088)]
+ROWS_PER_PASS = 2048   # PSTATS_BLOCKS of hk_param_stats.hip: row y is walked by workgroup y % 2048, as its (y // 2048)-th row
 VALUES = {'unit': (1.0, 0.3, 0.25), 'dn': (1000.0, 150.0, 900.0)}                            # mean, sigma, thresh
-CASES = ['no_holes', 'nan_frame_holes', 'all_nan', 'nodata_0', 'inf_pixel', 'thresh_0p1']
+CASES = ['no_holes', 'nan_frame_holes', 'all_nan', 'nodata_0', 'inf_pixel', 'thresh_0p1', 'shrinking_box']
 
 
 def make_case(shape, values, case):
@@ -108,7 +111,40 @@ def make_case(shape, values, case):
         near = np.float32(0.1)
         for v in (near, np.nextafter(near, np.float32(0)), np.nextafter(near, np.float32(1))):
             x[rng.integers(0, height), rng.integers(0, width)] = v
+    elif case == 'shrinking_box':
+        x[~shrinking_box_valid(height, width)] = np.nan
     return x, nodata, thresh
+
+
+def shrinking_box_valid(height, width):
+    """ The valid pixels of 'shrinking_box'.  Row 0 alone is valid over its whole width, so both column bounds of the box come from
+    the first row of workgroup 0; every other row y is valid in [inset, width - inset) with inset = 1 + y // 2048, so the second and
+    third rows of every workgroup (y + 2048, y + 4096) are strictly narrower than its first, and empty where the width is used up.
+    Rows with y % 5 == 3 hold no valid pixel, nor does the last row: the last valid row is followed, in the workgroups that walk
+    the rows behind it, by an empty one, which a count or a column maximum left over from the row before would turn into data. """
+    valid = np.zeros((height, width), bool)
+    for y in range(height):
+        inset = 1 + y // ROWS_PER_PASS if y else 0
+        if y == 0 or not (y % 5 == 3 or y == height - 1):
+            valid[y, inset:max(inset, width - inset)] = True
+    return valid
+
+
+def test_the_shrinking_box_is_what_it_says():
+    """ (no device: the statement of the case, checked on the shapes that are taller than one pass) """
+    for height, width, _ in SHAPES:
+        valid = shrinking_box_valid(height, width)
+        lo = np.where(valid.any(1), valid.argmax(1), width)
+        hi = np.where(valid.any(1), width - 1 - valid[:, ::-1].argmax(1), -1)
+        assert lo[0] == 0 and hi[0] == width - 1 and (lo[1:] > 0).all() and (hi[1:] < width - 1).all()
+        for y in range(ROWS_PER_PASS, height):   # a workgroup's next row lies strictly inside the one before it, or is empty
+            above = y - ROWS_PER_PASS
+            assert not valid[y].any() or not valid[above].any() or (lo[y] > lo[above] and hi[y] < hi[above]), (height, width, y)
+        if height > ROWS_PER_PASS:   # an empty row behind the last valid one, walked by a workgroup that has seen valid pixels
+            last = int(np.nonzero(valid.any(1))[0][-1])
+            assert any(valid[y - ROWS_PER_PASS].any() for y in range(max(last + 1, ROWS_PER_PASS), height)), (height, width)
+        if height > ROWS_PER_PASS + 2:
+            assert valid[ROWS_PER_PASS:].any() and last >= ROWS_PER_PASS
 
 
 @pytest.mark.oracle
