@@ -13,16 +13,13 @@ Deviation: the block sums come back as float64 (exact sums of the float32 per-pi
 float32 pairwise sums; the statistics agree with the reference's to its own summation error (~1e-6 relative).
 """
 import math
-from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
 from homonim_amd import _hk, utils
 from homonim_amd.enums import ProcCrs, Resampling
-from homonim_amd.fuse import RasterFuse
-from homonim_amd.geo import Affine
-from homonim_amd.raster_array import RasterArray
+from homonim_amd.fuse import RasterFuse, default_devices
 
 _SUM_KEYS = ('src_sum', 'ref_sum', 'src2_sum', 'ref2_sum', 'src_ref_sum', 'res2_sum', 'mask_sum')
 
@@ -95,15 +92,11 @@ class RasterCompare(RasterFuse):
 
     def _block_sums(self, bp, ctx, config) -> Dict:
         """ compare.py:232-256 for one block """
-        if self._same_grid:
-            src_ra, ref_ra = self._read(bp)
-        else:
-            s_arr, s_nd = self._read_boundless(self._src[bp.band_i], self._src_nodata, bp.src_in_block)
-            r_arr, r_nd = self._read_boundless(self._ref[bp.band_i], self._ref_nodata, bp.ref_in_block)
-            src_tf = self._transform * Affine.translation(bp.src_in_block.col_off, bp.src_in_block.row_off)
-            ref_tf = self._ref_transform * Affine.translation(bp.ref_in_block.col_off, bp.ref_in_block.row_off)
-            src_ra = RasterArray(np.ascontiguousarray(s_arr, dtype=np.float32), self._crs, src_tf, nodata=s_nd)
-            ref_ra = RasterArray(np.ascontiguousarray(r_arr, dtype=np.float32), self._crs, ref_tf, nodata=r_nd)
+        src_ra, ref_ra = self._read_pair(bp)
+        if not self._same_grid:
+            # ``reproject`` is float32 to float32 (on a shared grid ``compare_sums`` takes the views as they are)
+            src_ra.array = np.ascontiguousarray(src_ra.array, dtype=np.float32)
+            ref_ra.array = np.ascontiguousarray(ref_ra.array, dtype=np.float32)
             if self._proc_crs == ProcCrs.ref:
                 resampling = self._get_resampling(src_ra.res, ref_ra.res, **config)
                 src_ra = src_ra.reproject(**ref_ra.proj_profile, resampling=resampling, context=ctx)
@@ -120,26 +113,12 @@ class RasterCompare(RasterFuse):
             raise IoError('The raster pair has been closed')
         config = self.create_config(**kwargs)
         device_config = RasterFuse.create_device_config(**(device_config or {}))
-        import os
-        devices = device_config['devices']
-        if devices is None:
-            devices = [int(os.environ.get('HOMONIM_AMD_DEVICE', os.environ.get('LOCAL_RANK', '0')))]
-        contexts = [_hk.get_context(dev, device_config['streams']) for dev in devices]
+        contexts = [_hk.get_context(dev, device_config['streams']) for dev in default_devices(device_config['devices'])]
         blocks = list(self.block_pairs(max_block_mem=config['max_block_mem'] or math.inf))
+        block_sums = self._run_blocks(blocks, lambda bp, wi: self._block_sums(bp, contexts[wi], config), contexts, config['threads'])
         image_sums = [dict.fromkeys(_SUM_KEYS, 0.) for _ in range(self._src.shape[0])]
-
-        def accumulate(bp, sums):
+        for bp, sums in zip(blocks, block_sums):  # block order: the accumulation is reproducible run to run
             acc = image_sums[bp.band_i]
             for k, v in sums.items():
                 acc[k] += v
-
-        if config['threads'] == 1 and len(contexts) == 1:
-            for bp in blocks:
-                accumulate(bp, self._block_sums(bp, contexts[0], config))
-        else:
-            with ThreadPoolExecutor(max_workers=max(config['threads'], len(contexts))) as ex:
-                futures = [(bp, ex.submit(self._block_sums, bp, contexts[i % len(contexts)], config))
-                           for i, bp in enumerate(blocks)]
-                for bp, f in futures:  # block order: the accumulation is reproducible run to run
-                    accumulate(bp, f.result())
         return self._get_image_stats(image_sums)

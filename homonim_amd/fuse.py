@@ -23,7 +23,7 @@ wavelength stays outside (GDAL).
 import math
 import os
 import threading
-from concurrent.futures import ThreadPoolExecutor, as_completed
+from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -277,6 +277,18 @@ def shard(items: Sequence, index: int, count: int, contiguous: bool = False) -> 
     return list(items[index::count])
 
 
+def _is_path(x) -> bool:
+    return isinstance(x, (str, os.PathLike))
+
+
+def default_devices(devices: Optional[Sequence[int]] = None) -> Sequence[int]:
+    """ The ``devices`` of a device configuration; None: the one device of this process -- HOMONIM_AMD_DEVICE, else the launcher's
+    LOCAL_RANK, else 0. """
+    if devices is None:
+        return [int(os.environ.get('HOMONIM_AMD_DEVICE', os.environ.get('LOCAL_RANK', '0')))]
+    return devices
+
+
 class RasterFuse:
     """
     Correct a source raster to surface reflectance by fusion with a reference raster.
@@ -305,32 +317,11 @@ class RasterFuse:
         image -- ``proc_crs=src``: the source, otherwise the reference -- is first warped into the other's CRS
         (``_to_one_crs``), with the reference's warning.
         """
-        from_file = any(isinstance(x, (str, os.PathLike)) for x in (src, ref))
-        inflater, lzw = _hk.block_decoders(inflate, _hk.default_context if from_file else None)
-        self._src_filename = self._ref_filename = None
-        self._ref_descriptions = ()   # band descriptions of a reference opened from a file (name the parameter bands)
-        if isinstance(src, (str, os.PathLike)):  # a GeoTIFF, as homonim.RasterFuse(src_filename, ref_filename, ...)
-            from homonim_amd.tiff import read_tiff
-            self._src_filename = os.fspath(src)
-            tif = read_tiff(src, inflater=inflater, lzw=lzw)
-            src, src_nodata, _ = dataset_masked(tif)
-            crs, transform = tif.crs, tif.transform
-        if isinstance(ref, (str, os.PathLike)):
-            from homonim_amd.tiff import read_tiff
-            self._ref_filename = os.fspath(ref)
-            tif = read_tiff(ref, inflater=inflater, lzw=lzw)
-            ref, ref_nodata, self._ref_descriptions = dataset_masked(tif)
-            ref_transform, ref_crs = tif.transform, tif.crs
-        if isinstance(src, RasterArray):
-            src, src_nodata, crs, transform = src.array, src.nodata, src.crs, src.transform
-        if isinstance(ref, RasterArray):
-            ref, ref_nodata, ref_transform, ref_crs = ref.array, ref.nodata, ref.transform, ref.crs
-        src = np.asarray(src)
-        ref = np.asarray(ref)
-        if src.ndim == 2:
-            src = src[None]
-        if ref.ndim == 2:
-            ref = ref[None]
+        decoders = _hk.block_decoders(inflate, _hk.default_context if (_is_path(src) or _is_path(ref)) else None)
+        src, src_nodata, crs, transform, self._src_filename, _ = self._open(src, src_nodata, crs, transform, decoders)
+        # (the band descriptions of a reference opened from a file name the parameter bands)
+        ref, ref_nodata, ref_crs, ref_transform, self._ref_filename, self._ref_descriptions = self._open(
+            ref, ref_nodata, ref_crs, ref_transform, decoders)
         if src.ndim != 3 or ref.ndim != 3:
             raise ValueError('`src` and `ref` must be 2-D or 3-D (bands first) arrays')
         # transforms may come as plain 6-tuples (a, b, c, d, e, f)
@@ -375,8 +366,24 @@ class RasterFuse:
         self._write_lock = threading.Lock()
 
     @staticmethod
+    def _open(x, nodata, crs, transform, decoders):
+        """ ``x`` -- a GeoTIFF path, a ``RasterArray`` or an array -- with the caller's nodata, CRS and geo-transform, which a file or
+        a ``RasterArray`` replaces by its own -> (array, nodata, crs, transform, filename, descriptions), a 2-D array made 3-D. """
+        filename, descriptions = None, ()
+        if _is_path(x):  # a GeoTIFF, as homonim.RasterFuse(src_filename, ref_filename, ...)
+            from homonim_amd.tiff import read_tiff
+            filename = os.fspath(x)
+            tif = read_tiff(x, inflater=decoders[0], lzw=decoders[1])
+            x, nodata, descriptions = dataset_masked(tif)
+            crs, transform = tif.crs, tif.transform
+        if isinstance(x, RasterArray):
+            x, nodata, crs, transform = x.array, x.nodata, x.crs, x.transform
+        x = np.asarray(x)
+        return (x[None] if x.ndim == 2 else x), nodata, crs, transform, filename, descriptions
+
+    @staticmethod
     def _device_context():
-        return _hk.get_context(int(os.environ.get('HOMONIM_AMD_DEVICE', os.environ.get('LOCAL_RANK', '0'))))
+        return _hk.get_context(default_devices()[0])
 
     @classmethod
     def _north_up_warp(cls, array, nodata, crs, transform):
@@ -515,44 +522,25 @@ class RasterFuse:
             out[r0 - win.row_off:r1 - win.row_off, c0 - win.col_off:c1 - win.col_off] = band[r0:r1, c0:c1]
         return out, fill
 
-    def _process_block_multires(self, bp: BlockPair, model: KernelModel, corr: np.ndarray, params: Optional[np.ndarray],
-                                out_nodata: Optional[float]):
-        """ read (boundless) -> fit on the processing grid -> apply on the source grid -> write the out-block
-        (homonim/fuse.py:295-319 with RefSpaceModel / SrcSpaceModel doing the re-sampling on the device) """
+    # -- the block loop -----------------------------------------------------------------------------------------------
+    @property
+    def _param_grid(self) -> Grid:
+        """ parameters live on the processing grid (homonim/fuse.py:254-293): the reference's when proc_crs == ref """
+        return self._ref_grid if (self._proc_crs == ProcCrs.ref and not self._same_grid) else self._src_grid
+
+    def _band_params(self, params: np.ndarray, band_i: int) -> np.ndarray:
+        """ the planes of band ``band_i`` in the parameter raster: parameter ``pi`` of band ``b`` is plane ``pi * n_src + b``, the band
+        order of the reference's parameter file (fuse.py:316) """
+        return params[band_i::self._src.shape[0]]
+
+    def _read_pair(self, bp: BlockPair) -> Tuple[RasterArray, RasterArray]:
+        """ the in-blocks of a pair in the rasters' own dtypes (boundless: a source in-block may reach beyond the image), their
+        transforms translated to the blocks (homonim/fuse.py:304) """
         s_arr, s_nd = self._read_boundless(self._src[bp.band_i], self._src_nodata, bp.src_in_block)
         r_arr, r_nd = self._read_boundless(self._ref[bp.band_i], self._ref_nodata, bp.ref_in_block)
         src_tf = self._transform * Affine.translation(bp.src_in_block.col_off, bp.src_in_block.row_off)
         ref_tf = self._ref_transform * Affine.translation(bp.ref_in_block.col_off, bp.ref_in_block.row_off)
-        # one upload / download per block in the rasters' own dtypes, everything else stays in HBM (RefSpaceModel and
-        # SrcSpaceModel alike: hk_refspace_fit_apply, hk_srcspace_fit_apply)
-        src_ra = RasterArray(s_arr, self._crs, src_tf, nodata=s_nd)
-        ref_ra = RasterArray(r_arr, self._crs, ref_tf, nodata=r_nd)
-        corr_ra, param_ra = model.fit_apply(src_ra, ref_ra, want_params=params is not None, out_dtype=corr.dtype.name,
-                                            out_nodata=out_nodata)
-
-        def put(dst_plane, block_arr, in_win, out_win):
-            h, w = dst_plane.shape
-            r0, c0 = max(out_win.row_off, 0), max(out_win.col_off, 0)
-            r1, c1 = min(out_win.row_off + out_win.height, h), min(out_win.col_off + out_win.width, w)
-            if r1 > r0 and c1 > c0:
-                dst_plane[r0:r1, c0:c1] = block_arr[r0 - in_win.row_off:r1 - in_win.row_off,
-                                                    c0 - in_win.col_off:c1 - in_win.col_off]
-
-        put(corr[bp.band_i], corr_ra.array, bp.src_in_block, bp.src_out_block)
-        if params is not None:
-            n_src = self._src.shape[0]
-            p_in, p_out = (bp.ref_in_block, bp.ref_out_block) if self._proc_crs == ProcCrs.ref else \
-                (bp.src_in_block, bp.src_out_block)
-            for pi in range(param_ra.count):
-                put(params[pi * n_src + bp.band_i], param_ra.array[pi], p_in, p_out)
-
-    # -- the block loop -----------------------------------------------------------------------------------------------
-    def _read(self, bp: BlockPair) -> Tuple[RasterArray, RasterArray]:
-        rs, cs = bp.src_in_block.toslices()
-        tf = self._transform * Affine.translation(bp.src_in_block.col_off, bp.src_in_block.row_off)
-        src_ra = RasterArray(self._src[bp.band_i][rs, cs], self._crs, tf, nodata=self._src_nodata)
-        ref_ra = RasterArray(self._ref[bp.band_i][rs, cs], self._crs, tf, nodata=self._ref_nodata)
-        return src_ra, ref_ra
+        return RasterArray(s_arr, self._crs, src_tf, nodata=s_nd), RasterArray(r_arr, self._crs, ref_tf, nodata=r_nd)
 
     @staticmethod
     def _crop(bp: BlockPair) -> Tuple[slice, slice]:
@@ -561,27 +549,42 @@ class RasterFuse:
         c0 = bp.src_out_block.col_off - bp.src_in_block.col_off
         return slice(r0, r0 + bp.src_out_block.height), slice(c0, c0 + bp.src_out_block.width)
 
+    @staticmethod
+    def _put(dst_plane: np.ndarray, block_arr: np.ndarray, in_win: Window, out_win: Window):
+        """ the out-block of a block read at ``in_win`` into a plane of an output raster, clipped to the plane (inside it: the
+        halo crop, ``dst_plane[out_win] = block_arr[_crop]``) """
+        h, w = dst_plane.shape
+        r0, c0 = max(out_win.row_off, 0), max(out_win.col_off, 0)
+        r1, c1 = min(out_win.row_off + out_win.height, h), min(out_win.col_off + out_win.width, w)
+        if r1 > r0 and c1 > c0:
+            dst_plane[r0:r1, c0:c1] = block_arr[r0 - in_win.row_off:r1 - in_win.row_off,
+                                                c0 - in_win.col_off:c1 - in_win.col_off]
+
     def _process_block(self, bp: BlockPair, model: KernelModel, corr: np.ndarray, params: Optional[np.ndarray],
                        out_nodata: Optional[float]):
-        """ read -> fused fit+apply (+ output dtype conversion) on the GPU -> write (homonim/fuse.py:295-319) """
-        src_ra, ref_ra = self._read(bp)
-        crop = self._crop(bp)
-        rs, cs = bp.src_out_block.toslices()
+        """ read -> fit + apply (+ output dtype conversion) on the GPU -> write the out-block (homonim/fuse.py:295-319): fused into one
+        kernel on a shared grid, across grids with RefSpaceModel / SrcSpaceModel doing the re-sampling on the device """
+        src_ra, ref_ra = self._read_pair(bp)
+        band_params = self._band_params(params, bp.band_i) if params is not None else None
         if model.fuses_into(src_ra, ref_ra):
             # the out-block goes straight from the device into the corrected / parameter rasters (no block-sized
             # temporaries, no host-side crop copy; asynchronous when the rasters are page-locked)
-            n_src = self._src.shape[0]
-            params_dst = params[bp.band_i::n_src][:, rs, cs] if params is not None else None
+            rs, cs = bp.src_out_block.toslices()
+            crop = self._crop(bp)
             window = (crop[0].start, crop[1].start, bp.src_out_block.height, bp.src_out_block.width)
-            model.fit_apply_into(src_ra, ref_ra, window, corr[bp.band_i][rs, cs], params_dst, out_nodata=out_nodata)
+            model.fit_apply_into(src_ra, ref_ra, window, corr[bp.band_i][rs, cs],
+                                 band_params[:, rs, cs] if params is not None else None, out_nodata=out_nodata)
             return
+        # one upload / download per block in the rasters' own dtypes, everything else stays in HBM (RefSpaceModel and
+        # SrcSpaceModel alike: hk_refspace_fit_apply, hk_srcspace_fit_apply)
         corr_ra, param_ra = model.fit_apply(src_ra, ref_ra, want_params=params is not None, out_dtype=corr.dtype.name,
                                             out_nodata=out_nodata)
-        corr[bp.band_i][rs, cs] = corr_ra.array[crop]
+        self._put(corr[bp.band_i], corr_ra.array, bp.src_in_block, bp.src_out_block)
         if params is not None:
-            n_src = self._src.shape[0]
-            for pi in range(param_ra.count):  # band order of the reference's parameter file (fuse.py:316)
-                params[pi * n_src + bp.band_i][rs, cs] = param_ra.array[pi][crop]
+            p_in, p_out = (bp.ref_in_block, bp.ref_out_block) if self._param_grid is self._ref_grid else \
+                (bp.src_in_block, bp.src_out_block)
+            for plane, block in zip(band_params, param_ra.array):
+                self._put(plane, block, p_in, p_out)
 
     def process(self, corr_filename: Optional[Union[str, os.PathLike]] = None, model: Model = KernelModel.default_model,
                 kernel_shape: Tuple[int, int] = KernelModel.default_kernel_shape,
@@ -619,10 +622,26 @@ class RasterFuse:
         out_profile = RasterFuse.create_out_profile(**(out_profile or {}))
         device_config = RasterFuse.create_device_config(**(device_config or {}))
         want_params = param_filename is not None and param_filename is not False
-        for fn in (corr_filename, param_filename):
-            if isinstance(fn, (str, os.PathLike)) and os.path.exists(fn) and not overwrite:
-                raise FileExistsError(f"Corrected / parameter file exists and won't be overwritten: {fn}")
+        out_dtype, nodata, write_options = self._resolve_output(corr_filename, param_filename, want_params, overwrite, out_profile)
+        models, own_contexts = self._build_models(model_type, kernel_shape, want_params, model_config, device_config)
+        n_param = models[0].n_param
+        corr, params = self._allocate(out_dtype, nodata, corr_out, n_param if want_params else 0)
+        blocks = list(self.block_pairs(overlap=overlap, max_block_mem=block_config['max_block_mem']))
+        blocks = shard(blocks, device_config['rank'], device_config['world_size'], device_config['contiguous'])
+        want_ovw = (build_ovw and self._is_tiff(corr_filename), build_ovw and want_params and self._is_tiff(param_filename))
+        overviews = self._run(blocks, models, own_contexts, corr, params, nodata, block_config['threads'], device_config['pin'],
+                              want_ovw)
+        compressor = models[0].context.deflate_tiles if device_config['deflate'] == 'device' else None
+        self._write(corr_filename, param_filename if want_params else None, corr, params, nodata, n_param, overviews,
+                    dict(model=model_type, kernel_shape=tuple(kernel_shape), **model_config), compressor, write_options)
+        return corr, params
 
+    def _resolve_output(self, corr_filename, param_filename, want_params: bool, overwrite: bool, out_profile: Dict):
+        """ -> (output dtype, output nodata, ``write_options`` or None) of a ``process`` call, which is refused here when a file exists
+        and is not to be overwritten, or when the profile asks for what cannot be written. """
+        for fn in (corr_filename, param_filename):
+            if _is_path(fn) and os.path.exists(fn) and not overwrite:
+                raise FileExistsError(f"Corrected / parameter file exists and won't be overwritten: {fn}")
         nodata = out_profile['nodata']
         out_dtype = np.dtype(out_profile['dtype'])
         if out_dtype.name not in _hk.DTYPE_CODES:
@@ -631,14 +650,14 @@ class RasterFuse:
         # the creation options shape .tif outputs only: with none to write they stay ignored
         tiff_dtypes = ([('the corrected file', out_dtype)] if self._is_tiff(corr_filename) else []) + \
                       ([('the parameter file', np.dtype(np.float32))] if want_params and self._is_tiff(param_filename) else [])
-        write_options = self._write_options(out_profile['creation_options'], tiff_dtypes) if tiff_dtypes else None
+        return out_dtype, nodata, (self._write_options(out_profile['creation_options'], tiff_dtypes) if tiff_dtypes else None)
 
+    def _build_models(self, model_type: Model, kernel_shape, want_params: bool, model_config: Dict, device_config: Dict):
+        """ -> (models, own_contexts): one model with its context per entry of ``devices``; ``own_contexts``: those made for this
+        call (``separate_contexts``), to be closed after it. """
         model_cls = SrcSpaceModel if self._proc_crs == ProcCrs.src else RefSpaceModel
-        devices = device_config['devices']
-        if devices is None:
-            devices = [int(os.environ.get('HOMONIM_AMD_DEVICE', os.environ.get('LOCAL_RANK', '0')))]
         models, own_contexts, seen = [], [], set()
-        for dev in devices:
+        for dev in default_devices(device_config['devices']):
             m = model_cls(model_type, kernel_shape, find_r2=want_params, **model_config)
             if device_config['separate_contexts'] and dev in seen:
                 m.context = _hk.Context(dev, device_config['streams'])  # a second, independent context on this device
@@ -647,58 +666,57 @@ class RasterFuse:
                 m.context = _hk.get_context(dev, device_config['streams'])  # cached per process
             seen.add(dev)
             models.append(m)
+        return models, own_contexts
 
+    def _allocate(self, out_dtype: np.dtype, nodata, corr_out: Optional[np.ndarray], n_param: int):
+        """ -> (corr, params): the corrected raster -- ``corr_out`` when given, else filled with nodata -- and the NaN-filled raster of
+        ``n_param`` parameters per band on ``_param_grid``, None for ``n_param`` 0. """
         n_src = self._src.shape[0]
-        fill = (np.nan if out_dtype.kind == 'f' else 0) if nodata is None else nodata
         if corr_out is not None:
             if corr_out.shape != (n_src, *self.shape) or corr_out.dtype != out_dtype or not corr_out.flags['C_CONTIGUOUS']:
                 raise ValueError('`corr_out` must be a C-contiguous (bands, height, width) array of the output dtype')
             corr = corr_out
         else:
+            fill = (np.nan if out_dtype.kind == 'f' else 0) if nodata is None else nodata
             corr = np.full((n_src, *self.shape), fill, dtype=out_dtype)
-        n_param = 3 if models[0]._emit_r2 else 2
-        # parameters live on the processing grid (homonim/fuse.py:254-293): the reference's when proc_crs == ref
-        param_shape = self._ref.shape[-2:] if (self._proc_crs == ProcCrs.ref and not self._same_grid) else self.shape
-        params = np.full((n_param * n_src, *param_shape), np.nan, dtype=np.float32) if want_params else None
-        process_block = self._process_block if self._same_grid else self._process_block_multires
+        grid = self._param_grid
+        params = np.full((n_param * n_src, grid.height, grid.width), np.nan, dtype=np.float32) if n_param else None
+        return corr, params
 
-        blocks = list(self.block_pairs(overlap=overlap, max_block_mem=block_config['max_block_mem']))
-        blocks = shard(blocks, device_config['rank'], device_config['world_size'], device_config['contiguous'])
+    def _run(self, blocks, models, own_contexts, corr, params, nodata, threads: int, pin: bool, want_ovw: Tuple[bool, bool]):
+        """ The block loop -> (corr_ovw, param_ovw): the internal overviews asked for by ``want_ovw``, else None. """
+        ctx = models[0].context
         # on request: page-lock the rasters in place for the duration of the block loop (direct copies); by default pageable
         # rasters go through the context's pinned staging ring (hk_api.hip stage_h2d / stage_d2h) block by block
-        pinned = self._pin(models[0].context, [self._src, self._ref, corr, params]) if device_config['pin'] else []
-        corr_ovw = param_ovw = None
+        pinned = self._pin(ctx, [self._src, self._ref, corr, params]) if pin else []
         try:
-            self._run_blocks(blocks, models, process_block, corr, params, nodata, block_config)
+            self._run_blocks(blocks, lambda bp, wi: self._process_block(bp, models[wi], corr, params, nodata),
+                             [m.context for m in models], threads)
             # internal overviews of the files to be written, while the rasters are still page-locked (direct copies)
-            if build_ovw and self._is_tiff(corr_filename):
-                corr_ovw = self._overviews(models[0].context, corr, nodata)
-            if build_ovw and want_params and self._is_tiff(param_filename):
-                param_ovw = self._overviews(models[0].context, params, float('nan'))
+            return (self._overviews(ctx, corr, nodata) if want_ovw[0] else None,
+                    self._overviews(ctx, params, float('nan')) if want_ovw[1] else None)
         finally:
             for arr in pinned:
                 try:
-                    models[0].context.unpin(arr)
+                    ctx.unpin(arr)
                 except Exception:
                     pass
             for c in own_contexts:
                 c.close()
 
-        if isinstance(corr_filename, (str, os.PathLike)) or (want_params and isinstance(param_filename, (str, os.PathLike))):
-            compressor = models[0].context.deflate_tiles if device_config['deflate'] == 'device' else None
-            # provenance tags of homonim/fuse.py:193-207
-            meta = dict(FUSE_SRC_FILE=os.path.basename(self._src_filename or 'memory'),
-                        FUSE_REF_FILE=os.path.basename(self._ref_filename or 'memory'), FUSE_PROC_CRS=self._proc_crs.name,
-                        FUSE_MODEL=model_type.name, FUSE_KERNEL_SHAPE=tuple(kernel_shape),
-                        **{f'FUSE_{k.upper()}': getattr(v, 'name', v) for k, v in model_config.items()})
-            if isinstance(corr_filename, (str, os.PathLike)):
-                self._save(corr_filename, corr, self._transform, nodata, meta, overviews=corr_ovw, compressor=compressor,
-                           write_options=write_options)
-            if want_params and isinstance(param_filename, (str, os.PathLike)):
-                param_tf = self._ref_transform if (self._proc_crs == ProcCrs.ref and not self._same_grid) else self._transform
-                self._save(param_filename, params, param_tf, float('nan'), meta, self._param_descriptions(n_param),
-                           overviews=param_ovw, compressor=compressor, write_options=write_options)
-        return corr, params
+    def _write(self, corr_filename, param_filename, corr, params, nodata, n_param: int, overviews, settings: Dict, compressor,
+               write_options: Optional[Dict]):
+        """ The rasters into the files that are paths, with the provenance tags of homonim/fuse.py:193-207 (``settings``: model, kernel
+        shape and model configuration of the run). """
+        meta = dict(FUSE_SRC_FILE=os.path.basename(self._src_filename or 'memory'),
+                    FUSE_REF_FILE=os.path.basename(self._ref_filename or 'memory'), FUSE_PROC_CRS=self._proc_crs.name,
+                    **{f'FUSE_{k.upper()}': getattr(v, 'name', v) for k, v in settings.items()})
+        if _is_path(corr_filename):
+            self._save(corr_filename, corr, self._transform, nodata, meta, overviews=overviews[0], compressor=compressor,
+                       write_options=write_options)
+        if _is_path(param_filename):
+            self._save(param_filename, params, self._param_grid.transform, float('nan'), meta, self._param_descriptions(n_param),
+                       overviews=overviews[1], compressor=compressor, write_options=write_options)
 
     @staticmethod
     def _write_options(creation_options: Dict, tiff_dtypes: Sequence[Tuple[str, np.dtype]]) -> Dict:
@@ -763,26 +781,26 @@ class RasterFuse:
         return done
 
     @staticmethod
-    def _run_blocks(blocks, models, process_block, corr, params, nodata, block_config):
-        if block_config['threads'] == 1 and len(models) == 1:
-            for bp in blocks:
-                process_block(bp, models[0], corr, params, nodata)
-        else:
-            workers = max(block_config['threads'], len(models))
-            several = len({m.context.device for m in models}) > 1
+    def _run_blocks(blocks, fn, contexts, threads: int) -> List:
+        """ ``fn(bp, worker_i)`` of every block, the results in block order.  Blocks are dealt round-robin to the workers, one per
+        context; one thread with one context is a plain loop, anything else a pool of max(threads, contexts) threads.  A worker's
+        exception is re-raised (fuse.py:404-408). """
+        n = len(contexts)
+        if threads == 1 and n == 1:
+            return [fn(bp, 0) for bp in blocks]
+        several = len({c.device for c in contexts}) > 1
 
-            def on_device(bp, model):
-                # several GPUs in one process: the worker that packs this block into a GPU's pinned staging ring runs on that GPU's
-                # NUMA node (topology.bind_current_thread; one process per GPU binds the whole process instead: dist / bench.py)
-                if several:
-                    from homonim_amd import topology
-                    topology.bind_current_thread(model.context.device)
-                return process_block(bp, model, corr, params, nodata)
+        def on_device(bp, worker_i):
+            # several GPUs in one process: the worker that packs this block into a GPU's pinned staging ring runs on that GPU's
+            # NUMA node (topology.bind_current_thread; one process per GPU binds the whole process instead: dist / bench.py)
+            if several:
+                from homonim_amd import topology
+                topology.bind_current_thread(contexts[worker_i].device)
+            return fn(bp, worker_i)
 
-            with ThreadPoolExecutor(max_workers=workers) as ex:
-                futures = [ex.submit(on_device, bp, models[i % len(models)]) for i, bp in enumerate(blocks)]
-                for f in as_completed(futures):
-                    f.result()  # re-raise worker exceptions (fuse.py:404-408)
+        with ThreadPoolExecutor(max_workers=max(threads, n)) as ex:
+            futures = [ex.submit(on_device, bp, i % n) for i, bp in enumerate(blocks)]
+            return [f.result() for f in futures]
 
     def _param_descriptions(self, n_param: int) -> List[str]:
         """ Band descriptions of the parameter file (homonim/fuse.py:241-248): ``<ref band>_GAIN``, ``_OFFSET``, ``_R2`` in the
@@ -793,7 +811,7 @@ class RasterFuse:
 
     @staticmethod
     def _is_tiff(filename) -> bool:
-        return isinstance(filename, (str, os.PathLike)) and os.fspath(filename).lower().endswith(('.tif', '.tiff'))
+        return _is_path(filename) and os.fspath(filename).lower().endswith(('.tif', '.tiff'))
 
     @staticmethod
     def _overviews(ctx, array: np.ndarray, nodata) -> Optional[List[np.ndarray]]:

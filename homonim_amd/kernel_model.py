@@ -93,6 +93,11 @@ class KernelModel:
         # kernel_model.py:252 (gain models) / :325 (gain-offset)
         return bool(self._find_r2 or (self._model == Model.gain_offset and self._r2_inpaint_thresh is not None))
 
+    @property
+    def n_param(self) -> int:
+        """ The bands of the parameters: gain, offset and, when R2 is emitted, R2. """
+        return 3 if self._emit_r2 else 2
+
     def _desc(self, src_ra: RasterArray, ref_ra: RasterArray):
         thresh = self._r2_inpaint_thresh if self._model == Model.gain_offset else None
         return _hk.make_desc(self._model, self._kernel_shape, self._find_r2, thresh, src_ra.nodata, ref_ra.nodata)
@@ -106,10 +111,15 @@ class KernelModel:
             arr = arr[0]
         return arr
 
-    def _param_profile(self, src_ra: RasterArray, count: int) -> Dict:
-        profile = src_ra.profile.copy()
-        profile.update(count=count, nodata=RasterArray.default_nodata, dtype=RasterArray.default_dtype)
-        return profile
+    @staticmethod
+    def _wrap(corr: np.ndarray, params: Optional[np.ndarray], src_ra: RasterArray, param_grid_ra: RasterArray,
+              out_nodata: Optional[float], want_params: bool) -> Tuple[RasterArray, Optional[RasterArray]]:
+        """ (corr_ra, param_ra | None) of the arrays a fused device call returned; count and dtype are the arrays' own.  The corrected
+        block: one band of the output dtype with nodata ``out_nodata`` on the source block's grid.  The parameters: ``n_param`` float32
+        bands with NaN nodata on ``param_grid_ra``'s grid -- the reference block for RefSpaceModel across grids, else the source block. """
+        grid = param_grid_ra
+        param_ra = RasterArray(params, grid.crs, grid.transform, nodata=RasterArray.default_nodata) if want_params else None
+        return RasterArray(corr, src_ra.crs, src_ra.transform, nodata=out_nodata), param_ra
 
     # -- the hot path -------------------------------------------------------------------------------------------------
     def fit(self, src_ra: RasterArray, ref_ra: RasterArray) -> RasterArray:
@@ -118,19 +128,16 @@ class KernelModel:
         Returns the parameters: gains in band 0, offsets in band 1 and, when ``find_r2`` (or gain-offset with an
         ``r2_inpaint_thresh``), R2 in band 2; NaN where either input is nodata.
         """
-        if (ref_ra.transform != src_ra.transform) or (ref_ra.shape != src_ra.shape):
-            raise ValueError("'ref_ra' and 'src_ra' must have the same CRS, transform and shape")
-        count = 3 if self._emit_r2 else 2
+        _require_shared_grid(ref_ra, src_ra, "'ref_ra' and 'src_ra'")
         params, _, _, n_fail = self.context.fit_apply(
-            self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), self._band(ref_ra, 'ref_ra'), count,
+            self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), self._band(ref_ra, 'ref_ra'), self.n_param,
             want_params=True, want_corr=False
         )
-        return RasterArray.from_profile(params, self._param_profile(src_ra, count))
+        return RasterArray(params, src_ra.crs, src_ra.transform, nodata=RasterArray.default_nodata)
 
     def apply(self, src_ra: RasterArray, param_ra: RasterArray) -> RasterArray:
         """ Corrected block = gain * source + offset (kernel_model.py:442-463). """
-        if (param_ra.transform != src_ra.transform) or (param_ra.shape != src_ra.shape):
-            raise ValueError("'param_ra' and 'src_ra' must have the same CRS, transform and shape")
+        _require_shared_grid(param_ra, src_ra, "'param_ra' and 'src_ra'")
         corr = self.context.apply(self._band(src_ra, 'src_ra'), param_ra.array)
         return RasterArray.from_profile(corr, param_ra.profile)
 
@@ -144,17 +151,12 @@ class KernelModel:
         ``out_dtype`` / ``out_nodata`` convert the corrected block on the device the way the reference converts it when
         writing (raster_array.py:353-387); integer ``src_ra`` / ``ref_ra`` arrays are converted to float32 on the device.
         """
-        if (ref_ra.transform != src_ra.transform) or (ref_ra.shape != src_ra.shape):
-            raise ValueError("'ref_ra' and 'src_ra' must have the same CRS, transform and shape")
-        count = 3 if self._emit_r2 else 2
+        _require_shared_grid(ref_ra, src_ra, "'ref_ra' and 'src_ra'")
         params, corr, _, n_fail = self.context.fit_apply(
-            self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), self._band(ref_ra, 'ref_ra'), count,
+            self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), self._band(ref_ra, 'ref_ra'), self.n_param,
             want_params=want_params, want_corr=True, out_dtype=out_dtype, out_nodata=out_nodata
         )
-        profile = self._param_profile(src_ra, count)
-        corr_profile = dict(profile, nodata=out_nodata, dtype=str(out_dtype))
-        corr_ra = RasterArray.from_profile(corr, corr_profile)
-        return corr_ra, (RasterArray.from_profile(params, profile) if want_params else None)
+        return self._wrap(corr, params, src_ra, src_ra, out_nodata, want_params)
 
     def fuses_into(self, src_ra: RasterArray, ref_ra: RasterArray) -> bool:
         """ True when ``fit_apply_into`` covers this model configuration for the pair (base-class fit + apply on a shared
@@ -171,8 +173,7 @@ class KernelModel:
         one download of the out-block, one stream synchronisation; asynchronous when the rasters are page-locked.
         Returns the number of pixels that failed the r2 mask.
         """
-        if not KernelModel.fuses_into(self, src_ra, ref_ra):
-            raise ValueError("'ref_ra' and 'src_ra' must have the same CRS, transform and shape")
+        _require_shared_grid(ref_ra, src_ra, "'ref_ra' and 'src_ra'")
         _, n_fail = self.context.fit_apply_block(
             self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), self._band(ref_ra, 'ref_ra'), window, corr_dst,
             params_dst, out_nodata=out_nodata
@@ -183,6 +184,12 @@ class KernelModel:
         """ The [gain, offset] block normalisation of gain-blk-offset (kernel_model.py:216-229), float64[2]. """
         return self.context.block_norm(self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'),
                                        self._band(ref_ra, 'ref_ra'))
+
+
+def _require_shared_grid(a: RasterArray, b: RasterArray, names: str):
+    """ The base-class fit / apply take one grid (kernel_model.py:411-463); ``names``: the two arguments as the message names them. """
+    if (a.transform != b.transform) or (a.shape != b.shape):
+        raise ValueError(f'{names} must have the same CRS, transform and shape')
 
 
 def _same_grid(a: RasterArray, b: RasterArray) -> bool:
@@ -272,16 +279,12 @@ class RefSpaceModel(KernelModel):
         _require_one_crs(src_ra, ref_ra)
         down = self._get_resampling(src_ra.res, ref_ra.res)
         up = self._get_resampling(ref_ra.res, src_ra.res)
-        count = 3 if self._emit_r2 else 2
         params, corr, _ = self.context.refspace_fit_apply(
             self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), self._band(ref_ra, 'ref_ra'),
             grid_mapping(src_ra.transform, ref_ra.transform), grid_mapping(ref_ra.transform, src_ra.transform), int(down),
-            int(up), self._mask_partial, count, want_params, out_dtype=out_dtype, out_nodata=out_nodata
+            int(up), self._mask_partial, self.n_param, want_params, out_dtype=out_dtype, out_nodata=out_nodata
         )
-        corr_profile = dict(self._param_profile(src_ra, 1), nodata=out_nodata, dtype=str(out_dtype))
-        corr_ra = RasterArray.from_profile(corr, corr_profile)
-        param_ra = RasterArray.from_profile(params, self._param_profile(ref_ra, count)) if want_params else None
-        return corr_ra, param_ra
+        return self._wrap(corr, params, src_ra, ref_ra, out_nodata, want_params)
 
 
 class SrcSpaceModel(KernelModel):
@@ -331,15 +334,12 @@ class SrcSpaceModel(KernelModel):
                 ref, ky, oy = ref[::-1, :], -ky, ref.shape[0] - oy
             if kx < 0:
                 ref, kx, ox = ref[:, ::-1], -kx, ref.shape[1] - ox
-            count = 3 if self._emit_r2 else 2
             params, corr, _ = self.context.srcspace_fit_apply(
                 self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), ref, (kx, ox, ky, oy),
-                int(self._get_resampling(ref_ra.res, src_ra.res)), self._mask_partial, count, want_params, out_dtype=out_dtype,
-                out_nodata=out_nodata
+                int(self._get_resampling(ref_ra.res, src_ra.res)), self._mask_partial, self.n_param, want_params,
+                out_dtype=out_dtype, out_nodata=out_nodata
             )
-            profile = self._param_profile(src_ra, count)
-            corr_ra = RasterArray.from_profile(corr, dict(profile, count=1, nodata=out_nodata, dtype=str(np.dtype(out_dtype))))
-            return corr_ra, (RasterArray.from_profile(params, profile) if want_params else None)
+            return self._wrap(corr, params, src_ra, src_ra, out_nodata, want_params)
         param_ra = self.fit(src_ra.copy(), ref_ra)
         corr_ra = self.apply(src_ra, param_ra)
         if np.dtype(out_dtype) != np.float32 or not (out_nodata is None or (isinstance(out_nodata, float) and np.isnan(out_nodata))):

@@ -12,6 +12,8 @@ comparison on the bits, NaN equal to NaN, no tolerance.
 (3) RasterCompare: with `nearest` both ways the seven sums of every partition and thread count equal the whole-image sums in integer
     arithmetic; with the default re-sampling ``process`` equals the block-order accumulation of ``Context.compare_sums`` over windows the
     helper cut and re-projected through the public ``RasterArray.reproject``.
+(4) The rasters ``fit_apply`` returns: count, dtype, nodata, transform and shape of the corrected block and of the parameters, for the
+    three model classes on one grid and across two.
 
 Shapes: at most 72 x 38 and 62 x 102 reference pixels under 70 x 90 and 24 x 40 source pixels, 16 blocks per band.  The last test
 prints the file's total time and its slowest test. """
@@ -23,8 +25,9 @@ import pytest
 
 import _process_blocks as pb
 from conftest import assert_same_f32
-from homonim_amd import CRS, Model, RasterArray, RasterCompare, RasterFuse, RefSpaceModel, SrcSpaceModel, _hk
+from homonim_amd import CRS, KernelModel, Model, RasterArray, RasterCompare, RasterFuse, RefSpaceModel, SrcSpaceModel, _hk
 from homonim_amd.enums import Resampling
+from homonim_amd.geo import Affine
 
 pytestmark = pytest.mark.gpu
 
@@ -289,6 +292,35 @@ def test_compare_with_default_resampling_equals_its_blocks(ctx, case_name, proc_
         stats = _compare(case_name, proc_crs).process(threads=threads, max_block_mem=mem)
     assert stats['Ref. band 1'] == exp
     assert exp['n'] > 100 and 0 < exp['r2'] < 1
+
+
+# -- 4: the rasters fit_apply returns ------------------------------------------------------------------------------------------------
+WRAP_SRC_TF = Affine(1., 0., 100., 0., -1., 200.)      # 24 x 24 source pixels of 1.0
+WRAP_REF_TF = Affine(2., 0., 100., 0., -2., 200.)      # 12 x 12 reference pixels of 2.0 over them
+WRAP_CASES = [(KernelModel, 'same')] + [(cls, grid) for cls in (RefSpaceModel, SrcSpaceModel) for grid in ('same', 'two')]
+
+
+@pytest.mark.parametrize('out_dtype, out_nodata', [('float32', float('nan')), ('uint16', 0)])
+@pytest.mark.parametrize('model_cls, grid', WRAP_CASES, ids=lambda v: v if isinstance(v, str) else v.__name__)
+def test_fit_apply_returns_rasters_with_the_stated_profiles(ctx, model_cls, grid, out_dtype, out_nodata):
+    """ the corrected block: one band of the output dtype and nodata on the source block's grid; the parameters: gain and offset,
+    float32 with NaN nodata, on the reference block's grid for RefSpaceModel across two grids and on the source block's otherwise """
+    rng = np.random.default_rng(7)
+    src = rng.uniform(50, 150, (24, 24)).astype(np.float32)
+    ref_shape, ref_tf = ((24, 24), WRAP_SRC_TF) if grid == 'same' else ((12, 12), WRAP_REF_TF)
+    ref = rng.uniform(60, 180, ref_shape).astype(np.float32)
+    km = model_cls(Model.gain, (3, 3))
+    corr_ra, param_ra = km.fit_apply(RasterArray(src, CRS(), WRAP_SRC_TF), RasterArray(ref, CRS(), ref_tf), want_params=True,
+                                     out_dtype=out_dtype, out_nodata=out_nodata)
+    assert (corr_ra.count, corr_ra.dtype, corr_ra.transform, corr_ra.shape) == (1, out_dtype, WRAP_SRC_TF, (24, 24))
+    assert corr_ra.array.dtype == np.dtype(out_dtype) and corr_ra.profile['dtype'] == out_dtype and corr_ra.profile['count'] == 1
+    assert corr_ra.nodata == 0 if out_dtype == 'uint16' else np.isnan(corr_ra.nodata)
+    on_ref = model_cls is RefSpaceModel and grid == 'two'
+    assert (param_ra.count, param_ra.dtype) == (2, 'float32') and np.isnan(param_ra.nodata)
+    assert param_ra.profile['count'] == 2 and param_ra.profile['dtype'] == 'float32'
+    assert (param_ra.transform, param_ra.shape) == ((WRAP_REF_TF, (12, 12)) if on_ref else (WRAP_SRC_TF, (24, 24)))
+    assert param_ra.array.shape == (2, *param_ra.shape) and np.isfinite(param_ra.array).any()
+    assert (np.isfinite(corr_ra.array) if out_dtype == 'float32' else corr_ra.array != 0).any()
 
 
 # -- timings ---------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """ The references of tests/_process_blocks.py, checked on the host before a GPU sees them: the window rule in rationals against
 ``fuse.block_pairs_multires`` (on the helper's geometries and on the dyadic cases of tests/golden/block_pairs_multires.json), reference
-(B) and the RasterCompare closed form against the oracle's own per-block composition over the helper's reader and placement, and
-``RasterFuse._read_boundless`` against the helper's reader. """
+(B) and the RasterCompare closed form against the oracle's own per-block composition over the helper's reader and placement,
+``RasterFuse._read_boundless`` against the helper's reader, and the pool of the block loop (``RasterFuse._run_blocks``) on a fake ``fn``. """
 import json
 import os
 import warnings
@@ -163,3 +163,45 @@ def test_read_boundless_against_the_helpers_reader(window, raster):
         assert exp_nd is nodata or exp_nd == nodata or (exp_nd != exp_nd and nodata != nodata)
     else:
         assert (exp_nd != exp_nd) if nan_fill else exp_nd == nodata
+
+
+# -- the pool ------------------------------------------------------------------------------------------------------------------------
+class _FakeContext:
+    device = 0      # (contexts on one device: no thread is bound to a NUMA node)
+
+
+@pytest.mark.parametrize('threads', [1, 4])
+def test_run_blocks_hands_the_results_back_in_block_order(threads):
+    import threading
+    third_done = threading.Event()
+
+    def fn(bp, worker_i):
+        if threads > 1 and bp == 0:      # with a pool the first block ends after the third: completion order is not block order
+            assert third_done.wait(30), 'the pool does not run four blocks at a time'
+        if bp == 2:
+            third_done.set()
+        return bp * 10, worker_i
+
+    got = fuse.RasterFuse._run_blocks(list(range(8)), fn, [_FakeContext()], threads)
+    assert got == [(bp * 10, 0) for bp in range(8)]
+
+
+@pytest.mark.parametrize('threads', [1, 4])
+def test_run_blocks_raises_what_a_worker_raised(threads):
+    ran = []
+
+    def fn(bp, worker_i):
+        ran.append(bp)
+        if bp == 2:                      # the third of eight
+            raise KeyError('block 2')
+        return bp
+
+    with pytest.raises(KeyError, match='block 2'):
+        fuse.RasterFuse._run_blocks(list(range(8)), fn, [_FakeContext()], threads)
+    assert 2 in ran and (threads > 1 or ran == [0, 1, 2])
+
+
+@pytest.mark.parametrize('threads', [1, 4])
+def test_run_blocks_deals_the_blocks_round_robin_to_two_contexts(threads):
+    got = fuse.RasterFuse._run_blocks(list(range(7)), lambda bp, worker_i: worker_i, [_FakeContext(), _FakeContext()], threads)
+    assert got == [i % 2 for i in range(7)]
