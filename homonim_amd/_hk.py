@@ -133,6 +133,12 @@ SIGNATURES = {
                                C.c_double, C.c_int32, _P(C.c_void_p), _P(C.c_int64), _P(C.c_int64)]),
     'hk_overviews_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                    C.c_int32, C.c_double, C.c_int32, _P(C.c_void_p), _P(C.c_int64), _P(C.c_int64), C.c_int32]),
+    'hk_overviews_valid': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                     _P(C.c_uint8), C.c_int64, C.c_int32, _P(C.c_void_p), _P(C.c_int64), _P(C.c_int64),
+                                     _P(C.c_void_p), _P(C.c_int64)]),
+    'hk_overviews_valid_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                         C.c_void_p, C.c_int64, C.c_int32, _P(C.c_void_p), _P(C.c_int64), _P(C.c_int64),
+                                         _P(C.c_void_p), _P(C.c_int64), C.c_int32]),
     'hk_dataset_mask': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                   C.c_int64, _f32p, C.c_int64]),
     'hk_dataset_mask_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
@@ -168,6 +174,12 @@ SIGNATURES = {
     'hk_srcspace_fit_apply': (C.c_int, [C.c_void_p, _P(FitDesc), _P(IoDesc), _P(SrcSpaceDesc), C.c_void_p, C.c_int64, C.c_int32,
                                         C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _f32p, C.c_int32,
                                         C.c_void_p, _u64p]),
+    'hk_refspace_fit_apply_valid': (C.c_int, [C.c_void_p, _P(FitDesc), _P(IoDesc), _P(SpaceDesc), C.c_void_p, C.c_int64, C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _f32p, C.c_int32,
+                                              C.c_void_p, C.c_void_p, _u64p]),
+    'hk_srcspace_fit_apply_valid': (C.c_int, [C.c_void_p, _P(FitDesc), _P(IoDesc), _P(SrcSpaceDesc), C.c_void_p, C.c_int64, C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _f32p, C.c_int32,
+                                              C.c_void_p, C.c_void_p, _u64p]),
     'hk_reproject': (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_double, C.c_double,
                                C.c_double, C.c_double, C.c_int32, _f32p, C.c_int32, C.c_int32, C.c_float]),
     'hk_reproject_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_float,
@@ -196,6 +208,9 @@ SIGNATURES = {
                                   C.c_int32, C.c_int32, _f64p, _f32p, C.c_int32, C.c_void_p, _f64p, _u64p]),
     'hk_fit_apply_block': (C.c_int, [C.c_void_p, _P(FitDesc), _P(IoDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                      C.c_int32, C.c_int32, _f64p, C.c_void_p, C.c_int32, C.c_void_p, _P(OutWindow), _f64p, _u64p]),
+    'hk_fit_apply_block_valid': (C.c_int, [C.c_void_p, _P(FitDesc), _P(IoDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                           C.c_int32, C.c_int32, _f64p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _P(OutWindow),
+                                           _f64p, _u64p]),
     'hk_host_alloc': (C.c_int, [C.c_void_p, C.c_size_t, _P(C.c_void_p)]),
     'hk_host_free': (C.c_int, [C.c_void_p, C.c_void_p]),
     'hk_host_register': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -618,11 +633,14 @@ class Context:
                                         _ptr(stats, _f64p)))
         return stats
 
-    def overviews(self, array: np.ndarray, nodata, n_levels: int) -> list:
+    def overviews(self, array: np.ndarray, nodata, n_levels: int, valid: Optional[np.ndarray] = None):
         """ Average overviews of a (bands, h, w) or (h, w) raster of any DTYPE_CODES dtype in host memory: ``n_levels`` arrays
         of the same rank and dtype, level m of shape (ceil(h / 2^m), ceil(w / 2^m)), each the clipped 2 x 2 mean of the
         valid pixels of the level before it (hk_overviews; all levels from one pass over the raster on the device).  Rows and
-        bands may be strided (unit column stride); anything else is copied first. """
+        bands may be strided (unit column stride); anything else is copied first.
+        ``valid``: an (h, w) uint8 or bool validity plane of the raster, valid where not 0, in place of ``nodata`` (which is then
+        not read): the masked build (hk_overviews_valid) -- a cell without a valid pixel gives 0 / NaN -- and the return value
+        becomes ``(levels, level_valids)``, level_valids[m - 1] the (h_m, w_m) uint8 validity of level m, 255 / 0. """
         arr = np.asarray(array)
         squeeze = arr.ndim == 2
         if squeeze:
@@ -634,17 +652,34 @@ class Context:
         arr, it = _unit_column_stride(arr)
         nb, h, w = arr.shape
         n_levels = int(n_levels)
+        if valid is not None:
+            valid = np.asarray(valid)
+            if valid.shape != (h, w) or valid.dtype not in (np.uint8, np.bool_):
+                raise ValueError(f'`valid` must be a uint8 or bool plane of the raster\'s shape {(h, w)}, not {valid.dtype} {valid.shape}')
+            if not 1 <= n_levels <= 31:
+                raise ValueError(f'`n_levels` must lie in 1..31, not {n_levels}')
+            valid = valid.view(np.uint8)
+            if valid.strides[1] != 1 or valid.strides[0] < w:
+                valid = np.ascontiguousarray(valid)
         if n_levels < 1:
             return []
         outs = [np.empty((nb, lh, lw), arr.dtype) for lh, lw in overview_shapes(h, w, n_levels)]
         ptrs = (C.c_void_p * n_levels)(*[o.ctypes.data for o in outs])
         strides = (C.c_int64 * n_levels)(*[o.shape[2] for o in outs])
         bstrides = (C.c_int64 * n_levels)(*[o.shape[1] * o.shape[2] for o in outs])
-        mode, value = nodata_code(nodata)
-        _check(self._lib.hk_overviews(self._h, arr.ctypes.data_as(C.c_void_p), DTYPE_CODES[arr.dtype.name], nb, h, w,
-                                      arr.strides[1] // it, arr.strides[0] // it if nb > 1 else 0, mode, value, n_levels, ptrs,
-                                      strides, bstrides))
-        return [o[0] for o in outs] if squeeze else outs
+        head = (self._h, arr.ctypes.data_as(C.c_void_p), DTYPE_CODES[arr.dtype.name], nb, h, w, arr.strides[1] // it,
+                arr.strides[0] // it if nb > 1 else 0)
+        levels = lambda: [o[0] for o in outs] if squeeze else outs   # noqa: E731
+        if valid is None:
+            mode, value = nodata_code(nodata)
+            _check(self._lib.hk_overviews(*head, mode, value, n_levels, ptrs, strides, bstrides))
+            return levels()
+        vouts = [np.empty(o.shape[1:], np.uint8) for o in outs]
+        vptrs = (C.c_void_p * n_levels)(*[o.ctypes.data for o in vouts])
+        vstrides = (C.c_int64 * n_levels)(*[o.shape[1] for o in vouts])
+        _check(self._lib.hk_overviews_valid(*head, valid.ctypes.data_as(_P(C.c_uint8)), valid.strides[0], n_levels, ptrs, strides,
+                                            bstrides, vptrs, vstrides))
+        return levels(), vouts
 
     def dataset_mask(self, array: np.ndarray, mask: Optional[np.ndarray] = None, alpha: Optional[np.ndarray] = None) -> np.ndarray:
         """ The per-dataset mask of a GeoTIFF applied to its bands (hk_dataset_mask): a (bands, h, w) or (h, w) raster of any
@@ -800,13 +835,16 @@ class Context:
 
     def fit_apply_block(self, desc: FitDesc, src: np.ndarray, ref: np.ndarray, window, corr_dst: Optional[np.ndarray],
                         params_dst: Optional[np.ndarray] = None, norm_in: Optional[np.ndarray] = None,
-                        out_nodata: Optional[float] = None):
+                        out_nodata: Optional[float] = None, valid_dst: Optional[np.ndarray] = None):
         """
         One block of RasterFuse.process (homonim/fuse.py:295-319) in one call: fit + apply on the read-block
         ``src`` / ``ref`` (2-D views, any dtype of DTYPE_CODES), and the window ``(row0, col0, rows, cols)`` of it -- the
         out-block -- written straight into ``corr_dst`` (2-D view of the caller's corrected raster where the out-block
         belongs, any DTYPE_CODES dtype, unit column stride) and ``params_dst`` (3-D view, float32).  With page-locked
         arrays (``pin`` / ``pinned_empty``) the transfers are asynchronous.  -> (norm, r2_fail_count)
+        ``valid_dst``: a (rows, cols) uint8 view, unit column stride, that receives the window's validity -- 255 where the float32
+        corrected value is not NaN, 0 where it is (hk_fit_apply_block_valid).  It needs ``corr_dst``, and its rows lie as many BYTES
+        apart as ``corr_dst``'s lie elements: both are windows of rasters of one width.
         """
         src, ref = _as_2d_native(src, 'src'), _as_2d_native(ref, 'ref')
         if src.shape != ref.shape:
@@ -836,17 +874,27 @@ class Context:
                 stride = pstride
         if out_dtype.name not in DTYPE_CODES:
             raise ValueError(f'unsupported output dtype {out_dtype}')
+        if valid_dst is not None:
+            if corr_dst is None:
+                raise ValueError('`valid_dst` needs `corr_dst`: validity is that of the corrected block')
+            if valid_dst.dtype != np.uint8 or valid_dst.shape != (rows, cols) or valid_dst.strides[1] != 1 or \
+                    (rows > 1 and valid_dst.strides[0] != stride):
+                raise ValueError('`valid_dst` must be a uint8 (rows, cols) view of the window with unit column stride whose rows '
+                                 f'lie {stride} bytes apart, `corr_dst`\'s row stride in elements')
         io = _io_desc(src, ref, out_dtype, out_nodata)
         win = OutWindow(stride, band_stride, row0, col0, rows, cols, pstride)
         norm = np.zeros(2, np.float64)
         fail = C.c_uint64(0)
         nin = np.ascontiguousarray(norm_in, dtype=np.float64) if norm_in is not None else None
-        _check(self._lib.hk_fit_apply_block(
-            self._h, C.byref(desc), C.byref(io), src.ctypes.data_as(vp), src.strides[0] // src.dtype.itemsize,
-            ref.ctypes.data_as(vp), ref.strides[0] // ref.dtype.itemsize, h, w,
-            _ptr(nin, _f64p) if nin is not None else None,
-            params_dst.ctypes.data_as(vp) if params_dst is not None else None, n_param,
-            corr_dst.ctypes.data_as(vp) if corr_dst is not None else None, C.byref(win), _ptr(norm, _f64p), C.byref(fail)))
+        head = (self._h, C.byref(desc), C.byref(io), src.ctypes.data_as(vp), src.strides[0] // src.dtype.itemsize,
+                ref.ctypes.data_as(vp), ref.strides[0] // ref.dtype.itemsize, h, w, _ptr(nin, _f64p) if nin is not None else None,
+                params_dst.ctypes.data_as(vp) if params_dst is not None else None, n_param,
+                corr_dst.ctypes.data_as(vp) if corr_dst is not None else None)
+        tail = (C.byref(win), _ptr(norm, _f64p), C.byref(fail))
+        if valid_dst is None:
+            _check(self._lib.hk_fit_apply_block(*head, *tail))
+        else:
+            _check(self._lib.hk_fit_apply_block_valid(*head, valid_dst.ctypes.data_as(vp), *tail))
         return norm, int(fail.value)
 
     def apply(self, src: np.ndarray, params: np.ndarray) -> np.ndarray:
@@ -862,9 +910,10 @@ class Context:
     def refspace_fit_apply(self, desc: FitDesc, src: np.ndarray, ref: np.ndarray, down, up, down_resampling: int,
                            up_resampling: int, mask_partial: bool, n_param_bands: int, want_params: bool,
                            out_dtype: str = 'float32', out_nodata: Optional[float] = None,
-                           out_corr: Optional[np.ndarray] = None):
+                           out_corr: Optional[np.ndarray] = None, want_valid: bool = False):
         """ hk_refspace_fit_apply: RefSpaceModel.fit + apply of one block pair on different grids, all on the device.
-        -> (params on the reference grid | None, corrected on the source grid, r2_fail_count) """
+        -> (params on the reference grid | None, corrected on the source grid, r2_fail_count), and with ``want_valid``
+        (hk_refspace_fit_apply_valid) a fourth: the uint8 validity of the corrected block, 255 where its float32 value is not NaN """
         src, ref = _as_2d_native(src, 'src'), _as_2d_native(ref, 'ref')
         out_dtype = np.dtype(out_dtype)
         io = _io_desc(src, ref, out_dtype, out_nodata)
@@ -877,18 +926,24 @@ class Context:
         assert corr.shape == src.shape and corr.dtype == out_dtype and corr.flags['C_CONTIGUOUS']
         fail = C.c_uint64(0)
         vp = C.c_void_p
-        _check(self._lib.hk_refspace_fit_apply(
-            self._h, C.byref(desc), C.byref(io), C.byref(sp), src.ctypes.data_as(vp), src.strides[0] // src.dtype.itemsize,
-            src.shape[0], src.shape[1], ref.ctypes.data_as(vp), ref.strides[0] // ref.dtype.itemsize, ref.shape[0],
-            ref.shape[1], _ptr(params) if want_params else None, n_param_bands, corr.ctypes.data_as(vp), C.byref(fail)))
-        return params, corr, int(fail.value)
+        head = (self._h, C.byref(desc), C.byref(io), C.byref(sp), src.ctypes.data_as(vp), src.strides[0] // src.dtype.itemsize,
+                src.shape[0], src.shape[1], ref.ctypes.data_as(vp), ref.strides[0] // ref.dtype.itemsize, ref.shape[0],
+                ref.shape[1], _ptr(params) if want_params else None, n_param_bands, corr.ctypes.data_as(vp))
+        if not want_valid:
+            _check(self._lib.hk_refspace_fit_apply(*head, C.byref(fail)))
+            return params, corr, int(fail.value)
+        valid = np.empty(src.shape, np.uint8)
+        _check(self._lib.hk_refspace_fit_apply_valid(*head, valid.ctypes.data_as(vp), C.byref(fail)))
+        return params, corr, int(fail.value), valid
 
     def srcspace_fit_apply(self, desc: FitDesc, src: np.ndarray, ref: np.ndarray, mapping, resampling: int, mask_partial: bool,
                            n_param_bands: int, want_params: bool, out_dtype: str = 'float32',
-                           out_nodata: Optional[float] = None, out_corr: Optional[np.ndarray] = None):
+                           out_nodata: Optional[float] = None, out_corr: Optional[np.ndarray] = None, want_valid: bool = False):
         """ hk_srcspace_fit_apply: SrcSpaceModel.fit + KernelModel.apply of one block pair on different grids, all on the device.
         ``mapping``: reference <- source grid as ``reproject`` takes it, both factors positive.  ``src`` / ``ref`` may be float32 or
-        any dtype of DTYPE_CODES.  -> (params on the source grid | None, corrected on the source grid, r2_fail_count) """
+        any dtype of DTYPE_CODES.  -> (params on the source grid | None, corrected on the source grid, r2_fail_count), and with
+        ``want_valid`` (hk_srcspace_fit_apply_valid) a fourth: the uint8 validity of the corrected block, 255 where its float32 value
+        is not NaN """
         src, ref = _as_2d_native(src, 'src'), _as_2d_native(ref, 'ref')
         out_dtype = np.dtype(out_dtype)
         if out_dtype.name not in DTYPE_CODES:
@@ -903,11 +958,15 @@ class Context:
         assert corr.shape == src.shape and corr.dtype == out_dtype and corr.flags['C_CONTIGUOUS']
         fail = C.c_uint64(0)
         vp = C.c_void_p
-        _check(self._lib.hk_srcspace_fit_apply(
-            self._h, C.byref(desc), C.byref(io), C.byref(sp), src.ctypes.data_as(vp), src.strides[0] // src.dtype.itemsize,
-            src.shape[0], src.shape[1], ref.ctypes.data_as(vp), ref.strides[0] // ref.dtype.itemsize, ref.shape[0],
-            ref.shape[1], _ptr(params) if want_params else None, n_param_bands, corr.ctypes.data_as(vp), C.byref(fail)))
-        return params, corr, int(fail.value)
+        head = (self._h, C.byref(desc), C.byref(io), C.byref(sp), src.ctypes.data_as(vp), src.strides[0] // src.dtype.itemsize,
+                src.shape[0], src.shape[1], ref.ctypes.data_as(vp), ref.strides[0] // ref.dtype.itemsize, ref.shape[0],
+                ref.shape[1], _ptr(params) if want_params else None, n_param_bands, corr.ctypes.data_as(vp))
+        if not want_valid:
+            _check(self._lib.hk_srcspace_fit_apply(*head, C.byref(fail)))
+            return params, corr, int(fail.value)
+        valid = np.empty(src.shape, np.uint8)
+        _check(self._lib.hk_srcspace_fit_apply_valid(*head, valid.ctypes.data_as(vp), C.byref(fail)))
+        return params, corr, int(fail.value), valid
 
     def reproject(self, src: np.ndarray, src_nodata, mapping, dst_shape, resampling: int, dst_fill: float) -> np.ndarray:
         """ hk_reproject: (bands, h, w) or (h, w) float32 -> same rank on the destination grid. """
@@ -1369,6 +1428,22 @@ class Context:
         _check(self._lib.hk_overviews_dev(self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height,
                                           width, stride, band_stride, mode, value, n, (C.c_void_p * n)(*out_dptrs),
                                           (C.c_int64 * n)(*out_strides), (C.c_int64 * n)(*out_band_strides), stream))
+
+    def overviews_valid_dev(self, planes_dptr: int, dtype: str, n_bands: int, height: int, width: int, stride: int, band_stride: int,
+                            valid_dptr: int, valid_stride: int, out_dptrs: Sequence[int], out_strides: Sequence[int],
+                            out_band_strides: Sequence[int], out_valid_dptrs: Sequence[int], out_valid_strides: Sequence[int],
+                            stream: int = 0):
+        """ ``overviews_dev`` under the device-resident uint8 validity plane ``valid_dptr`` (valid where not 0, ``valid_stride`` bytes
+        between rows) in place of a nodata value; level m's own validity (255 / 0) goes to ``out_valid_dptrs[m - 1]``
+        (hk_overviews_valid_dev; asynchronous). """
+        n = len(out_dptrs)
+        if len(out_valid_dptrs) != n or len(out_valid_strides) != n:
+            raise ValueError(f'{len(out_valid_dptrs)} validity planes for {n} levels')
+        _check(self._lib.hk_overviews_valid_dev(self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height,
+                                                width, stride, band_stride, C.c_void_p(valid_dptr), valid_stride, n,
+                                                (C.c_void_p * n)(*out_dptrs), (C.c_int64 * n)(*out_strides),
+                                                (C.c_int64 * n)(*out_band_strides), (C.c_void_p * n)(*out_valid_dptrs),
+                                                (C.c_int64 * n)(*out_valid_strides), stream))
 
     def dataset_mask_dev(self, planes_dptr: int, dtype: str, n_bands: int, height: int, width: int, stride: int, band_stride: int,
                          mask_dptr: int, mask_kind: int, mask_stride: int, out_dptr: int, out_stride: int, out_band_stride: int,

@@ -1206,8 +1206,10 @@ struct FitIo {
     int sdt = 0, rdt = 0, odt = 0, out_has_nodata = 0;
     double out_nodata = 0;
     bool out_cast = false, r2 = false;  // out_cast: the corrected plane goes through cast_out (another dtype, or an output nodata)
+    bool want_valid = false;            // ... through cast_out_valid, which writes the validity plane beside it (float32 included)
 };
-int check_fit_io(const hk_fit_desc* desc, const hk_io_desc* io, const float* params_out, int32_t n_param_bands, FitIo* f) {
+int check_fit_io(const hk_fit_desc* desc, const hk_io_desc* io, const float* params_out, int32_t n_param_bands, FitIo* f,
+                 const void* corr_out = nullptr, const uint8_t* valid_out = nullptr) {
     if (io) f->sdt = io->src_dtype, f->rdt = io->ref_dtype, f->odt = io->out_dtype;
     if (!hk::dtype_size(f->sdt) || !hk::dtype_size(f->rdt) || !hk::dtype_size(f->odt)) return fail(HK_ERR_ARG, "unknown dtype");
     if (io) {
@@ -1215,6 +1217,10 @@ int check_fit_io(const hk_fit_desc* desc, const hk_io_desc* io, const float* par
         if (rc) return rc;
         f->out_cast = f->odt != 0 || io->out_has_nodata;
         f->out_has_nodata = io->out_has_nodata, f->out_nodata = io->out_nodata;
+    }
+    if (valid_out) {
+        if (!corr_out) return fail(HK_ERR_ARG, "valid_out needs corr_out: validity is that of the corrected block");
+        f->want_valid = f->out_cast = true;
     }
     f->r2 = needs_r2(desc);
     if (params_out && n_param_bands != (f->r2 ? 3 : 2))
@@ -1239,6 +1245,8 @@ struct FitResults {
     int64_t d_stride;
     int32_t height, width;
     hk_out_window cw;         // ... and its window into corr_out
+    uint8_t* valid_out = nullptr;        // nullable: the validity of the corrected plane (255 / 0), the same window and row stride, ...
+    unsigned char* d_valid = nullptr;    // ... on the device rows d_stride bytes apart (FitIo::want_valid)
 };
 // queues the copies of both, and behind them the r2-mask failure counter (nullable d_fail) into the slot's pinned word
 int stage_fit_results(Slot& sl, const FitIo& f, const FitResults& r, const unsigned long long* d_fail) {
@@ -1254,13 +1262,17 @@ int stage_fit_results(Slot& sl, const FitIo& f, const FitResults& r, const unsig
         const size_t es = hk::dtype_size(f.odt);  // (4 without a cast: the output is float32 then)
         const char* d_out = reinterpret_cast<const char*>(r.d_corr);
         if (f.out_cast) {
-            HK_HIP(hk::launch_cast_out(f.odt, {.in = r.d_corr, .in_stride = r.d_stride, .out = r.d_raw, .out_stride = r.d_stride,
-                                               .height = r.height, .width = r.width, .has_nodata = f.out_has_nodata, .nodata = f.out_nodata},
-                                       sl.stream));
+            const hk::CastPlane cp = {.in = r.d_corr, .in_stride = r.d_stride, .out = r.d_raw, .out_stride = r.d_stride,
+                                      .height = r.height, .width = r.width, .has_nodata = f.out_has_nodata, .nodata = f.out_nodata,
+                                      .valid = r.d_valid, .valid_stride = r.d_stride};
+            HK_HIP(f.want_valid ? hk::launch_cast_out_valid(f.odt, cp, sl.stream) : hk::launch_cast_out(f.odt, cp, sl.stream));
             d_out = static_cast<const char*>(r.d_raw);
         }
         if ((rc = stage_d2h(sl, r.corr_out, cw.stride * es, d_out + ((size_t)cw.row0 * r.d_stride + cw.col0) * es, r.d_stride * es,
                             (size_t)cw.cols * es, cw.rows)))
+            return rc;
+        if (f.want_valid &&
+            (rc = stage_d2h(sl, r.valid_out, cw.stride, r.d_valid + (size_t)cw.row0 * r.d_stride + cw.col0, r.d_stride, cw.cols, cw.rows)))
             return rc;
     }
     if (d_fail) HK_HIP(hipMemcpyAsync(sl.fail_host, d_fail, sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
@@ -1343,6 +1355,7 @@ struct HostFit {
     uint64_t* r2_fail_count = nullptr;
     bool norm_only = false;  // hk_block_norm: the block statistics alone
     const hk_out_window* window = nullptr;
+    uint8_t* valid_out = nullptr;  // nullable: the validity of the corrected window, rows window->stride bytes apart (packed without one)
 };
 
 // The whole host-pointer path: stage in (+ typed -> float32), (norm), fused kernel, (float32 -> typed) stage out.
@@ -1356,7 +1369,7 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const H
     if (height < 1 || width < 1) return fail(HK_ERR_ARG, "empty raster %d x %d", height, width);
     if ((rc = check_strides(c.src_stride, width, c.ref_stride, width))) return rc;
     FitIo f;
-    if ((rc = check_fit_io(desc, io, c.params_out, c.n_param_bands, &f))) return rc;
+    if ((rc = check_fit_io(desc, io, c.params_out, c.n_param_bands, &f, c.corr_out, c.valid_out))) return rc;
     if (!c.norm_only && !c.params_out && !c.corr_out) return fail(HK_ERR_ARG, "nothing to compute: params_out and corr_out are NULL");
     // output window (defaults: the whole block, written packed); param_stride is resolved to the row stride of params_out
     hk_out_window win = c.window ? *c.window : whole_block(height, width);
@@ -1383,6 +1396,7 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const H
     const size_t o_r2 = (want_par && c.n_param_bands == 3) ? L.take(plane) : 0;
     const size_t o_corr = want_corr ? L.take(plane) : 0;
     const size_t o_raw_o = (want_corr && f.out_cast) ? L.take((size_t)stride * height * hk::dtype_size(f.odt)) : 0;
+    const size_t o_valid = (want_corr && f.want_valid) ? L.take((size_t)stride * height) : 0;
     const size_t o_raw_s = f.sdt ? L.take((size_t)stride * height * hk::dtype_size(f.sdt)) : 0;
     const size_t o_raw_r = f.rdt ? L.take((size_t)stride * height * hk::dtype_size(f.rdt)) : 0;
     const size_t o_aux = L.take(256);
@@ -1413,7 +1427,8 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const H
     // plane apart in the slab
     const FitResults res = {.params_out = c.params_out, .n_param_bands = c.n_param_bands, .d_par = d_gain, .d_par_stride = stride,
                             .d_par_band = (int64_t)(o_off - o_gain) / 4, .pw = win, .corr_out = c.corr_out, .d_corr = d_corr,
-                            .d_raw = hc.at(o_raw_o), .d_stride = stride, .height = height, .width = width, .cw = win};
+                            .d_raw = hc.at(o_raw_o), .d_stride = stride, .height = height, .width = width, .cw = win,
+                            .valid_out = c.valid_out, .d_valid = hc.at<unsigned char>(o_valid)};
 
     // The fit, its outputs and its r2-mask counter are queued back to back and the stream is synchronised ONCE; only
     // when pixels failed the mask do the in-painting passes follow, and the outputs are copied again behind them.
@@ -1582,13 +1597,22 @@ int hk_fit_apply_io(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, 
                                     .corr_out = corr_out, .norm_out = norm_out, .r2_fail_count = r2_fail_count});
 }
 
+int hk_fit_apply_block_valid(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const void* src, int64_t src_stride,
+                             const void* ref, int64_t ref_stride, int32_t height, int32_t width, const double* norm_in,
+                             float* params_out, int32_t n_param_bands, void* corr_out, uint8_t* valid_out,
+                             const hk_out_window* window, double* norm_out, uint64_t* r2_fail_count) {
+    return run_host(ctx, desc, io, {.src = src, .src_stride = src_stride, .ref = ref, .ref_stride = ref_stride, .height = height,
+                                    .width = width, .norm_in = norm_in, .params_out = params_out, .n_param_bands = n_param_bands,
+                                    .corr_out = corr_out, .norm_out = norm_out, .r2_fail_count = r2_fail_count, .window = window,
+                                    .valid_out = valid_out});
+}
+
 int hk_fit_apply_block(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const void* src, int64_t src_stride,
                        const void* ref, int64_t ref_stride, int32_t height, int32_t width, const double* norm_in,
                        float* params_out, int32_t n_param_bands, void* corr_out, const hk_out_window* window,
                        double* norm_out, uint64_t* r2_fail_count) {
-    return run_host(ctx, desc, io, {.src = src, .src_stride = src_stride, .ref = ref, .ref_stride = ref_stride, .height = height,
-                                    .width = width, .norm_in = norm_in, .params_out = params_out, .n_param_bands = n_param_bands,
-                                    .corr_out = corr_out, .norm_out = norm_out, .r2_fail_count = r2_fail_count, .window = window});
+    return hk_fit_apply_block_valid(ctx, desc, io, src, src_stride, ref, ref_stride, height, width, norm_in, params_out,
+                                    n_param_bands, corr_out, /*valid_out=*/nullptr, window, norm_out, r2_fail_count);
 }
 
 int hk_apply(hk_ctx* ctx, const float* src, int64_t src_stride, const float* params, int32_t height, int32_t width,
@@ -1615,10 +1639,10 @@ int hk_apply(hk_ctx* ctx, const float* src, int64_t src_stride, const float* par
     return stage_finish(hc.sl);
 }
 
-int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_space_desc* space,
-                          const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
-                          int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
-                          int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count) {
+int hk_refspace_fit_apply_valid(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_space_desc* space,
+                                const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
+                                int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
+                                int32_t n_param_bands, void* corr_out, uint8_t* valid_out, uint64_t* r2_fail_count) {
     const HostGrid sg = {src, src_stride, src_height, src_width}, rg = {ref, ref_stride, ref_height, ref_width};
     int rc = check_two_grids(ctx, desc, space, sg, rg, corr_out);
     if (rc) return rc;
@@ -1627,7 +1651,7 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     if (!(space->down[0] > 0 && space->down[2] > 0 && space->up[0] > 0 && space->up[2] > 0))
         return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
     FitIo f;
-    if ((rc = check_fit_io(desc, io, params_out, n_param_bands, &f))) return rc;
+    if ((rc = check_fit_io(desc, io, params_out, n_param_bands, &f, corr_out, valid_out))) return rc;
     HK_ENTER(ctx);
 
     const int64_t ss = row_align(sg.width), rs = row_align(rg.width);  // row strides of the source and the reference grid
@@ -1648,6 +1672,7 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     const size_t o_raw_s = f.sdt ? L.take((size_t)ss * sg.height * hk::dtype_size(f.sdt)) : 0;
     const size_t o_raw_r = f.rdt ? L.take((size_t)rs * rg.height * hk::dtype_size(f.rdt)) : 0;
     const size_t o_raw_o = f.out_cast ? L.take((size_t)ss * sg.height * hk::dtype_size(f.odt)) : 0;
+    const size_t o_valid = f.want_valid ? L.take((size_t)ss * sg.height) : 0;
     const size_t o_aux = L.take(256);
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
     const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, rg.height, rg.width)) : 0;
@@ -1723,24 +1748,32 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     const FitResults res = {.params_out = params_out, .n_param_bands = n_param_bands, .d_par = d_gain, .d_par_stride = rs,
                             .d_par_band = par_band, .pw = whole_block(ref_height, ref_width), .corr_out = corr_out, .d_corr = d_corr,
                             .d_raw = hc.at(o_raw_o), .d_stride = ss, .height = src_height, .width = src_width,
-                            .cw = whole_block(src_height, src_width)};
+                            .cw = whole_block(src_height, src_width), .valid_out = valid_out, .d_valid = hc.at<unsigned char>(o_valid)};
     if ((rc = stage_fit_results(sl, f, res, d_fail))) return rc;
     if ((rc = stage_finish(sl))) return rc;
     if (r2_fail_count) *r2_fail_count = *sl.fail_host;
     return HK_OK;
 }
 
-int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_srcspace_desc* space,
+int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_space_desc* space,
                           const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
                           int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
                           int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count) {
+    return hk_refspace_fit_apply_valid(ctx, desc, io, space, src, src_stride, src_height, src_width, ref, ref_stride, ref_height,
+                                       ref_width, params_out, n_param_bands, corr_out, /*valid_out=*/nullptr, r2_fail_count);
+}
+
+int hk_srcspace_fit_apply_valid(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_srcspace_desc* space,
+                                const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
+                                int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
+                                int32_t n_param_bands, void* corr_out, uint8_t* valid_out, uint64_t* r2_fail_count) {
     const HostGrid sg = {src, src_stride, src_height, src_width}, rg = {ref, ref_stride, ref_height, ref_width};
     int rc = check_two_grids(ctx, desc, space, sg, rg, corr_out);
     if (rc) return rc;
     if (!resampling_built(space->resampling)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not built", space->resampling);
     if (!(space->map[0] > 0 && space->map[2] > 0)) return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
     FitIo f;
-    if ((rc = check_fit_io(desc, io, params_out, n_param_bands, &f))) return rc;
+    if ((rc = check_fit_io(desc, io, params_out, n_param_bands, &f, corr_out, valid_out))) return rc;
     const bool r2 = f.r2, partial = space->mask_partial != 0;
     HK_ENTER(ctx);
 
@@ -1762,6 +1795,7 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     const size_t o_raw_s = f.sdt ? L.take((size_t)ss * sg.height * hk::dtype_size(f.sdt)) : 0;
     const size_t o_raw_r = f.rdt ? L.take((size_t)rs * rg.height * hk::dtype_size(f.rdt)) : 0;
     const size_t o_raw_o = f.out_cast ? L.take((size_t)ss * sg.height * hk::dtype_size(f.odt)) : 0;
+    const size_t o_valid = f.want_valid ? L.take((size_t)ss * sg.height) : 0;
     const size_t o_aux = L.take(256);
     const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
     const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, sg.height, sg.width)) : 0;
@@ -1828,11 +1862,20 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
     const hk_out_window whole = whole_block(src_height, src_width);
     const FitResults res = {.params_out = params_out, .n_param_bands = n_param_bands, .d_par = d_pout, .d_par_stride = ss,
                             .d_par_band = pbs, .pw = whole, .corr_out = corr_out, .d_corr = d_corr, .d_raw = hc.at(o_raw_o),
-                            .d_stride = ss, .height = src_height, .width = src_width, .cw = whole};
+                            .d_stride = ss, .height = src_height, .width = src_width, .cw = whole, .valid_out = valid_out,
+                            .d_valid = hc.at<unsigned char>(o_valid)};
     if ((rc = stage_fit_results(sl, f, res, d_fail))) return rc;
     if ((rc = stage_finish(sl))) return rc;
     if (r2_fail_count) *r2_fail_count = *sl.fail_host;
     return HK_OK;
+}
+
+int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_srcspace_desc* space,
+                          const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
+                          int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
+                          int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count) {
+    return hk_srcspace_fit_apply_valid(ctx, desc, io, space, src, src_stride, src_height, src_width, ref, ref_stride, ref_height,
+                                       ref_width, params_out, n_param_bands, corr_out, /*valid_out=*/nullptr, r2_fail_count);
 }
 
 int hk_reproject(hk_ctx* ctx, const float* src, int32_t n_bands, int32_t src_height, int32_t src_width,
@@ -2496,6 +2539,19 @@ static int check_overviews(hk_ctx* ctx, int32_t dtype, const hk::OverviewLevels&
         return fail(HK_ERR_ARG, "nodata %g is not a value of the integer sample type", r.nodata);
     return HK_OK;
 }
+// ... and of the masked forms: the raster's validity plane and one validity plane per level, strides in bytes
+static int check_overviews_valid(hk_ctx* ctx, int32_t dtype, const hk::OverviewLevels& r) {
+    int rc = check_overviews(ctx, dtype, r);
+    if (rc) return rc;
+    if (!r.valid || !r.out_valid || !r.out_valid_stride) return null_arg();
+    if ((rc = check_strides(r.valid_stride, r.planes.width))) return rc;
+    for (int m = 1; m <= r.n_levels; ++m) {
+        const int64_t wm = ((int64_t)r.planes.width + (1ll << m) - 1) >> m;
+        if (!r.out_valid[m - 1]) return fail(HK_ERR_ARG, "level %d: NULL validity plane", m);
+        if (r.out_valid_stride[m - 1] < wm) return fail(HK_ERR_ARG, "level %d: validity row stride smaller than its width %lld", m, (long long)wm);
+    }
+    return HK_OK;
+}
 
 int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
                      int64_t stride, int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels,
@@ -2506,6 +2562,25 @@ int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t
                                   .out_stride = reinterpret_cast<const long long*>(out_stride),
                                   .out_band_stride = reinterpret_cast<const long long*>(out_band_stride)};
     int rc = check_overviews(ctx, dtype, r);
+    if (rc || (rc = check_stream(ctx, stream))) return rc;
+    DevEnter entered(ctx, stream);
+    HK_ENTER(ctx);
+    HK_HIP(hk::launch_overviews(dtype, r, ctx->slots[stream].stream));
+    return HK_OK;
+}
+
+int hk_overviews_valid_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                           int64_t stride, int64_t band_stride, const uint8_t* valid_dev, int64_t valid_stride, int32_t n_levels,
+                           void* const out_dev[], const int64_t out_stride[], const int64_t out_band_stride[],
+                           uint8_t* const out_valid_dev[], const int64_t out_valid_stride[], int32_t stream) {
+    const hk::OverviewLevels r = {.planes = {.src = planes_dev, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
+                                             .band_stride = band_stride},
+                                  .nd_mode = HK_NODATA_NONE, .nodata = 0., .n_levels = n_levels, .out = out_dev,
+                                  .out_stride = reinterpret_cast<const long long*>(out_stride),
+                                  .out_band_stride = reinterpret_cast<const long long*>(out_band_stride), .valid = valid_dev,
+                                  .valid_stride = valid_stride, .out_valid = out_valid_dev,
+                                  .out_valid_stride = reinterpret_cast<const long long*>(out_valid_stride)};
+    int rc = check_overviews_valid(ctx, dtype, r);
     if (rc || (rc = check_stream(ctx, stream))) return rc;
     DevEnter entered(ctx, stream);
     HK_ENTER(ctx);
@@ -2525,15 +2600,15 @@ static int64_t overview_strip_rows(int32_t n_bands, int32_t height, int32_t widt
     return rows < unit ? unit : rows;
 }
 
-int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
-                 int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels, void* const out[],
-                 const int64_t out_stride[], const int64_t out_band_stride[]) {
-    const hk::OverviewLevels host = {.planes = {.src = planes, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
-                                                .band_stride = band_stride},
-                                     .nd_mode = nodata_mode, .nodata = nodata, .n_levels = n_levels, .out = out,
-                                     .out_stride = reinterpret_cast<const long long*>(out_stride),
-                                     .out_band_stride = reinterpret_cast<const long long*>(out_band_stride)};
-    int rc = check_overviews(ctx, dtype, host);
+// The body of hk_overviews and hk_overviews_valid: `host` names the caller's arrays, with host.valid the masked form
+static int overviews_host(hk_ctx* ctx, int32_t dtype, const hk::OverviewLevels& host) {
+    const void* planes = host.planes.src;
+    const int32_t n_bands = host.planes.n_bands, height = host.planes.height, width = host.planes.width, n_levels = host.n_levels;
+    const int64_t stride = host.planes.stride, band_stride = host.planes.band_stride;
+    void* const* out = host.out;
+    const long long *out_stride = host.out_stride, *out_band_stride = host.out_band_stride;
+    const bool masked = host.valid != nullptr;
+    int rc = masked ? check_overviews_valid(ctx, dtype, host) : check_overviews(ctx, dtype, host);
     if (rc) return rc;
     HK_ENTER(ctx);
     const size_t es = hk::dtype_size(dtype);
@@ -2551,12 +2626,18 @@ int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands
         l_band[m - 1] = l_stride[m - 1] * ceil_shift(rows_max, m);
         o_lev[m - 1] = L.take((size_t)n_bands * l_band[m - 1] * es);
     }
+    // ... and in the masked form the strip's validity plane and every level's, one byte per pixel on the same row strides
+    const size_t o_val = masked ? L.take((size_t)rows_max * d_stride) : 0;
+    size_t o_lval[OVERVIEW_MAX_LEVELS];
+    for (int m = 1; masked && m <= n_levels; ++m) o_lval[m - 1] = L.take((size_t)l_band[m - 1]);
     HostCall hc(ctx, L.total);
     if (hc.rc) return hc.rc;
     Slot& sl = hc.sl;
     char* const base = hc.at(0);
     void* d_out[OVERVIEW_MAX_LEVELS];
+    unsigned char* d_out_valid[OVERVIEW_MAX_LEVELS];
     for (int m = 1; m <= n_levels; ++m) d_out[m - 1] = base + o_lev[m - 1];
+    for (int m = 1; masked && m <= n_levels; ++m) d_out_valid[m - 1] = reinterpret_cast<unsigned char*>(base + o_lval[m - 1]);
     const char* h_src = static_cast<const char*>(planes);
     for (int64_t r0 = 0; r0 < height; r0 += strip) {
         const int64_t rows = std::min<int64_t>(strip, height - r0);
@@ -2564,10 +2645,16 @@ int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands
             if ((rc = stage_h2d(sl, base + o_src + (size_t)b * rows_max * d_stride * es, d_stride * es,
                                 h_src + ((size_t)b * band_stride + (size_t)r0 * stride) * es, stride * es, (size_t)width * es, rows)))
                 return rc;
+        if (masked && (rc = stage_h2d(sl, base + o_val, d_stride, host.valid + (size_t)r0 * host.valid_stride, host.valid_stride, width, rows)))
+            return rc;
         hk::OverviewLevels slab = host;  // this strip on the device
         slab.planes = {.src = base + o_src, .n_bands = n_bands, .height = (int)rows, .width = width, .stride = d_stride,
                        .band_stride = rows_max * d_stride};
         slab.out = d_out, slab.out_stride = l_stride, slab.out_band_stride = l_band;
+        if (masked) {
+            slab.valid = reinterpret_cast<const unsigned char*>(base + o_val), slab.valid_stride = d_stride;
+            slab.out_valid = d_out_valid, slab.out_valid_stride = l_stride;
+        }
         HK_HIP(hk::launch_overviews(dtype, slab, sl.stream));
         for (int m = 1; m <= n_levels; ++m) {
             char* h_out = static_cast<char*>(out[m - 1]);
@@ -2576,9 +2663,37 @@ int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands
                                     out_stride[m - 1] * es, base + o_lev[m - 1] + (size_t)b * l_band[m - 1] * es,
                                     l_stride[m - 1] * es, (size_t)ceil_shift(width, m) * es, ceil_shift(rows, m))))
                     return rc;
+            if (masked && (rc = stage_d2h(sl, host.out_valid[m - 1] + (size_t)(r0 >> m) * host.out_valid_stride[m - 1],
+                                          host.out_valid_stride[m - 1], d_out_valid[m - 1], l_stride[m - 1], ceil_shift(width, m),
+                                          ceil_shift(rows, m))))
+                return rc;
         }
     }
     return stage_finish(sl);
+}
+
+int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                 int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels, void* const out[],
+                 const int64_t out_stride[], const int64_t out_band_stride[]) {
+    return overviews_host(ctx, dtype, {.planes = {.src = planes, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
+                                                  .band_stride = band_stride},
+                                       .nd_mode = nodata_mode, .nodata = nodata, .n_levels = n_levels, .out = out,
+                                       .out_stride = reinterpret_cast<const long long*>(out_stride),
+                                       .out_band_stride = reinterpret_cast<const long long*>(out_band_stride)});
+}
+
+int hk_overviews_valid(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                       int64_t band_stride, const uint8_t* valid, int64_t valid_stride, int32_t n_levels, void* const out[],
+                       const int64_t out_stride[], const int64_t out_band_stride[], uint8_t* const out_valid[],
+                       const int64_t out_valid_stride[]) {
+    if (!valid) return null_arg();
+    return overviews_host(ctx, dtype, {.planes = {.src = planes, .n_bands = n_bands, .height = height, .width = width, .stride = stride,
+                                                  .band_stride = band_stride},
+                                       .nd_mode = HK_NODATA_NONE, .nodata = 0., .n_levels = n_levels, .out = out,
+                                       .out_stride = reinterpret_cast<const long long*>(out_stride),
+                                       .out_band_stride = reinterpret_cast<const long long*>(out_band_stride), .valid = valid,
+                                       .valid_stride = valid_stride, .out_valid = out_valid,
+                                       .out_valid_stride = reinterpret_cast<const long long*>(out_valid_stride)});
 }
 
 // The per-dataset mask of a GeoTIFF applied to its bands (hk_dataset_mask.hip): see include/homonim_hk.h

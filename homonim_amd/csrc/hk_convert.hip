@@ -36,11 +36,30 @@ template <> struct OutTraits<int>            { static constexpr double lo = -214
 template <> struct OutTraits<float>          { static constexpr double lo = 0., hi = 0.; static constexpr bool wide = false, is_float = true; };
 template <> struct OutTraits<double>         { static constexpr double lo = 0., hi = 0.; static constexpr bool wide = true, is_float = true; };
 
+// one sample of the corrected plane as the output holds it: a masked pixel (NaN) -> the output nodata (without one: 0, or the NaN
+// itself in a float type), everything else rounded half to even and clipped to the type's range
+template <typename T>
+__device__ __forceinline__ T cast_out_sample(float f, int has_nodata, T nd) {
+    using TR = OutTraits<T>;
+    if (f != f) {
+        return has_nodata ? nd : (TR::is_float ? (T)f : (T)0);  // masked pixel -> output nodata
+    } else if constexpr (TR::is_float) {
+        return (T)f;
+    } else if constexpr (TR::wide) {
+        double v = rint((double)f);
+        v = fmin(fmax(v, TR::lo), TR::hi);
+        return (T)v;
+    } else {
+        float v = rintf(f);  // np.round: half to even
+        v = fminf(fmaxf(v, (float)TR::lo), (float)TR::hi);
+        return (T)v;
+    }
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) cast_out_kernel(const float* __restrict__ in, long long in_stride, T* __restrict__ out,
                                                        long long out_stride, int height, int width, int has_nodata,
                                                        double nodata) {
-    using TR = OutTraits<T>;
     const int x = (blockIdx.x * blockDim.x + threadIdx.x) * PX;
     if (x >= width) return;
     const T nd = has_nodata ? (T)nodata : (T)0;
@@ -49,23 +68,33 @@ __global__ void __launch_bounds__(256) cast_out_kernel(const float* __restrict__
         const float f[PX] = {f4.x, f4.y, f4.z, f4.w};
         T* op = out + (long long)y * out_stride + x;
 #pragma unroll
+        for (int i = 0; i < PX; ++i) op[i] = cast_out_sample<T>(f[i], has_nodata, nd);
+    }
+}
+
+// cast_out_kernel + the validity of every pixel from the same read: `valid` = 255 where the corrected value is not NaN, else 0 --
+// the mask of the reference's corrected RasterArray, taken BEFORE the conversion (an integer output cannot tell a masked pixel
+// from a 0).  The PX validity bytes of a lane are one 4-byte store (rows of `valid` are padded to PX like the others).
+template <typename T>
+__global__ void __launch_bounds__(256) cast_out_valid_kernel(const float* __restrict__ in, long long in_stride, T* __restrict__ out,
+                                                             long long out_stride, unsigned char* __restrict__ valid,
+                                                             long long valid_stride, int height, int width, int has_nodata,
+                                                             double nodata) {
+    static_assert(PX == 4, "the validity of a lane's pixels is one 4-byte word");
+    const int x = (blockIdx.x * blockDim.x + threadIdx.x) * PX;
+    if (x >= width) return;
+    const T nd = has_nodata ? (T)nodata : (T)0;
+    for (int y = blockIdx.y; y < height; y += gridDim.y) {
+        const float4 f4 = *reinterpret_cast<const float4*>(in + (long long)y * in_stride + x);
+        const float f[PX] = {f4.x, f4.y, f4.z, f4.w};
+        T* op = out + (long long)y * out_stride + x;
+        unsigned ok = 0;
+#pragma unroll
         for (int i = 0; i < PX; ++i) {
-            T o;
-            if (f[i] != f[i]) {
-                o = has_nodata ? nd : (TR::is_float ? (T)f[i] : (T)0);  // masked pixel -> output nodata
-            } else if constexpr (TR::is_float) {
-                o = (T)f[i];
-            } else if constexpr (TR::wide) {
-                double v = rint((double)f[i]);
-                v = fmin(fmax(v, TR::lo), TR::hi);
-                o = (T)v;
-            } else {
-                float v = rintf(f[i]);  // np.round: half to even
-                v = fminf(fmaxf(v, (float)TR::lo), (float)TR::hi);
-                o = (T)v;
-            }
-            op[i] = o;
+            op[i] = cast_out_sample<T>(f[i], has_nodata, nd);
+            ok |= (f[i] == f[i] ? 255u : 0u) << (8 * i);
         }
+        *reinterpret_cast<unsigned*>(valid + (long long)y * valid_stride + x) = ok;
     }
 }
 
@@ -106,6 +135,26 @@ hipError_t launch_cast_out(int dtype, const CastPlane& r, hipStream_t stream) {
         default: return hipErrorInvalidValue;
     }
 #undef HK_CAST_OUT
+    return hipGetLastError();
+}
+
+hipError_t launch_cast_out_valid(int dtype, const CastPlane& r, hipStream_t stream) {
+    const dim3 g = cast_grid(r.height, r.width), b(256);
+    if (!r.valid || r.valid_stride % PX || (uintptr_t)r.valid % PX) return hipErrorInvalidValue;
+#define HK_CAST_OUT_VALID(T)                                                                                                                 \
+    HK_LAUNCH(cast_out_valid_kernel<T>, g, b, 0, stream, static_cast<const float*>(r.in), r.in_stride, static_cast<T*>(r.out), r.out_stride, \
+              r.valid, r.valid_stride, r.height, r.width, r.has_nodata, r.nodata)
+    switch (dtype) {
+        case 0: HK_CAST_OUT_VALID(float); break;
+        case 1: HK_CAST_OUT_VALID(unsigned char); break;
+        case 2: HK_CAST_OUT_VALID(unsigned short); break;
+        case 3: HK_CAST_OUT_VALID(short); break;
+        case 4: HK_CAST_OUT_VALID(unsigned int); break;
+        case 5: HK_CAST_OUT_VALID(int); break;
+        case 6: HK_CAST_OUT_VALID(double); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef HK_CAST_OUT_VALID
     return hipGetLastError();
 }
 

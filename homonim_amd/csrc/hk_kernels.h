@@ -309,6 +309,19 @@ struct OverviewLevels {
     void* const* out;
     const long long* out_stride;
     const long long* out_band_stride;
+    // the masked build (nullable `valid`: validity under nd_mode / nodata): a uint8 validity plane of the raster, 255 / 0, shared by
+    // all bands -- nd_mode / nodata are not read then -- and one validity plane per level out; strides in bytes
+    const unsigned char* valid = nullptr;
+    long long valid_stride = 0;
+    unsigned char* const* out_valid = nullptr;
+    const long long* out_valid_stride = nullptr;
+};
+struct OverviewValid {  // the validity planes of one masked launch, beside its OverviewArgs
+    const unsigned char* src;
+    long long stride;
+    unsigned char* out[OVERVIEW_PASS_LEVELS];
+    long long out_stride[OVERVIEW_PASS_LEVELS];
+    int vec_ok, out_vec_ok;  // set by the launcher: 16-byte loads of `src` / 8-byte level-1 stores are legal
 };
 struct OverviewArgs {
     const void* src;
@@ -400,9 +413,13 @@ struct CastPlane {
     int height, width;
     int has_nodata = 0;
     double nodata = 0.;
+    unsigned char* valid = nullptr;  // launch_cast_out_valid: the validity plane (255 / 0), rows valid_stride bytes apart,
+    long long valid_stride = 0;      // base and stride multiples of PX
 };
 hipError_t launch_cast_in(int dtype, const CastPlane& r, hipStream_t stream);
 hipError_t launch_cast_out(int dtype, const CastPlane& r, hipStream_t stream);
+// cast_out and, from the same read of the float32 plane, `valid` = 255 where it is not NaN, else 0 (every dtype, float32 included)
+hipError_t launch_cast_out_valid(int dtype, const CastPlane& r, hipStream_t stream);
 inline int dtype_size(int dtype) { const int sz[7] = {4, 1, 2, 2, 4, 4, 8}; return dtype >= 0 && dtype < 7 ? sz[dtype] : 0; }
 
 // The per-dataset mask of a GeoTIFF applied to its bands (hk_dataset_mask.hip; homonim/raster_array.py:161-197): float32 planes

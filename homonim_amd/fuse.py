@@ -561,11 +561,14 @@ class RasterFuse:
                                                 c0 - in_win.col_off:c1 - in_win.col_off]
 
     def _process_block(self, bp: BlockPair, model: KernelModel, corr: np.ndarray, params: Optional[np.ndarray],
-                       out_nodata: Optional[float]):
+                       out_nodata: Optional[float], valid: Optional[np.ndarray] = None):
         """ read -> fit + apply (+ output dtype conversion) on the GPU -> write the out-block (homonim/fuse.py:295-319): fused into one
-        kernel on a shared grid, across grids with RefSpaceModel / SrcSpaceModel doing the re-sampling on the device """
+        kernel on a shared grid, across grids with RefSpaceModel / SrcSpaceModel doing the re-sampling on the device.  ``valid``: the
+        (H, W) validity raster, which the blocks of band 0 fill where they fill ``corr[0]`` """
         src_ra, ref_ra = self._read_pair(bp)
         band_params = self._band_params(params, bp.band_i) if params is not None else None
+        if bp.band_i != 0:
+            valid = None
         if model.fuses_into(src_ra, ref_ra):
             # the out-block goes straight from the device into the corrected / parameter rasters (no block-sized
             # temporaries, no host-side crop copy; asynchronous when the rasters are page-locked)
@@ -573,13 +576,16 @@ class RasterFuse:
             crop = self._crop(bp)
             window = (crop[0].start, crop[1].start, bp.src_out_block.height, bp.src_out_block.width)
             model.fit_apply_into(src_ra, ref_ra, window, corr[bp.band_i][rs, cs],
-                                 band_params[:, rs, cs] if params is not None else None, out_nodata=out_nodata)
+                                 band_params[:, rs, cs] if params is not None else None, out_nodata=out_nodata,
+                                 valid_dst=valid[rs, cs] if valid is not None else None)
             return
         # one upload / download per block in the rasters' own dtypes, everything else stays in HBM (RefSpaceModel and
         # SrcSpaceModel alike: hk_refspace_fit_apply, hk_srcspace_fit_apply)
-        corr_ra, param_ra = model.fit_apply(src_ra, ref_ra, want_params=params is not None, out_dtype=corr.dtype.name,
-                                            out_nodata=out_nodata)
+        corr_ra, param_ra, *block_valid = model.fit_apply(src_ra, ref_ra, want_params=params is not None, out_dtype=corr.dtype.name,
+                                                          out_nodata=out_nodata, want_valid=valid is not None)
         self._put(corr[bp.band_i], corr_ra.array, bp.src_in_block, bp.src_out_block)
+        if valid is not None:
+            self._put(valid, block_valid[0], bp.src_in_block, bp.src_out_block)
         if params is not None:
             p_in, p_out = (bp.ref_in_block, bp.ref_out_block) if self._param_grid is self._ref_grid else \
                 (bp.src_in_block, bp.src_out_block)
@@ -591,7 +597,7 @@ class RasterFuse:
                 param_filename: Optional[Union[str, os.PathLike, bool]] = None, build_ovw: bool = True,
                 overwrite: bool = False, model_config: Optional[Dict] = None, out_profile: Optional[Dict] = None,
                 block_config: Optional[Dict] = None, device_config: Optional[Dict] = None,
-                corr_out: Optional[np.ndarray] = None):
+                corr_out: Optional[np.ndarray] = None, return_valid: bool = False):
         """
         Same arguments as homonim.RasterFuse.process (fuse.py:321-332) plus ``device_config``.  Returns
         ``(corrected, params)``: float32 arrays (bands, H, W) and (n_param_bands * bands, H, W) or None.  When
@@ -612,6 +618,16 @@ class RasterFuse:
         With ``world_size > 1`` only this rank's blocks are filled in (others stay nodata).
         ``corr_out``: a caller-owned corrected raster (bands, H, W) of the output dtype to fill instead of a new one, e.g.
         page-locked memory of a pipeline that processes many rasters (it is NOT pre-filled with nodata).
+        An output WITHOUT a nodata value (``out_profile['nodata'] is None``) written to a ``.tif`` gets an internal mask, as the
+        reference's does (``rio_dataset.write_mask`` "once (for first band) if nodata is None", raster_array.py:493-500, under
+        ``GDAL_TIFF_INTERNAL_MASK=True``, raster_pair.py:303): a 1-bit mask directory behind the main image (``tiff.write_tiff``), and
+        the overviews are averaged under that mask and carry masks of their own.  The mask is the validity of the corrected block
+        BEFORE its conversion to the output dtype -- a pixel is valid where its float32 corrected value is not NaN -- gathered on the
+        device next to the conversion, and THE FILE'S MASK IS BAND 1'S: one (H, W) uint8 raster, zero-filled, that only the blocks of
+        the first band fill (255 / 0), placed like ``corr[0]``; with ``world_size > 1`` it holds this rank's blocks only.
+        ``return_valid=True`` returns ``(corrected, params, valid)`` with that raster, whatever the nodata and the file type
+        (``.npy`` outputs write no mask: this is the way to get it); otherwise, and with a nodata value, nothing is gathered.
+        The parameter file has nodata NaN and never a mask.
         """
         if self._closed:
             raise IoError('The raster pair has been closed')
@@ -626,15 +642,18 @@ class RasterFuse:
         models, own_contexts = self._build_models(model_type, kernel_shape, want_params, model_config, device_config)
         n_param = models[0].n_param
         corr, params = self._allocate(out_dtype, nodata, corr_out, n_param if want_params else 0)
+        write_mask = nodata is None and self._is_tiff(corr_filename)
+        valid = np.zeros(self.shape, np.uint8) if (return_valid or write_mask) else None
         blocks = list(self.block_pairs(overlap=overlap, max_block_mem=block_config['max_block_mem']))
         blocks = shard(blocks, device_config['rank'], device_config['world_size'], device_config['contiguous'])
         want_ovw = (build_ovw and self._is_tiff(corr_filename), build_ovw and want_params and self._is_tiff(param_filename))
         overviews = self._run(blocks, models, own_contexts, corr, params, nodata, block_config['threads'], device_config['pin'],
-                              want_ovw)
+                              want_ovw, valid, write_mask)
         compressor = models[0].context.deflate_tiles if device_config['deflate'] == 'device' else None
         self._write(corr_filename, param_filename if want_params else None, corr, params, nodata, n_param, overviews,
-                    dict(model=model_type, kernel_shape=tuple(kernel_shape), **model_config), compressor, write_options)
-        return corr, params
+                    dict(model=model_type, kernel_shape=tuple(kernel_shape), **model_config), compressor, write_options,
+                    valid if write_mask else None)
+        return (corr, params, valid) if return_valid else (corr, params)
 
     def _resolve_output(self, corr_filename, param_filename, want_params: bool, overwrite: bool, out_profile: Dict):
         """ -> (output dtype, output nodata, ``write_options`` or None) of a ``process`` call, which is refused here when a file exists
@@ -683,17 +702,20 @@ class RasterFuse:
         params = np.full((n_param * n_src, grid.height, grid.width), np.nan, dtype=np.float32) if n_param else None
         return corr, params
 
-    def _run(self, blocks, models, own_contexts, corr, params, nodata, threads: int, pin: bool, want_ovw: Tuple[bool, bool]):
-        """ The block loop -> (corr_ovw, param_ovw): the internal overviews asked for by ``want_ovw``, else None. """
+    def _run(self, blocks, models, own_contexts, corr, params, nodata, threads: int, pin: bool, want_ovw: Tuple[bool, bool],
+             valid: Optional[np.ndarray] = None, masked_ovw: bool = False):
+        """ The block loop -> (corr_ovw, param_ovw): the internal overviews asked for by ``want_ovw``, else None.  ``valid``: the
+        validity raster the blocks of band 0 fill; ``masked_ovw``: the corrected raster's overviews are built under it, and
+        corr_ovw is ``(levels, level_valids)``. """
         ctx = models[0].context
         # on request: page-lock the rasters in place for the duration of the block loop (direct copies); by default pageable
         # rasters go through the context's pinned staging ring (hk_api.hip stage_h2d / stage_d2h) block by block
-        pinned = self._pin(ctx, [self._src, self._ref, corr, params]) if pin else []
+        pinned = self._pin(ctx, [self._src, self._ref, corr, params, valid]) if pin else []
         try:
-            self._run_blocks(blocks, lambda bp, wi: self._process_block(bp, models[wi], corr, params, nodata),
+            self._run_blocks(blocks, lambda bp, wi: self._process_block(bp, models[wi], corr, params, nodata, valid),
                              [m.context for m in models], threads)
             # internal overviews of the files to be written, while the rasters are still page-locked (direct copies)
-            return (self._overviews(ctx, corr, nodata) if want_ovw[0] else None,
+            return (self._overviews(ctx, corr, nodata, valid if masked_ovw else None) if want_ovw[0] else None,
                     self._overviews(ctx, params, float('nan')) if want_ovw[1] else None)
         finally:
             for arr in pinned:
@@ -705,15 +727,17 @@ class RasterFuse:
                 c.close()
 
     def _write(self, corr_filename, param_filename, corr, params, nodata, n_param: int, overviews, settings: Dict, compressor,
-               write_options: Optional[Dict]):
+               write_options: Optional[Dict], mask: Optional[np.ndarray] = None):
         """ The rasters into the files that are paths, with the provenance tags of homonim/fuse.py:193-207 (``settings``: model, kernel
-        shape and model configuration of the run). """
+        shape and model configuration of the run).  ``mask``: the internal mask of the corrected file; its overviews are then
+        ``(levels, level_masks)``. """
         meta = dict(FUSE_SRC_FILE=os.path.basename(self._src_filename or 'memory'),
                     FUSE_REF_FILE=os.path.basename(self._ref_filename or 'memory'), FUSE_PROC_CRS=self._proc_crs.name,
                     **{f'FUSE_{k.upper()}': getattr(v, 'name', v) for k, v in settings.items()})
         if _is_path(corr_filename):
-            self._save(corr_filename, corr, self._transform, nodata, meta, overviews=overviews[0], compressor=compressor,
-                       write_options=write_options)
+            levels, level_masks = overviews[0] if (mask is not None and overviews[0] is not None) else (overviews[0], None)
+            self._save(corr_filename, corr, self._transform, nodata, meta, overviews=levels, compressor=compressor,
+                       write_options=write_options, mask=mask, overview_masks=level_masks)
         if _is_path(param_filename):
             self._save(param_filename, params, self._param_grid.transform, float('nan'), meta, self._param_descriptions(n_param),
                        overviews=overviews[1], compressor=compressor, write_options=write_options)
@@ -814,22 +838,25 @@ class RasterFuse:
         return _is_path(filename) and os.fspath(filename).lower().endswith(('.tif', '.tiff'))
 
     @staticmethod
-    def _overviews(ctx, array: np.ndarray, nodata) -> Optional[List[np.ndarray]]:
+    def _overviews(ctx, array: np.ndarray, nodata, valid: Optional[np.ndarray] = None):
         """ The internal overviews of a finished (bands, H, W) raster (homonim/fuse.py:152-165), finest first; None when the
-        raster is too small for one. """
+        raster is too small for one.  ``valid``: the raster's validity in place of a nodata value -- the masked build, which
+        returns ``(levels, level_valids)``. """
         n_levels = len(overview_factors(array.shape[-2:]))
-        return ctx.overviews(array, nodata, n_levels) if n_levels else None
+        return ctx.overviews(array, nodata, n_levels, valid=valid) if n_levels else None
 
     def _save(self, filename, array: np.ndarray, transform: Affine, nodata, metadata: Dict,
               descriptions: Optional[List[str]] = None, overviews: Optional[List[np.ndarray]] = None, compressor=None,
-              write_options: Optional[Dict] = None):
+              write_options: Optional[Dict] = None, mask: Optional[np.ndarray] = None,
+              overview_masks: Optional[List[np.ndarray]] = None):
         """ ``.tif`` / ``.tiff``: tiled GeoTIFF as ``write_options`` say (``_write_options``; None: the reference's default output
         profile), with ``overviews`` as its internal overviews when given, its tiles compressed by ``compressor``
-        (``tiff.write_tiff``; None: host zlib); anything else: ``numpy.save``. """
+        (``tiff.write_tiff``; None: host zlib), with ``mask`` / ``overview_masks`` as its internal masks; anything else:
+        ``numpy.save`` (no mask). """
         if self._is_tiff(filename):
             from homonim_amd.tiff import write_tiff
             write_tiff(filename, array, transform, self._crs, nodata, {k: str(v) for k, v in metadata.items()},
-                       descriptions=descriptions, overviews=overviews,
+                       descriptions=descriptions, overviews=overviews, mask=mask, overview_masks=overview_masks,
                        compressor=compressor if (write_options or {}).get('compress', True) else None, **(write_options or {}))
         else:
             np.save(filename, array)

@@ -142,16 +142,26 @@ class KernelModel:
         return RasterArray.from_profile(corr, param_ra.profile)
 
     def fit_apply(self, src_ra: RasterArray, ref_ra: RasterArray, want_params: bool = False,
-                  out_dtype: str = RasterArray.default_dtype,
-                  out_nodata: Optional[float] = RasterArray.default_nodata) -> Tuple[RasterArray, Optional[RasterArray]]:
+                  out_dtype: str = RasterArray.default_dtype, out_nodata: Optional[float] = RasterArray.default_nodata,
+                  want_valid: bool = False):
         """
         ``apply(src_ra, fit(src_ra.copy(), ref_ra))`` in ONE pass over the data (window sums, solve, R2 test and
         correction fused in a single kernel; each input byte is read once).  Returns (corr_ra, param_ra | None).
 
         ``out_dtype`` / ``out_nodata`` convert the corrected block on the device the way the reference converts it when
         writing (raster_array.py:353-387); integer ``src_ra`` / ``ref_ra`` arrays are converted to float32 on the device.
+        ``want_valid``: returns (corr_ra, param_ra | None, valid) -- ``valid`` the block's uint8 validity, 255 where the float32
+        corrected value is not NaN and 0 where it is: the ``mask`` of the reference's corrected ``RasterArray`` before its
+        conversion, which an integer output without a nodata value cannot carry itself (raster_array.py:493-500).
         """
         _require_shared_grid(ref_ra, src_ra, "'ref_ra' and 'src_ra'")
+        if want_valid:   # the block entry with the whole block as its window: the one that writes validity (hk_fit_apply_block_valid)
+            h, w = src_ra.shape
+            corr, valid = np.empty((h, w), np.dtype(out_dtype)), np.empty((h, w), np.uint8)
+            params = np.empty((self.n_param, h, w), np.float32) if want_params else None
+            self.context.fit_apply_block(self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), self._band(ref_ra, 'ref_ra'),
+                                         (0, 0, h, w), corr, params, out_nodata=out_nodata, valid_dst=valid)
+            return (*self._wrap(corr, params, src_ra, src_ra, out_nodata, want_params), valid)
         params, corr, _, n_fail = self.context.fit_apply(
             self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), self._band(ref_ra, 'ref_ra'), self.n_param,
             want_params=want_params, want_corr=True, out_dtype=out_dtype, out_nodata=out_nodata
@@ -164,19 +174,21 @@ class KernelModel:
         return (ref_ra.transform == src_ra.transform) and (ref_ra.shape == src_ra.shape)
 
     def fit_apply_into(self, src_ra: RasterArray, ref_ra: RasterArray, window, corr_dst: np.ndarray,
-                       params_dst: Optional[np.ndarray] = None, out_nodata: Optional[float] = RasterArray.default_nodata) -> int:
+                       params_dst: Optional[np.ndarray] = None, out_nodata: Optional[float] = RasterArray.default_nodata,
+                       valid_dst: Optional[np.ndarray] = None) -> int:
         """
         ``fit_apply`` for the block loop of ``RasterFuse.process`` (homonim/fuse.py:295-319): the window
         ``(row0, col0, rows, cols)`` of the block -- its out-block, i.e. the block without the halo that
         raster_array.py:478-491 crops on writing -- goes straight into ``corr_dst`` / ``params_dst``, views of the
         caller's corrected / parameter rasters (their dtype is the output dtype).  One call = one upload of the read-block,
         one download of the out-block, one stream synchronisation; asynchronous when the rasters are page-locked.
-        Returns the number of pixels that failed the r2 mask.
+        Returns the number of pixels that failed the r2 mask.  ``valid_dst``: a uint8 view of the caller's validity raster at the
+        same window, filled with the out-block's validity (255 / 0, ``fit_apply``'s ``want_valid``).
         """
         _require_shared_grid(ref_ra, src_ra, "'ref_ra' and 'src_ra'")
         _, n_fail = self.context.fit_apply_block(
             self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), self._band(ref_ra, 'ref_ra'), window, corr_dst,
-            params_dst, out_nodata=out_nodata
+            params_dst, out_nodata=out_nodata, valid_dst=valid_dst
         )
         return n_fail
 
@@ -269,22 +281,24 @@ class RefSpaceModel(KernelModel):
         return _same_grid(src_ra, ref_ra) and not self._mask_partial
 
     def fit_apply(self, src_ra: RasterArray, ref_ra: RasterArray, want_params: bool = False,
-                  out_dtype: str = RasterArray.default_dtype,
-                  out_nodata: Optional[float] = RasterArray.default_nodata) -> Tuple[RasterArray, Optional[RasterArray]]:
+                  out_dtype: str = RasterArray.default_dtype, out_nodata: Optional[float] = RasterArray.default_nodata,
+                  want_valid: bool = False):
         """ ``apply(src_ra, fit(src_ra, ref_ra))`` with everything between the two blocks kept in HBM
-        (hk_refspace_fit_apply): one upload of source + reference, one download of the corrected block. """
+        (hk_refspace_fit_apply): one upload of source + reference, one download of the corrected block.  ``want_valid``: as in
+        ``KernelModel.fit_apply`` (here the validity carries ``mask_partial``'s erosion as well). """
         if _same_grid(src_ra, ref_ra) and not self._mask_partial:
-            return KernelModel.fit_apply(self, src_ra, ref_ra, want_params, out_dtype, out_nodata)
+            return KernelModel.fit_apply(self, src_ra, ref_ra, want_params, out_dtype, out_nodata, want_valid)
         from homonim_amd.geo import grid_mapping
         _require_one_crs(src_ra, ref_ra)
         down = self._get_resampling(src_ra.res, ref_ra.res)
         up = self._get_resampling(ref_ra.res, src_ra.res)
-        params, corr, _ = self.context.refspace_fit_apply(
+        params, corr, _, *valid = self.context.refspace_fit_apply(
             self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), self._band(ref_ra, 'ref_ra'),
             grid_mapping(src_ra.transform, ref_ra.transform), grid_mapping(ref_ra.transform, src_ra.transform), int(down),
-            int(up), self._mask_partial, self.n_param, want_params, out_dtype=out_dtype, out_nodata=out_nodata
+            int(up), self._mask_partial, self.n_param, want_params, out_dtype=out_dtype, out_nodata=out_nodata,
+            want_valid=want_valid
         )
-        return self._wrap(corr, params, src_ra, ref_ra, out_nodata, want_params)
+        return (*self._wrap(corr, params, src_ra, ref_ra, out_nodata, want_params), *valid)
 
 
 class SrcSpaceModel(KernelModel):
@@ -314,16 +328,17 @@ class SrcSpaceModel(KernelModel):
         return _same_grid(src_ra, ref_ra) and not self._mask_partial
 
     def fit_apply(self, src_ra: RasterArray, ref_ra: RasterArray, want_params: bool = False,
-                  out_dtype: str = RasterArray.default_dtype,
-                  out_nodata: Optional[float] = RasterArray.default_nodata) -> Tuple[RasterArray, Optional[RasterArray]]:
+                  out_dtype: str = RasterArray.default_dtype, out_nodata: Optional[float] = RasterArray.default_nodata,
+                  want_valid: bool = False):
         """ One fused pass on a shared grid.  Across grids everything between the two blocks stays in HBM as well
         (hk_srcspace_fit_apply): one upload of source + reference in their own dtypes, one download of the corrected block; with
         `average` the reference block -- the finer, larger one -- is read once, by the kernel that forms the averaged value and
         the coverage fraction of ``mask_partial`` together.  ``mask_partial`` on a shared grid keeps the reference's own sequence
         ``apply(src_ra, fit(src_ra, ref_ra))`` -- SrcSpaceModel.fit masks the parameters with the eroded full-coverage mask
-        (kernel_model.py:526-531), which the fused kernel does not know about. """
+        (kernel_model.py:526-531), which the fused kernel does not know about.  ``want_valid``: as in ``KernelModel.fit_apply``; that
+        sequence has its float32 corrected block on the host, and its validity is read from it there. """
         if self.fuses_into(src_ra, ref_ra):
-            return KernelModel.fit_apply(self, src_ra, ref_ra, want_params, out_dtype, out_nodata)
+            return KernelModel.fit_apply(self, src_ra, ref_ra, want_params, out_dtype, out_nodata, want_valid)
         _require_one_crs(src_ra, ref_ra)
         if not _same_grid(src_ra, ref_ra):
             from homonim_amd.geo import grid_mapping
@@ -334,16 +349,19 @@ class SrcSpaceModel(KernelModel):
                 ref, ky, oy = ref[::-1, :], -ky, ref.shape[0] - oy
             if kx < 0:
                 ref, kx, ox = ref[:, ::-1], -kx, ref.shape[1] - ox
-            params, corr, _ = self.context.srcspace_fit_apply(
+            params, corr, _, *valid = self.context.srcspace_fit_apply(
                 self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'), ref, (kx, ox, ky, oy),
                 int(self._get_resampling(ref_ra.res, src_ra.res)), self._mask_partial, self.n_param, want_params,
-                out_dtype=out_dtype, out_nodata=out_nodata
+                out_dtype=out_dtype, out_nodata=out_nodata, want_valid=want_valid
             )
-            return self._wrap(corr, params, src_ra, src_ra, out_nodata, want_params)
+            return (*self._wrap(corr, params, src_ra, src_ra, out_nodata, want_params), *valid)
         param_ra = self.fit(src_ra.copy(), ref_ra)
         corr_ra = self.apply(src_ra, param_ra)
+        valid = (~np.isnan(corr_ra.array)).astype(np.uint8) * np.uint8(255) if want_valid else None
         if np.dtype(out_dtype) != np.float32 or not (out_nodata is None or (isinstance(out_nodata, float) and np.isnan(out_nodata))):
             from homonim_amd.fuse import convert_dtype
             arr = convert_dtype(corr_ra.array, str(np.dtype(out_dtype)), out_nodata)
             corr_ra = RasterArray.from_profile(arr, dict(corr_ra.profile, nodata=out_nodata, dtype=str(np.dtype(out_dtype))))
+        if want_valid:
+            return corr_ra, (param_ra if want_params else None), (valid[0] if valid.ndim == 3 else valid)
         return corr_ra, (param_ra if want_params else None)

@@ -12,8 +12,9 @@ default output profile -- classic or BigTIFF, with predictor 2 or 3 on request -
 images chained behind the first) on request;
 ``read_tiff_overviews`` reads those back.  A rotated or sheared grid is read from, and on request written as, a
 ModelTransformation matrix.  Alpha bands (ExtraSamples 1 / 2) are named and an internal 1-bit mask directory (NewSubfileType 4) is
-decoded to its packed bits (``TiffRaster.alpha_bands``, ``mask_band``, ``mask``; applying them is ``fuse.dataset_masked``'s); masks of
-overviews are skipped, masks are not written.  LZW is read only (``lzw_decode``, or a hook of ``read_tiff``).  Everything else (other
+decoded to its packed bits (``TiffRaster.alpha_bands``, ``mask_band``, ``mask``; applying them is ``fuse.dataset_masked``'s).  The writer
+chains such a mask behind an image without a nodata value on request, and one (NewSubfileType 5) behind every overview level;
+``read_tiff_overviews(masks=True)`` reads those back.  LZW is read only (``lzw_decode``, or a hook of ``read_tiff``).  Everything else (other
 compressions, palettes) raises.
 """
 import mmap
@@ -299,21 +300,37 @@ def read_tiff(path, inflater=None, lzw=None) -> TiffRaster:
                       _mask_band(t, out.dtype, nodata, mask is not None, alpha))
 
 
-def read_tiff_overviews(path, inflater=None, lzw=None) -> List[np.ndarray]:
+def read_tiff_overviews(path, inflater=None, lzw=None, masks: bool = False):
     """ The internal overviews of a GeoTIFF: the reduced-resolution images (NewSubfileType bit 0) chained behind the first, in
     file order, each as a (bands, height, width) array.  ``[]`` for a file without any.  ``inflater``, ``lzw``: as in ``read_tiff``,
-    called once per level. """
+    called once per level.  ``masks``: return ``(levels, level_masks)`` -- a level's mask is the first directory with NewSubfileType
+    5 (reduced + mask), 1 bit per sample and one sample per pixel that has the level's shape, as an (h, w) bool array, True = valid;
+    None for a level without one. """
     with open(path, 'rb') as f:
         buf = f.read()
     bo, t, nxt = _read_ifd(buf)
-    out, seen = [], set()
+    out, mask_dirs, seen = [], [], set()
     while nxt and nxt not in seen:
         seen.add(nxt)
         bo, t, following = _read_ifd(buf, nxt)
         if t.get(T_SUBFILE, (0,))[0] & 1 and not _is_mask(t):   # (a mask of an overview is no overview)
             out.append(_decode_image(buf, bo, t, inflater, lzw))
+        elif t.get(T_SUBFILE, (0,))[0] & 5 == 5 and tuple(t.get(T_BITS, (1,))) == (1,) and t.get(T_SPP, (1,))[0] == 1:
+            mask_dirs.append(t)
         nxt = following
-    return out
+    if not masks:
+        return out
+    level_masks = []
+    for lv in out:
+        mt = next((t for t in mask_dirs if (t[T_HEIGHT][0], t[T_WIDTH][0]) == lv.shape[1:]), None)
+        level_masks.append(None if mt is None else unpack_mask(_decode_mask(buf, bo, mt, inflater, lzw), lv.shape[2]))
+    return out, level_masks
+
+
+def unpack_mask(packed: np.ndarray, width: int) -> np.ndarray:
+    """ The packed bits of an internal mask (``TiffRaster.mask``: (height, ceil(width / 8)) uint8, most significant bit first) as
+    an (height, width) bool array, True = valid """
+    return np.unpackbits(packed, axis=1, count=width).astype(bool)
 
 
 # why ``lzw_decode`` refuses a stream: the texts of HK_LZW_* (include/homonim_hk.h), by status
@@ -559,7 +576,8 @@ def _directory(entries, chunks, ifd_off: int, has_next: bool, big: bool = False)
 def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = None, nodata: Optional[float] = None,
                metadata: Optional[Dict[str, str]] = None, tile: int = 512, compress: bool = True,
                descriptions: Optional[Sequence[Optional[str]]] = None, overviews: Optional[Sequence[np.ndarray]] = None,
-               rotated: bool = False, compressor=None, predictor: int = 1, bigtiff='if_safer'):
+               rotated: bool = False, compressor=None, predictor: int = 1, bigtiff='if_safer', mask: Optional[np.ndarray] = None,
+               overview_masks: Optional[Sequence[np.ndarray]] = None):
     """ Write (bands, height, width) as a little-endian GeoTIFF: tiled, DEFLATE, band-separate -- the reference's
     default output profile (homonim/fuse.py:124-149: tiled 512 x 512, compress=deflate, interleave=band).  ``descriptions``:
     one band description per band (None: none for that band), written as GDAL writes them.  ``overviews``: the internal
@@ -578,7 +596,17 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
     ``compressor(array3d, tile, predictor=predictor)`` and returns the streams of the predicted tiles; it needs ``compress``.
     ``bigtiff``: 'yes', 'no', 'if_needed' or 'if_safer' (``bigtiff_wanted``): classic TIFF or BigTIFF (magic 43, 64-bit offsets,
     tile offsets and byte counts as LONG8).  A main image of at most 2 000 000 000 raw bytes is, with the defaults, the classic
-    file this function always wrote. """
+    file this function always wrote.
+    ``mask``: an (height, width) array, a pixel valid where it is not 0 -- the per-dataset internal mask of an image WITHOUT a nodata
+    value (rasterio's ``write_mask`` under GDAL_TIFF_INTERNAL_MASK=True); ``overview_masks``: one such mask per overview level, of
+    the level's shape.  Either beside a nodata value is a ``ValueError``: the reader lets a mask overrule the tag, and this writer
+    does not produce such files.  Every mask is a directory of its own: NewSubfileType 4 (the main image's) or 5 (a level's:
+    reduced + mask), the image's width and length, 1 bit per sample, 1 sample per pixel, PhotometricInterpretation 4
+    (transparency mask), no FillOrder (most significant bit first), no predictor, tiled at its image's tile size (a tile row is
+    ``tile / 8`` bytes, edge tiles zero-padded), Compression 8 with one zlib stream per tile where the file is compressed, else
+    1.  The bits are packed with ``numpy.packbits`` and compressed with zlib on this thread: ``compressor`` is for sample tiles.
+    Directory order: the main image, its mask, the overview levels, their masks in level order; the main image's directory and
+    data lie where they lie without a mask, only its next-directory pointer differs. """
     if compressor is not None and not compress:
         raise ValueError('a compressor was given for an uncompressed file (compress=False)')
     a = np.asarray(array)
@@ -607,6 +635,19 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
         if lv.ndim != 3 or lv.shape[0] != nb or lv.dtype != a.dtype or lv.size == 0:
             raise ValueError(f'an overview of shape {lv.shape}, dtype {lv.dtype} for a raster of {nb} band(s), dtype {a.dtype}')
         levels.append(lv.astype(lv.dtype.newbyteorder('<'), copy=False))
+    if (mask is not None or overview_masks is not None) and nodata is not None:
+        raise ValueError(f'an internal mask beside a nodata value ({nodata}): a masked file carries no nodata tag')
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.shape != (h, w):
+            raise ValueError(f'a mask of shape {mask.shape} for a raster of {h} x {w}')
+    level_masks = [np.asarray(m) for m in overview_masks] if overview_masks is not None else []
+    if overview_masks is not None:
+        if len(level_masks) != len(levels):
+            raise ValueError(f'{len(level_masks)} overview masks for {len(levels)} overview levels')
+        for m, lv in zip(level_masks, levels):
+            if m.shape != lv.shape[1:]:
+                raise ValueError(f'an overview mask of shape {m.shape} for a level of {lv.shape[1]} x {lv.shape[2]}')
     a = a.astype(a.dtype.newbyteorder('<'), copy=False)
     tile = max(16, (int(tile) + 15) // 16 * 16)
 
@@ -640,6 +681,24 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
         if not reduced:
             geo_entries(add)
         return entries
+
+    def mask_image(m, img_tile, reduced):
+        """ (directory entries, tile chunks) of the 1-bit mask directory of an image tiled at ``img_tile`` """
+        mh, mw = m.shape
+        bits_ = np.zeros((-(-mh // img_tile) * img_tile, -(-mw // img_tile) * img_tile), np.uint8)
+        bits_[:mh, :mw] = m != 0
+        packed = np.packbits(bits_, axis=1)   # most significant bit first; a tile row is img_tile / 8 bytes
+        tb = img_tile // 8
+        chunks = []
+        for by in range(bits_.shape[0] // img_tile):
+            for bx in range(bits_.shape[1] // img_tile):
+                raw = packed[by * img_tile:(by + 1) * img_tile, bx * tb:(bx + 1) * tb].tobytes()
+                chunks.append(zlib.compress(raw, 6) if compress else raw)
+        entries = [(code, typ, len(values), struct.pack('<' + _TYPES[typ] * len(values), *values)) for code, typ, values in (
+            (T_SUBFILE, 4, [5 if reduced else 4]), (T_WIDTH, 4, [mw]), (T_HEIGHT, 4, [mh]), (T_BITS, 3, [1]),
+            (T_COMPRESSION, 3, [8 if compress else 1]), (T_PHOTOMETRIC, 3, [4]), (T_SPP, 3, [1]), (T_PLANAR, 3, [1]),
+            (T_TILE_W, 4, [img_tile]), (T_TILE_H, 4, [img_tile]))]
+        return entries, chunks
 
     def tile_streams(img, img_tile):
         if compressor is None:
@@ -680,7 +739,10 @@ def write_tiff(path, array: np.ndarray, transform: Affine, crs: Optional[CRS] = 
     # byte is written, and a raster past 4 GiB is never lost after the work is done.  The images lie one behind the other, each
     # directory in front of its own data: the main image lies where it does without overviews.
     images = [(image_entries(a, tile, False), tile_streams(a, tile))]
+    if mask is not None:
+        images.append(mask_image(mask, tile, False))
     images += [(image_entries(lv, OVERVIEW_TILE, True), tile_streams(lv, OVERVIEW_TILE)) for lv in levels]
+    images += [mask_image(m, OVERVIEW_TILE, True) for m in level_masks]
     classic_end = 8
     for entries, chunks in images:
         classic_end = _layout(entries, chunks, classic_end, False)[3]

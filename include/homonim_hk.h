@@ -79,7 +79,9 @@ typedef struct {
  * hk_inflate_image, hk_inflate_image_dev, with the new struct hk_inflate_layout) were added WITHOUT a new version: no existing
  * layout or prototype changed, so a version-12 consumer runs unchanged against either library; a consumer that wants them looks
  * them up by symbol (dlsym) and does without where they are absent.  hk_deflate_tiles_pred and hk_deflate_tiles_pred_dev were
- * added the same way, and so were hk_dataset_mask and hk_dataset_mask_dev (plain scalar arguments, no struct).
+ * added the same way, and so were hk_dataset_mask and hk_dataset_mask_dev (plain scalar arguments, no struct), and the forms that
+ * carry validity planes: hk_fit_apply_block_valid, hk_refspace_fit_apply_valid, hk_srcspace_fit_apply_valid, hk_overviews_valid and
+ * hk_overviews_valid_dev (the structs they take are those of the entries they extend).
  * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
 #define HK_ABI_VERSION 12
 int hk_abi_version(void);
@@ -139,6 +141,16 @@ int hk_overview_count(int32_t height, int32_t width, int32_t* n);
 int hk_overviews(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
                  int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels, void* const out[],
                  const int64_t out_stride[], const int64_t out_band_stride[]);
+
+/* hk_overviews under a per-dataset validity mask instead of a nodata value -- the overviews of a file that is written with an
+ * internal mask (RasterArray.to_rio_dataset's write_mask, homonim/raster_array.py:493-500, and build_overviews on that dataset).
+ * `valid`: height rows of one byte per pixel in host memory, valid_stride bytes apart, valid where not 0, one plane for all bands.
+ * out_valid[m - 1] (host; out_valid_stride[m - 1] bytes between rows) receives level m's own validity, 255 / 0.  See
+ * hk_overviews_valid_dev for the rule.  Strips as in hk_overviews, HK_OVERVIEW_STRIP_KB included. */
+int hk_overviews_valid(hk_ctx* ctx, const void* planes, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                       int64_t band_stride, const uint8_t* valid, int64_t valid_stride, int32_t n_levels, void* const out[],
+                       const int64_t out_stride[], const int64_t out_band_stride[], uint8_t* const out_valid[],
+                       const int64_t out_valid_stride[]);
 
 /* The per-dataset mask of a GeoTIFF -- an internal 1-bit mask or an alpha band -- applied to its bands, as
  * RasterArray.from_rio_dataset reads such a file (homonim/raster_array.py:161-197): out[b][y][x] = valid(y, x) ?
@@ -441,6 +453,19 @@ int hk_fit_apply_block(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* i
                        float* params_out, int32_t n_param_bands, void* corr_out, const hk_out_window* window,
                        double* norm_out, uint64_t* r2_fail_count);
 
+/* hk_fit_apply_block that also returns the validity of the corrected window.  valid_out (nullable: then this IS
+ * hk_fit_apply_block, launch for launch): one byte per pixel of the window, 255 where the float32 corrected value is not NaN and
+ * 0 where it is -- the mask of the reference's corrected RasterArray (what RasterArray.to_rio_dataset hands to write_mask when the
+ * output has no nodata value, homonim/raster_array.py:493-500), taken BEFORE the conversion to the output dtype, so it carries the
+ * source mask, the r2 in-painting and (the two-grid forms) mask_partial as the corrected block has them.  Its rows lie
+ * window->stride BYTES apart (the validity raster has the corrected raster's width), packed without a window; it needs corr_out.
+ * The typed window is bit for bit hk_fit_apply_block's; a float32 output without nodata keeps its NaNs.  One kernel
+ * (cast_out_valid_kernel, every output dtype, float32 included) reads the float32 plane once and writes both. */
+int hk_fit_apply_block_valid(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const void* src, int64_t src_stride,
+                             const void* ref, int64_t ref_stride, int32_t height, int32_t width, const double* norm_in,
+                             float* params_out, int32_t n_param_bands, void* corr_out, uint8_t* valid_out,
+                             const hk_out_window* window, double* norm_out, uint64_t* r2_fail_count);
+
 
 /* RefSpaceModel.fit + RefSpaceModel.apply (homonim/kernel_model.py:476-503) of one block pair on DIFFERENT grids of one
  * CRS, entirely on the device -- source and reference blocks in, corrected block (source grid) out:
@@ -461,6 +486,12 @@ int hk_refspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
                           const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
                           int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
                           int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count);
+/* ... and the validity of the corrected block, src_height x src_width bytes, packed (valid_out nullable; see
+ * hk_fit_apply_block_valid) */
+int hk_refspace_fit_apply_valid(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_space_desc* space,
+                                const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
+                                int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
+                                int32_t n_param_bands, void* corr_out, uint8_t* valid_out, uint64_t* r2_fail_count);
 
 /* SrcSpaceModel.fit + KernelModel.apply (homonim/kernel_model.py:506-535, :442-463) of one block pair on DIFFERENT grids of one
  * CRS, entirely on the device -- source and reference blocks in, corrected block (source grid) out:
@@ -482,6 +513,12 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
                           const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
                           int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
                           int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count);
+/* ... and the validity of the corrected block, src_height x src_width bytes, packed (valid_out nullable; see
+ * hk_fit_apply_block_valid) */
+int hk_srcspace_fit_apply_valid(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_srcspace_desc* space,
+                                const void* src, int64_t src_stride, int32_t src_height, int32_t src_width, const void* ref,
+                                int64_t ref_stride, int32_t ref_height, int32_t ref_width, float* params_out,
+                                int32_t n_param_bands, void* corr_out, uint8_t* valid_out, uint64_t* r2_fail_count);
 
 /* Page-lock caller memory so the host-pointer entry points above become truly asynchronous: with pinned src/ref/output
  * arrays the H2D copy, the kernel and the D2H copy of different calls (different host threads, different pooled streams)
@@ -659,6 +696,19 @@ int hk_param_stats_dev(hk_ctx* ctx, const float* planes_dev, int32_t n_bands, in
 int hk_overviews_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
                      int64_t stride, int64_t band_stride, int32_t nodata_mode, double nodata, int32_t n_levels,
                      void* const out_dev[], const int64_t out_stride[], const int64_t out_band_stride[], int32_t stream);
+
+/* hk_overviews_dev under a validity plane: valid_dev holds one byte per pixel of the raster (valid where not 0; valid_stride bytes
+ * between rows; one plane for all bands).  Level m's pixel (i, j) takes the pixels of level m - 1 that lie inside its 2 x 2 cell AND
+ * are valid, with the arithmetic above: float types the float64 sum in row-major order divided by the count and rounded once,
+ * integer types floor((2 S + n) / (2 n)).  A NaN under a valid byte is data and propagates, as under HK_NODATA_NONE.  A cell
+ * without a valid pixel gives 0 (integer types) or NaN (float types).  The same pass writes level m's own validity to
+ * out_valid_dev[m - 1] (out_valid_stride[m - 1] bytes between rows): 255 where the cell had a valid pixel, else 0; level m + 1
+ * cascades from level m's values and validity as stored.  16-byte loads of the samples and whole-word loads of the validity are
+ * used where the planes allow it (valid_dev and its stride multiples of 16); any other layout gives the same bits. */
+int hk_overviews_valid_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                           int64_t stride, int64_t band_stride, const uint8_t* valid_dev, int64_t valid_stride, int32_t n_levels,
+                           void* const out_dev[], const int64_t out_stride[], const int64_t out_band_stride[],
+                           uint8_t* const out_valid_dev[], const int64_t out_valid_stride[], int32_t stream);
 
 /* hk_dataset_mask for device-resident planes (band b at planes_dev + b * band_stride elements, out_dev + b * out_band_stride),
  * mask and output: one launch for all bands -- a lane reads the validity of 8 consecutive pixels once and loops the bands inside.
