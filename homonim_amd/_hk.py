@@ -90,6 +90,23 @@ class DevJob(C.Structure):
     ]  # yapf: disable
 
 
+class TwoGridJob(C.Structure):
+    """ hk_two_grid_job: source and reference blocks on different grids, resident on the device (hk_refspace_fit_apply_dev /
+    hk_srcspace_fit_apply_dev) """
+    _fields_ = [
+        ('src', C.c_void_p), ('ref', C.c_void_p), ('corr', C.c_void_p), ('valid', C.c_void_p), ('params', C.c_void_p),
+        ('src_stride', C.c_int64), ('src_band_stride', C.c_int64), ('ref_stride', C.c_int64), ('ref_band_stride', C.c_int64),
+        ('corr_stride', C.c_int64), ('corr_band_stride', C.c_int64), ('valid_stride', C.c_int64), ('valid_band_stride', C.c_int64),
+        ('param_stride', C.c_int64), ('param_band_stride', C.c_int64),
+        ('n_bands', C.c_int32), ('n_param_bands', C.c_int32),
+        ('src_height', C.c_int32), ('src_width', C.c_int32), ('ref_height', C.c_int32), ('ref_width', C.c_int32),
+        ('out_row0', C.c_int32), ('out_col0', C.c_int32), ('out_rows', C.c_int32), ('out_cols', C.c_int32),
+        ('par_row0', C.c_int32), ('par_col0', C.c_int32), ('par_rows', C.c_int32), ('par_cols', C.c_int32),
+        ('stream', C.c_int32), ('reserved', C.c_int32),
+        ('scratch', C.c_void_p), ('scratch_bytes', C.c_uint64),
+    ]  # yapf: disable
+
+
 _P = C.POINTER
 _f32p, _f64p, _u64p = _P(C.c_float), _P(C.c_double), _P(C.c_uint64)
 
@@ -180,6 +197,10 @@ SIGNATURES = {
     'hk_srcspace_fit_apply_valid': (C.c_int, [C.c_void_p, _P(FitDesc), _P(IoDesc), _P(SrcSpaceDesc), C.c_void_p, C.c_int64, C.c_int32,
                                               C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _f32p, C.c_int32,
                                               C.c_void_p, C.c_void_p, _u64p]),
+    'hk_refspace_dev_scratch_bytes': (C.c_uint64, [_P(FitDesc), _P(IoDesc), _P(SpaceDesc), _P(TwoGridJob)]),
+    'hk_srcspace_dev_scratch_bytes': (C.c_uint64, [_P(FitDesc), _P(IoDesc), _P(SrcSpaceDesc), _P(TwoGridJob)]),
+    'hk_refspace_fit_apply_dev': (C.c_int, [C.c_void_p, _P(FitDesc), _P(IoDesc), _P(SpaceDesc), _P(TwoGridJob), _u64p]),
+    'hk_srcspace_fit_apply_dev': (C.c_int, [C.c_void_p, _P(FitDesc), _P(IoDesc), _P(SrcSpaceDesc), _P(TwoGridJob), _u64p]),
     'hk_reproject': (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_double, C.c_double,
                                C.c_double, C.c_double, C.c_int32, _f32p, C.c_int32, C.c_int32, C.c_float]),
     'hk_reproject_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_float,
@@ -264,6 +285,18 @@ def r2_certificate_constants(thresh: float):
     pb, fa, k, kf = C.c_double(), C.c_double(), C.c_float(), C.c_float()
     _check(load_library().hk_r2_certificate_constants(C.c_float(thresh), C.byref(pb), C.byref(fa), C.byref(k), C.byref(kf)))
     return pb.value, fa.value, k.value, kf.value
+
+
+def refspace_dev_scratch_bytes(desc: FitDesc, space: SpaceDesc, job: TwoGridJob, io: Optional[IoDesc] = None) -> int:
+    """ hk_refspace_dev_scratch_bytes (host arithmetic, no device): the scratch of one hk_refspace_fit_apply_dev call, 0 if refused """
+    return int(load_library().hk_refspace_dev_scratch_bytes(C.byref(desc), C.byref(io) if io is not None else None, C.byref(space),
+                                                            C.byref(job)))
+
+
+def srcspace_dev_scratch_bytes(desc: FitDesc, space: SrcSpaceDesc, job: TwoGridJob, io: Optional[IoDesc] = None) -> int:
+    """ hk_srcspace_dev_scratch_bytes: the same for hk_srcspace_fit_apply_dev """
+    return int(load_library().hk_srcspace_dev_scratch_bytes(C.byref(desc), C.byref(io) if io is not None else None, C.byref(space),
+                                                            C.byref(job)))
 
 
 def overview_count(height: int, width: int) -> int:
@@ -469,8 +502,7 @@ def out_nodata_code(out_dtype, out_nodata):
 
 
 def _io_desc(src: np.ndarray, ref: np.ndarray, out_dtype: np.dtype, out_nodata) -> IoDesc:
-    return IoDesc(DTYPE_CODES[src.dtype.name], DTYPE_CODES[ref.dtype.name], DTYPE_CODES[out_dtype.name],
-                  *out_nodata_code(out_dtype, out_nodata))
+    return make_io_desc(src.dtype, ref.dtype, out_dtype, out_nodata)
 
 
 def make_desc(model: str, kernel_shape, find_r2: bool, r2_inpaint_thresh: Optional[float], src_nodata, ref_nodata):
@@ -483,6 +515,86 @@ def make_desc(model: str, kernel_shape, find_r2: bool, r2_inpaint_thresh: Option
     d.src_nodata_mode, d.src_nodata = nodata_code(src_nodata)
     d.ref_nodata_mode, d.ref_nodata = nodata_code(ref_nodata)
     return d
+
+
+class DeviceRaster:
+    """ A raster that lies in device memory: what ``RefSpaceModel.fit_apply_dev`` / ``SrcSpaceModel.fit_apply_dev`` take for their
+    inputs and outputs.  ``dptr``: device address of the first pixel of band 0; ``shape``: (bands, height, width); ``stride`` /
+    ``band_stride``: elements of ``dtype`` between rows / between bands (default: packed).  Inputs also carry their grid:
+    ``transform`` (Affine), ``crs`` and ``nodata``.  The memory is the caller's (``Context.dev_alloc``). """
+
+    def __init__(self, dptr: int, dtype, shape, stride: Optional[int] = None, band_stride: Optional[int] = None, transform=None,
+                 crs=None, nodata=None):
+        self.dptr, self.dtype = int(dptr), np.dtype(dtype)
+        if len(shape) != 3:
+            raise ValueError('`shape` must be (bands, height, width)')
+        self.shape = tuple(int(v) for v in shape)
+        self.stride = int(stride) if stride is not None else self.shape[2]
+        self.band_stride = int(band_stride) if band_stride is not None else self.shape[1] * self.stride
+        self.transform, self.crs, self.nodata = transform, crs, nodata
+
+    @property
+    def res(self):
+        """ (x, y) pixel size, as ``RasterArray.res`` """
+        return abs(self.grid_transform.a), abs(self.grid_transform.e)
+
+    @property
+    def grid_transform(self):
+        """ the transform of an input raster; ValueError where it was not given """
+        if self.transform is None:
+            raise ValueError('a DeviceRaster that is an input (`src`, `ref`) needs its `transform`')
+        return self.transform
+
+
+def make_space_desc(down, up, down_resampling: int, up_resampling: int, mask_partial: bool) -> SpaceDesc:
+    sp = SpaceDesc()
+    for i in range(4):
+        sp.down[i], sp.up[i] = float(down[i]), float(up[i])
+    sp.down_resampling, sp.up_resampling, sp.mask_partial = int(down_resampling), int(up_resampling), int(bool(mask_partial))
+    return sp
+
+
+def make_srcspace_desc(mapping, resampling: int, mask_partial: bool) -> SrcSpaceDesc:
+    sp = SrcSpaceDesc()
+    for i in range(4):
+        sp.map[i] = float(mapping[i])
+    sp.resampling, sp.mask_partial = int(resampling), int(bool(mask_partial))
+    return sp
+
+
+def make_two_grid_job(src: DeviceRaster, ref: DeviceRaster, corr: DeviceRaster, params: Optional[DeviceRaster] = None,
+                      valid: Optional[DeviceRaster] = None, window=None, param_window=None, stream: int = 0, scratch: int = 0,
+                      scratch_bytes: int = 0) -> TwoGridJob:
+    """ hk_two_grid_job from device rasters.  ``corr`` / ``valid`` / ``params``: ``dptr`` is the place of the window's first pixel of
+    band 0 in the caller's raster (``params``: of parameter 0 of band 0; its ``band_stride`` separates consecutive planes, which are
+    ordered parameter-major: plane p * n_bands + b) and ``shape[0]`` of ``params`` is n_param_bands * n_bands.  ``window`` /
+    ``param_window``: (row0, col0, rows, cols) of the source block / of the parameter grid, None for the whole. """
+    j = TwoGridJob()
+    j.src, j.ref, j.corr = src.dptr or None, ref.dptr or None, corr.dptr or None
+    j.valid = (valid.dptr or None) if valid is not None else None
+    j.params = (params.dptr or None) if params is not None else None
+    j.src_stride, j.src_band_stride, j.ref_stride, j.ref_band_stride = src.stride, src.band_stride, ref.stride, ref.band_stride
+    j.corr_stride, j.corr_band_stride = corr.stride, corr.band_stride
+    if valid is not None:
+        j.valid_stride, j.valid_band_stride = valid.stride, valid.band_stride
+    j.n_bands = src.shape[0]
+    if params is not None:
+        j.param_stride, j.param_band_stride = params.stride, params.band_stride
+        j.n_param_bands = params.shape[0] // max(j.n_bands, 1)
+    j.src_height, j.src_width, j.ref_height, j.ref_width = src.shape[1], src.shape[2], ref.shape[1], ref.shape[2]
+    if window is not None:
+        j.out_row0, j.out_col0, j.out_rows, j.out_cols = (int(v) for v in window)
+    if param_window is not None:
+        j.par_row0, j.par_col0, j.par_rows, j.par_cols = (int(v) for v in param_window)
+    j.stream, j.reserved = int(stream), 0
+    j.scratch, j.scratch_bytes = (int(scratch) or None), int(scratch_bytes)
+    return j
+
+
+def make_io_desc(src_dtype, ref_dtype, out_dtype, out_nodata=None) -> IoDesc:
+    """ hk_io_desc from the three dtypes and the output nodata (``out_nodata_code``) """
+    return IoDesc(DTYPE_CODES[np.dtype(src_dtype).name], DTYPE_CODES[np.dtype(ref_dtype).name], DTYPE_CODES[np.dtype(out_dtype).name],
+                  *out_nodata_code(out_dtype, out_nodata))
 
 
 def make_warp_desc(src_def, src_transform, dst_def, dst_transform) -> WarpDesc:
@@ -917,10 +1029,7 @@ class Context:
         src, ref = _as_2d_native(src, 'src'), _as_2d_native(ref, 'ref')
         out_dtype = np.dtype(out_dtype)
         io = _io_desc(src, ref, out_dtype, out_nodata)
-        sp = SpaceDesc()
-        for i in range(4):
-            sp.down[i], sp.up[i] = float(down[i]), float(up[i])
-        sp.down_resampling, sp.up_resampling, sp.mask_partial = int(down_resampling), int(up_resampling), int(mask_partial)
+        sp = make_space_desc(down, up, down_resampling, up_resampling, mask_partial)
         params = np.empty((n_param_bands, *ref.shape), np.float32) if want_params else None
         corr = out_corr if out_corr is not None else np.empty(src.shape, out_dtype)
         assert corr.shape == src.shape and corr.dtype == out_dtype and corr.flags['C_CONTIGUOUS']
@@ -949,10 +1058,7 @@ class Context:
         if out_dtype.name not in DTYPE_CODES:
             raise ValueError(f'unsupported output dtype {out_dtype}')
         io = _io_desc(src, ref, out_dtype, out_nodata)
-        sp = SrcSpaceDesc()
-        for i in range(4):
-            sp.map[i] = float(mapping[i])
-        sp.resampling, sp.mask_partial = int(resampling), int(bool(mask_partial))
+        sp = make_srcspace_desc(mapping, resampling, mask_partial)
         params = np.empty((n_param_bands, *src.shape), np.float32) if want_params else None
         corr = out_corr if out_corr is not None else np.empty(src.shape, out_dtype)
         assert corr.shape == src.shape and corr.dtype == out_dtype and corr.flags['C_CONTIGUOUS']
@@ -967,6 +1073,35 @@ class Context:
         valid = np.empty(src.shape, np.uint8)
         _check(self._lib.hk_srcspace_fit_apply_valid(*head, valid.ctypes.data_as(vp), C.byref(fail)))
         return params, corr, int(fail.value), valid
+
+    def _two_grid_dev(self, entry, desc: FitDesc, sp, job: TwoGridJob, io: Optional[IoDesc]) -> np.ndarray:
+        counts = np.zeros(max(int(job.n_bands), 1), np.uint64)
+        _check(entry(self._h, C.byref(desc), C.byref(io) if io is not None else None, C.byref(sp), C.byref(job),
+                     counts.ctypes.data_as(_u64p)))
+        return counts[:max(int(job.n_bands), 0)]
+
+    def refspace_fit_apply_dev(self, desc: FitDesc, down, up, down_resampling: int, up_resampling: int, mask_partial: bool,
+                               job: TwoGridJob, io: Optional[IoDesc] = None) -> np.ndarray:
+        """ hk_refspace_fit_apply_dev: ``refspace_fit_apply`` of every band of a device-resident job, queued on ``job.stream``; the
+        windows of the corrected, validity and parameter planes go to their places in the caller's device rasters.  -> the per-band
+        r2-mask failure counts (uint64; all 0 unless gain-offset runs with an r2 threshold, the one case in which the call waits). """
+        return self._two_grid_dev(self._lib.hk_refspace_fit_apply_dev, desc,
+                                  make_space_desc(down, up, down_resampling, up_resampling, mask_partial), job, io)
+
+    def srcspace_fit_apply_dev(self, desc: FitDesc, mapping, resampling: int, mask_partial: bool, job: TwoGridJob,
+                               io: Optional[IoDesc] = None) -> np.ndarray:
+        """ hk_srcspace_fit_apply_dev: ``srcspace_fit_apply`` of every band of a device-resident job (see ``refspace_fit_apply_dev``) """
+        return self._two_grid_dev(self._lib.hk_srcspace_fit_apply_dev, desc, make_srcspace_desc(mapping, resampling, mask_partial),
+                                  job, io)
+
+    def refspace_dev_scratch_bytes(self, desc: FitDesc, down, up, down_resampling: int, up_resampling: int, mask_partial: bool,
+                                   job: TwoGridJob, io: Optional[IoDesc] = None) -> int:
+        """ hk_refspace_dev_scratch_bytes: the size of ``job.scratch`` for this call, 0 for arguments the entry would refuse """
+        return refspace_dev_scratch_bytes(desc, make_space_desc(down, up, down_resampling, up_resampling, mask_partial), job, io)
+
+    def srcspace_dev_scratch_bytes(self, desc: FitDesc, mapping, resampling: int, mask_partial: bool, job: TwoGridJob,
+                                   io: Optional[IoDesc] = None) -> int:
+        return srcspace_dev_scratch_bytes(desc, make_srcspace_desc(mapping, resampling, mask_partial), job, io)
 
     def reproject(self, src: np.ndarray, src_nodata, mapping, dst_shape, resampling: int, dst_fill: float) -> np.ndarray:
         """ hk_reproject: (bands, h, w) or (h, w) float32 -> same rank on the destination grid. """

@@ -1248,6 +1248,18 @@ struct FitResults {
     uint8_t* valid_out = nullptr;        // nullable: the validity of the corrected plane (255 / 0), the same window and row stride, ...
     unsigned char* d_valid = nullptr;    // ... on the device rows d_stride bytes apart (FitIo::want_valid)
 };
+// The corrected plane as the output holds it: through the cast where the output has one (FitIo::out_cast), which writes the validity
+// plane beside it (FitIo::want_valid).  *d_out: where the plane then lies, rows d_stride elements of the output dtype apart.
+int cast_fit_results(Slot& sl, const FitIo& f, const FitResults& r, const char** d_out) {
+    *d_out = reinterpret_cast<const char*>(r.d_corr);
+    if (!f.out_cast) return HK_OK;
+    const hk::CastPlane cp = {.in = r.d_corr, .in_stride = r.d_stride, .out = r.d_raw, .out_stride = r.d_stride,
+                              .height = r.height, .width = r.width, .has_nodata = f.out_has_nodata, .nodata = f.out_nodata,
+                              .valid = r.d_valid, .valid_stride = r.d_stride};
+    HK_HIP(f.want_valid ? hk::launch_cast_out_valid(f.odt, cp, sl.stream) : hk::launch_cast_out(f.odt, cp, sl.stream));
+    *d_out = static_cast<const char*>(r.d_raw);
+    return HK_OK;
+}
 // queues the copies of both, and behind them the r2-mask failure counter (nullable d_fail) into the slot's pinned word
 int stage_fit_results(Slot& sl, const FitIo& f, const FitResults& r, const unsigned long long* d_fail) {
     int rc;
@@ -1260,14 +1272,8 @@ int stage_fit_results(Slot& sl, const FitIo& f, const FitResults& r, const unsig
                 return rc;
     if (r.corr_out) {
         const size_t es = hk::dtype_size(f.odt);  // (4 without a cast: the output is float32 then)
-        const char* d_out = reinterpret_cast<const char*>(r.d_corr);
-        if (f.out_cast) {
-            const hk::CastPlane cp = {.in = r.d_corr, .in_stride = r.d_stride, .out = r.d_raw, .out_stride = r.d_stride,
-                                      .height = r.height, .width = r.width, .has_nodata = f.out_has_nodata, .nodata = f.out_nodata,
-                                      .valid = r.d_valid, .valid_stride = r.d_stride};
-            HK_HIP(f.want_valid ? hk::launch_cast_out_valid(f.odt, cp, sl.stream) : hk::launch_cast_out(f.odt, cp, sl.stream));
-            d_out = static_cast<const char*>(r.d_raw);
-        }
+        const char* d_out;
+        if ((rc = cast_fit_results(sl, f, r, &d_out))) return rc;
         if ((rc = stage_d2h(sl, r.corr_out, cw.stride * es, d_out + ((size_t)cw.row0 * r.d_stride + cw.col0) * es, r.d_stride * es,
                             (size_t)cw.cols * es, cw.rows)))
             return rc;
@@ -1278,6 +1284,30 @@ int stage_fit_results(Slot& sl, const FitIo& f, const FitResults& r, const unsig
     if (d_fail) HK_HIP(hipMemcpyAsync(sl.fail_host, d_fail, sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
     return HK_OK;
 }
+// The same results for a caller whose rasters are on the device (params_out, corr_out and valid_out are device pointers here): the
+// windows go to their places by strided device copies, in stream order; valid_stride: bytes between the rows of valid_out.
+int place_fit_results(Slot& sl, const FitIo& f, const FitResults& r, int64_t valid_stride) {
+    int rc;
+    const hk_out_window &pw = r.pw, &cw = r.cw;
+    auto copy = [&](void* dst, size_t d_pitch, const void* src, size_t s_pitch, size_t row_bytes, size_t rows) {
+        return hipMemcpy2DAsync(dst, d_pitch, src, s_pitch, row_bytes, rows, hipMemcpyDeviceToDevice, sl.stream);
+    };
+    if (r.params_out)
+        for (int b = 0; b < r.n_param_bands; ++b)
+            HK_HIP(copy(r.params_out + (int64_t)b * pw.band_stride, pw.param_stride * sizeof(float),
+                        r.d_par + (int64_t)b * r.d_par_band + (int64_t)pw.row0 * r.d_par_stride + pw.col0,
+                        r.d_par_stride * sizeof(float), (size_t)pw.cols * sizeof(float), pw.rows));
+    if (r.corr_out) {
+        const size_t es = hk::dtype_size(f.odt);
+        const char* d_out;
+        if ((rc = cast_fit_results(sl, f, r, &d_out))) return rc;
+        HK_HIP(copy(r.corr_out, cw.stride * es, d_out + ((int64_t)cw.row0 * r.d_stride + cw.col0) * es, r.d_stride * es,
+                    (size_t)cw.cols * es, cw.rows));
+        if (f.want_valid)
+            HK_HIP(copy(r.valid_out, valid_stride, r.d_valid + (int64_t)cw.row0 * r.d_stride + cw.col0, r.d_stride, cw.cols, cw.rows));
+    }
+    return HK_OK;
+}
 
 // mask_partial counts the valid pixels of a (kh+2) x (kw+2) window in an unsigned short (hk_mask.hip)
 int check_mask_kernel(int kh, int kw) {
@@ -1286,10 +1316,8 @@ int check_mask_kernel(int kh, int kw) {
 
 // What hk_refspace_fit_apply and hk_srcspace_fit_apply ask alike of a source block and a reference block on another grid.
 // (The mask_partial refusal cannot be reached today: validate_desc keeps kh <= 255 and kw <= 193, 257 * 195 counts fit.)
-template <class Space>
-int check_two_grids(const hk_ctx* ctx, const hk_fit_desc* desc, const Space* space, const HostGrid& src, const HostGrid& ref,
-                    const void* corr_out) {
-    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+template <class Space, class Grid>
+int check_two_grid_args(const hk_fit_desc* desc, const Space* space, const Grid& src, const Grid& ref, const void* corr_out) {
     int rc = validate_desc(desc);
     if (rc) return rc;
     if (!space || !src.data || !ref.data || !corr_out) return null_arg();
@@ -1297,6 +1325,11 @@ int check_two_grids(const hk_ctx* ctx, const hk_fit_desc* desc, const Space* spa
     if ((rc = check_strides(src.stride, src.width, ref.stride, ref.width))) return rc;
     if (src.height > 65535 || ref.height > 65535) return fail(HK_ERR_UNSUPPORTED, "block taller than 65535 rows");
     return space->mask_partial ? check_mask_kernel(desc->kh, desc->kw) : HK_OK;
+}
+template <class Space>
+int check_two_grids(const hk_ctx* ctx, const hk_fit_desc* desc, const Space* space, const HostGrid& src, const HostGrid& ref,
+                    const void* corr_out) {
+    return ctx ? check_two_grid_args(desc, space, src, ref, corr_out) : fail(HK_ERR_ARG, "ctx is NULL");
 }
 
 // hk_reproject and hk_reproject_dev ask the same of a re-projection between two axis-aligned grids of one CRS; the band count is
@@ -1464,6 +1497,393 @@ int run_host(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const H
         }
     }
     if (c.r2_fail_count) *c.r2_fail_count = n_fail;
+    return HK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Source and reference on DIFFERENT grids: the RefSpace and the SrcSpace chain.  Each chain of launches is stated once, for one
+// band whose blocks are on the device; the host-pointer entries stage their blocks into the slab, run it and stage the results
+// out, the device-resident entries run it band by band on the caller's planes and place the windows by device copies.
+
+// One plane of a raster on the device: rows `stride` elements of its dtype apart.  staged: the host form put it where the chain's
+// slab expects a staged block (a float32 plane in its place, another dtype in the raw plane, on the slab's stride)
+struct DevGrid {
+    const void* data;
+    int64_t stride;
+    int32_t height, width;
+    bool staged = false;
+};
+
+// The plane `g` of dtype `dt` as the float32 plane `dplane` (row stride `dstride`) that the chains read.  A staged float32 plane
+// lies there already; float32 elsewhere is copied.  Another dtype is converted by cast_in, which reads whole quads of a row: a
+// staged plane (rows padded in the slab) and a caller's plane whose width is a multiple of the quad are read where they lie, any
+// other goes through a copy in `raw` (the slab's stride, in elements of the dtype) -- a caller owns `width` elements of its last row
+// and no more.
+int bring_in(Slot& s, const DevGrid& g, int dt, float* dplane, void* raw, int64_t dstride) {
+    const size_t es = hk::dtype_size(dt);
+    const void* from = g.data;
+    int64_t from_stride = g.stride;
+    if (!dt) {
+        if (!g.staged)
+            HK_HIP(hipMemcpy2DAsync(dplane, dstride * es, from, from_stride * es, (size_t)g.width * es, g.height, hipMemcpyDeviceToDevice, s.stream));
+        return HK_OK;
+    }
+    if (!g.staged && g.width % hk::PX != 0) {
+        HK_HIP(hipMemcpy2DAsync(raw, dstride * es, from, from_stride * es, (size_t)g.width * es, g.height, hipMemcpyDeviceToDevice, s.stream));
+        from = raw, from_stride = dstride;
+    }
+    HK_HIP(hk::launch_cast_in(dt, {.in = from, .in_stride = from_stride, .out = dplane, .out_stride = dstride, .height = g.height,
+                                   .width = g.width}, s.stream));
+    return HK_OK;
+}
+
+// ... and a host block staged to where `d` says (the slab)
+int stage_grid(Slot& s, const HostGrid& g, int dt, const DevGrid& d) {
+    const size_t es = hk::dtype_size(dt);
+    return stage_h2d(s, const_cast<void*>(d.data), d.stride * es, g.data, g.stride * es, (size_t)g.width * es, g.height);
+}
+
+int check_refspace(const hk_space_desc* space) {
+    for (int m : {space->down_resampling, space->up_resampling})
+        if (!resampling_built(m)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not built", m);
+    if (!(space->down[0] > 0 && space->down[2] > 0 && space->up[0] > 0 && space->up[2] > 0))
+        return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
+    return HK_OK;
+}
+int check_srcspace(const hk_srcspace_desc* space) {
+    if (!resampling_built(space->resampling)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not built", space->resampling);
+    if (!(space->map[0] > 0 && space->map[2] > 0)) return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
+    return HK_OK;
+}
+
+// Where a chain left one band's results in its slab (FitResults' device side), and the band's r2-mask failure counter
+struct ChainOut {
+    const float* d_par;  // the parameter planes, d_par_band elements apart, rows d_par_stride apart
+    int64_t d_par_stride, d_par_band;
+    float* d_corr;       // the corrected plane, rows d_stride apart; d_raw / d_valid: where the cast writes
+    void* d_raw;
+    unsigned char* d_valid;
+    int64_t d_stride;
+    unsigned long long* d_fail;
+};
+
+// The slab of the RefSpace chain for one band: planes on the source grid (row stride ss) and on the reference grid (rs)
+struct RefSpaceSlab {
+    int64_t ss, rs;
+    bool fused_up;  // bilinear / cubic_spline parameters are up-sampled inside the apply kernel (no full-resolution parameter planes)
+    size_t o_src, o_ref, o_ds, o_gain, o_off, o_r2, o_gus, o_ous, o_corr, o_rowtab, o_vs, o_cov, o_mk, o_mkf, o_keep, o_cnt;
+    size_t o_raw_s, o_raw_r, o_raw_o, o_valid, o_aux, o_ws, total;
+};
+RefSpaceSlab refspace_slab(const hk_fit_desc* desc, const FitIo& f, const hk_space_desc* space, int32_t sh, int32_t sw, int32_t rh,
+                           int32_t rw) {
+    RefSpaceSlab s;
+    const int64_t ss = s.ss = row_align(sw), rs = s.rs = row_align(rw);
+    const size_t splane = (size_t)ss * sh * 4, rplane = (size_t)rs * rh * 4;
+    SlabLayout L;
+    s.o_src = L.take(splane), s.o_ref = L.take(rplane), s.o_ds = L.take(rplane);
+    s.o_gain = L.take(rplane), s.o_off = L.take(rplane), s.o_r2 = f.r2 ? L.take(rplane) : 0;
+    s.fused_up = (space->up_resampling == 1 || space->up_resampling == 3) && rw >= 4 && space->up[0] <= 1.0 + 1e-9 &&
+                 space->up[2] <= 1.0 + 1e-9 && (long long)rh * rs < 0x7fffffffLL;
+    const bool fused_up = s.fused_up, partial = space->mask_partial != 0;
+    s.o_gus = fused_up ? 0 : L.take(splane), s.o_ous = fused_up ? 0 : L.take(splane), s.o_corr = L.take(splane);
+    s.o_rowtab = fused_up ? L.take(hk::upsample_apply_workspace_bytes(sh)) : 0;
+    s.o_vs = partial ? L.take(splane) : 0, s.o_cov = partial ? L.take(rplane) : 0;
+    s.o_mk = partial ? L.take((size_t)rs * rh) : 0;
+    s.o_mkf = partial ? L.take(rplane) : 0, s.o_keep = partial ? L.take(splane) : 0;
+    s.o_cnt = partial ? L.take((size_t)rs * rh * 2) : 0;
+    s.o_raw_s = f.sdt ? L.take((size_t)ss * sh * hk::dtype_size(f.sdt)) : 0;
+    s.o_raw_r = f.rdt ? L.take((size_t)rs * rh * hk::dtype_size(f.rdt)) : 0;
+    s.o_raw_o = f.out_cast ? L.take((size_t)ss * sh * hk::dtype_size(f.odt)) : 0;
+    s.o_valid = f.want_valid ? L.take((size_t)ss * sh) : 0;
+    s.o_aux = L.take(256);
+    s.o_ws = desc->model == HK_MODEL_GAIN_BLK_OFFSET ? L.take(hk::norm_workspace_bytes(1, rh, rw)) : 0;
+    s.total = L.total;
+    return s;
+}
+
+// RefSpaceModel.fit + RefSpaceModel.apply (homonim/kernel_model.py:476-503) of one band: sg / rg are its source and reference
+// block on the device (dtypes f.sdt / f.rdt), `base` the slab L describes.  Queues on the slot's stream and waits only where
+// fit_on_device does (gain-offset with an r2 threshold: once, for the failure count).
+int refspace_chain(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, const FitIo& f, const hk_space_desc* space, const RefSpaceSlab& L,
+                   char* base, const DevGrid& sg, const DevGrid& rg, ChainOut* out) {
+    int rc;
+    const int64_t ss = L.ss, rs = L.rs;
+    const int32_t src_height = sg.height, src_width = sg.width, ref_height = rg.height, ref_width = rg.width;
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+    float *d_src = F(L.o_src), *d_ref = F(L.o_ref), *d_ds = F(L.o_ds), *d_gain = F(L.o_gain), *d_off = F(L.o_off);
+    float *d_r2 = f.r2 ? F(L.o_r2) : nullptr, *d_gus = F(L.o_gus), *d_ous = F(L.o_ous), *d_corr = F(L.o_corr);
+    const int64_t par_band = (int64_t)(L.o_off - L.o_gain) / 4;  // gain -> offset plane, elements
+    double* d_norm = reinterpret_cast<double*>(base + L.o_aux);
+    unsigned long long* d_fail = reinterpret_cast<unsigned long long*>(base + L.o_aux + 64);
+    const float nan = std::nanf("");
+
+    if ((rc = bring_in(sl, sg, f.sdt, d_src, base + L.o_raw_s, ss))) return rc;
+    if ((rc = bring_in(sl, rg, f.rdt, d_ref, base + L.o_raw_r, rs))) return rc;
+
+    // one plane from the source grid down to the reference grid, or from there up to the source grid
+    auto resample = [&](int mode, bool down, const float* from, int nd_mode, float nodata, float* to, float fill) {
+        const DevGrid &a = down ? sg : rg, &b = down ? rg : sg;  // from a's shape to b's, on the slab's strides
+        const hk::ResamplePlanes p = {.src = from, .dst = to, .src_stride = down ? ss : rs, .src_band_stride = 0, .dst_stride = down ? rs : ss,
+                                      .dst_band_stride = 0, .sh = a.height, .sw = a.width, .dh = b.height, .dw = b.width, .n_bands = 1,
+                                      .nd_mode = nd_mode, .nodata = nodata, .dst_fill = fill};
+        const double* m = down ? space->down : space->up;
+        return hk::launch_resample(mode, p, m[0], m[1], m[2], m[3], sl.stream);
+    };
+
+    // RefSpaceModel.fit (:476-482): source -> reference grid (nodata nan), then the base-class fit there
+    HK_HIP(resample(space->down_resampling, true, d_src, desc->src_nodata_mode, desc->src_nodata, d_ds, nan));
+    hk_fit_desc fd = *desc;
+    fd.src_nodata_mode = HK_NODATA_NAN, fd.src_nodata = nan;
+    const hk_dev_job job = {.src = d_ds, .ref = d_ref, .gain = d_gain, .offset = d_off, .r2 = d_r2, .norm = d_norm,
+                            .fail_count = reinterpret_cast<uint64_t*>(d_fail), .n_bands = 1, .height = ref_height, .width = ref_width,
+                            .stride = rs};
+    if ((rc = fit_on_device(ctx, sl, &fd, job, base + L.o_ws))) return rc;
+
+    // RefSpaceModel.apply (:484-503): gain / offset -> source grid, re-mask, apply
+    if (!L.fused_up)
+        for (int b = 0; b < 2; ++b)
+            HK_HIP(resample(space->up_resampling, false, b ? d_off : d_gain, HK_NODATA_NAN, nan, b ? d_ous : d_gus, nan));
+    const float* d_keep = nullptr;
+    if (space->mask_partial) {
+        // _full_coverage_mask (:375-409): source mask --average--> reference grid (>= 1) & parameter mask, eroded by
+        // (kh+2) x (kw+2); back to the source grid with `nearest` (nodata 0)
+        HK_HIP(hk::launch_valid_plane({.in = d_src, .in_stride = ss, .nd_mode = desc->src_nodata_mode, .nodata = desc->src_nodata,
+                                       .out = F(L.o_vs), .out_stride = ss, .height = src_height, .width = src_width}, sl.stream));
+        HK_HIP(resample(hk::RS_AVERAGE, true, F(L.o_vs), HK_NODATA_NONE, 0.f, F(L.o_cov), 0.f));
+        unsigned char* d_mk = reinterpret_cast<unsigned char*>(base + L.o_mk);
+        // the parameters as two bands: gain, and offset one band stride further on
+        HK_HIP(hk::launch_partial_mask({.in = F(L.o_cov), .nd_mode = hk::ND_COVERAGE, .params = d_gain, .n_bands = 2, .band_stride = par_band,
+                                        .height = ref_height, .width = ref_width, .stride = rs, .kh = desc->kh, .kw = desc->kw, .mask_out = d_mk},
+                                       reinterpret_cast<unsigned short*>(base + L.o_cnt), sl.stream));
+        HK_HIP(hk::launch_cast_in(HK_DTYPE_U8, {.in = d_mk, .in_stride = rs, .out = F(L.o_mkf), .out_stride = rs, .height = ref_height,
+                                                .width = ref_width}, sl.stream));
+        HK_HIP(resample(hk::RS_NEAREST, false, F(L.o_mkf), HK_NODATA_NONE, 0.f, F(L.o_keep), 0.f));
+        d_keep = F(L.o_keep);
+    }
+    if (L.fused_up) {
+        const double* up = space->up;
+        HK_HIP(hk::launch_upsample_apply(space->up_resampling, {.src = d_src, .src_stride = ss, .nd_mode = desc->src_nodata_mode,
+                                         .nodata = desc->src_nodata, .gain = d_gain, .offset = d_off, .par_stride = rs, .ph = ref_height,
+                                         .pw = ref_width, .keep = d_keep, .keep_stride = ss, .out = d_corr, .out_stride = ss,
+                                         .height = src_height, .width = src_width, .kx = up[0], .ox = up[1], .ky = up[2], .oy = up[3]},
+                                         base + L.o_rowtab, sl.stream));
+    } else {
+        HK_HIP(hk::launch_apply_space({.src = d_src, .src_stride = ss, .nd_mode = desc->src_nodata_mode, .nodata = desc->src_nodata,
+                                       .gain = d_gus, .offset = d_ous, .par_stride = ss, .keep = d_keep, .out = d_corr, .out_stride = ss,
+                                       .height = src_height, .width = src_width}, sl.stream));
+    }
+    // the parameters on the reference grid, the corrected block on the source grid
+    *out = {.d_par = d_gain, .d_par_stride = rs, .d_par_band = par_band, .d_corr = d_corr, .d_raw = base + L.o_raw_o,
+            .d_valid = reinterpret_cast<unsigned char*>(base + L.o_valid), .d_stride = ss, .d_fail = d_fail};
+    return HK_OK;
+}
+
+// The slab of the SrcSpace chain for one band; want_params: the (masked) parameter planes are an output
+struct SrcSpaceSlab {
+    int64_t ss, rs, pbs;  // pbs: band stride of the parameter planes, elements
+    int n_par;
+    bool typed_foot;      // `average` reads the reference as it lies there (footprint_typed_kernel): no float32 copy, no valid plane
+    size_t o_src, o_rus, o_par, o_corr, o_cov, o_cnt, o_mpar, o_ref, o_vr, o_raw_s, o_raw_r, o_raw_o, o_valid, o_aux, o_ws, total;
+};
+SrcSpaceSlab srcspace_slab(const hk_fit_desc* desc, const FitIo& f, const hk_srcspace_desc* space, bool want_params, int32_t sh,
+                           int32_t sw, int32_t rh, int32_t rw) {
+    SrcSpaceSlab s;
+    const int64_t ss = s.ss = row_align(sw), rs = s.rs = row_align(rw);
+    const size_t splane = (size_t)ss * sh * 4, rplane = (size_t)rs * rh * 4;
+    const bool partial = space->mask_partial != 0;
+    const int n_par = s.n_par = f.r2 ? 3 : 2;
+    const bool typed_foot = s.typed_foot = space->resampling == hk::RS_AVERAGE;
+    SlabLayout L;
+    s.o_src = L.take(splane), s.o_rus = L.take(splane);
+    s.o_par = L.take(splane);  // gain, offset, (r2): planes of one size, one band stride apart
+    for (int b = 1; b < n_par; ++b) L.take(splane);
+    s.o_corr = L.take(splane);
+    s.o_cov = partial ? L.take(splane) : 0, s.o_cnt = partial ? L.take((size_t)ss * sh * 2) : 0;
+    s.o_mpar = (partial && want_params) ? L.take(splane) : 0;  // the masked parameters
+    if (partial && want_params)
+        for (int b = 1; b < n_par; ++b) L.take(splane);
+    s.o_ref = (!typed_foot || !f.rdt) ? L.take(rplane) : 0, s.o_vr = (partial && !typed_foot) ? L.take(rplane) : 0;
+    s.o_raw_s = f.sdt ? L.take((size_t)ss * sh * hk::dtype_size(f.sdt)) : 0;
+    s.o_raw_r = f.rdt ? L.take((size_t)rs * rh * hk::dtype_size(f.rdt)) : 0;
+    s.o_raw_o = f.out_cast ? L.take((size_t)ss * sh * hk::dtype_size(f.odt)) : 0;
+    s.o_valid = f.want_valid ? L.take((size_t)ss * sh) : 0;
+    s.o_aux = L.take(256);
+    s.o_ws = desc->model == HK_MODEL_GAIN_BLK_OFFSET ? L.take(hk::norm_workspace_bytes(1, sh, sw)) : 0;
+    s.pbs = (int64_t)((splane + 255) / 256 * 256 / 4);
+    s.total = L.total;
+    return s;
+}
+
+// SrcSpaceModel.fit + KernelModel.apply (homonim/kernel_model.py:506-535, :442-463) of one band, as refspace_chain states its own.
+// With `average` the reference is read where rg says it lies, on rg's stride.
+int srcspace_chain(hk_ctx* ctx, Slot& sl, const hk_fit_desc* desc, const FitIo& f, const hk_srcspace_desc* space, bool want_params,
+                   const SrcSpaceSlab& L, char* base, const DevGrid& sg, const DevGrid& rg, ChainOut* out) {
+    int rc;
+    const int64_t ss = L.ss, rs = L.rs, pbs = L.pbs;
+    const int32_t src_height = sg.height, src_width = sg.width, ref_height = rg.height, ref_width = rg.width;
+    const bool r2 = f.r2, partial = space->mask_partial != 0;
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+    float *d_src = F(L.o_src), *d_rus = F(L.o_rus), *d_gain = F(L.o_par), *d_off = d_gain + pbs, *d_r2 = r2 ? d_gain + 2 * pbs : nullptr;
+    float* d_corr = F(L.o_corr);
+    double* d_norm = reinterpret_cast<double*>(base + L.o_aux);
+    unsigned long long* d_fail = reinterpret_cast<unsigned long long*>(base + L.o_aux + 64);
+    const float nan = std::nanf("");
+    const double* m = space->map;
+
+    if ((rc = bring_in(sl, sg, f.sdt, d_src, base + L.o_raw_s, ss))) return rc;
+
+    // SrcSpaceModel.fit (:520): reference -> source grid (nodata nan), and for mask_partial the coverage of its valid mask
+    // (_full_coverage_mask, :375-399: mask_ra re-projected with `average`, no nodata)
+    if (L.typed_foot) {
+        HK_HIP(hk::launch_footprint_typed(f.rdt, {.src = rg.data, .src_stride = rg.stride, .sh = ref_height, .sw = ref_width,
+                                                  .nd_mode = desc->ref_nodata_mode, .nodata = desc->ref_nodata, .value = d_rus,
+                                                  .coverage = partial ? F(L.o_cov) : nullptr, .dst_stride = ss, .dh = src_height,
+                                                  .dw = src_width, .fill = nan, .kx = m[0], .ox = m[1], .ky = m[2], .oy = m[3]},
+                                          sl.stream));
+    } else {
+        float* d_ref = F(L.o_ref);
+        if ((rc = bring_in(sl, rg, f.rdt, d_ref, base + L.o_raw_r, rs))) return rc;
+        hk::ResamplePlanes p = {.src = d_ref, .dst = d_rus, .src_stride = rs, .src_band_stride = 0, .dst_stride = ss, .dst_band_stride = 0,
+                                .sh = rg.height, .sw = rg.width, .dh = sg.height, .dw = sg.width, .n_bands = 1,
+                                .nd_mode = desc->ref_nodata_mode, .nodata = desc->ref_nodata, .dst_fill = nan};
+        HK_HIP(hk::launch_resample(space->resampling, p, m[0], m[1], m[2], m[3], sl.stream));
+        if (partial) {
+            HK_HIP(hk::launch_valid_plane({.in = d_ref, .in_stride = rs, .nd_mode = desc->ref_nodata_mode, .nodata = desc->ref_nodata,
+                                           .out = F(L.o_vr), .out_stride = rs, .height = ref_height, .width = ref_width}, sl.stream));
+            p.src = F(L.o_vr), p.dst = F(L.o_cov), p.nd_mode = HK_NODATA_NONE, p.nodata = 0.f, p.dst_fill = 0.f;
+            HK_HIP(hk::launch_resample(hk::RS_AVERAGE, p, m[0], m[1], m[2], m[3], sl.stream));
+        }
+    }
+
+    // KernelModel.fit on the source grid; without mask_partial the fused kernel applies as well: the parameters are nodata
+    // wherever the source is, so that masking them with the source mask (:533) changes nothing
+    hk_fit_desc fd = *desc;
+    fd.ref_nodata_mode = HK_NODATA_NAN, fd.ref_nodata = nan;
+    const hk_dev_job job = {.src = d_src, .ref = d_rus, .gain = d_gain, .offset = d_off, .r2 = d_r2, .corr = partial ? nullptr : d_corr,
+                            .norm = d_norm, .fail_count = reinterpret_cast<uint64_t*>(d_fail), .n_bands = 1, .height = src_height,
+                            .width = src_width, .stride = ss};
+    if ((rc = fit_on_device(ctx, sl, &fd, job, base + L.o_ws))) return rc;
+
+    float* d_pout = d_gain;
+    if (partial) {
+        // :526-531: coverage >= 1 & "has gain or offset", eroded by (kh+2) x (kw+2), on ALL parameter bands; then KernelModel.apply
+        d_pout = want_params ? F(L.o_mpar) : nullptr;
+        HK_HIP(hk::launch_partial_mask({.in = F(L.o_cov), .nd_mode = hk::ND_COVERAGE, .params = d_gain, .n_bands = L.n_par, .band_stride = pbs,
+                                        .src = d_src, .height = src_height, .width = src_width, .stride = ss, .kh = desc->kh,
+                                        .kw = desc->kw, .params_out = d_pout, .corr_out = d_corr},
+                                       reinterpret_cast<unsigned short*>(base + L.o_cnt), sl.stream));
+    }
+    *out = {.d_par = d_pout, .d_par_stride = ss, .d_par_band = pbs, .d_corr = d_corr, .d_raw = base + L.o_raw_o,
+            .d_valid = reinterpret_cast<unsigned char*>(base + L.o_valid), .d_stride = ss, .d_fail = d_fail};
+    return HK_OK;
+}
+
+// The two store windows of a device-resident two-grid job as place_fit_results takes them (FitResults::cw, ::pw): all zero in
+// the job = the whole grid.  Resolved here, once.
+struct TwoGridWindows {
+    hk_out_window cw, pw;
+};
+
+// What a device-resident two-grid job asks beyond what the host forms check: n_bands, the reserved word, windows (resolved into
+// *w), strides, planes that overlap, and -- with a context -- the stream and the caller's scratch (`need` bytes).  `ph` x `pw`: the
+// parameter grid.  ctx NULL: the scratch-size helpers, which have no stream pool and do not look at the job's own scratch.
+int check_two_grid_job(const hk_ctx* ctx, const hk_two_grid_job* j, int32_t ph, int32_t pw, uint64_t need, TwoGridWindows* w) {
+    if (j->n_bands < 1) return fail(HK_ERR_ARG, "n_bands must be at least 1");
+    if (j->reserved != 0) return fail(HK_ERR_ARG, "hk_two_grid_job.reserved must be 0");
+    // -> 0: the window inside a grid of rows x cols (all zero: the whole grid), 1: outside it
+    auto resolve = [](int32_t row0, int32_t col0, int32_t nrows, int32_t ncols, int32_t rows, int32_t cols, hk_out_window* out) {
+        if (!(row0 || col0 || nrows || ncols)) nrows = rows, ncols = cols;
+        if (row0 < 0 || col0 < 0 || nrows < 1 || ncols < 1 || row0 + (int64_t)nrows > rows || col0 + (int64_t)ncols > cols) return 1;
+        out->row0 = row0, out->col0 = col0, out->rows = nrows, out->cols = ncols;
+        return 0;
+    };
+    if (resolve(j->out_row0, j->out_col0, j->out_rows, j->out_cols, j->src_height, j->src_width, &w->cw))
+        return fail(HK_ERR_ARG, "output window outside the block");
+    if (resolve(j->par_row0, j->par_col0, j->par_rows, j->par_cols, ph, pw, &w->pw))
+        return fail(HK_ERR_ARG, "parameter window outside the parameter grid");
+    w->cw.stride = j->corr_stride, w->cw.band_stride = 0, w->cw.param_stride = 0;
+    w->pw.stride = w->pw.param_stride = j->param_stride, w->pw.band_stride = (int64_t)j->n_bands * j->param_band_stride;
+    const hk_out_window &cw = w->cw, &pwin = w->pw;
+    if (j->corr_stride < cw.cols || (j->valid && j->valid_stride < cw.cols) || (j->params && j->param_stride < pwin.cols))
+        return fail(HK_ERR_ARG, "output row stride smaller than the window");
+    // planes of one array must not overlap: a band stride spans at least the rows that are read or written
+    auto spans = [](int64_t band_stride, int64_t stride, int64_t rows, int64_t cols) { return band_stride >= (rows - 1) * stride + cols; };
+    if (j->n_bands > 1 && (!spans(j->src_band_stride, j->src_stride, j->src_height, j->src_width) ||
+                           !spans(j->ref_band_stride, j->ref_stride, j->ref_height, j->ref_width) ||
+                           !spans(j->corr_band_stride, j->corr_stride, cw.rows, cw.cols) ||
+                           (j->valid && !spans(j->valid_band_stride, j->valid_stride, cw.rows, cw.cols))))
+        return fail(HK_ERR_ARG, "band stride smaller than a plane: the planes overlap");
+    if (j->params && !spans(j->param_band_stride, j->param_stride, pwin.rows, pwin.cols))
+        return fail(HK_ERR_ARG, "band stride smaller than a plane: the planes overlap");
+    if (!ctx) return HK_OK;
+    if (const int rc = check_stream(ctx, j->stream)) return rc;
+    if (j->scratch) {
+        if ((uintptr_t)j->scratch & 255) return fail(HK_ERR_ARG, "job scratch must be 256-byte aligned");
+        if (j->scratch_bytes < need)
+            return fail(HK_ERR_ARG, "job scratch of %llu bytes is smaller than the %llu bytes this job needs", (unsigned long long)j->scratch_bytes,
+                        (unsigned long long)need);
+    }
+    return HK_OK;
+}
+
+// Everything a device-resident two-grid call is refused for, in the host form's order and words where the check is shared; the
+// slab of one band (*L) and the resolved windows (*w).  ctx NULL: the scratch-size helpers (check_two_grid_job).
+template <class Space, class Slab>
+int check_two_grid_dev(const hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const Space* space, const hk_two_grid_job* j,
+                       FitIo* f, Slab* L, TwoGridWindows* w) {
+    if (!j) return null_arg();
+    const DevGrid sg = {j->src, j->src_stride, j->src_height, j->src_width}, rg = {j->ref, j->ref_stride, j->ref_height, j->ref_width};
+    int rc = check_two_grid_args(desc, space, sg, rg, j->corr);
+    if (rc) return rc;
+    if constexpr (std::is_same_v<Space, hk_space_desc>) rc = check_refspace(space);
+    else rc = check_srcspace(space);
+    if (rc || (rc = check_fit_io(desc, io, j->params, j->n_param_bands, f, j->corr, j->valid))) return rc;
+    int32_t ph, pw;
+    if constexpr (std::is_same_v<Space, hk_space_desc>) {
+        *L = refspace_slab(desc, *f, space, j->src_height, j->src_width, j->ref_height, j->ref_width);
+        ph = j->ref_height, pw = j->ref_width;
+    } else {
+        *L = srcspace_slab(desc, *f, space, j->params != nullptr, j->src_height, j->src_width, j->ref_height, j->ref_width);
+        ph = j->src_height, pw = j->src_width;
+    }
+    return check_two_grid_job(ctx, j, ph, pw, L->total, w);
+}
+
+// One device-resident two-grid call: the refusals, the scratch, then `chain` band by band on the job's stream, each band's
+// windows placed behind it.  The bands share one band's slab in stream order.
+template <class Space, class Slab, class Chain>
+int two_grid_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const Space* space, const hk_two_grid_job* j,
+                 uint64_t* n_fail_out, Chain chain) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    FitIo f;
+    Slab L;
+    TwoGridWindows w;
+    int rc = check_two_grid_dev(ctx, desc, io, space, j, &f, &L, &w);
+    if (rc) return rc;
+    DevEnter entered(ctx, j->stream);
+    HK_ENTER(ctx);
+    Slot& sl = ctx->slots[j->stream];
+    char* base = static_cast<char*>(j->scratch);
+    if (!base) {
+        std::lock_guard<std::mutex> lk(ctx->mu);  // (as ensure_stream_ws: the slab may be reallocated)
+        if ((rc = ensure_dev(sl, L.total))) return rc;
+        base = static_cast<char*>(sl.dev);
+    }
+    const bool counts = desc->model == HK_MODEL_GAIN_OFFSET && desc->has_r2_thresh;
+    const size_t ses = hk::dtype_size(f.sdt), res = hk::dtype_size(f.rdt), oes = hk::dtype_size(f.odt);
+    for (int64_t b = 0; b < j->n_bands; ++b) {
+        const DevGrid sg = {static_cast<const char*>(j->src) + b * j->src_band_stride * (int64_t)ses, j->src_stride, j->src_height, j->src_width};
+        const DevGrid rg = {static_cast<const char*>(j->ref) + b * j->ref_band_stride * (int64_t)res, j->ref_stride, j->ref_height, j->ref_width};
+        ChainOut o;
+        if ((rc = chain(sl, f, L, base, sg, rg, &o))) return rc;
+        if (n_fail_out) n_fail_out[b] = counts ? *sl.fail_host : 0;  // (fit_on_device has waited for it)
+        FitResults res_b = {.params_out = j->params ? j->params + b * j->param_band_stride : nullptr, .n_param_bands = j->n_param_bands,
+                            .d_par = o.d_par, .d_par_stride = o.d_par_stride, .d_par_band = o.d_par_band, .pw = w.pw,
+                            .corr_out = static_cast<char*>(j->corr) + b * j->corr_band_stride * (int64_t)oes, .d_corr = o.d_corr,
+                            .d_raw = o.d_raw, .d_stride = o.d_stride, .height = j->src_height, .width = j->src_width, .cw = w.cw,
+                            .valid_out = j->valid ? j->valid + b * j->valid_band_stride : nullptr, .d_valid = o.d_valid};
+        if ((rc = place_fit_results(sl, f, res_b, j->valid_stride))) return rc;
+    }
     return HK_OK;
 }
 
@@ -1645,111 +2065,28 @@ int hk_refspace_fit_apply_valid(hk_ctx* ctx, const hk_fit_desc* desc, const hk_i
                                 int32_t n_param_bands, void* corr_out, uint8_t* valid_out, uint64_t* r2_fail_count) {
     const HostGrid sg = {src, src_stride, src_height, src_width}, rg = {ref, ref_stride, ref_height, ref_width};
     int rc = check_two_grids(ctx, desc, space, sg, rg, corr_out);
-    if (rc) return rc;
-    for (int m : {space->down_resampling, space->up_resampling})
-        if (!resampling_built(m)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not built", m);
-    if (!(space->down[0] > 0 && space->down[2] > 0 && space->up[0] > 0 && space->up[2] > 0))
-        return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
+    if (rc || (rc = check_refspace(space))) return rc;
     FitIo f;
     if ((rc = check_fit_io(desc, io, params_out, n_param_bands, &f, corr_out, valid_out))) return rc;
     HK_ENTER(ctx);
 
-    const int64_t ss = row_align(sg.width), rs = row_align(rg.width);  // row strides of the source and the reference grid
-    const size_t splane = (size_t)ss * sg.height * 4, rplane = (size_t)rs * rg.height * 4;
-    SlabLayout L;
-    const size_t o_src = L.take(splane), o_ref = L.take(rplane), o_ds = L.take(rplane);
-    const size_t o_gain = L.take(rplane), o_off = L.take(rplane), o_r2 = f.r2 ? L.take(rplane) : 0;
-    // bilinear / cubic_spline parameters are up-sampled inside the apply kernel (no full-resolution parameter planes)
-    const bool fused_up = (space->up_resampling == 1 || space->up_resampling == 3) && rg.width >= 4 &&
-                          space->up[0] <= 1.0 + 1e-9 && space->up[2] <= 1.0 + 1e-9 &&
-                          (long long)rg.height * rs < 0x7fffffffLL;
-    const size_t o_gus = fused_up ? 0 : L.take(splane), o_ous = fused_up ? 0 : L.take(splane), o_corr = L.take(splane);
-    const size_t o_rowtab = fused_up ? L.take(hk::upsample_apply_workspace_bytes(sg.height)) : 0;
-    const size_t o_vs = space->mask_partial ? L.take(splane) : 0, o_cov = space->mask_partial ? L.take(rplane) : 0;
-    const size_t o_mk = space->mask_partial ? L.take((size_t)rs * rg.height) : 0;
-    const size_t o_mkf = space->mask_partial ? L.take(rplane) : 0, o_keep = space->mask_partial ? L.take(splane) : 0;
-    const size_t o_cnt = space->mask_partial ? L.take((size_t)rs * rg.height * 2) : 0;
-    const size_t o_raw_s = f.sdt ? L.take((size_t)ss * sg.height * hk::dtype_size(f.sdt)) : 0;
-    const size_t o_raw_r = f.rdt ? L.take((size_t)rs * rg.height * hk::dtype_size(f.rdt)) : 0;
-    const size_t o_raw_o = f.out_cast ? L.take((size_t)ss * sg.height * hk::dtype_size(f.odt)) : 0;
-    const size_t o_valid = f.want_valid ? L.take((size_t)ss * sg.height) : 0;
-    const size_t o_aux = L.take(256);
-    const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
-    const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, rg.height, rg.width)) : 0;
-
+    const RefSpaceSlab L = refspace_slab(desc, f, space, src_height, src_width, ref_height, ref_width);
     HostCall hc(ctx, L.total);
     if (hc.rc) return hc.rc;
     Slot& sl = hc.sl;
-    auto F = [&](size_t off) { return hc.at<float>(off); };
-    float *d_src = F(o_src), *d_ref = F(o_ref), *d_ds = F(o_ds), *d_gain = F(o_gain), *d_off = F(o_off);
-    float *d_r2 = f.r2 ? F(o_r2) : nullptr, *d_gus = F(o_gus), *d_ous = F(o_ous), *d_corr = F(o_corr);
-    const int64_t par_band = (int64_t)(o_off - o_gain) / 4;  // gain -> offset plane, elements
-    double* d_norm = hc.at<double>(o_aux);
-    unsigned long long* d_fail = hc.at<unsigned long long>(o_aux + 64);
-    const float nan = std::nanf("");
+    // stage in: each block where the chain's bring_in expects a staged one, on the slab's strides
+    const DevGrid d_sg = {hc.at(f.sdt ? L.o_raw_s : L.o_src), L.ss, src_height, src_width, /*staged=*/true};
+    const DevGrid d_rg = {hc.at(f.rdt ? L.o_raw_r : L.o_ref), L.rs, ref_height, ref_width, /*staged=*/true};
+    if ((rc = stage_grid(sl, sg, f.sdt, d_sg)) || (rc = stage_grid(sl, rg, f.rdt, d_rg))) return rc;
+    ChainOut o;
+    if ((rc = refspace_chain(ctx, sl, desc, f, space, L, hc.at(0), d_sg, d_rg, &o))) return rc;
 
-    if ((rc = stage_in(sl, sg, f.sdt, d_src, hc.at(o_raw_s), ss))) return rc;
-    if ((rc = stage_in(sl, rg, f.rdt, d_ref, hc.at(o_raw_r), rs))) return rc;
-
-    // one plane from the source grid down to the reference grid, or from there up to the source grid
-    auto resample = [&](int mode, bool down, const float* from, int nd_mode, float nodata, float* to, float fill) {
-        const HostGrid &a = down ? sg : rg, &b = down ? rg : sg;  // from a's shape to b's, on the slab's strides
-        const hk::ResamplePlanes p = {.src = from, .dst = to, .src_stride = down ? ss : rs, .src_band_stride = 0, .dst_stride = down ? rs : ss,
-                                      .dst_band_stride = 0, .sh = a.height, .sw = a.width, .dh = b.height, .dw = b.width, .n_bands = 1,
-                                      .nd_mode = nd_mode, .nodata = nodata, .dst_fill = fill};
-        const double* m = down ? space->down : space->up;
-        return hk::launch_resample(mode, p, m[0], m[1], m[2], m[3], sl.stream);
-    };
-
-    // RefSpaceModel.fit (:476-482): source -> reference grid (nodata nan), then the base-class fit there
-    HK_HIP(resample(space->down_resampling, true, d_src, desc->src_nodata_mode, desc->src_nodata, d_ds, nan));
-    hk_fit_desc fd = *desc;
-    fd.src_nodata_mode = HK_NODATA_NAN, fd.src_nodata = nan;
-    const hk_dev_job job = {.src = d_ds, .ref = d_ref, .gain = d_gain, .offset = d_off, .r2 = d_r2, .norm = d_norm,
-                            .fail_count = reinterpret_cast<uint64_t*>(d_fail), .n_bands = 1, .height = ref_height, .width = ref_width,
-                            .stride = rs};
-    if ((rc = fit_on_device(ctx, sl, &fd, job, hc.at(o_ws)))) return rc;
-
-    // RefSpaceModel.apply (:484-503): gain / offset -> source grid, re-mask, apply
-    if (!fused_up)
-        for (int b = 0; b < 2; ++b)
-            HK_HIP(resample(space->up_resampling, false, b ? d_off : d_gain, HK_NODATA_NAN, nan, b ? d_ous : d_gus, nan));
-    const float* d_keep = nullptr;
-    if (space->mask_partial) {
-        // _full_coverage_mask (:375-409): source mask --average--> reference grid (>= 1) & parameter mask, eroded by
-        // (kh+2) x (kw+2); back to the source grid with `nearest` (nodata 0)
-        HK_HIP(hk::launch_valid_plane({.in = d_src, .in_stride = ss, .nd_mode = desc->src_nodata_mode, .nodata = desc->src_nodata,
-                                       .out = F(o_vs), .out_stride = ss, .height = src_height, .width = src_width}, sl.stream));
-        HK_HIP(resample(hk::RS_AVERAGE, true, F(o_vs), HK_NODATA_NONE, 0.f, F(o_cov), 0.f));
-        unsigned char* d_mk = hc.at<unsigned char>(o_mk);
-        // the parameters as two bands: gain, and offset one band stride further on
-        HK_HIP(hk::launch_partial_mask({.in = F(o_cov), .nd_mode = hk::ND_COVERAGE, .params = d_gain, .n_bands = 2, .band_stride = par_band,
-                                        .height = ref_height, .width = ref_width, .stride = rs, .kh = desc->kh, .kw = desc->kw, .mask_out = d_mk},
-                                       hc.at<unsigned short>(o_cnt), sl.stream));
-        HK_HIP(hk::launch_cast_in(HK_DTYPE_U8, {.in = d_mk, .in_stride = rs, .out = F(o_mkf), .out_stride = rs, .height = ref_height,
-                                                .width = ref_width}, sl.stream));
-        HK_HIP(resample(hk::RS_NEAREST, false, F(o_mkf), HK_NODATA_NONE, 0.f, F(o_keep), 0.f));
-        d_keep = F(o_keep);
-    }
-    if (fused_up) {
-        const double* up = space->up;
-        HK_HIP(hk::launch_upsample_apply(space->up_resampling, {.src = d_src, .src_stride = ss, .nd_mode = desc->src_nodata_mode,
-                                         .nodata = desc->src_nodata, .gain = d_gain, .offset = d_off, .par_stride = rs, .ph = ref_height,
-                                         .pw = ref_width, .keep = d_keep, .keep_stride = ss, .out = d_corr, .out_stride = ss,
-                                         .height = src_height, .width = src_width, .kx = up[0], .ox = up[1], .ky = up[2], .oy = up[3]},
-                                         hc.at(o_rowtab), sl.stream));
-    } else {
-        HK_HIP(hk::launch_apply_space({.src = d_src, .src_stride = ss, .nd_mode = desc->src_nodata_mode, .nodata = desc->src_nodata,
-                                       .gain = d_gus, .offset = d_ous, .par_stride = ss, .keep = d_keep, .out = d_corr, .out_stride = ss,
-                                       .height = src_height, .width = src_width}, sl.stream));
-    }
-
-    // the parameters on the reference grid, the corrected block on the source grid, both whole and packed
-    const FitResults res = {.params_out = params_out, .n_param_bands = n_param_bands, .d_par = d_gain, .d_par_stride = rs,
-                            .d_par_band = par_band, .pw = whole_block(ref_height, ref_width), .corr_out = corr_out, .d_corr = d_corr,
-                            .d_raw = hc.at(o_raw_o), .d_stride = ss, .height = src_height, .width = src_width,
-                            .cw = whole_block(src_height, src_width), .valid_out = valid_out, .d_valid = hc.at<unsigned char>(o_valid)};
-    if ((rc = stage_fit_results(sl, f, res, d_fail))) return rc;
+    // stage out: the parameters on the reference grid, the corrected block on the source grid, both whole and packed
+    const FitResults res = {.params_out = params_out, .n_param_bands = n_param_bands, .d_par = o.d_par, .d_par_stride = o.d_par_stride,
+                            .d_par_band = o.d_par_band, .pw = whole_block(ref_height, ref_width), .corr_out = corr_out, .d_corr = o.d_corr,
+                            .d_raw = o.d_raw, .d_stride = o.d_stride, .height = src_height, .width = src_width,
+                            .cw = whole_block(src_height, src_width), .valid_out = valid_out, .d_valid = o.d_valid};
+    if ((rc = stage_fit_results(sl, f, res, o.d_fail))) return rc;
     if ((rc = stage_finish(sl))) return rc;
     if (r2_fail_count) *r2_fail_count = *sl.fail_host;
     return HK_OK;
@@ -1769,102 +2106,29 @@ int hk_srcspace_fit_apply_valid(hk_ctx* ctx, const hk_fit_desc* desc, const hk_i
                                 int32_t n_param_bands, void* corr_out, uint8_t* valid_out, uint64_t* r2_fail_count) {
     const HostGrid sg = {src, src_stride, src_height, src_width}, rg = {ref, ref_stride, ref_height, ref_width};
     int rc = check_two_grids(ctx, desc, space, sg, rg, corr_out);
-    if (rc) return rc;
-    if (!resampling_built(space->resampling)) return fail(HK_ERR_UNSUPPORTED, "resampling %d is not built", space->resampling);
-    if (!(space->map[0] > 0 && space->map[2] > 0)) return fail(HK_ERR_UNSUPPORTED, "flipped or degenerate grid mapping");
+    if (rc || (rc = check_srcspace(space))) return rc;
     FitIo f;
     if ((rc = check_fit_io(desc, io, params_out, n_param_bands, &f, corr_out, valid_out))) return rc;
-    const bool r2 = f.r2, partial = space->mask_partial != 0;
     HK_ENTER(ctx);
 
-    const int64_t ss = row_align(sg.width), rs = row_align(rg.width);  // row strides of the source and the reference grid
-    const size_t splane = (size_t)ss * sg.height * 4, rplane = (size_t)rs * rg.height * 4;
-    const int n_par = r2 ? 3 : 2;
-    // `average` reads the reference as it was uploaded (footprint_typed_kernel): no float32 copy, no valid plane
-    const bool typed_foot = space->resampling == hk::RS_AVERAGE;
-    SlabLayout L;
-    const size_t o_src = L.take(splane), o_rus = L.take(splane);
-    const size_t o_par = L.take(splane);  // gain, offset, (r2): planes of one size, one band stride apart
-    for (int b = 1; b < n_par; ++b) L.take(splane);
-    const size_t o_corr = L.take(splane);
-    const size_t o_cov = partial ? L.take(splane) : 0, o_cnt = partial ? L.take((size_t)ss * sg.height * 2) : 0;
-    const size_t o_mpar = (partial && params_out) ? L.take(splane) : 0;  // the masked parameters
-    if (partial && params_out)
-        for (int b = 1; b < n_par; ++b) L.take(splane);
-    const size_t o_ref = (!typed_foot || !f.rdt) ? L.take(rplane) : 0, o_vr = (partial && !typed_foot) ? L.take(rplane) : 0;
-    const size_t o_raw_s = f.sdt ? L.take((size_t)ss * sg.height * hk::dtype_size(f.sdt)) : 0;
-    const size_t o_raw_r = f.rdt ? L.take((size_t)rs * rg.height * hk::dtype_size(f.rdt)) : 0;
-    const size_t o_raw_o = f.out_cast ? L.take((size_t)ss * sg.height * hk::dtype_size(f.odt)) : 0;
-    const size_t o_valid = f.want_valid ? L.take((size_t)ss * sg.height) : 0;
-    const size_t o_aux = L.take(256);
-    const bool blk = desc->model == HK_MODEL_GAIN_BLK_OFFSET;
-    const size_t o_ws = blk ? L.take(hk::norm_workspace_bytes(1, sg.height, sg.width)) : 0;
-
+    const SrcSpaceSlab L = srcspace_slab(desc, f, space, params_out != nullptr, src_height, src_width, ref_height, ref_width);
     HostCall hc(ctx, L.total);
     if (hc.rc) return hc.rc;
     Slot& sl = hc.sl;
-    auto F = [&](size_t off) { return hc.at<float>(off); };
-    const long long pbs = (long long)((splane + 255) / 256 * 256 / 4);  // band stride of the parameter planes, elements
-    float *d_src = F(o_src), *d_rus = F(o_rus), *d_gain = F(o_par), *d_off = d_gain + pbs, *d_r2 = r2 ? d_gain + 2 * pbs : nullptr;
-    float* d_corr = F(o_corr);
-    double* d_norm = hc.at<double>(o_aux);
-    unsigned long long* d_fail = hc.at<unsigned long long>(o_aux + 64);
-    const float nan = std::nanf("");
-    const double* m = space->map;
+    // stage in: each block where the chain expects a staged one, on the slab's strides (`average` reads the reference there as it is)
+    const DevGrid d_sg = {hc.at(f.sdt ? L.o_raw_s : L.o_src), L.ss, src_height, src_width, /*staged=*/true};
+    const DevGrid d_rg = {hc.at(f.rdt ? L.o_raw_r : L.o_ref), L.rs, ref_height, ref_width, /*staged=*/true};
+    if ((rc = stage_grid(sl, sg, f.sdt, d_sg)) || (rc = stage_grid(sl, rg, f.rdt, d_rg))) return rc;
+    ChainOut o;
+    if ((rc = srcspace_chain(ctx, sl, desc, f, space, params_out != nullptr, L, hc.at(0), d_sg, d_rg, &o))) return rc;
 
-    if ((rc = stage_in(sl, sg, f.sdt, d_src, hc.at(o_raw_s), ss))) return rc;
-
-    // SrcSpaceModel.fit (:520): reference -> source grid (nodata nan), and for mask_partial the coverage of its valid mask
-    // (_full_coverage_mask, :375-399: mask_ra re-projected with `average`, no nodata)
-    if (typed_foot) {
-        const size_t es = hk::dtype_size(f.rdt);
-        void* d_raw = hc.at(f.rdt ? o_raw_r : o_ref);
-        if ((rc = stage_h2d(sl, d_raw, rs * es, ref, ref_stride * es, (size_t)ref_width * es, ref_height))) return rc;
-        HK_HIP(hk::launch_footprint_typed(f.rdt, {.src = d_raw, .src_stride = rs, .sh = ref_height, .sw = ref_width,
-                                                  .nd_mode = desc->ref_nodata_mode, .nodata = desc->ref_nodata, .value = d_rus,
-                                                  .coverage = partial ? F(o_cov) : nullptr, .dst_stride = ss, .dh = src_height,
-                                                  .dw = src_width, .fill = nan, .kx = m[0], .ox = m[1], .ky = m[2], .oy = m[3]},
-                                          sl.stream));
-    } else {
-        float* d_ref = F(o_ref);
-        if ((rc = stage_in(sl, rg, f.rdt, d_ref, hc.at(o_raw_r), rs))) return rc;
-        hk::ResamplePlanes p = {.src = d_ref, .dst = d_rus, .src_stride = rs, .src_band_stride = 0, .dst_stride = ss, .dst_band_stride = 0,
-                                .sh = rg.height, .sw = rg.width, .dh = sg.height, .dw = sg.width, .n_bands = 1,
-                                .nd_mode = desc->ref_nodata_mode, .nodata = desc->ref_nodata, .dst_fill = nan};
-        HK_HIP(hk::launch_resample(space->resampling, p, m[0], m[1], m[2], m[3], sl.stream));
-        if (partial) {
-            HK_HIP(hk::launch_valid_plane({.in = d_ref, .in_stride = rs, .nd_mode = desc->ref_nodata_mode, .nodata = desc->ref_nodata,
-                                           .out = F(o_vr), .out_stride = rs, .height = ref_height, .width = ref_width}, sl.stream));
-            p.src = F(o_vr), p.dst = F(o_cov), p.nd_mode = HK_NODATA_NONE, p.nodata = 0.f, p.dst_fill = 0.f;
-            HK_HIP(hk::launch_resample(hk::RS_AVERAGE, p, m[0], m[1], m[2], m[3], sl.stream));
-        }
-    }
-
-    // KernelModel.fit on the source grid; without mask_partial the fused kernel applies as well: the parameters are nodata
-    // wherever the source is, so that masking them with the source mask (:533) changes nothing
-    hk_fit_desc fd = *desc;
-    fd.ref_nodata_mode = HK_NODATA_NAN, fd.ref_nodata = nan;
-    const hk_dev_job job = {.src = d_src, .ref = d_rus, .gain = d_gain, .offset = d_off, .r2 = d_r2, .corr = partial ? nullptr : d_corr,
-                            .norm = d_norm, .fail_count = reinterpret_cast<uint64_t*>(d_fail), .n_bands = 1, .height = src_height,
-                            .width = src_width, .stride = ss};
-    if ((rc = fit_on_device(ctx, sl, &fd, job, hc.at(o_ws)))) return rc;
-
-    float* d_pout = d_gain;
-    if (partial) {
-        // :526-531: coverage >= 1 & "has gain or offset", eroded by (kh+2) x (kw+2), on ALL parameter bands; then KernelModel.apply
-        d_pout = params_out ? F(o_mpar) : nullptr;
-        HK_HIP(hk::launch_partial_mask({.in = F(o_cov), .nd_mode = hk::ND_COVERAGE, .params = d_gain, .n_bands = n_par, .band_stride = pbs,
-                                        .src = d_src, .height = src_height, .width = src_width, .stride = ss, .kh = desc->kh,
-                                        .kw = desc->kw, .params_out = d_pout, .corr_out = d_corr},
-                                       hc.at<unsigned short>(o_cnt), sl.stream));
-    }
-
+    // stage out: the parameters and the corrected block on the source grid, whole and packed
     const hk_out_window whole = whole_block(src_height, src_width);
-    const FitResults res = {.params_out = params_out, .n_param_bands = n_param_bands, .d_par = d_pout, .d_par_stride = ss,
-                            .d_par_band = pbs, .pw = whole, .corr_out = corr_out, .d_corr = d_corr, .d_raw = hc.at(o_raw_o),
-                            .d_stride = ss, .height = src_height, .width = src_width, .cw = whole, .valid_out = valid_out,
-                            .d_valid = hc.at<unsigned char>(o_valid)};
-    if ((rc = stage_fit_results(sl, f, res, d_fail))) return rc;
+    const FitResults res = {.params_out = params_out, .n_param_bands = n_param_bands, .d_par = o.d_par, .d_par_stride = o.d_par_stride,
+                            .d_par_band = o.d_par_band, .pw = whole, .corr_out = corr_out, .d_corr = o.d_corr, .d_raw = o.d_raw,
+                            .d_stride = o.d_stride, .height = src_height, .width = src_width, .cw = whole, .valid_out = valid_out,
+                            .d_valid = o.d_valid};
+    if ((rc = stage_fit_results(sl, f, res, o.d_fail))) return rc;
     if ((rc = stage_finish(sl))) return rc;
     if (r2_fail_count) *r2_fail_count = *sl.fail_host;
     return HK_OK;
@@ -1876,6 +2140,39 @@ int hk_srcspace_fit_apply(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc
                           int32_t n_param_bands, void* corr_out, uint64_t* r2_fail_count) {
     return hk_srcspace_fit_apply_valid(ctx, desc, io, space, src, src_stride, src_height, src_width, ref, ref_stride, ref_height,
                                        ref_width, params_out, n_param_bands, corr_out, /*valid_out=*/nullptr, r2_fail_count);
+}
+
+uint64_t hk_refspace_dev_scratch_bytes(const hk_fit_desc* desc, const hk_io_desc* io, const hk_space_desc* space,
+                                       const hk_two_grid_job* job) {
+    FitIo f;
+    RefSpaceSlab L;
+    TwoGridWindows w;
+    return check_two_grid_dev(nullptr, desc, io, space, job, &f, &L, &w) ? 0 : L.total;
+}
+uint64_t hk_srcspace_dev_scratch_bytes(const hk_fit_desc* desc, const hk_io_desc* io, const hk_srcspace_desc* space,
+                                       const hk_two_grid_job* job) {
+    FitIo f;
+    SrcSpaceSlab L;
+    TwoGridWindows w;
+    return check_two_grid_dev(nullptr, desc, io, space, job, &f, &L, &w) ? 0 : L.total;
+}
+
+int hk_refspace_fit_apply_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_space_desc* space,
+                              const hk_two_grid_job* job, uint64_t* n_fail_out) {
+    return two_grid_dev<hk_space_desc, RefSpaceSlab>(
+        ctx, desc, io, space, job, n_fail_out,
+        [&](Slot& sl, const FitIo& f, const RefSpaceSlab& L, char* base, const DevGrid& sg, const DevGrid& rg, ChainOut* o) {
+            return refspace_chain(ctx, sl, desc, f, space, L, base, sg, rg, o);
+        });
+}
+
+int hk_srcspace_fit_apply_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io, const hk_srcspace_desc* space,
+                              const hk_two_grid_job* job, uint64_t* n_fail_out) {
+    return two_grid_dev<hk_srcspace_desc, SrcSpaceSlab>(
+        ctx, desc, io, space, job, n_fail_out,
+        [&](Slot& sl, const FitIo& f, const SrcSpaceSlab& L, char* base, const DevGrid& sg, const DevGrid& rg, ChainOut* o) {
+            return srcspace_chain(ctx, sl, desc, f, space, job->params != nullptr, L, base, sg, rg, o);
+        });
 }
 
 int hk_reproject(hk_ctx* ctx, const float* src, int32_t n_bands, int32_t src_height, int32_t src_width,

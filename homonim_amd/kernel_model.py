@@ -192,6 +192,29 @@ class KernelModel:
         )
         return n_fail
 
+    def _two_grid_dev_job(self, src, ref, corr, params, valid, window, param_window, out_nodata, stream, scratch):
+        """ What ``RefSpaceModel.fit_apply_dev`` / ``SrcSpaceModel.fit_apply_dev`` share: the refusals of ``fit_apply`` (two CRSs,
+        rotated grids) in its words, and (desc, io, job) of the device call. """
+        from types import SimpleNamespace
+        a, b = (SimpleNamespace(crs=r.crs, transform=r.grid_transform, shape=r.shape[1:]) for r in (src, ref))
+        _require_one_crs(a, b)
+        if src.shape[0] != ref.shape[0] or corr.shape[0] != src.shape[0]:
+            raise ValueError(f'`src`, `ref` and `corr` must hold the same number of bands, got {src.shape[0]}, {ref.shape[0]} and {corr.shape[0]}')
+        if params is not None:
+            if params.dtype != np.float32:
+                raise ValueError('`params` must be float32')
+            if params.shape[0] != self.n_param * src.shape[0]:
+                raise ValueError(f'`params` must hold {self.n_param} planes per band ({self.n_param * src.shape[0]}), got {params.shape[0]}')
+        if valid is not None and valid.dtype != np.uint8:
+            raise ValueError('`valid` must be uint8')
+        if corr.dtype.name not in _hk.DTYPE_CODES:
+            raise ValueError(f'unsupported output dtype {corr.dtype}')
+        desc = self._desc(src, ref)
+        io = _hk.make_io_desc(src.dtype, ref.dtype, corr.dtype, out_nodata)
+        scratch_ptr, scratch_bytes = scratch if scratch is not None else (0, 0)
+        job = _hk.make_two_grid_job(src, ref, corr, params, valid, window, param_window, stream, scratch_ptr, scratch_bytes)
+        return desc, io, job
+
     def block_norm(self, src_ra: RasterArray, ref_ra: RasterArray) -> np.ndarray:
         """ The [gain, offset] block normalisation of gain-blk-offset (kernel_model.py:216-229), float64[2]. """
         return self.context.block_norm(self._desc(src_ra, ref_ra), self._band(src_ra, 'src_ra'),
@@ -220,6 +243,25 @@ def _require_one_crs(a: RasterArray, b: RasterArray):
     if (is_rotated(a.transform) or is_rotated(b.transform)) and not _same_grid(a, b):
         raise NotImplementedError('re-projection between rotated / sheared grids is not built for the kernel models: bring the '
                                   'raster north-up with RasterArray.reproject first (RasterFuse does)')
+
+
+def _dev_grid_mapping(to_raster, from_raster, host_form: str):
+    """ ``geo.grid_mapping`` between the grids of two device rasters, `src` and `ref`.  A raster on the device is the caller's and is
+    not flipped for it; ``host_form``: what ``fit_apply`` of the class does with host arrays whose grids run opposite ways. """
+    from homonim_amd.geo import grid_mapping
+    kx, ox, ky, oy = grid_mapping(to_raster.grid_transform, from_raster.grid_transform)
+    if kx < 0 or ky < 0:
+        raise ValueError(f"'src' and 'ref' have opposite orientations along an axis: a device raster is not flipped for the caller "
+                         f'({host_form}); flip one of them on the device first')
+    return kx, ox, ky, oy
+
+
+def _same_dev_grid(a, b) -> bool:
+    return a.grid_transform == b.grid_transform and a.shape[1:] == b.shape[1:] and a.crs == b.crs
+
+
+_SHARED_GRID_DEV = ('`src` and `ref` share one grid: the device-resident form of that is hk_fit_apply_dev (Context.fit_apply_dev), '
+                    'which already serves it')
 
 
 def _full_coverage_mask(model: KernelModel, in_mask_ra: RasterArray, param_ra: RasterArray) -> np.ndarray:
@@ -301,6 +343,25 @@ class RefSpaceModel(KernelModel):
         return (*self._wrap(corr, params, src_ra, ref_ra, out_nodata, want_params), *valid)
 
 
+    def fit_apply_dev(self, src, ref, corr, params=None, valid=None, window=None, param_window=None,
+                      out_nodata: Optional[float] = RasterArray.default_nodata, stream: int = 0, scratch=None) -> np.ndarray:
+        """ ``fit_apply`` of every band of two rasters that are resident on the device (hk_refspace_fit_apply_dev): nothing is
+        staged, the call queues its work on pooled stream ``stream`` and returns the per-band r2-mask failure counts.
+        ``src`` / ``ref``: ``_hk.DeviceRaster`` blocks with their transform, CRS and nodata; ``corr`` (the output dtype is its
+        dtype), ``valid`` (uint8) and ``params`` (float32, ``n_param`` x bands planes, parameter-major, on the REFERENCE grid):
+        device rasters whose ``dptr`` is the place of the window's first pixel.  ``window`` / ``param_window``: (row0, col0, rows,
+        cols) of the source block / the reference block that is stored, None for the whole.  ``scratch``: (dptr, bytes) of
+        ``Context.refspace_dev_scratch_bytes`` bytes, or None for the stream's own.  The bytes are ``fit_apply``'s, band by band. """
+        if _same_dev_grid(src, ref) and not self._mask_partial:
+            raise ValueError(_SHARED_GRID_DEV)
+        desc, io, job = self._two_grid_dev_job(src, ref, corr, params, valid, window, param_window, out_nodata, stream, scratch)
+        down = self._get_resampling(src.res, ref.res)
+        up = self._get_resampling(ref.res, src.res)
+        down_map, up_map = (_dev_grid_mapping(a, b, 'fit_apply passes such host arrays on and the library refuses their mapping')
+                            for a, b in ((src, ref), (ref, src)))
+        return self.context.refspace_fit_apply_dev(desc, down_map, up_map, int(down), int(up), self._mask_partial, job, io)
+
+
 class SrcSpaceModel(KernelModel):
     """ Parameters estimated on the source grid (kernel_model.py:506-535): the reference block is re-sampled to it. """
 
@@ -365,3 +426,15 @@ class SrcSpaceModel(KernelModel):
         if want_valid:
             return corr_ra, (param_ra if want_params else None), (valid[0] if valid.ndim == 3 else valid)
         return corr_ra, (param_ra if want_params else None)
+
+    def fit_apply_dev(self, src, ref, corr, params=None, valid=None, window=None, param_window=None,
+                      out_nodata: Optional[float] = RasterArray.default_nodata, stream: int = 0, scratch=None) -> np.ndarray:
+        """ ``RefSpaceModel.fit_apply_dev`` for this model (hk_srcspace_fit_apply_dev): the parameters, and ``param_window``, are on
+        the SOURCE grid.  A shared grid is refused: without ``mask_partial`` hk_fit_apply_dev serves it, with it ``fit_apply`` runs a
+        host sequence that has no device-resident form. """
+        if _same_dev_grid(src, ref):
+            raise ValueError(_SHARED_GRID_DEV if not self._mask_partial else
+                             '`src` and `ref` share one grid: SrcSpaceModel with mask_partial has no device-resident form there')
+        desc, io, job = self._two_grid_dev_job(src, ref, corr, params, valid, window, param_window, out_nodata, stream, scratch)
+        mapping = _dev_grid_mapping(ref, src, 'fit_apply flips the host array')
+        return self.context.srcspace_fit_apply_dev(desc, mapping, int(self._get_resampling(ref.res, src.res)), self._mask_partial, job, io)

@@ -81,7 +81,9 @@ typedef struct {
  * them up by symbol (dlsym) and does without where they are absent.  hk_deflate_tiles_pred and hk_deflate_tiles_pred_dev were
  * added the same way, and so were hk_dataset_mask and hk_dataset_mask_dev (plain scalar arguments, no struct), and the forms that
  * carry validity planes: hk_fit_apply_block_valid, hk_refspace_fit_apply_valid, hk_srcspace_fit_apply_valid, hk_overviews_valid and
- * hk_overviews_valid_dev (the structs they take are those of the entries they extend).
+ * hk_overviews_valid_dev (the structs they take are those of the entries they extend).  The device-resident two-grid entries
+ * (hk_refspace_fit_apply_dev, hk_srcspace_fit_apply_dev, hk_refspace_dev_scratch_bytes, hk_srcspace_dev_scratch_bytes, with the new
+ * struct hk_two_grid_job) were added the same way.
  * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
 #define HK_ABI_VERSION 12
 int hk_abi_version(void);
@@ -741,6 +743,65 @@ int hk_inflate_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const voi
 int hk_lzw_image_dev(hk_ctx* ctx, const hk_inflate_layout* layout, const void* streams_dev, const int64_t* offsets_dev,
                      const int64_t* sizes_dev, void* work_dev, void* out_dev, int64_t stride, int64_t band_stride,
                      int32_t* status_dev, int32_t stream);
+
+/* hk_refspace_fit_apply_valid / hk_srcspace_fit_apply_valid on device-resident rasters: source and reference blocks on DIFFERENT
+ * grids of one CRS, many bands per call, typed planes on the caller's strides, store windows, a named stream, caller-owned scratch.
+ * The result is the host form's, byte for byte: for every band b, the planes the host entry returns for that band's blocks under
+ * the same desc, io and space, cut to the windows, lie in corr, valid and params afterwards; nothing outside the windows, between
+ * rows or between planes is written.  Both forms run one chain of launches (the host form is staging in, that chain, staging out),
+ * so no allowance is involved.
+ *   Strides  : any value >= the width; planes are aligned to their element only, and of a plane's last row only `width` elements
+ *              need to exist: nothing past a row's last pixel is read.  Every input plane is brought into scratch laid out as the
+ *              host form lays out its slab: float32 by a strided device copy, another dtype by the conversion kernel -- which
+ *              reads whole quads of a row, so it reads the caller's plane only where the width is a multiple of 4 and a strided
+ *              device copy of the plane (in scratch) otherwise.  The SrcSpace chain's reference under `average` is read where it
+ *              lies, pixel by pixel, whatever its dtype and stride.  All address arithmetic is 64-bit: planes may lie 2^32
+ *              elements and more apart.
+ *   Windows  : act at the last stage only -- the whole block is computed (in-painting and mask_partial need it), converted to the
+ *              output dtype in scratch (the conversion kernels store whole quads of a row, so they do not write into the caller's
+ *              raster), and the windows of the corrected, validity and parameter planes are put in place by strided device copies.
+ *   Bands    : run one after the other in stream order on job->stream and share one band's worth of scratch.
+ *   Waiting  : the call only queues work and returns, except for gain-offset with an r2 threshold, where it waits for the stream once
+ *              per band to read that band's failure count (and in-paints where it is not 0, as hk_fit does).  n_fail_out[b] is that
+ *              count, and 0 for every other configuration.  The in-painting's own workspace is the stream's, never `scratch`.
+ *   Streams  : hk_dev_job's rules apply unchanged -- jobs on one stream are issued by one host thread at a time, host-pointer calls
+ *              lease the same pooled streams, and a call waits while its stream is leased.  With scratch == NULL the slab is the
+ *              stream's own staging slab, grown as needed (growing it waits for the stream).
+ *   Refusals : before anything is launched; the host form's status and text wherever the check is shared.  Also HK_ERR_ARG:
+ *              n_bands < 1; reserved not 0; n_param_bands not what the model configuration gives (with params); a stride below its width (or its
+ *              window's); band strides that make planes overlap; a window outside its grid; valid without corr; a stream index
+ *              outside the pool; scratch not 256-byte aligned or smaller than hk_*_dev_scratch_bytes() (the text names the size).
+ * hk_*_dev_scratch_bytes: the size of `scratch` for this call (a multiple of 256), 0 for arguments the entry would refuse; the
+ * job's own scratch fields are not looked at.  Plain host arithmetic (no device needed). */
+typedef struct {
+    const void* src;      /* device: n_bands planes of io->src_dtype (float32 when io is NULL), first pixel of the source block */
+    const void* ref;      /* device: n_bands planes of io->ref_dtype, first pixel of the reference block */
+    void* corr;           /* device: io->out_dtype; the place of the corrected WINDOW's first pixel in the caller's raster */
+    uint8_t* valid;       /* device, nullable: n_bands planes, 255 / 0 as hk_fit_apply_block_valid defines; the same window */
+    float* params;        /* device, nullable: parameter p of band b is the plane params + (p * n_bands + b) * param_band_stride
+                             (the band order of the reference's parameter file); the place of the PARAMETER window's first pixel */
+    int64_t src_stride, src_band_stride, ref_stride, ref_band_stride;        /* elements of the respective dtype */
+    int64_t corr_stride, corr_band_stride, valid_stride, valid_band_stride;  /* valid_*: bytes */
+    int64_t param_stride, param_band_stride;
+    int32_t n_bands, n_param_bands;
+    int32_t src_height, src_width, ref_height, ref_width;
+    int32_t out_row0, out_col0, out_rows, out_cols;  /* window of the source-grid block stored to corr / valid; all 0: the whole block */
+    int32_t par_row0, par_col0, par_rows, par_cols;  /* window of the parameter grid (refspace: the reference block's; srcspace: the
+                                                        source block's) stored to params; all 0: the whole grid */
+    int32_t stream;       /* index into the context's stream pool, as in hk_dev_job */
+    int32_t reserved;     /* 0 */
+    void* scratch;        /* device, nullable: hk_*_dev_scratch_bytes() bytes, 256-byte aligned, the caller's until the stream has
+                             passed this call; NULL: the stream's own scratch, grown as needed */
+    uint64_t scratch_bytes;
+} hk_two_grid_job;
+uint64_t hk_refspace_dev_scratch_bytes(const hk_fit_desc* desc, const hk_io_desc* io, const hk_space_desc* space,
+                                       const hk_two_grid_job* job);
+uint64_t hk_srcspace_dev_scratch_bytes(const hk_fit_desc* desc, const hk_io_desc* io, const hk_srcspace_desc* space,
+                                       const hk_two_grid_job* job);
+int hk_refspace_fit_apply_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io /* nullable */, const hk_space_desc* space,
+                              const hk_two_grid_job* job, uint64_t* n_fail_out /* host, nullable: n_bands counts */);
+int hk_srcspace_fit_apply_dev(hk_ctx* ctx, const hk_fit_desc* desc, const hk_io_desc* io /* nullable */,
+                              const hk_srcspace_desc* space, const hk_two_grid_job* job, uint64_t* n_fail_out);
 
 /* HIP events on the pooled streams, so callers time exactly the stream the kernels run on. */
 int hk_event_create(hk_ctx* ctx, hk_event** ev);
