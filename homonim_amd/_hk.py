@@ -160,6 +160,12 @@ SIGNATURES = {
                                   C.c_int64, _f32p, C.c_int64]),
     'hk_dataset_mask_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                       C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]),
+    'hk_fill_planes_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double,
+                                     C.c_int32]),
+    'hk_boundless_window_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                          C.c_int64, C.c_int32]),
+    'hk_dev_mem_info': (C.c_int, [C.c_void_p, _u64p, _u64p]),
     'hk_deflate_bound': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int64), _P(C.c_int64)]),
     'hk_deflate_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
                                    C.c_void_p, C.c_int64, _P(C.c_int64), _P(C.c_int64)]),
@@ -1589,6 +1595,44 @@ class Context:
         _check(self._lib.hk_dataset_mask_dev(self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height,
                                              width, stride, band_stride, C.c_void_p(mask_dptr), int(mask_kind), mask_stride,
                                              C.c_void_p(out_dptr), out_stride, out_band_stride, stream))
+
+    def fill_planes_dev(self, planes_dptr: int, dtype, n_bands: int, height: int, width: int, stride: int, band_stride: int, value,
+                        stream: int = 0):
+        """ Queue the typed prefill of ``n_bands`` device-resident planes of dtype ``dtype`` (strides in elements): ``value`` -- NaN
+        allowed for the float types -- into ``width`` samples of every row, nothing into the row padding (hk_fill_planes_dev;
+        asynchronous). """
+        _check(self._lib.hk_fill_planes_dev(self._h, C.c_void_p(planes_dptr), DTYPE_CODES[np.dtype(dtype).name], n_bands, height, width,
+                                            stride, band_stride, float(value), stream))
+
+    def boundless_window_dev(self, raster: 'DeviceRaster', window, out_dptr: int, out_stride: Optional[int] = None,
+                             out_band_stride: Optional[int] = None, stream: int = 0) -> 'DeviceRaster':
+        """ Queue the window ``(row_off, col_off, height, width)`` of a device-resident raster -- it may hang over the raster or miss it
+        -- into ``out_dptr``, all bands in one launch (hk_boundless_window_dev; asynchronous): what ``RasterFuse._read_boundless``
+        gives on the host.  A window inside the raster is a copy in the raster's dtype under the raster's nodata.  One that reaches
+        beyond it: a raster with a numeric nodata gives a window of its own dtype with the nodata outside; one without a nodata
+        value, or with NaN, gives float32 with NaN outside.  -> the window as a ``DeviceRaster`` with that dtype and nodata (grid
+        and CRS are not set). """
+        row_off, col_off, height, width = (int(v) for v in window)
+        mode, value = nodata_code(raster.nodata)
+        inside = row_off >= 0 and col_off >= 0 and row_off + height <= raster.shape[1] and col_off + width <= raster.shape[2]
+        to_float = mode != NODATA_VALUE and not inside
+        if inside:   # (no fill is written)
+            mode, value = NODATA_VALUE, 0.0
+        elif not to_float:   # the fill as numpy.full puts it into an array of the raster's dtype
+            value = float(np.full((), raster.nodata, raster.dtype))
+        out = DeviceRaster(out_dptr, np.float32 if to_float else raster.dtype, (raster.shape[0], height, width), out_stride,
+                           out_band_stride, nodata=float('nan') if to_float else raster.nodata)
+        _check(self._lib.hk_boundless_window_dev(self._h, C.c_void_p(raster.dptr), DTYPE_CODES[raster.dtype.name], raster.shape[0],
+                                                 raster.shape[1], raster.shape[2], raster.stride, raster.band_stride, row_off, col_off,
+                                                 height, width, mode, 0.0 if to_float else value, C.c_void_p(out_dptr), out.stride,
+                                                 out.band_stride, stream))
+        return out
+
+    def mem_info(self):
+        """ -> (free, total) bytes of the context's device as the runtime reports them (hk_dev_mem_info) """
+        free, total = C.c_uint64(), C.c_uint64()
+        _check(self._lib.hk_dev_mem_info(self._h, C.byref(free), C.byref(total)))
+        return int(free.value), int(total.value)
 
     def deflate_tiles_dev(self, planes_dptr: int, dtype: str, n_bands: int, height: int, width: int, stride: int, band_stride: int,
                           tile: int, out_dptr: int, out_capacity: int, offsets_dptr: int, sizes_dptr: int, stream: int = 0,

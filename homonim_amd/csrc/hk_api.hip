@@ -3036,6 +3036,73 @@ int hk_dataset_mask_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int3
     return HK_OK;
 }
 
+// The resident rasters of RasterFuse.process (hk_convert.hip): see include/homonim_hk.h
+static int check_planes(const char* what, const void* p, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                        int64_t band_stride) {
+    if (!p) return fail(HK_ERR_ARG, "%s is NULL", what);
+    if (n_bands < 1 || height < 1 || width < 1) return fail(HK_ERR_ARG, "%s: empty raster %d x %d x %d", what, n_bands, height, width);
+    if (stride < width) return fail(HK_ERR_ARG, "%s: stride %lld is smaller than the width %d", what, (long long)stride, width);
+    if (band_stride < 0) return fail(HK_ERR_ARG, "%s: band_stride is negative", what);
+    if (n_bands > 1 && band_stride < ((int64_t)height - 1) * stride + width)
+        return fail(HK_ERR_ARG, "%s: band stride smaller than a plane: the planes overlap", what);
+    if (reinterpret_cast<uintptr_t>(p) % (uintptr_t)hk::dtype_size(dtype)) return fail(HK_ERR_ARG, "%s: not aligned to the sample size", what);
+    return HK_OK;
+}
+static int check_sample_value(int32_t dtype, double value, bool nan_allowed) {
+    if (dtype == HK_DTYPE_F64) return (nan_allowed || value == value) ? HK_OK : fail(HK_ERR_ARG, "NaN is not a sample value here");
+    if (dtype == HK_DTYPE_F32) {
+        if (value != value) return nan_allowed ? HK_OK : fail(HK_ERR_ARG, "NaN is not a sample value here");
+        return (!std::isfinite(value) || std::fabs(value) < 0x1.ffffffp127) ? HK_OK : fail(HK_ERR_ARG, "value %.17g is not a float32", value);
+    }
+    return int_sample_holds(dtype, value) ? HK_OK : fail(HK_ERR_ARG, "value %.17g is not a value of the integer sample type", value);
+}
+
+int hk_fill_planes_dev(hk_ctx* ctx, void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                       int64_t band_stride, double value, int32_t stream) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    if (!hk::dtype_size(dtype)) return fail(HK_ERR_ARG, "bad dtype %d", dtype);
+    int rc = check_planes("planes_dev", planes_dev, dtype, n_bands, height, width, stride, band_stride);
+    if (rc || (rc = check_sample_value(dtype, value, true)) || (rc = check_stream(ctx, stream))) return rc;
+    DevEnter entered(ctx, stream);
+    HK_ENTER(ctx);
+    HK_HIP(hk::launch_fill_planes(dtype, {.out = planes_dev, .stride = stride, .band_stride = band_stride, .n_bands = n_bands,
+                                          .height = height, .width = width, .value = value}, ctx->slots[stream].stream));
+    return HK_OK;
+}
+
+int hk_boundless_window_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                            int64_t stride, int64_t band_stride, int32_t row_off, int32_t col_off, int32_t out_height,
+                            int32_t out_width, int32_t nodata_mode, double nodata, void* out_dev, int64_t out_stride,
+                            int64_t out_band_stride, int32_t stream) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    if (!hk::dtype_size(dtype)) return fail(HK_ERR_ARG, "bad dtype %d", dtype);
+    int rc = check_nodata_mode(nodata_mode);
+    if (rc) return rc;
+    const bool to_float = nodata_mode != HK_NODATA_VALUE;
+    if ((rc = check_planes("planes_dev", planes_dev, dtype, n_bands, height, width, stride, band_stride)) ||
+        (rc = check_planes("out_dev", out_dev, to_float ? HK_DTYPE_F32 : dtype, n_bands, out_height, out_width, out_stride, out_band_stride)) ||
+        (!to_float && (rc = check_sample_value(dtype, nodata, false))) || (rc = check_stream(ctx, stream)))
+        return rc;
+    DevEnter entered(ctx, stream);
+    HK_ENTER(ctx);
+    HK_HIP(hk::launch_boundless_window(dtype, {.in = planes_dev, .in_stride = stride, .in_band_stride = band_stride, .n_bands = n_bands,
+                                               .height = height, .width = width, .row_off = row_off, .col_off = col_off,
+                                               .out_height = out_height, .out_width = out_width, .to_float = to_float,
+                                               .fill = to_float ? 0. : nodata, .out = out_dev, .out_stride = out_stride,
+                                               .out_band_stride = out_band_stride}, ctx->slots[stream].stream));
+    return HK_OK;
+}
+
+int hk_dev_mem_info(hk_ctx* ctx, uint64_t* free_bytes, uint64_t* total_bytes) {
+    if (!ctx) return fail(HK_ERR_ARG, "ctx is NULL");
+    HK_ENTER(ctx);
+    size_t f = 0, t = 0;
+    HK_HIP(hipMemGetInfo(&f, &t));
+    if (free_bytes) *free_bytes = f;
+    if (total_bytes) *total_bytes = t;
+    return HK_OK;
+}
+
 // device bytes of one chunk of the host path (rows are independent: the chunking cannot change a bit)
 constexpr size_t DATASET_MASK_CHUNK_BYTES = 64u << 20;
 

@@ -158,4 +158,172 @@ hipError_t launch_cast_out_valid(int dtype, const CastPlane& r, hipStream_t stre
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Resident rasters of RasterFuse.process (device_config resident=True): the typed prefill of an output raster and the boundless
+// window of an input raster.  Both are element-wise and HBM-bound; a lane owns one 16-byte unit of a row -- VEC = 16 / sizeof(T)
+// samples, cut where the row's ADDRESSES are multiples of 16, not where its columns are -- so whole units move as one 16-byte
+// access whatever the row's offset and the ragged ends go sample by sample behind their bounds.  All index arithmetic is 64-bit;
+// nothing outside [row, row + width) of any plane is touched.
+
+// N consecutive samples to `p`: 16-byte stores where `p` and N allow them, else one by one
+template <typename U, int N>
+__device__ __forceinline__ void store_run(U* __restrict__ p, const U (&v)[N]) {
+    if constexpr ((N * sizeof(U)) % 16 == 0) {
+        if (((uintptr_t)p & 15u) == 0) {
+            union { uint4 q[N * sizeof(U) / 16]; U e[N]; } u;
+#pragma unroll
+            for (int i = 0; i < N; ++i) u.e[i] = v[i];
+#pragma unroll
+            for (int i = 0; i < (int)(N * sizeof(U) / 16); ++i) reinterpret_cast<uint4*>(p)[i] = u.q[i];
+            return;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) p[i] = v[i];
+}
+
+// samples of a row before its first 16-byte boundary, counted back from it: unit k of the row holds the columns
+// [k * VEC - lead, (k + 1) * VEC - lead)
+template <typename T>
+__device__ __forceinline__ long long row_lead(const T* row) {
+    constexpr int VEC = 16 / sizeof(T);
+    return (long long)(((uintptr_t)row / sizeof(T)) % VEC);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) fill_planes_kernel(FillPlanes<T> a) {
+    constexpr int VEC = 16 / sizeof(T);
+    const long long unit = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    T v[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) v[i] = a.value;
+    for (long long b = blockIdx.z; b < a.n_bands; b += gridDim.z) {
+        for (long long y = blockIdx.y; y < a.height; y += gridDim.y) {
+            T* __restrict__ const row = a.out + b * a.band_stride + y * a.stride;
+            const long long x0 = unit * VEC - row_lead(row);
+            if (x0 >= a.width) continue;
+            if (x0 >= 0 && x0 + VEC <= a.width) {
+                store_run<T, VEC>(row + x0, v);
+            } else {
+#pragma unroll
+                for (int i = 0; i < VEC; ++i)
+                    if (x0 + i >= 0 && x0 + i < a.width) row[x0 + i] = a.value;
+            }
+        }
+    }
+}
+
+// RasterFuse._read_boundless of every band in one launch.  `to_float`: the raster has no nodata value, or NaN -- the window is
+// float32 (out_f), the plain value conversion of every sample inside the raster and NaN outside; else it is of the raster's own
+// type (out_t) with `fill` outside.
+template <typename T>
+__global__ void __launch_bounds__(256) boundless_window_kernel(BoundlessWindow<T> a) {
+    constexpr int VEC = 16 / sizeof(T);
+    const long long unit = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool to_float = a.out_f != nullptr;
+    const float nan32 = __uint_as_float(0x7FC00000u);
+    for (long long b = blockIdx.z; b < a.n_bands; b += gridDim.z) {
+        for (long long y = blockIdx.y; y < a.out_height; y += gridDim.y) {
+            const long long ry = y + a.row_off;
+            const bool row_in = ry >= 0 && ry < a.height;
+            // the raster's row, or -- outside it -- row 0 for the cut of the units only: nothing of it is read
+            const T* __restrict__ const in_row = a.in + b * a.in_band_stride + (row_in ? ry : 0) * a.in_stride;
+            const long long lead = row_lead(in_row);
+            // the first unit that holds a column of the window (floor division: col_off may be negative)
+            const long long c = (long long)a.col_off + lead;
+            const long long k0 = c >= 0 ? c / VEC : -((-c + VEC - 1) / VEC);
+            const long long cx0 = (k0 + unit) * VEC - lead;   // raster column of this lane's first sample
+            const long long x0 = cx0 - a.col_off;             // ... and its column in the window
+            if (x0 >= a.out_width) continue;
+            T v[VEC];
+            if (row_in && cx0 >= 0 && cx0 + VEC <= a.width) {
+                union { uint4 q; T e[VEC]; } u;
+                u.q = *reinterpret_cast<const uint4*>(in_row + cx0);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) v[i] = u.e[i];
+            } else {
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) v[i] = (row_in && cx0 + i >= 0 && cx0 + i < a.width) ? in_row[cx0 + i] : a.fill;
+            }
+            const bool whole = x0 >= 0 && x0 + VEC <= a.out_width;
+            if (to_float) {
+                float f[VEC];
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) f[i] = (row_in && cx0 + i >= 0 && cx0 + i < a.width) ? (float)v[i] : nan32;
+                float* __restrict__ const out_row = a.out_f + b * a.out_band_stride + y * a.out_stride;
+                if (whole) {
+                    store_run<float, VEC>(out_row + x0, f);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i)
+                        if (x0 + i >= 0 && x0 + i < a.out_width) out_row[x0 + i] = f[i];
+                }
+            } else {
+                T* __restrict__ const out_row = a.out_t + b * a.out_band_stride + y * a.out_stride;
+                if (whole) {
+                    store_run<T, VEC>(out_row + x0, v);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i)
+                        if (x0 + i >= 0 && x0 + i < a.out_width) out_row[x0 + i] = v[i];
+                }
+            }
+        }
+    }
+}
+
+// units of 16 bytes that can hold a sample of a row of `width` samples of `es` bytes, wherever the row starts
+static dim3 unit_grid(long long width, int es, int height, int n_bands) {
+    const long long units = width / (16 / es) + 2;
+    return dim3((unsigned)((units + 255) / 256), height < 2048 ? height : 2048, n_bands < 64 ? n_bands : 64);
+}
+
+hipError_t launch_fill_planes(int dtype, const PlaneFill& r, hipStream_t stream) {
+    const dim3 g = unit_grid(r.width, dtype_size(dtype) ? dtype_size(dtype) : 1, r.height, r.n_bands), b(256);
+#define HK_FILL_PLANES(T) \
+    HK_LAUNCH(fill_planes_kernel<T>, g, b, 0, stream, FillPlanes<T>{static_cast<T*>(r.out), r.stride, r.band_stride, r.n_bands, r.height, r.width, (T)r.value})
+    switch (dtype) {
+        case 0: HK_FILL_PLANES(float); break;
+        case 1: HK_FILL_PLANES(unsigned char); break;
+        case 2: HK_FILL_PLANES(unsigned short); break;
+        case 3: HK_FILL_PLANES(short); break;
+        case 4: HK_FILL_PLANES(unsigned int); break;
+        case 5: HK_FILL_PLANES(int); break;
+        case 6: HK_FILL_PLANES(double); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef HK_FILL_PLANES
+    return hipGetLastError();
+}
+
+template <typename T>
+static BoundlessWindow<T> boundless_args(const WindowGather& r) {
+    BoundlessWindow<T> a;
+    a.in = static_cast<const T*>(r.in);
+    a.out_t = r.to_float ? nullptr : static_cast<T*>(r.out);
+    a.out_f = r.to_float ? static_cast<float*>(r.out) : nullptr;
+    a.in_stride = r.in_stride, a.in_band_stride = r.in_band_stride, a.out_stride = r.out_stride, a.out_band_stride = r.out_band_stride;
+    a.n_bands = r.n_bands, a.height = r.height, a.width = r.width;
+    a.row_off = r.row_off, a.col_off = r.col_off, a.out_height = r.out_height, a.out_width = r.out_width;
+    a.fill = r.to_float ? (T)0 : (T)r.fill;
+    return a;
+}
+
+hipError_t launch_boundless_window(int dtype, const WindowGather& r, hipStream_t stream) {
+    const dim3 g = unit_grid(r.out_width, dtype_size(dtype) ? dtype_size(dtype) : 1, r.out_height, r.n_bands), b(256);
+#define HK_BOUNDLESS(T) HK_LAUNCH(boundless_window_kernel<T>, g, b, 0, stream, boundless_args<T>(r))
+    switch (dtype) {
+        case 0: HK_BOUNDLESS(float); break;
+        case 1: HK_BOUNDLESS(unsigned char); break;
+        case 2: HK_BOUNDLESS(unsigned short); break;
+        case 3: HK_BOUNDLESS(short); break;
+        case 4: HK_BOUNDLESS(unsigned int); break;
+        case 5: HK_BOUNDLESS(int); break;
+        case 6: HK_BOUNDLESS(double); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef HK_BOUNDLESS
+    return hipGetLastError();
+}
+
 }  // namespace hk

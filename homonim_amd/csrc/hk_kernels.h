@@ -422,6 +422,47 @@ hipError_t launch_cast_out(int dtype, const CastPlane& r, hipStream_t stream);
 hipError_t launch_cast_out_valid(int dtype, const CastPlane& r, hipStream_t stream);
 inline int dtype_size(int dtype) { const int sz[7] = {4, 1, 2, 2, 4, 4, 8}; return dtype >= 0 && dtype < 7 ? sz[dtype] : 0; }
 
+// Resident rasters (hk_convert.hip).  The kernels' own argument structs carry typed pointers, so that the compiler knows their
+// address space; the launchers take the untyped forms below.  Strides in elements of each side's own type.
+template <typename T>
+struct FillPlanes {
+    T* __restrict__ out;
+    long long stride, band_stride;
+    int n_bands, height, width;
+    T value;
+};
+template <typename T>
+struct BoundlessWindow {
+    const T* __restrict__ in;   // pixel (0, 0) of band 0 of the raster
+    T* __restrict__ out_t;      // the window in the raster's own type (numeric nodata), or
+    float* __restrict__ out_f;  // the window as float32 (no nodata value, or NaN): exactly one of the two is set
+    long long in_stride, in_band_stride, out_stride, out_band_stride;
+    int n_bands, height, width;                      // the raster
+    int row_off, col_off, out_height, out_width;     // the window in raster coordinates: may hang over the raster or miss it
+    T fill;
+};
+// `value` in every one of `width` samples of `height` rows of `n_bands` planes of dtype; the row padding is not written
+struct PlaneFill {
+    void* out;
+    long long stride, band_stride;
+    int n_bands, height, width;
+    double value;
+};
+hipError_t launch_fill_planes(int dtype, const PlaneFill& r, hipStream_t stream);
+// RasterFuse._read_boundless of all bands: the window (row_off, col_off, out_height, out_width) of a raster of dtype.  to_float:
+// `out` is float32, the plain value conversion inside the raster and NaN outside; else `out` is of dtype with `fill` outside.
+struct WindowGather {
+    const void* in;
+    long long in_stride, in_band_stride;
+    int n_bands, height, width;
+    int row_off, col_off, out_height, out_width;
+    bool to_float;
+    double fill;
+    void* out;
+    long long out_stride, out_band_stride;
+};
+hipError_t launch_boundless_window(int dtype, const WindowGather& r, hipStream_t stream);
+
 // The per-dataset mask of a GeoTIFF applied to its bands (hk_dataset_mask.hip; homonim/raster_array.py:161-197): float32 planes
 // `out` = valid ? (float)planes : NaN (0x7FC00000), the same validity for every band.  kind 0 (BITS): `mask` are packed rows of
 // bits, most significant first, 1 = valid, mask_stride BYTES apart; kind 1 (ALPHA): a plane of the bands' sample type (uint8 /

@@ -277,6 +277,39 @@ def shard(items: Sequence, index: int, count: int, contiguous: bool = False) -> 
     return list(items[index::count])
 
 
+class BlockCall(NamedTuple):
+    """ Consecutive bands of one spatial block: one device-resident call (``group_block_calls``). """
+    band_i: int            # the first band
+    n_bands: int
+    src_in_block: Window
+    ref_in_block: Window
+    src_out_block: Window
+    ref_out_block: Window
+
+    @property
+    def bands(self) -> range:
+        return range(self.band_i, self.band_i + self.n_bands)
+
+
+def group_block_calls(blocks: Sequence[BlockPair]) -> List[BlockCall]:
+    """ The calls of the resident block loop for a (shard of a) block list: the pairs that share their four windows form a group,
+    in the order in which the list first names the windows, and every maximal run of consecutive band indices of a group is one
+    call.  A whole block list gives one call per spatial block for all bands; a shard gives the runs that it holds.  A pure
+    function of the list: every (band, block) pair of it is in exactly one call. """
+    groups: Dict[Tuple[Window, Window, Window, Window], List[int]] = {}
+    for bp in blocks:
+        groups.setdefault((bp.src_in_block, bp.ref_in_block, bp.src_out_block, bp.ref_out_block), []).append(bp.band_i)
+    calls = []
+    for windows, bands in groups.items():
+        bands = sorted(set(bands))
+        start = 0
+        for i in range(1, len(bands) + 1):
+            if i == len(bands) or bands[i] != bands[i - 1] + 1:
+                calls.append(BlockCall(bands[start], i - start, *windows))
+                start = i
+    return calls
+
+
 def _is_path(x) -> bool:
     return isinstance(x, (str, os.PathLike))
 
@@ -481,7 +514,7 @@ class RasterFuse:
     @staticmethod
     def create_device_config(devices: Optional[Sequence[int]] = None, streams: int = 4, rank: int = 0,
                              world_size: int = 1, contiguous: bool = False, pin: bool = True,
-                             separate_contexts: bool = False, deflate: str = 'host') -> Dict:
+                             separate_contexts: bool = False, deflate: str = 'host', resident: bool = False) -> Dict:
         """ (this package only) GPUs of this process, streams per GPU, this process's shard of the block list
         (round-robin, or ``contiguous`` runs), whether every entry of ``devices`` gets a context of its own even when a
         device is listed twice, and ``pin``: True (default) -- the rasters are registered in place for the duration of the
@@ -492,12 +525,19 @@ class RasterFuse:
         leases, profiles/r04_abort_followup.txt); False -- everything through the staging ring: the GPU never touches
         caller-allocated pages.  ``deflate``: who compresses the tiles of the GeoTIFFs ``process`` writes: 'host' (default) --
         zlib level 6 on the writing thread, byte for byte as before; 'device' -- ``Context.deflate_tiles``: the same pixels, tags
-        and overviews in files a few percent larger, written without the minutes of host zlib. """
+        and overviews in files a few percent larger, written without the minutes of host zlib.  ``resident``: where
+        the rasters of a source / reference pair on DIFFERENT grids live during ``process``: False (default) -- on the host, every
+        block pair staged up and down band by band, as ever; True -- on the device: source and reference go up once, every block
+        pair runs on the resident rasters all bands at a time (``fit_apply_dev`` of the model), overviews are built there and
+        the results come down once: the same bytes in arrays and files.  ``process`` then refuses, before anything
+        is allocated or launched, a pair on a shared grid, more than one device or ``separate_contexts``, an in-block taller than
+        65535 rows and rasters that do not fit the device's free memory; it never falls back to the host path.  Read by
+        ``RasterFuse.process`` only. """
         if deflate not in ('host', 'device'):
             raise ValueError(f"`deflate` must be 'host' or 'device', not {deflate!r}")
         return dict(devices=None if devices is None else list(devices), streams=int(streams), rank=int(rank),
                     world_size=int(world_size), contiguous=bool(contiguous), pin=bool(pin),
-                    separate_contexts=bool(separate_contexts), deflate=deflate)
+                    separate_contexts=bool(separate_contexts), deflate=deflate, resident=bool(resident))
 
     def block_pairs(self, overlap: Tuple[int, int] = (0, 0), max_block_mem: float = math.inf) -> Iterable[BlockPair]:
         if self._same_grid:
@@ -638,9 +678,15 @@ class RasterFuse:
         out_profile = RasterFuse.create_out_profile(**(out_profile or {}))
         device_config = RasterFuse.create_device_config(**(device_config or {}))
         want_params = param_filename is not None and param_filename is not False
+        if device_config['resident']:
+            self._check_resident(device_config)
         out_dtype, nodata, write_options = self._resolve_output(corr_filename, param_filename, want_params, overwrite, out_profile)
         models, own_contexts = self._build_models(model_type, kernel_shape, want_params, model_config, device_config)
         n_param = models[0].n_param
+        if device_config['resident']:
+            return self._process_resident(corr_filename, param_filename, want_params, build_ovw, models[0], model_type, kernel_shape,
+                                          model_config, block_config, device_config, out_dtype, nodata, write_options, corr_out,
+                                          return_valid)
         corr, params = self._allocate(out_dtype, nodata, corr_out, n_param if want_params else 0)
         write_mask = nodata is None and self._is_tiff(corr_filename)
         valid = np.zeros(self.shape, np.uint8) if (return_valid or write_mask) else None
@@ -654,6 +700,36 @@ class RasterFuse:
                     dict(model=model_type, kernel_shape=tuple(kernel_shape), **model_config), compressor, write_options,
                     valid if write_mask else None)
         return (corr, params, valid) if return_valid else (corr, params)
+
+    def _process_resident(self, corr_filename, param_filename, want_params: bool, build_ovw: bool, model: KernelModel, model_type: Model,
+                          kernel_shape, model_config: Dict, block_config: Dict, device_config: Dict, out_dtype: np.dtype, nodata,
+                          write_options: Optional[Dict], corr_out: Optional[np.ndarray], return_valid: bool):
+        """ ``process`` with ``resident=True``: the same block list and shard, the same files and return values; the rasters live on
+        the device from the first block to the last (homonim_amd/resident.py). """
+        from homonim_amd.resident import ResidentRun
+        n_param = model.n_param
+        write_mask = nodata is None and self._is_tiff(corr_filename)
+        blocks = list(self.block_pairs(overlap=utils.overlap_for_kernel(kernel_shape), max_block_mem=block_config['max_block_mem']))
+        blocks = shard(blocks, device_config['rank'], device_config['world_size'], device_config['contiguous'])
+        want_ovw = (build_ovw and self._is_tiff(corr_filename), build_ovw and want_params and self._is_tiff(param_filename))
+        corr, params, valid, overviews = ResidentRun(
+            self, model, group_block_calls(blocks), out_dtype, nodata, corr_out, n_param if want_params else 0,
+            return_valid or write_mask, block_config['threads'], device_config['streams'], device_config['pin'], want_ovw,
+            write_mask).run()
+        compressor = model.context.deflate_tiles if device_config['deflate'] == 'device' else None
+        self._write(corr_filename, param_filename if want_params else None, corr, params, nodata, n_param, overviews,
+                    dict(model=model_type, kernel_shape=tuple(kernel_shape), **model_config), compressor, write_options,
+                    valid if write_mask else None)
+        return (corr, params, valid) if return_valid else (corr, params)
+
+    def _check_resident(self, device_config: Dict):
+        """ What ``resident=True`` refuses from the pair and the device configuration alone, before any library call """
+        if self._same_grid:
+            raise ValueError('`resident=True` is for a source and a reference on different grids: on a shared grid the host path is '
+                             'already one fused kernel per block (and SrcSpaceModel with mask_partial has no device-resident form there)')
+        if len(default_devices(device_config['devices'])) != 1 or device_config['separate_contexts']:
+            raise ValueError('`resident=True` takes one device and one context: the resident rasters live on one device '
+                             f"(devices={device_config['devices']}, separate_contexts={device_config['separate_contexts']})")
 
     def _resolve_output(self, corr_filename, param_filename, want_params: bool, overwrite: bool, out_profile: Dict):
         """ -> (output dtype, output nodata, ``write_options`` or None) of a ``process`` call, which is refused here when a file exists

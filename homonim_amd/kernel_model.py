@@ -361,6 +361,17 @@ class RefSpaceModel(KernelModel):
                             for a, b in ((src, ref), (ref, src)))
         return self.context.refspace_fit_apply_dev(desc, down_map, up_map, int(down), int(up), self._mask_partial, job, io)
 
+    def dev_scratch_bytes(self, src, ref, corr, params=None, valid=None, window=None, param_window=None,
+                          out_nodata: Optional[float] = RasterArray.default_nodata) -> int:
+        """ The bytes of ``scratch`` that ``fit_apply_dev`` of the same arguments needs (hk_refspace_dev_scratch_bytes: host arithmetic,
+        no device; the pointers are looked at for NULL only), 0 for arguments the entry would refuse. """
+        desc, io, job = self._two_grid_dev_job(src, ref, corr, params, valid, window, param_window, out_nodata, 0, None)
+        down_map, up_map = (_dev_grid_mapping(a, b, 'fit_apply passes such host arrays on and the library refuses their mapping')
+                            for a, b in ((src, ref), (ref, src)))
+        return _hk.refspace_dev_scratch_bytes(desc, _hk.make_space_desc(down_map, up_map, int(self._get_resampling(src.res, ref.res)),
+                                                                        int(self._get_resampling(ref.res, src.res)), self._mask_partial),
+                                              job, io)
+
 
 class SrcSpaceModel(KernelModel):
     """ Parameters estimated on the source grid (kernel_model.py:506-535): the reference block is re-sampled to it. """
@@ -438,3 +449,11 @@ class SrcSpaceModel(KernelModel):
         desc, io, job = self._two_grid_dev_job(src, ref, corr, params, valid, window, param_window, out_nodata, stream, scratch)
         mapping = _dev_grid_mapping(ref, src, 'fit_apply flips the host array')
         return self.context.srcspace_fit_apply_dev(desc, mapping, int(self._get_resampling(ref.res, src.res)), self._mask_partial, job, io)
+
+    def dev_scratch_bytes(self, src, ref, corr, params=None, valid=None, window=None, param_window=None,
+                          out_nodata: Optional[float] = RasterArray.default_nodata) -> int:
+        """ ``RefSpaceModel.dev_scratch_bytes`` for this model (hk_srcspace_dev_scratch_bytes) """
+        desc, io, job = self._two_grid_dev_job(src, ref, corr, params, valid, window, param_window, out_nodata, 0, None)
+        mapping = _dev_grid_mapping(ref, src, 'fit_apply flips the host array')
+        return _hk.srcspace_dev_scratch_bytes(desc, _hk.make_srcspace_desc(mapping, int(self._get_resampling(ref.res, src.res)),
+                                                                           self._mask_partial), job, io)

@@ -83,7 +83,8 @@ typedef struct {
  * carry validity planes: hk_fit_apply_block_valid, hk_refspace_fit_apply_valid, hk_srcspace_fit_apply_valid, hk_overviews_valid and
  * hk_overviews_valid_dev (the structs they take are those of the entries they extend).  The device-resident two-grid entries
  * (hk_refspace_fit_apply_dev, hk_srcspace_fit_apply_dev, hk_refspace_dev_scratch_bytes, hk_srcspace_dev_scratch_bytes, with the new
- * struct hk_two_grid_job) were added the same way.
+ * struct hk_two_grid_job) were added the same way, and so were the entries of the resident rasters of RasterFuse.process
+ * (hk_fill_planes_dev, hk_boundless_window_dev, hk_dev_mem_info: plain scalar arguments, no struct).
  * hk_abi_version() returns the library's HK_ABI_VERSION; compare it with the header's at load time. */
 #define HK_ABI_VERSION 12
 int hk_abi_version(void);
@@ -720,6 +721,37 @@ int hk_overviews_valid_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, i
 int hk_dataset_mask_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
                         int64_t stride, int64_t band_stride, const void* mask_dev, int32_t mask_kind, int64_t mask_stride,
                         float* out_dev, int64_t out_stride, int64_t out_band_stride, int32_t stream);
+
+/* The typed prefill of a device-resident raster, as RasterFuse._allocate fills the host raster (numpy.full): `value` -- NaN allowed
+ * for HK_DTYPE_F32 / HK_DTYPE_F64, otherwise a value the sample type holds -- into `width` samples of each of `height` rows of
+ * `n_bands` planes of `dtype` (band b at planes_dev + b * band_stride elements, rows `stride` elements apart).  Nothing of the row
+ * padding (stride - width samples) and nothing between planes is written.  planes_dev is aligned to the sample size; all index
+ * arithmetic is 64-bit.  Whole 16-byte units of a row are one store, wherever the row starts.  Queued on pooled stream `stream`;
+ * asynchronous.  HK_ERR_ARG: a NULL pointer, an unknown dtype, a size below 1, stride < width, a negative band_stride, a plane
+ * that overlaps the next, a value the type does not hold. */
+int hk_fill_planes_dev(hk_ctx* ctx, void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width, int64_t stride,
+                       int64_t band_stride, double value, int32_t stream);
+
+/* A window of a device-resident raster that may reach beyond it, all bands in one launch: what the reference's boundless read
+ * gives (RasterArray.from_rio_dataset, homonim/raster_array.py:172-188).  `planes_dev`: n_bands x height x width samples of `dtype`
+ * on `stride` / `band_stride` (elements); the window is (row_off, col_off, out_height, out_width) in raster coordinates, offsets
+ * may be negative and the window may miss the raster altogether.  nodata_mode HK_NODATA_VALUE: out_dev holds samples of `dtype`,
+ * the raster's inside it and `nodata` (a value the type holds) outside; HK_NODATA_NONE / HK_NODATA_NAN: out_dev holds float32, the
+ * plain value conversion of the raster's samples inside (exact for 8/16-bit integers, round to nearest for 32-bit integers and
+ * float64; a float32 keeps its bits) and NaN (0x7FC00000) outside, `nodata` is not read.  Band b of the window goes to out_dev +
+ * b * out_band_stride, rows out_stride apart (elements of the output's type); nothing outside [row, row + out_width) of it is
+ * written and nothing outside the raster is read.  16-byte loads where a unit of a raster row lies inside the raster, sample by
+ * sample at the ragged ends; all index arithmetic is 64-bit.  Queued on pooled stream `stream`; asynchronous.  HK_ERR_ARG: a NULL
+ * pointer, an unknown dtype or nodata mode, a size below 1, a stride smaller than its width, a negative band stride, planes that
+ * overlap, a nodata the type does not hold, a pointer not aligned to its sample size. */
+int hk_boundless_window_dev(hk_ctx* ctx, const void* planes_dev, int32_t dtype, int32_t n_bands, int32_t height, int32_t width,
+                            int64_t stride, int64_t band_stride, int32_t row_off, int32_t col_off, int32_t out_height,
+                            int32_t out_width, int32_t nodata_mode, double nodata, void* out_dev, int64_t out_stride,
+                            int64_t out_band_stride, int32_t stream);
+
+/* Free and total bytes of the context's device as the runtime reports them (hipMemGetInfo): what a caller that is about to make
+ * whole rasters resident compares its needs with.  Either pointer may be NULL. */
+int hk_dev_mem_info(hk_ctx* ctx, uint64_t* free_bytes, uint64_t* total_bytes);
 
 /* hk_deflate_tiles for device-resident planes: streams, offsets and sizes stay on the device (out_dev of out_capacity >=
  * hk_deflate_bound's bytes; tile_offsets_dev: n_tiles + 1, tile_sizes_dev: n_tiles int64).  Queued on pooled stream `stream`;
